@@ -79,6 +79,11 @@ def parse(argv=None):
     ap.add_argument('--single-views', type=int, default=720,
                     help='views of the single_view_mode block (default: the whole spiral_step720 trajectory, as test_rnr.py renders it)')
     ap.add_argument('--no-dropin-loop', action='store_true', help='skip the dropin_view_loop block (INTEGRATION.md Level 1 timing)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): `frames`, '
+                         'every view of that step [views, 3, S, S] (all ranks\' views, as the frame gather hands them out, with '
+                         'N > 1).  At most 64 MB in all; a larger output is written as a fixed seeded sample of its elements '
+                         '(dump_outputs).  The same arguments give the same inputs, so two builds compare output for output')
     ap.add_argument('--stub-pipeline', action='store_true',
                     help='TEST HOOK (tests/test_bench_flow_cpu.py): run the control flow of this file — pose slicing, overlapped '
                          'frame gather, barrier + MAX-reduced timing, rank-0-only JSON, --check-gather — on CPU tensors with the '
@@ -359,6 +364,32 @@ def step_series_block(series, dt, K):
                        for i, x in enumerate(st) if x > 1.3 * med],
     })
     return {'step_series': out}
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: writes {name: array} as out_dir/<name>.npy (float64 kept, everything else as float32) and returns
+    {name: {'shape', 'dtype'[, 'sampled', 'sample_seed']}}.  If the arrays together exceed `limit` bytes, each one is
+    replaced by the same fraction of its elements, flattened, at sorted indices drawn without replacement by a generator
+    seeded with `seed`: the sample depends on the shape only, so files of two builds stay comparable element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {k: np.ascontiguousarray(v if v.dtype == np.float64 else v.astype(np.float32, copy=False))
+            for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    frac = (limit - 4096) / total if total > limit else 1.0        # 4 KiB left for the .npy headers
+    manifest = {}
+    for name, a in arrs.items():
+        entry = {'shape': list(a.shape), 'dtype': str(a.dtype)}
+        if frac < 1.0:
+            k = int(a.size * frac)
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, k, replace=False))
+            a = a.reshape(-1)[idx]
+            entry.update(sampled=k, sample_seed=seed)
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        manifest[name] = entry
+    return manifest
 
 
 def make_pipeline(sc, args, dev, V, **kw):
@@ -843,6 +874,14 @@ def main(argv=None):
         gather_check = {'ok': int(bad.sum().item()) == 0, 'ranks_with_mismatch': int(bad[0].item()),
                         'gathered_shape': list(gather.latest.shape), 'backend': dist.get_backend()}
     last_frame = img[V - 1:V].clone()       # the frame buffers are reused by the extra renders below
+    dumped = None
+    if args.dump_outputs:
+        # the last timed step of the last window (every window renders the same steps); with N > 1 the gathered frames of
+        # that step, which every rank receives
+        frames = (gather.latest if use_dist else img).detach().cpu().numpy()
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, {'frames': frames})
+        del frames
     # N > 1: BASELINE configs[3]'s own batch — 8 views per GPU (64 at 8 GPUs) — through the same pipeline, gather and timing
     # protocol, every rank taking part; reported beside the headline as with_8_views_per_gpu
     dt8 = None
@@ -950,6 +989,8 @@ def main(argv=None):
             res['cpu_baseline'] = None
         if gather_check is not None:
             res['gather_check'] = gather_check
+        if dumped is not None:
+            res['dumped_outputs'] = dumped
         if dt8 is not None:
             res['with_8_views_per_gpu'] = {
                 'frames_per_s': args.steps * world * V8 / dt8, 'ms_per_step': dt8 / args.steps * 1e3,

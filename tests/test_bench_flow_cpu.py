@@ -96,6 +96,60 @@ def test_plain_launch_with_gpus_1_is_one_process():
     assert 'with_8_views_per_gpu' not in res
 
 
+def _stub_frames(ids, S):
+    """What the stub pipeline renders for spiral views `ids` (its pose encoding, _StubPipeline.render)."""
+    import numpy as np
+    from rnr_amd import scene
+    v = scene.spiral_views(S, ids)
+    code = v['pose'][:, :3, 3] * 2.0 + v['proj'][:, 0, 0:1] * 1e-3
+    return np.broadcast_to(code[:, :, None, None], (len(ids), 3, S, S)).astype(np.float32)
+
+
+@pytest.mark.parametrize('gpus', [1, 2])
+def test_dump_outputs_is_the_last_timed_step(gpus, tmp_path):
+    """--dump-outputs DIR writes the frames of the LAST timed step (every rank's views with N > 1) as DIR/frames.npy in
+    float32, and two runs with the same arguments write the same file."""
+    import numpy as np
+    V, S, steps, warm = 2, 16, 3, 1
+    got = []
+    for run in range(2):
+        out = tmp_path / ('run%d' % run)
+        p = subprocess.run([sys.executable, 'bench.py', '--gpus', str(gpus), '--stub-pipeline', '--img-size', str(S), '--steps',
+                            str(steps), '--warmup', str(warm), '--views-per-step', str(V), '--dump-outputs', str(out)],
+                           cwd=ROOT, env=_plain_env(), capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-3000:]
+        res = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][0])
+        assert res['steps'] == steps and res['dumped_outputs'] == {'frames': {'shape': [gpus * V, 3, S, S], 'dtype': 'float32'}}
+        assert sorted(os.listdir(out)) == ['frames.npy']
+        got.append(np.load(out / 'frames.npy'))
+    assert got[0].dtype == np.float32 and got[0].shape == (gpus * V, 3, S, S)
+    assert np.array_equal(got[0], got[1])
+    last = warm + steps - 1
+    ids = (np.arange((steps + warm) * gpus * V) * 7) % 720
+    assert np.array_equal(got[0], _stub_frames(ids[last * gpus * V:(last + 1) * gpus * V], S))
+
+
+def test_dump_outputs_samples_what_exceeds_the_limit(tmp_path):
+    """Arrays above the byte limit are written as the same seeded sample of their elements on every call, within the limit."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    a = np.arange(300000, dtype=np.float32).reshape(3, 100000)
+    b = np.linspace(0.0, 1.0, 50000)                                     # float64 stays float64
+    limit = 400000
+    m1 = bench.dump_outputs(str(tmp_path / 'x'), {'a': a, 'b': b}, limit=limit)
+    m2 = bench.dump_outputs(str(tmp_path / 'y'), {'a': a, 'b': b}, limit=limit)
+    assert m1 == m2 and m1['a']['shape'] == [3, 100000] and m1['b']['dtype'] == 'float64'
+    files = {d: {n: np.load(tmp_path / d / (n + '.npy')) for n in 'ab'} for d in 'xy'}
+    assert sum(os.path.getsize(tmp_path / 'x' / (n + '.npy')) for n in 'ab') <= limit
+    for n, full in (('a', a), ('b', b)):
+        s = files['x'][n]
+        assert np.array_equal(s, files['y'][n]) and s.dtype == full.dtype and len(s) == m1[n]['sampled'] > 0
+        assert np.all(np.diff(s) > 0) and np.isin(s, full.reshape(-1)).all()      # distinct elements, in index order
+    small = bench.dump_outputs(str(tmp_path / 'z'), {'a': a}, limit=a.nbytes + 4096)
+    assert 'sampled' not in small['a'] and np.array_equal(np.load(tmp_path / 'z' / 'a.npy'), a)
+
+
 def test_launcher_world_size_must_equal_gpus():
     """A launcher that started another number of ranks than --gpus says is an error exit, never a bench line."""
     env = dict(_plain_env(), RANK='0', LOCAL_RANK='0', WORLD_SIZE='1', MASTER_ADDR='127.0.0.1', MASTER_PORT='29691')
