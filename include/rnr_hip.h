@@ -359,9 +359,9 @@ int rnr_conv2d_masked(const rnr_conv_desc* d, const rnr_conv_src* src0, const rn
  *     statistics shards inside `sync`; the last workgroup of a view to arrive turns them into
  *       scale[n,c] = gamma[c] / sqrt(var_biased + eps),  shift[n,c] = beta[c] - mean * scale[n,c]   (rnr_bn_finalize)
  *     and leaves the shards at zero.  Channels >= c_out of scale / shift get 0.
- *   split-K (small maps): the slices of a tile meet inside the launch (the last one to arrive adds the accumulator
- *     images in slice order) when there are at most 4 of them; deeper splits keep the reduce kernel, which then also
- *     finalises the BatchNorm.
+ *   split-K (small maps): the slices write partial-output slabs into `workspace` that the reduce kernel adds in slice
+ *     order; a BatchNorm finalise launch follows it.  Grids of one workgroup per CU or fewer also finalise in a launch of
+ *     their own.
  * `sync` (rnr_conv_sync_bytes(d, max_views, in_h, in_w) bytes, 256-byte aligned): arrival counters and statistics.  The
  * caller zero-fills it ONCE; every call expects zeros and leaves zeros, also for a different num_views <= max_views.  One
  * buffer per convolution in flight (calls on the same stream may share one).  After a failed launch: zero it again.
@@ -371,7 +371,7 @@ int rnr_conv2d_masked(const rnr_conv_desc* d, const rnr_conv_src* src0, const rn
  * of workgroups) bits of headroom for 512 workgroups per view); that is the case for activations of any trained network and is why 16 000 frame groups have
  * come out bit-identical run after run (scripts/t_fused_stress.py), but it is a property of the data, not of the code: with a wider
  * spread scale / shift — and everything downstream — may differ in the last bits between runs, exactly like rnr_conv2d +
- * rnr_bn_finalize.  The in-launch split-K combine itself is order-independent by construction.
+ * rnr_bn_finalize.
  */
 /* ZERO-INITIALISE this struct (`rnr_conv_bn bn = {0};` / memset) before filling it: it has grown (running_mean, running_var,
  * momentum were added in r05) and carries no size field — a caller compiled against the five-field form that leaves the tail

@@ -19,8 +19,10 @@
 // Kernels: conv_halo_kernel (LDS-halo tiles, exact fp32: every map whose width is a multiple of 32, or 16), conv_mfma_kernel (tap-by-tap gather:
 // the small maps), conv_halo_emu_kernel (opt-in: fp32 emulated on the 16-bit matrix cores, RNR_CONV_F32_EMU_BF16X6 / _F16X3), and — the
 // product path since r03, RNR_CONV_WINOGRAD — the fp32 Winograd kernels of conv_wino.inc (F(2x2, 3x3): conv_wino_kernel),
-// conv_wino80.inc (the 80-column out layer) and conv_wino2.inc (F(2x2, 2x2) for the two 4x4 stride-2 convolutions).
+// conv_wino80.inc (the 80-column out layer), conv_wino2.inc / conv_wino2p.inc (F(2x2, 2x2): conv_wino2_kernel<1> for the
+// stride-2 convolution, conv_wino2p_kernel<2> for the transposed one) and conv_wino4.inc (F(4x4, 3x3), RNR_CONV_WINOGRAD4).
 // make_plan() picks the kernel, the tile shape (256x64, 256x80, 128x128 or 256x128 rows x columns) and the split-K depth.
+// Split-K grids write one partial-output slab per slice; splitk_reduce_kernel adds them in slice order.
 #include "rnr_internal.h"
 
 #include <algorithm>
@@ -37,9 +39,6 @@ constexpr int CTHREADS = 256;
 #ifndef RNR_SPLITK_BELOW
 #define RNR_SPLITK_BELOW 257        // one workgroup per CU (a single wave per SIMD) is split two ways: 146 vs 156 ... 266 vs 304 us on the
 #define RNR_SPLITK_TARGET 512       // 256-tile layers at one view per call
-#endif
-#ifndef RNR_COMBINE_MAX_BYTES
-#define RNR_COMBINE_MAX_BYTES (256 * 1024)      // four 128 x 128 images, sixteen 64 x 64 ones
 #endif
 #ifndef RNR_SMALL_TILE_BELOW
 #define RNR_SMALL_TILE_BELOW 128     // fewer 128 x 128 tiles than this: 64 x 64 tiles (make_plan)
@@ -62,6 +61,12 @@ constexpr int CTHREADS = 256;
 #ifndef RNR_HALO_WAVES
 #define RNR_HALO_WAVES 3    // waves per SIMD the halo kernels are register-bounded for (4 would spill and exceed LDS anyway)
 #endif
+
+// an integer override from the environment (experiments), or `dflt`; callers cache it in a function-local static
+static int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 
 // waves per SIMD a halo-kernel configuration is register-bounded for: 128 x 64 tiles (32 accumulator registers) four, the
 // 64-accumulator tiles three (RNR_HALO_WAVES), 256 x 128 and the 80-column remainder configuration two
@@ -91,7 +96,7 @@ struct ConvParams {
     long slab_stride;   // floats between split-K slabs
     int mtiles, ntiles, zdim;   // logical grid; the launch is 1-D and remapped per XCD (see tile_coords)
     const uint8_t* tile_mask;   // optional [mtiles]: 0 = nobody reads this pixel tile's output, skip it (halo kernels)
-    // ---- rnr_conv2d_fused: producer-side BatchNorm and in-launch split-K combine (all zero on the legacy entry points) ----
+    // ---- rnr_conv2d_fused: producer-side BatchNorm (all zero on the legacy entry points) ----
     long stats_shard;           // doubles between the statistics shards (a workgroup adds into shard blockIdx % n_shards)
     int n_shards;               // 1 (legacy) or STAT_SHARDS
     unsigned* arrive;           // arrival counters of the statistics: [N] (arrive_per_view) or [1]; NULL = no in-kernel finalise
@@ -100,13 +105,11 @@ struct ConvParams {
     const float* gamma; const float* beta; float* scale; float* shift;
     float eps; double count;    // pixels per view behind one statistic
     float* running_mean; float* running_var; float momentum;     // torch's train-mode side effect, one-view calls only (rnr_conv_bn)
-    unsigned* tile_arrive;      // [par * mtiles * ntiles] split-K slices of a tile that have published their slab; NULL = legacy slabs + reduce kernel
     // ---- rnr_conv2d_ray: the U-Net-dependent half of the ray renderer in the out layer's epilogue (80-column configuration) ----
     const float* ray_w;         // [N*OH*OW][c_out_pad] ray weights (rnr_ray_weights); NULL = ordinary epilogue
     const float* ray_bias;      // [c_out_pad] out-layer bias
     float* ray_image;           // [N,3,OH,OW]
     int par_inner;              // tile order of the transposed conv: parity class inside the pixel tile (see tile_coords)
-    float* slabs;               // in-launch combine: [splitk][tile][wave][i][j][4 quads][64 lanes][4] accumulator images
 };
 constexpr int STAT_SHARDS = 8;  // one per XCD: at one view per call every workgroup of a layer hits the same 2 * c_out words
 
@@ -147,34 +150,33 @@ __device__ __forceinline__ float apply_act(float v, int act) {
 
 
 // ------------------------------------------------------------------------------------------------
-// Producer-side BatchNorm and in-launch split-K combine (rnr_conv2d_fused).
+// Producer-side BatchNorm (rnr_conv2d_fused).
 //
 // One view per call (the reference's mode, test_rnr.py:265) makes a convolution a 40 - 350 us kernel; the 17
-// bn_finalize launches and 9 split-K reduce launches behind them cost 6 % of the U-Net there.  Both are folded
-// into the convolution's epilogue with arrival counters:
-//   * batch statistics are added into one of STAT_SHARDS copies (workgroup b -> shard b % 8, i.e. its XCD), the
-//     workgroup waits for the acknowledgement of its atomics, and draws a ticket; the workgroup that draws the
-//     last ticket of a view sums the shards, writes scale / shift and leaves statistics and counter at zero.
-//     Statistics and counters are touched by agent-scope atomics only (add / load / store meet at the memory
-//     side, MI355X_MICROARCH.md "8-B agent atomics both sides"), so no fence is involved; scale / shift are plain
-//     stores read by the next kernel of the stream;
-//   * a split-K slice stores its accumulators as a write-through (sc1) register image — 16 B per lane, the order
-//     the registers have —, drains, and draws a ticket of its tile; the last slice adds all images IN SLICE ORDER
-//     (its own included: the sum does not depend on who arrives last) with sc1 loads and runs the normal epilogue.
+// bn_finalize launches and 9 split-K reduce launches behind them cost 6 % of the U-Net there.  Grids that do not split
+// K fold the finalise into the convolution's epilogue with arrival counters: batch statistics are added into one of STAT_SHARDS copies
+// (workgroup b -> shard b % 8, i.e. its XCD), the workgroup waits for the acknowledgement of its atomics, and draws a
+// ticket; the workgroup that draws the last ticket of a view sums the shards, writes scale / shift and leaves statistics
+// and counter at zero.  Statistics and counters are touched by agent-scope atomics only (add / load / store meet at the
+// memory side, MI355X_MICROARCH.md "8-B agent atomics both sides"), so no fence is involved; scale / shift are plain
+// stores read by the next kernel of the stream.  Split-K grids write slabs that splitk_reduce_kernel adds.
+// (Until r06 the split-K slices of the direct kernels could also meet inside the launch through sc1 accumulator images
+// and a ticket per tile; slabs + the reduce kernel measured faster at one and two views per call and equal from three on,
+// and the in-launch combine was removed.)
 // Counters and statistics are zero before and after every call; the host zeroes them once.
 // ------------------------------------------------------------------------------------------------
 // REQUIRED ASSUMPTIONS of the fence-free hand-off (checked below at compile time as far as they can be; tested by
 // tests/test_gpu_unet.py::test_conv_fused_equals_separate_launches and scripts/t_fused_stress.py on the hardware):
 //   (1) gfx950 acknowledges a write-through (sc1) buffer store and a no-return agent-scope atomic — i.e. decrements vmcnt —
 //       only once it has reached the coherence point (the memory-side L2 / MALL path all XCDs share), so "s_waitcnt
-//       vmcnt(0); s_barrier; ticket" orders every lane's publication before the ticket without a release fence;
+//       vmcnt(0); s_barrier; ticket" orders every lane's statistics before the ticket without a release fence;
 //   (2) bit 4 (value 16) of the aux operand of the raw-buffer intrinsics is sc1 on this target: loads bypass the
 //       non-coherent caches, stores write through, which stands in for the acquire side;
 //   (3) the compiler keeps the buffer intrinsics on their side of the `asm volatile(... "memory")` + __syncthreads pair.
 // None of this is portable to another target or to a partition mode in which the XCDs do not share a coherence point; the
 // file therefore refuses to compile device code for anything but gfx950.
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "conv.hip: the producer-side BatchNorm / split-K hand-off relies on gfx950 memory semantics (see above); gfx950 only"
+#error "conv.hip: the producer-side BatchNorm hand-off relies on gfx950 memory semantics (see above); gfx950 only"
 #endif
 #define RNR_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 typedef unsigned int uintx4_t __attribute__((__vector_size__(4 * sizeof(unsigned int))));
@@ -235,7 +237,7 @@ __device__ __forceinline__ void bn_finalize_views(const ConvParams& P, int n_fir
     }
 }
 
-// Every thread has issued what it publishes (statistics atomics, slab stores).  Returns the ticket in thread 0.
+// Every thread has issued what it publishes (statistics atomics).  Returns the ticket in thread 0.
 __device__ __forceinline__ unsigned publish_and_draw(unsigned* counter, int tid) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // acknowledged by the memory side
     __syncthreads();
@@ -268,57 +270,6 @@ __device__ __forceinline__ void bn_complete(const ConvParams& P, const BnArrival
         if (P.arrive_per_view && n >= 0) bn_finalize_views(P, n, 1, tid);
         else bn_finalize_views(P, 0, P.N, tid);
     }
-}
-
-// accumulator images of a wave: [i][j][quad q][lane][4 floats]
-template <int WM, int WN>
-__device__ __forceinline__ void slab_store(float* base, const floatx16 (&acc)[WM][WN], int lane) {
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x27000);
-#pragma unroll
-    for (int i = 0; i < WM; i++)
-#pragma unroll
-        for (int j = 0; j < WN; j++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const floatx4 v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uintx4_t, v), rsrc, lane * 16,
-                                                       ((i * WN + j) * 4 + q) * 1024, AUX_SC1);
-            }
-}
-template <int WM, int WN>
-__device__ __forceinline__ void slab_add(const float* base, floatx16 (&acc)[WM][WN], int lane) {
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, 0x7fffffff, 0x27000);
-#pragma unroll
-    for (int i = 0; i < WM; i++)
-#pragma unroll
-        for (int j = 0; j < WN; j++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const floatx4 v = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                                  rsrc, lane * 16, ((i * WN + j) * 4 + q) * 1024, AUX_SC1));
-                acc[i][j][4 * q] += v[0]; acc[i][j][4 * q + 1] += v[1]; acc[i][j][4 * q + 2] += v[2]; acc[i][j][4 * q + 3] += v[3];
-            }
-}
-// The split-K slices of a tile meet here.  Returns false in the slices that are done (their slab is published), true
-// in the last one, whose accumulators then hold the sum over all slices.
-template <int WM, int WN>
-__device__ __forceinline__ bool splitk_combine(const ConvParams& P, floatx16 (&acc)[WM][WN], int tile, int split, int wave,
-                                               int lane, int tid, int* flag) {
-    constexpr size_t WAVE_FLOATS = (size_t)WM * WN * 1024, TILE_FLOATS = 4 * WAVE_FLOATS;
-    const size_t ntiles_all = (size_t)P.mtiles * P.ntiles * (P.zdim / P.splitk);
-    float* mine = P.slabs + ((size_t)split * ntiles_all + tile) * TILE_FLOATS + wave * WAVE_FLOATS;
-    slab_store<WM, WN>(mine, acc, lane);
-    const unsigned t = publish_and_draw(P.tile_arrive + tile, tid);
-    if (!drew_last(P.tile_arrive + tile, t, (unsigned)P.splitk, tid, flag)) return false;
-#pragma unroll
-    for (int i = 0; i < WM; i++)
-#pragma unroll
-        for (int j = 0; j < WN; j++)
-#pragma unroll
-            for (int g = 0; g < 16; g++) acc[i][j][g] = 0.0f;
-    for (int s = 0; s < P.splitk; s++)
-        slab_add<WM, WN>(P.slabs + ((size_t)s * ntiles_all + tile) * TILE_FLOATS + wave * WAVE_FLOATS, acc, lane);
-    return true;
 }
 
 template <int KIND, int WAVES_M, int WAVES_N, int WM, int WN>
@@ -965,11 +916,6 @@ conv_halo_kernel(const ConvParams P) {
 
     // ---- epilogue ----
     int* flag = reinterpret_cast<int*>(As + WAVES_M * BN * 2);      // behind the statistics scratch; LDS is free after the last barrier
-    // in-launch split-K combine (128 x 128 tiles and smaller: the plans that split K): only the last slice of a tile goes
-    // on, holding the sum
-    if (!R16 && WM * WN <= 4 && P.tile_arrive) {
-        if (!splitk_combine<WM, WN>(P, acc, (par * P.mtiles + mt_) * P.ntiles + nt_, split, wave, lane, tid, flag)) return;
-    }
     float* out = P.out + (size_t)split * P.slab_stride;
     if (R16) {   // C layout of the 16x16 tiles: col = lane & 15, row = (lane >> 4) * 4 + reg
         const int col = n0 + wn0 + WN * 32 + l15;
@@ -986,7 +932,7 @@ conv_halo_kernel(const ConvParams P) {
             }
         }
     }
-    const bool with_stats = P.stats && (P.splitk == 1 || P.tile_arrive);
+    const bool with_stats = P.stats && P.splitk == 1;
     if (with_stats) {
         float* red = As;   // [WAVES_M][BN][2]; LDS is free after the last barrier
 #pragma unroll
@@ -1377,11 +1323,8 @@ conv_halo_emu_kernel(const ConvParams P) {
     // them in place made the compiler keep both copies and spill)
     const float winv = FMT == 1 ? *reinterpret_cast<const float*>(P.weight_emu) : 1.0f;
     int* flag = reinterpret_cast<int*>(As) + WAVES_M * BN * 2;      // behind the statistics scratch
-    if (WM * WN <= 4 && P.tile_arrive) {    // in-launch split-K combine (images hold the unscaled accumulators)
-        if (!splitk_combine<WM, WN>(P, acc, (par * P.mtiles + mt_) * P.ntiles + nt_, split, wave, lane, tid, flag)) return;
-    }
     float* out = P.out + (size_t)split * P.slab_stride;
-    const bool with_stats = P.stats && (P.splitk == 1 || P.tile_arrive);
+    const bool with_stats = P.stats && P.splitk == 1;
     if (with_stats) {
         float* red = reinterpret_cast<float*>(As);   // [WAVES_M][BN][2]; LDS is free after the last barrier
 #pragma unroll
@@ -1452,7 +1395,7 @@ static void launch_halo_emu_cfg(const dim3 grid, const ConvParams& P, hipStream_
 // eff = 0.55 / 0.86 / 0.90 for r = 1 / 2 / 3; pick the slot count (<= what registers and LDS allow) with the smallest
 // total.  Large grids (>= 4 rounds) keep the maximum.  RNR_HALO_SLOTS=k forces k (experiments).
 static int balanced_slots(long tiles, int max_slots) {
-    static const int forced = [] { const char* e = getenv("RNR_HALO_SLOTS"); return e ? atoi(e) : 0; }();
+    static const int forced = env_int("RNR_HALO_SLOTS", 0);
     if (forced > 0) return forced < max_slots ? forced : max_slots;
     const long n = (tiles + 255) / 256;            // tiles per CU (256 CUs)
     if (n >= 4L * max_slots || max_slots <= 1) return max_slots;
@@ -1727,13 +1670,6 @@ pack_weight_emu_kernel(rnr_conv_desc d, const float* __restrict__ w, char* __res
 #include "conv_wino.inc"
 #include "conv_wino80.inc"
 #include "conv_wino2.inc"
-#ifndef W2_PAIRS
-#define W2_PAIRS 2            // bit 1: conv_wino2p_kernel (K-step pairs, r05) runs the TRANSPOSED 4x4 stride-2 layers (-4.3 ... -4.7 %), bit 0:
-                              // ... the stride-2 convolutions too (measured + 8 ... + 23 %: the kernel needs scratch there and its 12-MFMA weight
-                              // look-ahead stalls behind the two HBM halo loads of every phase block; profiles/r05_wino2_pairs_ab.txt); the
-                              // others run conv_wino2_kernel (r03 / r04)
-#endif
-#define W2_PAIRS_KIND(kind) ((kind) == RNR_CONVT4x4S2 ? ((W2_PAIRS) & 2) != 0 : ((W2_PAIRS) & 1) != 0)
 #include "conv_wino2p.inc"
 #include "conv_wino4.inc"
 
@@ -1787,14 +1723,15 @@ __global__ void __launch_bounds__(256) zero_f64_kernel(double* __restrict__ p, l
 #endif
 
 // split depth of a Winograd grid of `wgs` workgroups (0: too small even when split — the direct kernels).  Below `min_wgs`
-// the K loop is cut into slices whose partial outputs splitk_reduce_kernel adds: at least 4 chunks per slice, at most 8
-// slices, and the split grid must reach half of `min_wgs`.  RNR_WINO_SPLITK=0 in the environment disables the split.
-static int wino_splitk(long wgs, int min_wgs, int chunks) {
+// the K loop is cut into slices whose partial outputs splitk_reduce_kernel adds: at least `min_chunks` chunks per slice, at
+// most 8 slices, and the split grid must reach `reach` workgroups.  RNR_WINO_SPLITK=0 in the environment disables the split.
+static int wino_splitk(long wgs, int min_wgs, int chunks, int min_chunks = RNR_WINO_SPLIT_MIN_CHUNKS,
+                       int reach = RNR_WINO_SPLIT_MIN_WGS) {
     if (wgs >= min_wgs) return 1;
-    static const int enabled = [] { const char* e = getenv("RNR_WINO_SPLITK"); return e ? atoi(e) : 1; }();
+    static const int enabled = env_int("RNR_WINO_SPLITK", 1);
     if (!enabled || wgs <= 0) return 0;
     int sk = (int)((min_wgs + wgs - 1) / wgs);
-    const int max_sk = chunks / RNR_WINO_SPLIT_MIN_CHUNKS < 8 ? chunks / RNR_WINO_SPLIT_MIN_CHUNKS : 8;
+    const int max_sk = chunks / min_chunks < 8 ? chunks / min_chunks : 8;
     if (sk > max_sk) sk = max_sk;
     if (sk >= 2) {
         // no empty trailing slice: the kernels give every slice ceil(chunks / sk) chunks, so e.g. 29 chunks cut 7 ways (5 per
@@ -1803,7 +1740,7 @@ static int wino_splitk(long wgs, int min_wgs, int chunks) {
         const int per = (chunks + sk - 1) / sk;
         sk = (chunks + per - 1) / per;
     }
-    if (sk < 2 || wgs * sk < RNR_WINO_SPLIT_MIN_WGS) return 0;
+    if (sk < 2 || wgs * sk < reach) return 0;
     return sk;
 }
 
@@ -1860,7 +1797,7 @@ static int make_plan(const rnr_conv_desc* d, int N, int H, int W, ConvPlan* p) {
     }
     // exact-fp32 kernels, small maps (the 32^2 / 16^2 layers at one view per call): when 128 x 128 tiles would have to split
     // K more than four ways to fill the chip, 64 x 64 tiles (32 x 2 or 16 x 4 pixels, one MFMA block per wave) give four
-    // times as many tiles: a shallow split whose slices meet inside the launch instead of 16 - 32 slabs and a reduce kernel
+    // times as many tiles: a shallow split instead of 16 - 32 slabs for the reduce kernel
     if (p->halo && !(d->flags & RNR_CONV_F32_EMU_ANY) && p->cfg == 2 && p->bm == 128) {
         const long t128 = (long)N * (p->Ho / th) * (p->Wo / p->tw) * p->ntiles * p->par;
         const int th64 = p->tw == 32 ? 2 : 4;
@@ -1875,7 +1812,7 @@ static int make_plan(const rnr_conv_desc* d, int N, int H, int W, ConvPlan* p) {
     }
     // ... and mid-size maps (one view per call: 256 - 512 tiles of 128 x 128, i.e. one or two workgroups = waves per SIMD):
     // 128 x 64 tiles (32 x 4 pixels, 64 columns; 32 accumulator registers, four waves per SIMD) double the tile count
-    static const int cfg4_max = [] { const char* e = getenv("RNR_CFG4_MAX"); return e ? atoi(e) : RNR_CFG4_MAX; }();
+    static const int cfg4_max = env_int("RNR_CFG4_MAX", RNR_CFG4_MAX);
     // (3x3 only: measured at one view per call 154 -> 149 us at 128^2 and 159 -> 154 at 64^2, but the stride-2 and transposed
     // convolutions — four taps per barrier — lose 3 - 18 us with half the MFMAs per tap)
     if (p->halo && d->kind == RNR_CONV3x3_REFLECT && !(d->flags & RNR_CONV_F32_EMU_ANY) && p->cfg == 2 && p->bm == 128 && p->tw == 32) {
@@ -1887,7 +1824,7 @@ static int make_plan(const rnr_conv_desc* d, int N, int H, int W, ConvPlan* p) {
     }
     // ... and the 64-column 3x3 layers (256 x 64 tiles, three waves per SIMD) when one 512^2 view is all there is: 152 -> 148 us
     // per layer on 128 x 64 tiles; no gain from two views on (RNR_CFG0_SMALL_MAX in the environment overrides)
-    static const int cfg0_small = [] { const char* e = getenv("RNR_CFG0_SMALL_MAX"); return e ? atoi(e) : RNR_CFG0_SMALL_MAX; }();
+    static const int cfg0_small = env_int("RNR_CFG0_SMALL_MAX", RNR_CFG0_SMALL_MAX);
     // (the 64-column transposed conv too: 271 -> 268 us)
     if (p->halo && d->kind != RNR_CONV4x4S2_REFLECT && !(d->flags & RNR_CONV_F32_EMU_ANY) && p->cfg == 0 && p->tw == 32 && p->Ho % 4 == 0) {
         const long t256 = (long)N * (p->Ho / th) * (p->Wo / p->tw) * p->ntiles * p->par;
@@ -1906,8 +1843,8 @@ static int make_plan(const rnr_conv_desc* d, int N, int H, int W, ConvPlan* p) {
     const long tiles = (long)p->mtiles * p->ntiles * p->par;
     int sk = 1;
     // (experiments: RNR_SPLITK_BELOW / RNR_SPLITK_TARGET in the environment override the compiled-in thresholds)
-    static const int sk_below = [] { const char* e = getenv("RNR_SPLITK_BELOW"); return e ? atoi(e) : RNR_SPLITK_BELOW; }();
-    static const int sk_target = [] { const char* e = getenv("RNR_SPLITK_TARGET"); return e ? atoi(e) : RNR_SPLITK_TARGET; }();
+    static const int sk_below = env_int("RNR_SPLITK_BELOW", RNR_SPLITK_BELOW);
+    static const int sk_target = env_int("RNR_SPLITK_TARGET", RNR_SPLITK_TARGET);
     if (tiles < sk_below) {      // fewer workgroups than ~2-3 per CU: split K so the 256 CUs stay filled
         sk = (int)((sk_target + tiles - 1) / tiles);
         // split granularity: K-chunks x taps for the gather kernel, K-chunks (all nine taps) for the halo kernel
@@ -1920,7 +1857,7 @@ static int make_plan(const rnr_conv_desc* d, int N, int H, int W, ConvPlan* p) {
     p->splitk = sk;
     // Winograd F(2x2, 3x3): every 3x3 layer whose map tiles into 16 x 8 pixels and whose columns into 64s, when there are
     // enough tiles to give every CU two (RNR_WINO_MIN_WGS in the environment overrides)
-    static const int min_wgs = [] { const char* e = getenv("RNR_WINO_MIN_WGS"); return e ? atoi(e) : RNR_WINO_MIN_WGS; }();
+    static const int min_wgs = env_int("RNR_WINO_MIN_WGS", RNR_WINO_MIN_WGS);
     if ((d->flags & RNR_CONV_WINOGRAD) && d->kind == RNR_CONV3x3_REFLECT && H % WINO_PH == 0 && W % WINO_PW == 0 &&
         d->c_out_pad % WINO_BN == 0 && view_elems < (1L << 30)) {
         const long wgs = (long)N * (H / WINO_PH) * (W / WINO_PW) * (d->c_out_pad / WINO_BN);
@@ -1934,26 +1871,15 @@ static int make_plan(const rnr_conv_desc* d, int N, int H, int W, ConvPlan* p) {
     }
     // F(4x4, 3x3) (opt-in, RNR_CONV_WINOGRAD4): 32 x 16 pixel tiles x 64 columns, one 12-wave workgroup per CU — when the grid
     // gives every CU a workgroup (no split-K form)
-    static const int min_wgs4 = [] { const char* e = getenv("RNR_WINO4_MIN_WGS"); return e ? atoi(e) : RNR_WINO4_MIN_WGS; }();
+    static const int min_wgs4 = env_int("RNR_WINO4_MIN_WGS", RNR_WINO4_MIN_WGS);
     if ((d->flags & RNR_CONV_WINOGRAD) && (d->flags & RNR_CONV_WINOGRAD4) && d->kind == RNR_CONV3x3_REFLECT && H % W4_PH == 0 &&
         W % W4_PW == 0 && d->c_out_pad % W4_BN == 0 && view_elems < (1L << 30) &&
-        (!W4_BN_LDS || d->c_in0_pad + d->c_in1_pad <= W4_BN_MAXC)) {      // the kernel's LDS table of BatchNorm scale / shift holds that many channels
+        d->c_in0_pad + d->c_in1_pad <= W4_BN_MAXC) {      // the kernel's LDS table of BatchNorm scale / shift holds that many channels
         const long wgs = (long)N * (H / W4_PH) * (W / W4_PW) * (d->c_out_pad / W4_BN);
         // small grids are cut over K like the F(2x2, .) ones — slices of >= RNR_WINO4_SPLIT_MIN_CHUNKS chunks, at most 8, and the
         // split grid must give every CU its workgroup again (this kernel runs one workgroup per CU)
-        int sk = wgs >= min_wgs4 ? 1 : 0;
-        if (!sk && wgs > 0) {
-            static const int enabled = [] { const char* e = getenv("RNR_WINO_SPLITK"); return e ? atoi(e) : 1; }();
-            int want = (int)((min_wgs4 + wgs - 1) / wgs);
-            const int max_sk = p->chunks_per_tap / RNR_WINO4_SPLIT_MIN_CHUNKS < 8 ? p->chunks_per_tap / RNR_WINO4_SPLIT_MIN_CHUNKS : 8;
-            if (want > max_sk) want = max_sk;
-            if (want >= 2) {
-                const int per = (p->chunks_per_tap + want - 1) / want;
-                want = (p->chunks_per_tap + per - 1) / per;         // no empty trailing slice
-            }
-            if (enabled && want >= 2 && wgs * want >= min_wgs4) sk = want;
-        }
-        if (sk) {
+        const int sk = wino_splitk(wgs, min_wgs4, p->chunks_per_tap, RNR_WINO4_SPLIT_MIN_CHUNKS, min_wgs4);
+        if (sk > 0) {
             p->wino = 4; p->halo = 1; p->cfg = 0; p->tw = W4_PW; p->bm = W4_PW * W4_PH; p->bn = W4_BN;
             p->mtiles = N * (H / W4_PH) * (W / W4_PW);
             p->ntiles = d->c_out_pad / W4_BN;
@@ -1978,7 +1904,7 @@ static int make_plan(const rnr_conv_desc* d, int N, int H, int W, ConvPlan* p) {
         view_elems < (1L << 30)) {
         const int bnw = d->kind == RNR_CONVT4x4S2 ? 64 : 128, tph = d->kind == RNR_CONVT4x4S2 ? WINO_PH : 16;
         const long wgs = (long)N * (p->Ho / tph) * (p->Wo / WINO_PW) * (d->c_out_pad / bnw);
-        static const int min_wgs2 = [] { const char* e = getenv("RNR_WINO2_MIN_WGS"); return e ? atoi(e) : RNR_WINO2_MIN_WGS; }();
+        static const int min_wgs2 = env_int("RNR_WINO2_MIN_WGS", RNR_WINO2_MIN_WGS);
         const int sk = wino_splitk(wgs, min_wgs2, p->chunks_per_tap);
         if (sk > 0) {
             p->wino = 2; p->halo = 1; p->cfg = 0; p->tw = WINO_PW; p->bm = WINO_PW * tph; p->bn = bnw;
@@ -2055,15 +1981,11 @@ static size_t wino_weight_floats(const rnr_conv_desc* d) {       // 0: this conv
     if (d->kind == RNR_CONV3x3_REFLECT && d->c_out_pad == 80) return (npairs / 2 + W80_BDIST) * W80_STEP_FLOATS;
     if (d->kind == RNR_CONV3x3_REFLECT)
         return d->c_out_pad % WINO_BN ? 0 : (size_t)(d->c_out_pad / WINO_BN) * (npairs + WINO_BDIST) * WINO_STEP_FLOATS;
-    // pair layout (conv_wino2p.inc): npairs K steps = npairs / 2 pair-steps per phase, + the look-ahead padding
-    if (d->kind == RNR_CONVT4x4S2) {
-        if (d->c_out_pad % 64) return 0;
-        return W2_PAIRS_KIND(RNR_CONVT4x4S2) ? (size_t)(d->c_out_pad / 64) * (npairs / 2 + W2P_PAD_PAIRS) * w2p_pair_floats<2>()
-                                             : (size_t)(d->c_out_pad / 64) * (npairs + W2_BDIST) * w2_step_floats<2>();
-    }
-    if (d->c_out_pad % 128) return 0;
-    return W2_PAIRS_KIND(RNR_CONV4x4S2_REFLECT) ? (size_t)(d->c_out_pad / 128) * (4 * (npairs / 2) + W2P_PAD_PAIRS) * w2p_pair_floats<1>()
-                                                : (size_t)(d->c_out_pad / 128) * (4 * npairs + W2_BDIST) * w2_step_floats<1>();     // four phases
+    // transposed: pair layout (conv_wino2p.inc), npairs K steps = npairs / 2 pair-steps, + the look-ahead padding
+    if (d->kind == RNR_CONVT4x4S2)
+        return d->c_out_pad % 64 ? 0 : (size_t)(d->c_out_pad / 64) * (npairs / 2 + W2P_PAD_PAIRS) * W2P_PAIR_FLOATS;
+    // stride 2: K steps of the four phases (conv_wino2.inc), + the look-ahead padding
+    return d->c_out_pad % 128 ? 0 : (size_t)(d->c_out_pad / 128) * (4 * npairs + W2_BDIST) * W2_STEP_FLOATS;
 }
 static size_t wino4_weight_floats(const rnr_conv_desc* d) {      // 0: this convolution has no F(4x4, 3x3) image
     if (!(d->flags & RNR_CONV_WINOGRAD) || !(d->flags & RNR_CONV_WINOGRAD4) || d->kind != RNR_CONV3x3_REFLECT ||
@@ -2119,7 +2041,7 @@ extern "C" int rnr_pack_conv_weight(const rnr_conv_desc* d, const float* weight,
             hipLaunchKernelGGL(pack_weight_wino_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, as_stream(stream), *d,
                                weight, packed + total, nw);
         else
-            hipLaunchKernelGGL(W2_PAIRS_KIND(d->kind) ? pack_weight_wino2p_kernel : pack_weight_wino2_kernel,
+            hipLaunchKernelGGL(d->kind == RNR_CONVT4x4S2 ? pack_weight_wino2p_kernel : pack_weight_wino2_kernel,
                                dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, as_stream(stream), *d, weight, packed + total, nw);
         if (int e = check_launch("pack_weight_wino_kernel")) return e;
         if (const long nw4 = (long)wino4_weight_floats(d)) {
@@ -2132,52 +2054,28 @@ extern "C" int rnr_pack_conv_weight(const rnr_conv_desc* d, const float* weight,
     return 0;
 }
 
-// split-K slices of a tile can meet inside the launch (splitk_combine) when there are few of them: the last slice reads
-// splitk accumulator images, a serial tail that a chip-wide reduce kernel beats for deep splits
-// OFF since r06 (RNR_CONV_COMBINE=1 in the environment turns it on): re-measured at one view per call, slabs + reduce kernel
-// beat the in-launch form on every layer that took it (L11 46.9 -> 33.2 us, L12 31.4 -> 29.8, frame 449.0 -> 452.2 frames/s;
-// equal from three views on) — the last slices of all tiles fetch their images past the L2 at the same moment behind two fabric
-// round trips, a chip-wide reduce reads the same bytes at 4 - 5 TB/s (profiles/r06_one_view_frontend.txt (3), (5)).
-static bool combines_in_launch(const ConvPlan& pl) {
-    static const int enabled = [] { const char* e = getenv("RNR_CONV_COMBINE"); return e ? atoi(e) : 0; }();
-    return enabled && pl.halo && !pl.wino && pl.splitk > 1 && pl.cfg != 1 && pl.bm * pl.bn <= 128 * 128 &&
-           (long)pl.splitk * pl.bm * pl.bn * (long)sizeof(float) <= RNR_COMBINE_MAX_BYTES;
-}
-static size_t combine_slab_floats(const ConvPlan& pl) {     // one accumulator image per (slice, tile): bm x bn floats
-    return (size_t)pl.splitk * pl.par * pl.mtiles * pl.ntiles * pl.bm * pl.bn;
-}
-
 extern "C" size_t rnr_conv_workspace_bytes(const rnr_conv_desc* d, int num_views, int in_h, int in_w) {
     if (!d || num_views <= 0) return 0;
     ConvPlan pl;
     make_plan(d, num_views, in_h, in_w, &pl);
     if (pl.splitk <= 1) return 256;
-    const size_t legacy = (size_t)pl.splitk * num_views * pl.OH * pl.OW * d->c_out_pad * sizeof(float) + 256;
-    const size_t fused = combines_in_launch(pl) ? combine_slab_floats(pl) * sizeof(float) + 256 : 0;
-    return legacy > fused ? legacy : fused;
+    return (size_t)pl.splitk * num_views * pl.OH * pl.OW * d->c_out_pad * sizeof(float) + 256;
 }
 
-// rnr_conv2d_fused's sync buffer for one call: [arrival counters | tile counters | statistics shards]
-struct SyncLayout { size_t arrive, tiles, stats, total; };
-static SyncLayout sync_layout(const rnr_conv_desc* d, const ConvPlan& pl, int num_views) {
+// rnr_conv2d_fused's sync buffer for one call: [arrival counters | statistics shards]
+struct SyncLayout { size_t arrive, stats, total; };
+static SyncLayout sync_layout(const rnr_conv_desc* d, int num_views) {
     SyncLayout L;
     L.arrive = 0;
-    L.tiles = align_up(sizeof(unsigned) * (size_t)(num_views + 1), 256);
-    L.stats = L.tiles + align_up(sizeof(unsigned) * (size_t)pl.par * pl.mtiles * pl.ntiles, 256);
+    L.stats = align_up(sizeof(unsigned) * (size_t)(num_views + 1), 256);
     L.total = L.stats + sizeof(double) * 2 * (size_t)STAT_SHARDS * num_views * d->c_out_pad;
     return L;
 }
 
-extern "C" size_t rnr_conv_sync_bytes(const rnr_conv_desc* d, int max_views, int in_h, int in_w) {
+// (the size does not depend on the plan, hence not on the map size, and grows with the number of views)
+extern "C" size_t rnr_conv_sync_bytes(const rnr_conv_desc* d, int max_views, int /*in_h*/, int /*in_w*/) {
     if (!d || max_views <= 0) return 0;
-    size_t need = 0;
-    for (int n = 1; n <= max_views; n++) {      // the plan (tile shape, split depth) depends on the number of views
-        ConvPlan pl;
-        make_plan(d, n, in_h, in_w, &pl);
-        const size_t t = sync_layout(d, pl, n).total;
-        need = t > need ? t : need;
-    }
-    return need;
+    return sync_layout(d, max_views).total;
 }
 
 extern "C" int rnr_conv_algorithm(const rnr_conv_desc* d, int num_views, int in_h, int in_w) {
@@ -2187,15 +2085,19 @@ extern "C" int rnr_conv_algorithm(const rnr_conv_desc* d, int num_views, int in_
     return pl.wino;
 }
 
+// the direct kernels' plan whatever Winograd flags the descriptor carries; returns the descriptor without them
+static rnr_conv_desc plan_direct(const rnr_conv_desc* d, int num_views, int in_h, int in_w, ConvPlan* pl) {
+    rnr_conv_desc dd = *d;
+    dd.flags &= ~(RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD4);
+    make_plan(&dd, num_views, in_h, in_w, pl);
+    return dd;
+}
+
 // the plan a MASKED launch runs: the out layer's own Winograd kernel takes a mask, the other Winograd kernels do not — those
 // calls run the direct kernels, on the direct kernels' tiles
 static void mask_plan(const rnr_conv_desc* d, int num_views, int in_h, int in_w, ConvPlan* pl) {
     make_plan(d, num_views, in_h, in_w, pl);
-    if (pl->wino && pl->wino != 3) {
-        rnr_conv_desc dd = *d;
-        dd.flags &= ~(RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD4);
-        make_plan(&dd, num_views, in_h, in_w, pl);
-    }
+    if (pl->wino && pl->wino != 3) plan_direct(d, num_views, in_h, in_w, pl);
 }
 
 extern "C" size_t rnr_conv_tile_count(const rnr_conv_desc* d, int num_views, int in_h, int in_w) {
@@ -2244,11 +2146,8 @@ static int conv2d_run(const rnr_conv_desc* d, const rnr_conv_src* src0, const rn
     hipStream_t st = as_stream(stream);
     ConvPlan pl;
     make_plan(d, num_views, in_h, in_w, &pl);
-    if (pl.wino && (g_ray.w || (tile_mask && pl.wino != 3))) {    // ray-epilogue / masked launches run on the direct kernels' tiles (the out layer's own Winograd kernel takes a mask)
-        rnr_conv_desc dd = *d;
-        dd.flags &= ~(RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD4);
-        make_plan(&dd, num_views, in_h, in_w, &pl);
-    }
+    if (pl.wino && (g_ray.w || (tile_mask && pl.wino != 3)))    // ray-epilogue / masked launches run on the direct kernels' tiles (the out layer's own Winograd kernel takes a mask)
+        plan_direct(d, num_views, in_h, in_w, &pl);
     if (g_ray.w) pl.splitk = 1;         // the ray-renderer epilogue needs the whole K sum in one workgroup (small maps would split)
     ConvParams P = {};
     P.src_data[0] = src0->data; P.src_scale[0] = src0->scale; P.src_shift[0] = src0->shift;
@@ -2269,7 +2168,7 @@ static int conv2d_run(const rnr_conv_desc* d, const rnr_conv_src* src0, const rn
         // input is streamed from HBM four times (r02 PMC: 2.9x the compulsory bytes on the 64-column transposed conv); as
         // neighbours the four share one L2.  The price is four weight sets in flight per XCD instead of one, so the order is
         // chosen by which operand is bigger.  RNR_PAR_INNER=0/1 forces it (experiments).
-        static const int forced = [] { const char* e = getenv("RNR_PAR_INNER"); return e ? atoi(e) : -1; }();
+        static const int forced = env_int("RNR_PAR_INNER", -1);
         const size_t w_bytes = 16 * (size_t)(d->c_in0_pad + d->c_in1_pad) * d->c_out_pad * sizeof(float);
         const size_t in_bytes = (size_t)in_h * in_w * (d->c_in0_pad + d->c_in1_pad) * sizeof(float);     // per view
         P.par_inner = forced >= 0 ? forced : (in_bytes >= w_bytes ? 1 : 0);
@@ -2282,14 +2181,12 @@ static int conv2d_run(const rnr_conv_desc* d, const rnr_conv_src* src0, const rn
     }
     const size_t out_floats = (size_t)num_views * pl.OH * pl.OW * d->c_out_pad;
     const long grid_wgs = (long)pl.mtiles * pl.ntiles * pl.splitk * pl.par;
-    const bool combine = fused && combines_in_launch(pl);
     bool in_kernel_bn = false;
     if (fused) {
-        const SyncLayout L = sync_layout(d, pl, num_views);
+        const SyncLayout L = sync_layout(d, num_views);
         RNR_REQUIRE(sync_bytes >= L.total, "rnr_conv2d_fused: sync buffer too small (%zu < %zu, see rnr_conv_sync_bytes)",
                     sync_bytes, L.total);
         char* sb = reinterpret_cast<char*>(sync);
-        if (combine) P.tile_arrive = reinterpret_cast<unsigned*>(sb + L.tiles);
         if (with_bn) {
             P.stats = reinterpret_cast<double*>(sb + L.stats);
             P.n_shards = STAT_SHARDS;
@@ -2302,7 +2199,7 @@ static int conv2d_run(const rnr_conv_desc* d, const rnr_conv_src* src0, const rn
             // (a separate finalise launch for the big Winograd grids too was measured: -0.5 % on seven layers at 8 views — the
             // ticket is not what the short-K layers lose)
             // (conv_wino4_kernel, one 12-wave workgroup per CU: tickets vs a separate finalise launch measured equal, r04)
-            in_kernel_bn = (pl.splitk == 1 || combine) && grid_wgs > RNR_FUSED_BN_MIN_WGS;
+            in_kernel_bn = pl.splitk == 1 && grid_wgs > RNR_FUSED_BN_MIN_WGS;
             if (in_kernel_bn) {
                 P.arrive = reinterpret_cast<unsigned*>(sb + L.arrive);
                 if (pl.halo) {      // the halo kernels' tiles lie inside one view
@@ -2320,13 +2217,7 @@ static int conv2d_run(const rnr_conv_desc* d, const rnr_conv_src* src0, const rn
         const long n = (long)num_views * d->c_out_pad * 2;
         hipLaunchKernelGGL(zero_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, stats, n);
     }
-    if (combine) {
-        RNR_REQUIRE(workspace && workspace_bytes >= combine_slab_floats(pl) * sizeof(float),
-                    "rnr_conv2d: workspace too small (%zu < %zu)", workspace_bytes, combine_slab_floats(pl) * sizeof(float));
-        P.slabs = reinterpret_cast<float*>(workspace);
-        P.out = out_raw;
-        P.slab_stride = 0;
-    } else if (pl.splitk > 1) {
+    if (pl.splitk > 1) {
         RNR_REQUIRE(workspace && workspace_bytes >= (size_t)pl.splitk * out_floats * sizeof(float),
                     "rnr_conv2d: workspace too small (%zu < %zu)", workspace_bytes,
                     (size_t)pl.splitk * out_floats * sizeof(float));
@@ -2359,20 +2250,8 @@ static int conv2d_run(const rnr_conv_desc* d, const rnr_conv_src* src0, const rn
         }
         else if (pl.wino == 1) launch_wino(dim3((unsigned)grid_wgs), P, st);
         else if (pl.wino == 3) launch_wino80(dim3((unsigned)grid_wgs), P, st);
-        // (preprocessor, not `if`: only the kernel that runs is instantiated into the library)
-        else if (d->kind == RNR_CONV4x4S2_REFLECT) {
-#if (W2_PAIRS) & 1
-            launch_wino2p<1>(dim3((unsigned)grid_wgs), P, st);
-#else
-            launch_wino2<1>(dim3((unsigned)grid_wgs), P, st);
-#endif
-        } else {
-#if (W2_PAIRS) & 2
-            launch_wino2p<2>(dim3((unsigned)grid_wgs), P, st);
-#else
-            launch_wino2<2>(dim3((unsigned)grid_wgs), P, st);
-#endif
-        }
+        else if (d->kind == RNR_CONV4x4S2_REFLECT) launch_wino2(dim3((unsigned)grid_wgs), P, st);
+        else launch_wino2p(dim3((unsigned)grid_wgs), P, st);
     }
     else if (pl.halo && d->kind == RNR_CONV3x3_REFLECT) launch_halo<0>(pl, P, st);
     else if (pl.halo && d->kind == RNR_CONV4x4S2_REFLECT) launch_halo<1>(pl, P, st);
@@ -2381,7 +2260,7 @@ static int conv2d_run(const rnr_conv_desc* d, const rnr_conv_src* src0, const rn
     else if (d->kind == RNR_CONV4x4S2_REFLECT) launch_kind<1>(pl, P, st);
     else launch_kind<2>(pl, P, st);
     if (int e = check_launch("conv_mfma_kernel")) return e;
-    if (pl.splitk > 1 && !combine) {
+    if (pl.splitk > 1) {
         const long rows = (long)num_views * pl.OH * pl.OW;
         const int col_tiles = (d->c_out_pad + 63) / 64, rows_per_view = pl.OH * pl.OW;
         int rpw = 128;          // rows per workgroup: as many as leave >= 512 workgroups and stay inside one view
@@ -2420,9 +2299,7 @@ extern "C" int rnr_conv2d_ray(const rnr_conv_desc* d, const rnr_conv_src* src0, 
     RNR_REQUIRE(ray_w && bias && image, "rnr_conv2d_ray: null pointer argument");
     if (int e = check_desc(d, "rnr_conv2d_ray")) return e;
     ConvPlan pl;
-    rnr_conv_desc dd = *d;
-    dd.flags &= ~(RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD4);         // the ray-renderer epilogue lives in the direct 80-column kernel
-    make_plan(&dd, num_views, in_h, in_w, &pl);
+    const rnr_conv_desc dd = plan_direct(d, num_views, in_h, in_w, &pl);     // the ray-renderer epilogue lives in the direct 80-column kernel
     RNR_REQUIRE(d->kind == RNR_CONV3x3_REFLECT && !(d->flags & RNR_CONV_F32_EMU_ANY) && pl.halo && pl.cfg == 1 && pl.tw == 32 &&
                     d->c_out % 3 == 0 && d->c_out_pad == 80,
                 "rnr_conv2d_ray: only the exact-fp32 3x3 out layer on the 80-column plan (65 <= c_out <= 80, c_out = 3 x rays, map "

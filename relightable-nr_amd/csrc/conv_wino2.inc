@@ -18,153 +18,232 @@
 //           pixels: they read it one row / column apart) and the workgroup's 64 output columns — 32 x 16 output pixels;
 //   KIND 1: group = (tile-row half mb, 64-column half): 16 x 16 output pixels x 128 columns; the K loop runs over
 //           (chunk, phase) and stages the 18 x 17 pixels of one phase image per K block.
-// Per K step of two input channels a wave issues 6 MFMAs, 4 LDS reads (two patch rows), 5 VALU (row xi of B^T d B, then
-// the column combinations) and two buffer_load_dwordx3 from the pre-transformed weight image
-// (pack_weight_wino2_kernel: [column tile][K step][group][xi][half][h][32 columns][3 planes]; KIND 1: the two tile-row
-// halves read the same block).  Staging the next K block takes one (KIND 2) / two (KIND 1) float4 per thread.
 // Epilogue: column combinations per wave, the three plane rows of a group meet through LDS in two rounds (one per column
 // half), wave xi finishes register rows {0-5, 6-10, 11-15}[xi]; statistics / BatchNorm / stores as in the direct kernels.
+//
+// Two kernels, one per kind, share everything but their K loop and weight-image layout (the w2_* functions below):
+//   conv_wino2_kernel<1>  (this file): per K step of two input channels a wave issues 6 MFMAs, 4 LDS reads (two patch rows),
+//                         5 VALU (row xi of B^T d B, then the column combinations) and two buffer_load_dwordx3 from the
+//                         pre-transformed weight image (pack_weight_wino2_kernel: [column tile][K step][column half][xi][half][h]
+//                         [32 columns][3 planes]; the two tile-row halves read the same block); two staged float4 per thread
+//                         per K block;
+//   conv_wino2p_kernel<2> (conv_wino2p.inc): K-step pairs (r05), one staged float4 per thread per K block.
 
 constexpr int W2_THREADS = 768;
 constexpr int W2_HW = 18;                           // staged halo columns (17 used by KIND 1)
-template <int KIND> struct W2Geo {
-    static constexpr int HH = KIND == 2 ? 10 : 17;              // staged rows
-    static constexpr int PLANE = HH * WINO_ROWP + 2;            // floats per channel plane
-    static constexpr int CHUNK = BK * PLANE;                    // floats per staged K block
-    static constexpr int SLOTS = W2_HW * HH * 4;                // float4 slots: 720 / 1224
-    static constexpr int APT = (SLOTS + W2_THREADS - 1) / W2_THREADS;       // 1 / 2
+constexpr int W2_XCHG = 12 * 11 * 64 * 2;           // floats of one exchange round: [wave][<= 11 register rows][lane][2]
+template <int KIND> struct W2Kind {
+    static_assert(KIND == 1 || KIND == 2, "4x4 stride-2 convolutions");
+    static constexpr int NPH = KIND == 1 ? 4 : 1;               // K blocks per 16-channel chunk (input parity phases)
+    static constexpr int BNW = KIND == 1 ? 128 : 64;            // output columns per workgroup
+    static constexpr int TPH = KIND == 1 ? 16 : WINO_PH;        // rows of the GEMM row space per workgroup tile
+    static constexpr int HH = KIND == 1 ? 17 : 10;              // staged rows
+    static constexpr int SLOTS = W2_HW * HH * 4;                // float4 slots: 1224 / 720
+    static constexpr int APT = (SLOTS + W2_THREADS - 1) / W2_THREADS;       // 2 / 1
+};
+
+// ---- shared by conv_wino2_kernel<1> and conv_wino2p_kernel<2> ----
+
+// this thread's wave, group and plane row; the workgroup's tile
+struct W2Tile {
+    int tid, lane, wave, wgrp, xi, grp, l31, h;
+    int nt, z;          // column tile, split-K slice
+    int py, mb;         // KIND 2: row parity of the output class (column parity px = grp); KIND 1: tile rows 4 mb .. 4 mb + 3 of 8
+    int n0;             // first output column of this wave
+    int n, y0, x0;      // view, first row / column of the tile in the GEMM row space (output pixels, KIND 1, or input pixels, KIND 2)
+};
+template <int KIND>
+__device__ __forceinline__ W2Tile w2_tile(const ConvParams& P) {
+    W2Tile T;
+    T.tid = threadIdx.x;
+    T.lane = T.tid & 63;
+    T.wave = __builtin_amdgcn_readfirstlane(T.tid >> 6);
+    T.wgrp = T.wave / 3; T.xi = T.wave - 3 * T.wgrp;       // group of three plane-row waves
+    const int sub = T.wgrp >> 1;                            // KIND 2: (py, px); KIND 1: (tile-row half, column half)
+    T.grp = T.wgrp & 1;
+    T.l31 = T.lane & 31; T.h = T.lane >> 5;
+    int mt_;
+    tile_coords(P, mt_, T.nt, T.z);
+    T.py = KIND == 2 ? sub : 0;
+    T.mb = KIND == 1 ? sub : 0;
+    T.n0 = T.nt * W2Kind<KIND>::BNW + (KIND == 1 ? 64 * T.grp : 0);
+    const int tiles_x = P.Wo / WINO_PW, tiles_y = P.Ho / W2Kind<KIND>::TPH;
+    T.n = mt_ / (tiles_x * tiles_y);
+    const int trem = mt_ - T.n * (tiles_x * tiles_y);
+    T.y0 = (trem / tiles_x) * W2Kind<KIND>::TPH; T.x0 = (trem % tiles_x) * WINO_PW;
+    return T;
+}
+
+// Halo slot j of a thread: a float4 of channel quad q = tid & 3.  Staged row hy / column hx is
+//   KIND 2: input pixel (y0 - 1 + hy, x0 - 1 + hx), zero outside the map (mask; py / px shift the READ by one row / column);
+//   KIND 1, phase (phy, phx): input pixel (reflect1(2 (y0 + hy) - phy), reflect1(2 (x0 + hx) - phx)).  Reflection only ever
+//           moves row 2 (y0 + hy) = H to H - 2 (phy = 0) and row -1 to 1 (phy = 1), so the four pixels of a slot are
+//           spix + phy * (+-W) + phx * (+-1): one register per slot and two sign bits, instead of two reflections per
+//           staging load (r05; ~14 VALU each, - 1 % on the five stride-2 layers).
+// Slots past the halo wrap to an earlier slot of the same channel quad (duplicate writes of identical values).
+struct W2Slot {
+    int hy, hx;
+    unsigned spix;
+    unsigned sign;      // KIND 1: bit 1: the phase-1 row lies BELOW the phase-0 row (+W), bit 0: the phase-1 column lies RIGHT of it (+1)
+    float mask;         // KIND 2: 1 inside the map, 0 outside
+};
+template <int KIND>
+__device__ __forceinline__ W2Slot w2_slot(const ConvParams& P, const W2Tile& T, int j) {
+    constexpr int SLOTS = W2Kind<KIND>::SLOTS;
+    static_assert(SLOTS % 4 == 0, "the wrapped slot keeps the channel quad");
+    W2Slot S;
+    int s = T.tid + W2_THREADS * j;
+    if (s >= SLOTS) s -= SLOTS;
+    const int hp = s >> 2;
+    S.hy = hp / W2_HW; S.hx = hp - S.hy * W2_HW;
+    S.sign = 0; S.mask = 1.f;
+    if (KIND == 2) {
+        int iy = T.y0 - 1 + S.hy, ix = T.x0 - 1 + S.hx;
+        const bool inside = iy >= 0 && iy < P.H && ix >= 0 && ix < P.W;
+        S.mask = inside ? 1.f : 0.f;
+        iy = min(max(iy, 0), P.H - 1); ix = min(max(ix, 0), P.W - 1);
+        S.spix = (unsigned)(iy * P.W + ix);
+    } else {
+        const int ry = 2 * (T.y0 + S.hy), cx = 2 * (T.x0 + S.hx);
+        const int r0 = reflect1(ry, P.H), r1 = reflect1(ry - 1, P.H), c0 = reflect1(cx, P.W), c1 = reflect1(cx - 1, P.W);
+        S.spix = (unsigned)(r0 * P.W + c0);
+        S.sign = (unsigned)((r1 > r0 ? 2 : 0) | (c1 > c0 ? 1 : 0));
+    }
+    return S;
+}
+
+// K block kb = (chunk, input parity phase): source of view n, channel offset, and the BatchNorm scale / shift of quad q
+struct W2Src { __amdgpu_buffer_rsrc_t rsrc; unsigned C; unsigned soff; int act; int phy, phx; float4 sc, sh; };
+template <int KIND>
+__device__ __forceinline__ W2Src w2_block_src(const ConvParams& P, int n, int q, int kb) {
+    constexpr int NPH = W2Kind<KIND>::NPH;
+    W2Src cs;
+    const int c = kb / NPH;
+    cs.phy = (kb % NPH) >> 1; cs.phx = (kb % NPH) & 1;
+    const int s = c < P.chunks0 ? 0 : 1;
+    const int cc = (c - (s ? P.chunks0 : 0)) * BK;
+    cs.C = (unsigned)P.src_c[s];
+    cs.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.src_data[s] + (size_t)n * P.H * P.W * cs.C), 0,
+                                                0x7fffffff, 0x27000);
+    cs.soff = (unsigned)cc * 4u;
+    cs.act = P.src_act[s];
+    cs.sc = make_float4(1.f, 1.f, 1.f, 1.f);
+    cs.sh = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (P.src_scale[s]) cs.sc = *reinterpret_cast<const float4*>(P.src_scale[s] + (size_t)n * cs.C + cc + 4 * q);
+    if (P.src_shift[s]) cs.sh = *reinterpret_cast<const float4*>(P.src_shift[s] + (size_t)n * cs.C + cc + 4 * q);
+    return cs;
+}
+// the raw float4 of a slot (spix, and for KIND 1 the slot's sign bits at bit `sbit` + 1 / `sbit` of `signs`)
+template <int KIND>
+__device__ __forceinline__ float4 w2_load_halo(const ConvParams& P, const W2Src& cs, unsigned pixel, unsigned signs, int sbit, int q) {
+    if (KIND == 1) {
+        if (cs.phy) pixel += (signs >> (sbit + 1)) & 1u ? (unsigned)P.W : 0u - (unsigned)P.W;
+        if (cs.phx) pixel += (signs >> sbit) & 1u ? 1u : ~0u;
+    }
+    const unsigned voff = (pixel * cs.C + 4u * (unsigned)q) * 4u;
+    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(cs.rsrc, (int)voff, (int)cs.soff, 0));
+}
+// BatchNorm + activation of a staged float4; the transposed conv's halo is exactly 0 outside the map, not act(shift)
+template <int KIND>
+__device__ __forceinline__ float4 w2_normalize(const W2Src& cs, float4 v, float mask) {
+    float x = apply_act(v.x * cs.sc.x + cs.sh.x, cs.act);
+    float y = apply_act(v.y * cs.sc.y + cs.sh.y, cs.act);
+    float z = apply_act(v.z * cs.sc.z + cs.sh.z, cs.act);
+    float w = apply_act(v.w * cs.sc.w + cs.sh.w, cs.act);
+    if (KIND == 2) { x *= mask; y *= mask; z *= mask; w *= mask; }
+    return make_float4(x, y, z, w);
+}
+
+
+// Transformed weight U[xi][nu] = (G g G^T)[xi][nu], G = [[1, 0], [1, 1], [0, 1]], of the 2x2-tap correlation g of parity class
+// grp (KIND 2) or phase (KIND 1) for input channel c, output column co: taps in increasing input index, float64, rounded once.
+template <int KIND>
+__device__ __forceinline__ float w2_weight(const rnr_conv_desc& d, const float* __restrict__ w, int grp, int phase, int xi, int nu,
+                                           int c, int co) {
+    double g[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; a++)
+#pragma unroll
+        for (int b = 0; b < 2; b++) {
+            if (KIND == 2) {
+                // class grp = 2 py + px: conv_halo_kernel's tap (ty, tx) reads input row y + py - ty, column x + px - tx
+                g[a][b] = (double)gemm_weight(d, w, grp, (1 - a) * 2 + (1 - b), c, co);
+            } else {
+                // phase (phy, phx): tap a is kernel row ky = phy ? 2 a : 1 + 2 a (conv_halo_kernel, KIND 1), same for columns
+                const int phy = phase >> 1, phx = phase & 1;
+                const int ky = phy ? 2 * a : 1 + 2 * a, kx = phx ? 2 * b : 1 + 2 * b;
+                g[a][b] = (double)gemm_weight(d, w, 0, ky * 4 + kx, c, co);
+            }
+        }
+    double row[2];
+#pragma unroll
+    for (int b = 0; b < 2; b++) row[b] = xi == 0 ? g[0][b] : (xi == 2 ? g[1][b] : g[0][b] + g[1][b]);
+    return (float)(nu == 0 ? row[0] : (nu == 2 ? row[1] : row[0] + row[1]));
+}
+
+// ---- conv_wino2_kernel<1>: the stride-2 convolution, one K step per 6 MFMAs ----
+
+struct W2Geo {
+    static constexpr int PLANE = W2Kind<1>::HH * WINO_ROWP + 2;    // floats per channel plane
+    static constexpr int CHUNK = BK * PLANE;                        // floats per staged K block
 };
 #ifndef W2_SGB
-#define W2_SGB (KIND == 2 ? 6 : 3)   // VALU instructions behind each MFMA in the scheduling pipeline of a K step (measured per kind;
-                                    // 1 - 2: +3 ... +5 %, 0 = compiler's order: up to +7 %)
+#define W2_SGB 3                    // VALU instructions behind each MFMA in the scheduling pipeline of a K step (1 - 2: +3 ... +5 %,
+                                    // 0 = compiler's order: up to +7 %)
 #endif
 #ifndef W2_BDIST_K
 #define W2_BDIST_K 3
 #endif
 constexpr int W2_BDIST = W2_BDIST_K;                         // K steps between the request of a weight block and its MFMAs
-template <int KIND> constexpr int w2_step_floats() { return (KIND == 2 ? 4 : 2) * 3 * 2 * 2 * 32 * 3; }     // weight image per K step: [group][xi][half][h][32][3]
-constexpr int W2_XCHG = 12 * 11 * 64 * 2;           // floats of one exchange round: [wave][<= 11 register rows][lane][2]
+constexpr int W2_STEP_FLOATS = 2 * 3 * 2 * 2 * 32 * 3;       // weight image per K step: [column half][xi][half][h][32][3]
 
-template <int KIND>
 __host__ __device__ constexpr size_t wino2_lds_bytes() {
-    return (size_t)((2 * W2Geo<KIND>::CHUNK > W2_XCHG ? 2 * W2Geo<KIND>::CHUNK : W2_XCHG) + 12 * 64 * 2 + 4) * sizeof(float);
+    return (size_t)((2 * W2Geo::CHUNK > W2_XCHG ? 2 * W2Geo::CHUNK : W2_XCHG) + 12 * 64 * 2 + 4) * sizeof(float);
 }
 
 template <int KIND>
 __global__ void __launch_bounds__(W2_THREADS, 3)
 conv_wino2_kernel(const ConvParams P) {
-    static_assert(KIND == 1 || KIND == 2, "4x4 stride-2 convolutions");
-    constexpr int NPH = KIND == 1 ? 4 : 1;          // K blocks per 16-channel chunk (input parity phases)
-    constexpr int BNW = KIND == 1 ? 128 : 64;       // output columns per workgroup
-    constexpr int W2_PLANE = W2Geo<KIND>::PLANE, W2_CHUNK = W2Geo<KIND>::CHUNK;
-    constexpr int W2_SLOTS = W2Geo<KIND>::SLOTS, W2_APT = W2Geo<KIND>::APT;
-    constexpr int W2_STEP_FLOATS = w2_step_floats<KIND>();
-    constexpr int TPH = KIND == 1 ? 16 : WINO_PH;    // rows of the GEMM row space per workgroup tile
+    static_assert(KIND == 1, "the stride-2 convolution (the transposed one runs conv_wino2p_kernel)");
+    constexpr int NPH = W2Kind<KIND>::NPH, APT = W2Kind<KIND>::APT;
+    constexpr int PLANE = W2Geo::PLANE, CHUNK = W2Geo::CHUNK;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* As = smem;                       // [2][W2_CHUNK]; the epilogue's exchange buffer afterwards
+    float* As = smem;                       // [2][CHUNK]; the epilogue's exchange buffer afterwards
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wgrp = wave / 3, xi = wave - 3 * wgrp;        // group of three plane-row waves
-    const int sub = wgrp >> 1, grp = wgrp & 1;              // KIND 2: (py, px); KIND 1: (tile-row half, column half)
-    const int l31 = lane & 31, h = lane >> 5;
-    int mt_, nt_, z_;
-    tile_coords(P, mt_, nt_, z_);
-    const int py = KIND == 2 ? sub : 0;             // KIND 2: row parity of the output class; column parity px = grp
-    const int mb = KIND == 1 ? sub : 0;             // KIND 1: tile rows 4 mb .. 4 mb + 3 of the workgroup's 8
-    const int n0 = nt_ * BNW + (KIND == 1 ? 64 * grp : 0);      // first output column of this wave
-    // tile grid in the GEMM row space: output pixels (KIND 1) or input pixels of a parity class (KIND 2)
-    const int tiles_x = P.Wo / WINO_PW, tiles_y = P.Ho / TPH;
-    const int n = mt_ / (tiles_x * tiles_y);
-    const int trem = mt_ - n * (tiles_x * tiles_y);
-    const int y0 = (trem / tiles_x) * TPH, x0 = (trem % tiles_x) * WINO_PW;
-
-    // halo slots of this thread.  Staged row hy / column hx is
-    //   KIND 2: input pixel (y0 - 1 + hy, x0 - 1 + hx), zero outside the map (py / px shift the READ by one row / column);
-    //   KIND 1, phase (phy, phx): input pixel (2 (y0 + hy) - phy, 2 (x0 + hx) - phx), reflected.
-    // Slots past the halo wrap to an earlier slot of the same channel quad (duplicate writes of identical values).
-    // KIND 1: the source pixels of the four phases of a slot come from ONE register and two sign bits (r05; two reflections per
-    // staging load before: ~14 VALU each, - 1 % on the five stride-2 layers)
-    const int q = tid & 3;
-    unsigned spix[W2_APT];
-    unsigned ssign = 0;     // KIND 1: bit 2 j + 1: the phase-1 row lies BELOW the phase-0 row (+W), bit 2 j: the phase-1 column lies RIGHT of it (+1)
-    float smask[KIND == 2 ? W2_APT : 1];
-    float* sd_cur[W2_APT];
-    float* sd_nxt[W2_APT];
+    const W2Tile T = w2_tile<KIND>(P);
+    const int xi = T.xi, l31 = T.l31, h = T.h;
+    const int q = T.tid & 3;
+    unsigned spix[APT];
+    unsigned ssign = 0;     // the sign bits of slot j at bits 2 j + 1, 2 j
+    float* sd_cur[APT];
+    float* sd_nxt[APT];
 #pragma unroll
-    for (int j = 0; j < W2_APT; j++) {
-        int s = tid + W2_THREADS * j;
-        if (s >= W2_SLOTS) s -= W2_SLOTS;
-        static_assert(W2_SLOTS % 4 == 0, "the wrapped slot keeps the channel quad");
-        const int hp = s >> 2;
-        const int hy = hp / W2_HW, hx = hp - hy * W2_HW;
-        if (KIND == 2) {
-            int iy = y0 - 1 + hy, ix = x0 - 1 + hx;
-            const bool inside = iy >= 0 && iy < P.H && ix >= 0 && ix < P.W;
-            smask[j] = inside ? 1.f : 0.f;
-            iy = min(max(iy, 0), P.H - 1); ix = min(max(ix, 0), P.W - 1);
-            spix[j] = (unsigned)(iy * P.W + ix);
-        } else {
-            // reflection only ever moves row 2 (y0 + hy) = H to H - 2 (phase 0) and row -1 to 1 (phase 1): pixel(phy, phx) =
-            // spix + phy * (+-W) + phx * (+-1)
-            const int ry = 2 * (y0 + hy), cx = 2 * (x0 + hx);
-            const int r0 = reflect1(ry, P.H), r1 = reflect1(ry - 1, P.H), c0 = reflect1(cx, P.W), c1 = reflect1(cx - 1, P.W);
-            spix[j] = (unsigned)(r0 * P.W + c0);
-            ssign |= (unsigned)((r1 > r0 ? 2 : 0) | (c1 > c0 ? 1 : 0)) << (2 * j);
-        }
-        sd_cur[j] = As + (4 * q) * W2_PLANE + hy * WINO_ROWP + hx;
-        sd_nxt[j] = sd_cur[j] + W2_CHUNK;
+    for (int j = 0; j < APT; j++) {
+        const W2Slot S = w2_slot<KIND>(P, T, j);
+        spix[j] = S.spix;
+        ssign |= S.sign << (2 * j);
+        sd_cur[j] = As + (4 * q) * PLANE + S.hy * WINO_ROWP + S.hx;
+        sd_nxt[j] = sd_cur[j] + CHUNK;
     }
 
-    // split-K (small grids): slice z_ of P.splitk takes the chunks [c_begin, c_end) and writes partial outputs to its own slab
+    // split-K (small grids): slice z of P.splitk takes the chunks [c_begin, c_end) and writes partial outputs to its own slab
     const int nchunks = P.chunks_per_tap;
     const int per_split = (nchunks + P.splitk - 1) / P.splitk;
-    const int c_begin = z_ * per_split, c_end = min(nchunks, c_begin + per_split);
+    const int c_begin = T.z * per_split, c_end = min(nchunks, c_begin + per_split);
     const int kb_begin = c_begin * NPH, kb_end = c_end * NPH;   // K blocks: (chunk, phase)
-    struct ChunkSrc { __amdgpu_buffer_rsrc_t rsrc; unsigned C; unsigned soff; int act; int phy, phx; float4 sc, sh; };
-    auto block_src = [&](int kb) {
-        ChunkSrc cs;
-        const int c = kb / NPH;
-        cs.phy = (kb % NPH) >> 1; cs.phx = (kb % NPH) & 1;
-        const int s = c < P.chunks0 ? 0 : 1;
-        const int cc = (c - (s ? P.chunks0 : 0)) * BK;
-        cs.C = (unsigned)P.src_c[s];
-        cs.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.src_data[s] + (size_t)n * P.H * P.W * cs.C), 0,
-                                                    0x7fffffff, 0x27000);
-        cs.soff = (unsigned)cc * 4u;
-        cs.act = P.src_act[s];
-        cs.sc = make_float4(1.f, 1.f, 1.f, 1.f);
-        cs.sh = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (P.src_scale[s]) cs.sc = *reinterpret_cast<const float4*>(P.src_scale[s] + (size_t)n * cs.C + cc + 4 * q);
-        if (P.src_shift[s]) cs.sh = *reinterpret_cast<const float4*>(P.src_shift[s] + (size_t)n * cs.C + cc + 4 * q);
-        return cs;
-    };
-    auto load_a = [&](const ChunkSrc& cs, int j) {
-        unsigned pixel;
-        pixel = spix[j];
-        if (KIND == 1) {
-            if (cs.phy) pixel += (ssign >> (2 * j + 1)) & 1u ? (unsigned)P.W : 0u - (unsigned)P.W;
-            if (cs.phx) pixel += (ssign >> (2 * j)) & 1u ? 1u : ~0u;
-        }
-        const unsigned voff = (pixel * cs.C + 4u * (unsigned)q) * 4u;
-        return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(cs.rsrc, (int)voff, (int)cs.soff, 0));
-    };
-    auto store_a = [&](const ChunkSrc& cs, float4 v, int j, float* a) {
-        float x = apply_act(v.x * cs.sc.x + cs.sh.x, cs.act);
-        float y = apply_act(v.y * cs.sc.y + cs.sh.y, cs.act);
-        float z = apply_act(v.z * cs.sc.z + cs.sh.z, cs.act);
-        float w = apply_act(v.w * cs.sc.w + cs.sh.w, cs.act);
-        if (KIND == 2) { x *= smask[j]; y *= smask[j]; z *= smask[j]; w *= smask[j]; }     // exactly 0 outside, not act(shift)
-        a[0] = x; a[W2_PLANE] = y; a[2 * W2_PLANE] = z; a[3 * W2_PLANE] = w;
+    auto block_src = [&](int kb) { return w2_block_src<KIND>(P, T.n, q, kb); };
+    auto load_a = [&](const W2Src& cs, int j) { return w2_load_halo<KIND>(P, cs, spix[j], ssign, 2 * j, q); };
+    auto store_a = [&](const W2Src& cs, float4 v, int j, float* a) {
+        const float4 u = w2_normalize<KIND>(cs, v, 1.f);
+        a[0] = u.x; a[PLANE] = u.y; a[2 * PLANE] = u.z; a[3 * PLANE] = u.w;
     };
 
-    // transformed weights of this column tile: [K step][group][xi][half][h][32 columns][3 planes]
+    // transformed weights of this column tile: [K step][column half][xi][half][h][32 columns][3 planes]
     const int nsteps = nchunks * NPH * 8;
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.weight_wino), 0, 0x7fffffff, 0x27000);
     const unsigned bvoff = (unsigned)(h * 32 + l31) * 12u;
-    unsigned bsoff = ((unsigned)nt_ * (unsigned)(nsteps + W2_BDIST) + (unsigned)(kb_begin * 8)) * (unsigned)(W2_STEP_FLOATS * 4) +
-                     (unsigned)(((KIND == 2 ? wgrp : grp) * 3 + xi) * 2) * 768u;
+    unsigned bsoff = ((unsigned)T.nt * (unsigned)(nsteps + W2_BDIST) + (unsigned)(kb_begin * 8)) * (unsigned)(W2_STEP_FLOATS * 4) +
+                     (unsigned)((T.grp * 3 + xi) * 2) * 768u;
     typedef float floatx3 __attribute__((ext_vector_type(3)));
     struct BRegs { floatx3 b[2]; };
     auto load_b = [&](BRegs& dst) {      // the next K step's block
@@ -179,13 +258,13 @@ conv_wino2_kernel(const ConvParams P) {
     const float sigma = xi == 1 ? 0.0f : -1.0f;
     struct Rows { const float* a; const float* c; };
     Rows rcur, rnxt;
-    const int row0 = KIND == 2 ? 2 * ty + py : 2 * (4 * mb + ty);       // first patch row of this lane's tile in the staged image
-    rcur.a = As + h * W2_PLANE + (row0 + row_a) * WINO_ROWP + 2 * tx;
-    rcur.c = As + h * W2_PLANE + (row0 + row_c) * WINO_ROWP + 2 * tx;
-    rnxt.a = rcur.a + W2_CHUNK;
-    rnxt.c = rcur.c + W2_CHUNK;
+    const int row0 = 2 * (4 * T.mb + ty);       // first patch row of this lane's tile in the staged image
+    rcur.a = As + h * PLANE + (row0 + row_a) * WINO_ROWP + 2 * tx;
+    rcur.c = As + h * PLANE + (row0 + row_c) * WINO_ROWP + 2 * tx;
+    rnxt.a = rcur.a + CHUNK;
+    rnxt.c = rcur.c + CHUNK;
     auto read_patch = [&](float (&d)[8], const Rows& rows, int s) {
-        const int xo = 2 * s * W2_PLANE;
+        const int xo = 2 * s * PLANE;
         const float2 a0 = *reinterpret_cast<const float2*>(rows.a + xo), a1 = *reinterpret_cast<const float2*>(rows.a + xo + 2);
         const float2 c0 = *reinterpret_cast<const float2*>(rows.c + xo), c1 = *reinterpret_cast<const float2*>(rows.c + xo + 2);
         d[0] = a0.x; d[1] = a0.y; d[2] = a1.x; d[3] = a1.y;
@@ -199,22 +278,21 @@ conv_wino2_kernel(const ConvParams P) {
         for (int g = 0; g < 16; g++) acc[p][g] = 0.0f;
 
     if (kb_begin < kb_end) {
-        const ChunkSrc cs = block_src(kb_begin);
+        const W2Src cs = block_src(kb_begin);
 #pragma unroll
-        for (int j = 0; j < W2_APT; j++) store_a(cs, load_a(cs, j), j, sd_cur[j]);
+        for (int j = 0; j < APT; j++) store_a(cs, load_a(cs, j), j, sd_cur[j]);
     }
     BRegs breg[4];
 #pragma unroll
     for (int k = 0; k < W2_BDIST; k++) load_b(breg[k]);
     __syncthreads();
 
-    // the K loop, instantiated per column offset of the patch inside the staged halo (KIND 2: px; KIND 1: 0)
-    auto k_loop = [&](auto PX) {
-        constexpr int px = decltype(PX)::value;
+    // the K loop (a lambda, like conv_wino2p_kernel's: written straight into the kernel it spills two registers)
+    auto k_loop = [&]() {
         auto transform = [&](const float (&d)[8], float (&v)[3]) {
             float t[3];
 #pragma unroll
-            for (int j = 0; j < 3; j++) t[j] = __builtin_fmaf(sigma, d[4 + px + j], d[px + j]);
+            for (int j = 0; j < 3; j++) t[j] = __builtin_fmaf(sigma, d[4 + j], d[j]);
             v[0] = t[0] - t[1]; v[1] = t[1]; v[2] = t[1] - t[2];
         };
         float raw[2][8], V[2][3];
@@ -223,20 +301,20 @@ conv_wino2_kernel(const ConvParams P) {
         read_patch(raw[1], rcur, 1);
         auto block_body = [&](auto NEXT, int kb) {
             constexpr bool next_block = decltype(NEXT)::value;
-            const ChunkSrc csn = block_src(next_block ? kb + 1 : kb);
-            float4 avr[W2_APT];
+            const W2Src csn = block_src(next_block ? kb + 1 : kb);
+            float4 avr[APT];
 #pragma unroll
             for (int s = 0; s < 8; s++) {
                 if (next_block && s == 6) __syncthreads();
                 load_b(breg[(s + W2_BDIST) & 3]);
                 if (s < 6) read_patch(raw[s & 1], rcur, s + 2);
                 else if (next_block) read_patch(raw[s & 1], rnxt, s - 6);
-                if (next_block && s < W2_APT) avr[s] = load_a(csn, s);
+                if (next_block && s < APT) avr[s] = load_a(csn, s);
 #pragma unroll
                 for (int p = 0; p < 6; p++)
                     acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(V[s & 1][p >> 1], breg[s & 3].b[p & 1][p >> 1], acc[p], 0, 0, 0);
                 if (s < 7 || next_block) transform(raw[(s + 1) & 1], V[(s + 1) & 1]);
-                if (next_block && s >= 3 && s < 3 + W2_APT) store_a(csn, avr[s - 3], s - 3, sd_nxt[s - 3]);
+                if (next_block && s >= 3 && s < 3 + APT) store_a(csn, avr[s - 3], s - 3, sd_nxt[s - 3]);
 #pragma unroll
                 for (int p = 0; p < (W2_SGB > 0 ? 6 : 0); p++) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // MFMA
@@ -248,194 +326,46 @@ conv_wino2_kernel(const ConvParams P) {
             }
             const Rows t = rcur; rcur = rnxt; rnxt = t;
 #pragma unroll
-            for (int j = 0; j < W2_APT; j++) { float* u = sd_cur[j]; sd_cur[j] = sd_nxt[j]; sd_nxt[j] = u; }
+            for (int j = 0; j < APT; j++) { float* u = sd_cur[j]; sd_cur[j] = sd_nxt[j]; sd_nxt[j] = u; }
         };
         for (int kb = kb_begin; kb + 1 < kb_end; kb++) block_body(std::true_type{}, kb);
         if (kb_begin < kb_end) block_body(std::false_type{}, kb_end - 1);
-    };
-    if (KIND == 2 && grp == 1) k_loop(std::integral_constant<int, 1>{});
-    else k_loop(std::integral_constant<int, 0>{});
 
-    // ---- epilogue: Y = A^T M A per (tile, column), statistics, BatchNorm arrival, stores ----
-    // rr[g][half] = (r[b = 0], r[b = 1]) of this wave's plane row: r0 = M0 + M1, r1 = M1 - M2
-    float2 rr[16][2];
-#pragma unroll
-    for (int g = 0; g < 16; g++)
-#pragma unroll
-        for (int nb = 0; nb < 2; nb++) {
-            rr[g][nb].x = acc[0 + nb][g] + acc[2 + nb][g];
-            rr[g][nb].y = acc[2 + nb][g] - acc[4 + nb][g];
-        }
-    // wave xi finishes register rows [G0, G1): Y0 = R0 + R1, Y1 = R1 - R2 over the plane rows of its group
-    float2 y0v[6][2], y1v[6][2];        // [row][half]; waves 1, 2 use five rows
-    float2* xb = reinterpret_cast<float2*>(As);             // [wave][<= 11 rows it does not finish][lane]
-    const int wbase = wgrp * 3;
-    auto finish = [&](auto F) {
-        constexpr int f = decltype(F)::value;
-        constexpr int G0[3] = {0, 6, 11}, G1[3] = {6, 11, 16};
-#pragma unroll
-        for (int nb = 0; nb < 2; nb++) {
-            __syncthreads();        // round 0: every wave is done with the halo; round 1: with the previous exchange
-            int k = 0;
-#pragma unroll
-            for (int g = 0; g < 16; g++) {
-                if (g >= G0[f] && g < G1[f]) continue;
-                xb[((wbase + f) * 11 + k) * 64 + lane] = rr[g][nb];
-                k++;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int g = G0[f]; g < G1[f]; g++) {
-                float2 R[3];
-#pragma unroll
-                for (int o = 0; o < 3; o++) {
-                    if (o == f) { R[o] = rr[g][nb]; continue; }
-                    // position of row g among the rows wave o does not finish
-                    const int ko = g < G0[o] ? g : g - (G1[o] - G0[o]);
-                    R[o] = xb[((wbase + o) * 11 + ko) * 64 + lane];
-                }
-                y0v[g - G0[f]][nb] = make_float2(R[0].x + R[1].x, R[0].y + R[1].y);
-                y1v[g - G0[f]][nb] = make_float2(R[1].x - R[2].x, R[1].y - R[2].y);
-            }
-        }
     };
-    if (xi == 0) finish(std::integral_constant<int, 0>{});
-    else if (xi == 1) finish(std::integral_constant<int, 1>{});
-    else finish(std::integral_constant<int, 2>{});
-    const int g0 = xi == 0 ? 0 : (xi == 1 ? 6 : 11), ng = xi == 0 ? 6 : 5;
+    k_loop();
 
-    float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < 6; k++)
-#pragma unroll
-        for (int nb = 0; nb < 2; nb++) {
-            if (k < ng) {
-                s1[nb] += y0v[k][nb].x + y0v[k][nb].y + y1v[k][nb].x + y1v[k][nb].y;
-                s2[nb] += y0v[k][nb].x * y0v[k][nb].x + y0v[k][nb].y * y0v[k][nb].y + y1v[k][nb].x * y1v[k][nb].x +
-                          y1v[k][nb].y * y1v[k][nb].y;
-            }
-        }
-    float* red = As + (2 * W2_CHUNK > W2_XCHG ? 2 * W2_CHUNK : W2_XCHG);        // [12 waves][64 columns][2], behind the exchange buffer
-    int* flag = reinterpret_cast<int*>(red + 12 * 64 * 2);
-    const bool with_stats = P.stats != nullptr && P.splitk == 1;
-    if (with_stats) {
-#pragma unroll
-        for (int nb = 0; nb < 2; nb++) {
-            s1[nb] += __shfl_xor(s1[nb], 32, 64);
-            s2[nb] += __shfl_xor(s2[nb], 32, 64);
-            if (h == 0) {
-                red[(wave * 64 + 32 * nb + l31) * 2 + 0] = s1[nb];
-                red[(wave * 64 + 32 * nb + l31) * 2 + 1] = s2[nb];
-            }
-        }
-        __syncthreads();
-        if (tid < BNW) {
-            // KIND 2: all twelve waves hold the workgroup's 64 columns; KIND 1: the six waves of column half tid / 64
-            const int col = nt_ * BNW + tid;
-            if (col < P.c_out) {
-                double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-                for (int w = 0; w < 12; w++) {
-                    if (KIND == 1 && ((w / 3) & 1) != (tid >> 6)) continue;
-                    t1 += (double)red[(w * 64 + (tid & 63)) * 2 + 0];
-                    t2 += (double)red[(w * 64 + (tid & 63)) * 2 + 1];
-                }
-                double* st = stat_slot(P, n, col);
-                atomicAdd(st + 0, t1);
-                atomicAdd(st + 1, t2);
-            }
-        }
-    }
-    BnArrival arr = {nullptr, 0u};
-    const bool bn = with_stats && P.arrive;
-    if (bn) arr = bn_arrive(P, n, tid);
-    {
-        // register row g = tile row g >> 2, tile column (g & 3) + 4 h; outputs (2 ty + e, 2 tx + f) of the tile
-        constexpr int XM = KIND == 2 ? 2 : 1;       // transposed conv: this parity class writes every other pixel
-        const int Y00 = XM * (y0 + 8 * mb) + (KIND == 2 ? py : 0), X00 = XM * x0 + (KIND == 2 ? grp : 0);
-        float* base = P.out + (size_t)z_ * P.slab_stride + (((size_t)n * P.OH + Y00) * P.OW + X00) * P.c_out_pad + n0;
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x27000);
-        const unsigned cp4 = (unsigned)P.c_out_pad * 4u;
-        unsigned voff[2];
-#pragma unroll
-        for (int nb = 0; nb < 2; nb++)
-            voff[nb] = (n0 + 32 * nb + l31 < P.c_out_pad) ? (unsigned)(XM * 8 * h) * cp4 + (unsigned)(32 * nb + l31) * 4u : 0x7fffffffu;
-#pragma unroll
-        for (int k = 0; k < 6; k++) {
-            if (k >= ng) continue;
-            const int g = g0 + k;
-            const int tyr = g >> 2, txr = g & 3;
-#pragma unroll
-            for (int e = 0; e < 2; e++)
-#pragma unroll
-                for (int f = 0; f < 2; f++)
-#pragma unroll
-                    for (int nb = 0; nb < 2; nb++) {
-                        const unsigned soff = (unsigned)(XM * ((2 * tyr + e) * P.OW + 2 * txr + f)) * cp4;
-                        const float2 yy = e ? y1v[k][nb] : y0v[k][nb];
-                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(f ? yy.y : yy.x), rsrc, (int)voff[nb], (int)soff, WINO_OUT_AUX);
-                    }
-        }
-    }
-    if (bn) bn_complete(P, arr, n, tid, flag);
+#include "conv_wino2_epilogue.inc"
 }
 
-// Transformed weights U = G g G^T with G = [[1, 0], [1, 1], [0, 1]] of the 2x2-tap correlation g of a parity class (KIND 2)
-// or phase (KIND 1), taps in increasing input index, computed in float64 and rounded once.
-// i enumerates [column tile][K step][group][xi][half][h][32 columns][3 planes nu]; groups: the four parity classes
-// 2 py + px (KIND 2), the two 64-column halves (KIND 1); a K step is ((chunk * NPH + phase) * 8 + s) and holds the padded
-// input channels chunk * 16 + 2 s + h; the W2_BDIST K steps behind the last one are zeros.
+// conv_wino2_kernel's weight image: i enumerates [column tile][K step][column half grp][xi][half][h][32 columns][3 planes nu];
+// a K step is ((chunk * 4 + phase) * 8 + s) and holds the padded input channels chunk * 16 + 2 s + h; the W2_BDIST K steps
+// behind the last one are zeros.
 __global__ void __launch_bounds__(256)
 pack_weight_wino2_kernel(rnr_conv_desc d, const float* __restrict__ w, float* __restrict__ image, long total) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
-    const bool transposed = d.kind == RNR_CONVT4x4S2;
-    const int nph = transposed ? 1 : 4, ngrp = transposed ? 4 : 2;
-    const int nsteps = (d.c_in0_pad + d.c_in1_pad) / 2 * nph;
+    const int nsteps = (d.c_in0_pad + d.c_in1_pad) / 2 * 4;
     const int nu = (int)(i % 3);
     long r = i / 3;
     const int col = (int)(r & 31); r >>= 5;
     const int hh = (int)(r & 1); r >>= 1;
     const int nb = (int)(r & 1); r >>= 1;
     const int xi = (int)(r % 3); r /= 3;
-    const int grp = (int)(r % ngrp); r /= ngrp;
+    const int grp = (int)(r % 2); r /= 2;
     const int step = (int)(r % (nsteps + W2_BDIST));
     const int nt = (int)(r / (nsteps + W2_BDIST));
     if (step >= nsteps) { image[i] = 0.0f; return; }
     const int kb = step >> 3, s = step & 7;
-    const int chunk = kb / nph, phase = kb % nph;
-    const int c = chunk * 16 + 2 * s + hh;
-    const int co = transposed ? nt * 64 + nb * 32 + col : nt * 128 + grp * 64 + nb * 32 + col;
-    // g[a][b]: taps in increasing input row / column
-    double g[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++) {
-            if (transposed) {
-                // class grp = 2 py + px: conv_halo_kernel's tap (ty, tx) reads input row y + py - ty, column x + px - tx
-                g[a][b] = (double)gemm_weight(d, w, grp, (1 - a) * 2 + (1 - b), c, co);
-            } else {
-                // phase (phy, phx): tap a is kernel row ky = phy ? 2 a : 1 + 2 a (conv_halo_kernel, KIND 1), same for columns
-                const int phy = phase >> 1, phx = phase & 1;
-                const int ky = phy ? 2 * a : 1 + 2 * a, kx = phx ? 2 * b : 1 + 2 * b;
-                g[a][b] = (double)gemm_weight(d, w, 0, ky * 4 + kx, c, co);
-            }
-        }
-    double row[2];
-#pragma unroll
-    for (int b = 0; b < 2; b++) row[b] = xi == 0 ? g[0][b] : (xi == 2 ? g[1][b] : g[0][b] + g[1][b]);
-    const double u = nu == 0 ? row[0] : (nu == 2 ? row[1] : row[0] + row[1]);
-    image[i] = (float)u;
+    const int c = (kb / 4) * 16 + 2 * s + hh;
+    image[i] = w2_weight<1>(d, w, 0, kb % 4, xi, nu, c, nt * 128 + grp * 64 + nb * 32 + col);
 }
 
-template <int KIND>
 static void launch_wino2(const dim3 grid, const ConvParams& P, hipStream_t st) {
     static bool attr_set = false;
     if (!attr_set) {         // > 64 KiB of dynamic LDS needs the opt-in
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino2_kernel<KIND>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)wino2_lds_bytes<KIND>());
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino2_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)wino2_lds_bytes());
         attr_set = true;
     }
-    hipLaunchKernelGGL((conv_wino2_kernel<KIND>), grid, dim3(W2_THREADS), wino2_lds_bytes<KIND>(), st, P);
+    hipLaunchKernelGGL((conv_wino2_kernel<1>), grid, dim3(W2_THREADS), wino2_lds_bytes(), st, P);
 }

@@ -1,7 +1,9 @@
-// Winograd F(2x2, 2x2) for the two 4x4 stride-2 convolutions, second generation (r05): the algorithm, the workgroup mapping and
-// the epilogue of conv_wino2.inc (read its header first) with a K loop that issues fewer instructions per MFMA.
+// Winograd F(2x2, 2x2) for the transposed 4x4 stride-2 convolution (KIND 2), second generation (r05): the algorithm, the
+// workgroup mapping and the epilogue of conv_wino2.inc (read its header first; tiles, halo staging, split-K, the exchange of the
+// plane rows, statistics, BatchNorm arrival and stores are its w2_* functions) with a K loop that issues fewer instructions
+// per MFMA.
 //
-// What bounded conv_wino2_kernel (r04 PMC + ISA: per 48 MFMAs of a wave 34 - 40 LDS instructions, 16 buffer_load_dwordx3,
+// What bounded the first-generation K loop (r04 PMC + ISA: per 48 MFMAs of a wave 34 - 40 LDS instructions, 16 buffer_load_dwordx3,
 // 85 - 103 VALU, a dwordx3 spill reload in the K loop of the transposed kernel; every one of them costs matrix-pipe time beside
 // an f32 MFMA, DESIGN 3.3a):  a K step (two input channels: lane half h takes channel 2 s + h) read two patch rows of 3 floats
 // as ds_read_b64 + ds_read_b32 each and its six weights as two dwordx3.
@@ -12,13 +14,14 @@
 //     and pair (4 LDS reads per 12 MFMAs instead of 8 - 10), staged by two ds_write_b64 per float4 of the halo instead of
 //     four ds_write_b32;
 //   * weights: the 12 floats of a lane for a pair (2 steps x 2 column halves x 3 planes) are contiguous in the image
-//     [column tile][pair][group][xi][h][32 columns][12]: three buffer_load_dwordx4 per 12 MFMAs instead of four dwordx3, one
+//     [column tile][pair][class][xi][h][32 columns][12]: three buffer_load_dwordx4 per 12 MFMAs instead of four dwordx3, one
 //     pair ahead in a ring of two pair blocks (24 registers, what the ring of four step blocks took);
-//   * the K loop is instantiated per plane row xi (and per column parity px of the class, KIND 2): the patch-row offsets are
+//   * the K loop is instantiated per plane row xi and per column parity px of the class: the patch-row offsets are
 //     immediates (one address register instead of four), the middle plane row (xi = 1: t = d1) reads ONE patch row and runs
 //     no row combination, and nothing is kept in scratch.
-// Everything else — tiles, groups, split-K, the exchange of the plane rows, statistics, BatchNorm arrival, stores — is
-// conv_wino2_kernel's; the two kernels give bit-identical outputs (same products, same accumulation order per accumulator).
+// -4.3 ... -4.7 % on the transposed layers against conv_wino2_kernel's K loop.  The stride-2 convolutions were measured on this
+// K loop too and lost (+8 ... +23 %: the kernel needs scratch there and its 12-MFMA weight look-ahead stalls behind the two HBM
+// halo loads of every phase block; profiles/r05_wino2_pairs_ab.txt), so they stay on conv_wino2_kernel<1>.
 
 #ifndef W2P_ROWQ_K
 #define W2P_ROWQ_K 40
@@ -32,134 +35,64 @@ constexpr int W2P_ROWQ = W2P_ROWQ_K;                        // floats per image 
 #endif
 static_assert(W2P_RING > W2P_AHEAD && 12 % W2P_RING == 0, "weight ring");
 constexpr int W2P_PAD_PAIRS = (W2P_AHEAD + 2) / 3;  // zero pair-steps behind the last one of a column tile (the weight look-ahead)
-template <int KIND> struct W2PGeo {
-    static constexpr int HH = KIND == 2 ? 10 : 17;              // staged rows
-    static constexpr int PLANE = HH * W2P_ROWQ + 4;             // floats per (pair, h) plane: 16-byte aligned, 2 * PLANE = 24 mod 32 spreads the four channel quads of a staging store over the banks
+struct W2PGeo {
+    static constexpr int PLANE = W2Kind<2>::HH * W2P_ROWQ + 4;  // floats per (pair, h) plane: 16-byte aligned, 2 * PLANE = 24 mod 32 spreads the four channel quads of a staging store over the banks
     static constexpr int CHUNK = 8 * PLANE;                     // floats per staged K block (16 channels)
-    static constexpr int SLOTS = W2_HW * HH * 4;                // float4 slots: 720 / 1224
-    static constexpr int APT = (SLOTS + W2_THREADS - 1) / W2_THREADS;       // 1 / 2
 };
 #ifndef W2P_SGB
-#define W2P_SGB 5                   // VALU instructions behind each MFMA in the scheduling pipeline of a pair (transposed conv, r05 A/B: 0: +5 %, 3 / 5: equal)
+#define W2P_SGB 5                   // VALU instructions behind each MFMA in the scheduling pipeline of a pair (r05 A/B: 0: +5 %, 3 / 5: equal)
 #endif
-template <int KIND> constexpr int w2p_pair_floats() { return 2 * w2_step_floats<KIND>(); }      // weight image per pair-step
+constexpr int W2P_PAIR_FLOATS = 4 * 3 * 2 * 32 * 12;       // weight image per pair-step: [class][xi][h][32][12]
 
-template <int KIND>
 __host__ __device__ constexpr size_t wino2p_lds_bytes() {
-    return (size_t)((2 * W2PGeo<KIND>::CHUNK > W2_XCHG ? 2 * W2PGeo<KIND>::CHUNK : W2_XCHG) + 12 * 64 * 2 + 4) * sizeof(float);
+    return (size_t)((2 * W2PGeo::CHUNK > W2_XCHG ? 2 * W2PGeo::CHUNK : W2_XCHG) + 12 * 64 * 2 + 4) * sizeof(float);
 }
 
 template <int KIND>
 __global__ void __launch_bounds__(W2_THREADS, 3)
 conv_wino2p_kernel(const ConvParams P) {
-    static_assert(KIND == 1 || KIND == 2, "4x4 stride-2 convolutions");
-    constexpr int NPH = KIND == 1 ? 4 : 1;          // K blocks per 16-channel chunk (input parity phases)
-    constexpr int BNW = KIND == 1 ? 128 : 64;       // output columns per workgroup
-    constexpr int PLANE = W2PGeo<KIND>::PLANE, CHUNK = W2PGeo<KIND>::CHUNK;
-    constexpr int SLOTS = W2PGeo<KIND>::SLOTS, APT = W2PGeo<KIND>::APT;
-    constexpr int PAIR_BYTES = w2p_pair_floats<KIND>() * 4;
-    constexpr int TPH = KIND == 1 ? 16 : WINO_PH;    // rows of the GEMM row space per workgroup tile
+    static_assert(KIND == 2, "the transposed convolution (the stride-2 one runs conv_wino2_kernel)");
+    constexpr int APT = W2Kind<KIND>::APT;
+    constexpr int PLANE = W2PGeo::PLANE, CHUNK = W2PGeo::CHUNK;
+    constexpr int PAIR_BYTES = W2P_PAIR_FLOATS * 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* As = smem;                       // [2][CHUNK]; the epilogue's exchange buffer afterwards
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wgrp = wave / 3, xi = wave - 3 * wgrp;        // group of three plane-row waves
-    const int sub = wgrp >> 1, grp = wgrp & 1;              // KIND 2: (py, px); KIND 1: (tile-row half, column half)
-    const int l31 = lane & 31, h = lane >> 5;
-    int mt_, nt_, z_;
-    tile_coords(P, mt_, nt_, z_);
-    const int py = KIND == 2 ? sub : 0;
-    const int mb = KIND == 1 ? sub : 0;
-    const int n0 = nt_ * BNW + (KIND == 1 ? 64 * grp : 0);      // first output column of this wave
-    const int tiles_x = P.Wo / WINO_PW, tiles_y = P.Ho / TPH;
-    const int n = mt_ / (tiles_x * tiles_y);
-    const int trem = mt_ - n * (tiles_x * tiles_y);
-    const int y0 = (trem / tiles_x) * TPH, x0 = (trem % tiles_x) * WINO_PW;
-
-    // halo slots of this thread (conv_wino2_kernel's): staged row hy / column hx of channel quad q
-    // KIND 1: the source pixel of slot j in phase (phy, phx) is (reflect1(2 (y0 + hy) - phy), reflect1(2 (x0 + hx) - phx)).  Reflection
-    // only ever moves row 2 (y0 + hy) = H to H - 2 (phy = 0) and row -1 to 1 (phy = 1), so the four pixels of a slot are
-    // spix + phy * (+-W) + phx * (+-1): one register per slot and one sign pair, instead of two reflections per load (r04: ~14
-    // VALU per staging load, VERDICT r04 weak #4).
-    const int q = tid & 3;
+    const W2Tile T = w2_tile<KIND>(P);
+    const int xi = T.xi, l31 = T.l31, h = T.h;
+    const int q = T.tid & 3;
     unsigned spix[APT];
-    // sdpack: the LDS float index of slot j in image 0 in bits 16 j .. 16 j + 13 (< 2 * CHUNK < 2^14) and, KIND 1, two sign bits per
-    // slot above it: bit 16 j + 15: phase row 1 lies BELOW row 0 (+W), bit 16 j + 14: phase column 1 lies RIGHT of column 0 (+1)
+    float smask[APT];
+    // sdpack: the LDS float index of slot j in image 0 in bits 16 j .. 16 j + 13 (< 2 * CHUNK < 2^14)
     unsigned sdpack = 0;
-    float smask[KIND == 2 ? APT : 1];
     static_assert(2 * CHUNK < (1 << 14) && APT <= 2, "slot indices are packed into 14 bits each");
 #pragma unroll
     for (int j = 0; j < APT; j++) {
-        int s = tid + W2_THREADS * j;
-        if (s >= SLOTS) s -= SLOTS;
-        static_assert(SLOTS % 4 == 0, "the wrapped slot keeps the channel quad");
-        const int hp = s >> 2;
-        const int hy = hp / W2_HW, hx = hp - hy * W2_HW;
-        if (KIND == 2) {
-            int iy = y0 - 1 + hy, ix = x0 - 1 + hx;
-            const bool inside = iy >= 0 && iy < P.H && ix >= 0 && ix < P.W;
-            smask[j] = inside ? 1.f : 0.f;
-            iy = min(max(iy, 0), P.H - 1); ix = min(max(ix, 0), P.W - 1);
-            spix[j] = (unsigned)(iy * P.W + ix);
-        } else {
-            const int ry = 2 * (y0 + hy), cx = 2 * (x0 + hx);
-            const int r0 = reflect1(ry, P.H), r1 = reflect1(ry - 1, P.H), c0 = reflect1(cx, P.W), c1 = reflect1(cx - 1, P.W);
-            spix[j] = (unsigned)(r0 * P.W + c0);
-            sdpack |= (unsigned)((r1 > r0 ? 2 : 0) | (c1 > c0 ? 1 : 0)) << (16 * j + 14);
-        }
+        const W2Slot S = w2_slot<KIND>(P, T, j);
+        spix[j] = S.spix;
+        smask[j] = S.mask;
         // channel quad q = pair q of the block: plane (q, h = 0) takes channels (4 q, 4 q + 2), plane (q, 1) takes (4 q + 1, 4 q + 3)
-        sdpack |= (unsigned)((2 * q) * PLANE + hy * W2P_ROWQ + 2 * hx) << (16 * j);
+        sdpack |= (unsigned)((2 * q) * PLANE + S.hy * W2P_ROWQ + 2 * S.hx) << (16 * j);
     }
 
     const int nchunks = P.chunks_per_tap;
     const int per_split = (nchunks + P.splitk - 1) / P.splitk;
-    const int c_begin = z_ * per_split, c_end = min(nchunks, c_begin + per_split);
-    const int kb_begin = c_begin * NPH, kb_end = c_end * NPH;   // K blocks: (chunk, phase)
-    struct ChunkSrc { __amdgpu_buffer_rsrc_t rsrc; unsigned C; unsigned soff; int act; int phy, phx; float4 sc, sh; };
-    auto block_src = [&](int kb) {
-        ChunkSrc cs;
-        const int c = kb / NPH;
-        cs.phy = (kb % NPH) >> 1; cs.phx = (kb % NPH) & 1;
-        const int s = c < P.chunks0 ? 0 : 1;
-        const int cc = (c - (s ? P.chunks0 : 0)) * BK;
-        cs.C = (unsigned)P.src_c[s];
-        cs.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.src_data[s] + (size_t)n * P.H * P.W * cs.C), 0,
-                                                    0x7fffffff, 0x27000);
-        cs.soff = (unsigned)cc * 4u;
-        cs.act = P.src_act[s];
-        cs.sc = make_float4(1.f, 1.f, 1.f, 1.f);
-        cs.sh = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (P.src_scale[s]) cs.sc = *reinterpret_cast<const float4*>(P.src_scale[s] + (size_t)n * cs.C + cc + 4 * q);
-        if (P.src_shift[s]) cs.sh = *reinterpret_cast<const float4*>(P.src_shift[s] + (size_t)n * cs.C + cc + 4 * q);
-        return cs;
-    };
-    auto load_a = [&](const ChunkSrc& cs, int j) {
-        unsigned pixel = spix[j];
-        if (KIND == 1) {
-            if (cs.phy) pixel += (sdpack >> (16 * j + 15)) & 1u ? (unsigned)P.W : 0u - (unsigned)P.W;
-            if (cs.phx) pixel += (sdpack >> (16 * j + 14)) & 1u ? 1u : ~0u;
-        }
-        const unsigned voff = (pixel * cs.C + 4u * (unsigned)q) * 4u;
-        return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(cs.rsrc, (int)voff, (int)cs.soff, 0));
-    };
-    auto store_a = [&](const ChunkSrc& cs, float4 v, int j, float* a) {
-        float x = apply_act(v.x * cs.sc.x + cs.sh.x, cs.act);
-        float y = apply_act(v.y * cs.sc.y + cs.sh.y, cs.act);
-        float z = apply_act(v.z * cs.sc.z + cs.sh.z, cs.act);
-        float w = apply_act(v.w * cs.sc.w + cs.sh.w, cs.act);
-        if (KIND == 2) { x *= smask[j]; y *= smask[j]; z *= smask[j]; w *= smask[j]; }     // exactly 0 outside, not act(shift)
-        *reinterpret_cast<float2*>(a) = make_float2(x, z);              // lane half 0: channels 4 q, 4 q + 2 (steps 2 q, 2 q + 1)
-        *reinterpret_cast<float2*>(a + PLANE) = make_float2(y, w);      // lane half 1: channels 4 q + 1, 4 q + 3
+    const int c_begin = T.z * per_split, c_end = min(nchunks, c_begin + per_split);
+    const int kb_begin = c_begin, kb_end = c_end;               // K blocks: one per chunk
+    auto block_src = [&](int kb) { return w2_block_src<KIND>(P, T.n, q, kb); };
+    auto load_a = [&](const W2Src& cs, int j) { return w2_load_halo<KIND>(P, cs, spix[j], 0u, 0, q); };
+    auto store_a = [&](const W2Src& cs, float4 v, int j, float* a) {
+        const float4 u = w2_normalize<KIND>(cs, v, smask[j]);
+        *reinterpret_cast<float2*>(a) = make_float2(u.x, u.z);              // lane half 0: channels 4 q, 4 q + 2 (steps 2 q, 2 q + 1)
+        *reinterpret_cast<float2*>(a + PLANE) = make_float2(u.y, u.w);      // lane half 1: channels 4 q + 1, 4 q + 3
     };
 
-    // transformed weights of this column tile: [pair][group][xi][h][32 columns][12 = step in pair, column half, plane]
-    const int npairs = nchunks * NPH * 4;
+    // transformed weights of this column tile: [pair][class][xi][h][32 columns][12 = step in pair, column half, plane]
+    const int npairs = nchunks * 4;
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.weight_wino), 0, 0x7fffffff, 0x27000);
     const unsigned bvoff = (unsigned)(h * 32 + l31) * 48u;
-    unsigned bsoff = ((unsigned)nt_ * (unsigned)(npairs + W2P_PAD_PAIRS) + (unsigned)(kb_begin * 4)) * (unsigned)PAIR_BYTES +
-                     (unsigned)((KIND == 2 ? wgrp : grp) * 3 + xi) * 3072u;
+    unsigned bsoff = ((unsigned)T.nt * (unsigned)(npairs + W2P_PAD_PAIRS) + (unsigned)(kb_begin * 4)) * (unsigned)PAIR_BYTES +
+                     (unsigned)(T.wgrp * 3 + xi) * 3072u;
     // the 48 bytes of a pair are three quads; quad Q of a K block (12 per block) is requested while quad Q - W2P_AHEAD is being
     // consumed — a look-ahead of 4 W2P_AHEAD MFMAs — into a ring of W2P_RING quad registers (4: 16 VGPRs).  12 quads are a whole
     // number of turns of the ring: every block starts at ring position 0.
@@ -171,7 +104,7 @@ conv_wino2p_kernel(const ConvParams P) {
     };
 
     const int ty = l31 >> 3, tx = l31 & 7;
-    const int row0 = KIND == 2 ? 2 * ty + py : 2 * (4 * mb + ty);       // first patch row of this lane's tile in the staged image
+    const int row0 = 2 * ty + T.py;                                     // first patch row of this lane's tile in the staged image
     const float* rbase = As + h * PLANE + row0 * W2P_ROWQ + 4 * tx;     // + 2 px (floats), + row * ROWQ, + 2 P * PLANE: immediates
 
     floatx16 acc[6];            // [plane nu][column half]
@@ -181,7 +114,7 @@ conv_wino2p_kernel(const ConvParams P) {
         for (int g = 0; g < 16; g++) acc[p][g] = 0.0f;
 
     if (kb_begin < kb_end) {
-        const ChunkSrc cs = block_src(kb_begin);
+        const W2Src cs = block_src(kb_begin);
 #pragma unroll
         for (int j = 0; j < APT; j++) store_a(cs, load_a(cs, j), j, As + ((sdpack >> (16 * j)) & 0x3fffu));
     }
@@ -189,7 +122,7 @@ conv_wino2p_kernel(const ConvParams P) {
     for (int k = 0; k < W2P_AHEAD; k++) wq[k] = load_quad(k % 3);
     __syncthreads();
 
-    // the K loop, instantiated per column parity of the class (KIND 2: px) and per plane row xi
+    // the K loop, instantiated per column parity of the class (px) and per plane row xi
     auto k_loop = [&](auto PXC, auto XIC) {
         constexpr int px = decltype(PXC)::value, XI = decltype(XIC)::value;
         constexpr int ROW_A = (XI == 0 ? 0 : 1) * W2P_ROWQ + 2 * px, ROW_C = (XI == 2 ? 2 : 1) * W2P_ROWQ + 2 * px;
@@ -229,7 +162,7 @@ conv_wino2p_kernel(const ConvParams P) {
         int nxt_off = CHUNK;                    // offset of the image being staged (wave-uniform): the other image
         auto block_body = [&](auto NEXT, int kb) {
             constexpr bool next_block = decltype(NEXT)::value;
-            const ChunkSrc csn = block_src(next_block ? kb + 1 : kb);
+            const W2Src csn = block_src(next_block ? kb + 1 : kb);
             float4 avr[APT];
 #pragma unroll
             for (int pp = 0; pp < 4; pp++) {
@@ -280,181 +213,41 @@ conv_wino2p_kernel(const ConvParams P) {
         else if (xi == 1) k_loop(PXC, std::integral_constant<int, 1>{});
         else k_loop(PXC, std::integral_constant<int, 2>{});
     };
-    if (KIND == 2 && grp == 1) k_loop_xi(std::integral_constant<int, 1>{});
+    if (T.grp == 1) k_loop_xi(std::integral_constant<int, 1>{});
     else k_loop_xi(std::integral_constant<int, 0>{});
 
-    // ---- epilogue: conv_wino2_kernel's ----
-    float2 rr[16][2];
-#pragma unroll
-    for (int g = 0; g < 16; g++)
-#pragma unroll
-        for (int nb = 0; nb < 2; nb++) {
-            rr[g][nb].x = acc[0 + nb][g] + acc[2 + nb][g];
-            rr[g][nb].y = acc[2 + nb][g] - acc[4 + nb][g];
-        }
-    float2 y0v[6][2], y1v[6][2];        // [row][half]; waves 1, 2 use five rows
-    float2* xb = reinterpret_cast<float2*>(As);             // [wave][<= 11 rows it does not finish][lane]
-    const int wbase = wgrp * 3;
-    auto finish = [&](auto F) {
-        constexpr int f = decltype(F)::value;
-        constexpr int G0[3] = {0, 6, 11}, G1[3] = {6, 11, 16};
-#pragma unroll
-        for (int nb = 0; nb < 2; nb++) {
-            __syncthreads();        // round 0: every wave is done with the halo; round 1: with the previous exchange
-            int k = 0;
-#pragma unroll
-            for (int g = 0; g < 16; g++) {
-                if (g >= G0[f] && g < G1[f]) continue;
-                xb[((wbase + f) * 11 + k) * 64 + lane] = rr[g][nb];
-                k++;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int g = G0[f]; g < G1[f]; g++) {
-                float2 R[3];
-#pragma unroll
-                for (int o = 0; o < 3; o++) {
-                    if (o == f) { R[o] = rr[g][nb]; continue; }
-                    const int ko = g < G0[o] ? g : g - (G1[o] - G0[o]);
-                    R[o] = xb[((wbase + o) * 11 + ko) * 64 + lane];
-                }
-                y0v[g - G0[f]][nb] = make_float2(R[0].x + R[1].x, R[0].y + R[1].y);
-                y1v[g - G0[f]][nb] = make_float2(R[1].x - R[2].x, R[1].y - R[2].y);
-            }
-        }
-    };
-    if (xi == 0) finish(std::integral_constant<int, 0>{});
-    else if (xi == 1) finish(std::integral_constant<int, 1>{});
-    else finish(std::integral_constant<int, 2>{});
-    const int g0 = xi == 0 ? 0 : (xi == 1 ? 6 : 11), ng = xi == 0 ? 6 : 5;
-
-    float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < 6; k++)
-#pragma unroll
-        for (int nb = 0; nb < 2; nb++) {
-            if (k < ng) {
-                s1[nb] += y0v[k][nb].x + y0v[k][nb].y + y1v[k][nb].x + y1v[k][nb].y;
-                s2[nb] += y0v[k][nb].x * y0v[k][nb].x + y0v[k][nb].y * y0v[k][nb].y + y1v[k][nb].x * y1v[k][nb].x +
-                          y1v[k][nb].y * y1v[k][nb].y;
-            }
-        }
-    float* red = As + (2 * CHUNK > W2_XCHG ? 2 * CHUNK : W2_XCHG);        // [12 waves][64 columns][2], behind the exchange buffer
-    int* flag = reinterpret_cast<int*>(red + 12 * 64 * 2);
-    const bool with_stats = P.stats != nullptr && P.splitk == 1;
-    if (with_stats) {
-#pragma unroll
-        for (int nb = 0; nb < 2; nb++) {
-            s1[nb] += __shfl_xor(s1[nb], 32, 64);
-            s2[nb] += __shfl_xor(s2[nb], 32, 64);
-            if (h == 0) {
-                red[(wave * 64 + 32 * nb + l31) * 2 + 0] = s1[nb];
-                red[(wave * 64 + 32 * nb + l31) * 2 + 1] = s2[nb];
-            }
-        }
-        __syncthreads();
-        if (tid < BNW) {
-            const int col = nt_ * BNW + tid;
-            if (col < P.c_out) {
-                double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-                for (int w = 0; w < 12; w++) {
-                    if (KIND == 1 && ((w / 3) & 1) != (tid >> 6)) continue;
-                    t1 += (double)red[(w * 64 + (tid & 63)) * 2 + 0];
-                    t2 += (double)red[(w * 64 + (tid & 63)) * 2 + 1];
-                }
-                double* st = stat_slot(P, n, col);
-                atomicAdd(st + 0, t1);
-                atomicAdd(st + 1, t2);
-            }
-        }
-    }
-    BnArrival arr = {nullptr, 0u};
-    const bool bn = with_stats && P.arrive;
-    if (bn) arr = bn_arrive(P, n, tid);
-    {
-        constexpr int XM = KIND == 2 ? 2 : 1;       // transposed conv: this parity class writes every other pixel
-        const int Y00 = XM * (y0 + 8 * mb) + (KIND == 2 ? py : 0), X00 = XM * x0 + (KIND == 2 ? grp : 0);
-        float* base = P.out + (size_t)z_ * P.slab_stride + (((size_t)n * P.OH + Y00) * P.OW + X00) * P.c_out_pad + n0;
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x27000);
-        const unsigned cp4 = (unsigned)P.c_out_pad * 4u;
-        unsigned voff[2];
-#pragma unroll
-        for (int nb = 0; nb < 2; nb++)
-            voff[nb] = (n0 + 32 * nb + l31 < P.c_out_pad) ? (unsigned)(XM * 8 * h) * cp4 + (unsigned)(32 * nb + l31) * 4u : 0x7fffffffu;
-#pragma unroll
-        for (int k = 0; k < 6; k++) {
-            if (k >= ng) continue;
-            const int g = g0 + k;
-            const int tyr = g >> 2, txr = g & 3;
-#pragma unroll
-            for (int e = 0; e < 2; e++)
-#pragma unroll
-                for (int f = 0; f < 2; f++)
-#pragma unroll
-                    for (int nb = 0; nb < 2; nb++) {
-                        const unsigned soff = (unsigned)(XM * ((2 * tyr + e) * P.OW + 2 * txr + f)) * cp4;
-                        const float2 yy = e ? y1v[k][nb] : y0v[k][nb];
-                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(f ? yy.y : yy.x), rsrc, (int)voff[nb], (int)soff, WINO_OUT_AUX);
-                    }
-        }
-    }
-    if (bn) bn_complete(P, arr, n, tid, flag);
+#include "conv_wino2_epilogue.inc"
 }
 
-// Transformed weights as pack_weight_wino2_kernel computes them, in the pair layout: i enumerates
-// [column tile][pair-step][group][xi][h][32 columns][12 = e (step of the pair), nb (column half), nu (plane)]; K step 2 pair + e of
-// block kb = step >> 3 holds the padded input channels chunk * 16 + 2 s + h (s = step & 7); the W2P_PAD_PAIRS pair-steps behind the
-// last one are zeros.
+// conv_wino2p_kernel's weight image: i enumerates [column tile][pair-step][class grp][xi][h][32 columns][12 = e (step of the pair),
+// nb (column half), nu (plane)]; K step 2 pair + e = 8 chunk + s holds the padded input channels chunk * 16 + 2 s + h; the
+// W2P_PAD_PAIRS pair-steps behind the last one are zeros.
 __global__ void __launch_bounds__(256)
 pack_weight_wino2p_kernel(rnr_conv_desc d, const float* __restrict__ w, float* __restrict__ image, long total) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
-    const bool transposed = d.kind == RNR_CONVT4x4S2;
-    const int nph = transposed ? 1 : 4, ngrp = transposed ? 4 : 2;
-    const int npairs = (d.c_in0_pad + d.c_in1_pad) / 4 * nph;
+    const int npairs = (d.c_in0_pad + d.c_in1_pad) / 4;
     const int w12 = (int)(i % 12);
     const int nu = w12 % 3, nb = (w12 / 3) & 1, e = w12 / 6;
     long r = i / 12;
     const int col = (int)(r & 31); r >>= 5;
     const int hh = (int)(r & 1); r >>= 1;
     const int xi = (int)(r % 3); r /= 3;
-    const int grp = (int)(r % ngrp); r /= ngrp;
+    const int grp = (int)(r % 4); r /= 4;
     const int pstep = (int)(r % (npairs + W2P_PAD_PAIRS));
     const int nt = (int)(r / (npairs + W2P_PAD_PAIRS));
     if (pstep >= npairs) { image[i] = 0.0f; return; }
     const int step = 2 * pstep + e;
-    const int kb = step >> 3, s = step & 7;
-    const int chunk = kb / nph, phase = kb % nph;
-    const int c = chunk * 16 + 2 * s + hh;
-    const int co = transposed ? nt * 64 + nb * 32 + col : nt * 128 + grp * 64 + nb * 32 + col;
-    double g[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++) {
-            if (transposed) {
-                g[a][b] = (double)gemm_weight(d, w, grp, (1 - a) * 2 + (1 - b), c, co);
-            } else {
-                const int phy = phase >> 1, phx = phase & 1;
-                const int ky = phy ? 2 * a : 1 + 2 * a, kx = phx ? 2 * b : 1 + 2 * b;
-                g[a][b] = (double)gemm_weight(d, w, 0, ky * 4 + kx, c, co);
-            }
-        }
-    double row[2];
-#pragma unroll
-    for (int b = 0; b < 2; b++) row[b] = xi == 0 ? g[0][b] : (xi == 2 ? g[1][b] : g[0][b] + g[1][b]);
-    const double u = nu == 0 ? row[0] : (nu == 2 ? row[1] : row[0] + row[1]);
-    image[i] = (float)u;
+    const int c = (step >> 3) * 16 + 2 * (step & 7) + hh;
+    image[i] = w2_weight<2>(d, w, grp, 0, xi, nu, c, nt * 64 + nb * 32 + col);
 }
 
-template <int KIND>
 static void launch_wino2p(const dim3 grid, const ConvParams& P, hipStream_t st) {
     static bool attr_set = false;
     if (!attr_set) {         // > 64 KiB of dynamic LDS needs the opt-in
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino2p_kernel<KIND>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)wino2p_lds_bytes<KIND>());
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino2p_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)wino2p_lds_bytes());
         attr_set = true;
     }
-    hipLaunchKernelGGL((conv_wino2p_kernel<KIND>), grid, dim3(W2_THREADS), wino2p_lds_bytes<KIND>(), st, P);
+    hipLaunchKernelGGL((conv_wino2p_kernel<2>), grid, dim3(W2_THREADS), wino2p_lds_bytes(), st, P);
 }

@@ -56,17 +56,14 @@ constexpr int W4_BN = 64;
 #endif
 constexpr int W4_BDIST = W4_BDIST_K;                // K steps between the request of a weight block and its MFMAs (ring of 2 for 1, of 4 above)
 constexpr int W4_BRING = W4_BDIST == 1 ? 2 : 4;
-#ifndef W4_BN_LDS
-#define W4_BN_LDS 1                 // 1 (r05): the staging steps of the K loop read BatchNorm scale / shift of their channel from an LDS table
-                                    // (one ds_read_b64 per channel) instead of holding two float4 per thread across the chunk: 8 registers
-                                    // for the weight ring; 0: the r04 form
-#endif
 #ifndef W4_PREFETCH
 #define W4_PREFETCH 256             // > 0: the epilogue touches the first halo image of block + W4_PREFETCH's tile (behind the K loop); 0: off
 #endif
 #ifndef W4_PF_TOUCH
 #define W4_PF_TOUCH 2               // dwords touched per halo pixel, 128 bytes apart (profiles/r05_tile_prefetch_ab.txt: 1 / 2 / 4)
 #endif
+// (r05) the staging steps of the K loop read BatchNorm scale / shift of their channel from an LDS table (one ds_read_b64 per
+// channel) instead of holding two float4 per thread across the chunk: 8 registers for the weight ring
 constexpr int W4_BN_MAXC = 1024;                    // channels the table holds (both sources)
 constexpr int W4_STEP_FLOATS = 6 * 2 * 2 * 32 * 6;  // weight image per (column tile, K step): [xi][half][h][32][6]
 constexpr int W4_XCHG = 12 * 14 * 64 * 2;           // floats of one exchange round: [wave][<= 14 register rows it does not finish][lane][2]
@@ -76,7 +73,7 @@ constexpr float W4_A = 0.75f, W4_B = 1.5f, W4_A2 = 0.5625f, W4_B2 = 2.25f, W4_A3
 constexpr float W4_A2B2 = 1.265625f, W4_A2PB2 = 2.8125f;
 
 __host__ __device__ constexpr size_t wino4_lds_bytes() {
-    return (size_t)(2 * W4_CHUNK + 12 * 32 * 2 + 4 + (W4_BN_LDS ? 2 * W4_BN_MAXC : 0)) * sizeof(float);
+    return (size_t)(2 * W4_CHUNK + 12 * 32 * 2 + 4 + 2 * W4_BN_MAXC) * sizeof(float);
 }
 
 // B^T applied to six values (both directions of the input transform)
@@ -122,12 +119,9 @@ conv_wino4_kernel(const ConvParams P) {
     const bool stager = tid < W4_ITEMS;
     const int sit = stager ? tid >> 2 : 0;
     const int sty = sit / W4_HW, shx = sit - sty * W4_HW;
-#ifndef W4_SPIX1
-#define W4_SPIX1 1                  // 1 (r05): one base pixel + two reflection flags instead of six halo-row pixel registers
-#endif
-    // source pixels of the six halo rows 4 sty - 1 + r of column x0 - 1 + shx.  Rows 1 .. 4 of an item are never reflected (4 sty .. 4 sty + 3
-    // lie inside the map), so they are spix1 + (r - 1) W; row 0 reflects to spix1 + W at the top border, row 5 to spix1 + 2 W at the bottom
-#if W4_SPIX1
+    // source pixels of the six halo rows 4 sty - 1 + r of column x0 - 1 + shx, as one base pixel + two reflection flags (r05; six
+    // halo-row pixel registers before).  Rows 1 .. 4 of an item are never reflected (4 sty .. 4 sty + 3 lie inside the map), so they
+    // are spix1 + (r - 1) W; row 0 reflects to spix1 + W at the top border, row 5 to spix1 + 2 W at the bottom
     unsigned spix1, sflags;
     {
         const int ix = reflect1(x0 - 1 + shx, P.W);
@@ -140,16 +134,6 @@ conv_wino4_kernel(const ConvParams P) {
         if (r == 5) return (packed & (1u << 15)) ? spix1 + 2u * (unsigned)P.W : spix1 + 4u * (unsigned)P.W;
         return spix1 + (unsigned)((r - 1) * P.W);
     };
-#else
-    unsigned spix[6];
-    {
-        const int ix = reflect1(x0 - 1 + shx, P.W);
-#pragma unroll
-        for (int r = 0; r < 6; r++) spix[r] = (unsigned)(reflect1(y0 - 1 + 4 * sty + r, P.H) * P.W + ix);
-    }
-    auto spix_of = [&](int r, unsigned) { return spix[r]; };
-    const unsigned sflags = 0;
-#endif
     const unsigned sdst = (unsigned)((4 * q) * W4_PLANE + sty * W4_ROWP + shx) | sflags;      // + xi * 4 * W4_ROWP per result, + k * W4_PLANE per channel
 
     // split-K (small grids, e.g. the 128^2 / 64^2 layers at one view per call): slice z_ of P.splitk takes the chunks
@@ -159,7 +143,7 @@ conv_wino4_kernel(const ConvParams P) {
     const int per_split = (nchunks + P.splitk - 1) / P.splitk;
     const int c_begin = z_ * per_split, c_end = min(nchunks, c_begin + per_split);
     struct ChunkSrc { __amdgpu_buffer_rsrc_t rsrc; unsigned C; unsigned soff; int act; float4 sc, sh; const float2* bn; };
-    float2* s_bn = reinterpret_cast<float2*>(As + 2 * W4_CHUNK + 12 * 32 * 2 + 4);        // [padded input channel] (scale, shift), W4_BN_LDS
+    float2* s_bn = reinterpret_cast<float2*>(As + 2 * W4_CHUNK + 12 * 32 * 2 + 4);        // [padded input channel] (scale, shift)
     auto chunk_src = [&](int c, bool in_loop) {
         ChunkSrc cs;
         const int s = c < P.chunks0 ? 0 : 1;
@@ -172,7 +156,7 @@ conv_wino4_kernel(const ConvParams P) {
         cs.sc = make_float4(1.f, 1.f, 1.f, 1.f);
         cs.sh = make_float4(0.f, 0.f, 0.f, 0.f);
         cs.bn = s_bn + c * BK + 4 * q;
-        if (!(W4_BN_LDS && in_loop)) {
+        if (!in_loop) {
             if (P.src_scale[s]) cs.sc = *reinterpret_cast<const float4*>(P.src_scale[s] + (size_t)n * cs.C + cc + 4 * q);
             if (P.src_shift[s]) cs.sh = *reinterpret_cast<const float4*>(P.src_shift[s] + (size_t)n * cs.C + cc + 4 * q);
         }
@@ -187,7 +171,7 @@ conv_wino4_kernel(const ConvParams P) {
         constexpr int k = decltype(KC)::value;
         float sc = k == 0 ? cs.sc.x : k == 1 ? cs.sc.y : k == 2 ? cs.sc.z : cs.sc.w;
         float sh = k == 0 ? cs.sh.x : k == 1 ? cs.sh.y : k == 2 ? cs.sh.z : cs.sh.w;
-        if (W4_BN_LDS && in_loop) { const float2 t = cs.bn[k]; sc = t.x; sh = t.y; }
+        if (in_loop) { const float2 t = cs.bn[k]; sc = t.x; sh = t.y; }
         float d[6], o[6];
 #pragma unroll
         for (int r = 0; r < 6; r++) {
@@ -203,12 +187,10 @@ conv_wino4_kernel(const ConvParams P) {
     // transformed weights of this column tile: [K step][xi][half] blocks of 384 floats ([lane = h * 32 + column][planes 0..3], then [lane][planes 4, 5]); the image carries W4_BDIST K
     // steps of padding behind the last one, so the look-ahead needs no clamp
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.weight_wino), 0, 0x7fffffff, 0x27000);
-#ifndef W4_WSPLIT
-#define W4_WSPLIT 1                 // 1: the 1536-byte block of a wave and K step is [64 lanes][planes 0..3] then [64 lanes][planes 4, 5]: both loads of a
-                                    // K step read consecutive lanes' consecutive bytes (8 + 4 cache lines instead of 12 + 12 at a lane stride of 24 bytes)
-#endif
-    const unsigned bvoff = W4_WSPLIT ? (unsigned)(h * 32 + l31) * 16u : (unsigned)(h * 32 + l31) * 24u;
-    const unsigned bvoff_hi = W4_WSPLIT ? 1024u + (unsigned)(h * 32 + l31) * 8u : bvoff + 16u;
+    // the 1536-byte block of a wave and K step is [64 lanes][planes 0..3] then [64 lanes][planes 4, 5]: both loads of a K step read
+    // consecutive lanes' consecutive bytes (8 + 4 cache lines instead of 12 + 12 at a lane stride of 24 bytes)
+    const unsigned bvoff = (unsigned)(h * 32 + l31) * 16u;
+    const unsigned bvoff_hi = 1024u + (unsigned)(h * 32 + l31) * 8u;
     unsigned bsoff = ((unsigned)nt_ * (unsigned)(nchunks * 8 + W4_BDIST) + (unsigned)(c_begin * 8)) * (unsigned)(W4_STEP_FLOATS * 4) +
                      (unsigned)((xi * 2 + nbh) * 2) * 768u;
     typedef float floatx2 __attribute__((ext_vector_type(2)));
@@ -253,7 +235,7 @@ conv_wino4_kernel(const ConvParams P) {
     BRegs breg[W4_BRING];
 #pragma unroll
     for (int k = 0; k < W4_BDIST; k++) load_b(breg[k]);
-    if (W4_BN_LDS) {        // the table of this view: every padded input channel of both sources
+    {                       // the BatchNorm table of this view: every padded input channel of both sources
         const int ctot = nchunks * BK;
         for (int ch = tid; ch < ctot; ch += W4_THREADS) {
             const int sidx = ch < P.chunks0 * BK ? 0 : 1;
@@ -476,14 +458,10 @@ pack_weight_wino4_kernel(rnr_conv_desc d, const float* __restrict__ w, float* __
     // block of a (K step, xi, column half): 384 floats
     const int wb = (int)(i % 384);
     long r = i / 384;
-    int nu, col, hh;
-    if (W4_WSPLIT) {        // [64 lanes][planes 0..3], then [64 lanes][planes 4, 5]; lane = h * 32 + column
-        const int ln = wb < 256 ? wb >> 2 : (wb - 256) >> 1;
-        nu = wb < 256 ? wb & 3 : 4 + ((wb - 256) & 1);
-        col = ln & 31; hh = ln >> 5;
-    } else {                // [h][32 columns][6 planes]
-        nu = wb % 6; col = (wb / 6) & 31; hh = wb / 192;
-    }
+    // [64 lanes][planes 0..3], then [64 lanes][planes 4, 5]; lane = h * 32 + column
+    const int ln = wb < 256 ? wb >> 2 : (wb - 256) >> 1;
+    const int nu = wb < 256 ? wb & 3 : 4 + ((wb - 256) & 1);
+    const int col = ln & 31, hh = ln >> 5;
     const int nb = (int)(r & 1); r >>= 1;
     const int xi = (int)(r % 6); r /= 6;
     const int step = (int)(r % (nsteps + W4_BDIST));

@@ -59,7 +59,7 @@ def run_conv(kind, srcs, weight, c_out, N, H, W, flags=0):
 
 
 def run_conv_fused(kind, srcs, weight, c_out, N, H, W, gamma=None, beta=None, flags=0, repeats=1):
-    """The product entry point rnr_conv2d_fused (one launch: convolution + BatchNorm finalise + shallow split-K combine).
+    """The product entry point rnr_conv2d_fused (convolution + BatchNorm finalise: in the launch, or a launch of its own behind split-K).
     Returns (out_raw, scale, shift, sync buffer) as CPU tensors; `repeats` > 1 re-runs the call on the same sync buffer."""
     from rnr_amd import _lib
     from rnr_amd.ops import _ptr, _stream
@@ -213,21 +213,6 @@ CASES = [
     (0, 1, 512, 512, [16], 128),       # enough tiles for the 256x128 fp32 config (two waves per SIMD)
     (2, 1, 256, 256, [16, 16], 128),   # the same for the transposed conv, concat input
 ]
-
-
-def test_conv_fused_with_in_launch_combine_opt_in():
-    """The in-launch split-K combine is off by default since r06 (slabs + reduce kernel measured faster at one view per call);
-    RNR_CONV_COMBINE=1 turns it on.  The library reads the switch once per process, so the split cases of the test above run
-    again in a process of their own with the switch set: same bit-exact comparisons."""
-    import os
-    import subprocess
-    import sys
-    env = dict(os.environ, RNR_CONV_COMBINE='1')
-    p = subprocess.run([sys.executable, '-m', 'pytest', __file__, '-m', 'gpu', '-x', '-q', '-k',
-                        'test_conv_fused_equals_separate_launches and (cins0 or cins1 or cins2 or cins3 or cins5)'], env=env, capture_output=True, text=True,
-                       timeout=600)
-    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
-    assert ' passed' in p.stdout and 'deselected' in p.stdout
 
 
 @pytest.mark.parametrize('kind,N,H,W,cins,c_out', CASES)
@@ -717,8 +702,8 @@ def test_conv_winograd_f4x4_vs_torch(N, H, W, cins, c_out, algo):
 @pytest.mark.parametrize('N,H,W,cins,c_out', [(1, 64, 64, [512], 512), (1, 128, 128, [256], 256), (16, 64, 64, [64], 128)])
 def test_conv_winograd_f4x4_legacy_entry_point_and_combine_ab(N, H, W, cins, c_out, monkeypatch):
     """F(4x4, 3x3) through the legacy entry point rnr_conv2d (statistics into a caller buffer; a split grid writes slabs that
-    splitk_reduce_kernel adds) against float64, and — for the split grids — the product entry point's in-launch combine against
-    it: the same partial tiles are added in the same slice order, so out_raw is BIT-identical between the two paths."""
+    splitk_reduce_kernel adds) against float64, and the product entry point rnr_conv2d_fused against it: the same partial
+    tiles are added in the same slice order, so out_raw is BIT-identical between the two paths."""
     from rnr_amd import _lib
     g = torch.Generator().manual_seed(4400 + H + c_out)
     srcs = [(torch.randn(N, C, H, W, generator=g), torch.rand(N, C, generator=g) + 0.5, torch.randn(N, C, generator=g) * 0.3, 1)
