@@ -380,7 +380,9 @@ shade_inputs_kernel(const ShadeParams P) {
     for (int i = tid; i < n4; i += SH_THREADS) dst[i] = src[i];
     if (P.neural_img) {  // [N, C, H, W] copy for the API (TextureMapper.forward's return value)
         const int hw = P.H * P.W;
-        for (int i = tid; i < (int)valid_pix * P.C; i += SH_THREADS) {
+        // i runs over a grid of SH_PIX pixels per channel, so the bound is SH_PIX * C even in a ragged last workgroup
+        // (valid_pix * C would stop before the last channels); the pixels past the end are masked below
+        for (int i = tid; i < SH_PIX * P.C; i += SH_THREADS) {
             const int p = i % SH_PIX, c = i / SH_PIX;
             if (p < valid_pix) {
                 const long pix = pix0 + p;
@@ -416,8 +418,11 @@ __device__ __forceinline__ float fast_atan2f(float y, float x) {
     p = __builtin_fmaf(p, s, 1.0f);
     float r = p * a;
     if (ay > ax) r = 1.57079632679489662f - r;
-    if (x < 0.0f) r = 3.14159265358979324f - r;
-    return y < 0.0f ? -r : r;
+    // quadrant from the sign BITS, as IEEE atan2 (ocml, torch.atan2) does: atan2(-0, x < 0) = -pi and atan2(+-0, -0) = +-pi.
+    // A test of y < 0 gave +pi for y = -0 — u = 1 instead of 0, the env-map tap of column W-1 instead of column 0 — on the
+    // seam direction an axis-aligned -x normal produces with the diffuse pivot (0, 0, 1)
+    if (__builtin_signbit(x)) r = 3.14159265358979324f - r;
+    return __builtin_copysignf(r, y);
 }
 __device__ __forceinline__ float fast_acosf(float x) {
     const float ax = fminf(fabsf(x), 1.0f);

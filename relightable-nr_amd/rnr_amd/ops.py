@@ -331,9 +331,10 @@ def frame_prepare(mesh, K, pose, image_size, v_uvz=None, tangents=None, lp_basis
 
 @_device_op
 def shade_inputs(gb, mesh, proj_inv, R_inv, textures, pivots_spec, pivots_diff, sh_start_ch, c_pad=None,
-                 want_rays_uv=False, want_neural_img=False, want_sh=False, net_in=None, tangents=None):
+                 want_rays_uv=False, want_neural_img=False, want_sh=False, net_in=None, tangents=None, neural_img=None):
     """G-buffer -> channel-last RenderingNet input [N,H,W,c_pad] (+ optional API copies).
-    textures: list of [1,S_l,S_l,C] or [S_l,S_l,C] device tensors; pivots_*: [3,R] CPU float tensors."""
+    textures: list of [1,S_l,S_l,C] or [S_l,S_l,C] device tensors; pivots_*: [3,R] CPU float tensors.
+    net_in / neural_img: optional output buffers ([N,H,W,c_pad] / [N,C,H,W]); a given neural_img is written."""
     L = _lib.load()
     fim, alpha, uv, nrm = gb['face_index_map'], gb['alpha'], gb['uv_map'], gb['normal_map']
     N, H, W = fim.shape
@@ -346,7 +347,11 @@ def shade_inputs(gb, mesh, proj_inv, R_inv, textures, pivots_spec, pivots_diff, 
     if net_in is None:
         net_in = torch.empty(N, H, W, c_pad, dtype=torch.float32, device=dev)
     rays_uv = torch.empty(N, H, W, 2, ns + nd, dtype=torch.float32, device=dev) if want_rays_uv else None
-    neural = torch.empty(N, C, H, W, dtype=torch.float32, device=dev) if want_neural_img else None
+    neural = neural_img
+    if neural is None and want_neural_img:
+        neural = torch.empty(N, C, H, W, dtype=torch.float32, device=dev)
+    elif neural is not None and (tuple(neural.shape) != (N, C, H, W) or not neural.is_contiguous() or neural.dtype != torch.float32):
+        raise ValueError('shade_inputs: neural_img must be a contiguous float32 [N,C,H,W] tensor')
     sh = torch.empty(N, H, W, 9, dtype=torch.float32, device=dev) if want_sh else None
     nl = len(textures)
     tex_ptrs = (ctypes.c_void_p * nl)(*[_chk(t, 'texture').data_ptr() for t in textures])

@@ -330,3 +330,71 @@ def test_frame_assembly(golden):
     assert torch.allclose(out['unet_out'], T(g['net_out']).float(), atol=2e-3)
     assert torch.allclose(out['image'], T(g['image']), atol=5e-5), (out['image'] - T(g['image'])).abs().max()
     assert orc.psnr(out['image'], T(g['image'])) > 80
+
+
+def _circular_u_close(a, b, atol):
+    """|a - b| <= atol for the u coordinate of the spherical mapping, allowing the 1.0 jump of atan2 at the seam only where the
+    two evaluations put the direction on different sides of it (|z| at rounding level)."""
+    d = (a - b).abs()
+    return torch.minimum(d, (d - 1.0).abs()) <= atol
+
+
+def test_shade64_pinned_to_oracle_and_fixtures(golden):
+    """oracle/shade64.py (the float64 reference of the shading sweeps) against the float32 oracle and the reference-generated
+    fixtures, at the fixtures' tolerances: float64 evaluation moves nothing beyond float32 rounding, and the float32 tap
+    expressions it keeps are the reference's."""
+    from oracle import shade64 as o64
+    g = golden('bilinear')
+    assert torch.allclose(o64.bilinear(T(g['data']), T(g['x']), T(g['y'])).float(), T(g['out']), atol=1e-6)
+    g = golden('texture_mapper')
+    tex = [T(g['tex%d' % i]) for i in range(4)]
+    for sh_start, key in ((6, 'out_sh6'), (3, 'out_sh3')):
+        got = o64.texture_mapper(tex, T(g['uv']), T(g['sh']), sh_start)
+        assert torch.allclose(got.float(), T(g[key]), atol=1e-6), key
+        assert torch.allclose(got.float(), orc.texture_mapper(tex, T(g['uv']), T(g['sh']), sh_start), atol=1e-6)
+    assert torch.allclose(o64.texture_mapper(tex, T(g['uv'])).float(), T(g['out_nosh']), atol=1e-6)
+    g = golden('shading_geometry64')
+    tan = o64.face_tangents(T(g['faces_v'])[0], T(g['faces_vt'])[0])
+    assert torch.allclose(tan.float(), orc.face_tangents(T(g['faces_v'])[0], T(g['faces_vt'])[0]), atol=1e-6)
+    tbn = o64.tbn_map(T(g['normal_map']), T(g['face_index_map']), tan)
+    assert torch.allclose(tbn.float(), T(g['tbn']), atol=1e-6)
+    vd, vdc = o64.view_dir_map((64, 64), T(g['proj_inv']), T(g['R_inv']))
+    assert torch.allclose(vd.float(), T(g['view_dir']), atol=1e-6) and torch.allclose(vdc.float(), T(g['view_dir_cam']), atol=1e-6)
+    alpha = T(g['alpha'])
+    for reflect, piv, tag in ((True, T(g['pivots_spec']), 'spec'), (False, T(g['pivots_diff']), 'diff')):
+        d, uv, dt = o64.ray_sampler(reflect, piv, T(g['tbn']), T(g['view_tangent']), alpha)
+        assert torch.allclose(d.float(), T(g['rays_dir_' + tag]), atol=2e-6), tag
+        ref_uv = T(g['rays_uv_' + tag])
+        assert _circular_u_close(uv[..., 0, :].float(), ref_uv[..., 0, :], 2e-6).all(), tag
+        assert torch.allclose(uv[..., 1, :].float(), ref_uv[..., 1, :], atol=2e-6), tag
+        if reflect:
+            assert torch.allclose(dt.float(), T(g['rays_dir_tangent_spec']), atol=2e-6)
+    assert torch.allclose(o64.spherical_uv(T(g['sm_dirs']), 0).float(), T(g['sm_uv']), atol=1e-7)
+    g = golden('ray_renderer')
+    out = o64.ray_renderer(T(g['albedo_specular']), T(g['rays_uv']), T(g['rays_lt']), T(g['lp']),
+                           albedo_diffuse=T(g['albedo_diffuse']), num_ray_diffuse=13, seperate_albedo=True)
+    for a, k in zip(out, ['out', 'out_specular', 'out_diffuse', 'ltt_specular', 'ltt_diffuse', 'rays_color']):
+        assert torch.allclose(a.float(), T(g[k]), atol=2e-6), k
+    out = o64.ray_renderer(T(g['albedo_specular']), T(g['rays_uv']), T(g['rays_lt']), T(g['lp']))
+    assert torch.allclose(out[0].float(), T(g['out_nodiffuse']), atol=2e-6)
+    g = golden('sh_linear')
+    assert torch.allclose(o64.sh_reconstruct(T(g['basis']), T(g['coeff'])[0]).float(), T(g['recon2']), atol=1e-5)
+    assert torch.allclose(o64.sh_fit(T(g['samples'])[0], T(g['basis'])).float(), T(g['fit2']), atol=1e-5)
+    # the assembled network input of the reference frame (frame64: the reference's own run, stored as fp16) from the
+    # reference G-buffer of view 0, and the float32 oracle on the same maps
+    gf, gm = golden('frame64'), golden('rasterizer_module64')
+    tex = [T(gf['tex%d' % i]) for i in range(4)]
+    _, ps = orc.ray_sampler_pivots(6, 2, 5)
+    _, pd = orc.ray_sampler_pivots(6, 2, 10)
+    gb = {k: T(gm['view0_' + k]) for k in ['face_index_map', 'alpha', 'uv_map', 'normal_map', 'faces_v', 'faces_vt']}
+    tan = o64.face_tangents(gb['faces_v'][0], gb['faces_vt'][0])
+    o = o64.shade_inputs(gb['face_index_map'], gb['alpha'], gb['uv_map'], gb['normal_map'], tan, T(gm['proj_inv'][:1]),
+                         T(gm['R_inv'][:1]), tex, ps, pd, 6)
+    net_in = o['net_in'].permute(0, 3, 1, 2)
+    assert torch.allclose(net_in.float(), T(gf['net_in'][:1]).float(), atol=2e-3)
+    assert torch.allclose(o['sh_basis_map'].float(), T(gf['sh_basis_map'][:1]), atol=1e-6)
+    o32 = orc.shade_inputs(gb, T(gm['proj_inv'][:1]), T(gm['R_inv'][:1]), tex, ps, pd)
+    assert torch.allclose(net_in.float(), o32['net_in'], atol=2e-5)
+    assert torch.allclose(o['neural_img'].float(), o32['neural_img'], atol=2e-5)
+    assert _circular_u_close(o['rays_uv'][..., 0, :].float(), o32['rays_uv'][..., 0, :], 2e-5).all()
+    assert torch.allclose(o['rays_uv'][..., 1, :].float(), o32['rays_uv'][..., 1, :], atol=2e-5)
