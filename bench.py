@@ -4,10 +4,13 @@
 A "step" = one pass of the full HIP hot path (projection -> rasterize -> shade inputs -> U-Net -> ray render) over
 one batch of `--views-per-step` synthetic 512x512 camera poses of the material_sphere-like scene,
 inputs resident in HBM.  `value` = views rendered by ALL ranks / max-over-ranks wall time of exactly K steps.
-Beside it, `single_view_mode`: the reference's own calling mode (test_rnr.py:265-393, one view per call, the 720
-`spiral_step720` views in order) with its own roofline block.
+A plain run does only that (set-up, pre-warm, warm-up, the timed windows, --dump-outputs, the line).  With --full it also
+measures what is reported beside the headline: box_calibration, the per-stage figures, other batch sizes, algorithms,
+precisions and stream configurations, `single_view_mode` (the reference's own calling mode, test_rnr.py:265-393, one view
+per call, the 720 `spiral_step720` views in order, with its own roofline block), config5_shape, dropin_view_loop and the
+CPU baseline.
 
-Single GPU:  python bench.py [--steps K --warmup W]
+Single GPU:  python bench.py [--steps K --warmup W] [--full]
 N GPUs:      python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
              bench.py --gpus N --steps K --warmup W       (weak scaling: every rank renders its own pose slice and the
              frames are all-gathered over RCCL each step — the only collective of the path)
@@ -51,6 +54,12 @@ def parse(argv=None):
                          'allocator, code objects); 0 = none')
     ap.add_argument('--nf0', type=int, default=64)
     ap.add_argument('--tex-ch', type=int, default=24)
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline: box_calibration around the timed windows, then (rank 0) '
+                         'the per-stage figures, the other batch sizes, algorithms, precisions and stream configurations, '
+                         'single_view_mode, config5_shape, dropin_view_loop and the CPU baseline with its parity figure; with '
+                         'N > 1 also with_8_views_per_gpu.  Without it a run sets up, warms up, times its windows, writes '
+                         '--dump-outputs and prints the line; the --no-* / --main-loop-only switches below thin out a --full run')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-parity', action='store_true')
     ap.add_argument('--tile-skip', action='store_true',
@@ -823,8 +832,8 @@ def main(argv=None):
         """What every rank's GPU sustains right now in a register-resident f32-MFMA loop (rnr_calibrate_mfma_f32, ~0.1 s):
         [TFLOP/s per rank] or None.  Outside every timed region.  Boxes of one pool differ by several per cent in the
         clock they hold under matrix load (r06: 552 / 577 / 580 frames/s from the same commit on three boxes): the
-        headline is only comparable across boxes beside this figure."""
-        if stub or args.no_calibration:
+        headline is only comparable across boxes beside this figure.  --full only."""
+        if stub or args.no_calibration or not args.full:
             return None
         from rnr_amd import ops
         tf = ops.calibrate_mfma_f32(dev, 0.1)['tflops']
@@ -883,10 +892,10 @@ def main(argv=None):
             dumped = dump_outputs(args.dump_outputs, {'frames': frames})
         del frames
     # N > 1: BASELINE configs[3]'s own batch — 8 views per GPU (64 at 8 GPUs) — through the same pipeline, gather and timing
-    # protocol, every rank taking part; reported beside the headline as with_8_views_per_gpu
+    # protocol, every rank taking part; reported beside the headline as with_8_views_per_gpu (--full)
     dt8 = None
     V8 = 8 if not stub else max(1, V // 2)
-    if use_dist and world > 1 and V > V8 and os.environ.get('RNR_BENCH_FAST') != '1':
+    if args.full and use_dist and world > 1 and V > V8 and os.environ.get('RNR_BENCH_FAST') != '1':
         from rnr_amd.dist import OverlappedFrameGather
         gather8 = OverlappedFrameGather(world, (V8, 3, args.img_size, args.img_size), torch.float32, dev)
 
@@ -998,7 +1007,7 @@ def main(argv=None):
                 'note': 'BASELINE configs[3] batch (8 views per GPU; 64 at 8 GPUs) with the same barrier + MAX-over-ranks protocol; '
                         'not the headline value'}
     if rank == 0 and not stub:
-        extras = not args.main_loop_only
+        extras = args.full and not args.main_loop_only
         fast = os.environ.get('RNR_BENCH_FAST') == '1'      # scripts/stage.sh: headline loop + per-stage figures only
         # per-stage HIP events (5 extra steps outside the timed region): the non-conv stages against the HBM roofline
         P_px = args.img_size * args.img_size
@@ -1209,7 +1218,7 @@ def main(argv=None):
                 res['dropin_view_loop'] = dropin_view_loop_block(sc, args, dev)
             except Exception as e:          # noqa: BLE001 - an extra must never fail the bench line
                 res['dropin_view_loop'] = {'error': repr(e)[:300]}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             last_id = int(ids[(args.warmup + args.steps - 1) * V + V - 1])
             hip_last = None if args.no_parity else last_frame
             cb, parity = cpu_baseline(sc, args, last_id, hip_last, emu_last)

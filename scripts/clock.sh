@@ -1,9 +1,11 @@
 #!/bin/bash
 # effective shader clock per conv kernel = GRBM_GUI_ACTIVE / 8 XCDs / kernel wall time
+# usage (from the repo root): scripts/clock.sh VARIANT...  -> bench_outputs/clock_VARIANT/
+ROOT=$PWD
 for v in "$@"; do
-  if [ "$v" != "base" ]; then export RNR_HIP_LIB=$GRAFT_REPO_ROOT/build_abl/librnr_$v.so; else unset RNR_HIP_LIB; fi
-  OUT=$GRAFT_REPO_ROOT/gpurun_out/clock_$v; mkdir -p $OUT
-  (cd /tmp; export TMPDIR=/tmp; rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --output-format csv -d $OUT -- python $GRAFT_REPO_ROOT/bench.py --views-per-step 8 --steps 3 --warmup 1 --no-cpu-baseline --no-parity > $OUT/log.txt 2>&1)
+  if [ "$v" != "base" ]; then export RNR_HIP_LIB=$ROOT/build_abl/librnr_$v.so; else unset RNR_HIP_LIB; fi
+  OUT=$ROOT/bench_outputs/clock_$v; mkdir -p $OUT
+  (cd /tmp; export TMPDIR=/tmp; rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --output-format csv -d $OUT -- python $ROOT/bench.py --full --views-per-step 8 --steps 3 --warmup 1 --no-cpu-baseline --no-parity > $OUT/log.txt 2>&1)
   python - $OUT $v <<'PY'
 import csv,glob,sys,collections
 out,v=sys.argv[1:3]

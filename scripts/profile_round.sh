@@ -45,6 +45,6 @@ done
 RNR_WINO_MIN_WGS=1 RNR_WINO2_MIN_WGS=1 timeout 600 python scripts/wino_check.py --views 2 > $OUT/${TAG}_winograd_accuracy.txt 2>&1
 RNR_WINO4_MIN_WGS=1 RNR_WINO_MIN_WGS=1 RNR_WINO2_MIN_WGS=1 timeout 600 python scripts/wino_check.py --views 2 --f4x4 > $OUT/${TAG}_winograd_f4x4_accuracy.txt 2>&1
 timeout 900 python scripts/wino_frames_720.py winograd4 > $OUT/${TAG}_winograd4_vs_direct_720views.json 2> $OUT/wf4.err
-timeout 900 python bench.py --pmc-file $OUT/${TAG}_pmc_per_kernel_f32_steps2_views16.json > $OUT/bench.log 2>&1
+timeout 900 python bench.py --full --pmc-file $OUT/${TAG}_pmc_per_kernel_f32_steps2_views16.json > $OUT/bench.log 2>&1
 grep "^{\"metric\"" $OUT/bench.log | tail -1 > $OUT/${TAG}_bench_final.json
 ls -la $OUT

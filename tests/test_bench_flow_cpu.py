@@ -31,7 +31,7 @@ def _launch(world, extra, port):
 @pytest.mark.parametrize('V,steps,warm', [(2, 3, 1), (1, 4, 0), (3, 2, 2)])
 def test_bench_control_flow_world2_gloo(V, steps, warm):
     port = 29700 + (os.getpid() % 200) + 7 * V
-    outs = _launch(2, ['--steps', str(steps), '--warmup', str(warm), '--views-per-step', str(V), '--check-gather'], port)
+    outs = _launch(2, ['--steps', str(steps), '--warmup', str(warm), '--views-per-step', str(V), '--check-gather', '--full'], port)
     lines0 = [l for l in outs[0].splitlines() if l.startswith('{')]
     assert len(lines0) == 1, outs[0]
     assert not [l for l in outs[1].splitlines() if l.startswith('{')], 'only rank 0 prints the JSON line'
@@ -83,6 +83,19 @@ def test_plain_launch_with_gpus_2_starts_two_ranks():
     assert res['n_gpus'] == 2 and res['n_ranks_seen'] == 2 and res['stub'] is True
     assert res['gather_check']['ok'] is True and res['gather_check']['gathered_shape'] == [4, 3, 16, 16]
     assert abs(res['value'] - 3 * 2 * 2 / (res['ms_per_step'] * 1e-3 * 3)) < 1e-6 * res['value']
+
+
+def test_run_without_full_measures_the_headline_only():
+    """Without --full the line carries the headline and nothing measured beside it: no with_8_views_per_gpu at N > 1 (its
+    batch is timed only with --full, as test_bench_control_flow_world2_gloo checks) and no CPU baseline."""
+    p = subprocess.run([sys.executable, 'bench.py', '--gpus', '2', '--stub-pipeline', '--img-size', '16', '--steps', '3',
+                        '--warmup', '1', '--views-per-step', '4'], cwd=ROOT, env=_plain_env(), capture_output=True, text=True,
+                       timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    res = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][0])
+    assert res['n_ranks_seen'] == 2 and res['steps'] == 3 and res['warmup'] == 1 and len(res['windows']) == 1
+    assert 'with_8_views_per_gpu' not in res and 'box_calibration' not in res and res['cpu_baseline'] is None
+    assert abs(res['value'] - 3 * 2 * 4 / (res['ms_per_step'] * 1e-3 * 3)) < 1e-6 * res['value']
 
 
 def test_plain_launch_with_gpus_1_is_one_process():

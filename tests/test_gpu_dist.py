@@ -26,7 +26,7 @@ def test_bench_under_torchrun_rccl_gather():
     port = 29600 + os.getpid() % 300
     res = _run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr',
                 '127.0.0.1', '--master-port', str(port), 'bench.py', '--gpus', '1', '--steps', '2', '--warmup', '1',
-                '--views-per-step', '2', '--no-cpu-baseline', '--main-loop-only', '--check-gather'], env)
+                '--views-per-step', '2', '--full', '--no-cpu-baseline', '--main-loop-only', '--check-gather'], env)
     assert res['n_gpus'] == 1 and res['steps'] == 2 and res['warmup'] == 1
     assert res['gather_check']['ok'] is True, res['gather_check']
     assert res['gather_check']['backend'] == 'nccl'
@@ -66,7 +66,7 @@ def test_bench_single_view_block():
     env = dict(os.environ, RNR_BENCH_FAST='1', RNR_BENCH_SINGLE='1')
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'RNR_BENCH_FORCE_DIST'):
         env.pop(k, None)
-    res = _run([sys.executable, 'bench.py', '--steps', '2', '--warmup', '1', '--views-per-step', '2', '--no-cpu-baseline',
+    res = _run([sys.executable, 'bench.py', '--steps', '2', '--warmup', '1', '--views-per-step', '2', '--full', '--no-cpu-baseline',
                 '--single-views', '24'], env)
     sv = res['single_view_mode']
     assert sv['views_per_call'] == 1 and sv['views'] == 24
@@ -85,3 +85,21 @@ def test_bench_single_view_block():
     fly = sv['two_calls_in_flight']
     assert fly['frames_per_s'] > 100.0 and fly['max_abs_diff_vs_sequential_last_frame'] < 2e-6
     assert res['n_ranks_seen'] == 1 and 'stages' in res
+
+
+def test_bench_without_full_is_the_headline_only():
+    """A run without --full sets up, warms up, times its three windows and prints the line: the headline with its roofline and
+    per-step series, and nothing that takes renders or measurements of its own (box_calibration, stages, the with_* variants,
+    single_view_mode, config5_shape, dropin_view_loop, the CPU baseline and its parity figure)."""
+    env = dict(os.environ)
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'RNR_BENCH_FORCE_DIST', 'RNR_BENCH_FAST', 'RNR_BENCH_SINGLE'):
+        env.pop(k, None)
+    res = _run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '2', '--warmup', '1', '--views-per-step', '2'], env)
+    assert res['n_gpus'] == res['n_ranks_seen'] == 1 and res['steps'] == 2 and res['warmup'] == 1
+    assert res['unit'] == 'frames/s' and res['higher_is_better'] is True and res['dtype'] == 'f32' and res['value'] > 10.0
+    assert abs(res['value'] - 2 * 2 / (res['ms_per_step'] * 1e-3 * 2)) < 1e-6 * res['value']
+    assert len(res['windows']) == 3 and len(res['step_series']['step_ms']) == 2 and 0.1 < res['roofline']['frac'] <= 1.0
+    assert res['cpu_baseline'] is None
+    extra = [k for k in res if k in ('box_calibration', 'stages', 'single_view_mode', 'config5_shape', 'dropin_view_loop', 'parity')
+             or k.startswith('with_')]
+    assert not extra, extra
