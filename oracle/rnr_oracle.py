@@ -27,18 +27,57 @@ from . import raster as _raster
 # ------------------------------------------------------------------------------------------------
 # camera / projection
 # ------------------------------------------------------------------------------------------------
-def projection(vertices, K, R, t, dist_coeffs, orig_size, offset=None, scale=None, eps=1e-9):
-    """neural_renderer/projection.py:6-53.  vertices [B,nv,3] world -> [B,nv,3] (u_ndc, v_ndc, z_cam)."""
-    cam = torch.matmul(vertices, R.transpose(2, 1)) + t
+def _fma32(a, b, c):
+    """Correctly rounded float32 fma(a, b, c) of float32 tensors: a * b is exact in float64, the float64 sum is rounded to
+    odd (its exact error from TwoSum decides the last bit), and rounding that to float32 is then the single rounding."""
+    a, b, c = [x.to(torch.float64) for x in torch.broadcast_tensors(a, b, c)]
+    p = a * b
+    s = p + c
+    bb = s - p
+    e = (p - (s - bb)) + (c - bb)
+    fix = (e != 0) & ((s.view(torch.int64) & 1) == 0) & torch.isfinite(s)
+    s = torch.where(fix, torch.nextafter(s, torch.where(e > 0, torch.full_like(s, math.inf), torch.full_like(s, -math.inf))), s)
+    return s.to(torch.float32)
+
+
+def matmul_fma(x, m):
+    """x [B,n,k] @ m [B,k,j] in float32 as the reference's torch.matmul evaluates it on the host that recorded the fixtures
+    (an FMA chain over k in ascending order: x0 m0, then fma(x1, m1, .), fma(x2, m2, .)), whatever BLAS kernel this host's
+    torch dispatches to: the oracle's projected vertices, and so every face index behind them, do not depend on the CPU."""
+    x, m = x.to(torch.float32), m.to(torch.float32)
+    out = x[..., :, 0:1] * m[..., 0:1, :]
+    for k in range(1, x.shape[-1]):
+        out = _fma32(x[..., :, k:k + 1], m[..., k:k + 1, :], out)
+    return out
+
+
+def _nudge(x, n):
+    """x moved by n float32 ulps."""
+    for _ in range(abs(int(n))):
+        x = torch.nextafter(x, torch.full_like(x, math.inf if n > 0 else -math.inf))
+    return x
+
+
+def projection(vertices, K, R, t, dist_coeffs, orig_size, offset=None, scale=None, eps=1e-9, ulps=None):
+    """neural_renderer/projection.py:6-53.  vertices [B,nv,3] world -> [B,nv,3] (u_ndc, v_ndc, z_cam).
+    The two matrix products are matmul_fma: the reference's torch.matmul bits, independent of this host's BLAS; sqrt and the
+    powers are rounded once from float64, also independent of the host."""
+    cam = matmul_fma(vertices, R.transpose(2, 1)) + t
     x, y, z = cam[..., 0], cam[..., 1], cam[..., 2]
     xn = x / (z + eps)
     yn = y / (z + eps)
     k1, k2, p1, p2, k3 = [dist_coeffs[:, None, i] for i in range(5)]
-    r = torch.sqrt(xn ** 2 + yn ** 2)
-    radial = 1 + k1 * (r ** 2) + k2 * (r ** 4) + k3 * (r ** 6)
+    # torch.sqrt and the powers r ** 4, r ** 6 evaluated in float64 and rounded once: the host libraries behind torch
+    # (vectorised pow, MKL's sqrt) round them faithfully, to one of the two neighbours, differently per CPU.  ulps = (dr, d4,
+    # d6) moves each by that many float32 ulps (tests: a fixture recorded with another host's rounding)
+    dr, d4, d6 = ulps if ulps is not None else (0, 0, 0)
+    r = _nudge(torch.sqrt((xn ** 2 + yn ** 2).to(torch.float64)).to(torch.float32), dr)
+    r4 = _nudge((r.to(torch.float64) ** 4).to(torch.float32), d4)
+    r6 = _nudge((r.to(torch.float64) ** 6).to(torch.float32), d6)
+    radial = 1 + k1 * (r ** 2) + k2 * r4 + k3 * r6
     xd = xn * radial + 2 * p1 * xn * yn + p2 * (r ** 2 + 2 * xn ** 2)
     yd = yn * radial + p1 * (r ** 2 + 2 * yn ** 2) + 2 * p2 * xn * yn
-    pix = torch.matmul(torch.stack([xd, yd, torch.ones_like(z)], dim=-1), K.transpose(1, 2))
+    pix = matmul_fma(torch.stack([xd, yd, torch.ones_like(z)], dim=-1), K.transpose(1, 2))
     u, v = pix[..., 0], pix[..., 1]
     if offset is not None and scale is not None:
         u = (u + offset[:, None, 1]) * scale[:, None, 1]
