@@ -471,15 +471,18 @@ conv_mfma_kernel(const ConvParams P) {
     // ---- epilogue: batch statistics of the raw output ----
     if (P.stats && P.splitk == 1) {
         if (single_view) {
-            float* red = &As[0][0];   // [WAVES_M][BN][2], LDS is free after the last barrier
+            // float64 from the first addition: v and v^2 are exact in double, a float32 partial would lose the low bits that
+            // the finalise's s2/n - mean^2 needs where |mean| >> std
+            static_assert(WAVES_M * BN * 2 * sizeof(double) <= sizeof(As), "statistics scratch fits the A tiles");
+            double* red = reinterpret_cast<double*>(&As[0][0]);   // [WAVES_M][BN][2], LDS is free after the last barrier
 #pragma unroll
             for (int j = 0; j < WN; j++) {
-                float s1 = 0.f, s2 = 0.f;
+                double s1 = 0.0, s2 = 0.0;
 #pragma unroll
                 for (int i = 0; i < WM; i++)
 #pragma unroll
                     for (int g = 0; g < 16; g++) {
-                        const float v = acc[i][j][g];
+                        const double v = acc[i][j][g];
                         s1 += v;
                         s2 += v * v;
                     }
@@ -498,8 +501,8 @@ conv_mfma_kernel(const ConvParams P) {
                     double s1 = 0.0, s2 = 0.0;
 #pragma unroll
                     for (int w = 0; w < WAVES_M; w++) {
-                        s1 += (double)red[(w * BN + tid) * 2 + 0];
-                        s2 += (double)red[(w * BN + tid) * 2 + 1];
+                        s1 += red[(w * BN + tid) * 2 + 0];
+                        s2 += red[(w * BN + tid) * 2 + 1];
                     }
                     double* st = stat_slot(P, n_tile, col);
                     atomicAdd(st + 0, s1);
@@ -915,7 +918,7 @@ conv_halo_kernel(const ConvParams P) {
     }
 
     // ---- epilogue ----
-    int* flag = reinterpret_cast<int*>(As + WAVES_M * BN * 2);      // behind the statistics scratch; LDS is free after the last barrier
+    int* flag = reinterpret_cast<int*>(As + WAVES_M * BN * 2 * 2);  // behind the (float64) statistics scratch; LDS is free after the last barrier
     float* out = P.out + (size_t)split * P.slab_stride;
     if (R16) {   // C layout of the 16x16 tiles: col = lane & 15, row = (lane >> 4) * 4 + reg
         const int col = n0 + wn0 + WN * 32 + l15;
@@ -934,15 +937,17 @@ conv_halo_kernel(const ConvParams P) {
     }
     const bool with_stats = P.stats && P.splitk == 1;
     if (with_stats) {
-        float* red = As;   // [WAVES_M][BN][2]; LDS is free after the last barrier
+        // float64 per lane (see conv_mfma_kernel)
+        static_assert(WAVES_M * BN * 2 * sizeof(double) + sizeof(int) <= 2 * ACH * sizeof(float), "statistics scratch and flag fit the halo buffers");
+        double* red = reinterpret_cast<double*>(As);   // [WAVES_M][BN][2]; LDS is free after the last barrier
 #pragma unroll
         for (int j = 0; j < WN; j++) {
-            float s1 = 0.f, s2 = 0.f;
+            double s1 = 0.0, s2 = 0.0;
 #pragma unroll
             for (int i = 0; i < WM; i++)
 #pragma unroll
                 for (int g = 0; g < 16; g++) {
-                    const float v = acc[i][j][g];
+                    const double v = acc[i][j][g];
                     s1 += v;
                     s2 += v * v;
                 }
@@ -955,12 +960,12 @@ conv_halo_kernel(const ConvParams P) {
             }
         }
         if (R16) {
-            float s1 = 0.f, s2 = 0.f;
+            double s1 = 0.0, s2 = 0.0;
 #pragma unroll
             for (int sb = 0; sb < 2 * WM; sb++)
 #pragma unroll
                 for (int g = 0; g < 4; g++) {
-                    const float v = acc16[sb][g];
+                    const double v = acc16[sb][g];
                     s1 += v;
                     s2 += v * v;
                 }
@@ -979,8 +984,8 @@ conv_halo_kernel(const ConvParams P) {
                 double s1 = 0.0, s2 = 0.0;
 #pragma unroll
                 for (int w = 0; w < WAVES_M; w++) {
-                    s1 += (double)red[(w * BN + tid) * 2 + 0];
-                    s2 += (double)red[(w * BN + tid) * 2 + 1];
+                    s1 += red[(w * BN + tid) * 2 + 0];
+                    s2 += red[(w * BN + tid) * 2 + 1];
                 }
                 double* st = stat_slot(P, n, col);
                 atomicAdd(st + 0, s1);
@@ -1322,19 +1327,21 @@ conv_halo_emu_kernel(const ConvParams P) {
     // two commutes with every fp32 rounding involved, so this equals scaling the accumulators first; scaling all 128 of
     // them in place made the compiler keep both copies and spill)
     const float winv = FMT == 1 ? *reinterpret_cast<const float*>(P.weight_emu) : 1.0f;
-    int* flag = reinterpret_cast<int*>(As) + WAVES_M * BN * 2;      // behind the statistics scratch
+    int* flag = reinterpret_cast<int*>(As + WAVES_M * BN * 2 * sizeof(double));      // behind the statistics scratch
     float* out = P.out + (size_t)split * P.slab_stride;
     const bool with_stats = P.stats && P.splitk == 1;
     if (with_stats) {
-        float* red = reinterpret_cast<float*>(As);   // [WAVES_M][BN][2]; LDS is free after the last barrier
+        // float64 per lane (see conv_mfma_kernel)
+        static_assert(WAVES_M * BN * 2 * sizeof(double) + sizeof(int) <= 2 * ACHB, "statistics scratch and flag fit the halo buffers");
+        double* red = reinterpret_cast<double*>(As);   // [WAVES_M][BN][2]; LDS is free after the last barrier
 #pragma unroll
         for (int j = 0; j < WN; j++) {
-            float s1 = 0.f, s2 = 0.f;
+            double s1 = 0.0, s2 = 0.0;
 #pragma unroll
             for (int i = 0; i < WM; i++)
 #pragma unroll
                 for (int g = 0; g < 16; g++) {
-                    const float v = acc[i][j][g];
+                    const double v = acc[i][j][g];
                     s1 += v;
                     s2 += v * v;
                 }
@@ -1354,8 +1361,8 @@ conv_halo_emu_kernel(const ConvParams P) {
                 double s1 = 0.0, s2 = 0.0;
 #pragma unroll
                 for (int w = 0; w < WAVES_M; w++) {
-                    s1 += (double)red[(w * BN + tid) * 2 + 0];
-                    s2 += (double)red[(w * BN + tid) * 2 + 1];
+                    s1 += red[(w * BN + tid) * 2 + 0];
+                    s2 += red[(w * BN + tid) * 2 + 1];
                 }
                 double* st = stat_slot(P, n, col);
                 atomicAdd(st + 0, s1);
@@ -1377,7 +1384,7 @@ static void launch_halo_emu_cfg(const dim3 grid, const ConvParams& P, hipStream_
     constexpr int TH = WAVES_M * WM * (32 / TW);
     constexpr int HP = (KIND == 1 ? TW + 1 : TW + 2) * (KIND == 1 ? TH + 1 : TH + 2);
     constexpr size_t lds_halo = (size_t)(2 * EmuFmt<FMT>::NT * 32 * HP);
-    constexpr size_t lds_red = (size_t)(WAVES_M * WAVES_N * WN * 32 * 2) * sizeof(float);
+    constexpr size_t lds_red = (size_t)(WAVES_M * WAVES_N * WN * 32 * 2) * sizeof(double) + sizeof(int);     // statistics + flag
     constexpr size_t lds = lds_halo > lds_red ? lds_halo : lds_red;
     static bool attr_set = false;
     if (!attr_set) {
@@ -1416,7 +1423,7 @@ static void launch_halo_cfg(const dim3 grid, const ConvParams& P, hipStream_t st
     constexpr int TH = WAVES_M * WM * (32 / TW), BN = WAVES_N * (WN * 32 + R16 * 16);
     constexpr int HP = (KIND == 1 ? TW + 1 : TW + 2) * (KIND == 1 ? TH + 1 : TH + 2);
     constexpr size_t lds_halo = (size_t)(2 * BK * HP) * sizeof(float);
-    constexpr size_t lds_red = (size_t)(WAVES_M * BN * 2) * sizeof(float);         // statistics reduction of the epilogue
+    constexpr size_t lds_red = (size_t)(WAVES_M * BN * 2) * sizeof(double) + sizeof(int);   // statistics reduction of the epilogue + flag
     constexpr size_t lds_min = lds_halo > lds_red ? lds_halo : lds_red;
     // workgroups per CU the registers allow (the kernel's __launch_bounds__) and LDS allows
     constexpr int nat = halo_waves(WM, WN, R16);

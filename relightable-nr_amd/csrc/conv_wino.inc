@@ -51,7 +51,7 @@ constexpr int WINO_STEP_FLOATS = 4 * 2 * 2 * 32 * 4;        // weight image per 
 constexpr int WINO_XCHG = 4 * 3 * 4 * 64 * 4;       // floats of the epilogue exchange: [finishing wave][source][4 register rows][lane][4]
 
 __host__ __device__ constexpr size_t wino_lds_bytes() {
-    return (size_t)((2 * WINO_CHUNK > WINO_XCHG ? 2 * WINO_CHUNK : WINO_XCHG) + 4 * WINO_BN * 2 + 4) * sizeof(float);
+    return (size_t)((2 * WINO_CHUNK > WINO_XCHG ? 2 * WINO_CHUNK : WINO_XCHG) + 4 * WINO_BN * 2 * 2 + 4) * sizeof(float);
 }
 
 __global__ void __launch_bounds__(CTHREADS, 2)
@@ -264,15 +264,18 @@ conv_wino_kernel(const ConvParams P) {
     else if (xi == 2) exchange(std::integral_constant<int, 2>{});
     else exchange(std::integral_constant<int, 3>{});
 
-    float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
+    // statistics in float64 from the first addition (see conv_mfma_kernel)
+    double s1[2] = {0.0, 0.0}, s2[2] = {0.0, 0.0};
 #pragma unroll
     for (int gq = 0; gq < 4; gq++)
 #pragma unroll
         for (int e = 0; e < 4; e++) {
-            s1[e >> 1] += y0v[gq][e] + y1v[gq][e];
-            s2[e >> 1] += y0v[gq][e] * y0v[gq][e] + y1v[gq][e] * y1v[gq][e];
+            const double a = y0v[gq][e], b = y1v[gq][e];
+            s1[e >> 1] += a + b;
+            s2[e >> 1] += a * a + b * b;
         }
-    float* red = As + WINO_XCHG;        // [4 waves][64 columns][2], behind the exchange buffer
+    static_assert(WINO_XCHG % 2 == 0, "float64 scratch alignment");
+    double* red = reinterpret_cast<double*>(As + WINO_XCHG);        // [4 waves][64 columns][2], behind the exchange buffer
     int* flag = reinterpret_cast<int*>(red + 4 * WINO_BN * 2);
     const bool with_stats = P.stats != nullptr && P.splitk == 1;
     if (with_stats) {
@@ -292,8 +295,8 @@ conv_wino_kernel(const ConvParams P) {
                 double t1 = 0.0, t2 = 0.0;
 #pragma unroll
                 for (int w = 0; w < 4; w++) {
-                    t1 += (double)red[(w * WINO_BN + tid) * 2 + 0];
-                    t2 += (double)red[(w * WINO_BN + tid) * 2 + 1];
+                    t1 += red[(w * WINO_BN + tid) * 2 + 0];
+                    t2 += red[(w * WINO_BN + tid) * 2 + 1];
                 }
                 double* st = stat_slot(P, n, col);
                 atomicAdd(st + 0, t1);

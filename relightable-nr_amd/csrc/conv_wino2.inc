@@ -198,7 +198,7 @@ constexpr int W2_BDIST = W2_BDIST_K;                         // K steps between 
 constexpr int W2_STEP_FLOATS = 2 * 3 * 2 * 2 * 32 * 3;       // weight image per K step: [column half][xi][half][h][32][3]
 
 __host__ __device__ constexpr size_t wino2_lds_bytes() {
-    return (size_t)((2 * W2Geo::CHUNK > W2_XCHG ? 2 * W2Geo::CHUNK : W2_XCHG) + 12 * 64 * 2 + 4) * sizeof(float);
+    return (size_t)((2 * W2Geo::CHUNK > W2_XCHG ? 2 * W2Geo::CHUNK : W2_XCHG) + 12 * 64 * 2 * 2 + 4) * sizeof(float);
 }
 
 template <int KIND>

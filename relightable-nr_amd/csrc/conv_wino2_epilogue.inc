@@ -7,7 +7,8 @@
 // [12 waves][64 columns][2] statistics scratch behind them, then the arrival flag.
 {
 
-    float* red = As + (2 * CHUNK > W2_XCHG ? 2 * CHUNK : W2_XCHG);
+    static_assert((2 * CHUNK > W2_XCHG ? 2 * CHUNK : W2_XCHG) % 2 == 0, "float64 scratch alignment");
+    double* red = reinterpret_cast<double*>(As + (2 * CHUNK > W2_XCHG ? 2 * CHUNK : W2_XCHG));
     constexpr int BNW = W2Kind<KIND>::BNW;
     const int tid = T.tid, lane = T.lane, n = T.n;
     // rr[g][half] = (r[b = 0], r[b = 1]) of this wave's plane row: r0 = M0 + M1, r1 = M1 - M2
@@ -57,15 +58,16 @@
     else finish(std::integral_constant<int, 2>{});
     const int g0 = xi == 0 ? 0 : (xi == 1 ? 6 : 11), ng = xi == 0 ? 6 : 5;
 
-    float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
+    // statistics in float64 from the first addition: v and v^2 are exact in double (see conv_mfma_kernel)
+    double s1[2] = {0.0, 0.0}, s2[2] = {0.0, 0.0};
 #pragma unroll
     for (int k = 0; k < 6; k++)
 #pragma unroll
         for (int nb = 0; nb < 2; nb++) {
             if (k < ng) {
-                s1[nb] += y0v[k][nb].x + y0v[k][nb].y + y1v[k][nb].x + y1v[k][nb].y;
-                s2[nb] += y0v[k][nb].x * y0v[k][nb].x + y0v[k][nb].y * y0v[k][nb].y + y1v[k][nb].x * y1v[k][nb].x +
-                          y1v[k][nb].y * y1v[k][nb].y;
+                const double a = y0v[k][nb].x, b = y0v[k][nb].y, c = y1v[k][nb].x, d = y1v[k][nb].y;
+                s1[nb] += (a + b) + (c + d);
+                s2[nb] += (a * a + b * b) + (c * c + d * d);
             }
         }
     int* flag = reinterpret_cast<int*>(red + 12 * 64 * 2);
@@ -89,8 +91,8 @@
 #pragma unroll
                 for (int w = 0; w < 12; w++) {
                     if (KIND == 1 && ((w / 3) & 1) != (tid >> 6)) continue;
-                    t1 += (double)red[(w * 64 + (tid & 63)) * 2 + 0];
-                    t2 += (double)red[(w * 64 + (tid & 63)) * 2 + 1];
+                    t1 += red[(w * 64 + (tid & 63)) * 2 + 0];
+                    t2 += red[(w * 64 + (tid & 63)) * 2 + 1];
                 }
                 double* st = stat_slot(P, n, col);
                 atomicAdd(st + 0, t1);

@@ -73,7 +73,7 @@ constexpr float W4_A = 0.75f, W4_B = 1.5f, W4_A2 = 0.5625f, W4_B2 = 2.25f, W4_A3
 constexpr float W4_A2B2 = 1.265625f, W4_A2PB2 = 2.8125f;
 
 __host__ __device__ constexpr size_t wino4_lds_bytes() {
-    return (size_t)(2 * W4_CHUNK + 12 * 32 * 2 + 4 + 2 * W4_BN_MAXC) * sizeof(float);
+    return (size_t)(2 * W4_CHUNK + 12 * 32 * 2 * 2 + 4 + 2 * W4_BN_MAXC) * sizeof(float);
 }
 
 // B^T applied to six values (both directions of the input transform)
@@ -143,7 +143,7 @@ conv_wino4_kernel(const ConvParams P) {
     const int per_split = (nchunks + P.splitk - 1) / P.splitk;
     const int c_begin = z_ * per_split, c_end = min(nchunks, c_begin + per_split);
     struct ChunkSrc { __amdgpu_buffer_rsrc_t rsrc; unsigned C; unsigned soff; int act; float4 sc, sh; const float2* bn; };
-    float2* s_bn = reinterpret_cast<float2*>(As + 2 * W4_CHUNK + 12 * 32 * 2 + 4);        // [padded input channel] (scale, shift)
+    float2* s_bn = reinterpret_cast<float2*>(As + 2 * W4_CHUNK + 12 * 32 * 2 * 2 + 4);    // [padded input channel] (scale, shift), behind the float64 statistics scratch
     auto chunk_src = [&](int c, bool in_loop) {
         ChunkSrc cs;
         const int s = c < P.chunks0 ? 0 : 1;
@@ -382,15 +382,17 @@ conv_wino4_kernel(const ConvParams P) {
     else finish(std::integral_constant<int, 5>{});
     const int g0 = xi < 4 ? 3 * xi : 12 + 2 * (xi - 4), ng = xi < 4 ? 3 : 2;
 
-    float s1 = 0.f, s2 = 0.f;
+    // statistics in float64 from the first addition: v and v^2 are exact in double (see conv_mfma_kernel)
+    double s1 = 0.0, s2 = 0.0;
 #pragma unroll
     for (int k = 0; k < 3; k++)
         if (k < ng)
 #pragma unroll
             for (int a = 0; a < 4; a++)
 #pragma unroll
-                for (int b = 0; b < 4; b++) { s1 += yv[k][a][b]; s2 += yv[k][a][b] * yv[k][a][b]; }
-    float* red = As + 2 * W4_CHUNK;         // [12 waves][32 columns][2], behind the image / exchange buffers
+                for (int b = 0; b < 4; b++) { const double v = yv[k][a][b]; s1 += v; s2 += v * v; }
+    static_assert(W4_CHUNK % 2 == 0, "float64 scratch alignment");
+    double* red = reinterpret_cast<double*>(As + 2 * W4_CHUNK);         // [12 waves][32 columns][2], behind the image / exchange buffers
     int* flag = reinterpret_cast<int*>(red + 12 * 32 * 2);
     const bool with_stats = P.stats != nullptr && P.splitk == 1;
     if (with_stats) {
@@ -407,8 +409,8 @@ conv_wino4_kernel(const ConvParams P) {
                 double t1 = 0.0, t2 = 0.0;
 #pragma unroll
                 for (int w = 0; w < 6; w++) {       // the six plane-row waves of column half tid >> 5
-                    t1 += (double)red[(((tid >> 5) * 6 + w) * 32 + (tid & 31)) * 2 + 0];
-                    t2 += (double)red[(((tid >> 5) * 6 + w) * 32 + (tid & 31)) * 2 + 1];
+                    t1 += red[(((tid >> 5) * 6 + w) * 32 + (tid & 31)) * 2 + 0];
+                    t2 += red[(((tid >> 5) * 6 + w) * 32 + (tid & 31)) * 2 + 1];
                 }
                 double* st = stat_slot(P, n, col);
                 atomicAdd(st + 0, t1);

@@ -37,7 +37,7 @@ constexpr int W80_XCHG = 4 * 3 * 5 * 64 * 2;        // floats of the epilogue ex
 
 __host__ __device__ constexpr int w80_plane_off(int p) { return p * W80_PLANE + (p >> 2) * 8; }
 __host__ __device__ constexpr size_t wino80_lds_bytes() {
-    return (size_t)((2 * W80_CHUNK > W80_XCHG ? 2 * W80_CHUNK : W80_XCHG) + 4 * 80 * 2 + 4) * sizeof(float);
+    return (size_t)((2 * W80_CHUNK > W80_XCHG ? 2 * W80_CHUNK : W80_XCHG) + 4 * 80 * 2 * 2 + 4) * sizeof(float);
 }
 
 __global__ void __launch_bounds__(CTHREADS, 2)
@@ -246,14 +246,17 @@ conv_wino80_kernel(const ConvParams P) {
     else if (xi == 2) exchange(std::integral_constant<int, 2>{});
     else exchange(std::integral_constant<int, 3>{});
 
-    float* red = As + (2 * W80_CHUNK > W80_XCHG ? 2 * W80_CHUNK : W80_XCHG);        // [4 waves][80 columns][2]
+    static_assert((2 * W80_CHUNK > W80_XCHG ? 2 * W80_CHUNK : W80_XCHG) % 2 == 0, "float64 scratch alignment");
+    double* red = reinterpret_cast<double*>(As + (2 * W80_CHUNK > W80_XCHG ? 2 * W80_CHUNK : W80_XCHG));        // [4 waves][80 columns][2]
     int* flag = reinterpret_cast<int*>(red + 4 * 80 * 2);
     const bool with_stats = P.stats != nullptr;
     if (with_stats) {
 #pragma unroll
         for (int b = 0; b < 5; b++) {
-            float s1 = y0v[b].x + y0v[b].y + y1v[b].x + y1v[b].y;
-            float s2 = y0v[b].x * y0v[b].x + y0v[b].y * y0v[b].y + y1v[b].x * y1v[b].x + y1v[b].y * y1v[b].y;
+            // float64 from the first addition: v and v^2 are exact in double (see conv_mfma_kernel)
+            const double p = y0v[b].x, q = y0v[b].y, r = y1v[b].x, t = y1v[b].y;
+            double s1 = (p + q) + (r + t);
+            double s2 = (p * p + q * q) + (r * r + t * t);
             s1 += __shfl_xor(s1, 16, 64); s2 += __shfl_xor(s2, 16, 64);
             s1 += __shfl_xor(s1, 32, 64); s2 += __shfl_xor(s2, 32, 64);
             if (kq == 0) {
@@ -266,8 +269,8 @@ conv_wino80_kernel(const ConvParams P) {
             double t1 = 0.0, t2 = 0.0;
 #pragma unroll
             for (int w = 0; w < 4; w++) {
-                t1 += (double)red[(w * 80 + tid) * 2 + 0];
-                t2 += (double)red[(w * 80 + tid) * 2 + 1];
+                t1 += red[(w * 80 + tid) * 2 + 0];
+                t2 += red[(w * 80 + tid) * 2 + 1];
             }
             double* st = stat_slot(P, n, tid);
             atomicAdd(st + 0, t1);

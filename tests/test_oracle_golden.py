@@ -463,3 +463,75 @@ def test_gbuffer64_pinned_to_oracle_and_fixture(golden):
                     ('normal_map', 1e-6 * (cond_n + 1)), ('normal_map_cam', 2e-6 * (cond_n + 1))]:
         assert close(o[k], r[k], atol, k), k
     assert float(o['uv_abs'].max()) > 1.5 and bool((o['normal_raw'].norm(dim=-1) < 0.1).any())    # the scramble is in effect
+
+
+def _bn64_input(N, H, W, C, c_pad, seed):
+    """float32 NHWC map with the channels a BatchNorm statistics test needs: mean/std 0 ... 1e4, a constant, an all-zero one."""
+    g = torch.Generator().manual_seed(seed)
+    ratios = [0.0, 1.0, 30.0, 1e3, 1e4]
+    x = torch.zeros(N, H, W, c_pad)
+    for c in range(C - 2):
+        r = ratios[c % len(ratios)]
+        x[..., c] = (torch.randn(N, H, W, generator=g) * 0.5 + 0.5 * r + 0.1 * c).float()
+    x[..., C - 2] = 2.75            # constant: variance exactly 0
+    x[..., C - 1] = 0.0             # all zero
+    x[..., C:] = float('nan')       # padding channels are never read
+    return x
+
+
+def test_bn64_pinned_to_torch_batch_norm():
+    """oracle/bn64.py against torch.nn.functional.batch_norm(training=True) in float64, per view and over the whole batch:
+    y = scale * x + shift must equal torch's normalised output, and the statistics torch reports must match; every term is
+    float64 on exact float32 inputs, so 1e-12 relative to the channel's magnitude (|mean| + std) covers both summation orders."""
+    import torch.nn.functional as F
+    from oracle import bn64
+    N, H, W, C, cp = 3, 5, 7, 12, 16
+    x = _bn64_input(N, H, W, C, cp, seed=1)
+    g = torch.Generator().manual_seed(2)
+    gamma = torch.rand(C, generator=g) * 2 - 0.5
+    gamma[3] = 0.0
+    gamma[4] = -1.25
+    beta = torch.randn(C, generator=g)
+    eps = 1e-5
+    xd = x[..., :C].double().permute(0, 3, 1, 2)
+    mag = xd.abs().amax(dim=(0, 2, 3))
+    ref = bn64.per_view(x, C, gamma, beta, eps)
+    for n in range(N):
+        y = F.batch_norm(xd[n:n + 1], None, None, gamma.double(), beta.double(), training=True, eps=eps)
+        got = ref['scale'][n][None, :, None, None] * xd[n:n + 1] + ref['shift'][n][None, :, None, None]
+        assert torch.allclose(got, y, rtol=0, atol=1e-9), n
+        assert torch.allclose(ref['mean'][n], xd[n].mean(dim=(1, 2)), rtol=1e-13, atol=1e-13 * float(mag.max()))
+        assert torch.allclose(ref['var'][n], xd[n].var(dim=(1, 2), unbiased=False), rtol=1e-12, atol=1e-20)
+    assert torch.equal(ref['var'][:, C - 2], torch.zeros(N, dtype=torch.float64))
+    assert torch.equal(ref['s1'][:, C - 1], torch.zeros(N, dtype=torch.float64))
+    assert torch.allclose(ref['s2'], (xd * xd).sum(dim=(2, 3)), rtol=1e-14)
+    allb = bn64.batch_all(x, C, gamma, beta, eps)
+    y = F.batch_norm(xd, None, None, gamma.double(), beta.double(), training=True, eps=eps)
+    got = allb['scale'][None, :, None, None] * xd + allb['shift'][None, :, None, None]
+    assert torch.allclose(got, y, rtol=0, atol=1e-9)
+    assert allb['count'] == N * H * W and float(allb['var'][C - 2]) == 0.0
+
+
+def test_bn64_running_buffers_pinned_to_torch_batchnorm2d():
+    """bn64.batch_all's running_mean / running_var update (momentum 0.1, unbiased variance) against torch.nn.BatchNorm2d in
+    float64 train mode, over two calls, with num_batches_tracked counting them; the float64 results agree to 1e-12."""
+    from oracle import bn64
+    N, H, W, C, cp = 2, 4, 6, 10, 16
+    bn = torch.nn.BatchNorm2d(C, momentum=0.1).double().train()
+    g = torch.Generator().manual_seed(3)
+    with torch.no_grad():
+        bn.weight.copy_(torch.rand(C, generator=g) + 0.5)
+        bn.bias.copy_(torch.randn(C, generator=g))
+        bn.running_mean.copy_(torch.randn(C, generator=g))
+        bn.running_var.copy_(torch.rand(C, generator=g) + 0.1)
+    rm, rv = bn.running_mean.clone(), bn.running_var.clone()
+    for call in range(2):
+        x = _bn64_input(N, H, W, C, cp, seed=10 + call)
+        ref = bn64.batch_all(x, C, bn.weight.detach(), bn.bias.detach(), bn.eps, rm, rv, bn.momentum)
+        with torch.no_grad():
+            bn(x[..., :C].double().permute(0, 3, 1, 2))
+        mag = 1.0 + bn.running_mean.abs() + bn.running_var
+        assert torch.allclose(ref['running_mean'], bn.running_mean, rtol=0, atol=1e-12 * float(mag.max()))
+        assert torch.allclose(ref['running_var'], bn.running_var, rtol=1e-12, atol=1e-12)
+        rm, rv = ref['running_mean'], ref['running_var']
+    assert int(bn.num_batches_tracked) == 2
