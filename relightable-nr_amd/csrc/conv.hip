@@ -182,8 +182,75 @@ __device__ __forceinline__ float apply_act(float v, int act) {
 typedef unsigned int uintx4_t __attribute__((__vector_size__(4 * sizeof(unsigned int))));
 constexpr int AUX_SC1 = 16;         // write-through / L1-bypassing buffer access
 
+// Batch statistics are summed in float64 from the first addition: v and v^2 of a float32 output are exact in double, and a
+// float32 partial would lose the low bits that the finalise's s2/n - mean^2 needs where |mean| >> std.
 __device__ __forceinline__ double* stat_slot(const ConvParams& P, int n, int col) {
     return P.stats + (size_t)(blockIdx.x & (unsigned)(P.n_shards - 1)) * P.stats_shard + ((size_t)n * P.c_out_pad + col) * 2;
+}
+__device__ __forceinline__ void stat_add(const ConvParams& P, int n, int col, double s1, double s2) {
+    double* st = stat_slot(P, n, col);
+    atomicAdd(st + 0, s1);
+    atomicAdd(st + 1, s2);
+}
+// one output value, for the workgroups whose rows straddle two views
+__device__ __forceinline__ void stat_add_value(const ConvParams& P, int n, int col, float v) {
+    double* st = stat_slot(P, n, col);
+    atomicAdd(st + 0, (double)v);
+    atomicAdd(st + 1, (double)v * (double)v);
+}
+
+// LDS scratch of the statistics epilogue: [SLOTS][COLS][2] partial (sum, sum of squares) per slot (a wave or row group) and
+// column, then bn_complete's arrival flag, padded to 16 bytes so that what lies behind it stays aligned.  The scratch
+// reuses LDS that is dead after the kernel's last barrier; its base must be 8-byte aligned.  Each kernel stores its lanes'
+// partials as red[(slot * COLS + col) * 2 + {0, 1}] itself: behind a helper the compiler folded that address arithmetic
+// differently and the Winograd kernels' register allocation changed (and their layers slowed by up to 2 %).
+template <int SLOTS, int COLS>
+struct StatScratch {
+    static constexpr size_t BYTES = (size_t)SLOTS * COLS * 2 * sizeof(double) + 16;
+    static __device__ __forceinline__ double* red(void* base) { return static_cast<double*>(base); }
+    static __device__ __forceinline__ int* flag(void* base) { return reinterpret_cast<int*>(red(base) + SLOTS * COLS * 2); }
+    // Once every slot is written: thread tid < NCOLS adds column col0 + tid of view n.  Column tid sums, in ascending slot
+    // order, column tid % COLS of the SLOTS * COLS / NCOLS slots slot(0), slot(1), ... (by default all slots, NCOLS = COLS).
+    template <int NCOLS = COLS, typename Slot>
+    static __device__ __forceinline__ void publish(const ConvParams& P, const double* red, int n, int col0, int tid, Slot slot) {
+        static_assert(SLOTS * COLS % NCOLS == 0, "every column sums the same number of slots");
+        __syncthreads();
+        if (tid < NCOLS) {
+            const int col = col0 + tid;
+            if (col < P.c_out) {
+                const int c = NCOLS == COLS ? tid : tid % COLS;
+                double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+                for (int j = 0; j < SLOTS * COLS / NCOLS; j++) {
+                    s1 += red[(slot(j) * COLS + c) * 2 + 0];
+                    s2 += red[(slot(j) * COLS + c) * 2 + 1];
+                }
+                stat_add(P, n, col, s1, s2);
+            }
+        }
+    }
+    static __device__ __forceinline__ void publish(const ConvParams& P, const double* red, int n, int col0, int tid) {
+        publish(P, red, n, col0, tid, [](int j) { return j; });
+    }
+};
+
+// BatchNorm's affine from a channel's statistics: biased variance clamped at 0, float64, one rounding to float32
+struct BnAffine { double mean, var; float scale, shift; };
+__device__ __forceinline__ BnAffine bn_affine(double s1, double s2, double count, float gamma, float beta, float eps) {
+    const double mean = s1 / count;
+    double var = s2 / count - mean * mean;
+    var = var < 0.0 ? 0.0 : var;
+    const double g = (double)gamma / sqrt(var + (double)eps);
+    return {mean, var, (float)g, (float)((double)beta - mean * g)};
+}
+// torch.nn.BatchNorm2d in train mode also moves its running statistics: momentum, UNBIASED variance
+__device__ __forceinline__ void bn_update_running(const BnAffine& a, double count, float momentum, float* running_mean,
+                                                  float* running_var, int c) {
+    if (running_mean) running_mean[c] = (float)((1.0 - (double)momentum) * (double)running_mean[c] + (double)momentum * a.mean);
+    if (running_var) {
+        const double unb = count > 1.0 ? a.var * count / (count - 1.0) : a.var;
+        running_var[c] = (float)((1.0 - (double)momentum) * (double)running_var[c] + (double)momentum * unb);
+    }
 }
 
 // scale / shift of views [n_first, n_first + n_views) from the summed shards (the arithmetic of bn_finalize_kernel).
@@ -218,19 +285,11 @@ __device__ __forceinline__ void bn_finalize_views(const ConvParams& P, int n_fir
         }
         float sc = 0.f, sf = 0.f;
         if (c < P.c_out) {
-            const double mean = s1 / P.count;
-            double var = s2 / P.count - mean * mean;    // biased variance
-            var = var < 0.0 ? 0.0 : var;
-            const double g = (double)P.gamma[c] / sqrt(var + (double)P.eps);
-            sc = (float)g;
-            sf = (float)((double)P.beta[c] - mean * g);
-            // torch.nn.BatchNorm2d in train mode also moves its running statistics (momentum, unbiased variance): the arithmetic
-            // of bn_finalize_batch_kernel; the host passes the buffers for one-view calls only, where per-view = whole batch
-            if (P.running_mean) P.running_mean[c] = (float)((1.0 - (double)P.momentum) * (double)P.running_mean[c] + (double)P.momentum * mean);
-            if (P.running_var) {
-                const double unb = P.count > 1.0 ? var * P.count / (P.count - 1.0) : var;
-                P.running_var[c] = (float)((1.0 - (double)P.momentum) * (double)P.running_var[c] + (double)P.momentum * unb);
-            }
+            const BnAffine a = bn_affine(s1, s2, P.count, P.gamma[c], P.beta[c], P.eps);
+            sc = a.scale;
+            sf = a.shift;
+            // the host passes the running buffers for one-view calls only, where per-view = whole batch
+            bn_update_running(a, P.count, P.momentum, P.running_mean, P.running_var, c);
         }
         P.scale[idx] = sc;
         P.shift[idx] = sf;
@@ -469,12 +528,11 @@ conv_mfma_kernel(const ConvParams P) {
     }
 
     // ---- epilogue: batch statistics of the raw output ----
+    typedef StatScratch<WAVES_M, BN> Stats;
+    static_assert(Stats::BYTES <= sizeof(As), "statistics scratch and flag fit the A tiles");
     if (P.stats && P.splitk == 1) {
         if (single_view) {
-            // float64 from the first addition: v and v^2 are exact in double, a float32 partial would lose the low bits that
-            // the finalise's s2/n - mean^2 needs where |mean| >> std
-            static_assert(WAVES_M * BN * 2 * sizeof(double) <= sizeof(As), "statistics scratch fits the A tiles");
-            double* red = reinterpret_cast<double*>(&As[0][0]);   // [WAVES_M][BN][2], LDS is free after the last barrier
+            double* red = Stats::red(&As[0][0]);
 #pragma unroll
             for (int j = 0; j < WN; j++) {
                 double s1 = 0.0, s2 = 0.0;
@@ -494,21 +552,7 @@ conv_mfma_kernel(const ConvParams P) {
                     red[(wave_m * BN + col) * 2 + 1] = s2;
                 }
             }
-            __syncthreads();
-            if (tid < BN) {
-                const int col = n0 + tid;
-                if (col < P.c_out) {
-                    double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-                    for (int w = 0; w < WAVES_M; w++) {
-                        s1 += red[(w * BN + tid) * 2 + 0];
-                        s2 += red[(w * BN + tid) * 2 + 1];
-                    }
-                    double* st = stat_slot(P, n_tile, col);
-                    atomicAdd(st + 0, s1);
-                    atomicAdd(st + 1, s2);
-                }
-            }
+            Stats::publish(P, red, n_tile, n0, tid);
         } else {   // tiles straddling views only occur for maps smaller than a tile (tiny layers)
 #pragma unroll
             for (int i = 0; i < WM; i++)
@@ -520,19 +564,14 @@ conv_mfma_kernel(const ConvParams P) {
 #pragma unroll
                         for (int j = 0; j < WN; j++) {
                             const int col = n0 + wn0 + 32 * j + l31;
-                            if (col < P.c_out) {
-                                const float v = acc[i][j][g];
-                                double* st = stat_slot(P, n, col);
-                                atomicAdd(st + 0, (double)v);
-                                atomicAdd(st + 1, (double)v * (double)v);
-                            }
+                            if (col < P.c_out) stat_add_value(P, n, col, acc[i][j][g]);
                         }
                     }
                 }
         }
         if (P.arrive) {      // producer-side BatchNorm: one counter for the launch (tiles may straddle views here)
             const BnArrival a = bn_arrive(P, -1, tid);
-            bn_complete(P, a, -1, tid, reinterpret_cast<int*>(&Bs[0][0]));
+            bn_complete(P, a, -1, tid, Stats::flag(&As[0][0]));
         }
     }
 }
@@ -918,7 +957,9 @@ conv_halo_kernel(const ConvParams P) {
     }
 
     // ---- epilogue ----
-    int* flag = reinterpret_cast<int*>(As + WAVES_M * BN * 2 * 2);  // behind the (float64) statistics scratch; LDS is free after the last barrier
+    typedef StatScratch<WAVES_M, BN> Stats;
+    static_assert(Stats::BYTES <= 2 * ACH * sizeof(float), "statistics scratch and flag fit the halo buffers");
+    double* red = Stats::red(As);
     float* out = P.out + (size_t)split * P.slab_stride;
     if (R16) {   // C layout of the 16x16 tiles: col = lane & 15, row = (lane >> 4) * 4 + reg
         const int col = n0 + wn0 + WN * 32 + l15;
@@ -937,9 +978,6 @@ conv_halo_kernel(const ConvParams P) {
     }
     const bool with_stats = P.stats && P.splitk == 1;
     if (with_stats) {
-        // float64 per lane (see conv_mfma_kernel)
-        static_assert(WAVES_M * BN * 2 * sizeof(double) + sizeof(int) <= 2 * ACH * sizeof(float), "statistics scratch and flag fit the halo buffers");
-        double* red = reinterpret_cast<double*>(As);   // [WAVES_M][BN][2]; LDS is free after the last barrier
 #pragma unroll
         for (int j = 0; j < WN; j++) {
             double s1 = 0.0, s2 = 0.0;
@@ -977,29 +1015,13 @@ conv_halo_kernel(const ConvParams P) {
                 red[(wave_m * BN + col) * 2 + 1] = s2;
             }
         }
-        __syncthreads();
-        if (tid < BN) {
-            const int col = n0 + tid;
-            if (col < P.c_out) {
-                double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-                for (int w = 0; w < WAVES_M; w++) {
-                    s1 += red[(w * BN + tid) * 2 + 0];
-                    s2 += red[(w * BN + tid) * 2 + 1];
-                }
-                double* st = stat_slot(P, n, col);
-                atomicAdd(st + 0, s1);
-                atomicAdd(st + 1, s2);
-            }
-        }
+        Stats::publish(P, red, n, n0, tid);
     }
-    if (with_stats && P.arrive) {       // producer-side BatchNorm: the output stores overlap the ticket's round trip
-        const BnArrival a = bn_arrive(P, n, tid);
-        store_acc_tiles<KIND, WM, WN, TW>(P, out, acc, n, y0, x0, py, px, wave_m, n0, wn0, l31, h);
-        bn_complete(P, a, n, tid, flag);
-    } else {
-        store_acc_tiles<KIND, WM, WN, TW>(P, out, acc, n, y0, x0, py, px, wave_m, n0, wn0, l31, h);
-    }
+    BnArrival arr = {nullptr, 0u};
+    const bool bn = with_stats && P.arrive;      // producer-side BatchNorm: the output stores overlap the ticket's round trip
+    if (bn) arr = bn_arrive(P, n, tid);
+    store_acc_tiles<KIND, WM, WN, TW>(P, out, acc, n, y0, x0, py, px, wave_m, n0, wn0, l31, h);
+    if (bn) bn_complete(P, arr, n, tid, Stats::flag(As));
 }
 
 // (r03 experiment, measured and not adopted: conv_halo_kernel as a persistent tile loop with next-tile prefetch — -1.4 % at 8
@@ -1327,13 +1349,12 @@ conv_halo_emu_kernel(const ConvParams P) {
     // two commutes with every fp32 rounding involved, so this equals scaling the accumulators first; scaling all 128 of
     // them in place made the compiler keep both copies and spill)
     const float winv = FMT == 1 ? *reinterpret_cast<const float*>(P.weight_emu) : 1.0f;
-    int* flag = reinterpret_cast<int*>(As + WAVES_M * BN * 2 * sizeof(double));      // behind the statistics scratch
+    typedef StatScratch<WAVES_M, BN> Stats;
+    static_assert(Stats::BYTES <= 2 * ACHB, "statistics scratch and flag fit the halo buffers");
+    double* red = Stats::red(As);
     float* out = P.out + (size_t)split * P.slab_stride;
     const bool with_stats = P.stats && P.splitk == 1;
     if (with_stats) {
-        // float64 per lane (see conv_mfma_kernel)
-        static_assert(WAVES_M * BN * 2 * sizeof(double) + sizeof(int) <= 2 * ACHB, "statistics scratch and flag fit the halo buffers");
-        double* red = reinterpret_cast<double*>(As);   // [WAVES_M][BN][2]; LDS is free after the last barrier
 #pragma unroll
         for (int j = 0; j < WN; j++) {
             double s1 = 0.0, s2 = 0.0;
@@ -1354,29 +1375,13 @@ conv_halo_emu_kernel(const ConvParams P) {
                 red[(wave_m * BN + col) * 2 + 1] = s2;
             }
         }
-        __syncthreads();
-        if (tid < BN) {
-            const int col = n0 + tid;
-            if (col < P.c_out) {
-                double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-                for (int w = 0; w < WAVES_M; w++) {
-                    s1 += red[(w * BN + tid) * 2 + 0];
-                    s2 += red[(w * BN + tid) * 2 + 1];
-                }
-                double* st = stat_slot(P, n, col);
-                atomicAdd(st + 0, s1);
-                atomicAdd(st + 1, s2);
-            }
-        }
+        Stats::publish(P, red, n, n0, tid);
     }
-    if (with_stats && P.arrive) {       // producer-side BatchNorm
-        const BnArrival a = bn_arrive(P, n, tid);
-        store_acc_tiles<KIND, WM, WN, TW, FMT == 1>(P, out, acc, n, y0, x0, py, px, wave_m, n0, wn0, l31, h, winv);
-        bn_complete(P, a, n, tid, flag);
-    } else {
-        store_acc_tiles<KIND, WM, WN, TW, FMT == 1>(P, out, acc, n, y0, x0, py, px, wave_m, n0, wn0, l31, h, winv);
-    }
+    BnArrival arr = {nullptr, 0u};
+    const bool bn = with_stats && P.arrive;      // producer-side BatchNorm
+    if (bn) arr = bn_arrive(P, n, tid);
+    store_acc_tiles<KIND, WM, WN, TW, FMT == 1>(P, out, acc, n, y0, x0, py, px, wave_m, n0, wn0, l31, h, winv);
+    if (bn) bn_complete(P, arr, n, tid, Stats::flag(As));
 }
 
 template <int FMT, int KIND, int WAVES_M, int WAVES_N, int WM, int WN, int TW = 32>
@@ -1384,7 +1389,7 @@ static void launch_halo_emu_cfg(const dim3 grid, const ConvParams& P, hipStream_
     constexpr int TH = WAVES_M * WM * (32 / TW);
     constexpr int HP = (KIND == 1 ? TW + 1 : TW + 2) * (KIND == 1 ? TH + 1 : TH + 2);
     constexpr size_t lds_halo = (size_t)(2 * EmuFmt<FMT>::NT * 32 * HP);
-    constexpr size_t lds_red = (size_t)(WAVES_M * WAVES_N * WN * 32 * 2) * sizeof(double) + sizeof(int);     // statistics + flag
+    constexpr size_t lds_red = StatScratch<WAVES_M, WAVES_N * WN * 32>::BYTES;
     constexpr size_t lds = lds_halo > lds_red ? lds_halo : lds_red;
     static bool attr_set = false;
     if (!attr_set) {
@@ -1423,7 +1428,7 @@ static void launch_halo_cfg(const dim3 grid, const ConvParams& P, hipStream_t st
     constexpr int TH = WAVES_M * WM * (32 / TW), BN = WAVES_N * (WN * 32 + R16 * 16);
     constexpr int HP = (KIND == 1 ? TW + 1 : TW + 2) * (KIND == 1 ? TH + 1 : TH + 2);
     constexpr size_t lds_halo = (size_t)(2 * BK * HP) * sizeof(float);
-    constexpr size_t lds_red = (size_t)(WAVES_M * BN * 2) * sizeof(double) + sizeof(int);   // statistics reduction of the epilogue + flag
+    constexpr size_t lds_red = StatScratch<WAVES_M, BN>::BYTES;
     constexpr size_t lds_min = lds_halo > lds_red ? lds_halo : lds_red;
     // workgroups per CU the registers allow (the kernel's __launch_bounds__) and LDS allows
     constexpr int nat = halo_waves(WM, WN, R16);
@@ -1447,7 +1452,10 @@ static void launch_halo_cfg(const dim3 grid, const ConvParams& P, hipStream_t st
 __global__ void __launch_bounds__(256)
 splitk_reduce_kernel(const float* __restrict__ slabs, long slab_stride, int splitk, float* __restrict__ out,
                      long rows, int rows_per_view, int rpw, const ConvParams P) {
-    __shared__ double red[16][64][2];
+    // the statistics scratch, 16 row groups as slots; the arrival flag takes its first word instead of the 16 bytes behind it
+    // (the partials are consumed before the ticket, and this kernel's LDS is the scratch alone)
+    typedef StatScratch<16, 64> Stats;
+    __shared__ double red[16 * 64 * 2];
     double* const stats = P.stats;
     const int c_out = P.c_out, c_out_pad = P.c_out_pad;
     const int tid = threadIdx.x;
@@ -1472,11 +1480,7 @@ splitk_reduce_kernel(const float* __restrict__ slabs, long slab_stride, int spli
         if (!single_view) {     // rows of two views in one workgroup (maps smaller than 16 pixels; rpw = 16 there)
 #pragma unroll
             for (int k = 0; k < 4; k++)
-                if (col + k < c_out) {
-                    double* st = stat_slot(P, (int)(m / rows_per_view), col + k);
-                    atomicAdd(st + 0, (double)vv[k]);
-                    atomicAdd(st + 1, (double)vv[k] * (double)vv[k]);
-                }
+                if (col + k < c_out) stat_add_value(P, (int)(m / rows_per_view), col + k, vv[k]);
         } else {
 #pragma unroll
             for (int k = 0; k < 4; k++) { s1[k] += (double)vv[k]; s2[k] += (double)vv[k] * (double)vv[k]; }
@@ -1486,25 +1490,14 @@ splitk_reduce_kernel(const float* __restrict__ slabs, long slab_stride, int spli
     if (single_view) {
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            red[ry][cq * 4 + k][0] = s1[k];
-            red[ry][cq * 4 + k][1] = s2[k];
+            red[(ry * 64 + cq * 4 + k) * 2 + 0] = s1[k];
+            red[(ry * 64 + cq * 4 + k) * 2 + 1] = s2[k];
         }
-        __syncthreads();
-        if (tid < 64) {
-            const int c = blockIdx.y * 64 + tid;
-            if (c < c_out) {
-                double a = 0.0, b2 = 0.0;
-#pragma unroll
-                for (int r = 0; r < 16; r++) { a += red[r][tid][0]; b2 += red[r][tid][1]; }
-                double* st = stat_slot(P, (int)(r0 / rows_per_view), c);
-                atomicAdd(st + 0, a);
-                atomicAdd(st + 1, b2);
-            }
-        }
+        Stats::publish(P, red, (int)(r0 / rows_per_view), blockIdx.y * 64, tid);
     }
     if (P.arrive) {      // producer-side BatchNorm: one counter for the launch
         const BnArrival a = bn_arrive(P, -1, tid);
-        bn_complete(P, a, -1, tid, reinterpret_cast<int*>(&red[0][0][0]));
+        bn_complete(P, a, -1, tid, reinterpret_cast<int*>(red));
     }
 }
 
@@ -1528,12 +1521,9 @@ bn_finalize_kernel(double* __restrict__ stats, const float* __restrict__ gamma, 
     const int c = i % c_pad;
     float sc = 0.f, sh = 0.f;
     if (c < channels) {
-        const double mean = stats[2 * (size_t)i + 0] / count;
-        double var = stats[2 * (size_t)i + 1] / count - mean * mean;    // biased variance
-        var = var < 0.0 ? 0.0 : var;
-        const double s = (double)gamma[c] / sqrt(var + (double)eps);
-        sc = (float)s;
-        sh = (float)((double)beta[c] - mean * s);
+        const BnAffine a = bn_affine(stats[2 * (size_t)i + 0], stats[2 * (size_t)i + 1], count, gamma[c], beta[c], eps);
+        sc = a.scale;
+        sh = a.shift;
     }
     scale[i] = sc;
     shift[i] = sh;
@@ -1561,17 +1551,10 @@ bn_finalize_batch_kernel(double* __restrict__ stats, const float* __restrict__ g
     float sc = 0.f, sh = 0.f;
     if (c < channels) {
         const double count = count_per_view * (double)nviews;
-        const double mean = s1 / count;
-        double var = s2 / count - mean * mean;
-        var = var < 0.0 ? 0.0 : var;
-        const double s = (double)gamma[c] / sqrt(var + (double)eps);
-        sc = (float)s;
-        sh = (float)((double)beta[c] - mean * s);
-        if (running_mean) running_mean[c] = (float)((1.0 - (double)momentum) * (double)running_mean[c] + (double)momentum * mean);
-        if (running_var) {
-            const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
-            running_var[c] = (float)((1.0 - (double)momentum) * (double)running_var[c] + (double)momentum * unb);
-        }
+        const BnAffine a = bn_affine(s1, s2, count, gamma[c], beta[c], eps);
+        sc = a.scale;
+        sh = a.shift;
+        bn_update_running(a, count, momentum, running_mean, running_var, c);
     }
     for (int n = 0; n < nviews; n++) {
         scale[(size_t)n * c_pad + c] = sc;

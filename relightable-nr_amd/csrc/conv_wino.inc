@@ -50,8 +50,9 @@ constexpr int WINO_BRING = WINO_BDIST < 4 ? 4 : 8;  // weight blocks in register
 constexpr int WINO_STEP_FLOATS = 4 * 2 * 2 * 32 * 4;        // weight image per (column tile, K step): [xi][half][h][32][4]
 constexpr int WINO_XCHG = 4 * 3 * 4 * 64 * 4;       // floats of the epilogue exchange: [finishing wave][source][4 register rows][lane][4]
 
+typedef StatScratch<4, WINO_BN> WinoStats;          // the statistics scratch: one slot per wave, behind the exchange buffer
 __host__ __device__ constexpr size_t wino_lds_bytes() {
-    return (size_t)((2 * WINO_CHUNK > WINO_XCHG ? 2 * WINO_CHUNK : WINO_XCHG) + 4 * WINO_BN * 2 * 2 + 4) * sizeof(float);
+    return (size_t)(2 * WINO_CHUNK > WINO_XCHG ? 2 * WINO_CHUNK : WINO_XCHG) * sizeof(float) + WinoStats::BYTES;
 }
 
 __global__ void __launch_bounds__(CTHREADS, 2)
@@ -264,7 +265,6 @@ conv_wino_kernel(const ConvParams P) {
     else if (xi == 2) exchange(std::integral_constant<int, 2>{});
     else exchange(std::integral_constant<int, 3>{});
 
-    // statistics in float64 from the first addition (see conv_mfma_kernel)
     double s1[2] = {0.0, 0.0}, s2[2] = {0.0, 0.0};
 #pragma unroll
     for (int gq = 0; gq < 4; gq++)
@@ -275,8 +275,7 @@ conv_wino_kernel(const ConvParams P) {
             s2[e >> 1] += a * a + b * b;
         }
     static_assert(WINO_XCHG % 2 == 0, "float64 scratch alignment");
-    double* red = reinterpret_cast<double*>(As + WINO_XCHG);        // [4 waves][64 columns][2], behind the exchange buffer
-    int* flag = reinterpret_cast<int*>(red + 4 * WINO_BN * 2);
+    double* red = WinoStats::red(As + WINO_XCHG);
     const bool with_stats = P.stats != nullptr && P.splitk == 1;
     if (with_stats) {
 #pragma unroll
@@ -288,21 +287,7 @@ conv_wino_kernel(const ConvParams P) {
                 red[(xi * WINO_BN + 32 * nb + l31) * 2 + 1] = s2[nb];
             }
         }
-        __syncthreads();
-        if (tid < WINO_BN) {
-            const int col = n0 + tid;
-            if (col < P.c_out) {
-                double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-                for (int w = 0; w < 4; w++) {
-                    t1 += red[(w * WINO_BN + tid) * 2 + 0];
-                    t2 += red[(w * WINO_BN + tid) * 2 + 1];
-                }
-                double* st = stat_slot(P, n, col);
-                atomicAdd(st + 0, t1);
-                atomicAdd(st + 1, t2);
-            }
-        }
+        WinoStats::publish(P, red, n, n0, tid);
     }
     BnArrival arr = {nullptr, 0u};
     const bool bn = with_stats && P.arrive;
@@ -327,7 +312,7 @@ conv_wino_kernel(const ConvParams P) {
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rsrc, (int)voff[e >> 1], (int)soff, WINO_OUT_AUX);
                 }
     }
-    if (bn) bn_complete(P, arr, n, tid, flag);
+    if (bn) bn_complete(P, arr, n, tid, WinoStats::flag(red));
 }
 
 // Transformed weights U = G g G^T, G = [[1, 0, 0], [1/2, 1/2, 1/2], [1/2, -1/2, 1/2], [0, 0, 1]], computed in float64 and

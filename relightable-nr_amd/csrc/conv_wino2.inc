@@ -197,8 +197,9 @@ struct W2Geo {
 constexpr int W2_BDIST = W2_BDIST_K;                         // K steps between the request of a weight block and its MFMAs
 constexpr int W2_STEP_FLOATS = 2 * 3 * 2 * 2 * 32 * 3;       // weight image per K step: [column half][xi][half][h][32][3]
 
+typedef StatScratch<12, 64> W2Stats;                // the statistics scratch of conv_wino2_epilogue.inc: one slot per wave
 __host__ __device__ constexpr size_t wino2_lds_bytes() {
-    return (size_t)((2 * W2Geo::CHUNK > W2_XCHG ? 2 * W2Geo::CHUNK : W2_XCHG) + 12 * 64 * 2 * 2 + 4) * sizeof(float);
+    return (size_t)(2 * W2Geo::CHUNK > W2_XCHG ? 2 * W2Geo::CHUNK : W2_XCHG) * sizeof(float) + W2Stats::BYTES;
 }
 
 template <int KIND>

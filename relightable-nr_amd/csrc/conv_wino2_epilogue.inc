@@ -3,12 +3,12 @@
 // It is a fragment of the kernel body, not a function: as a __forceinline__ function the compiler simplifies it on its own before
 // inlining and both kernels came out slower (more scalar work, an extra spill in the transposed kernel's K loop; 0.8 % of the
 // 16-view frame).  The including kernel provides: P, KIND, T (W2Tile), acc (floatx16[6], [plane nu][column half]), xi, l31, h,
-// As (its dynamic LDS, dead halo by now) and CHUNK (floats per staged K block).  As holds the exchange rounds, red the
-// [12 waves][64 columns][2] statistics scratch behind them, then the arrival flag.
+// As (its dynamic LDS, dead halo by now) and CHUNK (floats per staged K block).  As holds the exchange rounds, the
+// statistics scratch (a slot per wave) behind them.
 {
 
     static_assert((2 * CHUNK > W2_XCHG ? 2 * CHUNK : W2_XCHG) % 2 == 0, "float64 scratch alignment");
-    double* red = reinterpret_cast<double*>(As + (2 * CHUNK > W2_XCHG ? 2 * CHUNK : W2_XCHG));
+    double* red = W2Stats::red(As + (2 * CHUNK > W2_XCHG ? 2 * CHUNK : W2_XCHG));
     constexpr int BNW = W2Kind<KIND>::BNW;
     const int tid = T.tid, lane = T.lane, n = T.n;
     // rr[g][half] = (r[b = 0], r[b = 1]) of this wave's plane row: r0 = M0 + M1, r1 = M1 - M2
@@ -58,7 +58,6 @@
     else finish(std::integral_constant<int, 2>{});
     const int g0 = xi == 0 ? 0 : (xi == 1 ? 6 : 11), ng = xi == 0 ? 6 : 5;
 
-    // statistics in float64 from the first addition: v and v^2 are exact in double (see conv_mfma_kernel)
     double s1[2] = {0.0, 0.0}, s2[2] = {0.0, 0.0};
 #pragma unroll
     for (int k = 0; k < 6; k++)
@@ -70,7 +69,6 @@
                 s2[nb] += (a * a + b * b) + (c * c + d * d);
             }
         }
-    int* flag = reinterpret_cast<int*>(red + 12 * 64 * 2);
     const bool with_stats = P.stats != nullptr && P.splitk == 1;
     if (with_stats) {
 #pragma unroll
@@ -82,23 +80,10 @@
                 red[(T.wave * 64 + 32 * nb + l31) * 2 + 1] = s2[nb];
             }
         }
-        __syncthreads();
-        if (tid < BNW) {
-            // KIND 2: all twelve waves hold the workgroup's 64 columns; KIND 1: the six waves of column half tid / 64
-            const int col = T.nt * BNW + tid;
-            if (col < P.c_out) {
-                double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-                for (int w = 0; w < 12; w++) {
-                    if (KIND == 1 && ((w / 3) & 1) != (tid >> 6)) continue;
-                    t1 += red[(w * 64 + (tid & 63)) * 2 + 0];
-                    t2 += red[(w * 64 + (tid & 63)) * 2 + 1];
-                }
-                double* st = stat_slot(P, n, col);
-                atomicAdd(st + 0, t1);
-                atomicAdd(st + 1, t2);
-            }
-        }
+        // KIND 2: all twelve waves hold the workgroup's 64 columns; KIND 1: the six waves w with ((w / 3) & 1) == tid / 64
+        // hold column half tid / 64
+        W2Stats::publish<BNW>(P, red, n, T.nt * BNW, tid,
+                            [tid](int j) { return KIND == 1 ? (j / 3) * 6 + (tid >> 6) * 3 + j % 3 : j; });
     }
     BnArrival arr = {nullptr, 0u};
     const bool bn = with_stats && P.arrive;
@@ -131,5 +116,5 @@
                     }
         }
     }
-    if (bn) bn_complete(P, arr, n, tid, flag);
+    if (bn) bn_complete(P, arr, n, tid, W2Stats::flag(red));
 }

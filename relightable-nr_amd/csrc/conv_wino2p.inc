@@ -45,7 +45,7 @@ struct W2PGeo {
 constexpr int W2P_PAIR_FLOATS = 4 * 3 * 2 * 32 * 12;       // weight image per pair-step: [class][xi][h][32][12]
 
 __host__ __device__ constexpr size_t wino2p_lds_bytes() {
-    return (size_t)((2 * W2PGeo::CHUNK > W2_XCHG ? 2 * W2PGeo::CHUNK : W2_XCHG) + 12 * 64 * 2 * 2 + 4) * sizeof(float);
+    return (size_t)(2 * W2PGeo::CHUNK > W2_XCHG ? 2 * W2PGeo::CHUNK : W2_XCHG) * sizeof(float) + W2Stats::BYTES;
 }
 
 template <int KIND>

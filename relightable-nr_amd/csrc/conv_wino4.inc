@@ -72,8 +72,10 @@ static_assert(2 * W4_CHUNK >= W4_XCHG, "the exchange buffer of the epilogue live
 constexpr float W4_A = 0.75f, W4_B = 1.5f, W4_A2 = 0.5625f, W4_B2 = 2.25f, W4_A3 = 0.421875f, W4_B3 = 3.375f;
 constexpr float W4_A2B2 = 1.265625f, W4_A2PB2 = 2.8125f;
 
+typedef StatScratch<12, 32> W4Stats;                // the statistics scratch: one slot per wave, 32 columns each
+
 __host__ __device__ constexpr size_t wino4_lds_bytes() {
-    return (size_t)(2 * W4_CHUNK + 12 * 32 * 2 * 2 + 4 + 2 * W4_BN_MAXC) * sizeof(float);
+    return (size_t)(2 * W4_CHUNK + 2 * W4_BN_MAXC) * sizeof(float) + W4Stats::BYTES;
 }
 
 // B^T applied to six values (both directions of the input transform)
@@ -143,7 +145,7 @@ conv_wino4_kernel(const ConvParams P) {
     const int per_split = (nchunks + P.splitk - 1) / P.splitk;
     const int c_begin = z_ * per_split, c_end = min(nchunks, c_begin + per_split);
     struct ChunkSrc { __amdgpu_buffer_rsrc_t rsrc; unsigned C; unsigned soff; int act; float4 sc, sh; const float2* bn; };
-    float2* s_bn = reinterpret_cast<float2*>(As + 2 * W4_CHUNK + 12 * 32 * 2 * 2 + 4);    // [padded input channel] (scale, shift), behind the float64 statistics scratch
+    float2* s_bn = reinterpret_cast<float2*>(As + 2 * W4_CHUNK + W4Stats::BYTES / sizeof(float));    // [padded input channel] (scale, shift), behind the float64 statistics scratch
     auto chunk_src = [&](int c, bool in_loop) {
         ChunkSrc cs;
         const int s = c < P.chunks0 ? 0 : 1;
@@ -382,7 +384,6 @@ conv_wino4_kernel(const ConvParams P) {
     else finish(std::integral_constant<int, 5>{});
     const int g0 = xi < 4 ? 3 * xi : 12 + 2 * (xi - 4), ng = xi < 4 ? 3 : 2;
 
-    // statistics in float64 from the first addition: v and v^2 are exact in double (see conv_mfma_kernel)
     double s1 = 0.0, s2 = 0.0;
 #pragma unroll
     for (int k = 0; k < 3; k++)
@@ -392,8 +393,7 @@ conv_wino4_kernel(const ConvParams P) {
 #pragma unroll
                 for (int b = 0; b < 4; b++) { const double v = yv[k][a][b]; s1 += v; s2 += v * v; }
     static_assert(W4_CHUNK % 2 == 0, "float64 scratch alignment");
-    double* red = reinterpret_cast<double*>(As + 2 * W4_CHUNK);         // [12 waves][32 columns][2], behind the image / exchange buffers
-    int* flag = reinterpret_cast<int*>(red + 12 * 32 * 2);
+    double* red = W4Stats::red(As + 2 * W4_CHUNK);         // behind the image / exchange buffers
     const bool with_stats = P.stats != nullptr && P.splitk == 1;
     if (with_stats) {
         s1 += __shfl_xor(s1, 32, 64);
@@ -402,21 +402,8 @@ conv_wino4_kernel(const ConvParams P) {
             red[(wave * 32 + l31) * 2 + 0] = s1;
             red[(wave * 32 + l31) * 2 + 1] = s2;
         }
-        __syncthreads();
-        if (tid < W4_BN) {
-            const int col = nt_ * W4_BN + tid;
-            if (col < P.c_out) {
-                double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-                for (int w = 0; w < 6; w++) {       // the six plane-row waves of column half tid >> 5
-                    t1 += red[(((tid >> 5) * 6 + w) * 32 + (tid & 31)) * 2 + 0];
-                    t2 += red[(((tid >> 5) * 6 + w) * 32 + (tid & 31)) * 2 + 1];
-                }
-                double* st = stat_slot(P, n, col);
-                atomicAdd(st + 0, t1);
-                atomicAdd(st + 1, t2);
-            }
-        }
+        // the six plane-row waves of column half tid >> 5
+        W4Stats::publish<W4_BN>(P, red, n, nt_ * W4_BN, tid, [tid](int j) { return (tid >> 5) * 6 + j; });
     }
     BnArrival arr = {nullptr, 0u};
     const bool bn = with_stats && P.arrive;
@@ -441,7 +428,7 @@ conv_wino4_kernel(const ConvParams P) {
                 }
         }
     }
-    if (bn) bn_complete(P, arr, n, tid, flag);
+    if (bn) bn_complete(P, arr, n, tid, W4Stats::flag(red));
 #if W4_PREFETCH
 #pragma unroll
     for (int j = 0; j < W4_PF_TOUCH; j++) asm volatile("" :: "v"(pf[j]));

@@ -36,8 +36,9 @@ constexpr int W80_STEP_FLOATS = 4 * 5 * 4 * 16 * 4; // weight image per K step: 
 constexpr int W80_XCHG = 4 * 3 * 5 * 64 * 2;        // floats of the epilogue exchange: [finishing wave][source][block][lane][2]
 
 __host__ __device__ constexpr int w80_plane_off(int p) { return p * W80_PLANE + (p >> 2) * 8; }
+typedef StatScratch<4, 80> W80Stats;                // the statistics scratch: one slot per wave
 __host__ __device__ constexpr size_t wino80_lds_bytes() {
-    return (size_t)((2 * W80_CHUNK > W80_XCHG ? 2 * W80_CHUNK : W80_XCHG) + 4 * 80 * 2 * 2 + 4) * sizeof(float);
+    return (size_t)(2 * W80_CHUNK > W80_XCHG ? 2 * W80_CHUNK : W80_XCHG) * sizeof(float) + W80Stats::BYTES;
 }
 
 __global__ void __launch_bounds__(CTHREADS, 2)
@@ -247,13 +248,11 @@ conv_wino80_kernel(const ConvParams P) {
     else exchange(std::integral_constant<int, 3>{});
 
     static_assert((2 * W80_CHUNK > W80_XCHG ? 2 * W80_CHUNK : W80_XCHG) % 2 == 0, "float64 scratch alignment");
-    double* red = reinterpret_cast<double*>(As + (2 * W80_CHUNK > W80_XCHG ? 2 * W80_CHUNK : W80_XCHG));        // [4 waves][80 columns][2]
-    int* flag = reinterpret_cast<int*>(red + 4 * 80 * 2);
+    double* red = W80Stats::red(As + (2 * W80_CHUNK > W80_XCHG ? 2 * W80_CHUNK : W80_XCHG));
     const bool with_stats = P.stats != nullptr;
     if (with_stats) {
 #pragma unroll
         for (int b = 0; b < 5; b++) {
-            // float64 from the first addition: v and v^2 are exact in double (see conv_mfma_kernel)
             const double p = y0v[b].x, q = y0v[b].y, r = y1v[b].x, t = y1v[b].y;
             double s1 = (p + q) + (r + t);
             double s2 = (p * p + q * q) + (r * r + t * t);
@@ -264,18 +263,7 @@ conv_wino80_kernel(const ConvParams P) {
                 red[(xi * 80 + 16 * b + l15) * 2 + 1] = s2;
             }
         }
-        __syncthreads();
-        if (tid < 80 && tid < P.c_out) {
-            double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-            for (int w = 0; w < 4; w++) {
-                t1 += red[(w * 80 + tid) * 2 + 0];
-                t2 += red[(w * 80 + tid) * 2 + 1];
-            }
-            double* st = stat_slot(P, n, tid);
-            atomicAdd(st + 0, t1);
-            atomicAdd(st + 1, t2);
-        }
+        W80Stats::publish(P, red, n, 0, tid);
     }
     BnArrival arr = {nullptr, 0u};
     const bool bn = with_stats && P.arrive;
@@ -297,7 +285,7 @@ conv_wino80_kernel(const ConvParams P) {
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(e ? yy.y : yy.x), rsrc, (int)voff, (int)soff, WINO_OUT_AUX);
                 }
     }
-    if (bn) bn_complete(P, arr, n, tid, flag);
+    if (bn) bn_complete(P, arr, n, tid, W80Stats::flag(red));
 }
 
 // Transformed weights U = G g G^T (as pack_weight_wino_kernel) in the layout of conv_wino80_kernel:
