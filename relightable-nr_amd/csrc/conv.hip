@@ -21,7 +21,8 @@
 // product path since r03, RNR_CONV_WINOGRAD — the fp32 Winograd kernels of conv_wino.inc (F(2x2, 3x3): conv_wino_kernel),
 // conv_wino80.inc (the 80-column out layer), conv_wino2.inc / conv_wino2p.inc (F(2x2, 2x2): conv_wino2_kernel<1> for the
 // stride-2 convolution, conv_wino2p_kernel<2> for the transposed one) and conv_wino4.inc (F(4x4, 3x3), RNR_CONV_WINOGRAD4).
-// make_plan() picks the kernel, the tile shape (256x64, 256x80, 128x128 or 256x128 rows x columns) and the split-K depth.
+// Host side: CONV_TILES lists every instantiation of these kernels with its tile shape and launcher; plan_conv() tries the
+// candidates (try_wino80 ... try_gather) in priority order and returns the row, the grid and the split-K depth of one call.
 // Split-K grids write one partial-output slab per slice; splitk_reduce_kernel adds them in slice order.
 #include "rnr_internal.h"
 
@@ -41,10 +42,10 @@ constexpr int CTHREADS = 256;
 #define RNR_SPLITK_TARGET 512       // 256-tile layers at one view per call
 #endif
 #ifndef RNR_SMALL_TILE_BELOW
-#define RNR_SMALL_TILE_BELOW 128     // fewer 128 x 128 tiles than this: 64 x 64 tiles (make_plan)
+#define RNR_SMALL_TILE_BELOW 128     // fewer 128 x 128 tiles than this: 64 x 64 tiles (try_halo)
 #endif
 #ifndef RNR_CFG4_MAX
-#define RNR_CFG4_MAX 512             // at most this many 128 x 128 tiles: 128 x 64 tiles instead (make_plan, 3x3 only); 0 = never
+#define RNR_CFG4_MAX 512             // at most this many 128 x 128 tiles: 128 x 64 tiles instead (try_halo, 3x3 only); 0 = never
 #endif
 #ifndef RNR_CFG0_SMALL_MAX
 #define RNR_CFG0_SMALL_MAX 1024      // at most this many 256 x 64 tiles (one 512^2 view): 128 x 64 tiles, four waves per SIMD, instead
@@ -61,11 +62,41 @@ constexpr int CTHREADS = 256;
 #ifndef RNR_HALO_WAVES
 #define RNR_HALO_WAVES 3    // waves per SIMD the halo kernels are register-bounded for (4 would spill and exceed LDS anyway)
 #endif
+#ifndef RNR_WINO_SPLIT_MIN_CHUNKS
+#define RNR_WINO_SPLIT_MIN_CHUNKS 4     // 16-channel chunks per split-K slice of a Winograd kernel, at least
+#define RNR_WINO_SPLIT_MIN_WGS 192      // workgroups a split Winograd grid must reach (128: the 64^2 stride-2 and 16^2 transposed layers at one view lose 7 - 14 us)
+#endif
+#ifndef RNR_WINO2_MIN_WGS
+#define RNR_WINO2_MIN_WGS 200        // fewer workgroups (one per CU) than this: the direct kernels
+#endif
+#ifndef RNR_WINO4_SPLIT_MIN_CHUNKS
+#define RNR_WINO4_SPLIT_MIN_CHUNKS 4    // 16-channel chunks per split-K slice of conv_wino4_kernel, at least
+#endif
+#ifndef RNR_WINO4_MIN_WGS
+#define RNR_WINO4_MIN_WGS 256        // fewer 32 x 16 pixel x 64 column tiles than this (one 12-wave workgroup per CU): F(2x2, 3x3)
+#endif
+#ifndef RNR_WINO_MIN_WGS
+#define RNR_WINO_MIN_WGS 256         // fewer 16 x 8 pixel x 64 column tiles than this: the direct kernels (they split K)
+#endif
 
-// an integer override from the environment (experiments), or `dflt`; callers cache it in a function-local static
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
+// The experiment overrides: every threshold above that has one reads it from the environment ONCE, here (scripts/layer_time.py;
+// the -D macros of the same names set the defaults, scripts/mkvariant.sh).
+struct ConvTuning {
+    int splitk_below, splitk_target;        // direct kernels: grids below `below` workgroups are split over K towards `target`
+    int cfg4_max, cfg0_small_max;           // direct kernels: the 128 x 64 tiles (try_halo)
+    int wino_min_wgs, wino2_min_wgs, wino4_min_wgs;     // smallest unsplit grid of F(2x2, 3x3), F(2x2, 2x2), F(4x4, 3x3)
+    int wino_splitk;                        // 0: no split-K Winograd grids
+    int par_inner;                          // 0 / 1: order of the transposed convolution's parity classes, -1: by operand size (conv_params)
+    int halo_slots;                         // > 0: workgroups per CU of the halo kernels (balanced_slots)
+};
+static const ConvTuning& tuning() {
+    auto env = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+    static const ConvTuning t = {env("RNR_SPLITK_BELOW", RNR_SPLITK_BELOW), env("RNR_SPLITK_TARGET", RNR_SPLITK_TARGET),
+                                 env("RNR_CFG4_MAX", RNR_CFG4_MAX), env("RNR_CFG0_SMALL_MAX", RNR_CFG0_SMALL_MAX),
+                                 env("RNR_WINO_MIN_WGS", RNR_WINO_MIN_WGS), env("RNR_WINO2_MIN_WGS", RNR_WINO2_MIN_WGS),
+                                 env("RNR_WINO4_MIN_WGS", RNR_WINO4_MIN_WGS), env("RNR_WINO_SPLITK", 1),
+                                 env("RNR_PAR_INNER", -1), env("RNR_HALO_SLOTS", 0)};
+    return t;
 }
 
 // waves per SIMD a halo-kernel configuration is register-bounded for: 128 x 64 tiles (32 accumulator registers) four, the
@@ -732,7 +763,7 @@ conv_halo_kernel(const ConvParams P) {
     const int c_end = min(nchunks, c_begin + per_split);
 
     // view base + channel offset are wave-uniform (SGPR pair); the per-lane part is a 32-bit element offset
-    // (make_plan keeps H*W*C below 2^30), so a halo fetch is one global_load_dwordx4 v, voff, s[base] and one VALU mad.
+    // (plan_conv keeps H*W*C below 2^30), so a halo fetch is one global_load_dwordx4 v, voff, s[base] and one VALU mad.
     // (buffer loads: resource + scalar offset + one 32-bit lane offset; flat 64-bit addresses make the unrolled tap loop
     // keep a strength-reduced pointer pair per (tap, plane) alive across the chunk loop — registers the kernel lacks)
     // K steps: step = chunk * NPH + phase
@@ -1407,7 +1438,7 @@ static void launch_halo_emu_cfg(const dim3 grid, const ConvParams& P, hipStream_
 // eff = 0.55 / 0.86 / 0.90 for r = 1 / 2 / 3; pick the slot count (<= what registers and LDS allow) with the smallest
 // total.  Large grids (>= 4 rounds) keep the maximum.  RNR_HALO_SLOTS=k forces k (experiments).
 static int balanced_slots(long tiles, int max_slots) {
-    static const int forced = env_int("RNR_HALO_SLOTS", 0);
+    const int forced = tuning().halo_slots;
     if (forced > 0) return forced < max_slots ? forced : max_slots;
     const long n = (tiles + 255) / 256;            // tiles per CU (256 CUs)
     if (n >= 4L * max_slots || max_slots <= 1) return max_slots;
@@ -1678,48 +1709,125 @@ __global__ void __launch_bounds__(256) active_tile_kernel(const float* __restric
     if (threadIdx.x == 0) mask[mt] = any ? 1 : 0;
 }
 
-struct ConvPlan {
-    int halo;       // 1: conv3x3_halo_kernel (2-D pixel tiles), 0: conv_mfma_kernel (linear pixel tiles)
-    int wino;       // 4: conv_wino4_kernel (F(4x4, 3x3), 32 x 16 pixel tiles x 64 columns), 3: conv_wino80_kernel (F(2x2, 3x3) for the 80-column out layer, 16 x 4 pixel tiles),
-                    // 1: conv_wino_kernel (Winograd F(2x2, 3x3), 16 x 8 pixel tiles x 64 columns), 2: conv_wino2_kernel (F(2x2, 2x2),
-                    // the 4x4 stride-2 convolutions: 16 x 8 tiles of the GEMM row space x 128 (conv) / 64 (transposed) columns)
-    int cfg;        // column config 0: 64, 1: 96 (gather) / 80 (halo) / 96 (emulation), 2: 128; rows = bm (64 ... 256)
-    int bm, bn, mtiles, ntiles, par, splitk;
-    int tw;         // pixel-tile width of the halo plan: 32, or 16 (maps 16 pixels wide)
-    int Ho, Wo, OH, OW, M;
-    int taps, chunks_per_tap, kt_total;
-};
-
 __global__ void __launch_bounds__(256) zero_f64_kernel(double* __restrict__ p, long n) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i < n) p[i] = 0.0;
 }
 
-#ifndef RNR_WINO_SPLIT_MIN_CHUNKS
-#define RNR_WINO_SPLIT_MIN_CHUNKS 4     // 16-channel chunks per split-K slice of a Winograd kernel, at least
-#define RNR_WINO_SPLIT_MIN_WGS 192      // workgroups a split Winograd grid must reach (128: the 64^2 stride-2 and 16^2 transposed layers at one view lose 7 - 14 us)
-#endif
-#ifndef RNR_WINO2_MIN_WGS
-#define RNR_WINO2_MIN_WGS 200        // fewer workgroups (one per CU) than this: the direct kernels
-#endif
-#ifndef RNR_WINO4_SPLIT_MIN_CHUNKS
-#define RNR_WINO4_SPLIT_MIN_CHUNKS 4    // 16-channel chunks per split-K slice of conv_wino4_kernel, at least
-#endif
-#ifndef RNR_WINO4_MIN_WGS
-#define RNR_WINO4_MIN_WGS 256        // fewer 32 x 16 pixel x 64 column tiles than this (one 12-wave workgroup per CU): F(2x2, 3x3)
-#endif
-#ifndef RNR_WINO_MIN_WGS
-#define RNR_WINO_MIN_WGS 256         // fewer 16 x 8 pixel x 64 column tiles than this: the direct kernels (they split K)
-#endif
+// ---- host side: one table from tile to kernel, one plan per call ---------------------------------------------------------
+
+enum ConvFamily { GATHER, HALO, HALO_EMU, WINO, WINO80, WINO2, WINO2T, WINO4 };
+static const int CONV_ALGORITHM[] = {0, 0, 0, 1, 3, 2, 2, 4};       // what rnr_conv_algorithm reports, by family
+typedef void (*ConvLaunch)(const dim3, const ConvParams&, hipStream_t);
+
+// A kernel instantiation per (row, emulation format, kind).  The planner takes its tiles from CONV_TILES and the launch calls
+// the row's launcher, so a plan names a kernel that exists, and its grid is counted from the tile that kernel was built for.
+struct ConvTile {
+    ConvFamily family;
+    int tw, th, bn;             // pixel tile and columns (80: 64 + a 16-column remainder tile); GATHER: tw consecutive GEMM rows
+    ConvLaunch launch[2][3];    // [HALO_EMU: 0 bf16x6, 1 f16x3; the others: 0][kind], null where there is no such instantiation
+};
+
+template <int KIND, int WAVES_M, int WAVES_N, int WM, int WN>
+static void launch_gather_cfg(const dim3 grid, const ConvParams& P, hipStream_t st) {
+    hipLaunchKernelGGL((conv_mfma_kernel<KIND, WAVES_M, WAVES_N, WM, WN>), grid, dim3(CTHREADS), 0, st, P);
+}
+template <int WAVES_M, int WAVES_N, int WM, int WN>
+static ConvTile gather_tile() {
+    return {GATHER, WAVES_M * WM * 32, 1, WAVES_N * WN * 32,
+            {{launch_gather_cfg<0, WAVES_M, WAVES_N, WM, WN>, launch_gather_cfg<1, WAVES_M, WAVES_N, WM, WN>,
+              launch_gather_cfg<2, WAVES_M, WAVES_N, WM, WN>}, {}}};
+}
+template <int WAVES_M, int WAVES_N, int WM, int WN, int R16, int TW = 32>
+static ConvTile halo_tile() {
+    return {HALO, TW, WAVES_M * WM * (32 / TW), WAVES_N * (WN * 32 + R16 * 16),
+            {{launch_halo_cfg<0, WAVES_M, WAVES_N, WM, WN, R16, TW>, launch_halo_cfg<1, WAVES_M, WAVES_N, WM, WN, R16, TW>,
+              launch_halo_cfg<2, WAVES_M, WAVES_N, WM, WN, R16, TW>}, {}}};
+}
+template <int KINDS, int KIND, int WAVES_M, int WAVES_N, int WM, int WN, int TW>     // KINDS: bit k set = instantiated for kind k
+static void emu_launchers(ConvTile& t) {
+    if constexpr ((KINDS >> KIND) & 1) {
+        t.launch[0][KIND] = launch_halo_emu_cfg<0, KIND, WAVES_M, WAVES_N, WM, WN, TW>;
+        t.launch[1][KIND] = launch_halo_emu_cfg<1, KIND, WAVES_M, WAVES_N, WM, WN, TW>;
+    }
+}
+template <int KINDS, int WAVES_M, int WAVES_N, int WM, int WN, int TW = 32>
+static ConvTile emu_tile() {
+    ConvTile t = {HALO_EMU, TW, WAVES_M * WM * (32 / TW), WAVES_N * WN * 32, {}};
+    emu_launchers<KINDS, 0, WAVES_M, WAVES_N, WM, WN, TW>(t);
+    emu_launchers<KINDS, 1, WAVES_M, WAVES_N, WM, WN, TW>(t);
+    emu_launchers<KINDS, 2, WAVES_M, WAVES_N, WM, WN, TW>(t);
+    return t;
+}
+
+static const ConvTile CONV_TILES[] = {
+    gather_tile<4, 1, 2, 2>(),                  // 256 rows x 64 columns
+    gather_tile<4, 1, 2, 3>(),                  // 256 x 96 (65 ... 80 columns)
+    gather_tile<2, 2, 2, 2>(),                  // 128 x 128
+    halo_tile<4, 1, 2, 2, 0>(),                 // 32 x 8 pixels x 64 columns, three waves per SIMD
+    halo_tile<4, 1, 2, 2, 1>(),                 // 32 x 8 x 80
+    halo_tile<2, 2, 4, 2, 0>(),                 // 32 x 8 x 128, two waves per SIMD
+    halo_tile<2, 2, 2, 2, 0>(),                 // 32 x 4 x 128
+    halo_tile<4, 1, 1, 2, 0>(),                 // 32 x 4 x 64, 32 accumulator registers, four waves per SIMD
+    halo_tile<2, 2, 1, 1, 0>(),                 // 32 x 2 x 64, one MFMA block per wave
+    halo_tile<2, 2, 2, 2, 0, 16>(),             // 16 x 8 x 128 (two image rows per 32-row MFMA block)
+    halo_tile<2, 2, 1, 1, 0, 16>(),             // 16 x 4 x 64
+    emu_tile<5, 4, 1, 2, 2>(),                  // 32 x 8 x 64
+    emu_tile<5, 4, 1, 2, 3>(),                  // 32 x 8 x 96 (65 ... 80 columns)
+    emu_tile<7, 2, 2, 4, 2>(),                  // 32 x 8 x 128
+    emu_tile<7, 2, 2, 2, 2>(),                  // 32 x 4 x 128
+    emu_tile<2, 2, 2, 1, 2>(),                  // 32 x 2 x 128: the stride-2 convolution only, maps whose height 4 does not divide
+    emu_tile<7, 2, 2, 2, 2, 16>(),              // 16 x 8 x 128
+    {WINO80, W80_PW, W80_PH, 80, {{launch_wino80, nullptr, nullptr}, {}}},          // F(2x2, 3x3), the 80-column out layer
+    {WINO4, W4_PW, W4_PH, W4_BN, {{launch_wino4, nullptr, nullptr}, {}}},           // F(4x4, 3x3)
+    {WINO, WINO_PW, WINO_PH, WINO_BN, {{launch_wino, nullptr, nullptr}, {}}},       // F(2x2, 3x3)
+    {WINO2, WINO_PW, 16, 128, {{nullptr, launch_wino2, nullptr}, {}}},              // F(2x2, 2x2) stride 2: 16 x 16 output pixels
+    {WINO2T, WINO_PW, WINO_PH, 64, {{nullptr, nullptr, launch_wino2p}, {}}},        // ... transposed: the four parity classes of 16 x 8 input pixels
+};
+
+static ConvLaunch tile_launcher(const ConvTile& t, const rnr_conv_desc* d) {
+    if (d->kind < 0 || d->kind > 2) return nullptr;
+    return t.launch[t.family == HALO_EMU && (d->flags & RNR_CONV_F32_EMU_F16X3) ? 1 : 0][d->kind];
+}
+
+// the row of that family and tile which has a kernel for this descriptor's kind (null: none)
+static const ConvTile* find_tile(ConvFamily family, const rnr_conv_desc* d, int tw, int th, int bn) {
+    for (const ConvTile& t : CONV_TILES)
+        if (t.family == family && t.tw == tw && t.th == th && t.bn == bn && tile_launcher(t, d)) return &t;
+    return nullptr;
+}
+
+struct ConvPlan {
+    const ConvTile* tile;       // the kernel that runs (null: unknown kind)
+    int mtiles, ntiles, par, splitk;
+    long wgs() const { return (long)mtiles * ntiles * par; }     // workgroups of one K slice
+    bool maskable;              // the launch takes a tile mask of `mtiles` entries (rnr_conv_tile_count)
+    int N, Ho, Wo, OH, OW, M;
+    int taps, chunks_per_tap, kt_total;
+};
+enum ConvMode { CONV_PLAIN, CONV_MASKED, CONV_RAY };      // what the launch carries: nothing, a tile mask, the ray-renderer epilogue (+ a mask)
+
+// geometry `g` with the grid of one K slice on tile `t`: THE place tiles are counted.  The transposed convolution's four parity
+// classes are workgroups of their own in the direct kernels.
+static ConvPlan grid_of(const ConvTile& t, const rnr_conv_desc* d, ConvPlan g) {
+    g.tile = &t;
+    g.mtiles = t.family == GATHER ? (g.M + t.tw - 1) / t.tw : g.N * (g.Ho / t.th) * (g.Wo / t.tw);
+    g.ntiles = (d->c_out_pad + t.bn - 1) / t.bn;
+    g.par = d->kind == RNR_CONVT4x4S2 && t.family <= HALO_EMU ? 4 : 1;
+    return g;
+}
+// all pixels of a tile lie inside the map
+static bool fits(const ConvTile& t, const ConvPlan& g) { return g.Wo % t.tw == 0 && g.Ho % t.th == 0 && g.Ho >= t.th; }
+
+struct ConvChoice { const ConvTile* tile; int splitk; };          // tile null: the shape does not qualify
+static const ConvChoice NO_CHOICE = {nullptr, 0};
 
 // split depth of a Winograd grid of `wgs` workgroups (0: too small even when split — the direct kernels).  Below `min_wgs`
 // the K loop is cut into slices whose partial outputs splitk_reduce_kernel adds: at least `min_chunks` chunks per slice, at
 // most 8 slices, and the split grid must reach `reach` workgroups.  RNR_WINO_SPLITK=0 in the environment disables the split.
-static int wino_splitk(long wgs, int min_wgs, int chunks, int min_chunks = RNR_WINO_SPLIT_MIN_CHUNKS,
-                       int reach = RNR_WINO_SPLIT_MIN_WGS) {
+static int wino_splitk(long wgs, int min_wgs, int chunks, int min_chunks, int reach) {
     if (wgs >= min_wgs) return 1;
-    static const int enabled = env_int("RNR_WINO_SPLITK", 1);
-    if (!enabled || wgs <= 0) return 0;
+    if (!tuning().wino_splitk || wgs <= 0) return 0;
     int sk = (int)((min_wgs + wgs - 1) / wgs);
     const int max_sk = chunks / min_chunks < 8 ? chunks / min_chunks : 8;
     if (sk > max_sk) sk = max_sk;
@@ -1734,212 +1842,159 @@ static int wino_splitk(long wgs, int min_wgs, int chunks, int min_chunks = RNR_W
     return sk;
 }
 
-static int make_plan(const rnr_conv_desc* d, int N, int H, int W, ConvPlan* p) {
-    p->wino = 0;
-    p->taps = d->kind == RNR_CONV3x3_REFLECT ? 9 : (d->kind == RNR_CONV4x4S2_REFLECT ? 16 : 4);
-    p->par = d->kind == RNR_CONVT4x4S2 ? 4 : 1;
-    if (d->kind == RNR_CONV3x3_REFLECT) { p->Ho = H; p->Wo = W; p->OH = H; p->OW = W; }
-    else if (d->kind == RNR_CONV4x4S2_REFLECT) { p->Ho = H / 2; p->Wo = W / 2; p->OH = H / 2; p->OW = W / 2; }
-    else { p->Ho = H; p->Wo = W; p->OH = 2 * H; p->OW = 2 * W; }
-    p->M = N * p->Ho * p->Wo;
-    p->chunks_per_tap = (d->c_in0_pad + d->c_in1_pad) / BK;
-    p->kt_total = p->taps * p->chunks_per_tap;
-    // cfg 1: 256 x 96 columns in the gather kernel, 256 x 80 (64 + a 16-column remainder tile) in the halo kernel
-    if (d->c_out_pad <= 64) { p->cfg = 0; p->bm = 256; p->bn = 64; }
-    else if (d->c_out_pad <= 80) { p->cfg = 1; p->bm = 256; p->bn = 96; }
-    else { p->cfg = 2; p->bm = 128; p->bn = 128; }
-    p->mtiles = (p->M + p->bm - 1) / p->bm;
-    p->ntiles = (d->c_out_pad + p->bn - 1) / p->bn;
-    // halo kernels: 32 x th tiles of the GEMM row space, all tile pixels inside the map.  The 4x4-s2 convolution runs
-    // on the 128-column configuration.
-    if (d->kind == RNR_CONV4x4S2_REFLECT && p->cfg != 2 && p->Wo % 32 == 0 && p->Ho % 4 == 0) {
-        p->cfg = 2; p->bm = 128; p->bn = 128;
-        p->mtiles = (p->M + p->bm - 1) / p->bm;
-        p->ntiles = (d->c_out_pad + p->bn - 1) / p->bn;
-    }
-    // bf16x6 emulation: 256 x 128 tiles (32 x 8 pixels, two waves per SIMD) halve the weight traffic and barriers per MFMA
-    if ((d->flags & RNR_CONV_F32_EMU_ANY) && p->cfg == 2 && d->kind != RNR_CONV4x4S2_REFLECT && p->Wo % 32 == 0 &&
-        p->Ho % 8 == 0) {
-        p->bm = 256;
-        p->mtiles = (p->M + p->bm - 1) / p->bm;
-    }
-    // exact-fp32 kernels: 256 x 128 tiles (two waves per SIMD, half the weight traffic and barriers per MFMA) once there
-    // are enough of them to fill the 256 CUs twice over; below that the 128 x 128 tiles keep more CUs busy
-    if (!(d->flags & RNR_CONV_F32_EMU_ANY) && p->cfg == 2 && p->Wo % 32 == 0 &&
-        p->Ho % 8 == 0 && (long)(p->M / 256) * p->ntiles * p->par >= RNR_NATIVE_BIG_MIN) {
-        p->bm = 256;
-        p->mtiles = (p->M + p->bm - 1) / p->bm;
-    }
-    // ... the emulated 4x4-s2 convolution runs per input parity phase (conv_halo_emu_kernel): 256-, 128- or 64-row tiles
-    if ((d->flags & RNR_CONV_F32_EMU_ANY) && d->kind == RNR_CONV4x4S2_REFLECT && p->cfg == 2 && p->Wo % 32 == 0 &&
-        p->Ho % 2 == 0) {
-        p->bm = p->Ho % 8 == 0 ? 256 : (p->Ho % 4 == 0 ? 128 : 64);
-        p->mtiles = (p->M + p->bm - 1) / p->bm;
-    }
-    int th = p->bm / 32;
-    p->tw = 32;
-    p->halo = (p->Wo % 32 == 0 && p->Ho % th == 0 && p->Ho >= th) ? 1 : 0;
-    // maps 16 pixels wide: 16 x 8 pixel tiles (two image rows per 32-row MFMA block), 128 columns
-    if (!p->halo && p->Wo % 32 != 0 && p->Wo % 16 == 0 && p->Ho % 8 == 0) {
-        p->tw = 16; p->cfg = 2; p->bm = 128; p->bn = 128; th = 8;
-        p->ntiles = (d->c_out_pad + p->bn - 1) / p->bn;
-        p->halo = 1;
-    }
-    // exact-fp32 kernels, small maps (the 32^2 / 16^2 layers at one view per call): when 128 x 128 tiles would have to split
+// a Winograd kernel qualifies when the descriptor opts in, the map tiles into its pixel tiles and the columns into its column
+// tiles, and the grid — split over K if need be — fills the chip
+static ConvChoice wino_choice(const ConvTile* t, const rnr_conv_desc* d, const ConvPlan& g, int min_wgs,
+                              int min_chunks = RNR_WINO_SPLIT_MIN_CHUNKS, int reach = RNR_WINO_SPLIT_MIN_WGS) {
+    if (!(d->flags & RNR_CONV_WINOGRAD) || !t || d->c_out_pad % t->bn != 0 || !fits(*t, g)) return NO_CHOICE;
+    const int sk = wino_splitk(grid_of(*t, d, g).wgs(), min_wgs, g.chunks_per_tap, min_chunks, reach);
+    return sk > 0 ? ConvChoice{t, sk} : NO_CHOICE;
+}
+
+// the 80-column out layer on the 16 x 16 x 4 instruction: 16 x 4 pixel tiles x all 80 columns (conv_wino80_kernel; no split-K form)
+static ConvChoice try_wino80(const rnr_conv_desc* d, const ConvPlan& g) {
+    const ConvTile* t = find_tile(WINO80, d, W80_PW, W80_PH, 80);
+    if (!(d->flags & RNR_CONV_WINOGRAD) || !t || d->c_out_pad != 80 || !fits(*t, g)) return NO_CHOICE;
+    return grid_of(*t, d, g).wgs() >= tuning().wino_min_wgs ? ConvChoice{t, 1} : NO_CHOICE;
+}
+// F(4x4, 3x3) (opt-in, RNR_CONV_WINOGRAD4): 32 x 16 pixel tiles x 64 columns, one 12-wave workgroup per CU — when the grid gives
+// every CU a workgroup (RNR_WINO4_MIN_WGS).  Small grids are cut over K like the F(2x2, .) ones — slices of >=
+// RNR_WINO4_SPLIT_MIN_CHUNKS chunks, at most 8 — and the split grid must give every CU its workgroup again.
+static ConvChoice try_wino4(const rnr_conv_desc* d, const ConvPlan& g) {
+    if (!(d->flags & RNR_CONV_WINOGRAD4) || d->c_in0_pad + d->c_in1_pad > W4_BN_MAXC)     // the kernel's LDS table of BatchNorm scale / shift holds that many channels
+        return NO_CHOICE;
+    return wino_choice(find_tile(WINO4, d, W4_PW, W4_PH, W4_BN), d, g, tuning().wino4_min_wgs, RNR_WINO4_SPLIT_MIN_CHUNKS,
+                       tuning().wino4_min_wgs);
+}
+// Winograd F(2x2, 3x3): every 3x3 layer whose map tiles into 16 x 8 pixels and whose columns into 64s, when there are enough
+// tiles to give every CU two (RNR_WINO_MIN_WGS)
+static ConvChoice try_wino(const rnr_conv_desc* d, const ConvPlan& g) {
+    return wino_choice(find_tile(WINO, d, WINO_PW, WINO_PH, WINO_BN), d, g, tuning().wino_min_wgs);
+}
+// Winograd F(2x2, 2x2) for the 4x4 stride-2 convolutions: 16 x 16 output pixels x 128 columns (convolution) or the four
+// parity classes of 16 x 8 input pixels x 64 columns (transposed) per workgroup (RNR_WINO2_MIN_WGS: one workgroup per CU)
+static ConvChoice try_wino2(const rnr_conv_desc* d, const ConvPlan& g) {
+    const ConvTile* t = d->kind == RNR_CONVT4x4S2 ? find_tile(WINO2T, d, WINO_PW, WINO_PH, 64) : find_tile(WINO2, d, WINO_PW, 16, 128);
+    return wino_choice(t, d, g, tuning().wino2_min_wgs);
+}
+
+// the 4x4 stride-2 convolution runs on the 128-column configuration of the direct kernels whatever its column count
+static bool wide_columns(const rnr_conv_desc* d, const ConvPlan& g) {
+    return d->c_out_pad > 80 || (d->kind == RNR_CONV4x4S2_REFLECT && g.Wo % 32 == 0 && g.Ho % 4 == 0);
+}
+
+// split depth of a direct grid: fewer workgroups than ~2-3 per CU are split over K so the 256 CUs stay filled
+// (RNR_SPLITK_BELOW / RNR_SPLITK_TARGET); `units`: what a slice is made of
+static ConvChoice direct_choice(const ConvTile* t, const rnr_conv_desc* d, const ConvPlan& g) {
+    const long tiles = grid_of(*t, d, g).wgs();
+    if (tiles >= tuning().splitk_below || tiles <= 0) return {t, 1};
+    int sk = (int)((tuning().splitk_target + tiles - 1) / tiles);
+    // split granularity: K-chunks x taps for the gather kernel, K-chunks (all nine taps) for the halo kernels
+    const int units = t->family == GATHER ? g.kt_total / 4 : g.chunks_per_tap;
+    if (sk > units) sk = units;
+    if (sk > 64) sk = 64;
+    return {t, sk < 1 ? 1 : sk};
+}
+
+// The halo kernels (conv_halo_kernel, with an emulation flag conv_halo_emu_kernel): 2-D pixel tiles, 32 or 16 pixels wide, all of
+// them inside the map.
+static ConvChoice try_halo(const rnr_conv_desc* d, const ConvPlan& g) {
+    const bool emu = (d->flags & RNR_CONV_F32_EMU_ANY) != 0, s2 = d->kind == RNR_CONV4x4S2_REFLECT;
+    const int c = d->c_out_pad;
+    auto tile = [&](int tw, int th, int bn) {
+        const ConvTile* t = find_tile(emu ? HALO_EMU : HALO, d, tw, th, bn);
+        return t && fits(*t, g) ? t : nullptr;
+    };
+    auto count = [&](const ConvTile* t) { return grid_of(*t, d, g).wgs(); };
+    // exact-fp32 kernels, small maps (the 32^2 / 16^2 layers at one view per call): when 128 x 128 tiles `t` would have to split
     // K more than four ways to fill the chip, 64 x 64 tiles (32 x 2 or 16 x 4 pixels, one MFMA block per wave) give four
     // times as many tiles: a shallow split instead of 16 - 32 slabs for the reduce kernel
-    if (p->halo && !(d->flags & RNR_CONV_F32_EMU_ANY) && p->cfg == 2 && p->bm == 128) {
-        const long t128 = (long)N * (p->Ho / th) * (p->Wo / p->tw) * p->ntiles * p->par;
-        const int th64 = p->tw == 32 ? 2 : 4;
-        // (the 4x4-s2 convolution has a barrier every 4 taps: with 8 MFMAs per tap the halo fetch of the next K step is not
-        // covered any more — 64^2 -> 32^2 at one view: 95 us on 64 x 64 tiles against 88 on 128 x 128 x 16 slices — so
-        // it takes the small tiles only where the alternative is a 32-way split)
-        const int below = d->kind == RNR_CONV4x4S2_REFLECT ? RNR_SMALL_TILE_BELOW / 4 : RNR_SMALL_TILE_BELOW;
-        if (t128 < below && p->Ho % th64 == 0) {
-            p->cfg = 3; p->bm = 64; p->bn = 64; th = th64;
-            p->ntiles = (d->c_out_pad + p->bn - 1) / p->bn;
+    // (the 4x4-s2 convolution has a barrier every 4 taps: with 8 MFMAs per tap the halo fetch of the next K step is not
+    // covered any more — 64^2 -> 32^2 at one view: 95 us on 64 x 64 tiles against 88 on 128 x 128 x 16 slices — so
+    // it takes the small tiles only where the alternative is a 32-way split)
+    auto few = [&](const ConvTile* t) { return count(t) < (s2 ? RNR_SMALL_TILE_BELOW / 4 : RNR_SMALL_TILE_BELOW); };
+    const ConvTile* t = nullptr;
+    if (g.Wo % 32 != 0) {
+        // maps 16 pixels wide: 16 x 8 pixel tiles (two image rows per 32-row MFMA block), 128 columns
+        t = tile(16, 8, 128);
+        if (t && !emu && few(t)) t = tile(16, 4, 64);
+    } else if (!wide_columns(d, g)) {
+        // 256 x 64 or 256 x 80 tiles (emulation: 256 x 96)
+        t = tile(32, 8, c <= 64 ? 64 : (emu ? 96 : 80));
+        // the 64-column 3x3 layers (256 x 64 tiles, three waves per SIMD) when one 512^2 view is all there is: 152 -> 148 us
+        // per layer on 128 x 64 tiles; no gain from two views on (RNR_CFG0_SMALL_MAX; the 64-column transposed conv too: 271 -> 268 us)
+        // (the 80-column out layer was tried on 128 x 80 tiles at one view per call: 364 vs 351 us, not kept)
+        if (t && !emu && c <= 64 && count(t) <= tuning().cfg0_small_max) t = tile(32, 4, 64);
+    } else if (emu) {
+        // bf16x6 / f16x3 emulation: 256 x 128 tiles (32 x 8 pixels, two waves per SIMD) halve the weight traffic and barriers per
+        // MFMA; else 128 rows, and the 4x4-s2 convolution, which runs per input parity phase, also has 64-row tiles
+        for (int th = 8; th >= 2 && !t; th /= 2) t = tile(32, th, 128);
+    } else {
+        // exact-fp32 kernels: 256 x 128 tiles (two waves per SIMD, half the weight traffic and barriers per MFMA) once there
+        // are enough of them to fill the 256 CUs twice over; below that the 128 x 128 tiles keep more CUs busy
+        t = tile(32, 8, 128);
+        if (!t || count(t) < RNR_NATIVE_BIG_MIN) {
+            t = tile(32, 4, 128);
+            if (t && few(t)) t = tile(32, 2, 64);
+            // ... and mid-size maps (one view per call: 256 - 512 tiles of 128 x 128, i.e. one or two workgroups = waves per SIMD):
+            // 128 x 64 tiles (32 x 4 pixels, 64 columns; 32 accumulator registers, four waves per SIMD) double the tile count
+            // (3x3 only: measured at one view per call 154 -> 149 us at 128^2 and 159 -> 154 at 64^2, but the stride-2 and transposed
+            // convolutions — four taps per barrier — lose 3 - 18 us with half the MFMAs per tap; RNR_CFG4_MAX, 0 = never)
+            else if (t && d->kind == RNR_CONV3x3_REFLECT && count(t) <= tuning().cfg4_max) t = tile(32, 4, 64);
         }
     }
-    // ... and mid-size maps (one view per call: 256 - 512 tiles of 128 x 128, i.e. one or two workgroups = waves per SIMD):
-    // 128 x 64 tiles (32 x 4 pixels, 64 columns; 32 accumulator registers, four waves per SIMD) double the tile count
-    static const int cfg4_max = env_int("RNR_CFG4_MAX", RNR_CFG4_MAX);
-    // (3x3 only: measured at one view per call 154 -> 149 us at 128^2 and 159 -> 154 at 64^2, but the stride-2 and transposed
-    // convolutions — four taps per barrier — lose 3 - 18 us with half the MFMAs per tap)
-    if (p->halo && d->kind == RNR_CONV3x3_REFLECT && !(d->flags & RNR_CONV_F32_EMU_ANY) && p->cfg == 2 && p->bm == 128 && p->tw == 32) {
-        const long t128 = (long)N * (p->Ho / th) * (p->Wo / p->tw) * p->ntiles * p->par;
-        if (t128 <= cfg4_max && t128 >= RNR_SMALL_TILE_BELOW) {
-            p->cfg = 4; p->bm = 128; p->bn = 64;
-            p->ntiles = (d->c_out_pad + p->bn - 1) / p->bn;
-        }
-    }
-    // ... and the 64-column 3x3 layers (256 x 64 tiles, three waves per SIMD) when one 512^2 view is all there is: 152 -> 148 us
-    // per layer on 128 x 64 tiles; no gain from two views on (RNR_CFG0_SMALL_MAX in the environment overrides)
-    static const int cfg0_small = env_int("RNR_CFG0_SMALL_MAX", RNR_CFG0_SMALL_MAX);
-    // (the 64-column transposed conv too: 271 -> 268 us)
-    if (p->halo && d->kind != RNR_CONV4x4S2_REFLECT && !(d->flags & RNR_CONV_F32_EMU_ANY) && p->cfg == 0 && p->tw == 32 && p->Ho % 4 == 0) {
-        const long t256 = (long)N * (p->Ho / th) * (p->Wo / p->tw) * p->ntiles * p->par;
-        if (t256 <= cfg0_small) {
-            p->cfg = 4; p->bm = 128; p->bn = 64; th = 4;
-        }
-    }
-    // (the 80-column out layer was tried on 128 x 80 tiles at one view per call: 364 vs 351 us, not kept)
-    // the halo kernels address a view with 32-bit element offsets
-    const long view_elems = (long)H * W * (d->c_in0_pad > d->c_in1_pad ? d->c_in0_pad : d->c_in1_pad);
-    if (view_elems >= (1L << 30)) p->halo = 0;
-    if (p->halo) {
-        p->mtiles = N * (p->Ho / th) * (p->Wo / p->tw);
-        if (p->cfg == 1) { p->bn = 80; p->ntiles = (d->c_out_pad + p->bn - 1) / p->bn; }
-    }
-    const long tiles = (long)p->mtiles * p->ntiles * p->par;
-    int sk = 1;
-    // (experiments: RNR_SPLITK_BELOW / RNR_SPLITK_TARGET in the environment override the compiled-in thresholds)
-    static const int sk_below = env_int("RNR_SPLITK_BELOW", RNR_SPLITK_BELOW);
-    static const int sk_target = env_int("RNR_SPLITK_TARGET", RNR_SPLITK_TARGET);
-    if (tiles < sk_below) {      // fewer workgroups than ~2-3 per CU: split K so the 256 CUs stay filled
-        sk = (int)((sk_target + tiles - 1) / tiles);
-        // split granularity: K-chunks x taps for the gather kernel, K-chunks (all nine taps) for the halo kernel
-        const int units = p->halo ? p->chunks_per_tap : p->kt_total / 4;
-        const int max_sk = units > 0 ? units : 1;
-        if (sk > max_sk) sk = max_sk;
-        if (sk > 64) sk = 64;
-        if (sk < 1) sk = 1;
-    }
-    p->splitk = sk;
-    // Winograd F(2x2, 3x3): every 3x3 layer whose map tiles into 16 x 8 pixels and whose columns into 64s, when there are
-    // enough tiles to give every CU two (RNR_WINO_MIN_WGS in the environment overrides)
-    static const int min_wgs = env_int("RNR_WINO_MIN_WGS", RNR_WINO_MIN_WGS);
-    if ((d->flags & RNR_CONV_WINOGRAD) && d->kind == RNR_CONV3x3_REFLECT && H % WINO_PH == 0 && W % WINO_PW == 0 &&
-        d->c_out_pad % WINO_BN == 0 && view_elems < (1L << 30)) {
-        const long wgs = (long)N * (H / WINO_PH) * (W / WINO_PW) * (d->c_out_pad / WINO_BN);
-        const int sk = wino_splitk(wgs, min_wgs, p->chunks_per_tap);
-        if (sk > 0) {
-            p->wino = 1; p->halo = 1; p->cfg = 0; p->tw = WINO_PW; p->bm = WINO_PW * WINO_PH; p->bn = WINO_BN;
-            p->mtiles = N * (H / WINO_PH) * (W / WINO_PW);
-            p->ntiles = d->c_out_pad / WINO_BN;
-            p->splitk = sk;
-        }
-    }
-    // F(4x4, 3x3) (opt-in, RNR_CONV_WINOGRAD4): 32 x 16 pixel tiles x 64 columns, one 12-wave workgroup per CU — when the grid
-    // gives every CU a workgroup (no split-K form)
-    static const int min_wgs4 = env_int("RNR_WINO4_MIN_WGS", RNR_WINO4_MIN_WGS);
-    if ((d->flags & RNR_CONV_WINOGRAD) && (d->flags & RNR_CONV_WINOGRAD4) && d->kind == RNR_CONV3x3_REFLECT && H % W4_PH == 0 &&
-        W % W4_PW == 0 && d->c_out_pad % W4_BN == 0 && view_elems < (1L << 30) &&
-        d->c_in0_pad + d->c_in1_pad <= W4_BN_MAXC) {      // the kernel's LDS table of BatchNorm scale / shift holds that many channels
-        const long wgs = (long)N * (H / W4_PH) * (W / W4_PW) * (d->c_out_pad / W4_BN);
-        // small grids are cut over K like the F(2x2, .) ones — slices of >= RNR_WINO4_SPLIT_MIN_CHUNKS chunks, at most 8, and the
-        // split grid must give every CU its workgroup again (this kernel runs one workgroup per CU)
-        const int sk = wino_splitk(wgs, min_wgs4, p->chunks_per_tap, RNR_WINO4_SPLIT_MIN_CHUNKS, min_wgs4);
-        if (sk > 0) {
-            p->wino = 4; p->halo = 1; p->cfg = 0; p->tw = W4_PW; p->bm = W4_PW * W4_PH; p->bn = W4_BN;
-            p->mtiles = N * (H / W4_PH) * (W / W4_PW);
-            p->ntiles = d->c_out_pad / W4_BN;
-            p->splitk = sk;
-        }
-    }
-    // ... and the 80-column out layer on the 16 x 16 x 4 instruction: 16 x 4 pixel tiles x all 80 columns (conv_wino80_kernel)
-    if ((d->flags & RNR_CONV_WINOGRAD) && d->kind == RNR_CONV3x3_REFLECT && d->c_out_pad == 80 && H % W80_PH == 0 &&
-        W % W80_PW == 0 && view_elems < (1L << 30)) {
-        const long wgs = (long)N * (H / W80_PH) * (W / W80_PW);
-        if (wgs >= min_wgs) {
-            p->wino = 3; p->halo = 1; p->cfg = 1; p->tw = W80_PW; p->bm = W80_PW * W80_PH; p->bn = 80;
-            p->mtiles = N * (H / W80_PH) * (W / W80_PW);
-            p->ntiles = 1;
-            p->splitk = 1;
-        }
-    }
-    // Winograd F(2x2, 2x2) for the 4x4 stride-2 convolutions: 16 x 16 output pixels x 128 columns (convolution) or the four
-    // parity classes of 16 x 8 input pixels x 64 columns (transposed) per workgroup
-    if ((d->flags & RNR_CONV_WINOGRAD) && d->kind != RNR_CONV3x3_REFLECT && p->Wo % WINO_PW == 0 &&
-        p->Ho % (d->kind == RNR_CONVT4x4S2 ? WINO_PH : 16) == 0 && d->c_out_pad % (d->kind == RNR_CONVT4x4S2 ? 64 : 128) == 0 &&
-        view_elems < (1L << 30)) {
-        const int bnw = d->kind == RNR_CONVT4x4S2 ? 64 : 128, tph = d->kind == RNR_CONVT4x4S2 ? WINO_PH : 16;
-        const long wgs = (long)N * (p->Ho / tph) * (p->Wo / WINO_PW) * (d->c_out_pad / bnw);
-        static const int min_wgs2 = env_int("RNR_WINO2_MIN_WGS", RNR_WINO2_MIN_WGS);
-        const int sk = wino_splitk(wgs, min_wgs2, p->chunks_per_tap);
-        if (sk > 0) {
-            p->wino = 2; p->halo = 1; p->cfg = 0; p->tw = WINO_PW; p->bm = WINO_PW * tph; p->bn = bnw;
-            p->mtiles = N * (p->Ho / tph) * (p->Wo / WINO_PW);
-            p->ntiles = d->c_out_pad / bnw;
-            p->par = 1;
-            p->splitk = sk;
-        }
-    }
-    return 0;
+    return t ? direct_choice(t, d, g) : NO_CHOICE;
 }
 
-template <int FMT, int KIND>
-static void launch_halo_emu(const ConvPlan& pl, const dim3 grid, const ConvParams& P, hipStream_t st) {
-    if (pl.tw == 16) launch_halo_emu_cfg<FMT, KIND, 2, 2, 2, 2, 16>(grid, P, st);       // 16 x 8 pixel tiles, 128 columns
-    else if (KIND == 1) {        // make_plan forces the 128-column config; rows per tile by what divides the map
-        if (pl.bm == 256) launch_halo_emu_cfg<FMT, 1, 2, 2, 4, 2>(grid, P, st);
-        else if (pl.bm == 128) launch_halo_emu_cfg<FMT, 1, 2, 2, 2, 2>(grid, P, st);
-        else launch_halo_emu_cfg<FMT, 1, 2, 2, 1, 2>(grid, P, st);
+// the gather kernel (conv_mfma_kernel, linear pixel tiles): every shape
+static ConvChoice try_gather(const rnr_conv_desc* d, const ConvPlan& g) {
+    const int c = d->c_out_pad;
+    const ConvTile* t = wide_columns(d, g) ? find_tile(GATHER, d, 128, 1, 128) : find_tile(GATHER, d, 256, 1, c <= 64 ? 64 : 96);
+    return t ? direct_choice(t, d, g) : NO_CHOICE;
+}
+
+// The candidates in priority order; the first that qualifies runs.  The columns are THE rule for masked and ray-epilogue
+// launches: the out layer's own Winograd kernel takes a tile mask, the other Winograd kernels do not, and the ray-renderer
+// epilogue lives in the direct 80-column kernel — those calls run the direct kernels, on the direct kernels' tiles.  The halo and
+// Winograd kernels address a view with 32-bit element offsets: views of 2^30 elements and more are left to the gather kernel.
+static const struct {
+    ConvChoice (*qualify)(const rnr_conv_desc*, const ConvPlan&);
+    bool masked, ray, big_view;
+} CONV_CANDIDATES[] = {
+    {try_wino80, true, false, false},
+    {try_wino4, false, false, false},
+    {try_wino, false, false, false},
+    {try_wino2, false, false, false},
+    {try_halo, true, true, false},
+    {try_gather, true, true, true},
+};
+
+// the plan of ONE call: geometry, kernel, grid and split depth of the launch `mode` describes
+static ConvPlan plan_conv(const rnr_conv_desc* d, int N, int H, int W, ConvMode mode) {
+    ConvPlan p = {};
+    const bool s2 = d->kind == RNR_CONV4x4S2_REFLECT, transposed = d->kind == RNR_CONVT4x4S2;
+    p.N = N;
+    p.taps = d->kind == RNR_CONV3x3_REFLECT ? 9 : (s2 ? 16 : 4);
+    p.Ho = s2 ? H / 2 : H; p.Wo = s2 ? W / 2 : W;
+    p.OH = transposed ? 2 * H : p.Ho; p.OW = transposed ? 2 * W : p.Wo;
+    p.M = N * p.Ho * p.Wo;
+    p.chunks_per_tap = (d->c_in0_pad + d->c_in1_pad) / BK;
+    p.kt_total = p.taps * p.chunks_per_tap;
+    const bool big_view = (long)H * W * (d->c_in0_pad > d->c_in1_pad ? d->c_in0_pad : d->c_in1_pad) >= (1L << 30);
+    ConvChoice c = NO_CHOICE;
+    for (const auto& cand : CONV_CANDIDATES) {
+        if ((mode == CONV_MASKED && !cand.masked) || (mode == CONV_RAY && !cand.ray) || (big_view && !cand.big_view)) continue;
+        c = cand.qualify(d, p);
+        if (c.tile) break;
     }
-    else if (pl.cfg == 0) launch_halo_emu_cfg<FMT, KIND == 1 ? 0 : KIND, 4, 1, 2, 2>(grid, P, st);         // 256 x 64
-    else if (pl.cfg == 1) launch_halo_emu_cfg<FMT, KIND == 1 ? 0 : KIND, 4, 1, 2, 3>(grid, P, st);         // 256 x 96 (Cout 78)
-    else if (pl.bm == 256) launch_halo_emu_cfg<FMT, KIND == 1 ? 0 : KIND, 2, 2, 4, 2>(grid, P, st);        // 256 x 128
-    else launch_halo_emu_cfg<FMT, KIND == 1 ? 0 : KIND, 2, 2, 2, 2>(grid, P, st);                          // 128 x 128
-}
-
-template <int KIND>
-static void launch_halo(const ConvPlan& pl, const ConvParams& P, hipStream_t st) {
-    const dim3 grid((unsigned)(pl.mtiles * pl.ntiles * pl.splitk * pl.par));
-    if (pl.cfg == 4) launch_halo_cfg<KIND, 4, 1, 1, 2, 0>(grid, P, st);                         // 32 x 4 pixel tiles, 64 columns
-    else if (pl.cfg == 3 && pl.tw == 16) launch_halo_cfg<KIND, 2, 2, 1, 1, 0, 16>(grid, P, st);      // 16 x 4 pixel tiles, 64 columns
-    else if (pl.cfg == 3) launch_halo_cfg<KIND, 2, 2, 1, 1, 0>(grid, P, st);                    // 32 x 2 pixel tiles, 64 columns
-    else if (pl.tw == 16) launch_halo_cfg<KIND, 2, 2, 2, 2, 0, 16>(grid, P, st);       // 16 x 8 pixel tiles, 128 columns
-    else if (pl.cfg == 0) launch_halo_cfg<KIND, 4, 1, 2, 2, 0>(grid, P, st);
-    else if (pl.cfg == 1) launch_halo_cfg<KIND, 4, 1, 2, 2, 1>(grid, P, st);      // 256 x 80
-    else if (pl.bm == 256) launch_halo_cfg<KIND, 2, 2, 4, 2, 0>(grid, P, st);
-    else launch_halo_cfg<KIND, 2, 2, 2, 2, 0>(grid, P, st);
-}
-
-template <int KIND>
-static void launch_kind(const ConvPlan& pl, const ConvParams& P, hipStream_t st) {
-    const dim3 grid((unsigned)(pl.mtiles * pl.ntiles * pl.splitk * pl.par));
-    if (pl.cfg == 0) hipLaunchKernelGGL((conv_mfma_kernel<KIND, 4, 1, 2, 2>), grid, dim3(CTHREADS), 0, st, P);
-    else if (pl.cfg == 1) hipLaunchKernelGGL((conv_mfma_kernel<KIND, 4, 1, 2, 3>), grid, dim3(CTHREADS), 0, st, P);
-    else hipLaunchKernelGGL((conv_mfma_kernel<KIND, 2, 2, 2, 2>), grid, dim3(CTHREADS), 0, st, P);
+    if (!c.tile) return p;
+    p = grid_of(*c.tile, d, p);
+    p.splitk = c.splitk;
+    // a tile mask has one entry per 32-pixel-wide halo tile, or 16 x 4 tile of the out layer's Winograd kernel, of an unsplit 3x3 grid
+    p.maskable = d->kind == RNR_CONV3x3_REFLECT && p.splitk == 1 &&
+                 (c.tile->family == WINO80 || ((c.tile->family == HALO || c.tile->family == HALO_EMU) && c.tile->tw == 32));
+    if (mode == CONV_RAY) p.splitk = 1;     // the ray-renderer epilogue needs the whole K sum in one workgroup (small maps would split)
+    return p;
 }
 
 static int check_desc(const rnr_conv_desc* d, const char* who) {
@@ -2046,8 +2101,7 @@ extern "C" int rnr_pack_conv_weight(const rnr_conv_desc* d, const float* weight,
 
 extern "C" size_t rnr_conv_workspace_bytes(const rnr_conv_desc* d, int num_views, int in_h, int in_w) {
     if (!d || num_views <= 0) return 0;
-    ConvPlan pl;
-    make_plan(d, num_views, in_h, in_w, &pl);
+    const ConvPlan pl = plan_conv(d, num_views, in_h, in_w, CONV_PLAIN);
     if (pl.splitk <= 1) return 256;
     return (size_t)pl.splitk * num_views * pl.OH * pl.OW * d->c_out_pad * sizeof(float) + 256;
 }
@@ -2070,52 +2124,33 @@ extern "C" size_t rnr_conv_sync_bytes(const rnr_conv_desc* d, int max_views, int
 
 extern "C" int rnr_conv_algorithm(const rnr_conv_desc* d, int num_views, int in_h, int in_w) {
     if (!d || num_views <= 0 || d->kind < 0 || d->kind > 2) return -1;
-    ConvPlan pl;
-    make_plan(d, num_views, in_h, in_w, &pl);
-    return pl.wino;
+    return CONV_ALGORITHM[plan_conv(d, num_views, in_h, in_w, CONV_PLAIN).tile->family];
 }
 
-// the direct kernels' plan whatever Winograd flags the descriptor carries; returns the descriptor without them
-static rnr_conv_desc plan_direct(const rnr_conv_desc* d, int num_views, int in_h, int in_w, ConvPlan* pl) {
-    rnr_conv_desc dd = *d;
-    dd.flags &= ~(RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD4);
-    make_plan(&dd, num_views, in_h, in_w, pl);
-    return dd;
-}
-
-// the plan a MASKED launch runs: the out layer's own Winograd kernel takes a mask, the other Winograd kernels do not — those
-// calls run the direct kernels, on the direct kernels' tiles
-static void mask_plan(const rnr_conv_desc* d, int num_views, int in_h, int in_w, ConvPlan* pl) {
-    make_plan(d, num_views, in_h, in_w, pl);
-    if (pl->wino && pl->wino != 3) plan_direct(d, num_views, in_h, in_w, pl);
-}
-
+// (the tiles of a MASKED launch of this descriptor; the mask of a ray-epilogue launch is laid out like that of a masked
+// launch of the descriptor without its Winograd flags)
 extern "C" size_t rnr_conv_tile_count(const rnr_conv_desc* d, int num_views, int in_h, int in_w) {
-    if (!d || num_views <= 0 || d->kind != RNR_CONV3x3_REFLECT) return 0;
-    ConvPlan pl;
-    mask_plan(d, num_views, in_h, in_w, &pl);
-    return (pl.halo && (pl.wino == 3 || (!pl.wino && pl.tw == 32)) && pl.splitk == 1) ? (size_t)pl.mtiles : 0;
+    if (!d || num_views <= 0) return 0;
+    const ConvPlan pl = plan_conv(d, num_views, in_h, in_w, CONV_MASKED);
+    return pl.maskable ? (size_t)pl.mtiles : 0;
 }
 
 extern "C" int rnr_conv_active_tiles(const rnr_conv_desc* d, const float* alpha, uint8_t* tile_mask, int num_views,
                                      int in_h, int in_w, void* stream) {
     if (int e = check_desc(d, "rnr_conv_active_tiles")) return e;
     RNR_REQUIRE(alpha && tile_mask, "rnr_conv_active_tiles: null pointer argument");
-    RNR_REQUIRE(rnr_conv_tile_count(d, num_views, in_h, in_w) > 0,
+    const ConvPlan pl = plan_conv(d, num_views, in_h, in_w, CONV_MASKED);
+    RNR_REQUIRE(pl.maskable && pl.mtiles > 0,
                 "rnr_conv_active_tiles: this convolution does not run on maskable pixel tiles (3x3 halo plan without split-K)");
-    ConvPlan pl;
-    mask_plan(d, num_views, in_h, in_w, &pl);
     hipLaunchKernelGGL(active_tile_kernel, dim3((unsigned)pl.mtiles), dim3(256), 0, as_stream(stream), alpha, tile_mask,
-                       in_h, in_w, pl.bm / pl.tw, pl.tw);
+                       in_h, in_w, pl.tile->th, pl.tile->tw);
     return check_launch("active_tile_kernel");
 }
 
 struct RayEpilogue { const float* w; const float* bias; float* image; };
-static thread_local RayEpilogue g_ray = {nullptr, nullptr, nullptr};      // set by rnr_conv2d_ray around conv2d_run
 
-static int conv2d_run(const rnr_conv_desc* d, const rnr_conv_src* src0, const rnr_conv_src* src1, const float* weight_packed,
-                      float* out_raw, double* stats, const rnr_conv_bn* bn, void* sync, size_t sync_bytes, int num_views,
-                      int in_h, int in_w, void* workspace, size_t workspace_bytes, const uint8_t* tile_mask, void* stream) {
+static int check_call(const rnr_conv_desc* d, const rnr_conv_src* src0, const rnr_conv_src* src1, const float* weight_packed,
+                      const float* out_raw, const rnr_conv_bn* bn, int num_views, int in_h, int in_w) {
     if (int e = check_desc(d, "rnr_conv2d")) return e;
     RNR_REQUIRE(src0 && src0->data && weight_packed && out_raw, "rnr_conv2d: null pointer argument");
     RNR_REQUIRE(src0->channels == d->c_in0_pad, "rnr_conv2d: src0 has %d channels, descriptor says %d",
@@ -2127,18 +2162,18 @@ static int conv2d_run(const rnr_conv_desc* d, const rnr_conv_src* src0, const rn
                 in_h, in_w);
     RNR_REQUIRE(d->kind != RNR_CONV4x4S2_REFLECT || (in_h % 2 == 0 && in_w % 2 == 0),
                 "rnr_conv2d: stride-2 conv needs even input size");
-    const bool fused = sync != nullptr;          // rnr_conv2d_fused
-    const bool with_bn = fused && bn && bn->gamma;
-    if (with_bn) RNR_REQUIRE(bn->beta && bn->scale && bn->shift, "rnr_conv2d_fused: null BatchNorm pointer");
-    if (with_bn) RNR_REQUIRE(!(bn->running_mean || bn->running_var) || num_views == 1,
-                             "rnr_conv2d_fused: running statistics are per-view here; torch pools the batch — pass them for num_views == 1 only (got %d)",
-                             num_views);
-    hipStream_t st = as_stream(stream);
-    ConvPlan pl;
-    make_plan(d, num_views, in_h, in_w, &pl);
-    if (pl.wino && (g_ray.w || (tile_mask && pl.wino != 3)))    // ray-epilogue / masked launches run on the direct kernels' tiles (the out layer's own Winograd kernel takes a mask)
-        plan_direct(d, num_views, in_h, in_w, &pl);
-    if (g_ray.w) pl.splitk = 1;         // the ray-renderer epilogue needs the whole K sum in one workgroup (small maps would split)
+    if (bn && bn->gamma) {
+        RNR_REQUIRE(bn->beta && bn->scale && bn->shift, "rnr_conv2d_fused: null BatchNorm pointer");
+        RNR_REQUIRE(!(bn->running_mean || bn->running_var) || num_views == 1,
+                    "rnr_conv2d_fused: running statistics are per-view here; torch pools the batch — pass them for num_views == 1 only (got %d)",
+                    num_views);
+    }
+    return 0;
+}
+
+// the kernel arguments that do not depend on where statistics and output go
+static ConvParams conv_params(const rnr_conv_desc* d, const rnr_conv_src* src0, const rnr_conv_src* src1, const float* weight_packed,
+                              const ConvPlan& pl, int in_h, int in_w, const RayEpilogue* ray, const uint8_t* tile_mask) {
     ConvParams P = {};
     P.src_data[0] = src0->data; P.src_scale[0] = src0->scale; P.src_shift[0] = src0->shift;
     P.src_c[0] = src0->channels; P.src_act[0] = src0->act;
@@ -2146,110 +2181,102 @@ static int conv2d_run(const rnr_conv_desc* d, const rnr_conv_src* src0, const rn
         P.src_data[1] = src1->data; P.src_scale[1] = src1->scale; P.src_shift[1] = src1->shift;
         P.src_c[1] = src1->channels; P.src_act[1] = src1->act;
     }
-    P.weight = weight_packed; P.stats = stats; P.n_shards = 1;
-    P.N = num_views; P.H = in_h; P.W = in_w; P.Ho = pl.Ho; P.Wo = pl.Wo; P.OH = pl.OH; P.OW = pl.OW; P.M = pl.M;
+    P.weight = weight_packed; P.n_shards = 1;
+    P.N = pl.N; P.H = in_h; P.W = in_w; P.Ho = pl.Ho; P.Wo = pl.Wo; P.OH = pl.OH; P.OW = pl.OW; P.M = pl.M;
     P.c_out = d->c_out; P.c_out_pad = d->c_out_pad; P.wstride = weight_row_stride(d->c_out_pad);
     P.chunks0 = d->c_in0_pad / BK; P.chunks_per_tap = pl.chunks_per_tap; P.kt_total = pl.kt_total;
     P.splitk = pl.splitk;
     P.mtiles = pl.mtiles; P.ntiles = pl.ntiles; P.zdim = pl.splitk * pl.par;
-    P.ray_w = g_ray.w; P.ray_bias = g_ray.bias; P.ray_image = g_ray.image;
-    if (d->kind == RNR_CONVT4x4S2) {
+    P.tile_mask = tile_mask;
+    if (ray) { P.ray_w = ray->w; P.ray_bias = ray->bias; P.ray_image = ray->image; }
+    const size_t f32 = packed_f32_floats(d);          // the images behind the fp32 one (rnr_packed_weight_floats)
+    if (pl.tile->family == HALO_EMU) P.weight_emu = weight_packed + f32;
+    if (pl.tile->family >= WINO) P.weight_wino = weight_packed + f32 + (pl.tile->family == WINO4 ? wino_weight_floats(d) : 0);
+    if (pl.par > 1) {
         // Each parity class is its own workgroup and stages the same input halo.  With the class as the slowest tile index the
         // input is streamed from HBM four times (r02 PMC: 2.9x the compulsory bytes on the 64-column transposed conv); as
         // neighbours the four share one L2.  The price is four weight sets in flight per XCD instead of one, so the order is
         // chosen by which operand is bigger.  RNR_PAR_INNER=0/1 forces it (experiments).
-        static const int forced = env_int("RNR_PAR_INNER", -1);
         const size_t w_bytes = 16 * (size_t)(d->c_in0_pad + d->c_in1_pad) * d->c_out_pad * sizeof(float);
         const size_t in_bytes = (size_t)in_h * in_w * (d->c_in0_pad + d->c_in1_pad) * sizeof(float);     // per view
-        P.par_inner = forced >= 0 ? forced : (in_bytes >= w_bytes ? 1 : 0);
+        P.par_inner = tuning().par_inner >= 0 ? tuning().par_inner : (in_bytes >= w_bytes ? 1 : 0);
     }
+    return P;
+}
+
+// rnr_conv2d_fused's BatchNorm: statistics go to the shards of the sync buffer; P.arrive is set when the kernel itself finalises
+static int setup_fused_bn(const rnr_conv_desc* d, const rnr_conv_bn* bn, void* sync, size_t sync_bytes, const ConvPlan& pl,
+                          ConvParams& P) {
+    const SyncLayout L = sync_layout(d, pl.N);
+    RNR_REQUIRE(sync_bytes >= L.total, "rnr_conv2d_fused: sync buffer too small (%zu < %zu, see rnr_conv_sync_bytes)",
+                sync_bytes, L.total);
+    if (!(bn && bn->gamma)) return 0;
+    char* sb = reinterpret_cast<char*>(sync);
+    P.stats = reinterpret_cast<double*>(sb + L.stats);
+    P.n_shards = STAT_SHARDS;
+    P.stats_shard = 2L * pl.N * d->c_out_pad;
+    P.gamma = bn->gamma; P.beta = bn->beta; P.scale = bn->scale; P.shift = bn->shift;
+    P.eps = bn->eps; P.count = (double)pl.OH * pl.OW;
+    P.running_mean = bn->running_mean; P.running_var = bn->running_var; P.momentum = bn->momentum;
+    // tickets only where workgroups finish at different times: more than one workgroup per CU (see
+    // bn_finalize_shards_kernel); the others get the finalise as a launch of its own
+    // (a separate finalise launch for the big Winograd grids too was measured: -0.5 % on seven layers at 8 views — the
+    // ticket is not what the short-K layers lose)
+    // (conv_wino4_kernel, one 12-wave workgroup per CU: tickets vs a separate finalise launch measured equal, r04)
+    if (pl.splitk == 1 && pl.wgs() > RNR_FUSED_BN_MIN_WGS) {
+        P.arrive = reinterpret_cast<unsigned*>(sb + L.arrive);
+        P.arrive_per_view = pl.tile->family != GATHER;         // the pixel tiles of all but the gather kernel lie inside one view
+        P.n_arrive = (unsigned)(P.arrive_per_view ? pl.wgs() / pl.N : pl.wgs());
+    }
+    return 0;
+}
+
+static int conv2d_run(const rnr_conv_desc* d, const rnr_conv_src* src0, const rnr_conv_src* src1, const float* weight_packed,
+                      float* out_raw, double* stats, const rnr_conv_bn* bn, void* sync, size_t sync_bytes, int num_views,
+                      int in_h, int in_w, void* workspace, size_t workspace_bytes, const uint8_t* tile_mask,
+                      const RayEpilogue* ray, void* stream) {
+    if (int e = check_call(d, src0, src1, weight_packed, out_raw, sync ? bn : nullptr, num_views, in_h, in_w)) return e;
+    const bool with_bn = sync && bn && bn->gamma;            // sync: rnr_conv2d_fused
+    hipStream_t st = as_stream(stream);
+
+    const ConvPlan pl = plan_conv(d, num_views, in_h, in_w, ray ? CONV_RAY : (tile_mask ? CONV_MASKED : CONV_PLAIN));
+    RNR_REQUIRE(pl.tile, "rnr_conv2d: no kernel for this convolution");
+    if (ray)
+        RNR_REQUIRE(d->kind == RNR_CONV3x3_REFLECT && pl.tile->family == HALO && pl.tile->bn == 80 && d->c_out % 3 == 0,
+                    "rnr_conv2d_ray: only the exact-fp32 3x3 out layer on the 80-column plan (65 <= c_out <= 80, c_out = 3 x rays, map "
+                    "width a multiple of 32, height of 8) has the ray-renderer epilogue; run rnr_conv2d_masked + rnr_ray_render otherwise");
     if (tile_mask) {
         RNR_REQUIRE(!stats && !with_bn, "rnr_conv2d_masked: skipped tiles would falsify the batch statistics (no statistics / BatchNorm with a mask)");
-        RNR_REQUIRE(rnr_conv_tile_count(d, num_views, in_h, in_w) > 0,
-                    "rnr_conv2d_masked: this convolution does not run on maskable pixel tiles");
-        P.tile_mask = tile_mask;
+        RNR_REQUIRE(pl.maskable, "rnr_conv2d_masked: this convolution does not run on maskable pixel tiles");
     }
-    const size_t out_floats = (size_t)num_views * pl.OH * pl.OW * d->c_out_pad;
-    const long grid_wgs = (long)pl.mtiles * pl.ntiles * pl.splitk * pl.par;
-    bool in_kernel_bn = false;
-    if (fused) {
-        const SyncLayout L = sync_layout(d, num_views);
-        RNR_REQUIRE(sync_bytes >= L.total, "rnr_conv2d_fused: sync buffer too small (%zu < %zu, see rnr_conv_sync_bytes)",
-                    sync_bytes, L.total);
-        char* sb = reinterpret_cast<char*>(sync);
-        if (with_bn) {
-            P.stats = reinterpret_cast<double*>(sb + L.stats);
-            P.n_shards = STAT_SHARDS;
-            P.stats_shard = 2L * num_views * d->c_out_pad;
-            P.gamma = bn->gamma; P.beta = bn->beta; P.scale = bn->scale; P.shift = bn->shift;
-            P.eps = bn->eps; P.count = (double)pl.OH * pl.OW;
-            P.running_mean = bn->running_mean; P.running_var = bn->running_var; P.momentum = bn->momentum;
-            // tickets only where workgroups finish at different times: more than one workgroup per CU (see
-            // bn_finalize_shards_kernel); the others get the finalise as a launch of its own
-            // (a separate finalise launch for the big Winograd grids too was measured: -0.5 % on seven layers at 8 views — the
-            // ticket is not what the short-K layers lose)
-            // (conv_wino4_kernel, one 12-wave workgroup per CU: tickets vs a separate finalise launch measured equal, r04)
-            in_kernel_bn = pl.splitk == 1 && grid_wgs > RNR_FUSED_BN_MIN_WGS;
-            if (in_kernel_bn) {
-                P.arrive = reinterpret_cast<unsigned*>(sb + L.arrive);
-                if (pl.halo) {      // the halo kernels' tiles lie inside one view
-                    P.arrive_per_view = 1;
-                    P.n_arrive = (unsigned)((long)pl.mtiles * pl.ntiles * pl.par / num_views);
-                } else {
-                    P.arrive_per_view = 0;
-                    P.n_arrive = (unsigned)grid_wgs;
-                }
-            }
-        }
-    }
+    // the Winograd kernels run their last chunk unconditionally and give every slice ceil(chunks / splitk) chunks: an empty
+    // trailing slice would stage the wrong range and look ahead past the weight image (wino_splitk never produces one)
+    RNR_REQUIRE(pl.tile->family < WINO || pl.splitk <= 1 ||
+                    (long)(pl.splitk - 1) * ((pl.chunks_per_tap + pl.splitk - 1) / pl.splitk) < pl.chunks_per_tap,
+                "rnr_conv2d: split-K plan with an empty slice (%d chunks cut %d ways)", pl.chunks_per_tap, pl.splitk);
+
+    ConvParams P = conv_params(d, src0, src1, weight_packed, pl, in_h, in_w, ray, tile_mask);
+    P.stats = stats;
+    if (sync)
+        if (int e = setup_fused_bn(d, bn, sync, sync_bytes, pl, P)) return e;
     if (stats && !(d->flags & RNR_CONV_STATS_PREZEROED)) {
         // (a kernel, not hipMemsetAsync: memset nodes of a captured HIP graph went stale on replay, raster.hip)
         const long n = (long)num_views * d->c_out_pad * 2;
         hipLaunchKernelGGL(zero_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, stats, n);
     }
-    if (pl.splitk > 1) {
+    const size_t out_floats = (size_t)num_views * pl.OH * pl.OW * d->c_out_pad;
+    P.out = out_raw;
+    if (pl.splitk > 1) {         // one partial-output slab per slice
         RNR_REQUIRE(workspace && workspace_bytes >= (size_t)pl.splitk * out_floats * sizeof(float),
                     "rnr_conv2d: workspace too small (%zu < %zu)", workspace_bytes,
                     (size_t)pl.splitk * out_floats * sizeof(float));
         P.out = reinterpret_cast<float*>(workspace);
         P.slab_stride = (long)out_floats;
-    } else {
-        P.out = out_raw;
-        P.slab_stride = 0;
     }
-    // fp32 emulation on the 16-bit matrix cores: every convolution on the halo plan
-    const bool emu = (d->flags & RNR_CONV_F32_EMU_ANY) && pl.halo && (d->kind != RNR_CONV4x4S2_REFLECT || pl.cfg == 2);
-    if (emu) {
-        P.weight_emu = weight_packed + packed_f32_floats(d);
-        const dim3 grid((unsigned)grid_wgs);
-        const bool f16 = (d->flags & RNR_CONV_F32_EMU_F16X3) != 0;
-        if (d->kind == RNR_CONV4x4S2_REFLECT) { if (f16) launch_halo_emu<1, 1>(pl, grid, P, st); else launch_halo_emu<0, 1>(pl, grid, P, st); }
-        else if (d->kind == RNR_CONV3x3_REFLECT) { if (f16) launch_halo_emu<1, 0>(pl, grid, P, st); else launch_halo_emu<0, 0>(pl, grid, P, st); }
-        else { if (f16) launch_halo_emu<1, 2>(pl, grid, P, st); else launch_halo_emu<0, 2>(pl, grid, P, st); }
-    }
-    else if (pl.wino) {
-        // the Winograd kernels run their last chunk unconditionally and give every slice ceil(chunks / splitk) chunks: an empty
-        // trailing slice would stage the wrong range and look ahead past the weight image (make_plan never produces one)
-        RNR_REQUIRE(pl.splitk <= 1 || (long)(pl.splitk - 1) * ((pl.chunks_per_tap + pl.splitk - 1) / pl.splitk) < pl.chunks_per_tap,
-                    "rnr_conv2d: split-K plan with an empty slice (%d chunks cut %d ways)", pl.chunks_per_tap, pl.splitk);
-        P.weight_wino = weight_packed + packed_f32_floats(d);
-        P.par_inner = 0;
-        if (pl.wino == 4) {
-            P.weight_wino = weight_packed + packed_f32_floats(d) + wino_weight_floats(d);
-            launch_wino4(dim3((unsigned)grid_wgs), P, st);
-        }
-        else if (pl.wino == 1) launch_wino(dim3((unsigned)grid_wgs), P, st);
-        else if (pl.wino == 3) launch_wino80(dim3((unsigned)grid_wgs), P, st);
-        else if (d->kind == RNR_CONV4x4S2_REFLECT) launch_wino2(dim3((unsigned)grid_wgs), P, st);
-        else launch_wino2p(dim3((unsigned)grid_wgs), P, st);
-    }
-    else if (pl.halo && d->kind == RNR_CONV3x3_REFLECT) launch_halo<0>(pl, P, st);
-    else if (pl.halo && d->kind == RNR_CONV4x4S2_REFLECT) launch_halo<1>(pl, P, st);
-    else if (pl.halo) launch_halo<2>(pl, P, st);
-    else if (d->kind == RNR_CONV3x3_REFLECT) launch_kind<0>(pl, P, st);
-    else if (d->kind == RNR_CONV4x4S2_REFLECT) launch_kind<1>(pl, P, st);
-    else launch_kind<2>(pl, P, st);
+
+    tile_launcher(*pl.tile, d)(dim3((unsigned)(pl.wgs() * pl.splitk)), P, st);        // (find_tile returns rows that have one)
     if (int e = check_launch("conv_mfma_kernel")) return e;
+
     if (pl.splitk > 1) {
         const long rows = (long)num_views * pl.OH * pl.OW;
         const int col_tiles = (d->c_out_pad + 63) / 64, rows_per_view = pl.OH * pl.OW;
@@ -2260,7 +2287,7 @@ static int conv2d_run(const rnr_conv_desc* d, const rnr_conv_src* src0, const rn
                            (long)out_floats, pl.splitk, out_raw, rows, rows_per_view, rpw, P);
         if (int e = check_launch("splitk_reduce_kernel")) return e;
     }
-    if (with_bn && !in_kernel_bn) {
+    if (with_bn && !P.arrive) {
         hipLaunchKernelGGL(bn_finalize_shards_kernel, dim3((unsigned)num_views, (unsigned)((d->c_out_pad + CTHREADS - 1) / CTHREADS)),
                            dim3(CTHREADS), 0, st, P);
         if (int e = check_launch("bn_finalize_shards_kernel")) return e;
@@ -2272,7 +2299,7 @@ extern "C" int rnr_conv2d(const rnr_conv_desc* d, const rnr_conv_src* src0, cons
                           const float* weight_packed, float* out_raw, double* stats, int num_views, int in_h,
                           int in_w, void* workspace, size_t workspace_bytes, void* stream) {
     return conv2d_run(d, src0, src1, weight_packed, out_raw, stats, nullptr, nullptr, 0, num_views, in_h, in_w, workspace,
-                      workspace_bytes, nullptr, stream);
+                      workspace_bytes, nullptr, nullptr, stream);
 }
 
 extern "C" int rnr_conv2d_masked(const rnr_conv_desc* d, const rnr_conv_src* src0, const rnr_conv_src* src1,
@@ -2280,27 +2307,18 @@ extern "C" int rnr_conv2d_masked(const rnr_conv_desc* d, const rnr_conv_src* src
                                  int in_w, void* workspace, size_t workspace_bytes, const uint8_t* tile_mask,
                                  void* stream) {
     return conv2d_run(d, src0, src1, weight_packed, out_raw, stats, nullptr, nullptr, 0, num_views, in_h, in_w, workspace,
-                      workspace_bytes, tile_mask, stream);
+                      workspace_bytes, tile_mask, nullptr, stream);
 }
 
+// (the plan, the tile count and therefore the layout tile_mask is read in are those of the direct 32 x 8-pixel tiles whatever
+// Winograd flags the descriptor carries: CONV_RAY in plan_conv)
 extern "C" int rnr_conv2d_ray(const rnr_conv_desc* d, const rnr_conv_src* src0, const rnr_conv_src* src1,
                               const float* weight_packed, const float* ray_w, const float* bias, float* image, int num_views,
                               int in_h, int in_w, const uint8_t* tile_mask, void* stream) {
     RNR_REQUIRE(ray_w && bias && image, "rnr_conv2d_ray: null pointer argument");
-    if (int e = check_desc(d, "rnr_conv2d_ray")) return e;
-    ConvPlan pl;
-    const rnr_conv_desc dd = plan_direct(d, num_views, in_h, in_w, &pl);     // the ray-renderer epilogue lives in the direct 80-column kernel
-    RNR_REQUIRE(d->kind == RNR_CONV3x3_REFLECT && !(d->flags & RNR_CONV_F32_EMU_ANY) && pl.halo && pl.cfg == 1 && pl.tw == 32 &&
-                    d->c_out % 3 == 0 && d->c_out_pad == 80,
-                "rnr_conv2d_ray: only the exact-fp32 3x3 out layer on the 80-column plan (65 <= c_out <= 80, c_out = 3 x rays, map "
-                "width a multiple of 32, height of 8) has the ray-renderer epilogue; run rnr_conv2d_masked + rnr_ray_render otherwise");
-    g_ray = {ray_w, bias, image};
-    // the stripped descriptor goes down: the plan, the tile count and therefore the layout tile_mask is read in are those of
-    // the direct 32 x 8-pixel tiles whatever flags the caller's descriptor carries
-    const int rc = conv2d_run(&dd, src0, src1, weight_packed, image /* never written as out_raw */, nullptr, nullptr, nullptr, 0,
-                              num_views, in_h, in_w, nullptr, 0, tile_mask, stream);
-    g_ray = {nullptr, nullptr, nullptr};
-    return rc;
+    const RayEpilogue ray = {ray_w, bias, image};
+    return conv2d_run(d, src0, src1, weight_packed, image /* never written as out_raw */, nullptr, nullptr, nullptr, 0,
+                      num_views, in_h, in_w, nullptr, 0, tile_mask, &ray, stream);
 }
 
 extern "C" int rnr_conv2d_fused(const rnr_conv_desc* d, const rnr_conv_src* src0, const rnr_conv_src* src1,
@@ -2309,7 +2327,7 @@ extern "C" int rnr_conv2d_fused(const rnr_conv_desc* d, const rnr_conv_src* src0
                                 const uint8_t* tile_mask, void* stream) {
     RNR_REQUIRE(sync, "rnr_conv2d_fused: null sync buffer");
     return conv2d_run(d, src0, src1, weight_packed, out_raw, nullptr, bn, sync, sync_bytes, num_views, in_h, in_w, workspace,
-                      workspace_bytes, tile_mask, stream);
+                      workspace_bytes, tile_mask, nullptr, stream);
 }
 
 static int bn_finalize_impl(double* stats, const float* gamma, const float* beta, float* scale, float* shift,

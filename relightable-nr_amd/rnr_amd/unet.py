@@ -239,17 +239,7 @@ class UNetPlan:
         return 2 * (2 * h) * (2 * w) * 4 * cin * d.c_out
 
     def _count_flops(self):
-        total = 0
-        for s in self.steps:
-            d, (h, w) = s['desc'], s['in_hw']
-            cin = d.c_in0 + d.c_in1
-            if d.kind == CONV3x3_REFLECT:
-                total += 2 * h * w * 9 * cin * d.c_out
-            elif d.kind == CONV4x4S2_REFLECT:
-                total += 2 * (h // 2) * (w // 2) * 16 * cin * d.c_out
-            else:
-                total += 2 * (2 * h) * (2 * w) * 4 * cin * d.c_out
-        return total
+        return sum(self._layer_flops(s['desc'], *s['in_hw']) for s in self.steps)
 
     def _src(self, a, n):
         return RnrConvSrc(a.data.data_ptr(), a.scale.data_ptr() if a.scale is not None else None,
@@ -279,7 +269,10 @@ class UNetPlan:
         last = self.steps[-1]
         mask = None
         # the ray-renderer epilogue lives in the direct 80-column kernel: that call (and its tile mask) use the out layer's
-        # descriptor without the Winograd flag (same packed buffer: the direct image comes first)
+        # descriptor without the Winograd flag (same packed buffer: the direct image comes first).  rnr_conv2d_ray itself plans
+        # on the direct tiles whatever the flags, but rnr_conv_tile_count / rnr_conv_active_tiles have no mode argument and
+        # describe a MASKED launch, which with the flag runs the out layer's Winograd kernel on 16 x 4 tiles: the mask of a
+        # ray launch has to be built from the stripped descriptor, so the strip stays here
         out_desc = last['desc']
         if ray is not None and (out_desc.flags & _lib.CONV_WINOGRAD):
             out_desc = RnrConvDesc(out_desc.kind, out_desc.c_in0, out_desc.c_in0_pad, out_desc.c_in1, out_desc.c_in1_pad,

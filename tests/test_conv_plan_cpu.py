@@ -1,6 +1,7 @@
 """CPU: host-side planning of the convolutions through the C ABI (no kernel launches): which algorithm a call runs
 (rnr_conv_algorithm), the packed-weight, workspace and sync sizes that go with it."""
 import ctypes
+import os
 
 import pytest
 
@@ -147,3 +148,70 @@ def test_winograd_f4x4_split_grids():
         sk = L.rnr_conv_workspace_bytes(ctypes.byref(d), 1, 128, 128) // (128 * 128 * 64 * 4)
         per = -(-chunks // sk)
         assert sk >= 2 and (sk - 1) * per < chunks and per >= 4 and 32 * sk >= 256, (chunks, sk)
+
+
+SWEEP_FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'conv_plan_sweep.csv')
+SWEEP_FLAGS = (0, _lib.CONV_WINOGRAD, _lib.CONV_WINOGRAD | _lib.CONV_WINOGRAD4, _lib.CONV_F32_EMU_BF16X6, _lib.CONV_F32_EMU_F16X3)
+
+
+def plan_sweep():
+    """The calls of the plan sweep: (kind, in_h, in_w, c_in0, c_in1, c_out, flags, views)."""
+    shapes = []
+    for kind, h, cins, c_out in LAYERS:
+        shapes.append((kind, h, h, cins, c_out))                                    # one 512 x 512 frame
+        shapes.append((kind, h // 2, h // 2, cins, c_out))                          # 256 x 256
+        shapes.append((kind, 2 * h, 2 * h, (100,) if cins == (108,) else cins, c_out))      # 1024 x 1024 (config 5)
+        # the narrow network of smoke() (nf0 = 4, 64 x 64): every width of k x 64 channels becomes k x 4
+        narrow = lambda c: c // 16 if c % 64 == 0 else c
+        shapes.append((kind, h // 8, h // 8, tuple(narrow(c) for c in cins), narrow(c_out)))
+    calls = [s + (f, n) for s in shapes for f in SWEEP_FLAGS for n in (1, 2, 3, 4, 8, 16)]
+    # the shapes the planner has branches for: maps 16 and 48 pixels wide (and 40: no halo tile), heights divisible by 8, by 4,
+    # by 2 and odd, 48 / 80 / 96 / 128 columns, two sources with more than 1024 channels (over the F(4x4, 3x3) table)
+    awkward = []
+    for kind in (0, 1, 2):
+        up = 2 if kind == 1 else 1           # given as sizes of the GEMM row space (Ho x Wo)
+        for ho in (16, 36, 34, 33):
+            for wo in (16, 48, 32, 40):
+                for c_out in (48, 78, 96, 128):
+                    for cins in ((64,), (1024, 512)):
+                        awkward.append((kind, up * ho, up * wo, cins, c_out))
+    # a view of 2^30 elements and more: the halo and Winograd kernels address a view with 32-bit offsets
+    for kind, h, w, cins, c_out in ((0, 4096, 4096, (64,), 64), (0, 4096, 4096, (64, 64), 78), (0, 4096, 4112, (64,), 128),
+                                    (1, 4096, 4096, (64,), 64), (1, 4096, 4096, (64,), 128), (2, 4096, 4096, (32, 64), 64),
+                                    (0, 4096, 4096, (48,), 64), (1, 512, 1024, (1024, 1024), 64)):
+        awkward.append((kind, h, w, cins, c_out))
+    calls += [s + (f, n) for s in awkward for f in SWEEP_FLAGS for n in (1, 4)]
+    return [(k, h, w, cins[0], cins[1] if len(cins) > 1 else 0, c_out, f, n) for k, h, w, cins, c_out, f, n in calls]
+
+
+def plan_row(L, call):
+    kind, h, w, c0, c1, c_out, flags, n = call
+    d = ctypes.byref(desc(kind, (c0, c1) if c1 else (c0,), c_out, flags))
+    return (L.rnr_conv_algorithm(d, n, h, w), L.rnr_conv_workspace_bytes(d, n, h, w), L.rnr_conv_tile_count(d, n, h, w),
+            L.rnr_packed_weight_floats(d))
+
+
+def test_plan_sweep_matches_the_recorded_table():
+    """Algorithm, workspace size (hence the split depth), maskable tile count and packed-weight size of every call of the sweep
+    equal the table recorded from the library BEFORE the planner was rewritten as a list of candidates (tests/golden/
+    conv_plan_sweep.csv; `python tests/test_conv_plan_cpu.py` records it again from the library in the tree, or from the one
+    RNR_HIP_LIB names).  The sweep holds shapes where several candidates qualify (F(4x4, 3x3) over F(2x2, 3x3), the small direct
+    tiles over the 128 x 128 ones), so precedence is part of what is compared."""
+    L = _lib.load()
+    with open(SWEEP_FIXTURE) as f:
+        lines = [ln.strip() for ln in f if ln.strip() and not ln.startswith('#')]
+    recorded = [tuple(int(v) for v in ln.split(',')) for ln in lines]
+    calls = plan_sweep()
+    assert len(calls) > 3000 and [r[:8] for r in recorded] == calls
+    assert {r[8] for r in recorded} == {0, 1, 2, 3, 4} and any(r[10] > 0 for r in recorded)
+    wrong = [(r[:8], r[8:], plan_row(L, r[:8])) for r in recorded if plan_row(L, r[:8]) != r[8:]]
+    assert not wrong, '%d of %d calls differ, first: %s' % (len(wrong), len(recorded), wrong[:5])
+
+
+if __name__ == '__main__':
+    L = _lib.load()
+    with open(SWEEP_FIXTURE, 'w') as f:
+        f.write('# kind,in_h,in_w,c_in0,c_in1,c_out,flags,views,algorithm,workspace_bytes,tile_count,packed_weight_floats\n')
+        for call in plan_sweep():
+            f.write(','.join(str(v) for v in call + plan_row(L, call)) + '\n')
+    print('recorded %d calls from %s' % (len(plan_sweep()), _lib.LIB_PATH))
