@@ -11,6 +11,26 @@
 //
 // Built with -ffp-contract=off: the integer tap indices of the bilinear sampler (misc.py:16-25) must be the
 // bits the reference's float32 expressions produce (u*(S-1), (S-1) - v*(S-1), floor), so no FMA contraction.
+//
+// Every per-pixel formula of the reference is stated ONCE, as a force-inlined device function that the fused kernels and
+// the stand-alone operators of the drop-in API both call.  Without contraction and without fast-math the same operations
+// on the same operands in the same order give the same bits wherever they are inlined.
+//
+//   NormExact / NormFast              normalize3 (sqrt + divisions) | normalize3_fast (v_rsq): the Norm argument below
+//   TrigOcml / TrigPoly               equirect u, v from ocml's atan2f / acosf | the polynomial pair: the Trig argument
+//   pixel_coords, view_dir<Norm>      view / row / column of a pixel; its camera / world view direction   camera.py:19-30
+//   wrap_face_index, tbn_frame<Norm>  negative face-index wrap; N, B = N x T, T = B x N        render.py:152-161
+//   reflect_ray<Norm>, tbn_ray<Norm>  reflected ray in tangent space; normalise(TBN . lt)      camera.py:43, network.py:455-465
+//   ray_uv<Trig>                      rays_uv from a direction, alpha, the background -1       render.py:96-102, network.py:469-470
+//   Taps::blend / Taps::blend_fma     four-tap blend, plain | explicit-FMA chain               misc.py:42
+//   level_taps                        taps at the texture-level coordinates u (S-1), (S-1) - v (S-1)   network.py:71-85
+//   envmap_taps, envmap_texels        env-map taps min(u W, W-1); the four texel pointers      network.py:497, misc.py:5-42
+//   finish_ray_api                    RayRenderer's group means, albedo choice, five stores    network.py:505-527
+//   RayLanes                          32-lanes-per-pixel layout, net_in row staging, alpha of ray_render / ray_weights
+//   view_offset                       view index and in-view offset from the workgroup quotient
+// Host side: grid256 / ray_grid, transpose_pivots, fill_texture_levels, ray_launch_checks (ni_need and the shared checks).
+// One exception: ray_render_kernel keeps the text of envmap_texels and Taps::blend_fma in its own body (sharing them changed
+// its register allocation); the comment there names what it mirrors.
 #include "rnr_internal.h"
 
 namespace rnr {
@@ -34,6 +54,117 @@ __device__ __forceinline__ float3 normalize3(float3 a) {
 __device__ __forceinline__ float3 normalize3_fast(float3 a) {
     const float inv = fminf(__builtin_amdgcn_rsqf(a.x * a.x + a.y * a.y + a.z * a.z), 1e12f);
     return f3(a.x * inv, a.y * inv, a.z * inv);
+}
+struct NormExact { static __device__ __forceinline__ float3 of(float3 a) { return normalize3(a); } };
+struct NormFast { static __device__ __forceinline__ float3 of(float3 a) { return normalize3_fast(a); } };
+
+// Polynomial atan2 / acos for the fused ray renderer (max abs error 3e-8 / 8e-8 rad, i.e. float rounding level; the
+// uv they feed is only used to pick env-map taps).  ocml's atan2f/acosf cost ~100 instructions each and made this
+// kernel transcendental-bound (26 rays per pixel).  The stand-alone ray-sampler operator keeps the ocml versions.
+__device__ __forceinline__ float fast_atan2f(float y, float x) {
+    const float ax = fabsf(x), ay = fabsf(y);
+    const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
+    const float a = mx > 0.0f ? mn * __builtin_amdgcn_rcpf(mx) : 0.0f;      // 1 ulp reciprocal: the result only picks env-map taps
+    const float s = a * a;
+    // explicit FMAs: this file is compiled with -ffp-contract=off (bit-exact tap indices elsewhere), which would turn
+    // every Horner step into a multiply and an add — the kernel is VALU-bound
+    float p = 0.002899040700867772f;
+    p = __builtin_fmaf(p, s, -0.01637016236782074f);
+    p = __builtin_fmaf(p, s, 0.04338274151086807f);
+    p = __builtin_fmaf(p, s, -0.07582952827215195f);
+    p = __builtin_fmaf(p, s, 0.10688958317041397f);
+    p = __builtin_fmaf(p, s, -0.14219146966934204f);
+    p = __builtin_fmaf(p, s, 0.19995006918907166f);
+    p = __builtin_fmaf(p, s, -0.3333321213722229f);
+    p = __builtin_fmaf(p, s, 1.0f);
+    float r = p * a;
+    if (ay > ax) r = 1.57079632679489662f - r;
+    // quadrant from the sign BITS, as IEEE atan2 (ocml, torch.atan2) does: atan2(-0, x < 0) = -pi and atan2(+-0, -0) = +-pi.
+    // A test of y < 0 gave +pi for y = -0 — u = 1 instead of 0, the env-map tap of column W-1 instead of column 0 — on the
+    // seam direction an axis-aligned -x normal produces with the diffuse pivot (0, 0, 1)
+    if (__builtin_signbit(x)) r = 3.14159265358979324f - r;
+    return __builtin_copysignf(r, y);
+}
+__device__ __forceinline__ float fast_acosf(float x) {
+    const float ax = fminf(fabsf(x), 1.0f);
+    float p = -0.001102376147173345f;
+    p = __builtin_fmaf(p, ax, 0.006096228025853634f);
+    p = __builtin_fmaf(p, ax, -0.01627347804605961f);
+    p = __builtin_fmaf(p, ax, 0.03031114861369133f);
+    p = __builtin_fmaf(p, ax, -0.049957286566495895f);
+    p = __builtin_fmaf(p, ax, 0.08893882483243942f);
+    p = __builtin_fmaf(p, ax, -0.2145957499742508f);
+    p = __builtin_fmaf(p, ax, 1.570796251296997f);
+    const float r = __builtin_amdgcn_sqrtf(1.0f - ax) * p;
+    return x < 0.0f ? 3.14159265358979324f - r : r;
+}
+// equirect u, v of a unit direction before the alpha mask (render.py:96-102): ocml's functions with the reference's
+// operation order, or the polynomial pair with the scaling folded into one FMA / one multiplication
+struct TrigOcml {
+    static __device__ __forceinline__ float u(float z, float x) { return atan2f(z, x) * 0.5f / RNR_PI_F + 0.5f; }
+    static __device__ __forceinline__ float v(float y) { return acosf(y) * 1.0f / RNR_PI_F; }
+};
+struct TrigPoly {
+    static __device__ __forceinline__ float u(float z, float x) { return __builtin_fmaf(fast_atan2f(z, x), 0.5f / RNR_PI_F, 0.5f); }
+    static __device__ __forceinline__ float v(float y) { return fast_acosf(y) * (1.0f / RNR_PI_F); }
+};
+
+// ---- the per-pixel formulas, each stated once -------------------------------------------------------
+// view n, row and column of pixel pix of an [N,H,W] batch
+__device__ __forceinline__ void pixel_coords(long pix, int H, int W, int& n, int& row, int& col) {
+    const int hw = H * W;
+    n = (int)(pix / hw);
+    const int rem = (int)(pix % hw);
+    row = rem / W; col = rem % W;
+}
+// view direction of pixel (row, col) of view n in camera (dc) and world (vd) coordinates (camera.py:19-30)
+template <class Norm>
+__device__ __forceinline__ void view_dir(const float* proj_inv, const float* R_inv, int n, int row, int col, float3& dc, float3& vd) {
+    const float* Pi = proj_inv + n * 9;
+    const float* Ri = R_inv + n * 9;
+    const float pu = (float)col + 0.5f, pv = (float)row + 0.5f;    // camera.py:19-20
+    float3 c = f3(-(Pi[0] * pu + Pi[1] * pv + Pi[2]), -(Pi[3] * pu + Pi[4] * pv + Pi[5]), -(Pi[6] * pu + Pi[7] * pv + Pi[8]));
+    c = Norm::of(c);
+    float3 w = f3(Ri[0] * c.x + Ri[1] * c.y + Ri[2] * c.z, Ri[3] * c.x + Ri[4] * c.y + Ri[5] * c.z,
+                  Ri[6] * c.x + Ri[7] * c.y + Ri[8] * c.z);
+    w = Norm::of(w);
+    dc = c; vd = w;     // (locals, not the references, feed the second product: the callers' machine code stays what it was)
+}
+
+// row of the per-face tangent table a pixel's face index selects: torch's negative index wrap (render.py:152)
+__device__ __forceinline__ int wrap_face_index(int fi, int num_faces) { return fi < 0 ? fi + num_faces : fi; }
+// the orthonormal frame of get_TBN_map from the interpolated normal and the face tangent
+template <class Norm>
+__device__ __forceinline__ void tbn_frame(const float3& normal_in, const float3& tangent, float3& tt, float3& bt, float3& nm) {
+    nm = Norm::of(normal_in);                   // render.py:155
+    bt = Norm::of(cross3(nm, tangent));         // render.py:156-157
+    tt = Norm::of(cross3(bt, nm));              // render.py:160-161
+}
+
+// tangent-space view direction v reflected about the pivot pv, scaled by alpha (camera.py:43, network.py:455-459)
+template <class Norm>
+__device__ __forceinline__ float3 reflect_ray(const float3& pv, const float3& v, float a) {
+    const float s = dot3(pv, v) * 2.0f;                         // camera.py:43
+    const float3 lt = Norm::of(f3(s * pv.x - v.x, s * pv.y - v.y, s * pv.z - v.z));
+    return f3(lt.x * a, lt.y * a, lt.z * a);
+}
+// world direction of the tangent-space ray lt: normalise(TBN . lt), columns T, B, N (network.py:461-465).  The sums run
+// T, B, N in this order whether the caller holds the columns (fused kernel) or the stored row-major 3x3 (ray sampler)
+template <class Norm>
+__device__ __forceinline__ float3 tbn_ray(const float3& tt, const float3& bt, const float3& nm, const float3& lt) {
+    float3 d = f3(tt.x * lt.x + bt.x * lt.y + nm.x * lt.z, tt.y * lt.x + bt.y * lt.y + nm.y * lt.z,
+                  tt.z * lt.x + bt.z * lt.y + nm.z * lt.z);
+    d = Norm::of(d);
+    return d;
+}
+// rays_uv of the unit direction d at a pixel of coverage a; background pixels get -1 (render.py:96-102, network.py:469-470)
+template <class Trig>
+__device__ __forceinline__ void ray_uv(const float3& d, float a, float& u, float& v) {
+    u = Trig::u(d.z, d.x);
+    v = Trig::v(d.y);
+    const float bg = (a == 0.0f) ? 1.0f : 0.0f;
+    u = u * a - bg;
+    v = v * a - bg;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -121,6 +252,14 @@ face_tangents_kernel(rnr_mesh mesh, float* __restrict__ out) {
 struct Taps {
     int x0, y0, x1, y1;
     float w00, w10, w01, w11;
+    // I00*w00 + I10*w10 + I01*w01 + I11*w11 (misc.py:42), every product rounded as the reference's torch ops round it
+    __device__ __forceinline__ float blend(float i00, float i10, float i01, float i11) const {
+        return i00 * w00 + i10 * w10 + i01 * w01 + i11 * w11;
+    }
+    // the same sum as an explicit FMA chain for the VALU-bound ray kernels (see fast_atan2f; <= 1 ulp from blend)
+    __device__ __forceinline__ float blend_fma(float i00, float i10, float i01, float i11) const {
+        return __builtin_fmaf(i11, w11, __builtin_fmaf(i01, w01, __builtin_fmaf(i10, w10, i00 * w00)));
+    }
 };
 __device__ __forceinline__ Taps bilinear_taps(float x, float y, int W, int H) {
     Taps t;
@@ -140,6 +279,30 @@ __device__ __forceinline__ Taps bilinear_taps(float x, float y, int W, int H) {
     t.w01 = (x - x0w) * (y1f - y) * valid;
     t.w11 = (x - x0w) * (y - y0w) * valid;
     return t;
+}
+// taps of a square texture level of size s at uv (TextureMapper.forward, network.py:71-85): x = u (s-1), y = (s-1) - v (s-1)
+__device__ __forceinline__ Taps level_taps(float u, float v, int s) {
+    const float sm1 = (float)(s - 1);
+    const float x = u * sm1;
+    const float y = sm1 - v * sm1;
+    return bilinear_taps(x, y, s, s);
+}
+// env-map taps of a ray (network.py:497; misc.py:5-42): clamp(max=) only, then the validity mask zeroes uv = -1
+__device__ __forceinline__ Taps envmap_taps(float u, float v, int lp_w, int lp_h) {
+    const float x = fminf(u * (float)lp_w, (float)(lp_w - 1));
+    const float y = fminf(v * (float)lp_h, (float)(lp_h - 1));
+    return bilinear_taps(x, y, lp_w, lp_h);
+}
+// the four texels of a three-channel env map (lp_w3 = 3 lp_w) under the taps t.  Texel offsets with 24-bit multiplies (full
+// rate; v_mul_lo_u32 runs at a quarter of it): the probe has far fewer than 2^24 floats
+__device__ __forceinline__ void envmap_texels(const float* lp, int lp_w3, const Taps& t, const float*& l00,
+                                              const float*& l10, const float*& l01, const float*& l11) {
+    const unsigned r0 = __umul24((unsigned)t.y0, (unsigned)lp_w3), r1 = __umul24((unsigned)t.y1, (unsigned)lp_w3);
+    const unsigned q0 = __umul24((unsigned)t.x0, 3u), q1 = __umul24((unsigned)t.x1, 3u);
+    l00 = lp + (r0 + q0);
+    l10 = lp + (r1 + q0);
+    l01 = lp + (r0 + q1);
+    l11 = lp + (r1 + q1);
 }
 
 constexpr int SH_PIX = 32;        // pixels per workgroup (32 beat 16 / 64 / 128 on the GPU: 17 KB of LDS, 9 workgroups per CU)
@@ -177,10 +340,7 @@ __device__ __forceinline__ float4 texture_quad(const ShadeParams& P, float u, fl
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int l = 0; l < P.num_levels; l++) {
         const int s = P.tex_size[l];
-        const float sm1 = (float)(s - 1);
-        const float x = u * sm1;
-        const float y = sm1 - v * sm1;
-        const Taps t = bilinear_taps(x, y, s, s);
+        const Taps t = level_taps(u, v, s);
         // r04: a workgroup-uniform buffer resource per level and one 32-bit lane offset per tap (a level of <= 2 GiB): the flat
         // form spent ~6 VALU instructions of 64-bit address arithmetic on each of the 16 gathers of an item
         const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.tex[l]), 0, 0x7fffffff, 0x27000);
@@ -192,11 +352,8 @@ __device__ __forceinline__ float4 texture_quad(const ShadeParams& P, float u, fl
         const float4 i10 = tap(r1 + c0);
         const float4 i01 = tap(r0 + c1);
         const float4 i11 = tap(r1 + c1);
-        float4 lv;   // I00*w00 + I10*w10 + I01*w01 + I11*w11 (misc.py:42)
-        lv.x = i00.x * t.w00 + i10.x * t.w10 + i01.x * t.w01 + i11.x * t.w11;
-        lv.y = i00.y * t.w00 + i10.y * t.w10 + i01.y * t.w01 + i11.y * t.w11;
-        lv.z = i00.z * t.w00 + i10.z * t.w10 + i01.z * t.w01 + i11.z * t.w11;
-        lv.w = i00.w * t.w00 + i10.w * t.w10 + i01.w * t.w01 + i11.w * t.w11;
+        const float4 lv = make_float4(t.blend(i00.x, i10.x, i01.x, i11.x), t.blend(i00.y, i10.y, i01.y, i11.y),
+                                      t.blend(i00.z, i10.z, i01.z, i11.z), t.blend(i00.w, i10.w, i01.w, i11.w));
         if (l == 0) acc = lv;
         else { acc.x += lv.x; acc.y += lv.y; acc.z += lv.z; acc.w += lv.w; }
     }
@@ -248,28 +405,15 @@ shade_inputs_kernel(const ShadeParams P) {
         const long pix = pix0 + tid;
         float* g = geo + tid * GEO;
         if (pix < P.npix) {
-            const int hw = P.H * P.W;
-            const int n = (int)(pix / hw);
-            const int rem = (int)(pix % hw);
-            const int row = rem / P.W, col = rem % P.W;
-            int fi = P.face_index_map[pix];
-            if (fi < 0) fi += P.num_faces;            // torch negative index wrap (render.py:152)
+            int n, row, col;
+            pixel_coords(pix, P.H, P.W, n, row, col);
+            const int fi = wrap_face_index(P.face_index_map[pix], P.num_faces);
             const float a = P.alpha[pix];
             const float3 tg = f3(P.tangents[fi * 3 + 0], P.tangents[fi * 3 + 1], P.tangents[fi * 3 + 2]);
             const float3 nm_in = f3(P.normal_map[pix * 3 + 0], P.normal_map[pix * 3 + 1], P.normal_map[pix * 3 + 2]);
-            const float3 nm = normalize3_fast(nm_in);                        // render.py:155
-            const float3 bt = normalize3_fast(cross3(nm, tg));               // render.py:156-157
-            const float3 tt = normalize3_fast(cross3(bt, nm));               // render.py:160-161
-            // view direction (camera.py:19-30)
-            const float* Pi = P.proj_inv + n * 9;
-            const float* Ri = P.R_inv + n * 9;
-            const float pu = (float)col + 0.5f, pv = (float)row + 0.5f;
-            float3 dc = f3(-(Pi[0] * pu + Pi[1] * pv + Pi[2]), -(Pi[3] * pu + Pi[4] * pv + Pi[5]),
-                           -(Pi[6] * pu + Pi[7] * pv + Pi[8]));
-            dc = normalize3_fast(dc);
-            float3 vd = f3(Ri[0] * dc.x + Ri[1] * dc.y + Ri[2] * dc.z, Ri[3] * dc.x + Ri[4] * dc.y + Ri[5] * dc.z,
-                           Ri[6] * dc.x + Ri[7] * dc.y + Ri[8] * dc.z);
-            vd = normalize3_fast(vd);
+            float3 tt, bt, nm, dc, vd;
+            tbn_frame<NormFast>(nm_in, tg, tt, bt, nm);
+            view_dir<NormFast>(P.proj_inv, P.R_inv, n, row, col, dc, vd);
             // tangent-space view direction = normalize(TBN^T v) (test_rnr.py:314-315)
             const float3 vt = normalize3_fast(f3(dot3(tt, vd), dot3(bt, vd), dot3(nm, vd)));
             g[0] = tt.x; g[1] = tt.y; g[2] = tt.z;
@@ -318,27 +462,19 @@ shade_inputs_kernel(const ShadeParams P) {
         float3 lt;   // direction in tangent space
         if (r < P.n_spec) {
             const float3 pv = f3(P.piv_spec[r * 3 + 0], P.piv_spec[r * 3 + 1], P.piv_spec[r * 3 + 2]);
-            const float3 v = f3(g[9], g[10], g[11]);
-            const float s = dot3(pv, v) * 2.0f;                         // camera.py:43
-            lt = normalize3_fast(f3(s * pv.x - v.x, s * pv.y - v.y, s * pv.z - v.z));
-            lt = f3(lt.x * a, lt.y * a, lt.z * a);
+            lt = reflect_ray<NormFast>(pv, f3(g[9], g[10], g[11]), a);
         } else {
             const int rd = r - P.n_spec;
             lt = f3(P.piv_diff[rd * 3 + 0], P.piv_diff[rd * 3 + 1], P.piv_diff[rd * 3 + 2]);
         }
-        float3 d = f3(tt.x * lt.x + bt.x * lt.y + nm.x * lt.z, tt.y * lt.x + bt.y * lt.y + nm.y * lt.z,
-                      tt.z * lt.x + bt.z * lt.y + nm.z * lt.z);        // TBN . lt (columns T,B,N)
-        d = normalize3_fast(d);
+        const float3 d = tbn_ray<NormFast>(tt, bt, nm, lt);
         float* tp = tile + p * cp + 3 * r;                              // ray-major, xyz inner (test_rnr.py:350)
         tp[0] = d.x; tp[1] = d.y; tp[2] = d.z;
         if (P.rays_uv) {
             const long pix = pix0 + p;
-            if (pix < P.npix) {                                         // render.py:96-102, network.py:469-470
-                float u = atan2f(d.z, d.x) * 0.5f / RNR_PI_F + 0.5f;
-                float v = acosf(d.y) * 1.0f / RNR_PI_F;
-                const float bg = (a == 0.0f) ? 1.0f : 0.0f;
-                u = u * a - bg;
-                v = v * a - bg;
+            if (pix < P.npix) {
+                float u, v;
+                ray_uv<TrigOcml>(d, a, u, v);
                 P.rays_uv[(pix * 2 + 0) * n_rays + r] = u;
                 P.rays_uv[(pix * 2 + 1) * n_rays + r] = v;
             }
@@ -397,46 +533,6 @@ shade_inputs_kernel(const ShadeParams P) {
 // Ray renderer: 32 lanes per pixel (one ray each), 16-lane segmented shuffle reductions.
 // lane layout inside a 32-lane half: lanes 0..15 -> specular rays 0..15, lanes 16..31 -> diffuse rays 0..15
 // ------------------------------------------------------------------------------------------------
-// Polynomial atan2 / acos for the fused ray renderer (max abs error 3e-8 / 8e-8 rad, i.e. float rounding level; the
-// uv they feed is only used to pick env-map taps).  ocml's atan2f/acosf cost ~100 instructions each and made this
-// kernel transcendental-bound (26 rays per pixel).  The stand-alone ray-sampler operator keeps the ocml versions.
-__device__ __forceinline__ float fast_atan2f(float y, float x) {
-    const float ax = fabsf(x), ay = fabsf(y);
-    const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-    const float a = mx > 0.0f ? mn * __builtin_amdgcn_rcpf(mx) : 0.0f;      // 1 ulp reciprocal: the result only picks env-map taps
-    const float s = a * a;
-    // explicit FMAs: this file is compiled with -ffp-contract=off (bit-exact tap indices elsewhere), which would turn
-    // every Horner step into a multiply and an add — the kernel is VALU-bound
-    float p = 0.002899040700867772f;
-    p = __builtin_fmaf(p, s, -0.01637016236782074f);
-    p = __builtin_fmaf(p, s, 0.04338274151086807f);
-    p = __builtin_fmaf(p, s, -0.07582952827215195f);
-    p = __builtin_fmaf(p, s, 0.10688958317041397f);
-    p = __builtin_fmaf(p, s, -0.14219146966934204f);
-    p = __builtin_fmaf(p, s, 0.19995006918907166f);
-    p = __builtin_fmaf(p, s, -0.3333321213722229f);
-    p = __builtin_fmaf(p, s, 1.0f);
-    float r = p * a;
-    if (ay > ax) r = 1.57079632679489662f - r;
-    // quadrant from the sign BITS, as IEEE atan2 (ocml, torch.atan2) does: atan2(-0, x < 0) = -pi and atan2(+-0, -0) = +-pi.
-    // A test of y < 0 gave +pi for y = -0 — u = 1 instead of 0, the env-map tap of column W-1 instead of column 0 — on the
-    // seam direction an axis-aligned -x normal produces with the diffuse pivot (0, 0, 1)
-    if (__builtin_signbit(x)) r = 3.14159265358979324f - r;
-    return __builtin_copysignf(r, y);
-}
-__device__ __forceinline__ float fast_acosf(float x) {
-    const float ax = fminf(fabsf(x), 1.0f);
-    float p = -0.001102376147173345f;
-    p = __builtin_fmaf(p, ax, 0.006096228025853634f);
-    p = __builtin_fmaf(p, ax, -0.01627347804605961f);
-    p = __builtin_fmaf(p, ax, 0.03031114861369133f);
-    p = __builtin_fmaf(p, ax, -0.049957286566495895f);
-    p = __builtin_fmaf(p, ax, 0.08893882483243942f);
-    p = __builtin_fmaf(p, ax, -0.2145957499742508f);
-    p = __builtin_fmaf(p, ax, 1.570796251296997f);
-    const float r = __builtin_amdgcn_sqrtf(1.0f - ax) * p;
-    return x < 0.0f ? 3.14159265358979324f - r : r;
-}
 
 struct RayParams {
     const float* unet_raw; int c_out_pad;
@@ -473,37 +569,71 @@ __device__ __forceinline__ float seg16_sum(float v) {
 #define RNR_RR_PIX 4
 #endif
 constexpr int RR_PIX = RNR_RR_PIX;     // pixels per lane: independent load chains in flight (the kernel is latency-bound)
+// a 32-lane half-wave owns RR_PIX consecutive pixels; a workgroup owns 8 * RR_PIX consecutive pixels, so every
+// global address is a workgroup-uniform base (SGPR pair) plus a small 32-bit lane offset: no 64-bit VALU math
+constexpr int RR_WG_PIX = 8 * RR_PIX;
+
+// What ray_render_kernel and ray_weights_kernel share: the lane layout above, the coverage of a lane's pixels and the staging
+// of the workgroup's net_in rows
+struct RayLanes {
+    int sub, lp0;           // lane inside the 32-lane half; first pixel of this half-wave inside the workgroup
+    bool is_diff, ray_live; // diffuse group; the lane holds a ray
+    int r;                  // its index among the n_spec + n_diff rays
+    int wg_valid;           // pixels of the workgroup inside the batch
+    __device__ __forceinline__ RayLanes(int n_spec, int n_diff, long npix, long wg_pix0) {
+        sub = (int)(threadIdx.x & 31);
+        lp0 = (int)(threadIdx.x >> 5) * RR_PIX;
+        is_diff = sub >= 16;
+        const int rr = sub & 15;
+        ray_live = is_diff ? rr < n_diff : rr < n_spec;
+        r = is_diff ? n_spec + rr : rr;
+        wg_valid = (int)min((long)RR_WG_PIX, npix - wg_pix0);
+    }
+    __device__ __forceinline__ void load_alpha(const float* wg_alpha, float (&al)[RR_PIX]) const {
+#pragma unroll
+        for (int k = 0; k < RR_PIX; k++) al[k] = (lp0 + k < wg_valid) ? wg_alpha[lp0 + k] : 0.0f;
+    }
+    // Stage the workgroup's rows in LDS with coalesced float4 loads: the vector memory path retires one wave instruction
+    // per ~16 cycles whatever its width, and 3-float-per-lane reads of the rows cost 7 instructions per (pixel, lane
+    // group) — 112 per 32 pixels against 22 for the float4 sweep.  ni_need = ray directions + normal / view + the albedo
+    // channels, rounded up to whole float4s (multiple of 4, <= c_pad): s_ni is [RR_WG_PIX][ni_need]
+    __device__ __forceinline__ void stage_net_in(float* s_ni, const float* wg_net_in, int c_pad, int ni_need) const {
+        const int q_ni = ni_need >> 2;
+        const float inv_q = 1.0f / (float)q_ni;
+        for (int i = threadIdx.x; i < wg_valid * q_ni; i += 256) {
+            const int p = (int)(((float)i + 0.5f) * inv_q), q4 = i - __mul24(p, q_ni);
+            reinterpret_cast<float4*>(s_ni)[i] = *reinterpret_cast<const float4*>(wg_net_in + (unsigned)(__mul24(p, c_pad) + 4 * q4));
+        }
+    }
+};
+// view and in-view offset of the pixel at offset rem0 >= 0 from the start of view n0, walked from the workgroup's (scalar)
+// quotient: no per-lane 64-bit division
+__device__ __forceinline__ void view_offset(long n0, int rem0, int hw, long& n, int& rem) {
+    rem = rem0;
+    n = n0;
+    while (rem >= hw) { rem -= hw; n += 1; }      // at most once unless a view has fewer pixels than a workgroup
+}
 
 __global__ void __launch_bounds__(256)
 ray_render_kernel(const RayParams P) {
-    // a 32-lane half-wave owns RR_PIX consecutive pixels; a workgroup owns 8 * RR_PIX consecutive pixels, so every
-    // global address is a workgroup-uniform base (SGPR pair) plus a small 32-bit lane offset: no 64-bit VALU math
-    constexpr int PIX_PER_WG = 8 * RR_PIX;
+    constexpr int PIX_PER_WG = RR_WG_PIX;
     const long wg_pix0 = (long)blockIdx.x * PIX_PER_WG;
-    const int sub = (int)(threadIdx.x & 31);
-    const int lp0 = (int)(threadIdx.x >> 5) * RR_PIX;       // first pixel of this half-wave inside the workgroup
-    const bool is_diff = sub >= 16;
-    const int rr = sub & 15;
-    const bool ray_live = is_diff ? rr < P.n_diff : rr < P.n_spec;
-    const int r = is_diff ? P.n_spec + rr : rr;
+    const RayLanes L(P.n_spec, P.n_diff, P.npix, wg_pix0);
+    const int sub = L.sub, lp0 = L.lp0, r = L.r, wg_valid = L.wg_valid;
+    const bool ray_live = L.ray_live;
     const long pix0 = wg_pix0 + lp0;
     const long wg_n0 = wg_pix0 / P.hw;                       // workgroup-uniform (SALU)
     const int wg_rem0 = (int)(wg_pix0 - wg_n0 * P.hw);
     const float* wg_net_in = P.net_in + wg_pix0 * P.c_pad;
     const float* wg_raw = P.unet_raw + wg_pix0 * P.c_out_pad;
     const float* wg_alpha = P.alpha + wg_pix0;
-    // Stage the workgroup's rows in LDS with coalesced float4 loads: the vector memory path retires one wave instruction
-    // per ~16 cycles whatever its width, and 3-float-per-lane reads of the rows cost 7 instructions per (pixel, lane
-    // group) — 112 per 32 pixels against 22 for the float4 sweep.  ni_need = ray directions + normal / view + the albedo
-    // channels, rounded up to whole float4s.
+    // unet_raw and net_in rows go through LDS (RayLanes::stage_net_in)
     extern __shared__ __attribute__((aligned(16))) float rr_smem[];
     const int ni_need = P.ni_need;                          // multiple of 4, <= c_pad
     float* s_raw = rr_smem;                                 // [PIX_PER_WG][c_out_pad]
     float* s_ni = rr_smem + PIX_PER_WG * P.c_out_pad;       // [PIX_PER_WG][ni_need]
-    const int wg_valid = (int)min((long)PIX_PER_WG, P.npix - wg_pix0);
     float al[RR_PIX];
-#pragma unroll
-    for (int k = 0; k < RR_PIX; k++) al[k] = (lp0 + k < wg_valid) ? wg_alpha[lp0 + k] : 0.0f;
+    L.load_alpha(wg_alpha, al);
     {
         // r04: a workgroup whose 32 pixels are all background writes its zeros and is done — the frame is exactly 0 there
         // whatever the network produced (rays_uv = -1 masks every env-map tap, network.py:469-470, 497), so neither the 320 +
@@ -517,9 +647,9 @@ ray_render_kernel(const RayParams P) {
 #pragma unroll
                 for (int k = 0; k < RR_PIX; k++) {
                     if (lp0 + k >= wg_valid) continue;
-                    int rem = wg_rem0 + lp0 + k;
-                    long n = wg_n0;
-                    while (rem >= P.hw) { rem -= P.hw; n += 1; }
+                    int rem;
+                    long n;
+                    view_offset(wg_n0, wg_rem0 + lp0 + k, P.hw, n, rem);
 #pragma unroll
                     for (int c = 0; c < 3; c++) P.image[(n * 3 + c) * P.hw + rem] = 0.0f;
                 }
@@ -528,14 +658,10 @@ ray_render_kernel(const RayParams P) {
         }
     }
     {
-        const int q_raw = P.c_out_pad >> 2, q_ni = ni_need >> 2;
+        const int q_raw = P.c_out_pad >> 2;
         const float4* g_raw = reinterpret_cast<const float4*>(wg_raw);
         for (int i = threadIdx.x; i < wg_valid * q_raw; i += 256) reinterpret_cast<float4*>(s_raw)[i] = g_raw[i];
-        const float inv_q = 1.0f / (float)q_ni;
-        for (int i = threadIdx.x; i < wg_valid * q_ni; i += 256) {
-            const int p = (int)(((float)i + 0.5f) * inv_q), q4 = i - __mul24(p, q_ni);
-            reinterpret_cast<float4*>(s_ni)[i] = *reinterpret_cast<const float4*>(wg_net_in + (unsigned)(__mul24(p, P.c_pad) + 4 * q4));
-        }
+        L.stage_net_in(s_ni, wg_net_in, P.c_pad, ni_need);
     }
     __syncthreads();
     float dx[RR_PIX], dy[RR_PIX], dz[RR_PIX], y0[RR_PIX], y1[RR_PIX], y2[RR_PIX];
@@ -556,16 +682,9 @@ ray_render_kernel(const RayParams P) {
     Taps tp[RR_PIX];
 #pragma unroll
     for (int k = 0; k < RR_PIX; k++) {
-        // rays_uv (render.py:96-102; network.py:469-470)
-        float u = __builtin_fmaf(fast_atan2f(dz[k], dx[k]), 0.5f / RNR_PI_F, 0.5f);
-        float v = fast_acosf(dy[k]) * (1.0f / RNR_PI_F);
-        const float bg = (al[k] == 0.0f) ? 1.0f : 0.0f;
-        u = u * al[k] - bg;
-        v = v * al[k] - bg;
-        // env-map taps (network.py:497; misc.py:5-42): clamp(max=) only, then the validity mask zeroes uv = -1
-        const float x = fminf(u * (float)P.lp_w, (float)(P.lp_w - 1));
-        const float y = fminf(v * (float)P.lp_h, (float)(P.lp_h - 1));
-        tp[k] = bilinear_taps(x, y, P.lp_w, P.lp_h);
+        float u, v;
+        ray_uv<TrigPoly>(f3(dx[k], dy[k], dz[k]), al[k], u, v);
+        tp[k] = envmap_taps(u, v, P.lp_w, P.lp_h);
     }
     // mean over the rays of a group as a multiplication by the reciprocal (one division per thread instead of six
     // correctly rounded ones per pixel; <= 1 ulp from network.py:505-513's `.sum(1) / num_ray`)
@@ -578,15 +697,13 @@ ray_render_kernel(const RayParams P) {
         c0[k] = c1[k] = c2[k] = 0.f;
         if (live[k]) {
             const Taps& t = tp[k];
-            // texel offsets with 24-bit multiplies (full rate; v_mul_lo_u32 runs at a quarter of it): the probe has far
-            // fewer than 2^24 floats
+            // (mirrors envmap_texels and Taps::blend_fma: sharing them changed this kernel's register allocation)
             const unsigned r0 = __umul24((unsigned)t.y0, (unsigned)lp_w3), r1 = __umul24((unsigned)t.y1, (unsigned)lp_w3);
             const unsigned q0 = __umul24((unsigned)t.x0, 3u), q1 = __umul24((unsigned)t.x1, 3u);
             const float* l00 = P.lp + (r0 + q0);
             const float* l10 = P.lp + (r1 + q0);
             const float* l01 = P.lp + (r0 + q1);
             const float* l11 = P.lp + (r1 + q1);
-            // (explicit FMAs, see fast_atan2f; the reference's torch ops round every product, <= 1 ulp apart)
             const float col0 = __builtin_fmaf(l11[0], t.w11, __builtin_fmaf(l01[0], t.w01, __builtin_fmaf(l10[0], t.w10, l00[0] * t.w00)));
             const float col1 = __builtin_fmaf(l11[1], t.w11, __builtin_fmaf(l01[1], t.w01, __builtin_fmaf(l10[1], t.w10, l00[1] * t.w00)));
             const float col2 = __builtin_fmaf(l11[2], t.w11, __builtin_fmaf(l01[2], t.w01, __builtin_fmaf(l10[2], t.w10, l00[2] * t.w00)));
@@ -608,10 +725,9 @@ ray_render_kernel(const RayParams P) {
         const long pix = pix0 + k;
         if (sub == 0 && pix < P.npix) {
             const float* ni = s_ni + __mul24(lp0 + k, ni_need) + 3 * (P.n_spec + P.n_diff) + 6;
-            // view / in-view pixel from the workgroup's (scalar) quotient: no per-lane 64-bit division
-            int rem = wg_rem0 + lp0 + k;
-            long n = wg_n0;
-            while (rem >= P.hw) { rem -= P.hw; n += 1; }      // at most once unless a view has fewer pixels than a workgroup
+            int rem;
+            long n;
+            view_offset(wg_n0, wg_rem0 + lp0 + k, P.hw, n, rem);
             const float o[3] = {s0, s1, s2}, dd[3] = {d0, d1, d2};
 #pragma unroll
             for (int c = 0; c < 3; c++) {
@@ -642,32 +758,20 @@ struct RayWeightParams {
 
 __global__ void __launch_bounds__(256)
 ray_weights_kernel(const RayWeightParams P) {
-    constexpr int PIX_PER_WG = 8 * RR_PIX;
+    constexpr int PIX_PER_WG = RR_WG_PIX;
     const long wg_pix0 = (long)blockIdx.x * PIX_PER_WG;
-    const int sub = (int)(threadIdx.x & 31);
-    const int lp0 = (int)(threadIdx.x >> 5) * RR_PIX;
-    const bool is_diff = sub >= 16;
-    const int rr = sub & 15;
-    const bool ray_live = is_diff ? rr < P.n_diff : rr < P.n_spec;
-    const int r = is_diff ? P.n_spec + rr : rr;
+    const RayLanes L(P.n_spec, P.n_diff, P.npix, wg_pix0);
+    const int sub = L.sub, lp0 = L.lp0, r = L.r, wg_valid = L.wg_valid;
+    const bool is_diff = L.is_diff, ray_live = L.ray_live;
     const float* wg_net_in = P.net_in + wg_pix0 * P.c_pad;
     const float* wg_alpha = P.alpha + wg_pix0;
     extern __shared__ __attribute__((aligned(16))) float rw_smem[];
     const int ni_need = P.ni_need;
     float* s_ni = rw_smem;                                  // [PIX_PER_WG][ni_need]
     float* s_w = rw_smem + PIX_PER_WG * ni_need;            // [PIX_PER_WG][c_w]: the weights leave as coalesced float4 rows
-    const int wg_valid = (int)min((long)PIX_PER_WG, P.npix - wg_pix0);
-    {
-        const int q_ni = ni_need >> 2;
-        const float inv_q = 1.0f / (float)q_ni;
-        for (int i = threadIdx.x; i < wg_valid * q_ni; i += 256) {
-            const int p = (int)(((float)i + 0.5f) * inv_q), q4 = i - __mul24(p, q_ni);
-            reinterpret_cast<float4*>(s_ni)[i] = *reinterpret_cast<const float4*>(wg_net_in + (unsigned)(__mul24(p, P.c_pad) + 4 * q4));
-        }
-    }
+    L.stage_net_in(s_ni, wg_net_in, P.c_pad, ni_need);
     float al[RR_PIX];
-#pragma unroll
-    for (int k = 0; k < RR_PIX; k++) al[k] = (lp0 + k < wg_valid) ? wg_alpha[lp0 + k] : 0.0f;
+    L.load_alpha(wg_alpha, al);
     __syncthreads();
     const int lp_w3 = P.lp_w * 3;
     const float inv_n = is_diff ? (P.n_diff > 0 ? 1.0f / (float)P.n_diff : 0.0f) : 1.0f / (float)P.n_spec;
@@ -680,24 +784,15 @@ ray_weights_kernel(const RayWeightParams P) {
         if (sub == 31) for (int c = n_cols; c < P.c_w; c++) out[c] = 0.0f;        // padding columns (lane 31 never holds a ray)
         if (!ray_live) continue;
         const float* d = s_ni + __mul24(lp0 + k, ni_need) + 3 * r;
-        float u = __builtin_fmaf(fast_atan2f(d[2], d[0]), 0.5f / RNR_PI_F, 0.5f);      // render.py:96-102; network.py:469-470
-        float v = fast_acosf(d[1]) * (1.0f / RNR_PI_F);
-        const float bg = (al[k] == 0.0f) ? 1.0f : 0.0f;
-        u = u * al[k] - bg;
-        v = v * al[k] - bg;
-        const float x = fminf(u * (float)P.lp_w, (float)(P.lp_w - 1));                  // network.py:497; misc.py:5-42
-        const float y = fminf(v * (float)P.lp_h, (float)(P.lp_h - 1));
-        const Taps t = bilinear_taps(x, y, P.lp_w, P.lp_h);
-        const unsigned r0 = __umul24((unsigned)t.y0, (unsigned)lp_w3), r1 = __umul24((unsigned)t.y1, (unsigned)lp_w3);
-        const unsigned q0 = __umul24((unsigned)t.x0, 3u), q1 = __umul24((unsigned)t.x1, 3u);
-        const float* l00 = P.lp + (r0 + q0);
-        const float* l10 = P.lp + (r1 + q0);
-        const float* l01 = P.lp + (r0 + q1);
-        const float* l11 = P.lp + (r1 + q1);
+        float u, v;
+        ray_uv<TrigPoly>(f3(d[0], d[1], d[2]), al[k], u, v);
+        const Taps t = envmap_taps(u, v, P.lp_w, P.lp_h);
+        const float *l00, *l10, *l01, *l11;
+        envmap_texels(P.lp, lp_w3, t, l00, l10, l01, l11);
         const float* alb = s_ni + __mul24(lp0 + k, ni_need) + alb_ch;
 #pragma unroll
         for (int c = 0; c < 3; c++) {
-            const float col = __builtin_fmaf(l11[c], t.w11, __builtin_fmaf(l01[c], t.w01, __builtin_fmaf(l10[c], t.w10, l00[c] * t.w00)));
+            const float col = t.blend_fma(l00[c], l10[c], l01[c], l11[c]);
             out[3 * r + c] = (al[k] == 0.0f) ? 0.0f : alb[c] * (col * inv_n);
         }
     }
@@ -835,9 +930,8 @@ interpolate_bilinear_kernel(const float* __restrict__ data, int h, int w, int c,
     if (i >= (long)n * c) return;
     const int s = (int)(i / c), ch = (int)(i % c);
     const Taps t = bilinear_taps(x[s], y[s], w, h);
-    const float v = data[((size_t)t.y0 * w + t.x0) * c + ch] * t.w00 + data[((size_t)t.y1 * w + t.x0) * c + ch] * t.w10 +
-                    data[((size_t)t.y0 * w + t.x1) * c + ch] * t.w01 + data[((size_t)t.y1 * w + t.x1) * c + ch] * t.w11;
-    out[i] = v;
+    out[i] = t.blend(data[((size_t)t.y0 * w + t.x0) * c + ch], data[((size_t)t.y1 * w + t.x0) * c + ch],
+                     data[((size_t)t.y0 * w + t.x1) * c + ch], data[((size_t)t.y1 * w + t.x1) * c + ch]);
     if (taps && ch == 0) {
         taps[s * 4 + 0] = t.x0; taps[s * 4 + 1] = t.y0; taps[s * 4 + 2] = t.x1; taps[s * 4 + 3] = t.y1;
     }
@@ -853,18 +947,10 @@ view_dir_map_kernel(const float* __restrict__ proj_inv, const float* __restrict_
                     float* __restrict__ out_cam, long npix, int H, int W) {
     const long pix = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= npix) return;
-    const int hw = H * W;
-    const int n = (int)(pix / hw), rem = (int)(pix % hw);
-    const int row = rem / W, col = rem % W;
-    const float* Pi = proj_inv + n * 9;
-    const float* Ri = R_inv + n * 9;
-    const float pu = (float)col + 0.5f, pv = (float)row + 0.5f;    // camera.py:19-20
-    float3 dc = f3(-(Pi[0] * pu + Pi[1] * pv + Pi[2]), -(Pi[3] * pu + Pi[4] * pv + Pi[5]),
-                   -(Pi[6] * pu + Pi[7] * pv + Pi[8]));
-    dc = normalize3(dc);
-    float3 vd = f3(Ri[0] * dc.x + Ri[1] * dc.y + Ri[2] * dc.z, Ri[3] * dc.x + Ri[4] * dc.y + Ri[5] * dc.z,
-                   Ri[6] * dc.x + Ri[7] * dc.y + Ri[8] * dc.z);
-    vd = normalize3(vd);
+    int n, row, col;
+    pixel_coords(pix, H, W, n, row, col);
+    float3 dc, vd;
+    view_dir<NormExact>(proj_inv, R_inv, n, row, col, dc, vd);
     out_world[pix * 3 + 0] = vd.x; out_world[pix * 3 + 1] = vd.y; out_world[pix * 3 + 2] = vd.z;
     if (out_cam) { out_cam[pix * 3 + 0] = dc.x; out_cam[pix * 3 + 1] = dc.y; out_cam[pix * 3 + 2] = dc.z; }
 }
@@ -874,12 +960,10 @@ tbn_map_kernel(const float* __restrict__ normal_map, const int32_t* __restrict__
                const float* __restrict__ tangents, int num_faces, float* __restrict__ out, long npix) {
     const long pix = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= npix) return;
-    int fi = face_index_map[pix];
-    if (fi < 0) fi += num_faces;
+    const int fi = wrap_face_index(face_index_map[pix], num_faces);
     const float3 tg = f3(tangents[fi * 3 + 0], tangents[fi * 3 + 1], tangents[fi * 3 + 2]);
-    const float3 nm = normalize3(f3(normal_map[pix * 3 + 0], normal_map[pix * 3 + 1], normal_map[pix * 3 + 2]));
-    const float3 bt = normalize3(cross3(nm, tg));
-    const float3 tt = normalize3(cross3(bt, nm));
+    float3 tt, bt, nm;
+    tbn_frame<NormExact>(f3(normal_map[pix * 3 + 0], normal_map[pix * 3 + 1], normal_map[pix * 3 + 2]), tg, tt, bt, nm);
     float* o = out + pix * 9;      // [3,3] row-major, columns (T, B, N)  (render.py:164)
     o[0] = tt.x; o[1] = bt.x; o[2] = nm.x;
     o[3] = tt.y; o[4] = bt.y; o[5] = nm.y;
@@ -905,16 +989,12 @@ ray_sampler_kernel(const RaySamplerParams P) {
     const float3 pv = f3(P.piv[r * 3 + 0], P.piv[r * 3 + 1], P.piv[r * 3 + 2]);
     float3 lt;
     if (P.reflect) {
-        const float3 v = f3(P.view_tangent[pix * 3 + 0], P.view_tangent[pix * 3 + 1], P.view_tangent[pix * 3 + 2]);
-        const float s = dot3(pv, v) * 2.0f;
-        lt = normalize3(f3(s * pv.x - v.x, s * pv.y - v.y, s * pv.z - v.z));
-        lt = f3(lt.x * a, lt.y * a, lt.z * a);
+        lt = reflect_ray<NormExact>(pv, f3(P.view_tangent[pix * 3 + 0], P.view_tangent[pix * 3 + 1], P.view_tangent[pix * 3 + 2]), a);
     } else {
         lt = pv;
     }
-    float3 d = f3(M[0] * lt.x + M[1] * lt.y + M[2] * lt.z, M[3] * lt.x + M[4] * lt.y + M[5] * lt.z,
-                  M[6] * lt.x + M[7] * lt.y + M[8] * lt.z);
-    d = normalize3(d);
+    // the stored 3x3 is row-major with columns (T, B, N): row i of M . lt is the sum tbn_ray writes column-wise
+    const float3 d = tbn_ray<NormExact>(f3(M[0], M[3], M[6]), f3(M[1], M[4], M[7]), f3(M[2], M[5], M[8]), lt);
     const int R = P.n_rays;
     P.rays_dir[(pix * 3 + 0) * R + r] = d.x;
     P.rays_dir[(pix * 3 + 1) * R + r] = d.y;
@@ -924,11 +1004,10 @@ ray_sampler_kernel(const RaySamplerParams P) {
         P.rays_dir_tangent[(pix * 3 + 1) * R + r] = lt.y;
         P.rays_dir_tangent[(pix * 3 + 2) * R + r] = lt.z;
     }
-    float u = atan2f(d.z, d.x) * 0.5f / RNR_PI_F + 0.5f;
-    float v = acosf(d.y) * 1.0f / RNR_PI_F;
-    const float bg = (a == 0.0f) ? 1.0f : 0.0f;
-    P.rays_uv[(pix * 2 + 0) * R + r] = u * a - bg;
-    P.rays_uv[(pix * 2 + 1) * R + r] = v * a - bg;
+    float u, v;
+    ray_uv<TrigOcml>(d, a, u, v);
+    P.rays_uv[(pix * 2 + 0) * R + r] = u;
+    P.rays_uv[(pix * 2 + 1) * R + r] = v;
 }
 
 struct TexMapParams {
@@ -954,11 +1033,10 @@ texture_mapper_kernel(const TexMapParams P) {
     float acc = 0.f;
     for (int l = 0; l < P.num_levels; l++) {
         const int s = P.tex_size[l];
-        const float sm1 = (float)(s - 1);
-        const Taps t = bilinear_taps(u * sm1, sm1 - v * sm1, s, s);
+        const Taps t = level_taps(u, v, s);
         const float* tex = P.tex[l];
-        const float lv = tex[((size_t)t.y0 * s + t.x0) * P.C + c] * t.w00 + tex[((size_t)t.y1 * s + t.x0) * P.C + c] * t.w10 +
-                         tex[((size_t)t.y0 * s + t.x1) * P.C + c] * t.w01 + tex[((size_t)t.y1 * s + t.x1) * P.C + c] * t.w11;
+        const float lv = t.blend(tex[((size_t)t.y0 * s + t.x0) * P.C + c], tex[((size_t)t.y1 * s + t.x0) * P.C + c],
+                                 tex[((size_t)t.y0 * s + t.x1) * P.C + c], tex[((size_t)t.y1 * s + t.x1) * P.C + c]);
         acc = (l == 0) ? lv : acc + lv;
     }
     if (P.sh && c >= P.sh_start && c < P.sh_start + 9) acc *= P.sh[pix * 9 + (c - P.sh_start)];
@@ -978,6 +1056,24 @@ struct RayApiParams {
     long npix; int hw;
 };
 
+// output element i = (n, c, pixel) from its sums over the specular and the diffuse rays: group means, albedo choice and the
+// optional outputs of RayRenderer.forward (network.py:505-527)
+__device__ __forceinline__ void finish_ray_api(const RayApiParams& P, long i, float s_spec, float s_diff) {
+    const float ls = s_spec / (float)(P.R - P.n_diff);
+    const float as = P.alb_spec[i];
+    const float os = P.no_albedo ? ls : as * ls;
+    float ld = 0.f, od = 0.f;
+    if (P.n_diff > 0) {
+        ld = s_diff / (float)P.n_diff;
+        od = P.no_albedo ? ld : ((P.separate && P.alb_diff) ? P.alb_diff[i] : as) * ld;
+    }
+    P.out[i] = os + od;
+    if (P.out_spec) P.out_spec[i] = os;
+    if (P.out_diff) P.out_diff[i] = od;
+    if (P.ltt_spec) P.ltt_spec[i] = ls;
+    if (P.ltt_diff) P.ltt_diff[i] = ld;
+}
+
 __global__ void __launch_bounds__(256)
 ray_renderer_api_kernel(const RayApiParams P) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;     // over N*C*hw
@@ -992,31 +1088,17 @@ ray_renderer_api_kernel(const RayApiParams P) {
     float ss = 0.f, sd = 0.f;
     for (int r = 0; r < P.R; r++) {
         const float u = P.rays_uv[(pix * 2 + 0) * P.R + r], v = P.rays_uv[(pix * 2 + 1) * P.R + r];
-        const float x = fminf(u * (float)P.lp_w, (float)(P.lp_w - 1));
-        const float y = fminf(v * (float)P.lp_h, (float)(P.lp_h - 1));
-        const Taps t = bilinear_taps(x, y, P.lp_w, P.lp_h);
-        const float col = (lp[((size_t)t.y0 * P.lp_w + t.x0) * P.C + c] * P.lp_scale) * t.w00 +
-                          (lp[((size_t)t.y1 * P.lp_w + t.x0) * P.C + c] * P.lp_scale) * t.w10 +
-                          (lp[((size_t)t.y0 * P.lp_w + t.x1) * P.C + c] * P.lp_scale) * t.w01 +
-                          (lp[((size_t)t.y1 * P.lp_w + t.x1) * P.C + c] * P.lp_scale) * t.w11;
+        const Taps t = envmap_taps(u, v, P.lp_w, P.lp_h);
+        const float col = t.blend(lp[((size_t)t.y0 * P.lp_w + t.x0) * P.C + c] * P.lp_scale,
+                                  lp[((size_t)t.y1 * P.lp_w + t.x0) * P.C + c] * P.lp_scale,
+                                  lp[((size_t)t.y0 * P.lp_w + t.x1) * P.C + c] * P.lp_scale,
+                                  lp[((size_t)t.y1 * P.lp_w + t.x1) * P.C + c] * P.lp_scale);
         const size_t li = (((size_t)n * P.R + r) * P.C + c) * P.hw + p;
         if (P.rays_color) P.rays_color[li] = col;
         const float prod = P.rays_lt[li] * col;
         if (r < n_spec) ss += prod; else sd += prod;
     }
-    const float ls = ss / (float)n_spec;
-    const float as = P.alb_spec[i];
-    const float os = P.no_albedo ? ls : as * ls;
-    float ld = 0.f, od = 0.f;
-    if (P.n_diff > 0) {
-        ld = sd / (float)P.n_diff;
-        od = P.no_albedo ? ld : ((P.separate && P.alb_diff) ? P.alb_diff[i] : as) * ld;
-    }
-    P.out[i] = os + od;
-    if (P.out_spec) P.out_spec[i] = os;
-    if (P.out_diff) P.out_diff[i] = od;
-    if (P.ltt_spec) P.ltt_spec[i] = ls;
-    if (P.ltt_diff) P.ltt_diff[i] = ld;
+    finish_ray_api(P, i, ss, sd);
 }
 
 // The same operator for <= 4 colour channels (the repo's probes have 3): a workgroup owns 64 consecutive pixels; thread (pixel lane,
@@ -1046,9 +1128,7 @@ ray_renderer_api_tiled_kernel(const RayApiParams P) {
     if (live) {
         for (int r = qtr; r < R; r += 4) {
             const float u = ra_sm[lane * urow + r], v = ra_sm[lane * urow + R + r];
-            const float x = fminf(u * (float)P.lp_w, (float)(P.lp_w - 1));
-            const float y = fminf(v * (float)P.lp_h, (float)(P.lp_h - 1));
-            const Taps t = bilinear_taps(x, y, P.lp_w, P.lp_h);
+            const Taps t = envmap_taps(u, v, P.lp_w, P.lp_h);
             const float* l00 = lp + ((size_t)t.y0 * P.lp_w + t.x0) * C;
             const float* l10 = lp + ((size_t)t.y1 * P.lp_w + t.x0) * C;
             const float* l01 = lp + ((size_t)t.y0 * P.lp_w + t.x1) * C;
@@ -1056,8 +1136,7 @@ ray_renderer_api_tiled_kernel(const RayApiParams P) {
 #pragma unroll
             for (int c = 0; c < 4; c++) {
                 if (c >= C) break;
-                const float col = (l00[c] * P.lp_scale) * t.w00 + (l10[c] * P.lp_scale) * t.w10 + (l01[c] * P.lp_scale) * t.w01 +
-                                  (l11[c] * P.lp_scale) * t.w11;
+                const float col = t.blend(l00[c] * P.lp_scale, l10[c] * P.lp_scale, l01[c] * P.lp_scale, l11[c] * P.lp_scale);
                 const size_t li = (((size_t)n * R + r) * C + c) * P.hw + p;
                 if (P.rays_color) P.rays_color[li] = col;
                 const float prod = P.rays_lt[li] * col;
@@ -1080,20 +1159,7 @@ ray_renderer_api_tiled_kernel(const RayApiParams P) {
         s_spec += ra_sm[((q4 * 2 + 0) * 4 + c) * 64 + lane];
         s_diff += ra_sm[((q4 * 2 + 1) * 4 + c) * 64 + lane];
     }
-    const long i = (n * C + c) * P.hw + p;
-    const float ls = s_spec / (float)n_spec;
-    const float as = P.alb_spec[i];
-    const float os = P.no_albedo ? ls : as * ls;
-    float ld = 0.f, od = 0.f;
-    if (P.n_diff > 0) {
-        ld = s_diff / (float)P.n_diff;
-        od = P.no_albedo ? ld : ((P.separate && P.alb_diff) ? P.alb_diff[i] : as) * ld;
-    }
-    P.out[i] = os + od;
-    if (P.out_spec) P.out_spec[i] = os;
-    if (P.out_diff) P.out_diff[i] = od;
-    if (P.ltt_spec) P.ltt_spec[i] = ls;
-    if (P.ltt_diff) P.ltt_diff[i] = ld;
+    finish_ray_api(P, (n * C + c) * P.hw + p, s_spec, s_diff);
 }
 
 // ---- layout helpers --------------------------------------------------------------------------------
@@ -1174,6 +1240,45 @@ nhwc_to_nchw_kernel(const float* __restrict__ in, float* __restrict__ out, const
 
 using namespace rnr;
 
+// ---- host helpers ----------------------------------------------------------------------------------
+// workgroups of 256 threads for `total` one-thread items
+static dim3 grid256(long total) { return dim3((unsigned)((total + 255) / 256)); }
+
+// ray pivots arrive as [3][R] (the reference's layout); the kernels read [R][3]
+static void transpose_pivots(float* dst, const float* src_host, int num_rays) {
+    for (int r = 0; r < num_rays; r++)
+        for (int k = 0; k < 3; k++) dst[r * 3 + k] = src_host[k * num_rays + r];
+}
+
+// texture-level table of a kernel parameter block.  max_level_bytes > 0 bounds a level's size: the buffer-resource path of
+// shade_inputs_kernel addresses texels with 32-bit offsets
+static int fill_texture_levels(const char* fn, const float** tex, int* tex_size, const float* const* textures_host,
+                               const int* tex_sizes_host, int num_levels, int tex_channels, size_t max_level_bytes) {
+    for (int l = 0; l < num_levels; l++) {
+        RNR_REQUIRE(textures_host[l] && tex_sizes_host[l] >= 2, "%s: bad texture level %d", fn, l);
+        RNR_REQUIRE(!max_level_bytes || (size_t)tex_sizes_host[l] * tex_sizes_host[l] * tex_channels * sizeof(float) < max_level_bytes,
+                    "%s: texture level %d exceeds 2 GiB (32-bit texel offsets)", fn, l);
+        tex[l] = textures_host[l];
+        tex_size[l] = tex_sizes_host[l];
+    }
+    return 0;
+}
+
+// What rnr_ray_render and rnr_ray_weights check alike, and ni_need: the floats of a net_in row their kernels stage (ray
+// directions, normal / view, the albedo channels, rounded up to whole float4s).  max_diff is each kernel's own limit.
+static int ray_launch_checks(const char* fn, int num_spec, int num_diff, int max_diff, int lp_h, int lp_w, int albedo_diff_ch,
+                             int albedo_spec_ch, int c_pad, int* ni_need) {
+    RNR_REQUIRE(num_spec >= 1 && num_spec <= 16 && num_diff >= 0 && num_diff <= max_diff,
+                "%s: at most 16 specular / %d diffuse rays (got %d, %d)", fn, max_diff, num_spec, num_diff);
+    RNR_REQUIRE(lp_h >= 2 && lp_w >= 2, "%s: bad light-probe size", fn);
+    const int alb_hi = (albedo_diff_ch > albedo_spec_ch ? albedo_diff_ch : albedo_spec_ch) + 3;
+    *ni_need = (3 * (num_spec + num_diff) + 6 + alb_hi + 3) / 4 * 4;
+    RNR_REQUIRE(*ni_need <= c_pad && c_pad % 4 == 0, "%s: channel stride must be a multiple of 4 and cover the albedo channels", fn);
+    return 0;
+}
+// workgroups of the two ray kernels: 32 lanes per pixel group of RR_PIX pixels
+static dim3 ray_grid(long npix) { return grid256((npix + RR_PIX - 1) / RR_PIX * 32); }
+
 extern "C" int rnr_project_vertices(const float* vertices, const float* K, const float* R, const float* t,
                                     const float* dist_coeffs, const float* offset, const float* scale,
                                     float* out, int num_views, int num_vertices, float orig_size, float eps,
@@ -1182,7 +1287,7 @@ extern "C" int rnr_project_vertices(const float* vertices, const float* K, const
     RNR_REQUIRE((offset == nullptr) == (scale == nullptr), "rnr_project_vertices: offset and scale go together");
     RNR_REQUIRE(num_views > 0 && num_vertices > 0, "rnr_project_vertices: bad sizes");
     const long total = (long)num_views * num_vertices;
-    hipLaunchKernelGGL(project_vertices_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+    hipLaunchKernelGGL(project_vertices_kernel, grid256(total), dim3(256), 0,
                        as_stream(stream), vertices, K, R, t, dist_coeffs, offset, scale, out, num_views,
                        num_vertices, orig_size, eps);
     return check_launch("project_vertices_kernel");
@@ -1219,19 +1324,13 @@ extern "C" int rnr_shade_inputs(const int32_t* face_index_map, const float* alph
     ShadeParams P = {};
     P.face_index_map = face_index_map; P.alpha = alpha; P.uv_map = uv_map; P.normal_map = normal_map;
     P.tangents = face_tangents; P.num_faces = num_faces; P.proj_inv = proj_inv; P.R_inv = R_inv;
-    for (int l = 0; l < num_levels; l++) {
-        RNR_REQUIRE(textures_host[l] && tex_sizes_host[l] >= 2, "rnr_shade_inputs: bad texture level %d", l);
-        RNR_REQUIRE((size_t)tex_sizes_host[l] * tex_sizes_host[l] * tex_channels * sizeof(float) < (1ull << 31),
-                    "rnr_shade_inputs: texture level %d exceeds 2 GiB (32-bit texel offsets)", l);
-        P.tex[l] = textures_host[l];
-        P.tex_size[l] = tex_sizes_host[l];
-    }
+    if (int e = fill_texture_levels("rnr_shade_inputs", P.tex, P.tex_size, textures_host, tex_sizes_host, num_levels, tex_channels,
+                                    (size_t)1 << 31))
+        return e;
     P.num_levels = num_levels; P.C = tex_channels; P.sh_start = sh_start_ch;
     P.n_spec = rays->num_spec; P.n_diff = rays->num_diff;
-    for (int r = 0; r < rays->num_spec; r++)
-        for (int k = 0; k < 3; k++) P.piv_spec[r * 3 + k] = rays->pivots_spec_host[k * rays->num_spec + r];
-    for (int r = 0; r < rays->num_diff; r++)
-        for (int k = 0; k < 3; k++) P.piv_diff[r * 3 + k] = rays->pivots_diff_host[k * rays->num_diff + r];
+    transpose_pivots(P.piv_spec, rays->pivots_spec_host, rays->num_spec);
+    transpose_pivots(P.piv_diff, rays->pivots_diff_host, rays->num_diff);
     P.net_in = net_in; P.c_pad = c_pad; P.rays_uv = rays_uv; P.neural_img = neural_img; P.sh_basis_map = sh_basis_map;
     P.npix = (long)num_views * height * width; P.H = height; P.W = width;
     const size_t lds = (size_t)(SH_PIX * c_pad + SH_PIX * GEO) * sizeof(float);
@@ -1246,21 +1345,18 @@ extern "C" int rnr_ray_render(const float* unet_raw, int c_out_pad, const float*
                               int num_diff, int albedo_diff_ch, int albedo_spec_ch, float* image, int num_views,
                               int height, int width, void* stream) {
     RNR_REQUIRE(unet_raw && bias && net_in && alpha && lp && image, "rnr_ray_render: null pointer argument");
-    RNR_REQUIRE(num_spec >= 1 && num_spec <= 16 && num_diff >= 0 && num_diff <= 16,
-                "rnr_ray_render: ray counts must be <= 16 per group (got %d, %d)", num_spec, num_diff);
-    RNR_REQUIRE(lp_h >= 2 && lp_w >= 2, "rnr_ray_render: bad light-probe size");
     RayParams P;
+    // 16 diffuse rays: one per lane of the second 16-lane segment
+    if (int e = ray_launch_checks("rnr_ray_render", num_spec, num_diff, 16, lp_h, lp_w, albedo_diff_ch, albedo_spec_ch, c_pad, &P.ni_need))
+        return e;
+    RNR_REQUIRE(c_out_pad % 4 == 0, "rnr_ray_render: c_out_pad must be a multiple of 4");
     P.unet_raw = unet_raw; P.c_out_pad = c_out_pad; P.bias = bias; P.net_in = net_in; P.c_pad = c_pad;
     P.alpha = alpha; P.lp = lp; P.lp_h = lp_h; P.lp_w = lp_w; P.n_spec = num_spec; P.n_diff = num_diff;
     P.alb_diff_ch = albedo_diff_ch; P.alb_spec_ch = albedo_spec_ch; P.image = image;
     P.npix = (long)num_views * height * width; P.hw = height * width;
-    const int alb_hi = (albedo_diff_ch > albedo_spec_ch ? albedo_diff_ch : albedo_spec_ch) + 3;
-    P.ni_need = (3 * (num_spec + num_diff) + 6 + alb_hi + 3) / 4 * 4;
-    RNR_REQUIRE(P.ni_need <= c_pad && c_pad % 4 == 0 && c_out_pad % 4 == 0, "rnr_ray_render: channel strides must be multiples of 4 and cover the albedo channels");
-    const long lanes = (P.npix + RR_PIX - 1) / RR_PIX * 32;
-    const size_t lds = (size_t)(8 * RR_PIX) * (size_t)(c_out_pad + P.ni_need) * sizeof(float);
+    const size_t lds = (size_t)RR_WG_PIX * (size_t)(c_out_pad + P.ni_need) * sizeof(float);
     RNR_REQUIRE(lds <= 64 * 1024, "rnr_ray_render: rows too wide for the LDS staging (%zu bytes)", lds);
-    hipLaunchKernelGGL(ray_render_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), lds, as_stream(stream), P);
+    hipLaunchKernelGGL(ray_render_kernel, ray_grid(P.npix), dim3(256), lds, as_stream(stream), P);
     return check_launch("ray_render_kernel");
 }
 
@@ -1268,21 +1364,17 @@ extern "C" int rnr_ray_weights(const float* net_in, int c_pad, const float* alph
                                int num_spec, int num_diff, int albedo_diff_ch, int albedo_spec_ch, float* ray_w, int c_w,
                                int num_views, int height, int width, void* stream) {
     RNR_REQUIRE(net_in && alpha && lp && ray_w, "rnr_ray_weights: null pointer argument");
-    RNR_REQUIRE(num_spec >= 1 && num_spec <= 16 && num_diff >= 0 && num_diff <= 15,
-                "rnr_ray_weights: at most 16 specular / 15 diffuse rays (got %d, %d)", num_spec, num_diff);
-    RNR_REQUIRE(lp_h >= 2 && lp_w >= 2, "rnr_ray_weights: bad light-probe size");
-    RNR_REQUIRE(c_w >= 3 * (num_spec + num_diff), "rnr_ray_weights: c_w %d < 3 * rays", c_w);
     RayWeightParams P;
+    // 15 diffuse rays: lane 31 never holds a ray, it writes the padding columns
+    if (int e = ray_launch_checks("rnr_ray_weights", num_spec, num_diff, 15, lp_h, lp_w, albedo_diff_ch, albedo_spec_ch, c_pad, &P.ni_need))
+        return e;
+    RNR_REQUIRE(c_w >= 3 * (num_spec + num_diff), "rnr_ray_weights: c_w %d < 3 * rays", c_w);
     P.net_in = net_in; P.c_pad = c_pad; P.alpha = alpha; P.lp = lp; P.lp_h = lp_h; P.lp_w = lp_w;
     P.n_spec = num_spec; P.n_diff = num_diff; P.alb_diff_ch = albedo_diff_ch; P.alb_spec_ch = albedo_spec_ch;
     P.ray_w = ray_w; P.c_w = c_w; P.npix = (long)num_views * height * width;
-    const int alb_hi = (albedo_diff_ch > albedo_spec_ch ? albedo_diff_ch : albedo_spec_ch) + 3;
-    P.ni_need = (3 * (num_spec + num_diff) + 6 + alb_hi + 3) / 4 * 4;
-    RNR_REQUIRE(P.ni_need <= c_pad && c_pad % 4 == 0, "rnr_ray_weights: channel stride must be a multiple of 4 and cover the albedo channels");
-    const long lanes = (P.npix + RR_PIX - 1) / RR_PIX * 32;
     RNR_REQUIRE(c_w % 4 == 0, "rnr_ray_weights: c_w must be a multiple of 4");
-    const size_t lds = (size_t)(8 * RR_PIX) * (size_t)(P.ni_need + c_w) * sizeof(float);
-    hipLaunchKernelGGL(ray_weights_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), lds, as_stream(stream), P);
+    const size_t lds = (size_t)RR_WG_PIX * (size_t)(P.ni_need + c_w) * sizeof(float);
+    hipLaunchKernelGGL(ray_weights_kernel, ray_grid(P.npix), dim3(256), lds, as_stream(stream), P);
     return check_launch("ray_weights_kernel");
 }
 
@@ -1355,7 +1447,7 @@ extern "C" int rnr_interpolate_bilinear(const float* data, int h, int w, int c, 
                                         float* out, int32_t* taps, int n, void* stream) {
     RNR_REQUIRE(data && x && y && out && h > 0 && w > 0 && c > 0 && n > 0, "rnr_interpolate_bilinear: bad arguments");
     const long total = (long)n * c;
-    hipLaunchKernelGGL(interpolate_bilinear_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+    hipLaunchKernelGGL(interpolate_bilinear_kernel, grid256(total), dim3(256), 0,
                        as_stream(stream), data, h, w, c, x, y, out, taps, n);
     return check_launch("interpolate_bilinear_kernel");
 }
@@ -1427,7 +1519,7 @@ extern "C" int rnr_resize_area(const float* src, float* dst, int src_h, int src_
                                void* stream) {
     RNR_REQUIRE(src && dst && src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0 && channels > 0, "rnr_resize_area: bad arguments");
     const long total = (long)dst_h * dst_w * channels;
-    hipLaunchKernelGGL(resize_area_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), src, dst,
+    hipLaunchKernelGGL(resize_area_kernel, grid256(total), dim3(256), 0, as_stream(stream), src, dst,
                        src_h, src_w, dst_h, dst_w, channels);
     return check_launch("resize_area_kernel");
 }
@@ -1440,7 +1532,7 @@ extern "C" int rnr_nchw_to_nhwc(const float* in, float* out, int n, int c, int h
         hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3((unsigned)((npix + 63) / 64)), dim3(256), (size_t)c_pad * 65 * sizeof(float),
                            as_stream(stream), in, out, c, h * w, c_pad, total);
     else
-        hipLaunchKernelGGL(nchw_to_nhwc_wide_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream),
+        hipLaunchKernelGGL(nchw_to_nhwc_wide_kernel, grid256(total), dim3(256), 0, as_stream(stream),
                            in, out, c, h * w, c_pad, total);
     return check_launch("nchw_to_nhwc_kernel");
 }
@@ -1454,7 +1546,7 @@ extern "C" int rnr_nhwc_to_nchw(const float* in, float* out, const float* bias, 
         hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3((unsigned)((npix + 63) / 64)), dim3(256), (size_t)c_pad * 65 * sizeof(float),
                            as_stream(stream), in, out, bias, apply_tanh, c, h * w, c_pad, total);
     else
-        hipLaunchKernelGGL(nhwc_to_nchw_wide_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream),
+        hipLaunchKernelGGL(nhwc_to_nchw_wide_kernel, grid256(total), dim3(256), 0, as_stream(stream),
                            in, out, bias, apply_tanh, c, h * w, c_pad, total);
     return check_launch("nhwc_to_nchw_kernel");
 }
@@ -1463,7 +1555,7 @@ extern "C" int rnr_view_dir_map(const float* proj_inv, const float* R_inv, float
                                 int num_views, int height, int width, void* stream) {
     RNR_REQUIRE(proj_inv && R_inv && out_world && num_views > 0 && height > 0 && width > 0, "rnr_view_dir_map: bad arguments");
     const long npix = (long)num_views * height * width;
-    hipLaunchKernelGGL(view_dir_map_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, as_stream(stream),
+    hipLaunchKernelGGL(view_dir_map_kernel, grid256(npix), dim3(256), 0, as_stream(stream),
                        proj_inv, R_inv, out_world, out_cam, npix, height, width);
     return check_launch("view_dir_map_kernel");
 }
@@ -1472,7 +1564,7 @@ extern "C" int rnr_tbn_map(const float* normal_map, const int32_t* face_index_ma
                            int num_faces, float* out, int num_views, int height, int width, void* stream) {
     RNR_REQUIRE(normal_map && face_index_map && face_tangents && out && num_faces > 0, "rnr_tbn_map: bad arguments");
     const long npix = (long)num_views * height * width;
-    hipLaunchKernelGGL(tbn_map_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, as_stream(stream), normal_map,
+    hipLaunchKernelGGL(tbn_map_kernel, grid256(npix), dim3(256), 0, as_stream(stream), normal_map,
                        face_index_map, face_tangents, num_faces, out, npix);
     return check_launch("tbn_map_kernel");
 }
@@ -1498,7 +1590,7 @@ tbn_matvec_kernel(const float* __restrict__ tbn, const float* __restrict__ v, fl
 
 extern "C" int rnr_tbn_matvec(const float* tbn, const float* vec, float* out, long num_pixels, int transposed, void* stream) {
     RNR_REQUIRE(tbn && vec && out && num_pixels > 0, "rnr_tbn_matvec: bad arguments");
-    hipLaunchKernelGGL(tbn_matvec_kernel, dim3((unsigned)((num_pixels + 255) / 256)), dim3(256), 0, as_stream(stream), tbn, vec, out,
+    hipLaunchKernelGGL(tbn_matvec_kernel, grid256(num_pixels), dim3(256), 0, as_stream(stream), tbn, vec, out,
                        num_pixels, transposed);
     return check_launch("tbn_matvec_kernel");
 }
@@ -1512,11 +1604,10 @@ extern "C" int rnr_ray_sampler(int reflect, const float* pivots_host, int num_ra
     RaySamplerParams P;
     P.tbn = tbn; P.view_tangent = view_tangent; P.alpha = alpha; P.rays_dir = rays_dir; P.rays_uv = rays_uv;
     P.rays_dir_tangent = reflect ? rays_dir_tangent : nullptr;
-    for (int r = 0; r < num_rays; r++)
-        for (int k = 0; k < 3; k++) P.piv[r * 3 + k] = pivots_host[k * num_rays + r];
+    transpose_pivots(P.piv, pivots_host, num_rays);
     P.n_rays = num_rays; P.reflect = reflect; P.npix = num_pixels;
     const long total = num_pixels * num_rays;
-    hipLaunchKernelGGL(ray_sampler_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), P);
+    hipLaunchKernelGGL(ray_sampler_kernel, grid256(total), dim3(256), 0, as_stream(stream), P);
     return check_launch("ray_sampler_kernel");
 }
 
@@ -1529,11 +1620,13 @@ extern "C" int rnr_texture_mapper(const float* uv_map, const float* sh_basis_map
                 "rnr_texture_mapper: sh_start_ch + 9 > channels");
     TexMapParams P = {};
     P.uv_map = uv_map; P.sh = sh_basis_map;
-    for (int l = 0; l < num_levels; l++) { P.tex[l] = textures_host[l]; P.tex_size[l] = tex_sizes_host[l]; }
+    // no size bound here: texture_mapper_kernel addresses texels with 64-bit offsets
+    if (int e = fill_texture_levels("rnr_texture_mapper", P.tex, P.tex_size, textures_host, tex_sizes_host, num_levels, tex_channels, 0))
+        return e;
     P.num_levels = num_levels; P.C = tex_channels; P.sh_start = sh_start_ch; P.out = out;
     P.npix = (long)num_views * height * width; P.hw = height * width;
     const long total = P.npix * tex_channels;
-    hipLaunchKernelGGL(texture_mapper_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), P);
+    hipLaunchKernelGGL(texture_mapper_kernel, grid256(total), dim3(256), 0, as_stream(stream), P);
     return check_launch("texture_mapper_kernel");
 }
 
@@ -1559,7 +1652,7 @@ extern "C" int rnr_ray_renderer(const float* rays_uv, const float* rays_lt, cons
         const size_t lds = sizeof(float) * (size_t)std::max(64 * (2 * num_rays + 1), 4 * 2 * 4 * 64);
         hipLaunchKernelGGL(ray_renderer_api_tiled_kernel, dim3((unsigned)((P.npix + 63) / 64)), dim3(256), lds, as_stream(stream), P);
     } else {
-        hipLaunchKernelGGL(ray_renderer_api_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), P);
+        hipLaunchKernelGGL(ray_renderer_api_kernel, grid256(total), dim3(256), 0, as_stream(stream), P);
     }
     return check_launch("ray_renderer_api_kernel");
 }
