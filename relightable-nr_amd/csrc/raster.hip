@@ -6,18 +6,19 @@
 // and, in the fused entry point, the torch glue of network.Rasterizer.forward (network.py:156-214).
 //
 // Design:
-//   1. face_setup_kernel, one lane per (view, face): back-face predicate, the 3x3 barycentric inverse
-//      (same IEEE binary32 operation sequence as the reference, this file is built with
-//      -ffp-contract=off), and a conservative pixel bounding box.  Faces whose box cannot be trusted
-//      (degenerate / sliver / non-finite) are flagged and decided by the exact tile test below.
-//      (On the product path the setup shares the launch and the registers of step 2: setup_splat_faces_kernel.)
-//   2. splat_faces_kernel, one lane per (view, face) (near >= 0, the product path): a face whose trusted box
-//      covers <= 256 pixels walks them itself and folds (depth bits, face index) into a per-pixel 64-bit key
-//      with one atomicMin; a bigger trusted box is binned into the 16x16-pixel tiles it touches (exact,
-//      rounding-monotone tile test); untrusted boxes and huge faces go to a per-view wide list, which
-//      every tile of raster_tile_kernel tests against itself (records of six coordinates + index, 1024 per round
-//      trip).  (near < 0: bin_faces_kernel bins everything.)  With at most two views in the launch four lanes share
-//      a face (box rows modulo 4).
+//   1. face_setup (one lane per (view, face)): back-face predicate, the 3x3 barycentric inverse (same IEEE
+//      binary32 operation sequence as the reference, this file is built with -ffp-contract=off), and a
+//      conservative pixel bounding box.  Faces whose box cannot be trusted (degenerate / sliver / non-finite)
+//      are flagged and decided by the exact tile test (may_touch_tile).
+//   2. What becomes of a face, in the same lane.  near >= 0, the product path: setup_splat_faces_kernel goes on
+//      from the setup's registers — a face whose trusted box covers <= 256 pixels walks them itself
+//      (splat_pixels) and folds (depth bits, face index) into a per-pixel 64-bit key with one atomicMin; every
+//      other face takes bin_or_list_face: a trusted box over at most 64 tiles is binned into the 16x16-pixel
+//      tiles it touches (exact, rounding-monotone tile test), untrusted boxes and huge faces go to a per-view
+//      wide list, which every tile of raster_tile_kernel tests against itself (records of six coordinates +
+//      index, 1024 per round trip).  With at most two views in the launch four lanes share a face (box rows
+//      modulo 4).  near < 0, where the key order does not hold: face_setup_kernel, then bin_faces_kernel puts
+//      every face through bin_or_list_face.
 //   3. raster_tile_kernel, one 256-thread workgroup per tile: evaluates the reference's per-candidate
 //      arithmetic for its binned candidates on LDS-broadcast face records — unordered lists, so the
 //      reference's "ascending faces, strict <" rule is applied in its order-free form (smallest zp, ties ->
@@ -64,6 +65,16 @@ __device__ __forceinline__ float pix_center(int i, int is) {
     // rasterize_cuda_kernel.cu:93-94: (2*i + 1 - is) / is  (exact small integer, one correctly rounded divide)
     return (float)(2 * i + 1 - is) / (float)is;
 }
+// pix_center for the loops that take many centres: where `is` is a power of two, (2i + 1 - is) / is == (2i + 1 - is) * (1 / is)
+// exactly (both are exact), without the division sequence per pixel.  pow2 may be a compile-time constant (splat_pixels).
+struct PixCenter {
+    int is;
+    float inv_is;
+    bool pow2;
+    __device__ __forceinline__ PixCenter(int is_, bool pow2_) : is(is_), inv_is(1.0f / (float)is_), pow2(pow2_) {}
+    __device__ __forceinline__ float operator()(int i) const { return pow2 ? (float)(2 * i + 1 - is) * inv_is : pix_center(i, is); }
+};
+__host__ __device__ __forceinline__ bool is_pow2(int is) { return (is & (is - 1)) == 0; }
 
 // ------------------------------------------------------------------------------------------------
 // 1. per-face setup
@@ -153,6 +164,11 @@ __device__ __forceinline__ bool face_setup(long i, const float* __restrict__ fac
     return true;
 }
 
+struct FaceSetupArgs {
+    const float* faces_in; const float* v_uvz; const int32_t* fidx; int nv;     // GATHER: v_uvz / fidx / nv, else faces_in
+    float* faces_out; float* faces_inv; FaceBox* boxes;                          // faces_out: GATHER only
+};
+
 template <bool GATHER>
 __global__ void __launch_bounds__(256)
 face_setup_kernel(const float* __restrict__ faces_in, const float* __restrict__ v_uvz,
@@ -178,7 +194,17 @@ __device__ __forceinline__ bool edge_rejects_tile(float xa, float ya, float xb, 
     const float q0 = (xlo - xa) * dy, q1 = (xhi - xa) * dy;
     return (p0 < q0) && (p0 < q1) && (p1 < q0) && (p1 < q1);
 }
-
+// the centres of a tile's first / last column and row: what the test above needs of tile (tx, ty)
+struct TileBounds { float xlo, xhi, ylo, yhi; };
+__device__ __forceinline__ TileBounds tile_bounds(int tx, int ty, int is) {
+    const int tx0 = tx * TILE, ty0 = ty * TILE;
+    const int tx1 = min(tx0 + TILE - 1, is - 1), ty1 = min(ty0 + TILE - 1, is - 1);
+    return {pix_center(tx0, is), pix_center(tx1, is), pix_center(ty0, is), pix_center(ty1, is)};
+}
+__device__ __forceinline__ bool may_touch_tile(float x0, float y0, float x1, float y1, float x2, float y2, const TileBounds t) {
+    return !(edge_rejects_tile(x0, y0, x1, y1, t.xlo, t.xhi, t.ylo, t.yhi) || edge_rejects_tile(x1, y1, x2, y2, t.xlo, t.xhi, t.ylo, t.yhi) ||
+             edge_rejects_tile(x2, y2, x0, y0, t.xlo, t.xhi, t.ylo, t.yhi));
+}
 
 // ------------------------------------------------------------------------------------------------
 // 1b. face-parallel binning: O(faces x tiles-per-face) instead of every tile scanning every face.
@@ -190,91 +216,111 @@ __device__ __forceinline__ bool edge_rejects_tile(float xa, float ya, float xb, 
 // ------------------------------------------------------------------------------------------------
 constexpr int BIN_CAP = 2048;
 constexpr int WIDE_TILES = 64;
-
-__device__ __forceinline__ bool face_may_touch_tile(const float* f, int tx, int ty, int is) {
-    const int tx0 = tx * TILE, ty0 = ty * TILE;
-    const int tx1 = min(tx0 + TILE - 1, is - 1), ty1 = min(ty0 + TILE - 1, is - 1);
-    const float xlo = pix_center(tx0, is), xhi = pix_center(tx1, is);
-    const float ylo = pix_center(ty0, is), yhi = pix_center(ty1, is);
-    const float x0 = f[0], y0 = f[1], x1 = f[3], y1 = f[4], x2 = f[6], y2 = f[7];
-    return !(edge_rejects_tile(x0, y0, x1, y1, xlo, xhi, ylo, yhi) || edge_rejects_tile(x1, y1, x2, y2, xlo, xhi, ylo, yhi) ||
-             edge_rejects_tile(x2, y2, x0, y0, xlo, xhi, ylo, yhi));
-}
-
-__device__ __forceinline__ void bin_append(int* tile_count, int* tile_list, int tile, int fn) {
-    const int slot = atomicAdd(tile_count + tile, 1);
-    if (slot < BIN_CAP) tile_list[(size_t)tile * BIN_CAP + slot] = fn;
-}
-// The same test on the six coordinates of a wide-list record (below).
-__device__ __forceinline__ bool coords_may_touch_tile(float x0, float y0, float x1, float y1, float x2, float y2, float xlo,
-                                                      float xhi, float ylo, float yhi) {
-    return !(edge_rejects_tile(x0, y0, x1, y1, xlo, xhi, ylo, yhi) || edge_rejects_tile(x1, y1, x2, y2, xlo, xhi, ylo, yhi) ||
-             edge_rejects_tile(x2, y2, x0, y0, xlo, xhi, ylo, yhi));
-}
-// A face on the wide list leaves, beside its index, the record every tile tests: (x0, y0, x1, y1) (x2, y2, face index, -) —
-// two 16-byte loads at consecutive addresses per lane, where the tile kernel used to chase index -> box -> nine floats at
-// a stride of 36 bytes through three dependent round trips per 256 wide faces (the 65 536-face sphere has 520 of them, its
-// zero-area pole faces: 42 of the tile kernel's 52 us at one view per call, r06).
+// A face on the wide list leaves the record every tile tests: (x0, y0, x1, y1) (x2, y2, face index, -) — two 16-byte loads
+// at consecutive addresses per lane, where the tile kernel used to chase index -> box -> nine floats at a stride of 36 bytes
+// through three dependent round trips per 256 wide faces (the 65 536-face sphere has 520 of them, its zero-area pole faces:
+// 42 of the tile kernel's 52 us at one view per call, r06).
 constexpr int WIDE_REC_FLOATS = 8;
-__device__ __forceinline__ void wide_append(int* wide_count, int* wide_list, float* wide_rec, int bn, int nf, int fn, float x0,
-                                            float y0, float x1, float y1, float x2, float y2) {
-    const int pos = atomicAdd(wide_count + bn, 1);
-    wide_list[(size_t)bn * nf + pos] = fn;
-    float4* r = reinterpret_cast<float4*>(wide_rec + ((size_t)bn * nf + pos) * WIDE_REC_FLOATS);
-    r[0] = make_float4(x0, y0, x1, y1);
-    r[1] = make_float4(x2, y2, __builtin_bit_cast(float, fn), 0.0f);
+
+// what the binning writes: per view, candidate lists of the tiles and the wide list
+struct BinLists {
+    int* tile_count;    // [B,ntiles]  candidates binned per tile (may exceed BIN_CAP: then the tile rescans)
+    int* tile_list;     // [B,ntiles,BIN_CAP]
+    int* wide_count;    // [B]
+    float* wide_rec;    // [B,nf,WIDE_REC_FLOATS]
+};
+
+__device__ __forceinline__ bool box_is_empty(const FaceBox b) { return b.xlo != BOX_EXACT && b.xlo > b.xhi; }  // empty_box()
+// a box that is not empty as pixel ranges inside the image (all of it for an untrusted box, `exact`)
+struct PixBox {
+    int xa, xb, ya, yb;
+    bool exact;
+    __device__ __forceinline__ int pixels() const { return (xb - xa + 1) * (yb - ya + 1); }
+};
+__device__ __forceinline__ PixBox pix_box(const FaceBox b) {
+    return {max((int)b.xlo, 0), b.xhi, max((int)b.ylo, 0), b.yhi, b.xlo == BOX_EXACT};
+}
+
+// Face fn of view bn (box p, coordinates in f[0..8]) is not resolved by its own lane: it is appended to the list of every tile
+// it may touch, or — untrusted box, or more than WIDE_TILES tiles — to the view's wide list.
+__device__ __forceinline__ void bin_or_list_face(const BinLists L, const PixBox p, const float* f, int bn, int fn, int nf, int is) {
+    const int tiles_x = (is + TILE - 1) / TILE;
+    const int txa = p.xa / TILE, txb = p.xb / TILE, tya = p.ya / TILE, tyb = p.yb / TILE;
+    if (p.exact || (txb - txa + 1) * (tyb - tya + 1) > WIDE_TILES) {
+        const int pos = atomicAdd(L.wide_count + bn, 1);
+        float4* r = reinterpret_cast<float4*>(L.wide_rec + ((size_t)bn * nf + pos) * WIDE_REC_FLOATS);
+        r[0] = make_float4(f[0], f[1], f[3], f[4]);
+        r[1] = make_float4(f[6], f[7], __builtin_bit_cast(float, fn), 0.0f);
+        return;
+    }
+    int* tc = L.tile_count + (size_t)bn * tiles_x * tiles_x;
+    int* tl = L.tile_list + (size_t)bn * tiles_x * tiles_x * BIN_CAP;
+    for (int ty = tya; ty <= tyb; ty++)
+        for (int tx = txa; tx <= txb; tx++) {
+            if (!may_touch_tile(f[0], f[1], f[3], f[4], f[6], f[7], tile_bounds(tx, ty, is))) continue;
+            const int tile = ty * tiles_x + tx;
+            const int slot = atomicAdd(tc + tile, 1);
+            if (slot < BIN_CAP) tl[(size_t)tile * BIN_CAP + slot] = fn;
+        }
 }
 
 __global__ void __launch_bounds__(256)
 bin_faces_kernel(const float* __restrict__ faces, const FaceBox* __restrict__ boxes, int* __restrict__ tile_count,
-                 int* __restrict__ tile_list, int* __restrict__ wide_count, int* __restrict__ wide_list,
-                 float* __restrict__ wide_rec, int batch, int nf, int is) {
+                 int* __restrict__ tile_list, int* __restrict__ wide_count, float* __restrict__ wide_rec, int batch, int nf, int is) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)batch * nf) return;
-    const int bn = (int)(i / nf), fn = (int)(i % nf);
     const FaceBox b = boxes[i];
-    if (b.xlo != BOX_EXACT && b.xlo > b.xhi) return;                    // empty_box(): culled / off-screen
-    const int tiles_x = (is + TILE - 1) / TILE;
-    const int ntiles = tiles_x * tiles_x;
-    const int txa = max(b.xlo, (short)0) / TILE, txb = b.xhi / TILE, tya = max(b.ylo, (short)0) / TILE, tyb = b.yhi / TILE;
-    const float* f = faces + i * 9;
-    if (b.xlo == BOX_EXACT || (txb - txa + 1) * (tyb - tya + 1) > WIDE_TILES) {
-        wide_append(wide_count, wide_list, wide_rec, bn, nf, fn, f[0], f[1], f[3], f[4], f[6], f[7]);
-        return;
-    }
-    int* tc = tile_count + (size_t)bn * ntiles;
-    int* tl = tile_list + (size_t)bn * ntiles * BIN_CAP;
-    for (int ty = tya; ty <= tyb; ty++)
-        for (int tx = txa; tx <= txb; tx++)
-            if (face_may_touch_tile(f, tx, ty, is)) bin_append(tc, tl, ty * tiles_x + tx, fn);
+    if (box_is_empty(b)) return;
+    bin_or_list_face({tile_count, tile_list, wide_count, wide_rec}, pix_box(b), faces + i * 9, (int)(i / nf), (int)(i % nf), nf, is);
 }
 
 // The reference's per-(face, pixel) candidate arithmetic (rasterize_cuda_kernel.cu:115-139) on a 24-float face record
-//   r0 = (x0, y0, x1, y1)  r1 = (x2, y2, x1-x0, y1-y0)  r2 = (x2-x1, y2-y1, x0-x2, y0-y2)
-//   r3 = (inv0..3)  r4 = (inv4..7)  r5 = (inv8, z0, z1, z2)
-// Used by the tile kernel (LDS-broadcast records) and by the face-parallel splat kernel: one definition, so both paths
-// produce the same bits for the same (face, pixel).
-__device__ __forceinline__ bool cand_inside(const float4 r0, const float4 r1, const float4 r2, float xp, float yp) {
+//   r0 = (x0, y0, x1, y1)  r1 = (x2, y2, x1-x0, y1-y0)  r2 = (x2-x1, y2-y1, x0-x2, y0-y2)                 the edge half
+//   r3 = (inv0..3)  r4 = (inv4..7)  r5 = (inv8, z0, z1, z2)                                                the depth half
+// One record, one builder per half and one definition of the arithmetic for the pixel walk (splat_pixels), the tile queue
+// (LDS-broadcast records) and the line walk: the same (face, pixel) gives the same bits on every path.
+struct FaceEdges { float4 r0, r1, r2; };
+struct FaceDepth { float4 r3, r4, r5; };
+struct FaceRec { FaceEdges e; FaceDepth d; };
+static_assert(sizeof(FaceRec) == STAGE_FLOATS * sizeof(float), "the LDS image of a record");
+
+__device__ __forceinline__ FaceEdges face_edges(float x0, float y0, float x1, float y1, float x2, float y2) {
+    return {make_float4(x0, y0, x1, y1), make_float4(x2, y2, x1 - x0, y1 - y0), make_float4(x2 - x1, y2 - y1, x0 - x2, y0 - y2)};
+}
+// f / fi: the face's 9 + 9 floats (global memory or the registers of the setup that has just produced them)
+__device__ __forceinline__ FaceDepth face_depth(const float* f, const float* fi) {
+    return {make_float4(fi[0], fi[1], fi[2], fi[3]), make_float4(fi[4], fi[5], fi[6], fi[7]), make_float4(fi[8], f[2], f[5], f[8])};
+}
+__device__ __forceinline__ FaceRec face_rec(const float* f, const float* fi) {
+    return {face_edges(f[0], f[1], f[3], f[4], f[6], f[7]), face_depth(f, fi)};
+}
+
+__device__ __forceinline__ bool cand_inside(const FaceEdges e, float xp, float yp) {
     // inside test (rasterize_cuda_kernel.cu:115-118)
-    if ((yp - r0.y) * r1.z < (xp - r0.x) * r1.w) return false;
-    if ((yp - r0.w) * r2.x < (xp - r0.z) * r2.y) return false;
-    if ((yp - r1.y) * r2.z < (xp - r1.x) * r2.w) return false;
+    if ((yp - e.r0.y) * e.r1.z < (xp - e.r0.x) * e.r1.w) return false;
+    if ((yp - e.r0.w) * e.r2.x < (xp - e.r0.z) * e.r2.y) return false;
+    if ((yp - e.r1.y) * e.r2.z < (xp - e.r1.x) * e.r2.w) return false;
     return true;
 }
-__device__ __forceinline__ bool cand_depth(const float4 r3, const float4 r4, const float4 r5, float fxi, float fyi,
-                                           float near_, float far_, float& zp, float& w0, float& w1, float& w2) {
+__device__ __forceinline__ bool cand_depth(const FaceDepth d, float fxi, float fyi, float near_, float far_, float& zp, float& w0,
+                                           float& w1, float& w2) {
     // w = face_inv * (xi, yi, 1), clamp, renormalise (cu:121-134)
-    w0 = r3.x * fxi + r3.y * fyi + r3.z;
-    w1 = r3.w * fxi + r4.x * fyi + r4.y;
-    w2 = r4.z * fxi + r4.w * fyi + r5.x;
+    w0 = d.r3.x * fxi + d.r3.y * fyi + d.r3.z;
+    w1 = d.r3.w * fxi + d.r4.x * fyi + d.r4.y;
+    w2 = d.r4.z * fxi + d.r4.w * fyi + d.r5.x;
     w0 = fminf(fmaxf(w0, 0.0f), 1.0f);
     w1 = fminf(fmaxf(w1, 0.0f), 1.0f);
     w2 = fminf(fmaxf(w2, 0.0f), 1.0f);
     float wsum = 0.0f;
     wsum += w0; wsum += w1; wsum += w2;
     w0 /= wsum; w1 /= wsum; w2 /= wsum;
-    zp = 1.0f / (w0 / r5.y + w1 / r5.z + w2 / r5.w);   // cu:136
-    return !(zp <= near_ || far_ <= zp);                // cu:137-139 (a NaN zp is rejected by neither test: kept, never wins)
+    zp = 1.0f / (w0 / d.r5.y + w1 / d.r5.z + w2 / d.r5.w);   // cu:136
+    return !(zp <= near_ || far_ <= zp);                      // cu:137-139 (a NaN zp is rejected by neither test: kept, never wins)
+}
+// The reference's winner rule — ascending faces, strict `<` (cu:142-153) — in its order-free form: smallest zp, equal zp ->
+// smallest face index; a NaN zp never wins either way.  (best < 0: nothing yet, best_z = far.)
+__device__ __forceinline__ bool beats(float zp, int fn, float best_z, int best) {
+    return zp < best_z || (zp == best_z && best >= 0 && fn < best);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -282,104 +328,50 @@ __device__ __forceinline__ bool cand_depth(const float4 r3, const float4 r4, con
 //     trusted bounding box, runs the reference's candidate arithmetic on each and folds the result into a per-pixel
 //     64-bit key with ONE atomic:  key = (bits of zp) << 32 | face index,  atomicMin.
 //     For zp > 0 the bit pattern of a float orders like the float, so the minimum key is "smallest zp, ties -> smallest
-//     face index" — exactly the order-free form of the reference's rule (ascending faces, strict `<`, cu:142-153) the
-//     tile kernel applies.  zp > near >= 0 is guaranteed by the near test; a NaN zp never passes `zp < far`-style
-//     comparisons and is skipped here just as it never wins there (see cand_depth: NaN is kept by the reject test, so
-//     it is filtered explicitly).  The path is only taken when near >= 0.
+//     face index" — exactly beats().  The path is only taken when near >= 0.
 //     Work: faces x box pixels (a pixel-sized face of the bench mesh: ~16-36 tests) instead of tiles x candidates x 256.
-//     Faces whose box cannot be trusted (BOX_EXACT) or covers more than SPLAT_MAX_PIX pixels go to the wide list and
-//     to the tile kernel as before; the tile kernel merges both results per pixel.
+//     Every other face goes to the tile lists or the wide list and to the tile kernel (bin_or_list_face); the tile kernel
+//     merges both results per pixel.
 // ------------------------------------------------------------------------------------------------
 constexpr int SPLAT_MAX_PIX = 256;
 constexpr unsigned long long KEY_EMPTY = ~0ull;
 
+// Only a zp > 0 has a key.  zp > near >= 0 is what cand_depth's near test leaves — except a NaN, which no reject test
+// catches (it never wins in beats() either) and whose bits the key order cannot rank: every path that makes keys filters
+// with this first.
+__device__ __forceinline__ bool has_key(float zp) { return zp > 0.0f; }
+__device__ __forceinline__ unsigned long long make_key(float zp, int fn) {
+    return ((unsigned long long)__builtin_bit_cast(unsigned, zp) << 32) | (unsigned)fn;
+}
+__device__ __forceinline__ float key_depth(unsigned long long key) { return __builtin_bit_cast(float, (unsigned)(key >> 32)); }
+__device__ __forceinline__ int key_face(unsigned long long key) { return (int)(unsigned)(key & 0xffffffffull); }
+
 // The pixel walk of one face.  A row is scanned in 32-column pieces: first the cheap inside tests of the piece (a bit per
 // pixel), then the depth arithmetic — seven correctly rounded divisions — for the set bits only: a wave then runs it as
 // often as its busiest lane has inside pixels, not once per column in which ANY lane is inside.
-// POW2: `is` is a power of two, where (2i + 1 - is) / is == (2i + 1 - is) * (1 / is) exactly (both are exact), without the
-// division sequence per pixel.
-template <bool POW2>
-__device__ __forceinline__ void splat_pixels(const float4 r0, const float4 r1, const float4 r2, const float4 r3, const float4 r4,
-                                             const float4 r5, int xa, int xb, int ya, int yb, int ystep, int fn,
+__device__ __forceinline__ void splat_pixels(const FaceRec r, const PixCenter center, int xa, int xb, int ya, int yb, int ystep, int fn,
                                              unsigned long long* __restrict__ kv, int is, float near_, float far_) {
-    const float inv_is = 1.0f / (float)is;
-    auto center = [&](int i) { return POW2 ? (float)(2 * i + 1 - is) * inv_is : pix_center(i, is); };
     for (int yi = ya; yi <= yb; yi += ystep) {
         const float yp = center(yi);
         for (int xc = xa; xc <= xb; xc += 32) {
             const int xe = min(xb, xc + 31);
             unsigned m = 0u;
             for (int xi = xc; xi <= xe; xi++)
-                if (cand_inside(r0, r1, r2, center(xi), yp)) m |= 1u << (xi - xc);
+                if (cand_inside(r.e, center(xi), yp)) m |= 1u << (xi - xc);
             while (m) {
                 const int xi = xc + __builtin_ctz(m);
                 m &= m - 1u;
                 float zp, w0, w1, w2;
-                if (!cand_depth(r3, r4, r5, (float)xi, (float)yi, near_, far_, zp, w0, w1, w2)) continue;
-                if (!(zp > 0.0f)) continue;                             // NaN (and anything the bit order cannot rank)
-                const unsigned long long key = ((unsigned long long)__builtin_bit_cast(unsigned, zp) << 32) | (unsigned)fn;
-                atomicMin(kv + (size_t)yi * is + xi, key);
+                if (!cand_depth(r.d, (float)xi, (float)yi, near_, far_, zp, w0, w1, w2)) continue;
+                if (!has_key(zp)) continue;
+                atomicMin(kv + (size_t)yi * is + xi, make_key(zp, fn));
             }
         }
     }
 }
 
-// f / fi: the face's 9 + 9 floats (global memory or the registers of the setup that has just produced them)
-template <typename FP>
-__device__ __forceinline__ void splat_face(long i, int bn, int fn, const FaceBox b, FP f, FP fi,
-                                           unsigned long long* __restrict__ keys, int* __restrict__ tile_count,
-                                           int* __restrict__ tile_list, int* __restrict__ wide_count, int* __restrict__ wide_list,
-                                           float* __restrict__ wide_rec, int nf, int is, float near_, float far_, int sub = 0,
-                                           int nsub = 1) {
-    // sub / nsub: this lane is one of nsub that share the face (setup_splat_faces_kernel<., LPF>): it walks the box rows
-    // sub, sub + nsub, ...; lane 0 alone bins / lists a face that is not walked
-    if (b.xlo != BOX_EXACT && b.xlo > b.xhi) return;                    // empty_box(): culled / off-screen
-    const int xa = max((int)b.xlo, 0), xb = b.xhi, ya = max((int)b.ylo, 0), yb = b.yhi;
-    if (b.xlo == BOX_EXACT || (xb - xa + 1) * (yb - ya + 1) > SPLAT_MAX_PIX) {
-        if (sub != 0) return;
-        // too big to walk pixel by pixel.  A trusted box over a few tiles is binned right here (bin_faces_kernel's loop);
-        // only untrusted boxes and huge faces take the wide list, whose faces the tile kernel tests against
-        // EVERY tile — with every > 256-pixel face on it, a close-up of a coarse mesh cost wide x tiles pair tests
-        const int tiles_x = (is + TILE - 1) / TILE;
-        const int txa = xa / TILE, txb = xb / TILE, tya = ya / TILE, tyb = yb / TILE;
-        if (b.xlo != BOX_EXACT && (txb - txa + 1) * (tyb - tya + 1) <= WIDE_TILES) {
-            int* tc = tile_count + (size_t)bn * tiles_x * tiles_x;
-            int* tl = tile_list + (size_t)bn * tiles_x * tiles_x * BIN_CAP;
-            for (int ty = tya; ty <= tyb; ty++)
-                for (int tx = txa; tx <= txb; tx++)
-                    if (face_may_touch_tile(f, tx, ty, is)) bin_append(tc, tl, ty * tiles_x + tx, fn);
-            return;
-        }
-        wide_append(wide_count, wide_list, wide_rec, bn, nf, fn, f[0], f[1], f[3], f[4], f[6], f[7]);
-        return;
-    }
-    const float x0 = f[0], y0 = f[1], z0 = f[2], x1 = f[3], y1 = f[4], z1 = f[5], x2 = f[6], y2 = f[7], z2 = f[8];
-    const float4 r0 = make_float4(x0, y0, x1, y1);
-    const float4 r1 = make_float4(x2, y2, x1 - x0, y1 - y0);
-    const float4 r2 = make_float4(x2 - x1, y2 - y1, x0 - x2, y0 - y2);
-    const float4 r3 = make_float4(fi[0], fi[1], fi[2], fi[3]);
-    const float4 r4 = make_float4(fi[4], fi[5], fi[6], fi[7]);
-    const float4 r5 = make_float4(fi[8], z0, z1, z2);
-    unsigned long long* kv = keys + (size_t)bn * is * is;
-    if ((is & (is - 1)) == 0) splat_pixels<true>(r0, r1, r2, r3, r4, r5, xa, xb, ya + sub, yb, nsub, fn, kv, is, near_, far_);
-    else splat_pixels<false>(r0, r1, r2, r3, r4, r5, xa, xb, ya + sub, yb, nsub, fn, kv, is, near_, far_);
-}
-
-__global__ void __launch_bounds__(256)
-splat_faces_kernel(const float* __restrict__ faces, const float* __restrict__ faces_inv, const FaceBox* __restrict__ boxes,
-                   unsigned long long* __restrict__ keys, int* __restrict__ tile_count, int* __restrict__ tile_list,
-                   int* __restrict__ wide_count, int* __restrict__ wide_list, float* __restrict__ wide_rec, int batch, int nf,
-                   int is, float near_, float far_) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)batch * nf) return;
-    splat_face<const float*>(i, (int)(i / nf), (int)(i % nf), boxes[i], faces + i * 9, faces_inv + i * 9, keys, tile_count,
-                             tile_list, wide_count, wide_list, wide_rec, nf, is, near_, far_);
-}
-
-// face_setup_kernel + splat_faces_kernel in one launch (r04): both are one lane per (view, face) and the splat needs nothing
-// but its own face's record, which it takes from the registers of the setup — the same values the setup writes for the tile
-// kernel, hence the same bits as the two launches (tests/test_gpu_raster.py).
-struct FaceSetupArgs { const float* faces_in; const float* v_uvz; const int32_t* fidx; float* faces_out; int nv; int gather; };
+// face_setup + the splat in one launch (r04): both are one lane per (view, face) and the splat needs nothing but its own
+// face's record, which it takes from the registers of the setup — the same values the setup writes for the tile kernel.
 // LPF lanes per face (r06): with a single view in the launch two thirds of the waves hold back faces only and leave at once,
 // the others walk ~30 pixels per lane at one wave per SIMD; four lanes per face (each repeats the setup — same instructions,
 // lane 0 stores — and walks every fourth box row) spread the live faces over four times the waves: 23.8 -> 15.7 us per 512^2 view.
@@ -389,17 +381,26 @@ __global__ void __launch_bounds__(256)
 setup_splat_faces_kernel(const float* __restrict__ faces_in, const float* __restrict__ v_uvz, const int32_t* __restrict__ fidx,
                          float* __restrict__ faces_out, float* __restrict__ faces_inv, FaceBox* __restrict__ boxes,
                          unsigned long long* __restrict__ keys, int* __restrict__ tile_count, int* __restrict__ tile_list,
-                         int* __restrict__ wide_count, int* __restrict__ wide_list, float* __restrict__ wide_rec, int batch,
-                         int nf, int nv, int is, float near_, float far_) {
+                         int* __restrict__ wide_count, float* __restrict__ wide_rec, int batch, int nf, int nv, int is,
+                         float near_, float far_) {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long i = t / LPF;
-    const int sub = (int)(t % LPF);
+    const int sub = (int)(t % LPF);     // this lane walks the box rows sub, sub + LPF, ...; lane 0 alone stores, bins and lists
     if (i >= (long)batch * nf) return;
     float f[9], inv[9];
-    FaceBox box;
-    if (!face_setup<GATHER>(i, faces_in, v_uvz, fidx, faces_out, faces_inv, boxes, nf, nv, is, f, inv, box, sub == 0)) return;
-    splat_face<const float (&)[9]>(i, (int)(i / nf), (int)(i % nf), box, f, inv, keys, tile_count, tile_list, wide_count,
-                                   wide_list, wide_rec, nf, is, near_, far_, sub, LPF);
+    FaceBox b;
+    if (!face_setup<GATHER>(i, faces_in, v_uvz, fidx, faces_out, faces_inv, boxes, nf, nv, is, f, inv, b, sub == 0)) return;
+    const int bn = (int)(i / nf), fn = (int)(i % nf);
+    if (box_is_empty(b)) return;
+    const PixBox p = pix_box(b);
+    if (p.exact || p.pixels() > SPLAT_MAX_PIX) {        // not to be walked pixel by pixel
+        if (sub == 0) bin_or_list_face({tile_count, tile_list, wide_count, wide_rec}, p, f, bn, fn, nf, is);
+        return;
+    }
+    const FaceRec r = face_rec(f, inv);
+    unsigned long long* kv = keys + (size_t)bn * is * is;
+    if (is_pow2(is)) splat_pixels(r, PixCenter(is, true), p.xa, p.xb, p.ya + sub, p.yb, LPF, fn, kv, is, near_, far_);
+    else splat_pixels(r, PixCenter(is, false), p.xa, p.xb, p.ya + sub, p.yb, LPF, fn, kv, is, near_, far_);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -413,8 +414,7 @@ struct RasterParams {
     const int* tile_list;    // [B,ntiles,BIN_CAP]
     const unsigned long long* keys;   // [B,is,is] winners of the face-parallel path (KEY_EMPTY = none) or NULL
     const int* wide_count;   // [B] faces on the wide list: untrusted or huge boxes, tested by every tile itself
-    const int* wide_list;    // [B,nf]
-    const float* wide_rec;   // [B,nf,WIDE_REC_FLOATS] what the tiles test of a wide face (wide_append)
+    const float* wide_rec;   // [B,nf,WIDE_REC_FLOATS] what the tiles test of a wide face (bin_or_list_face)
     int nf, is;
     float near_, far_;
     int flip;                // 1: write row (is-1-yi)
@@ -428,6 +428,111 @@ struct RasterParams {
     rnr_gbuffer gb;
     const float* pose;       // [B,4,4] or NULL
 };
+
+// Wave-ballot compaction into an LDS queue: the lanes of a wave whose pred holds take consecutive slots from *counter, one
+// LDS atomic per wave.  Returns the lane's slot (meaningless where pred is false).
+__device__ __forceinline__ int queue_slot(bool pred, int* counter, int lane) {
+    const unsigned long long bal = __ballot(pred);
+    if (!bal) return 0;                                 // wave-uniform: most calls add nothing
+    int base = 0;
+    if (lane == 0) base = atomicAdd(counter, __popcll(bal));
+    base = __shfl(base, 0, 64);
+    return base + __popcll(bal & ((1ull << lane) - 1ull));
+}
+
+// Epilogue, drop-in mode: the extension's maps.  Uncovered pixels keep the caller's pre-fill (cu:156-168).
+__device__ __forceinline__ void write_dropin_maps(const RasterParams& P, const float* faces_inv, size_t pix, int best, float best_z,
+                                                  float bw0, float bw1, float bw2) {
+    if (best < 0) return;
+    P.depth_map[pix] = best_z;
+    P.face_index_map[pix] = best;
+    P.weight_map[3 * pix + 0] = bw0;
+    P.weight_map[3 * pix + 1] = bw1;
+    P.weight_map[3 * pix + 2] = bw2;
+    if (P.face_inv_map) {
+        const float* fi = faces_inv + (size_t)best * 9;
+#pragma unroll
+        for (int k = 0; k < 9; k++) P.face_inv_map[9 * pix + k] = fi[k];
+    }
+}
+
+// out = the rows idx[0..2] of attr [.,N], blended with the perspective-corrected weights
+template <int N>
+__device__ __forceinline__ void blend_rows(const float* attr, const int32_t* idx, float wp0, float wp1, float wp2, float (&out)[N]) {
+    const float* a = attr + (size_t)idx[0] * N;
+    const float* b = attr + (size_t)idx[1] * N;
+    const float* c = attr + (size_t)idx[2] * N;
+#pragma unroll
+    for (int k = 0; k < N; k++) out[k] = a[k] * wp0 + b[k] * wp1 + c[k] * wp2;
+}
+
+// Epilogue, fused mode: network.Rasterizer.forward's attribute interpolation (network.py:176-214)
+__device__ __forceinline__ void write_gbuffer(const RasterParams& P, const float* faces, int bn, size_t pix, int best, float best_z,
+                                              float bw0, float bw1, float bw2) {
+    const rnr_gbuffer& G = P.gb;
+    const int fa = best >= 0 ? best : P.nf - 1;  // torch indexing wraps -1 to the last face (weights are 0 there)
+    const float* f = faces + (size_t)fa * 9;
+    const float depth = best_z;                 // far on background (rasterize.py:52)
+    const float wp0 = ((1.0f / f[2]) * bw0) * depth;
+    const float wp1 = ((1.0f / f[5]) * bw1) * depth;
+    const float wp2 = ((1.0f / f[8]) * bw2) * depth;
+    if (G.face_index_map) G.face_index_map[pix] = best;
+    if (G.alpha) G.alpha[pix] = best >= 0 ? 1.0f : 0.0f;
+    if (G.depth) G.depth[pix] = depth;
+    if (G.raw_weight_map) {
+        G.raw_weight_map[3 * pix + 0] = bw0; G.raw_weight_map[3 * pix + 1] = bw1; G.raw_weight_map[3 * pix + 2] = bw2;
+    }
+    if (G.weight_map) {
+        G.weight_map[3 * pix + 0] = wp0; G.weight_map[3 * pix + 1] = wp1; G.weight_map[3 * pix + 2] = wp2;
+    }
+    if (G.uv_map) {
+        float uv[2];
+        blend_rows<2>(P.mesh.vt, P.mesh.f_vt_idx + (size_t)fa * 3, wp0, wp1, wp2, uv);
+        G.uv_map[2 * pix + 0] = uv[0] - floorf(uv[0]);
+        G.uv_map[2 * pix + 1] = uv[1] - floorf(uv[1]);
+    }
+    float R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, T[3] = {0, 0, 0};
+    if (P.pose) {
+        const float* ps = P.pose + (size_t)bn * 16;
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            R[3 * r + 0] = ps[4 * r + 0]; R[3 * r + 1] = ps[4 * r + 1]; R[3 * r + 2] = ps[4 * r + 2];
+            T[r] = ps[4 * r + 3];
+        }
+    }
+    if (G.normal_map || G.normal_map_cam) {
+        float n[3];
+        blend_rows<3>(P.mesh.vn, P.mesh.f_vn_idx + (size_t)fa * 3, wp0, wp1, wp2, n);
+        float n0 = n[0], n1 = n[1], n2 = n[2];
+        float inv = 1.0f / fmaxf(sqrtf(n0 * n0 + n1 * n1 + n2 * n2), 1e-12f);  // F.normalize
+        n0 *= inv; n1 *= inv; n2 *= inv;
+        if (G.normal_map) {
+            G.normal_map[3 * pix + 0] = n0; G.normal_map[3 * pix + 1] = n1; G.normal_map[3 * pix + 2] = n2;
+        }
+        if (G.normal_map_cam) {
+            float c0 = R[0] * n0 + R[1] * n1 + R[2] * n2;
+            float c1 = R[3] * n0 + R[4] * n1 + R[5] * n2;
+            float c2 = R[6] * n0 + R[7] * n1 + R[8] * n2;
+            float ic = 1.0f / fmaxf(sqrtf(c0 * c0 + c1 * c1 + c2 * c2), 1e-12f);
+            G.normal_map_cam[3 * pix + 0] = c0 * ic;
+            G.normal_map_cam[3 * pix + 1] = c1 * ic;
+            G.normal_map_cam[3 * pix + 2] = c2 * ic;
+        }
+    }
+    if (G.position_map || G.position_map_cam) {
+        float p[3];
+        blend_rows<3>(P.mesh.v, P.mesh.f_v_idx + (size_t)fa * 3, wp0, wp1, wp2, p);
+        const float p0 = p[0], p1 = p[1], p2 = p[2];
+        if (G.position_map) {
+            G.position_map[3 * pix + 0] = p0; G.position_map[3 * pix + 1] = p1; G.position_map[3 * pix + 2] = p2;
+        }
+        if (G.position_map_cam) {
+            G.position_map_cam[3 * pix + 0] = R[0] * p0 + R[1] * p1 + R[2] * p2 + T[0];
+            G.position_map_cam[3 * pix + 1] = R[3] * p0 + R[4] * p1 + R[5] * p2 + T[1];
+            G.position_map_cam[3 * pix + 2] = R[6] * p0 + R[7] * p1 + R[8] * p2 + T[2];
+        }
+    }
+}
 
 template <int MODE>
 __global__ void __launch_bounds__(RTHREADS)
@@ -450,8 +555,7 @@ raster_tile_kernel(const RasterParams P) {
     const int tx1 = min(tx0 + TILE - 1, is - 1), ty1 = min(ty0 + TILE - 1, is - 1);
     const float xp = pix_center(xi, is), yp = pix_center(yi, is);
     const float fxi = (float)xi, fyi = (float)yi;
-    const float t_xlo = pix_center(tx0, is), t_xhi = pix_center(tx1, is);
-    const float t_ylo = pix_center(ty0, is), t_yhi = pix_center(ty1, is);
+    const TileBounds tb = tile_bounds(tile % tiles_x, tile / tiles_x, is);
 
     const float* faces = P.faces + (size_t)bn * nf * 9;
     const float* faces_inv = P.faces_inv + (size_t)bn * nf * 9;
@@ -469,36 +573,23 @@ raster_tile_kernel(const RasterParams P) {
     s_key[tid] = KEY_EMPTY;
     __syncthreads();
 
-    // Evaluate the queued candidates.  The queue is NOT in face order (waves append independently), so the
-    // reference's "ascending faces, strict <" rule (cu:142-153) is applied as its order-free equivalent:
-    // smallest zp wins, equal zp -> smallest face index; a NaN zp never wins either way.
+    // Evaluate the queued candidates.  The queue is NOT in face order (waves append independently): beats() is order-free.
     auto process_queue = [&](const int* ids, int qn) {
+        FaceRec* stage = reinterpret_cast<FaceRec*>(s_stage);
         for (int s0 = 0; s0 < qn; s0 += STAGE) {
             const int n = min(STAGE, qn - s0);
             if (tid < n) {
                 const int fn = ids[s0 + tid];
-                const float* f = faces + (size_t)fn * 9;
-                const float* fi = faces_inv + (size_t)fn * 9;
-                float4* dst = reinterpret_cast<float4*>(s_stage + tid * STAGE_FLOATS);
-                const float x0 = f[0], y0 = f[1], z0 = f[2], x1 = f[3], y1 = f[4], z1 = f[5], x2 = f[6],
-                            y2 = f[7], z2 = f[8];
-                dst[0] = make_float4(x0, y0, x1, y1);
-                dst[1] = make_float4(x2, y2, x1 - x0, y1 - y0);
-                dst[2] = make_float4(x2 - x1, y2 - y1, x0 - x2, y0 - y2);
-                dst[3] = make_float4(fi[0], fi[1], fi[2], fi[3]);
-                dst[4] = make_float4(fi[4], fi[5], fi[6], fi[7]);
-                dst[5] = make_float4(fi[8], z0, z1, z2);
+                stage[tid] = face_rec(faces + (size_t)fn * 9, faces_inv + (size_t)fn * 9);
             }
             __syncthreads();
             if (in_img) {
                 for (int c = 0; c < n; c++) {
-                    const float4* rec = reinterpret_cast<const float4*>(s_stage + c * STAGE_FLOATS);
-                    const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
-                    if (!cand_inside(r0, r1, r2, xp, yp)) continue;
+                    if (!cand_inside(stage[c].e, xp, yp)) continue;
                     float zp, w0, w1, w2;
-                    if (!cand_depth(rec[3], rec[4], rec[5], fxi, fyi, P.near_, P.far_, zp, w0, w1, w2)) continue;
+                    if (!cand_depth(stage[c].d, fxi, fyi, P.near_, P.far_, zp, w0, w1, w2)) continue;
                     const int fn = ids[s0 + c];
-                    if (zp < best_z || (zp == best_z && best >= 0 && fn < best)) {  // cu:142, order-free form
+                    if (beats(zp, fn, best_z, best)) {
                         best_z = zp;
                         best = fn;
                         bw0 = w0; bw1 = w1; bw2 = w2;
@@ -549,10 +640,7 @@ raster_tile_kernel(const RasterParams P) {
         dst[1] = make_float4(x2, y2, rb.z, steep ? 1.0f : 0.0f);
         reinterpret_cast<double2*>(dst)[2] = make_double2(c0, c1);
     };
-    const bool pow2 = (is & (is - 1)) == 0;
-    const float inv_is = 1.0f / (float)is;
-    // pix_center without the division where `is` is a power of two (both forms are exact there)
-    auto center = [&](int i) { return pow2 ? (float)(2 * i + 1 - is) * inv_is : pix_center(i, is); };
+    const PixCenter center(is, is_pow2(is));
     // The first RTHREADS records were staged by the lanes that queued them (registers -> LDS, no second fetch); later batches
     // are fetched again by their slot number.
     auto walk_lines = [&](int dn) {
@@ -571,7 +659,6 @@ raster_tile_kernel(const RasterParams P) {
                 const float4* rec = reinterpret_cast<const float4*>(s_stage + c * LINE_FLOATS);
                 const float4 ra = rec[0], rb = rec[1];
                 const double2 cc = reinterpret_cast<const double2*>(rec)[2];
-                const float x0 = ra.x, y0 = ra.y, x1 = ra.z, y1 = ra.w, x2 = rb.x, y2 = rb.y;
                 const int fn = __builtin_bit_cast(int, rb.z);
                 const bool steep = rb.w != 0.0f;
                 // the crossing of this lane's row (steep) or column with the line, in pixel coordinates
@@ -580,23 +667,18 @@ raster_tile_kernel(const RasterParams P) {
                 const double tp = cc.x + cc.y * (double)cf;
                 if (!(tp > -2.0 && tp < (double)is + 1.0)) continue;
                 const int lo = (int)floor(tp);
-                const float4 r0 = make_float4(x0, y0, x1, y1);
-                const float4 r1 = make_float4(x2, y2, x1 - x0, y1 - y0);
-                const float4 r2 = make_float4(x2 - x1, y2 - y1, x0 - x2, y0 - y2);
+                const FaceEdges e = face_edges(ra.x, ra.y, ra.z, ra.w, rb.x, rb.y);
 #pragma unroll
                 for (int side = 0; side < 2; side++) {
                     const int pxi = steep ? lo + side : fixed, pyi = steep ? fixed : lo + side;
                     if (pxi < tx0 || pxi > tx1 || pyi < ty0 || pyi > ty1) continue;
-                    if (!cand_inside(r0, r1, r2, steep ? center(pxi) : cf, steep ? cf : center(pyi))) continue;
-                    const float* f = faces + (size_t)fn * 9;
-                    const float* fi = faces_inv + (size_t)fn * 9;
+                    if (!cand_inside(e, steep ? center(pxi) : cf, steep ? cf : center(pyi))) continue;
                     float zp, w0, w1, w2;
-                    if (!cand_depth(make_float4(fi[0], fi[1], fi[2], fi[3]), make_float4(fi[4], fi[5], fi[6], fi[7]),
-                                    make_float4(fi[8], f[2], f[5], f[8]), (float)pxi, (float)pyi, P.near_, P.far_, zp, w0, w1, w2))
+                    if (!cand_depth(face_depth(faces + (size_t)fn * 9, faces_inv + (size_t)fn * 9), (float)pxi, (float)pyi, P.near_,
+                                    P.far_, zp, w0, w1, w2))
                         continue;
-                    if (!(zp > 0.0f)) continue;         // NaN (never wins) — and the key order needs zp > 0 (near >= 0 here)
-                    atomicMin(&s_key[(pyi - ty0) * TILE + (pxi - tx0)],
-                              ((unsigned long long)__builtin_bit_cast(unsigned, zp) << 32) | (unsigned)fn);
+                    if (!has_key(zp)) continue;         // (near >= 0 here)
+                    atomicMin(&s_key[(pyi - ty0) * TILE + (pxi - tx0)], make_key(zp, fn));
                 }
             }
             __syncthreads();
@@ -619,33 +701,21 @@ raster_tile_kernel(const RasterParams P) {
             for (int j = 0; j < WIDE_ITEMS; j++) {
                 const int w = w0 + j * RTHREADS + tid;
                 if (w0 + j * RTHREADS >= wn) break;                     // block-uniform
-                const bool k = w < wn && coords_may_touch_tile(ra[j].x, ra[j].y, ra[j].z, ra[j].w, rb[j].x, rb[j].y, t_xlo, t_xhi,
-                                                               t_ylo, t_yhi);
+                const float x0 = ra[j].x, y0 = ra[j].y, x1 = ra[j].z, y1 = ra[j].w, x2 = rb[j].x, y2 = rb[j].y;
+                const bool k = w < wn && may_touch_tile(x0, y0, x1, y1, x2, y2, tb);
                 bool line = false;
                 if (k && P.keys) {      // (P.keys: near >= 0)
-                    const float x0 = ra[j].x, y0 = ra[j].y, x1 = ra[j].z, y1 = ra[j].w, x2 = rb[j].x, y2 = rb[j].y;
                     const int ne = (x0 == x1 && y0 == y1 ? 1 : 0) + (x1 == x2 && y1 == y2 ? 1 : 0) + (x2 == x0 && y2 == y0 ? 1 : 0);
                     const float amax = fmaxf(fmaxf(fmaxf(fabsf(x0), fabsf(y0)), fmaxf(fabsf(x1), fabsf(y1))), fmaxf(fabsf(x2), fabsf(y2)));
                     const float ex = (x0 == x1 && y0 == y1) ? x2 - x0 : x1 - x0, ey = (x0 == x1 && y0 == y1) ? y2 - y0 : y1 - y0;
                     line = ne == 1 && amax <= 4.0f && fmaxf(fabsf(ex), fabsf(ey)) >= 1e-6f;
                 }
-                const unsigned long long bal = __ballot(k && !line);
-                if (bal) {
-                    int base = 0;
-                    if (lane == 0) base = atomicAdd(&s_qn, __popcll(bal));
-                    base = __shfl(base, 0, 64);
-                    if (k && !line) s_queue[base + __popcll(bal & ((1ull << lane) - 1ull))] = __builtin_bit_cast(int, rb[j].z);
-                }
-                const unsigned long long bld = __ballot(line);
-                if (bld) {              // the record's slot number, from the end of the queue
-                    int base = 0;
-                    if (lane == 0) base = atomicAdd(&s_dn, __popcll(bld));
-                    base = __shfl(base, 0, 64);
-                    if (line) {
-                        const int slot = base + __popcll(bld & ((1ull << lane) - 1ull));
-                        s_queue[QCAP - 1 - slot] = w;
-                        if (slot < RTHREADS) stage_line(slot, ra[j], rb[j]);
-                    }
+                const int qs = queue_slot(k && !line, &s_qn, lane);
+                if (k && !line) s_queue[qs] = __builtin_bit_cast(int, rb[j].z);
+                const int slot = queue_slot(line, &s_dn, lane);
+                if (line) {             // the record's slot number, from the end of the queue
+                    s_queue[QCAP - 1 - slot] = w;
+                    if (slot < RTHREADS) stage_line(slot, ra[j], rb[j]);
                 }
             }
             __syncthreads();
@@ -683,18 +753,10 @@ raster_tile_kernel(const RasterParams P) {
             const bool exact_only = (b.xlo == BOX_EXACT);
             if (fn < nf && (exact_only || (b.xlo <= tx1 && b.xhi >= tx0 && b.ylo <= ty1 && b.yhi >= ty0))) {
                 const float* f = faces + (size_t)fn * 9;
-                const float x0 = f[0], y0 = f[1], x1 = f[3], y1 = f[4], x2 = f[6], y2 = f[7];
-                k = !(edge_rejects_tile(x0, y0, x1, y1, t_xlo, t_xhi, t_ylo, t_yhi) ||
-                      edge_rejects_tile(x1, y1, x2, y2, t_xlo, t_xhi, t_ylo, t_yhi) ||
-                      edge_rejects_tile(x2, y2, x0, y0, t_xlo, t_xhi, t_ylo, t_yhi));
+                k = may_touch_tile(f[0], f[1], f[3], f[4], f[6], f[7], tb);
             }
-            const unsigned long long bal = __ballot(k);
-            if (bal) {                                          // wave-uniform: most steps add nothing
-                int base = 0;
-                if (lane == 0) base = atomicAdd(&s_qn, __popcll(bal));
-                base = __shfl(base, 0, 64);
-                if (k) s_queue[base + __popcll(bal & ((1ull << lane) - 1ull))] = fn;
-            }
+            const int qs = queue_slot(k, &s_qn, lane);
+            if (k) s_queue[qs] = fn;
         }
         if ((step % FLUSH_EVERY) == FLUSH_EVERY - 1 || step == nsteps - 1) {
             __syncthreads();
@@ -709,119 +771,17 @@ raster_tile_kernel(const RasterParams P) {
     }
 
     if (!in_img) return;
-    {                   // winner of the face-parallel paths for this pixel: same rule (smallest zp, then smallest face index)
-        key = min(key, s_key[tid]);     // (walk_lines ended with a barrier; the key order IS that rule)
-        if (key != KEY_EMPTY) {
-            const float kz = __builtin_bit_cast(float, (unsigned)(key >> 32));
-            const int kf = (int)(unsigned)(key & 0xffffffffull);
-            if (kz < best_z || (kz == best_z && best >= 0 && kf < best)) {
-                // recompute this face's weights at this pixel: the same arithmetic on the same inputs, hence the same bits
-                const float* f = faces + (size_t)kf * 9;
-                const float* fi = faces_inv + (size_t)kf * 9;
-                float zp, w0, w1, w2;
-                cand_depth(make_float4(fi[0], fi[1], fi[2], fi[3]), make_float4(fi[4], fi[5], fi[6], fi[7]),
-                           make_float4(fi[8], f[2], f[5], f[8]), fxi, fyi, P.near_, P.far_, zp, w0, w1, w2);
-                best_z = zp; best = kf; bw0 = w0; bw1 = w1; bw2 = w2;
-            }
-        }
+    // winner of the face-parallel paths for this pixel (walk_lines ended with a barrier); the key order is beats()
+    key = min(key, s_key[tid]);
+    if (key != KEY_EMPTY && beats(key_depth(key), key_face(key), best_z, best)) {
+        // recompute this face's weights at this pixel: the same arithmetic on the same inputs, hence the same bits
+        best = key_face(key);
+        cand_depth(face_depth(faces + (size_t)best * 9, faces_inv + (size_t)best * 9), fxi, fyi, P.near_, P.far_, best_z, bw0, bw1, bw2);
     }
     const int yo = P.flip ? (is - 1 - yi) : yi;
     const size_t pix = ((size_t)bn * is + yo) * is + xi;
-
-    if (MODE == 0) {
-        if (best >= 0) {  // uncovered pixels keep the caller's pre-fill (cu:156-168)
-            P.depth_map[pix] = best_z;
-            P.face_index_map[pix] = best;
-            P.weight_map[3 * pix + 0] = bw0;
-            P.weight_map[3 * pix + 1] = bw1;
-            P.weight_map[3 * pix + 2] = bw2;
-            if (P.face_inv_map) {
-                const float* fi = faces_inv + (size_t)best * 9;
-#pragma unroll
-                for (int k = 0; k < 9; k++) P.face_inv_map[9 * pix + k] = fi[k];
-            }
-        }
-        return;
-    }
-
-    // ---- MODE 1: network.Rasterizer.forward attribute interpolation (network.py:176-214) ----
-    const rnr_gbuffer& G = P.gb;
-    const int fa = best >= 0 ? best : nf - 1;  // torch indexing wraps -1 to the last face (weights are 0 there)
-    const float* f = faces + (size_t)fa * 9;
-    const float depth = best_z;                 // far on background (rasterize.py:52)
-    const float wp0 = ((1.0f / f[2]) * bw0) * depth;
-    const float wp1 = ((1.0f / f[5]) * bw1) * depth;
-    const float wp2 = ((1.0f / f[8]) * bw2) * depth;
-    if (G.face_index_map) G.face_index_map[pix] = best;
-    if (G.alpha) G.alpha[pix] = best >= 0 ? 1.0f : 0.0f;
-    if (G.depth) G.depth[pix] = depth;
-    if (G.raw_weight_map) {
-        G.raw_weight_map[3 * pix + 0] = bw0; G.raw_weight_map[3 * pix + 1] = bw1; G.raw_weight_map[3 * pix + 2] = bw2;
-    }
-    if (G.weight_map) {
-        G.weight_map[3 * pix + 0] = wp0; G.weight_map[3 * pix + 1] = wp1; G.weight_map[3 * pix + 2] = wp2;
-    }
-    if (G.uv_map) {
-        const int32_t* ti = P.mesh.f_vt_idx + (size_t)fa * 3;
-        const float* a = P.mesh.vt + (size_t)ti[0] * 2;
-        const float* b = P.mesh.vt + (size_t)ti[1] * 2;
-        const float* c = P.mesh.vt + (size_t)ti[2] * 2;
-        float u = a[0] * wp0 + b[0] * wp1 + c[0] * wp2;
-        float v = a[1] * wp0 + b[1] * wp1 + c[1] * wp2;
-        u = u - floorf(u);
-        v = v - floorf(v);
-        G.uv_map[2 * pix + 0] = u;
-        G.uv_map[2 * pix + 1] = v;
-    }
-    float R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, T[3] = {0, 0, 0};
-    if (P.pose) {
-        const float* ps = P.pose + (size_t)bn * 16;
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            R[3 * r + 0] = ps[4 * r + 0]; R[3 * r + 1] = ps[4 * r + 1]; R[3 * r + 2] = ps[4 * r + 2];
-            T[r] = ps[4 * r + 3];
-        }
-    }
-    if (G.normal_map || G.normal_map_cam) {
-        const int32_t* ni = P.mesh.f_vn_idx + (size_t)fa * 3;
-        const float* a = P.mesh.vn + (size_t)ni[0] * 3;
-        const float* b = P.mesh.vn + (size_t)ni[1] * 3;
-        const float* c = P.mesh.vn + (size_t)ni[2] * 3;
-        float n0 = a[0] * wp0 + b[0] * wp1 + c[0] * wp2;
-        float n1 = a[1] * wp0 + b[1] * wp1 + c[1] * wp2;
-        float n2 = a[2] * wp0 + b[2] * wp1 + c[2] * wp2;
-        float inv = 1.0f / fmaxf(sqrtf(n0 * n0 + n1 * n1 + n2 * n2), 1e-12f);  // F.normalize
-        n0 *= inv; n1 *= inv; n2 *= inv;
-        if (G.normal_map) {
-            G.normal_map[3 * pix + 0] = n0; G.normal_map[3 * pix + 1] = n1; G.normal_map[3 * pix + 2] = n2;
-        }
-        if (G.normal_map_cam) {
-            float c0 = R[0] * n0 + R[1] * n1 + R[2] * n2;
-            float c1 = R[3] * n0 + R[4] * n1 + R[5] * n2;
-            float c2 = R[6] * n0 + R[7] * n1 + R[8] * n2;
-            float ic = 1.0f / fmaxf(sqrtf(c0 * c0 + c1 * c1 + c2 * c2), 1e-12f);
-            G.normal_map_cam[3 * pix + 0] = c0 * ic;
-            G.normal_map_cam[3 * pix + 1] = c1 * ic;
-            G.normal_map_cam[3 * pix + 2] = c2 * ic;
-        }
-    }
-    if (G.position_map || G.position_map_cam) {
-        const int32_t* vi = P.mesh.f_v_idx + (size_t)fa * 3;
-        const float* a = P.mesh.v + (size_t)vi[0] * 3;
-        const float* b = P.mesh.v + (size_t)vi[1] * 3;
-        const float* c = P.mesh.v + (size_t)vi[2] * 3;
-        const float p0 = a[0] * wp0 + b[0] * wp1 + c[0] * wp2;
-        const float p1 = a[1] * wp0 + b[1] * wp1 + c[1] * wp2;
-        const float p2 = a[2] * wp0 + b[2] * wp1 + c[2] * wp2;
-        if (G.position_map) {
-            G.position_map[3 * pix + 0] = p0; G.position_map[3 * pix + 1] = p1; G.position_map[3 * pix + 2] = p2;
-        }
-        if (G.position_map_cam) {
-            G.position_map_cam[3 * pix + 0] = R[0] * p0 + R[1] * p1 + R[2] * p2 + T[0];
-            G.position_map_cam[3 * pix + 1] = R[3] * p0 + R[4] * p1 + R[5] * p2 + T[1];
-            G.position_map_cam[3 * pix + 2] = R[6] * p0 + R[7] * p1 + R[8] * p2 + T[2];
-        }
-    }
+    if (MODE == 0) write_dropin_maps(P, faces_inv, pix, best, best_z, bw0, bw1, bw2);
+    else write_gbuffer(P, faces, bn, pix, best, best_z, bw0, bw1, bw2);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -871,20 +831,56 @@ texture_sampling_kernel(const float* __restrict__ faces, const float* __restrict
     rgb_map[3 * i + 0] = acc0; rgb_map[3 * i + 1] = acc1; rgb_map[3 * i + 2] = acc2;
 }
 
-static size_t box_bytes(int batch, int nf) { return align_up((size_t)batch * nf * sizeof(FaceBox), 256); }
-static size_t face_bytes(int batch, int nf) { return align_up((size_t)batch * nf * 9 * sizeof(float), 256); }
+// ------------------------------------------------------------------------------------------------
+// workspace
+// ------------------------------------------------------------------------------------------------
 static int num_tiles(int is) { const int t = (is + TILE - 1) / TILE; return t * t; }
-// binning scratch: [tile_count B*ntiles | wide_count B] (zeroed every call) | tile_list | wide_list
-static size_t bin_counter_bytes(int batch, int is) { return align_up((size_t)batch * (num_tiles(is) + 1) * sizeof(int), 256); }
-static size_t key_bytes(int batch, int is) { return align_up((size_t)batch * is * is * sizeof(unsigned long long), 256); }
-static size_t wide_rec_bytes(int batch, int nf) { return align_up((size_t)batch * nf * WIDE_REC_FLOATS * sizeof(float), 256); }
-// ... | keys | wide records (behind everything earlier rounds laid out: gbuffer_clear_regions' offsets are unchanged)
-static size_t bin_bytes(int batch, int nf, int is) {
-    return bin_counter_bytes(batch, is) + align_up((size_t)batch * num_tiles(is) * BIN_CAP * sizeof(int), 256) +
-           align_up((size_t)batch * nf * sizeof(int), 256) + key_bytes(batch, is) + wide_rec_bytes(batch, nf);
-}
 
-// Small trusted faces are resolved face-parallel into P.keys (near >= 0), everything else is binned into the tile lists;
+// The layout of a rasterizer workspace, stated once:
+//   boxes | faces | faces_inv (the fused entry point only: the drop-in one has the caller's arrays) |
+//   tile_count, wide_count | tile_list | keys | wide_rec
+// Every region is 256-byte aligned and padded, so the two that are cleared before every call — the counters to 0, the keys
+// to ~0 — are whole uint4 vectors.  ws == NULL: sizes only.
+struct RasterWorkspace {
+    FaceBox* boxes;             // [B,nf]
+    float* faces;               // [B,nf,9]
+    float* faces_inv;           // [B,nf,9]
+    int* tile_count;            // [B,ntiles], followed by
+    int* wide_count;            // [B]
+    int* tile_list;             // [B,ntiles,BIN_CAP]
+    unsigned long long* keys;   // [B,is,is]
+    float* wide_rec;            // [B,nf,WIDE_REC_FLOATS]
+    long counter_vec, key_vec;  // uint4 vectors from tile_count / keys to the end of their region
+
+    RasterWorkspace(void* ws, int batch, int nf, int is, bool with_face_arrays) {
+        const size_t faces_n = with_face_arrays ? (size_t)batch * nf * 9 : 0;
+        boxes = take<FaceBox>(ws, (size_t)batch * nf);
+        faces = take<float>(ws, faces_n);
+        faces_inv = take<float>(ws, faces_n);
+        tile_count = take<int>(ws, (size_t)batch * (num_tiles(is) + 1));
+        wide_count = tile_count + (size_t)batch * num_tiles(is);
+        counter_vec = vectors_to_end(tile_count, ws);
+        tile_list = take<int>(ws, (size_t)batch * num_tiles(is) * BIN_CAP);
+        keys = take<unsigned long long>(ws, (size_t)batch * is * is);
+        key_vec = vectors_to_end(keys, ws);
+        wide_rec = take<float>(ws, (size_t)batch * nf * WIDE_REC_FLOATS);
+    }
+    size_t bytes() const { return end; }
+    uint4* counter_region() const { return reinterpret_cast<uint4*>(tile_count); }
+    uint4* key_region() const { return reinterpret_cast<uint4*>(keys); }
+
+private:
+    size_t end = 0;
+    template <typename T> T* take(void* ws, size_t n) {
+        T* p = reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(ws) + end);
+        end += align_up(n * sizeof(T), 256);
+        return p;
+    }
+    template <typename T> long vectors_to_end(const T* region, void* ws) const {
+        return (long)((reinterpret_cast<uintptr_t>(ws) + end - reinterpret_cast<uintptr_t>(region)) / sizeof(uint4));
+    }
+};
+
 // Clears the bin counters (zeros) and the per-pixel depth keys (all ones) in one launch.  Not hipMemsetAsync: memset
 // nodes of a captured HIP graph went stale on replay once any other copy / fill had run in between (GPU write fault,
 // scripts/exp_graph2.py raster), kernels replay correctly.
@@ -895,68 +891,48 @@ raster_clear_kernel(uint4* __restrict__ counters, long counter_vec, uint4* __res
     else if (i - counter_vec < key_vec) keys[i - counter_vec] = make_uint4(~0u, ~0u, ~0u, ~0u);
 }
 
-// fills P.tile_count / P.tile_list / P.keys.
-// setup != NULL: the per-face setup has not run yet; on the splat path it shares the splat's launch, otherwise it is launched first
-static int run_binning(char* ws, const float* faces, const float* faces_inv, const FaceBox* boxes, int batch, int nf, int is,
-                       RasterParams* P, hipStream_t st, bool precleared = false, const FaceSetupArgs* setup = nullptr) {
-    const int ntiles = num_tiles(is);
-    int* tile_count = reinterpret_cast<int*>(ws);
-    int* wide_count = tile_count + (size_t)batch * ntiles;
-    int* tile_list = reinterpret_cast<int*>(ws + bin_counter_bytes(batch, is));
-    int* wide_list = reinterpret_cast<int*>(ws + bin_counter_bytes(batch, is) +
-                                            align_up((size_t)batch * ntiles * BIN_CAP * sizeof(int), 256));
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(
-        ws + bin_counter_bytes(batch, is) + align_up((size_t)batch * ntiles * BIN_CAP * sizeof(int), 256) +
-        align_up((size_t)batch * nf * sizeof(int), 256));
-    float* wide_rec = reinterpret_cast<float*>(reinterpret_cast<char*>(keys) + key_bytes(batch, is));
+// Everything in front of the tile kernel: runs the per-face setup S and fills W's lists and keys (P's pointers to them).
+// near >= 0: small trusted faces are resolved face-parallel into the keys by the setup's own launch, the others binned by it;
+// near < 0: the setup, then bin_faces_kernel for every face.  precleared: the caller has cleared W's two regions already.
+static int run_binning(const RasterWorkspace& W, const FaceSetupArgs& S, int batch, int nf, int is, RasterParams* P,
+                       hipStream_t st, bool precleared) {
     const long total = (long)batch * nf;
-    const bool splat = P->near_ >= 0.0f;            // the key order needs zp > 0, which the near test then guarantees
-    if (!precleared) {   // both regions are 256-byte aligned and padded (bin_counter_bytes / key_bytes): whole uint4 stores
-        const long cvec = (long)(bin_counter_bytes(batch, is) / sizeof(uint4));
-        const long kvec = splat ? (long)(key_bytes(batch, is) / sizeof(uint4)) : 0;
-        hipLaunchKernelGGL(raster_clear_kernel, dim3((unsigned)((cvec + kvec + 255) / 256)), dim3(256), 0, st,
-                           reinterpret_cast<uint4*>(tile_count), cvec, reinterpret_cast<uint4*>(keys), kvec);
+    const bool gather = S.v_uvz != nullptr;
+    const bool splat = P->near_ >= 0.0f;            // the key order needs zp > 0, which the near test then guarantees (has_key)
+    if (!precleared) {
+        const long kvec = splat ? W.key_vec : 0;
+        hipLaunchKernelGGL(raster_clear_kernel, dim3((unsigned)((W.counter_vec + kvec + 255) / 256)), dim3(256), 0, st,
+                           W.counter_region(), W.counter_vec, W.key_region(), kvec);
         if (int e = check_launch("raster_clear_kernel")) return e;
     }
     const dim3 fgrid((unsigned)((total + 255) / 256));
-    float* faces_inv_w = const_cast<float*>(faces_inv);
-    FaceBox* boxes_w = const_cast<FaceBox*>(boxes);
-    if (setup && !splat) {
-        if (setup->gather) hipLaunchKernelGGL(face_setup_kernel<true>, fgrid, dim3(256), 0, st, setup->faces_in, setup->v_uvz, setup->fidx,
-                                              setup->faces_out, faces_inv_w, boxes_w, batch, nf, setup->nv, is);
-        else hipLaunchKernelGGL(face_setup_kernel<false>, fgrid, dim3(256), 0, st, setup->faces_in, setup->v_uvz, setup->fidx,
-                                setup->faces_out, faces_inv_w, boxes_w, batch, nf, setup->nv, is);
+    if (!splat) {
+        auto setup = [&](auto kernel) { hipLaunchKernelGGL(kernel, fgrid, dim3(256), 0, st, S.faces_in, S.v_uvz, S.fidx, S.faces_out, S.faces_inv, S.boxes, batch, nf, S.nv, is);
+        };
+        if (gather) setup(face_setup_kernel<true>); else setup(face_setup_kernel<false>);
         if (int e = check_launch("face_setup_kernel")) return e;
-    }
-    if (splat && setup) {
+        hipLaunchKernelGGL(bin_faces_kernel, fgrid, dim3(256), 0, st, P->faces, W.boxes, W.tile_count, W.tile_list, W.wide_count, W.wide_rec,
+                           batch, nf, is);
+        if (int e = check_launch("bin_faces_kernel")) return e;
+    } else {
         // lanes per face: four while the launch would otherwise leave most SIMDs with one wave or none (RNR_SPLAT_LPF overrides)
         static const int forced = [] { const char* e = getenv("RNR_SPLAT_LPF"); return e ? atoi(e) : 0; }();
         const int lpf = forced == 1 || forced == 4 ? forced : (total <= 2 * 65536 ? 4 : 1);
         const dim3 sgrid((unsigned)((total * lpf + 255) / 256));
-#define RNR_LAUNCH_SETUP_SPLAT(G, L)                                                                                            \
-        hipLaunchKernelGGL((setup_splat_faces_kernel<G, L>), sgrid, dim3(256), 0, st, setup->faces_in, setup->v_uvz, setup->fidx, \
-                           setup->faces_out, faces_inv_w, boxes_w, keys, tile_count, tile_list, wide_count, wide_list, wide_rec,  \
-                           batch, nf, setup->nv, is, P->near_, P->far_)
-        if (setup->gather) { if (lpf == 4) RNR_LAUNCH_SETUP_SPLAT(true, 4); else RNR_LAUNCH_SETUP_SPLAT(true, 1); }
-        else { if (lpf == 4) RNR_LAUNCH_SETUP_SPLAT(false, 4); else RNR_LAUNCH_SETUP_SPLAT(false, 1); }
-#undef RNR_LAUNCH_SETUP_SPLAT
+        auto setup_splat = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, sgrid, dim3(256), 0, st, S.faces_in, S.v_uvz, S.fidx, S.faces_out, S.faces_inv, S.boxes, W.keys,
+                               W.tile_count, W.tile_list, W.wide_count, W.wide_rec, batch, nf, S.nv, is, P->near_, P->far_);
+        };
+        if (gather) { if (lpf == 4) setup_splat(setup_splat_faces_kernel<true, 4>); else setup_splat(setup_splat_faces_kernel<true, 1>); }
+        else { if (lpf == 4) setup_splat(setup_splat_faces_kernel<false, 4>); else setup_splat(setup_splat_faces_kernel<false, 1>); }
         if (int e = check_launch("setup_splat_faces_kernel")) return e;
-        P->keys = keys;
-    } else if (splat) {
-        hipLaunchKernelGGL(splat_faces_kernel, fgrid, dim3(256), 0, st, faces, faces_inv, boxes,
-                           keys, tile_count, tile_list, wide_count, wide_list, wide_rec, batch, nf, is, P->near_, P->far_);
-        if (int e = check_launch("splat_faces_kernel")) return e;
-        P->keys = keys;
-    } else {
-        hipLaunchKernelGGL(bin_faces_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, faces, boxes, tile_count,
-                           tile_list, wide_count, wide_list, wide_rec, batch, nf, is);
-        if (int e = check_launch("bin_faces_kernel")) return e;
+        P->keys = W.keys;
     }
-    P->wide_count = wide_count;      // tested by the tile kernel (bin_wide_kernel's work, without its launch)
-    P->wide_list = wide_list;
-    P->wide_rec = wide_rec;
-    P->tile_count = tile_count;
-    P->tile_list = tile_list;
+    P->boxes = W.boxes;
+    P->wide_count = W.wide_count;    // tested by the tile kernel (bin_wide_kernel's work, without its launch)
+    P->wide_rec = W.wide_rec;
+    P->tile_count = W.tile_count;
+    P->tile_list = W.tile_list;
     return 0;
 }
 
@@ -965,7 +941,7 @@ static int run_binning(char* ws, const float* faces, const float* faces_inv, con
 using namespace rnr;
 
 extern "C" size_t rnr_raster_workspace_bytes(int batch_size, int num_faces, int image_size) {
-    return box_bytes(batch_size, num_faces) + bin_bytes(batch_size, num_faces, image_size);
+    return RasterWorkspace(nullptr, batch_size, num_faces, image_size, false).bytes();
 }
 
 extern "C" int rnr_forward_face_index_map(const float* faces, int32_t* face_index_map, float* weight_map,
@@ -980,15 +956,14 @@ extern "C" int rnr_forward_face_index_map(const float* faces, int32_t* face_inde
                 "rnr_forward_face_index_map: bad sizes B=%d nf=%d is=%d", batch_size, num_faces, image_size);
     RNR_REQUIRE(!return_depth || face_inv_map, "rnr_forward_face_index_map: return_depth needs face_inv_map");
     hipStream_t st = as_stream(stream);
-    FaceBox* boxes = reinterpret_cast<FaceBox*>(workspace);
-    const FaceSetupArgs setup = {faces, nullptr, nullptr, nullptr, 0, 0};
+    const RasterWorkspace W(workspace, batch_size, num_faces, image_size, false);
+    const FaceSetupArgs setup = {faces, nullptr, nullptr, 0, nullptr, faces_inv, W.boxes};
     RasterParams P = {};
-    P.faces = faces; P.faces_inv = faces_inv; P.boxes = boxes; P.nf = num_faces; P.is = image_size;
+    P.faces = faces; P.faces_inv = faces_inv; P.nf = num_faces; P.is = image_size;
     P.near_ = near_; P.far_ = far_; P.flip = 0;
     P.face_index_map = face_index_map; P.weight_map = weight_map; P.depth_map = depth_map;
     P.face_inv_map = return_depth ? face_inv_map : nullptr;
-    if (int e = run_binning(reinterpret_cast<char*>(workspace) + box_bytes(batch_size, num_faces), faces, faces_inv, boxes,
-                            batch_size, num_faces, image_size, &P, st, false, &setup)) return e;
+    if (int e = run_binning(W, setup, batch_size, num_faces, image_size, &P, st, false)) return e;
     const int tiles = (image_size + TILE - 1) / TILE;
     hipLaunchKernelGGL(raster_tile_kernel<0>, dim3(tiles * tiles, batch_size), dim3(RTHREADS), 0, st, P);
     return check_launch("raster_tile_kernel<0>");
@@ -1013,35 +988,18 @@ extern "C" int rnr_forward_texture_sampling(const float* faces, const float* tex
 }
 
 extern "C" size_t rnr_gbuffer_workspace_bytes(int num_views, int num_faces, int image_size) {
-    return box_bytes(num_views, num_faces) + 2 * face_bytes(num_views, num_faces) + bin_bytes(num_views, num_faces, image_size);
+    return RasterWorkspace(nullptr, num_views, num_faces, image_size, true).bytes();
 }
 
 // the two regions of an rnr_rasterize_gbuffer workspace that must be cleared before every call (tile / wide-list counters to
 // 0, depth keys to ~0), as whole uint4 vectors: for rnr_frame_prepare (shade.hip), which clears them in its own launch
 void rnr::gbuffer_clear_regions(void* workspace, int num_views, int num_faces, int image_size, uint4** counters, long* counter_vec,
                                 uint4** keys, long* key_vec) {
-    char* ws = reinterpret_cast<char*>(workspace) + box_bytes(num_views, num_faces) + 2 * face_bytes(num_views, num_faces);
-    *counters = reinterpret_cast<uint4*>(ws);
-    *counter_vec = (long)(bin_counter_bytes(num_views, image_size) / sizeof(uint4));
-    *keys = reinterpret_cast<uint4*>(ws + bin_counter_bytes(num_views, image_size) +
-                                     align_up((size_t)num_views * num_tiles(image_size) * BIN_CAP * sizeof(int), 256) +
-                                     align_up((size_t)num_views * num_faces * sizeof(int), 256));
-    *key_vec = (long)(key_bytes(num_views, image_size) / sizeof(uint4));
-}
-
-static int rasterize_gbuffer_impl(const rnr_mesh* mesh, const float* v_uvz, const float* pose, int num_views, int image_size,
-                                  float near_, float far_, const rnr_gbuffer* out, void* workspace, void* stream, bool precleared);
-
-extern "C" int rnr_rasterize_gbuffer(const rnr_mesh* mesh, const float* v_uvz, const float* pose,
-                                     int num_views, int image_size, float near_, float far_,
-                                     const rnr_gbuffer* out, void* workspace, void* stream) {
-    return rasterize_gbuffer_impl(mesh, v_uvz, pose, num_views, image_size, near_, far_, out, workspace, stream, false);
-}
-
-extern "C" int rnr_rasterize_gbuffer_prepared(const rnr_mesh* mesh, const float* v_uvz, const float* pose,
-                                              int num_views, int image_size, float near_, float far_,
-                                              const rnr_gbuffer* out, void* workspace, void* stream) {
-    return rasterize_gbuffer_impl(mesh, v_uvz, pose, num_views, image_size, near_, far_, out, workspace, stream, true);
+    const RasterWorkspace W(workspace, num_views, num_faces, image_size, true);
+    *counters = W.counter_region();
+    *counter_vec = W.counter_vec;
+    *keys = W.key_region();
+    *key_vec = W.key_vec;
 }
 
 static int rasterize_gbuffer_impl(const rnr_mesh* mesh, const float* v_uvz, const float* pose, int num_views, int image_size,
@@ -1057,18 +1015,26 @@ static int rasterize_gbuffer_impl(const rnr_mesh* mesh, const float* v_uvz, cons
     RNR_REQUIRE(num_views > 0 && image_size > 0 && image_size <= 16384, "rnr_rasterize_gbuffer: bad sizes");
     hipStream_t st = as_stream(stream);
     const int nf = mesh->num_faces;
-    char* ws = reinterpret_cast<char*>(workspace);
-    FaceBox* boxes = reinterpret_cast<FaceBox*>(ws);
-    float* faces = reinterpret_cast<float*>(ws + box_bytes(num_views, nf));
-    float* faces_inv = reinterpret_cast<float*>(ws + box_bytes(num_views, nf) + face_bytes(num_views, nf));
-    const FaceSetupArgs setup = {nullptr, v_uvz, mesh->f_v_idx, faces, mesh->num_vertices, 1};
+    const RasterWorkspace W(workspace, num_views, nf, image_size, true);
+    const FaceSetupArgs setup = {nullptr, v_uvz, mesh->f_v_idx, mesh->num_vertices, W.faces, W.faces_inv, W.boxes};
     RasterParams P = {};
-    P.faces = faces; P.faces_inv = faces_inv; P.boxes = boxes; P.nf = nf; P.is = image_size;
+    P.faces = W.faces; P.faces_inv = W.faces_inv; P.nf = nf; P.is = image_size;
     P.near_ = near_; P.far_ = far_; P.flip = 1;
     P.mesh = *mesh; P.gb = *out; P.pose = pose;
-    if (int e = run_binning(ws + box_bytes(num_views, nf) + 2 * face_bytes(num_views, nf), faces, faces_inv, boxes, num_views,
-                            nf, image_size, &P, st, precleared, &setup)) return e;
+    if (int e = run_binning(W, setup, num_views, nf, image_size, &P, st, precleared)) return e;
     const int tiles = (image_size + TILE - 1) / TILE;
     hipLaunchKernelGGL(raster_tile_kernel<1>, dim3(tiles * tiles, num_views), dim3(RTHREADS), 0, st, P);
     return check_launch("raster_tile_kernel<1>");
+}
+
+extern "C" int rnr_rasterize_gbuffer(const rnr_mesh* mesh, const float* v_uvz, const float* pose,
+                                     int num_views, int image_size, float near_, float far_,
+                                     const rnr_gbuffer* out, void* workspace, void* stream) {
+    return rasterize_gbuffer_impl(mesh, v_uvz, pose, num_views, image_size, near_, far_, out, workspace, stream, false);
+}
+
+extern "C" int rnr_rasterize_gbuffer_prepared(const rnr_mesh* mesh, const float* v_uvz, const float* pose,
+                                              int num_views, int image_size, float near_, float far_,
+                                              const rnr_gbuffer* out, void* workspace, void* stream) {
+    return rasterize_gbuffer_impl(mesh, v_uvz, pose, num_views, image_size, near_, far_, out, workspace, stream, true);
 }
