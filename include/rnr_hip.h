@@ -412,7 +412,11 @@ int rnr_conv2d_fused(const rnr_conv_desc* d, const rnr_conv_src* src0, const rnr
  *                    rnr_conv2d_masked + rnr_ray_render there.  tile_mask as in rnr_conv2d_masked (skipped tiles get 0), laid
  *                    out for the DIRECT plan's 32 x 8-pixel tiles: RNR_CONV_WINOGRAD in d->flags is ignored by this entry
  *                    point, so build the mask with rnr_conv_active_tiles / rnr_conv_tile_count from the descriptor with
- *                    that flag cleared (with it set those describe the Winograd out layer's 16 x 4-pixel tiles).
+ *                    that flag cleared (with it set those describe the Winograd out layer's 16 x 4-pixel tiles).  A map whose
+ *                    direct grid would split K (fewer than 257 tiles) runs unsplit here but takes no mask: rnr_conv_tile_count is 0.
+ *                    bias [c_out_pad] — NOT [3 * rays] as for rnr_ray_render: the kernel loads the bias of all 80 columns of its
+ *                    tile; entries >= c_out reach no output, whatever they hold.
+ *                    ray_w [N, H, W, c_out_pad] as written by rnr_ray_weights; a pixel whose weights are all 0 gives exactly 0.
  * Differs from rnr_ray_render in summation order only (<= 1e-6 on frames in [0, 2]).
  */
 int rnr_ray_weights(const float* net_in, int c_pad, const float* alpha, const float* lp, int lp_h, int lp_w, int num_spec,

@@ -1,0 +1,90 @@
+"""ORACLE (test infrastructure, not product): float64 restatements of the convolution entry points of include/rnr_hip.h that
+take a tile mask or carry the ray-renderer epilogue, written from the header's contract and not from the kernels, plus a
+generator of inputs whose convolution is EXACT in float32.
+
+  conv64           out_raw of rnr_conv2d*: sum over taps and input channels of act(scale * raw + shift) * weight, the three
+                   kinds (3x3 reflect, 4x4 stride 2 reflect, transposed 4x4 stride 2), two sources = channel concat
+  tile_mask64      rnr_conv_active_tiles: one byte per th x tw pixel tile, 1 iff any alpha > 0 inside it
+  ray_epilogue64   rnr_conv2d_ray: image[n,c,y,x] = sum_r (tanh(conv[n,y,x,3r+c] + bias[3r+c]) + 1) * ray_w[n,y,x,3r+c]
+  exact_conv_case  small dyadic inputs: every product is a multiple of 2^-4 and every partial sum stays far below 2^24 of
+                   those, so ANY summation order, the F(2x2, 3x3) transforms (the data transform only adds, the weight transform
+                   divides by 2 and 4) and the bf16x6 / f16x3 operand splits (small dyadic operands sit entirely in the leading
+                   term; the f16x3 weight prescale is a power of two) give the same float32 bits: a kernel is compared with
+                   conv64(...).float() BITWISE, which no tolerance-based test can do
+tests/test_conv_mask_cpu.py pins conv64 to a four-loop numpy convolution, tile_mask64 to a hand-written example and the
+exactness property to torch's float32 convolution.
+"""
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+D = torch.float64
+ACT_NONE, ACT_LRELU02, ACT_RELU = 0, 1, 2           # RNR_ACT_* of include/rnr_hip.h
+
+
+def _act(x, a):
+    return F.leaky_relu(x, 0.2) if a == ACT_LRELU02 else (F.relu(x) if a == ACT_RELU else x)
+
+
+def conv_input(srcs):
+    """srcs: list of (raw [N,C,H,W], scale [N,C] or None, shift [N,C] or None, act) -> the convolution's input
+    cat_j act_j(scale_j * raw_j + shift_j) [N, sum C, H, W] in the dtype of raw (float32: one rounding per operation, as the
+    kernels' prologue; exact for exact_conv_case)."""
+    xs = []
+    for raw, sc, sh, act in srcs:
+        x = raw
+        if sc is not None:
+            x = x * sc[:, :, None, None]
+        if sh is not None:
+            x = x + sh[:, :, None, None]
+        xs.append(_act(x, act))
+    return torch.cat(xs, 1)
+
+
+def conv64(kind, srcs, weight):
+    """float64 out_raw [N, c_out, Ho, Wo] of rnr_conv2d for kind 0 (3x3, ReflectionPad2d(1)), 1 (4x4 stride 2,
+    ReflectionPad2d(1)) or 2 (ConvTranspose2d 4x4 stride 2 padding 1); weight in torch's layout ([c_out, c_in, k, k], transposed:
+    [c_in, c_out, 4, 4])."""
+    x = conv_input(srcs).to(D)
+    w = weight.to(D)
+    if kind == 0:
+        return F.conv2d(F.pad(x, (1, 1, 1, 1), mode='reflect'), w)
+    if kind == 1:
+        return F.conv2d(F.pad(x, (1, 1, 1, 1), mode='reflect'), w, stride=2)
+    return F.conv_transpose2d(x, w, stride=2, padding=1)
+
+
+def tile_mask64(alpha, th, tw):
+    """alpha [N,H,W] -> uint8 [N * (H/th) * (W/tw)], entry (n, ty, tx) in that order = any(alpha > 0) over the tile's pixels."""
+    a = torch.as_tensor(alpha)
+    N, H, W = a.shape
+    assert H % th == 0 and W % tw == 0
+    live = (a > 0).reshape(N, H // th, th, W // tw, tw).any(dim=4).any(dim=2)
+    return live.reshape(-1).to(torch.uint8)
+
+
+def ray_epilogue64(conv, bias, ray_w, c_out):
+    """conv [N,H,W,>=c_out] (channel-last, as out_raw), bias [>=c_out], ray_w [N,H,W,>=c_out] -> image [N,3,H,W] float64:
+    sum over the c_out // 3 rays of (tanh(conv + bias) + 1) * ray_w, colour channel c in columns 3 r + c."""
+    R = c_out // 3
+    y = conv[..., :3 * R].to(D) + torch.as_tensor(bias)[:3 * R].to(D)
+    t = (torch.tanh(y) + 1.0) * ray_w[..., :3 * R].to(D)
+    return t.reshape(*t.shape[:3], R, 3).sum(dim=3).permute(0, 3, 1, 2).contiguous()
+
+
+def exact_conv_case(rng, kind, N, H, W, cins, c_out):
+    """Inputs of a convolution that is exact in float32 in any summation order (rng: numpy Generator):
+    raw integers in [-3, 3], scale in {0.5, 1, 2} and shift a multiple of 0.5 in [-1.5, 1.5] per view and channel, act NONE or
+    RELU (never LReLU: 0.2 is not dyadic), weights integers in [-2, 2] times 2^-3.  Inputs are multiples of 0.5 with
+    |x| <= 7.5, products multiples of 2^-4, |sum| <= taps * c_in * 7.5 * 0.25 — below 2^24 * 2^-4 for c_in <= 512.
+    Returns (srcs, weight) as float32 torch tensors in run_conv's form."""
+    srcs = []
+    for C in cins:
+        raw = torch.from_numpy(rng.integers(-3, 4, size=(N, C, H, W)).astype(np.float32))
+        sc = torch.from_numpy(rng.choice(np.array([0.5, 1.0, 2.0], np.float32), size=(N, C)))
+        sh = torch.from_numpy((rng.integers(-3, 4, size=(N, C)) * 0.5).astype(np.float32))
+        srcs.append((raw, sc, sh, int(rng.choice([ACT_NONE, ACT_RELU]))))
+    cin = sum(cins)
+    shape = (cin, c_out, 4, 4) if kind == 2 else (c_out, cin, 3 if kind == 0 else 4, 3 if kind == 0 else 4)
+    weight = torch.from_numpy((rng.integers(-2, 3, size=shape) * 0.125).astype(np.float32))
+    return srcs, weight

@@ -29,7 +29,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_unet import run_conv, run_conv_fused
+from rnr_amd.testing import run_conv, run_conv_fused
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'

@@ -6,7 +6,9 @@ import ctypes
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
+
+from oracle.conv64 import conv64 as ref_conv
+from rnr_amd.testing import run_conv, run_conv_fused
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -14,96 +16,6 @@ DEV = 'cuda:0'
 
 def T(x):
     return torch.from_numpy(np.ascontiguousarray(x))
-
-
-def _act(x, a):
-    return F.leaky_relu(x, 0.2) if a == 1 else (F.relu(x) if a == 2 else x)
-
-
-def run_conv(kind, srcs, weight, c_out, N, H, W, flags=0):
-    """srcs: list of (raw NCHW cpu tensor, scale [N,C] or None, shift [N,C] or None, act)."""
-    from rnr_amd import _lib
-    from rnr_amd.ops import _ptr, _stream
-    L = _lib.load()
-    pad16 = lambda c: (c + 15) // 16 * 16
-    keep, csrc, cs = [], [], []
-    for raw, sc, sh, act in srcs:
-        C = raw.shape[1]
-        cp = pad16(C)
-        d = torch.zeros(N, H, W, cp)
-        d[..., :C] = raw.permute(0, 2, 3, 1)
-        d = d.to(DEV)
-        scd = shd = None
-        if sc is not None:
-            scd = torch.zeros(N, cp); scd[:, :C] = sc; scd = scd.to(DEV)
-        if sh is not None:
-            shd = torch.zeros(N, cp); shd[:, :C] = sh; shd = shd.to(DEV)
-        keep += [d, scd, shd]
-        csrc.append(_lib.RnrConvSrc(d.data_ptr(), scd.data_ptr() if scd is not None else None,
-                                    shd.data_ptr() if shd is not None else None, cp, act))
-        cs.append((C, cp))
-    desc = _lib.RnrConvDesc(kind, cs[0][0], cs[0][1], cs[1][0] if len(cs) > 1 else 0, cs[1][1] if len(cs) > 1 else 0,
-                            c_out, pad16(c_out), flags)
-    packed = torch.empty(L.rnr_packed_weight_floats(ctypes.byref(desc)), device=DEV)
-    wd = weight.contiguous().to(DEV)
-    _lib.check(L.rnr_pack_conv_weight(ctypes.byref(desc), _ptr(wd), _ptr(packed), _stream()))
-    oh, ow = (H, W) if kind == 0 else ((H // 2, W // 2) if kind == 1 else (2 * H, 2 * W))
-    out = torch.full((N, oh, ow, desc.c_out_pad), float('nan'), device=DEV)
-    stats = torch.zeros(N, desc.c_out_pad, 2, dtype=torch.float64, device=DEV)
-    wsb = L.rnr_conv_workspace_bytes(ctypes.byref(desc), N, H, W)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
-    _lib.check(L.rnr_conv2d(ctypes.byref(desc), ctypes.byref(csrc[0]), ctypes.byref(csrc[1]) if len(csrc) > 1 else None,
-                            _ptr(packed), _ptr(out), _ptr(stats), N, H, W, _ptr(ws), wsb, _stream()))
-    torch.cuda.synchronize()
-    return out.cpu(), stats.cpu()
-
-
-def run_conv_fused(kind, srcs, weight, c_out, N, H, W, gamma=None, beta=None, flags=0, repeats=1):
-    """The product entry point rnr_conv2d_fused (convolution + BatchNorm finalise: in the launch, or a launch of its own behind split-K).
-    Returns (out_raw, scale, shift, sync buffer) as CPU tensors; `repeats` > 1 re-runs the call on the same sync buffer."""
-    from rnr_amd import _lib
-    from rnr_amd.ops import _ptr, _stream
-    L = _lib.load()
-    pad16 = lambda c: (c + 15) // 16 * 16
-    keep, csrc, cs = [], [], []
-    for raw, sc, sh, act in srcs:
-        C = raw.shape[1]
-        cp = pad16(C)
-        d = torch.zeros(N, H, W, cp)
-        d[..., :C] = raw.permute(0, 2, 3, 1)
-        d = d.to(DEV)
-        scd = shd = None
-        if sc is not None:
-            scd = torch.zeros(N, cp); scd[:, :C] = sc; scd = scd.to(DEV)
-        if sh is not None:
-            shd = torch.zeros(N, cp); shd[:, :C] = sh; shd = shd.to(DEV)
-        keep += [d, scd, shd]
-        csrc.append(_lib.RnrConvSrc(d.data_ptr(), scd.data_ptr() if scd is not None else None,
-                                    shd.data_ptr() if shd is not None else None, cp, act))
-        cs.append((C, cp))
-    desc = _lib.RnrConvDesc(kind, cs[0][0], cs[0][1], cs[1][0] if len(cs) > 1 else 0, cs[1][1] if len(cs) > 1 else 0,
-                            c_out, pad16(c_out), flags)
-    packed = torch.empty(L.rnr_packed_weight_floats(ctypes.byref(desc)), device=DEV)
-    wd = weight.contiguous().to(DEV)
-    _lib.check(L.rnr_pack_conv_weight(ctypes.byref(desc), _ptr(wd), _ptr(packed), _stream()))
-    oh, ow = (H, W) if kind == 0 else ((H // 2, W // 2) if kind == 1 else (2 * H, 2 * W))
-    out = torch.full((N, oh, ow, desc.c_out_pad), float('nan'), device=DEV)
-    wsb = L.rnr_conv_workspace_bytes(ctypes.byref(desc), N, H, W)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
-    sync = torch.zeros(L.rnr_conv_sync_bytes(ctypes.byref(desc), N, H, W), dtype=torch.uint8, device=DEV)
-    scale = torch.full((N, desc.c_out_pad), float('nan'), device=DEV)
-    shift = torch.full((N, desc.c_out_pad), float('nan'), device=DEV)
-    cbn = None
-    if gamma is not None:
-        g, b = gamma.to(DEV), beta.to(DEV)
-        keep += [g, b]
-        cbn = _lib.RnrConvBn(g.data_ptr(), b.data_ptr(), scale.data_ptr(), shift.data_ptr(), 1e-5)
-    for _ in range(repeats):
-        _lib.check(L.rnr_conv2d_fused(ctypes.byref(desc), ctypes.byref(csrc[0]), ctypes.byref(csrc[1]) if len(csrc) > 1 else None,
-                                      _ptr(packed), _ptr(out), ctypes.byref(cbn) if cbn else None, N, H, W, _ptr(ws), wsb,
-                                      _ptr(sync), sync.numel(), None, _stream()))
-    torch.cuda.synchronize()
-    return out.cpu(), scale.cpu(), shift.cpu(), sync.cpu()
 
 
 FUSED_CASES = [
@@ -162,24 +74,6 @@ def test_conv_fused_equals_separate_launches(kind, N, H, cins, c_out):
     out_n, sc_n, _, sync_n = run_conv_fused(kind, srcs, w, c_out, N, H, H)
     assert torch.equal(out_l.view(torch.int32), out_n.view(torch.int32)) and bool(torch.isnan(sc_n).all())
     assert int(sync_n.abs().max()) == 0
-
-
-def ref_conv(kind, srcs, weight):
-    xs = []
-    for raw, sc, sh, act in srcs:
-        x = raw
-        if sc is not None:
-            x = x * sc[:, :, None, None]
-        if sh is not None:
-            x = x + sh[:, :, None, None]
-        xs.append(_act(x, act))
-    x = torch.cat(xs, 1).double()
-    w = weight.double()
-    if kind == 0:
-        return F.conv2d(F.pad(x, (1, 1, 1, 1), mode='reflect'), w)
-    if kind == 1:
-        return F.conv2d(F.pad(x, (1, 1, 1, 1), mode='reflect'), w, stride=2)
-    return F.conv_transpose2d(x, w, stride=2, padding=1)
 
 
 CASES = [
