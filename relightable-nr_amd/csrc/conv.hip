@@ -21,6 +21,7 @@
 // product path since r03, RNR_CONV_WINOGRAD — the fp32 Winograd kernels of conv_wino.inc (F(2x2, 3x3): conv_wino_kernel),
 // conv_wino80.inc (the 80-column out layer), conv_wino2.inc / conv_wino2p.inc (F(2x2, 2x2): conv_wino2_kernel<1> for the
 // stride-2 convolution, conv_wino2p_kernel<2> for the transposed one) and conv_wino4.inc (F(4x4, 3x3), RNR_CONV_WINOGRAD4).
+// Device side, shared: conv_stage.inc states tile decode, halo source / slot / prologue and the output-store preamble once for all of them.
 // Host side: CONV_TILES lists every instantiation of these kernels with its tile shape and launcher; plan_conv() tries the
 // candidates (try_wino80 ... try_gather) in priority order and returns the row, the grid and the split-K depth of one call.
 // Split-K grids write one partial-output slab per slice; splitk_reduce_kernel adds them in slice order.
@@ -179,6 +180,7 @@ __device__ __forceinline__ float apply_act(float v, int act) {
     return fmaxf(v, act_slope(act) * v);
 }
 
+#include "conv_stage.inc"
 
 // ------------------------------------------------------------------------------------------------
 // Producer-side BatchNorm (rnr_conv2d_fused).
@@ -292,7 +294,7 @@ __device__ __forceinline__ void bn_finalize_views(const ConvParams& P, int n_fir
                                                   int i_stride = 0) {
     const int total = n_views * P.c_out_pad;
     const int stride = i_stride ? i_stride : (int)blockDim.x;
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(P.stats, 0, 0x7fffffff, 0x27000);
+    const __amdgpu_buffer_rsrc_t rsrc = buffer_rsrc(P.stats);
     const uintx4_t zero4 = {0u, 0u, 0u, 0u};
     typedef double doublex2 __attribute__((ext_vector_type(2)));
     for (int i = i_first + tid; i < total; i += stride) {
@@ -383,12 +385,9 @@ conv_mfma_kernel(const ConvParams P) {
     const int l31 = lane & 31, h = lane >> 5;
     const int wave_m = wave / WAVES_N, wave_n = wave % WAVES_N;
     const int wm0 = wave_m * WM * 32, wn0 = wave_n * WN * 32;
-    int mt_, nt_, z_;
-    tile_coords(P, mt_, nt_, z_);
-    const int m0 = mt_ * BM, n0 = nt_ * BN;
-    const int par = (KIND == 2) ? (z_ & 3) : 0;
-    const int split = (KIND == 2) ? (z_ >> 2) : z_;
-    const int py = par >> 1, px = par & 1;
+    const ConvTileId T = conv_tile_z<KIND == 2>(P);          // row-linear tiles: mt counts blocks of BM GEMM rows
+    const int m0 = T.mt * BM, n0 = T.nt * BN;
+    const int par = T.par, split = T.split, py = T.py, px = T.px;
     const int hw_rows = P.Ho * P.Wo;
 
     // ---- the rows this thread stages (fixed for the whole K loop) ----
@@ -409,9 +408,8 @@ conv_mfma_kernel(const ConvParams P) {
     const bool single_view = (m0 / hw_rows) == (m_last / hw_rows);
     const int n_tile = m0 / hw_rows;
 
-    const int per_split = (P.kt_total + P.splitk - 1) / P.splitk;
-    const int kt0 = split * per_split;
-    const int kt1 = min(P.kt_total, kt0 + per_split);
+    const KRange kr = split_range(P, split, P.kt_total);     // K steps here: (tap, chunk)
+    const int kt0 = kr.begin, kt1 = kr.end;
 
     float4 areg[RPT];
     float4 breg[BPT];
@@ -457,10 +455,7 @@ conv_mfma_kernel(const ConvParams P) {
                     if (scp) sc = *reinterpret_cast<const float4*>(scp + (size_t)rn[p] * C + cc);
                     if (shp) sh = *reinterpret_cast<const float4*>(shp + (size_t)rn[p] * C + cc);
                 }
-                v.x = apply_act(v.x * sc.x + sh.x, act);
-                v.y = apply_act(v.y * sc.y + sh.y, act);
-                v.z = apply_act(v.z * sc.z + sh.z, act);
-                v.w = apply_act(v.w * sc.w + sh.w, act);
+                v = normalize4<false>(v, sc, sh, act);
             }
             areg[p] = v;
         }
@@ -564,25 +559,7 @@ conv_mfma_kernel(const ConvParams P) {
     if (P.stats && P.splitk == 1) {
         if (single_view) {
             double* red = Stats::red(&As[0][0]);
-#pragma unroll
-            for (int j = 0; j < WN; j++) {
-                double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-                for (int i = 0; i < WM; i++)
-#pragma unroll
-                    for (int g = 0; g < 16; g++) {
-                        const double v = acc[i][j][g];
-                        s1 += v;
-                        s2 += v * v;
-                    }
-                s1 += __shfl_xor(s1, 32, 64);
-                s2 += __shfl_xor(s2, 32, 64);
-                if (h == 0) {
-                    const int col = wn0 + 32 * j + l31;
-                    red[(wave_m * BN + col) * 2 + 0] = s1;
-                    red[(wave_m * BN + col) * 2 + 1] = s2;
-                }
-            }
+            acc_column_stats<WM, WN>(acc, red, wave_m, BN, wn0, l31, h, 1.0f);
             Stats::publish(P, red, n_tile, n0, tid);
         } else {   // tiles straddling views only occur for maps smaller than a tile (tiny layers)
 #pragma unroll
@@ -625,11 +602,8 @@ conv_mfma_kernel(const ConvParams P) {
 // stored to the alternate LDS buffer after them; ONE barrier per 16-channel chunk (round 1 staged weight tiles by
 // LDS-DMA and needed a barrier per tap).
 // ------------------------------------------------------------------------------------------------
-// Epilogue of the halo kernels: the wave's accumulator tiles go to the NHWC output as buffer stores.  The address of
-// element (row block i, register g, column block j) splits into a workgroup-uniform 64-bit base (the resource), a
-// wave-uniform 32-bit offset per (i, g) (SGPR) and ONE per-lane 32-bit offset per column block, computed once: a store
-// is one instruction (no 64-bit VALU address arithmetic, no branch); lanes of padding columns beyond c_out_pad get an
-// out-of-range offset and the hardware drops their store.
+// Epilogue of the halo kernels: the wave's accumulator tiles go to the NHWC output through a ColumnStore, element (row block i,
+// register g, column block j) at a wave-uniform offset per (i, g).
 // Accumulator layout of v_mfma_f32_32x32x*: lane (l31, h), register g holds row (g & 3) + 8 (g >> 2) + 4 h, column l31.
 template <int KIND, int WM, int WN, int TW, bool SCALED = false>
 __device__ __forceinline__ void store_acc_tiles(const ConvParams& P, float* out, const floatx16 (&acc)[WM][WN], int n, int y0,
@@ -639,27 +613,16 @@ __device__ __forceinline__ void store_acc_tiles(const ConvParams& P, float* out,
     const int wm = __builtin_amdgcn_readfirstlane(wave_m);
     const int Y00 = XM * y0 + (KIND == 2 ? py : 0), X00 = XM * x0 + (KIND == 2 ? px : 0);
     float* base = out + (((size_t)n * P.OH + Y00) * P.OW + X00) * P.c_out_pad + n0;
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x27000);
-    const unsigned cp4 = (unsigned)P.c_out_pad * 4u;
-    unsigned voff[WN];
-#pragma unroll
-    for (int j = 0; j < WN; j++) {
-        const int colw = wn0 + 32 * j + l31;
-        voff[j] = (n0 + colw < P.c_out_pad) ? (unsigned)(XM * 4 * h) * cp4 + (unsigned)colw * 4u : 0x7fffffffu;
-    }
+    const ColumnStore<WN> cst(P, base, n0, wn0, l31, XM * 4 * h);
 #pragma unroll
     for (int i = 0; i < WM; i++) {
 #pragma unroll
         for (int g = 0; g < 16; g++) {
             const int pb0 = (g & 3) + 8 * (g >> 2);             // + 4 h: lane part (never crosses an image row of the tile)
             const int yrel = (wm * WM + i) * RPB + pb0 / TW, xrel = pb0 % TW;
-            const unsigned soff = (unsigned)(XM * (yrel * P.OW + xrel)) * cp4;
+            const unsigned pix = (unsigned)(XM * (yrel * P.OW + xrel));
 #pragma unroll
-            for (int j = 0; j < WN; j++) {
-                // (bit_cast straight from the vector element stores element 0: compiler bug — go through a scalar)
-                const float v = SCALED ? acc[i][j][g] * scale : acc[i][j][g];
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rsrc, (int)voff[j], (int)soff, 0);
-            }
+            for (int j = 0; j < WN; j++) cst.store(SCALED ? acc[i][j][g] * scale : acc[i][j][g], j, pix);
         }
     }
 }
@@ -684,8 +647,8 @@ conv_halo_kernel(const ConvParams P) {
     constexpr int HWD = KIND == 1 ? TW + 1 : TW + 2;       // halo width
     constexpr int HHT = KIND == 1 ? TH + 1 : TH + 2;       // halo height
     constexpr int HP = HWD * HHT;
-    constexpr int ASLOTS = HP * 4;                         // float4 slots of one halo chunk (pixel x channel quad)
-    constexpr int APT = (ASLOTS + CTHREADS - 1) / CTHREADS;
+    typedef HaloSlots<KIND, HWD, HHT, CTHREADS> Slots;
+    constexpr int APT = Slots::APT;                        // float4 halo slots per thread
     constexpr int APS = (APT + TAPS - 1) / TAPS;           // halo float4 fetched per pipeline step
     // two taps of MFMAs between a halo slice's fetch and its store cover the HBM latency (+0.4 %); the transposed conv at
     // three waves per SIMD has no registers for the second slice (it would spill to scratch)
@@ -708,18 +671,12 @@ conv_halo_kernel(const ConvParams P) {
     const int wave_m = wave / WAVES_N, wave_n = wave % WAVES_N;
     const int wn0 = wave_n * WCOLS;
     const int l15 = lane & 15, kq = lane >> 4;
-    int mt_, nt_, z_;
-    tile_coords(P, mt_, nt_, z_);
-    const int par = (KIND == 2) ? (z_ & 3) : 0;
-    const int split = (KIND == 2) ? (z_ >> 2) : z_;
-    const int py = par >> 1, px = par & 1;
-    const int n0 = nt_ * BN;
     // tile grid lives in the GEMM row space: output pixels (KIND 0/1) or input pixels of a parity class (KIND 2)
-    const int tiles_x = P.Wo / TW, tiles_y = P.Ho / TH;
-    const int n = mt_ / (tiles_x * tiles_y);
-    const int trem = mt_ - n * (tiles_x * tiles_y);
-    const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
-    if (P.tile_mask && P.tile_mask[mt_] == 0) {             // workgroup-uniform, before any barrier
+    const ConvTileId T = conv_tile<TW, TH, KIND == 2>(P);
+    const int par = T.par, split = T.split, py = T.py, px = T.px;
+    const int n0 = T.nt * BN;
+    const int n = T.n, y0 = T.y0, x0 = T.x0;
+    if (P.tile_mask && P.tile_mask[T.mt] == 0) {             // workgroup-uniform, before any barrier
         if (R16 && KIND == 0 && P.ray_w) {                  // nobody computes this tile: its pixels are background, the frame is 0 there
             const int hw = P.OH * P.OW;
             for (int it = tid; it < 3 * TH * TW; it += CTHREADS) {
@@ -730,84 +687,36 @@ conv_halo_kernel(const ConvParams P) {
         return;
     }
 
-    // halo slots of this thread: fixed source pixels for the whole K loop.  Slots past the halo fetch a valid address
-    // (an earlier slot's) and are never stored; the zero border of the transposed conv is a 0/1 factor.
+    // halo slots of this thread and where each lands in a chunk image
     const int q = tid & 3;
-    unsigned spix[KIND == 1 ? 1 : APT];      // pixel index inside the view (KIND 1: recomputed per phase from siy / six)
-    short siy[KIND == 1 ? APT : 1], six[KIND == 1 ? APT : 1];      // KIND 1: 2 (y0 + hy), 2 (x0 + hx)
+    Slots slots;
     int sdst[APT];           // float index of the (x, z) pair inside a chunk image; the (y, w) pair is 2 planes on
-    float smask[KIND == 2 ? APT : 1];
 #pragma unroll
     for (int j = 0; j < APT; j++) {
-        int s = tid + CTHREADS * j;
-        if (s >= ASLOTS) s -= ASLOTS;
-        const int hp = s >> 2;
-        const int hy = hp / HWD, hx = hp - hy * HWD;
-        int iy = 0, ix = 0;
-        const int col = hx;
-        if (KIND == 0) { iy = reflect1(y0 - 1 + hy, P.H); ix = reflect1(x0 - 1 + hx, P.W); }
-        else if (KIND == 1) { siy[j] = (short)(2 * (y0 + hy)); six[j] = (short)(2 * (x0 + hx)); }
-        else {
-            iy = y0 - 1 + hy; ix = x0 - 1 + hx;
-            const bool inside = iy >= 0 && iy < P.H && ix >= 0 && ix < P.W;
-            smask[j] = inside ? 1.f : 0.f;                          // exactly 0 outside, not act(shift)
-            iy = min(max(iy, 0), P.H - 1); ix = min(max(ix, 0), P.W - 1);
-        }
-        sdst[j] = ((q >> 1) * HP + hy * HWD + col) * 4 + 2 * (q & 1);
-        if (KIND != 1) spix[j] = (unsigned)(iy * P.W + ix);
+        int hy, hx;
+        Slots::slot(tid, j, hy, hx);
+        slots.set(P, j, y0, x0, hy, hx);
+        sdst[j] = ((q >> 1) * HP + hy * HWD + hx) * 4 + 2 * (q & 1);
     }
 
     const int nchunks = P.chunks_per_tap;
-    const int per_split = (nchunks + P.splitk - 1) / P.splitk;
-    const int c_begin = split * per_split;
-    const int c_end = min(nchunks, c_begin + per_split);
+    const int c_begin = T.c_begin, c_end = T.c_end;
 
-    // view base + channel offset are wave-uniform (SGPR pair); the per-lane part is a 32-bit element offset
-    // (plan_conv keeps H*W*C below 2^30), so a halo fetch is one global_load_dwordx4 v, voff, s[base] and one VALU mad.
-    // (buffer loads: resource + scalar offset + one 32-bit lane offset; flat 64-bit addresses make the unrolled tap loop
-    // keep a strength-reduced pointer pair per (tap, plane) alive across the chunk loop — registers the kernel lacks)
     // K steps: step = chunk * NPH + phase
-    struct ChunkSrc { __amdgpu_buffer_rsrc_t rsrc; unsigned C; unsigned soff; int act; int phy, phx; float4 sc, sh; };
-    auto chunk_src = [&](int step) {
-        ChunkSrc cs;
-        const int c = step / NPH;
-        cs.phy = (step % NPH) >> 1; cs.phx = (step % NPH) & 1;
-        const int s = c < P.chunks0 ? 0 : 1;
-        const int cc = (c - (s ? P.chunks0 : 0)) * BK;
-        cs.C = (unsigned)P.src_c[s];
-        cs.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.src_data[s] + (size_t)n * P.H * P.W * cs.C), 0,
-                                                    0x7fffffff, 0x27000);
-        cs.soff = (unsigned)cc * 4u;
-        cs.act = P.src_act[s];
-        cs.sc = make_float4(1.f, 1.f, 1.f, 1.f);
-        cs.sh = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (P.src_scale[s]) cs.sc = *reinterpret_cast<const float4*>(P.src_scale[s] + (size_t)n * cs.C + cc + 4 * q);
-        if (P.src_shift[s]) cs.sh = *reinterpret_cast<const float4*>(P.src_shift[s] + (size_t)n * cs.C + cc + 4 * q);
-        return cs;
-    };
-    auto load_a = [&](const ChunkSrc& cs, int j) {
-        unsigned pixel;
-        if (KIND == 1) pixel = (unsigned)(reflect1(siy[j] - cs.phy, P.H) * P.W + reflect1(six[j] - cs.phx, P.W));
-        else pixel = spix[j];
-        const unsigned voff = (pixel * cs.C + 4u * (unsigned)q) * 4u;
-        return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(cs.rsrc, (int)voff, (int)cs.soff, 0));
-    };
-    auto store_a = [&](const ChunkSrc& cs, float4 v, int j, int buf) {
-        float x = apply_act(v.x * cs.sc.x + cs.sh.x, cs.act);
-        float y = apply_act(v.y * cs.sc.y + cs.sh.y, cs.act);
-        float z = apply_act(v.z * cs.sc.z + cs.sh.z, cs.act);
-        float w = apply_act(v.w * cs.sc.w + cs.sh.w, cs.act);
-        if (KIND == 2) { x *= smask[j]; y *= smask[j]; z *= smask[j]; w *= smask[j]; }
+    auto chunk_src = [&](int step) { return halo_src<NPH>(P, n, q, step); };
+    auto load_a = [&](const HaloSrc& cs, int j) { return slots.load(P, cs, j, q); };
+    auto store_a = [&](const HaloSrc& cs, float4 v, int j, int buf) {
+        const float4 u = normalize4<KIND == 2>(cs, v, slots.mask(j));
         float* a = As + buf * ACH + sdst[j];
-        *reinterpret_cast<float2*>(a) = make_float2(x, z);                  // channels 4q, 4q+2   (h = 0 planes)
-        *reinterpret_cast<float2*>(a + 2 * HP * 4) = make_float2(y, w);     // channels 4q+1, 4q+3 (h = 1 planes)
+        *reinterpret_cast<float2*>(a) = make_float2(u.x, u.z);                  // channels 4q, 4q+2   (h = 0 planes)
+        *reinterpret_cast<float2*>(a + 2 * HP * 4) = make_float2(u.y, u.w);     // channels 4q+1, 4q+3 (h = 1 planes)
     };
     // Weights of one (chunk, tap): the packed layout (pack_weight_kernel) is the plane image [4 planes][wstride][4 floats]
     // per chunk, and an MFMA lane (column, k parity h) needs exactly the float4s of planes 2h and 2h+1 at its column:
     // lanes of a wave are consecutive columns, so a tap's B operand is 2*WN coalesced buffer_load_dwordx4 per wave
     // straight into the operand registers, requested one tap ahead.  No LDS weight tile, no LDS-DMA, and therefore no
     // barrier per tap: the only LDS hazard left is the halo swap (one barrier per chunk).
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.weight), 0, 0x7fffffff, 0x27000);
+    const __amdgpu_buffer_rsrc_t wrsrc = buffer_rsrc(P.weight);
     const unsigned tile_bytes = 64u * (unsigned)P.wstride;                  // one (chunk, tap) block: 16 channels x wstride floats
     unsigned bvoff[2];
 #pragma unroll
@@ -851,10 +760,10 @@ conv_halo_kernel(const ConvParams P) {
     const float* a16_lane = As + (g16 * HP + wave_m * WM * HWD + (KIND == 2 ? py * HWD + px : 0) + l15) * 4;   // R16: TW = 32 only
 
     if (c_begin < c_end) {
-        const ChunkSrc cs = chunk_src(c_begin * NPH);
+        const HaloSrc cs = chunk_src(c_begin * NPH);
 #pragma unroll
         for (int j = 0; j < APT; j++)
-            if (tid + CTHREADS * j < ASLOTS) store_a(cs, load_a(cs, j), j, 0);
+            if (Slots::stored(tid, j)) store_a(cs, load_a(cs, j), j, 0);
     }
     const int s_begin = c_begin * NPH, s_end = c_end * NPH;
     BRegs breg[2];
@@ -863,7 +772,7 @@ conv_halo_kernel(const ConvParams P) {
     for (int c = s_begin; c < s_end; c++) {                     // c = K step (chunk, phase)
         const int abuf = (c - s_begin) & 1;
         const bool next_chunk = c + 1 < s_end;
-        ChunkSrc csn = chunk_src(next_chunk ? c + 1 : c);
+        HaloSrc csn = chunk_src(next_chunk ? c + 1 : c);
         float4 avr[HDIST < 2 ? 2 : HDIST][APS];     // halo slices in flight: fetched during tap t, stored after tap t + HDIST - 1
 #pragma unroll
         for (int t = 0; t < TAPS; t++) {
@@ -916,7 +825,7 @@ conv_halo_kernel(const ConvParams P) {
 #pragma unroll
                 for (int u = 0; u < APS; u++) {
                     const int j = ts * APS + u;
-                    if (next_chunk && j < APT && tid + CTHREADS * j < ASLOTS)
+                    if (next_chunk && j < APT && Slots::stored(tid, j))
                         store_a(csn, avr[ts % (HDIST < 2 ? 2 : HDIST)][u], j, abuf ^ 1);
                 }
             }
@@ -928,7 +837,7 @@ conv_halo_kernel(const ConvParams P) {
 #pragma unroll
             for (int u = 0; u < APS; u++) {
                 const int j = ts * APS + u;
-                if (next_chunk && j < APT && tid + CTHREADS * j < ASLOTS)
+                if (next_chunk && j < APT && Slots::stored(tid, j))
                     store_a(csn, avr[ts % (HDIST < 2 ? 2 : HDIST)][u], j, abuf ^ 1);
             }
         }
@@ -1009,6 +918,7 @@ conv_halo_kernel(const ConvParams P) {
     }
     const bool with_stats = P.stats && P.splitk == 1;
     if (with_stats) {
+        // acc_column_stats, written out: through the function ten instantiations of this kernel change their register allocation
 #pragma unroll
         for (int j = 0; j < WN; j++) {
             double s1 = 0.0, s2 = 0.0;
@@ -1166,10 +1076,6 @@ conv_halo_emu_kernel(const ConvParams P) {
     constexpr int HWD = KIND == 1 ? TW + 1 : TW + 2;
     constexpr int HHT = KIND == 1 ? TH + 1 : TH + 2;
     constexpr int HP = HWD * HHT;
-    constexpr int ASLOTS = HP * 4;
-    constexpr int APT = (ASLOTS + CTHREADS - 1) / CTHREADS;
-    constexpr int SPT = (APT + TAPS - 1) / TAPS;              // halo slots a thread converts per tap
-    constexpr int NGROUPS = (APT + SPT - 1) / SPT;            // <= TAPS
     constexpr int APL = 2 * HP * 16;                          // bytes per term plane (two k-halves)
     constexpr int ACHB = NT * APL;                            // bytes per halo image
     constexpr int ROWSTEP = RPB * HWD;                        // halo pixels between consecutive MFMA row blocks
@@ -1182,94 +1088,45 @@ conv_halo_emu_kernel(const ConvParams P) {
     const int l31 = lane & 31, h = lane >> 5;
     const int wave_m = wave / WAVES_N, wave_n = wave % WAVES_N;
     const int wn0 = wave_n * WN * 32;
-    int mt_, nt_, z_;
-    tile_coords(P, mt_, nt_, z_);
-    if (P.tile_mask && P.tile_mask[mt_] == 0) return;
-    const int par = (KIND == 2) ? (z_ & 3) : 0;
-    const int split = (KIND == 2) ? (z_ >> 2) : z_;
-    const int py = par >> 1, px = par & 1;
-    const int n0 = nt_ * BN;
-    const int tiles_x = P.Wo / TW, tiles_y = P.Ho / TH;
-    const int n = mt_ / (tiles_x * tiles_y);
-    const int trem = mt_ - n * (tiles_x * tiles_y);
-    const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
+    const ConvTileId T = conv_tile<TW, TH, KIND == 2>(P);
+    if (P.tile_mask && P.tile_mask[T.mt] == 0) return;
+    const int par = T.par, split = T.split, py = T.py, px = T.px;
+    const int n0 = T.nt * BN;
+    const int n = T.n, y0 = T.y0, x0 = T.x0;
 
     const int q = tid & 3;
-    unsigned spix[KIND == 1 ? 1 : APT];      // source pixel of a slot (KIND 1: recomputed per phase from siy / six)
-    short siy[KIND == 1 ? APT : 1], six[KIND == 1 ? APT : 1];      // KIND 1: 2 (y0 + hy), 2 (x0 + hx)
+    typedef HaloSlots<KIND, HWD, HHT, CTHREADS> Slots;
+    constexpr int APT = Slots::APT;
+    constexpr int SPT = (APT + TAPS - 1) / TAPS;              // halo slots a thread converts per tap
+    constexpr int NGROUPS = (APT + SPT - 1) / SPT;            // <= TAPS
+    Slots slots;
     int sdst[APT];           // byte offset of this slot's 4 bf16 inside a term plane
-    float smask[KIND == 2 ? APT : 1];
 #pragma unroll
     for (int j = 0; j < APT; j++) {
-        // slots past the halo only fetch (a valid address); they are never stored (every LDS slot is written once)
-        int s = tid + CTHREADS * j;
-        if (s >= ASLOTS) s -= ASLOTS;
-        const int hp = s >> 2;
-        const int hy = hp / HWD, hx = hp - hy * HWD;
-        int iy = 0, ix = 0;
-        const int col = hx;
-        if (KIND == 0) { iy = reflect1(y0 - 1 + hy, P.H); ix = reflect1(x0 - 1 + hx, P.W); }
-        else if (KIND == 1) { siy[j] = (short)(2 * (y0 + hy)); six[j] = (short)(2 * (x0 + hx)); }
-        else {
-            iy = y0 - 1 + hy; ix = x0 - 1 + hx;
-            const bool inside = iy >= 0 && iy < P.H && ix >= 0 && ix < P.W;
-            smask[j] = inside ? 1.f : 0.f;
-            iy = min(max(iy, 0), P.H - 1); ix = min(max(ix, 0), P.W - 1);
-        }
-        sdst[j] = ((q >> 1) * HP + hy * HWD + col) * 16 + (q & 1) * 8;      // k-half = channels 8*(q>>1) .., 4 bf16 at (q&1)*4
-        if (KIND != 1) spix[j] = (unsigned)(iy * P.W + ix);
+        int hy, hx;
+        Slots::slot(tid, j, hy, hx);
+        slots.set(P, j, y0, x0, hy, hx);
+        sdst[j] = ((q >> 1) * HP + hy * HWD + hx) * 16 + (q & 1) * 8;      // k-half = channels 8*(q>>1) .., 4 bf16 at (q&1)*4
     }
 
     const int nchunks = P.chunks_per_tap;
-    const int per_split = (nchunks + P.splitk - 1) / P.splitk;
-    const int c_begin = split * per_split;
-    const int c_end = min(nchunks, c_begin + per_split);
+    const int c_begin = T.c_begin, c_end = T.c_end;
 
-    // Global operands go through buffer loads: a wave-uniform base (resource + scalar offset) plus ONE 32-bit per-lane
-    // offset.  With flat 64-bit addresses the unrolled tap loop keeps a strength-reduced pointer pair per (tap, term)
-    // alive across the chunk loop and spills.
     // K steps: step = chunk * NPH + phase
-    struct ChunkSrc { __amdgpu_buffer_rsrc_t rsrc; unsigned C; unsigned soff; int act; int phy, phx; float4 sc, sh; };
-    auto chunk_src = [&](int step) {
-        ChunkSrc cs;
-        const int c = step / NPH;
-        cs.phy = (step % NPH) >> 1; cs.phx = (step % NPH) & 1;
-        const int s = c < P.chunks0 ? 0 : 1;
-        const int cc = (c - (s ? P.chunks0 : 0)) * BK;
-        cs.C = (unsigned)P.src_c[s];
-        cs.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.src_data[s] + (size_t)n * P.H * P.W * cs.C), 0,
-                                                    0x7fffffff, 0x27000);
-        cs.soff = (unsigned)cc * 4u;
-        cs.act = P.src_act[s];
-        cs.sc = make_float4(1.f, 1.f, 1.f, 1.f);
-        cs.sh = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (P.src_scale[s]) cs.sc = *reinterpret_cast<const float4*>(P.src_scale[s] + (size_t)n * cs.C + cc + 4 * q);
-        if (P.src_shift[s]) cs.sh = *reinterpret_cast<const float4*>(P.src_shift[s] + (size_t)n * cs.C + cc + 4 * q);
-        return cs;
-    };
-    auto load_a = [&](const ChunkSrc& cs, int j) {
-        unsigned pixel;
-        if (KIND == 1) pixel = (unsigned)(reflect1(siy[j] - cs.phy, P.H) * P.W + reflect1(six[j] - cs.phx, P.W));
-        else pixel = spix[j];
-        const unsigned voff = (pixel * cs.C + 4u * (unsigned)q) * 4u;
-        return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(cs.rsrc, (int)voff, (int)cs.soff, 0));
-    };
-    auto store_a = [&](const ChunkSrc& cs, float4 v, int j, char* img) {
-        float x = apply_act(v.x * cs.sc.x + cs.sh.x, cs.act);
-        float y = apply_act(v.y * cs.sc.y + cs.sh.y, cs.act);
-        float z = apply_act(v.z * cs.sc.z + cs.sh.z, cs.act);
-        float w = apply_act(v.w * cs.sc.w + cs.sh.w, cs.act);
-        if (KIND == 2) { x *= smask[j]; y *= smask[j]; z *= smask[j]; w *= smask[j]; }
+    auto chunk_src = [&](int step) { return halo_src<NPH>(P, n, q, step); };
+    auto load_a = [&](const HaloSrc& cs, int j) { return slots.load(P, cs, j, q); };
+    auto store_a = [&](const HaloSrc& cs, float4 v, int j, char* img) {
+        const float4 u = normalize4<KIND == 2>(cs, v, slots.mask(j));
         unsigned t0[NT], t1[NT];
-        F::split(x, y, t0);
-        F::split(z, w, t1);
+        F::split(u.x, u.y, t0);
+        F::split(u.z, u.w, t1);
         char* a = img + sdst[j];
 #pragma unroll
         for (int term = 0; term < NT; term++) *reinterpret_cast<uint2*>(a + term * APL) = make_uint2(t0[term], t1[term]);
     };
     // weights: packed image per (parity, tap, chunk) = [NT terms][2 k-halves][wstride][8 x 16 bit] behind a 64-byte header
     const char* wimg = reinterpret_cast<const char*>(P.weight_emu) + EMU_HEADER_BYTES;
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(wimg), 0, 0x7fffffff, 0x27000);
+    const __amdgpu_buffer_rsrc_t wrsrc = buffer_rsrc(wimg);
     const unsigned tile_bytes = (unsigned)(NT * 32) * (unsigned)P.wstride;
     unsigned bvoff[NT];
 #pragma unroll
@@ -1305,17 +1162,17 @@ conv_halo_emu_kernel(const ConvParams P) {
     const int s_begin = c_begin * NPH, s_end = c_end * NPH;
     vec8 b[2][NT][WN];
     if (s_begin < s_end) {
-        const ChunkSrc cs = chunk_src(s_begin);
+        const HaloSrc cs = chunk_src(s_begin);
         load_b(b[0], s_begin, 0);
 #pragma unroll
         for (int j = 0; j < APT; j++)
-            if (tid + CTHREADS * j < ASLOTS) store_a(cs, load_a(cs, j), j, As);
+            if (Slots::stored(tid, j)) store_a(cs, load_a(cs, j), j, As);
     }
     __syncthreads();
     int cur = 0;
     for (int c = s_begin; c < s_end; c++, cur ^= 1) {            // c = K step (chunk, phase)
         const bool next_chunk = c + 1 < s_end;
-        const ChunkSrc csn = chunk_src(next_chunk ? c + 1 : c);
+        const HaloSrc csn = chunk_src(next_chunk ? c + 1 : c);
         const char* a_rd = As + cur * ACHB + a_lane_off;
         char* a_wr = As + (cur ^ 1) * ACHB;
         float4 av[2][SPT];
@@ -1334,7 +1191,7 @@ conv_halo_emu_kernel(const ConvParams P) {
 #pragma unroll
                     for (int u = 0; u < SPT; u++) {
                         const int j = (t - 1) * SPT + u;
-                        if (j < APT && tid + CTHREADS * j < ASLOTS) store_a(csn, av[(t - 1) & 1][u], j, a_wr);
+                        if (j < APT && Slots::stored(tid, j)) store_a(csn, av[(t - 1) & 1][u], j, a_wr);
                     }
                 }
             }
@@ -1363,7 +1220,7 @@ conv_halo_emu_kernel(const ConvParams P) {
 #pragma unroll
             for (int u = 0; u < SPT; u++) {
                 const int j = (TAPS - 1) * SPT + u;
-                if (j < APT && tid + CTHREADS * j < ASLOTS) store_a(csn, av[(TAPS - 1) & 1][u], j, a_wr);
+                if (j < APT && Slots::stored(tid, j)) store_a(csn, av[(TAPS - 1) & 1][u], j, a_wr);
             }
         }
         if (TAPS & 1) {
@@ -1375,7 +1232,7 @@ conv_halo_emu_kernel(const ConvParams P) {
         __syncthreads();        // next halo complete and visible; everybody is done reading the current one
     }
 
-    // ---- epilogue (identical to conv_halo_kernel: same accumulator layout) ----
+    // ---- epilogue (as conv_halo_kernel: same accumulator layout) ----
     // f16x3: undo the power-of-two weight scale — at the store, and on the column sums of the statistics (a power of
     // two commutes with every fp32 rounding involved, so this equals scaling the accumulators first; scaling all 128 of
     // them in place made the compiler keep both copies and spill)
@@ -1386,26 +1243,7 @@ conv_halo_emu_kernel(const ConvParams P) {
     float* out = P.out + (size_t)split * P.slab_stride;
     const bool with_stats = P.stats && P.splitk == 1;
     if (with_stats) {
-#pragma unroll
-        for (int j = 0; j < WN; j++) {
-            double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-            for (int i = 0; i < WM; i++)
-#pragma unroll
-                for (int g = 0; g < 16; g++) {
-                    const double v = acc[i][j][g];
-                    s1 += v;
-                    s2 += v * v;
-                }
-            if (FMT == 1) { s1 *= winv; s2 = (s2 * winv) * winv; }
-            s1 += __shfl_xor(s1, 32, 64);
-            s2 += __shfl_xor(s2, 32, 64);
-            if (h == 0) {
-                const int col = wn0 + 32 * j + l31;
-                red[(wave_m * BN + col) * 2 + 0] = s1;
-                red[(wave_m * BN + col) * 2 + 1] = s2;
-            }
-        }
+        acc_column_stats<WM, WN>(acc, red, wave_m, BN, wn0, l31, h, winv);
         Stats::publish(P, red, n, n0, tid);
     }
     BnArrival arr = {nullptr, 0u};

@@ -64,30 +64,23 @@ conv_wino_kernel(const ConvParams P) {
     const int lane = tid & 63;
     const int xi = __builtin_amdgcn_readfirstlane(tid >> 6);        // the wave's plane row
     const int l31 = lane & 31, h = lane >> 5;
-    int mt_, nt_, z_;
-    tile_coords(P, mt_, nt_, z_);
+    const ConvTileId T = conv_tile<WINO_PW, WINO_PH, false>(P);
+    const int nt_ = T.nt, z_ = T.z;
     const int n0 = nt_ * WINO_BN;
-    const int tiles_x = P.W / WINO_PW, tiles_y = P.H / WINO_PH;
-    const int n = mt_ / (tiles_x * tiles_y);
-    const int trem = mt_ - n * (tiles_x * tiles_y);
-    const int y0 = (trem / tiles_x) * WINO_PH, x0 = (trem % tiles_x) * WINO_PW;
+    const int n = T.n, y0 = T.y0, x0 = T.x0;
 
-    // halo slots of this thread (fixed source pixels for the whole K loop).  Slots past the halo wrap to the thread's own
-    // earlier slot shifted by a multiple of four — the same channel quad of a pixel some other thread stages too — so that
-    // loads and stores need no predicate: the duplicate writes the identical value
+    // halo slots of this thread (fixed source pixels for the whole K loop); wrapped slots are staged twice: loads and stores
+    // need no predicate
     const int q = tid & 3;
     unsigned spix[WINO_APT];
     float* sd_cur[WINO_APT];        // staging destinations in the buffer being read / being filled
     float* sd_nxt[WINO_APT];
 #pragma unroll
     for (int j = 0; j < WINO_APT; j++) {
-        int s = tid + CTHREADS * j;
-        if (s >= WINO_SLOTS) s -= WINO_SLOTS;
-        static_assert(WINO_SLOTS % 4 == 0, "the wrapped slot keeps the channel quad");
-        const int hp = s >> 2;
-        const int hy = hp / WINO_HW, hx = hp - hy * WINO_HW;
-        const int iy = reflect1(y0 - 1 + hy, P.H), ix = reflect1(x0 - 1 + hx, P.W);
-        spix[j] = (unsigned)(iy * P.W + ix);
+        int hy, hx;
+        float m;
+        halo_slot<WINO_HW, WINO_SLOTS, CTHREADS>(tid, j, hy, hx);
+        spix[j] = halo_pixel<0>(P, y0, x0, hy, hx, m);
         sd_cur[j] = As + (4 * q) * WINO_PLANE + hy * WINO_ROWP + hx;
         sd_nxt[j] = sd_cur[j] + WINO_CHUNK;
     }
@@ -95,38 +88,17 @@ conv_wino_kernel(const ConvParams P) {
     // split-K (small grids): slice z_ of P.splitk takes the chunks [c_begin, c_end) and writes its partial outputs — the output
     // transform is linear — to its own slab; splitk_reduce_kernel adds the slabs (and takes the statistics)
     const int nchunks = P.chunks_per_tap;
-    const int per_split = (nchunks + P.splitk - 1) / P.splitk;
-    const int c_begin = z_ * per_split, c_end = min(nchunks, c_begin + per_split);
-    struct ChunkSrc { __amdgpu_buffer_rsrc_t rsrc; unsigned C; unsigned soff; int act; float4 sc, sh; };
-    auto chunk_src = [&](int c) {
-        ChunkSrc cs;
-        const int s = c < P.chunks0 ? 0 : 1;
-        const int cc = (c - (s ? P.chunks0 : 0)) * BK;
-        cs.C = (unsigned)P.src_c[s];
-        cs.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.src_data[s] + (size_t)n * P.H * P.W * cs.C), 0,
-                                                    0x7fffffff, 0x27000);
-        cs.soff = (unsigned)cc * 4u;
-        cs.act = P.src_act[s];
-        cs.sc = make_float4(1.f, 1.f, 1.f, 1.f);
-        cs.sh = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (P.src_scale[s]) cs.sc = *reinterpret_cast<const float4*>(P.src_scale[s] + (size_t)n * cs.C + cc + 4 * q);
-        if (P.src_shift[s]) cs.sh = *reinterpret_cast<const float4*>(P.src_shift[s] + (size_t)n * cs.C + cc + 4 * q);
-        return cs;
-    };
-    auto load_a = [&](const ChunkSrc& cs, int j) {
-        const unsigned voff = (spix[j] * cs.C + 4u * (unsigned)q) * 4u;
-        return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(cs.rsrc, (int)voff, (int)cs.soff, 0));
-    };
-    auto store_a = [&](const ChunkSrc& cs, float4 v, float* a) {
-        a[0] = apply_act(v.x * cs.sc.x + cs.sh.x, cs.act);
-        a[WINO_PLANE] = apply_act(v.y * cs.sc.y + cs.sh.y, cs.act);
-        a[2 * WINO_PLANE] = apply_act(v.z * cs.sc.z + cs.sh.z, cs.act);
-        a[3 * WINO_PLANE] = apply_act(v.w * cs.sc.w + cs.sh.w, cs.act);
+    const int c_begin = T.c_begin, c_end = T.c_end;
+    auto chunk_src = [&](int c) { return halo_src<1>(P, n, q, c); };
+    auto load_a = [&](const HaloSrc& cs, int j) { return halo_load(cs, spix[j], q); };
+    auto store_a = [&](const HaloSrc& cs, float4 v, float* a) {
+        const float4 u = normalize4<false>(cs, v);
+        a[0] = u.x; a[WINO_PLANE] = u.y; a[2 * WINO_PLANE] = u.z; a[3 * WINO_PLANE] = u.w;
     };
 
     // transformed weights of this column tile: [K step][xi][column half][h][32 columns][4 planes]; the image carries
     // WINO_BDIST K steps of padding behind the last one, so the look-ahead needs no clamp
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.weight_wino), 0, 0x7fffffff, 0x27000);
+    const __amdgpu_buffer_rsrc_t wrsrc = buffer_rsrc(P.weight_wino);
     const unsigned bvoff = (unsigned)(h * 32 + l31) * 16u;
     unsigned bsoff = ((unsigned)nt_ * (unsigned)(nchunks * 8 + WINO_BDIST) + (unsigned)(c_begin * 8)) * (unsigned)(WINO_STEP_FLOATS * 4) +
                      (unsigned)xi * 2048u;
@@ -169,7 +141,7 @@ conv_wino_kernel(const ConvParams P) {
         for (int g = 0; g < 16; g++) acc[p][g] = 0.0f;
 
     if (c_begin < c_end) {
-        const ChunkSrc cs = chunk_src(c_begin);
+        const HaloSrc cs = chunk_src(c_begin);
 #pragma unroll
         for (int j = 0; j < WINO_APT; j++) store_a(cs, load_a(cs, j), sd_cur[j]);
     }
@@ -185,7 +157,7 @@ conv_wino_kernel(const ConvParams P) {
 
     auto chunk_body = [&](auto NEXT, int c) {
         constexpr bool next_chunk = decltype(NEXT)::value;
-        const ChunkSrc csn = chunk_src(next_chunk ? c + 1 : c);
+        const HaloSrc csn = chunk_src(next_chunk ? c + 1 : c);
         float4 avr[WINO_APT];
 #pragma unroll
         for (int s = 0; s < 8; s++) {
@@ -295,22 +267,14 @@ conv_wino_kernel(const ConvParams P) {
     {
         // this wave finishes tile row xi: output rows 2 xi, 2 xi + 1 of the tile
         float* base = P.out + (size_t)z_ * P.slab_stride + (((size_t)n * P.OH + y0 + 2 * xi) * P.OW + x0) * P.c_out_pad + n0;
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x27000);
-        const unsigned cp4 = (unsigned)P.c_out_pad * 4u;
-        unsigned voff[2];
-#pragma unroll
-        for (int nb = 0; nb < 2; nb++)
-            voff[nb] = (n0 + 32 * nb + l31 < P.c_out_pad) ? (unsigned)(8 * h) * cp4 + (unsigned)(32 * nb + l31) * 4u : 0x7fffffffu;
+        const ColumnStore<2, WINO_OUT_AUX> cst(P, base, n0, 0, l31, 8 * h);
 #pragma unroll
         for (int gq = 0; gq < 4; gq++)
 #pragma unroll
             for (int a = 0; a < 2; a++)
 #pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    const unsigned soff = (unsigned)(a * P.OW + 2 * gq + (e & 1)) * cp4;
-                    const float v = a ? y1v[gq][e] : y0v[gq][e];
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rsrc, (int)voff[e >> 1], (int)soff, WINO_OUT_AUX);
-                }
+                for (int e = 0; e < 4; e++)
+                    cst.store(a ? y1v[gq][e] : y0v[gq][e], e >> 1, (unsigned)(a * P.OW + 2 * gq + (e & 1)));
     }
     if (bn) bn_complete(P, arr, n, tid, WinoStats::flag(red));
 }

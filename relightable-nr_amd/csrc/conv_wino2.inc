@@ -1,5 +1,5 @@
 // Winograd F(2x2, 2x2) for the two 4x4 stride-2 convolutions of the U-Net, exact-fp32 operands on v_mfma_f32_32x32x2_f32.
-// Included by conv.hip behind conv_wino.inc (same helpers, same LDS halo layout, same software pipeline).
+// Included by conv.hip behind conv_wino.inc (the staging helpers of conv_stage.inc, same LDS halo layout, same software pipeline).
 //
 // Both decompose into 2x2-tap stride-1 correlations (conv_halo_kernel does the same):
 //   KIND 2  ConvTranspose2d 4x4 s2 p1: output parity class (py, px) is a 2x2-tap correlation of the input,
@@ -51,6 +51,7 @@ struct W2Tile {
     int py, mb;         // KIND 2: row parity of the output class (column parity px = grp); KIND 1: tile rows 4 mb .. 4 mb + 3 of 8
     int n0;             // first output column of this wave
     int n, y0, x0;      // view, first row / column of the tile in the GEMM row space (output pixels, KIND 1, or input pixels, KIND 2)
+    int c_begin, c_end; // 16-channel chunks of the split-K slice
 };
 template <int KIND>
 __device__ __forceinline__ W2Tile w2_tile(const ConvParams& P) {
@@ -62,15 +63,14 @@ __device__ __forceinline__ W2Tile w2_tile(const ConvParams& P) {
     const int sub = T.wgrp >> 1;                            // KIND 2: (py, px); KIND 1: (tile-row half, column half)
     T.grp = T.wgrp & 1;
     T.l31 = T.lane & 31; T.h = T.lane >> 5;
-    int mt_;
-    tile_coords(P, mt_, T.nt, T.z);
+    // all four parity classes of the transposed conv live in one workgroup: z is the split-K slice alone for both kinds
+    const ConvTileId C = conv_tile<WINO_PW, W2Kind<KIND>::TPH, false>(P);
+    T.nt = C.nt; T.z = C.z;
     T.py = KIND == 2 ? sub : 0;
     T.mb = KIND == 1 ? sub : 0;
     T.n0 = T.nt * W2Kind<KIND>::BNW + (KIND == 1 ? 64 * T.grp : 0);
-    const int tiles_x = P.Wo / WINO_PW, tiles_y = P.Ho / W2Kind<KIND>::TPH;
-    T.n = mt_ / (tiles_x * tiles_y);
-    const int trem = mt_ - T.n * (tiles_x * tiles_y);
-    T.y0 = (trem / tiles_x) * W2Kind<KIND>::TPH; T.x0 = (trem % tiles_x) * WINO_PW;
+    T.n = C.n; T.y0 = C.y0; T.x0 = C.x0;
+    T.c_begin = C.c_begin; T.c_end = C.c_end;
     return T;
 }
 
@@ -80,7 +80,6 @@ __device__ __forceinline__ W2Tile w2_tile(const ConvParams& P) {
 //           moves row 2 (y0 + hy) = H to H - 2 (phy = 0) and row -1 to 1 (phy = 1), so the four pixels of a slot are
 //           spix + phy * (+-W) + phx * (+-1): one register per slot and two sign bits, instead of two reflections per
 //           staging load (r05; ~14 VALU each, - 1 % on the five stride-2 layers).
-// Slots past the halo wrap to an earlier slot of the same channel quad (duplicate writes of identical values).
 struct W2Slot {
     int hy, hx;
     unsigned spix;
@@ -89,20 +88,11 @@ struct W2Slot {
 };
 template <int KIND>
 __device__ __forceinline__ W2Slot w2_slot(const ConvParams& P, const W2Tile& T, int j) {
-    constexpr int SLOTS = W2Kind<KIND>::SLOTS;
-    static_assert(SLOTS % 4 == 0, "the wrapped slot keeps the channel quad");
     W2Slot S;
-    int s = T.tid + W2_THREADS * j;
-    if (s >= SLOTS) s -= SLOTS;
-    const int hp = s >> 2;
-    S.hy = hp / W2_HW; S.hx = hp - S.hy * W2_HW;
+    halo_slot<W2_HW, W2Kind<KIND>::SLOTS, W2_THREADS>(T.tid, j, S.hy, S.hx);
     S.sign = 0; S.mask = 1.f;
     if (KIND == 2) {
-        int iy = T.y0 - 1 + S.hy, ix = T.x0 - 1 + S.hx;
-        const bool inside = iy >= 0 && iy < P.H && ix >= 0 && ix < P.W;
-        S.mask = inside ? 1.f : 0.f;
-        iy = min(max(iy, 0), P.H - 1); ix = min(max(ix, 0), P.W - 1);
-        S.spix = (unsigned)(iy * P.W + ix);
+        S.spix = halo_pixel<2>(P, T.y0, T.x0, S.hy, S.hx, S.mask);
     } else {
         const int ry = 2 * (T.y0 + S.hy), cx = 2 * (T.x0 + S.hx);
         const int r0 = reflect1(ry, P.H), r1 = reflect1(ry - 1, P.H), c0 = reflect1(cx, P.W), c1 = reflect1(cx - 1, P.W);
@@ -112,48 +102,16 @@ __device__ __forceinline__ W2Slot w2_slot(const ConvParams& P, const W2Tile& T, 
     return S;
 }
 
-// K block kb = (chunk, input parity phase): source of view n, channel offset, and the BatchNorm scale / shift of quad q
-struct W2Src { __amdgpu_buffer_rsrc_t rsrc; unsigned C; unsigned soff; int act; int phy, phx; float4 sc, sh; };
+// the raw float4 of a slot in K block kb = (chunk, input parity phase): spix, and for KIND 1 the slot's sign bits at bit
+// `sbit` + 1 / `sbit` of `signs`
 template <int KIND>
-__device__ __forceinline__ W2Src w2_block_src(const ConvParams& P, int n, int q, int kb) {
-    constexpr int NPH = W2Kind<KIND>::NPH;
-    W2Src cs;
-    const int c = kb / NPH;
-    cs.phy = (kb % NPH) >> 1; cs.phx = (kb % NPH) & 1;
-    const int s = c < P.chunks0 ? 0 : 1;
-    const int cc = (c - (s ? P.chunks0 : 0)) * BK;
-    cs.C = (unsigned)P.src_c[s];
-    cs.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.src_data[s] + (size_t)n * P.H * P.W * cs.C), 0,
-                                                0x7fffffff, 0x27000);
-    cs.soff = (unsigned)cc * 4u;
-    cs.act = P.src_act[s];
-    cs.sc = make_float4(1.f, 1.f, 1.f, 1.f);
-    cs.sh = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (P.src_scale[s]) cs.sc = *reinterpret_cast<const float4*>(P.src_scale[s] + (size_t)n * cs.C + cc + 4 * q);
-    if (P.src_shift[s]) cs.sh = *reinterpret_cast<const float4*>(P.src_shift[s] + (size_t)n * cs.C + cc + 4 * q);
-    return cs;
-}
-// the raw float4 of a slot (spix, and for KIND 1 the slot's sign bits at bit `sbit` + 1 / `sbit` of `signs`)
-template <int KIND>
-__device__ __forceinline__ float4 w2_load_halo(const ConvParams& P, const W2Src& cs, unsigned pixel, unsigned signs, int sbit, int q) {
+__device__ __forceinline__ float4 w2_load_halo(const ConvParams& P, const HaloSrc& cs, unsigned pixel, unsigned signs, int sbit, int q) {
     if (KIND == 1) {
         if (cs.phy) pixel += (signs >> (sbit + 1)) & 1u ? (unsigned)P.W : 0u - (unsigned)P.W;
         if (cs.phx) pixel += (signs >> sbit) & 1u ? 1u : ~0u;
     }
-    const unsigned voff = (pixel * cs.C + 4u * (unsigned)q) * 4u;
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(cs.rsrc, (int)voff, (int)cs.soff, 0));
+    return halo_load(cs, pixel, q);
 }
-// BatchNorm + activation of a staged float4; the transposed conv's halo is exactly 0 outside the map, not act(shift)
-template <int KIND>
-__device__ __forceinline__ float4 w2_normalize(const W2Src& cs, float4 v, float mask) {
-    float x = apply_act(v.x * cs.sc.x + cs.sh.x, cs.act);
-    float y = apply_act(v.y * cs.sc.y + cs.sh.y, cs.act);
-    float z = apply_act(v.z * cs.sc.z + cs.sh.z, cs.act);
-    float w = apply_act(v.w * cs.sc.w + cs.sh.w, cs.act);
-    if (KIND == 2) { x *= mask; y *= mask; z *= mask; w *= mask; }
-    return make_float4(x, y, z, w);
-}
-
 
 // Transformed weight U[xi][nu] = (G g G^T)[xi][nu], G = [[1, 0], [1, 1], [0, 1]], of the 2x2-tap correlation g of parity class
 // grp (KIND 2) or phase (KIND 1) for input channel c, output column co: taps in increasing input index, float64, rounded once.
@@ -229,19 +187,17 @@ conv_wino2_kernel(const ConvParams P) {
 
     // split-K (small grids): slice z of P.splitk takes the chunks [c_begin, c_end) and writes partial outputs to its own slab
     const int nchunks = P.chunks_per_tap;
-    const int per_split = (nchunks + P.splitk - 1) / P.splitk;
-    const int c_begin = T.z * per_split, c_end = min(nchunks, c_begin + per_split);
-    const int kb_begin = c_begin * NPH, kb_end = c_end * NPH;   // K blocks: (chunk, phase)
-    auto block_src = [&](int kb) { return w2_block_src<KIND>(P, T.n, q, kb); };
-    auto load_a = [&](const W2Src& cs, int j) { return w2_load_halo<KIND>(P, cs, spix[j], ssign, 2 * j, q); };
-    auto store_a = [&](const W2Src& cs, float4 v, int j, float* a) {
-        const float4 u = w2_normalize<KIND>(cs, v, 1.f);
+    const int kb_begin = T.c_begin * NPH, kb_end = T.c_end * NPH;   // K blocks: (chunk, phase)
+    auto block_src = [&](int kb) { return halo_src<NPH>(P, T.n, q, kb); };
+    auto load_a = [&](const HaloSrc& cs, int j) { return w2_load_halo<KIND>(P, cs, spix[j], ssign, 2 * j, q); };
+    auto store_a = [&](const HaloSrc& cs, float4 v, int j, float* a) {
+        const float4 u = normalize4<false>(cs, v);
         a[0] = u.x; a[PLANE] = u.y; a[2 * PLANE] = u.z; a[3 * PLANE] = u.w;
     };
 
     // transformed weights of this column tile: [K step][column half][xi][half][h][32 columns][3 planes]
     const int nsteps = nchunks * NPH * 8;
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.weight_wino), 0, 0x7fffffff, 0x27000);
+    const __amdgpu_buffer_rsrc_t wrsrc = buffer_rsrc(P.weight_wino);
     const unsigned bvoff = (unsigned)(h * 32 + l31) * 12u;
     unsigned bsoff = ((unsigned)T.nt * (unsigned)(nsteps + W2_BDIST) + (unsigned)(kb_begin * 8)) * (unsigned)(W2_STEP_FLOATS * 4) +
                      (unsigned)((T.grp * 3 + xi) * 2) * 768u;
@@ -279,7 +235,7 @@ conv_wino2_kernel(const ConvParams P) {
         for (int g = 0; g < 16; g++) acc[p][g] = 0.0f;
 
     if (kb_begin < kb_end) {
-        const W2Src cs = block_src(kb_begin);
+        const HaloSrc cs = block_src(kb_begin);
 #pragma unroll
         for (int j = 0; j < APT; j++) store_a(cs, load_a(cs, j), j, sd_cur[j]);
     }
@@ -302,7 +258,7 @@ conv_wino2_kernel(const ConvParams P) {
         read_patch(raw[1], rcur, 1);
         auto block_body = [&](auto NEXT, int kb) {
             constexpr bool next_block = decltype(NEXT)::value;
-            const W2Src csn = block_src(next_block ? kb + 1 : kb);
+            const HaloSrc csn = block_src(next_block ? kb + 1 : kb);
             float4 avr[APT];
 #pragma unroll
             for (int s = 0; s < 8; s++) {

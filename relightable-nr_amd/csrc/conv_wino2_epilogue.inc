@@ -89,11 +89,12 @@
     const bool bn = with_stats && P.arrive;
     if (bn) arr = bn_arrive(P, n, tid);
     {
-        // register row g = tile row g >> 2, tile column (g & 3) + 4 h; outputs (2 ty + e, 2 tx + f) of the tile
+        // register row g = tile row g >> 2, tile column (g & 3) + 4 h; outputs (2 ty + e, 2 tx + f) of the tile.
+        // ColumnStore's layout written out: through the struct the transposed kernel's K loop gains four 16-byte scratch accesses
         constexpr int XM = KIND == 2 ? 2 : 1;       // transposed conv: this parity class writes every other pixel
         const int Y00 = XM * (T.y0 + 8 * T.mb) + (KIND == 2 ? T.py : 0), X00 = XM * T.x0 + (KIND == 2 ? T.grp : 0);
         float* base = P.out + (size_t)T.z * P.slab_stride + (((size_t)n * P.OH + Y00) * P.OW + X00) * P.c_out_pad + T.n0;
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x27000);
+        const __amdgpu_buffer_rsrc_t rsrc = buffer_rsrc(base);
         const unsigned cp4 = (unsigned)P.c_out_pad * 4u;
         unsigned voff[2];
 #pragma unroll

@@ -76,20 +76,18 @@ conv_wino2p_kernel(const ConvParams P) {
     }
 
     const int nchunks = P.chunks_per_tap;
-    const int per_split = (nchunks + P.splitk - 1) / P.splitk;
-    const int c_begin = T.z * per_split, c_end = min(nchunks, c_begin + per_split);
-    const int kb_begin = c_begin, kb_end = c_end;               // K blocks: one per chunk
-    auto block_src = [&](int kb) { return w2_block_src<KIND>(P, T.n, q, kb); };
-    auto load_a = [&](const W2Src& cs, int j) { return w2_load_halo<KIND>(P, cs, spix[j], 0u, 0, q); };
-    auto store_a = [&](const W2Src& cs, float4 v, int j, float* a) {
-        const float4 u = w2_normalize<KIND>(cs, v, smask[j]);
+    const int kb_begin = T.c_begin, kb_end = T.c_end;           // K blocks: one per chunk
+    auto block_src = [&](int kb) { return halo_src<1>(P, T.n, q, kb); };
+    auto load_a = [&](const HaloSrc& cs, int j) { return w2_load_halo<KIND>(P, cs, spix[j], 0u, 0, q); };
+    auto store_a = [&](const HaloSrc& cs, float4 v, int j, float* a) {
+        const float4 u = normalize4<true>(cs, v, smask[j]);
         *reinterpret_cast<float2*>(a) = make_float2(u.x, u.z);              // lane half 0: channels 4 q, 4 q + 2 (steps 2 q, 2 q + 1)
         *reinterpret_cast<float2*>(a + PLANE) = make_float2(u.y, u.w);      // lane half 1: channels 4 q + 1, 4 q + 3
     };
 
     // transformed weights of this column tile: [pair][class][xi][h][32 columns][12 = step in pair, column half, plane]
     const int npairs = nchunks * 4;
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.weight_wino), 0, 0x7fffffff, 0x27000);
+    const __amdgpu_buffer_rsrc_t wrsrc = buffer_rsrc(P.weight_wino);
     const unsigned bvoff = (unsigned)(h * 32 + l31) * 48u;
     unsigned bsoff = ((unsigned)T.nt * (unsigned)(npairs + W2P_PAD_PAIRS) + (unsigned)(kb_begin * 4)) * (unsigned)PAIR_BYTES +
                      (unsigned)(T.wgrp * 3 + xi) * 3072u;
@@ -114,7 +112,7 @@ conv_wino2p_kernel(const ConvParams P) {
         for (int g = 0; g < 16; g++) acc[p][g] = 0.0f;
 
     if (kb_begin < kb_end) {
-        const W2Src cs = block_src(kb_begin);
+        const HaloSrc cs = block_src(kb_begin);
 #pragma unroll
         for (int j = 0; j < APT; j++) store_a(cs, load_a(cs, j), j, As + ((sdpack >> (16 * j)) & 0x3fffu));
     }
@@ -162,7 +160,7 @@ conv_wino2p_kernel(const ConvParams P) {
         int nxt_off = CHUNK;                    // offset of the image being staged (wave-uniform): the other image
         auto block_body = [&](auto NEXT, int kb) {
             constexpr bool next_block = decltype(NEXT)::value;
-            const W2Src csn = block_src(next_block ? kb + 1 : kb);
+            const HaloSrc csn = block_src(next_block ? kb + 1 : kb);
             float4 avr[APT];
 #pragma unroll
             for (int pp = 0; pp < 4; pp++) {

@@ -108,13 +108,10 @@ conv_wino4_kernel(const ConvParams P) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nbh = wave / 6, xi = wave - 6 * nbh;          // column half, plane row
     const int l31 = lane & 31, h = lane >> 5;
-    int mt_, nt_, z_;
-    tile_coords(P, mt_, nt_, z_);
+    const ConvTileId T = conv_tile<W4_PW, W4_PH, false>(P);
+    const int nt_ = T.nt, z_ = T.z;
     const int n0 = nt_ * W4_BN + 32 * nbh;                  // first output column of this wave
-    const int tiles_x = P.W / W4_PW, tiles_y = P.H / W4_PH;
-    const int n = mt_ / (tiles_x * tiles_y);
-    const int trem = mt_ - n * (tiles_x * tiles_y);
-    const int y0 = (trem / tiles_x) * W4_PH, x0 = (trem % tiles_x) * W4_PW;
+    const int n = T.n, y0 = T.y0, x0 = T.x0;
 
     // staging item of this thread: (tile row sty, halo column shx, channel quad q); threads past the items stage nothing
     const int q = tid & 3;
@@ -142,31 +139,13 @@ conv_wino4_kernel(const ConvParams P) {
     // [c_begin, c_end) and writes its partial outputs — the output transform is linear — to its own slab; splitk_reduce_kernel
     // adds the slabs and takes the statistics
     const int nchunks = P.chunks_per_tap;
-    const int per_split = (nchunks + P.splitk - 1) / P.splitk;
-    const int c_begin = z_ * per_split, c_end = min(nchunks, c_begin + per_split);
-    struct ChunkSrc { __amdgpu_buffer_rsrc_t rsrc; unsigned C; unsigned soff; int act; float4 sc, sh; const float2* bn; };
+    const int c_begin = T.c_begin, c_end = T.c_end;
+    // the source of a chunk; inside the K loop scale / shift come from the LDS table (bn) and sc / sh are not loaded
+    struct ChunkSrc : HaloSrc { const float2* bn; };
     float2* s_bn = reinterpret_cast<float2*>(As + 2 * W4_CHUNK + W4Stats::BYTES / sizeof(float));    // [padded input channel] (scale, shift), behind the float64 statistics scratch
-    auto chunk_src = [&](int c, bool in_loop) {
-        ChunkSrc cs;
-        const int s = c < P.chunks0 ? 0 : 1;
-        const int cc = (c - (s ? P.chunks0 : 0)) * BK;
-        cs.C = (unsigned)P.src_c[s];
-        cs.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.src_data[s] + (size_t)n * P.H * P.W * cs.C), 0,
-                                                    0x7fffffff, 0x27000);
-        cs.soff = (unsigned)cc * 4u;
-        cs.act = P.src_act[s];
-        cs.sc = make_float4(1.f, 1.f, 1.f, 1.f);
-        cs.sh = make_float4(0.f, 0.f, 0.f, 0.f);
-        cs.bn = s_bn + c * BK + 4 * q;
-        if (!in_loop) {
-            if (P.src_scale[s]) cs.sc = *reinterpret_cast<const float4*>(P.src_scale[s] + (size_t)n * cs.C + cc + 4 * q);
-            if (P.src_shift[s]) cs.sh = *reinterpret_cast<const float4*>(P.src_shift[s] + (size_t)n * cs.C + cc + 4 * q);
-        }
-        return cs;
-    };
+    auto chunk_src = [&](int c, bool in_loop) { return ChunkSrc{halo_src<1>(P, n, q, c, !in_loop), s_bn + c * BK + 4 * q}; };
     auto load_a = [&](const ChunkSrc& cs, int r) {
-        const unsigned voff = (spix_of(r, sdst) * cs.C + 4u * (unsigned)q) * 4u;
-        return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(cs.rsrc, (int)voff, (int)cs.soff, 0));
+        return halo_load(cs, spix_of(r, sdst), q);
     };
     // BatchNorm + activation and the vertical transform of channel k of the quad, 6 LDS stores (one channel per K step)
     auto store_t1 = [&](const ChunkSrc& cs, const float4 (&v)[6], float* buf, auto KC, bool in_loop = false) {
@@ -178,7 +157,7 @@ conv_wino4_kernel(const ConvParams P) {
 #pragma unroll
         for (int r = 0; r < 6; r++) {
             const float x = k == 0 ? v[r].x : k == 1 ? v[r].y : k == 2 ? v[r].z : v[r].w;
-            d[r] = apply_act(x * sc + sh, cs.act);
+            d[r] = normalize1(x, sc, sh, cs.act);
         }
         w4_bt(d, o);
         float* a = buf + (sdst & 0x3fffu) + k * W4_PLANE;
@@ -188,7 +167,7 @@ conv_wino4_kernel(const ConvParams P) {
 
     // transformed weights of this column tile: [K step][xi][half] blocks of 384 floats ([lane = h * 32 + column][planes 0..3], then [lane][planes 4, 5]); the image carries W4_BDIST K
     // steps of padding behind the last one, so the look-ahead needs no clamp
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.weight_wino), 0, 0x7fffffff, 0x27000);
+    const __amdgpu_buffer_rsrc_t wrsrc = buffer_rsrc(P.weight_wino);
     // the 1536-byte block of a wave and K step is [64 lanes][planes 0..3] then [64 lanes][planes 4, 5]: both loads of a K step read
     // consecutive lanes' consecutive bytes (8 + 4 cache lines instead of 12 + 12 at a lane stride of 24 bytes)
     const unsigned bvoff = (unsigned)(h * 32 + l31) * 16u;
@@ -314,16 +293,14 @@ conv_wino4_kernel(const ConvParams P) {
             const int id = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
             const int t2 = id / P.ntiles;
             const int mt2 = t2 % P.mtiles, z2 = t2 / P.mtiles;
-            const int n2 = mt2 / (tiles_x * tiles_y);
-            const int trem2 = mt2 - n2 * (tiles_x * tiles_y);
-            const int y2 = (trem2 / tiles_x) * W4_PH, x2 = (trem2 % tiles_x) * W4_PW;
+            int n2, y2, x2;
+            tile_origin<W4_PW, W4_PH>(P, mt2, n2, y2, x2);
             const int hy = tid / W4_HW, hx = tid - hy * W4_HW;
             const int iy = min(max(y2 - 1 + hy, 0), P.H - 1), ix = min(max(x2 - 1 + hx, 0), P.W - 1);
-            const int c2 = z2 * per_split;
+            const int c2 = split_range(P, z2).begin;
             const int s2 = c2 < P.chunks0 ? 0 : 1;
             const unsigned C2 = (unsigned)P.src_c[s2];
-            const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<float*>(P.src_data[s2] + (size_t)n2 * P.H * P.W * C2), 0, 0x7fffffff, 0x27000);
+            const __amdgpu_buffer_rsrc_t r2 = buffer_rsrc(P.src_data[s2] + (size_t)n2 * P.H * P.W * C2);
             const unsigned pix = (unsigned)(iy * P.W + ix) * C2 * 4u, cb = (unsigned)((c2 - (s2 ? P.chunks0 : 0)) * BK) * 4u;
 #pragma unroll
             for (int j = 0; j < W4_PF_TOUCH; j++)
@@ -411,9 +388,7 @@ conv_wino4_kernel(const ConvParams P) {
     {
         // register row g = tile row g >> 2, tile column (g & 3) + 4 h; outputs (4 ty + a, 4 tx + b) of the tile
         float* base = P.out + (size_t)z_ * P.slab_stride + (((size_t)n * P.OH + y0) * P.OW + x0) * P.c_out_pad + n0;
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x27000);
-        const unsigned cp4 = (unsigned)P.c_out_pad * 4u;
-        const unsigned voff = (n0 + l31 < P.c_out_pad) ? (unsigned)(16 * h) * cp4 + (unsigned)l31 * 4u : 0x7fffffffu;
+        const ColumnStore<1, WINO_OUT_AUX> cst(P, base, n0, 0, l31, 16 * h);
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             if (k >= ng) continue;
@@ -422,10 +397,7 @@ conv_wino4_kernel(const ConvParams P) {
 #pragma unroll
             for (int a = 0; a < 4; a++)
 #pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    const unsigned soff = (unsigned)((4 * tyr + a) * P.OW + 4 * txr + b) * cp4;
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(yv[k][a][b]), rsrc, (int)voff, (int)soff, WINO_OUT_AUX);
-                }
+                for (int b = 0; b < 4; b++) cst.store(yv[k][a][b], 0, (unsigned)((4 * tyr + a) * P.OW + 4 * txr + b));
         }
     }
     if (bn) bn_complete(P, arr, n, tid, W4Stats::flag(red));

@@ -50,63 +50,35 @@ conv_wino80_kernel(const ConvParams P) {
     const int lane = tid & 63;
     const int xi = __builtin_amdgcn_readfirstlane(tid >> 6);        // the wave's plane row
     const int l15 = lane & 15, kq = lane >> 4;
-    int mt_, nt_, z_;
-    tile_coords(P, mt_, nt_, z_);
-    const int tiles_x = P.W / W80_PW, tiles_y = P.H / W80_PH;
-    const int n = mt_ / (tiles_x * tiles_y);
-    const int trem = mt_ - n * (tiles_x * tiles_y);
-    const int y0 = (trem / tiles_x) * W80_PH, x0 = (trem % tiles_x) * W80_PW;
-    if (P.tile_mask && P.tile_mask[mt_] == 0) return;       // workgroup-uniform, before any barrier
+    const ConvTileId T = conv_tile<W80_PW, W80_PH, false>(P);   // one column tile, no split-K: mt alone counts
+    const int n = T.n, y0 = T.y0, x0 = T.x0;
+    if (P.tile_mask && P.tile_mask[T.mt] == 0) return;      // workgroup-uniform, before any barrier
 
-    // halo slots of this thread (slots past the halo wrap to an earlier slot of the same channel quad: duplicate writes of
-    // identical values, no predicate)
+    // halo slots of this thread (wrapped slots are staged twice: no predicate)
     const int q = tid & 3;
     unsigned spix[W80_APT];
     float* sd_cur[W80_APT];
     float* sd_nxt[W80_APT];
 #pragma unroll
     for (int j = 0; j < W80_APT; j++) {
-        int s = tid + CTHREADS * j;
-        if (s >= W80_SLOTS) s -= W80_SLOTS;
-        static_assert(W80_SLOTS % 4 == 0, "the wrapped slot keeps the channel quad");
-        const int hp = s >> 2;
-        const int hy = hp / W80_HW, hx = hp - hy * W80_HW;
-        const int iy = reflect1(y0 - 1 + hy, P.H), ix = reflect1(x0 - 1 + hx, P.W);
-        spix[j] = (unsigned)(iy * P.W + ix);
+        int hy, hx;
+        float m;
+        halo_slot<W80_HW, W80_SLOTS, CTHREADS>(tid, j, hy, hx);
+        spix[j] = halo_pixel<0>(P, y0, x0, hy, hx, m);
         sd_cur[j] = As + (4 * q) * W80_PLANE + q * 8 + hy * WINO_ROWP + hx;      // plane 4 q: w80_plane_off
         sd_nxt[j] = sd_cur[j] + W80_CHUNK;
     }
 
     const int nchunks = P.chunks_per_tap;
-    struct ChunkSrc { __amdgpu_buffer_rsrc_t rsrc; unsigned C; unsigned soff; int act; float4 sc, sh; };
-    auto chunk_src = [&](int c) {
-        ChunkSrc cs;
-        const int s = c < P.chunks0 ? 0 : 1;
-        const int cc = (c - (s ? P.chunks0 : 0)) * BK;
-        cs.C = (unsigned)P.src_c[s];
-        cs.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.src_data[s] + (size_t)n * P.H * P.W * cs.C), 0,
-                                                    0x7fffffff, 0x27000);
-        cs.soff = (unsigned)cc * 4u;
-        cs.act = P.src_act[s];
-        cs.sc = make_float4(1.f, 1.f, 1.f, 1.f);
-        cs.sh = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (P.src_scale[s]) cs.sc = *reinterpret_cast<const float4*>(P.src_scale[s] + (size_t)n * cs.C + cc + 4 * q);
-        if (P.src_shift[s]) cs.sh = *reinterpret_cast<const float4*>(P.src_shift[s] + (size_t)n * cs.C + cc + 4 * q);
-        return cs;
-    };
-    auto load_a = [&](const ChunkSrc& cs, int j) {
-        const unsigned voff = (spix[j] * cs.C + 4u * (unsigned)q) * 4u;
-        return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(cs.rsrc, (int)voff, (int)cs.soff, 0));
-    };
-    auto store_a = [&](const ChunkSrc& cs, float4 v, float* a) {
-        a[0] = apply_act(v.x * cs.sc.x + cs.sh.x, cs.act);
-        a[W80_PLANE] = apply_act(v.y * cs.sc.y + cs.sh.y, cs.act);
-        a[2 * W80_PLANE] = apply_act(v.z * cs.sc.z + cs.sh.z, cs.act);
-        a[3 * W80_PLANE] = apply_act(v.w * cs.sc.w + cs.sh.w, cs.act);
+    auto chunk_src = [&](int c) { return halo_src<1>(P, n, q, c); };
+    auto load_a = [&](const HaloSrc& cs, int j) { return halo_load(cs, spix[j], q); };
+    auto store_a = [&](const HaloSrc& cs, float4 v, float* a) {
+        const float4 u = normalize4<false>(cs, v);
+        a[0] = u.x; a[W80_PLANE] = u.y; a[2 * W80_PLANE] = u.z; a[3 * W80_PLANE] = u.w;
     };
 
     // transformed weights: [K step][xi][column block][k][16 columns][4 planes]: lane-linear 1 KB per (xi, block)
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.weight_wino), 0, 0x7fffffff, 0x27000);
+    const __amdgpu_buffer_rsrc_t wrsrc = buffer_rsrc(P.weight_wino);
     const unsigned bvoff = (unsigned)lane * 16u;
     unsigned bsoff = (unsigned)xi * 5u * 1024u;
     struct BRegs { floatx4 b[5]; };
@@ -148,12 +120,12 @@ conv_wino80_kernel(const ConvParams P) {
         for (int b = 0; b < 5; b++) acc[p][b] = floatx4{0.f, 0.f, 0.f, 0.f};
 
     {
-        const ChunkSrc cs = chunk_src(0);
+        const HaloSrc cs = chunk_src(0);
 #pragma unroll
         for (int j = 0; j < W80_APT; j++) store_a(cs, load_a(cs, j), sd_cur[j]);
     }
     // the halo of chunk c + 1 is fetched during chunk c - 1 (its last two K steps) and stored during chunk c (its first two)
-    ChunkSrc cs_in = chunk_src(nchunks > 1 ? 1 : 0);
+    HaloSrc cs_in = chunk_src(nchunks > 1 ? 1 : 0);
     float4 avr[W80_APT];
 #pragma unroll
     for (int j = 0; j < W80_APT; j++) avr[j] = load_a(cs_in, j);
@@ -169,7 +141,7 @@ conv_wino80_kernel(const ConvParams P) {
 
     auto chunk_body = [&](auto NEXT, int c) {
         constexpr bool next_chunk = decltype(NEXT)::value;
-        const ChunkSrc cs_st = cs_in;                       // chunk c + 1: in flight since the previous chunk
+        const HaloSrc cs_st = cs_in;                       // chunk c + 1: in flight since the previous chunk
         if (next_chunk) cs_in = chunk_src(c + 2 < nchunks ? c + 2 : c + 1);
 #pragma unroll
         for (int s = 0; s < 4; s++) {
@@ -271,7 +243,8 @@ conv_wino80_kernel(const ConvParams P) {
     {
         // this lane's tile for register xi: 4 kq + xi -> tile row kq >> 1, tile column 4 (kq & 1) + xi
         float* base = P.out + (((size_t)n * P.OH + y0) * P.OW + x0) * P.c_out_pad;
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x27000);
+        // (not a ColumnStore: all 80 columns exist, there is no padding column to drop, and a column block is a byte offset)
+        const __amdgpu_buffer_rsrc_t rsrc = buffer_rsrc(base);
         const unsigned cp4 = (unsigned)P.c_out_pad * 4u;
         const unsigned voff = (unsigned)(2 * (kq >> 1) * P.OW + 8 * (kq & 1)) * cp4 + (unsigned)l15 * 4u;
 #pragma unroll
