@@ -233,6 +233,14 @@ def project_vertices(vertices, K, R, t, orig_size, dist_coeffs=None, offset=None
     for x, n in ((dist_coeffs, 'dist_coeffs'), (offset, 'offset'), (scale, 'scale')):
         if x is not None:
             _chk(x, n)
+    # the kernel indexes every one of these by view: one row per view of K, or it reads out of bounds
+    for x, n, per_view in ((K, 'K', 9), (R, 'R', 9), (t, 't', 3), (dist_coeffs, 'dist_coeffs', 5), (offset, 'offset', 2),
+                           (scale, 'scale', 2)):
+        if x is not None and (x.dim() < 2 or x.shape[0] != N or x.numel() != N * per_view):
+            raise ValueError('project_vertices: %s must hold %d values for each of the %d views of K, got shape %s'
+                             % (n, per_view, N, tuple(x.shape)))
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError('project_vertices: vertices must be [nv, 3], got shape %s' % (tuple(vertices.shape),))
     check(L.rnr_project_vertices(_ptr(vertices), _ptr(K), _ptr(R), _ptr(t), _ptr(dist_coeffs), _ptr(offset),
                                  _ptr(scale), _ptr(out), N, nv, float(orig_size), float(eps), _stream()))
     return out
