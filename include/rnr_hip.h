@@ -239,7 +239,15 @@ enum { RNR_CONV3x3_REFLECT = 0, RNR_CONV4x4S2_REFLECT = 1, RNR_CONVT4x4S2 = 2 };
 /* One input source of a convolution: a raw (pre-normalisation) channel-last tensor plus the per-view,
  * per-channel affine + activation the producer's BatchNorm/bias/activation implies:
  *     value(n,h,w,c) = act(scale[n,c] * raw[n,h,w,c] + shift[n,c]).
- * scale/shift NULL = identity.  Two sources = torch.cat([src0, src1], 1) (pytorch_prototyping.py:429). */
+ * scale/shift NULL = identity.  Two sources = torch.cat([src0, src1], 1) (pytorch_prototyping.py:429).
+ * Non-finite values PROPAGATE through every activation: act(v) is computed as max(v, slope * v) with slope 1 / 0.2 / 0, and a NaN
+ * v makes both operands NaN — RNR_ACT_RELU does not turn a NaN into 0, in any kernel family (direct, Winograd, emulated), so a
+ * non-finite raw value (or scale / shift) surfaces in out_raw where "Non-finite inputs" below says
+ * (tests/test_gpu_conv_guard.py; UNetPlan's check_finite = 'first' relies on it).
+ * Alignment of the convolution entry points' operands: the channel-strided tensors (data, scale, shift, out_raw, ray_w, stats,
+ * the packed weight, workspace) are read and written in 16-byte pieces and need 16-byte alignment — what every view n > 0 or row
+ * slice of a channel-last tensor has, its stride being a multiple of 16 channels (64 bytes); gamma, beta, bias, the unpacked
+ * weight and image need their element's 4 bytes, tile_mask none; only `sync` asks for more (256, see rnr_conv2d_fused). */
 typedef struct rnr_conv_src {
     const float* data;  /* [N, H, W, channels] */
     const float* scale; /* [N, channels] or NULL */
@@ -289,7 +297,16 @@ typedef struct rnr_conv_desc {
  * multiples of 64 / 128, masked launches, too few tiles to fill the chip: rnr_conv_algorithm tells) run the direct kernels
  * from the same buffer.  Not combined with the emulation flags.  Non-finite inputs: the data transforms take differences of
  * neighbouring pixels, so an inf / NaN activation reaches every output of the 2 x 2 tiles whose patch contains it (a direct
- * convolution confines it to the outputs whose window contains it). */
+ * convolution confines it to the outputs whose window contains it).  F(2x2, 3x3): tile (t, u) = outputs (2t .. 2t + 1,
+ * 2u .. 2u + 1), patch = the reflection-padded input rows 2t - 1 .. 2t + 2, columns 2u - 1 .. 2u + 2.  F(2x2, 2x2)
+ * (rnr_conv_algorithm 2) works per parity, 3 x 3 patches:
+ *   stride 2: per input parity phase (py, px), tile (t, u) = outputs (2t .. 2t + 1, 2u .. 2u + 1), patch = the padded input
+ *     pixels (2r - py, 2c - px), r = 2t .. 2t + 2, c = 2u .. 2u + 2 (reflected: -1 -> 1, H -> H - 2); an input pixel lies in
+ *     exactly one phase and may reach the tiles whose patch of THAT phase contains it;
+ *   transposed: per output parity class (py, px), tile (t, u) = the outputs (2y + py, 2x + px), y = 2t .. 2t + 1,
+ *     x = 2u .. 2u + 1, patch = the input pixels (2t + py - 1 .. 2t + py + 1, 2u + px - 1 .. 2u + px + 1) inside the map; an
+ *     input pixel may reach, in each of the four classes, the tiles whose patch in that class contains it.
+ * In every case the outputs whose own window contains the pixel DO become non-finite; the rest of those tiles may. */
 #define RNR_CONV_WINOGRAD 8
 /* (with RNR_CONV_WINOGRAD) F(4x4, 3x3) for the 3x3 convolutions whose maps tile into 32 x 16 pixels, whose columns into 64s and
  * whose grid fills the chip: 36 multiplications per 4 x 4 outputs (2.25 per output; F(2x2, 3x3): 4, direct: 9) on the

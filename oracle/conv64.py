@@ -11,6 +11,8 @@ generator of inputs whose convolution is EXACT in float32.
                    divides by 2 and 4) and the bf16x6 / f16x3 operand splits (small dyadic operands sit entirely in the leading
                    term; the f16x3 weight prescale is a power of two) give the same float32 bits: a kernel is compared with
                    conv64(...).float() BITWISE, which no tolerance-based test can do
+  nan_must / nan_may   where ONE non-finite input pixel must / may surface in out_raw (rnr_hip.h, "Non-finite inputs"): boolean
+                   maps from integer index arithmetic alone (tests/test_conv_guard_cpu.py pins them to brute-force loops)
 tests/test_conv_mask_cpu.py pins conv64 to a four-loop numpy convolution, tile_mask64 to a hand-written example and the
 exactness property to torch's float32 convolution.
 """
@@ -88,3 +90,84 @@ def exact_conv_case(rng, kind, N, H, W, cins, c_out):
     shape = (cin, c_out, 4, 4) if kind == 2 else (c_out, cin, 3 if kind == 0 else 4, 3 if kind == 0 else 4)
     weight = torch.from_numpy((rng.integers(-2, 3, size=shape) * 0.125).astype(np.float32))
     return srcs, weight
+
+
+# ---- the footprint of one non-finite input pixel (include/rnr_hip.h, "Non-finite inputs") ----
+# Every footprint below is a union of (set of output rows) x (set of output columns), so the maps are built from 1-D sets.
+
+def _reflect1(i, n):                    # ReflectionPad2d(1)
+    i = -i if i < 0 else i
+    return 2 * n - 2 - i if i >= n else i
+
+
+def _out_size(kind, n):
+    return n if kind == 0 else (n // 2 if kind == 1 else 2 * n)
+
+
+def _must1(kind, n, i):
+    """Output rows (or columns) whose own window contains input row i of n."""
+    o = np.zeros(_out_size(kind, n), bool)
+    for y in range(o.size):
+        if kind == 0:
+            o[y] = any(_reflect1(y - 1 + k, n) == i for k in range(3))
+        elif kind == 1:
+            o[y] = any(_reflect1(2 * y - 1 + k, n) == i for k in range(4))
+        else:
+            o[y] = y in (2 * i - 1, 2 * i, 2 * i + 1, 2 * i + 2)
+    return o
+
+
+def _may1_3x3(n, i, t):
+    """F(t x t, 3x3): the t outputs of every tile whose (t + 2)-pixel patch (reflected at the border) contains input row i."""
+    assert n % t == 0
+    o = np.zeros(n, bool)
+    for tile in range(n // t):
+        if any(_reflect1(t * tile - 1 + k, n) == i for k in range(t + 2)):
+            o[t * tile:t * tile + t] = True
+    return o
+
+
+def _may1_wino2(kind, n, i, p):
+    """F(2x2, 2x2), one input parity phase p (stride 2) resp. output parity class p (transposed): the two outputs of that
+    phase / class of every tile whose 3-pixel patch contains input row i.
+      stride 2:   phase image D_p[r] = pad(in)[2 r - p]; tile t (outputs 2t, 2t + 1) reads D_p[2t .. 2t + 2];
+      transposed: class p, out[2 y + p] = sum_a in[y + p - 1 + a] g[a]; tile t (y = 2t, 2t + 1) reads in[2t + p - 1 .. 2t + p + 1],
+                  zero outside the map."""
+    on = _out_size(kind, n)
+    o = np.zeros(on, bool)
+    if kind == 1:
+        assert on % 2 == 0
+        for t in range(on // 2):
+            if any(_reflect1(2 * (2 * t + k) - p, n) == i for k in range(3)):
+                o[2 * t:2 * t + 2] = True
+    else:
+        assert n % 2 == 0
+        for t in range(n // 2):
+            if 2 * t + p - 1 <= i <= 2 * t + p + 1:
+                o[2 * (2 * t) + p] = o[2 * (2 * t + 1) + p] = True
+    return o
+
+
+def nan_must(kind, H, W, i, j):
+    """bool [Ho, Wo]: the outputs whose own window contains input pixel (i, j) — kind 0: 3x3 under ReflectionPad2d(1), kind 1:
+    4x4 stride 2 under the same pad, kind 2: the outputs 2 i - 1 + k, k = 0..3, inside the map (both axes)."""
+    return np.outer(_must1(kind, H, i), _must1(kind, W, j))
+
+
+def nan_may(kind, algo, H, W, i, j):
+    """bool [Ho, Wo]: the header's bound on where a non-finite input pixel (i, j) may surface under algorithm `algo`
+    (rnr_conv_algorithm): 0 the window (= nan_must); 1 and 3 the 2 x 2 tiles whose 4 x 4 patch contains it; 4 the 4 x 4 tiles
+    whose 6 x 6 patch contains it; 2 the 2 x 2 tiles, per input parity phase (stride 2) resp. per output parity class
+    (transposed), whose 3 x 3 patch in that phase / class contains it."""
+    if algo == 0:
+        return nan_must(kind, H, W, i, j)
+    if algo in (1, 3, 4):
+        assert kind == 0
+        t = 4 if algo == 4 else 2
+        return np.outer(_may1_3x3(H, i, t), _may1_3x3(W, j, t))
+    assert algo == 2 and kind in (1, 2)
+    m = np.zeros((_out_size(kind, H), _out_size(kind, W)), bool)
+    for py in range(2):
+        for px in range(2):
+            m |= np.outer(_may1_wino2(kind, H, i, py), _may1_wino2(kind, W, j, px))
+    return m

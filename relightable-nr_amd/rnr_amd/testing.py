@@ -19,94 +19,212 @@ def conv_desc(kind, cins, c_out, flags=0):
                             pad16(cins[1]) if len(cins) > 1 else 0, c_out, pad16(c_out), flags)
 
 
-def _conv_upload(kind, srcs, weight, c_out, N, H, W, flags):
+# ---- guarded operands: every device operand of a call inside an allocation of its own, [front guard | payload | back guard] ----
+# The kernels address memory through descriptors without bounds, so an index slip reads or overwrites a neighbour instead of
+# faulting.  With guard=True the drivers below carve every operand out of a sentinel-filled allocation, at the weakest alignment
+# the header grants a caller, and report afterwards whether the guards still hold the sentinel.
+SENTINEL = 0x7FC5A5A5           # a quiet NaN as float32 (a pair of them read as float64: 3.04e307), no zero byte
+_SENTINEL_BYTES = tuple(SENTINEL.to_bytes(4, 'little'))
+# payload start as (modulus, residue) of the address
+ALIGN_SYNC = (256, 0)           # rnr_conv2d_fused's sync buffer: 256-byte aligned (rnr_hip.h)
+ALIGN_STRIDED = (128, 64)       # channel-strided tensors: where view n > 0 or a row slice of a channel-last tensor may start
+ALIGN_WORD = (8, 4)             # [c_out] vectors, the unpacked weight, the frame: a float, nothing more
+ALIGN_BYTE = (2, 1)             # the tile mask: bytes
+
+
+def guard_bytes(payload_bytes):
+    """Size of each guard: min(payload, 1 MiB) rounded up to 256 bytes, at least 4 KiB — a one-tile or one-row overrun stays
+    inside the allocation."""
+    return max((min(payload_bytes, 1 << 20) + 255) // 256 * 256, 4096)
+
+
+def _sentinel_bytes(n, phase=0):
+    """n bytes of the repeated sentinel word, starting `phase` bytes into a word (CPU uint8)."""
+    words = torch.tensor(_SENTINEL_BYTES, dtype=torch.uint8).repeat((n + phase + 3) // 4 + 1)
+    return words[phase:phase + n].clone()
+
+
+class Guarded:
+    """One operand: `base` (uint8, on `device`) = [slack | front guard | payload | back guard]; the guards and the slack hold
+    the sentinel word, laid so that whole words start at the payload's first byte."""
+
+    def __init__(self, name, nbytes, align, device, fill='sentinel'):
+        mod, res = align
+        self.name, self.nbytes, self.guard = name, int(nbytes), guard_bytes(nbytes)
+        self.base = torch.empty(mod + 2 * self.guard + self.nbytes, dtype=torch.uint8, device=device)
+        p = self.base.data_ptr() + self.guard
+        self.start = self.guard + (res - p) % mod       # payload offset inside base
+        self.base.copy_(_sentinel_bytes(self.base.numel(), (-self.start) % 4))
+        if fill == 'zero':
+            self.payload().zero_()
+        else:
+            assert fill == 'sentinel'
+
+    def payload(self, dtype=torch.uint8, shape=None):
+        t = self.base[self.start:self.start + self.nbytes].view(dtype)
+        return t if shape is None else t.view(shape)
+
+    def ptr(self):
+        return self.base.data_ptr() + self.start
+
+    def put(self, cpu_tensor):
+        src = cpu_tensor.contiguous()
+        assert src.numel() * src.element_size() == self.nbytes
+        self.payload().copy_(src.view(-1).view(torch.uint8))
+        return self
+
+    def damage(self):
+        """None while both guards are bit-identical to the sentinel, else the offset of the first damaged byte relative to the
+        payload's first byte (negative: front guard; >= nbytes: back guard)."""
+        b = self.base.cpu()
+        for lo, hi in ((self.start - self.guard, self.start), (self.start + self.nbytes, self.start + self.nbytes + self.guard)):
+            bad = (b[lo:hi] != _sentinel_bytes(hi - lo, (lo - self.start) % 4)).nonzero()
+            if bad.numel():
+                return lo + int(bad[0]) - self.start
+        return None
+
+
+def guard_report(operands):
+    """{operand name: None (guards intact) | offset of the first damaged byte relative to the payload}."""
+    return {g.name: g.damage() for g in operands}
+
+
+class _Operands:
+    """Where the drivers get their device tensors: plain torch allocations, or with `guard` one Guarded allocation each."""
+
+    def __init__(self, guard, device=None):
+        self.guard, self.device, self.all = guard, device or DEV, []
+
+    def _carve(self, name, nbytes, align, fill):
+        g = Guarded(name, nbytes, align, self.device, fill)
+        self.all.append(g)
+        return g
+
+    def put(self, name, t, align):
+        """An input: the CPU tensor `t` (None stays None) on the device."""
+        if t is None:
+            return None
+        t = t.contiguous()
+        if not self.guard:
+            return t.to(self.device)
+        return self._carve(name, t.numel() * t.element_size(), align, 'sentinel').put(t).payload(t.dtype, t.shape)
+
+    def new(self, name, shape, dtype, align, fill):
+        """An output or scratch tensor; fill: 'zero', 'nan' (the sentinel when guarded) or 'empty' (the sentinel when guarded)."""
+        if not self.guard:
+            if fill == 'zero':
+                return torch.zeros(shape, dtype=dtype, device=self.device)
+            if fill == 'nan':
+                return torch.full(shape, float('nan'), dtype=dtype, device=self.device)
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        n = 1
+        for s in (shape if isinstance(shape, (tuple, list)) else (shape,)):
+            n *= int(s)
+        nbytes = n * torch.empty((), dtype=dtype).element_size()
+        return self._carve(name, nbytes, align, 'zero' if fill == 'zero' else 'sentinel').payload(dtype, shape)
+
+    def report(self):
+        return guard_report(self.all)
+
+
+def _conv_upload(kind, srcs, weight, c_out, N, H, W, flags, ops=None):
     """srcs: list of (raw NCHW cpu tensor, scale [N,C] or None, shift [N,C] or None, act) -> channel-last device tensors, the
     descriptor and the packed weight.  Returns (L, desc, [rnr_conv_src], packed, tensors to keep alive)."""
     from . import _lib
     from .ops import _ptr, _stream
     L = _lib.load()
+    ops = ops or _Operands(False)
     keep, csrc = [], []
-    for raw, sc, sh, act in srcs:
+    for i, (raw, sc, sh, act) in enumerate(srcs):
         C = raw.shape[1]
         cp = pad16(C)
         d = torch.zeros(N, H, W, cp)
         d[..., :C] = raw.permute(0, 2, 3, 1)
-        d = d.to(DEV)
+        d = ops.put('src%d.data' % i, d, ALIGN_STRIDED)
         scd = shd = None
         if sc is not None:
-            scd = torch.zeros(N, cp); scd[:, :C] = sc; scd = scd.to(DEV)
+            scd = torch.zeros(N, cp); scd[:, :C] = sc; scd = ops.put('src%d.scale' % i, scd, ALIGN_STRIDED)
         if sh is not None:
-            shd = torch.zeros(N, cp); shd[:, :C] = sh; shd = shd.to(DEV)
+            shd = torch.zeros(N, cp); shd[:, :C] = sh; shd = ops.put('src%d.shift' % i, shd, ALIGN_STRIDED)
         keep += [d, scd, shd]
         csrc.append(_lib.RnrConvSrc(d.data_ptr(), scd.data_ptr() if scd is not None else None,
                                     shd.data_ptr() if shd is not None else None, cp, act))
     desc = conv_desc(kind, [raw.shape[1] for raw, _, _, _ in srcs], c_out, flags)
-    packed = torch.empty(L.rnr_packed_weight_floats(ctypes.byref(desc)), device=DEV)
-    wd = weight.contiguous().to(DEV)
+    packed = ops.new('packed', (L.rnr_packed_weight_floats(ctypes.byref(desc)),), torch.float32, ALIGN_STRIDED, 'empty')
+    wd = ops.put('weight', weight, ALIGN_WORD)
     _lib.check(L.rnr_pack_conv_weight(ctypes.byref(desc), _ptr(wd), _ptr(packed), _stream()))
+    keep.append(wd)
     return L, desc, csrc, packed, keep
 
 
-def _conv_out(kind, N, H, W, c_out_pad, out):
+def _conv_out(kind, N, H, W, c_out_pad, out, ops=None):
     """The out_raw buffer of a call: NaN, or the caller's prefill (a CPU tensor of the buffer's shape, float32 or int32 bit
     patterns; copied, so the caller's tensor stays what it was)."""
+    ops = ops or _Operands(False)
     oh, ow = (H, W) if kind == 0 else ((H // 2, W // 2) if kind == 1 else (2 * H, 2 * W))
     if out is None:
-        return torch.full((N, oh, ow, c_out_pad), float('nan'), device=DEV)
+        return ops.new('out_raw', (N, oh, ow, c_out_pad), torch.float32, ALIGN_STRIDED, 'nan')
     assert tuple(out.shape) == (N, oh, ow, c_out_pad) and out.dtype in (torch.float32, torch.int32)
-    return out.to(DEV).view(torch.float32)
+    return ops.put('out_raw', out.view(torch.float32), ALIGN_STRIDED)
 
 
-def _dev_mask(tile_mask):
-    return None if tile_mask is None else torch.as_tensor(tile_mask, dtype=torch.uint8).contiguous().to(DEV)
+def _dev_mask(tile_mask, ops=None):
+    if tile_mask is None:
+        return None
+    return (ops or _Operands(False)).put('tile_mask', torch.as_tensor(tile_mask, dtype=torch.uint8), ALIGN_BYTE)
 
 
-def run_conv(kind, srcs, weight, c_out, N, H, W, flags=0, tile_mask=None, out=None, masked=False, with_stats=None):
+def run_conv(kind, srcs, weight, c_out, N, H, W, flags=0, tile_mask=None, out=None, masked=False, with_stats=None, guard=False):
     """rnr_conv2d, or with `masked` / a `tile_mask` (uint8 per pixel tile, CPU) rnr_conv2d_masked (statistics only when
     `with_stats` asks: that entry point refuses them together with a mask).  Returns (out_raw, stats) as CPU tensors;
-    stats is None when the call took none."""
+    stats is None when the call took none.  guard: every operand guarded (see Guarded; out_raw, workspace and the packed
+    weight are prefilled with the sentinel), and the guard report is returned as a third value."""
     from . import _lib
     from .ops import _ptr, _stream
-    L, desc, csrc, packed, keep = _conv_upload(kind, srcs, weight, c_out, N, H, W, flags)
+    ops = _Operands(guard)
+    L, desc, csrc, packed, keep = _conv_upload(kind, srcs, weight, c_out, N, H, W, flags, ops)
     masked = masked or tile_mask is not None
-    outd = _conv_out(kind, N, H, W, desc.c_out_pad, out)
+    outd = _conv_out(kind, N, H, W, desc.c_out_pad, out, ops)
     if with_stats is None:
         with_stats = not masked
-    stats = torch.zeros(N, desc.c_out_pad, 2, dtype=torch.float64, device=DEV) if with_stats else None
+    stats = ops.new('stats', (N, desc.c_out_pad, 2), torch.float64, ALIGN_STRIDED, 'zero') if with_stats else None
     wsb = L.rnr_conv_workspace_bytes(ctypes.byref(desc), N, H, W)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
+    ws = ops.new('workspace', (wsb,), torch.uint8, ALIGN_STRIDED, 'empty')
     s0, s1 = ctypes.byref(csrc[0]), ctypes.byref(csrc[1]) if len(csrc) > 1 else None
     if masked:
-        mask = _dev_mask(tile_mask)
+        mask = _dev_mask(tile_mask, ops)
         rc = L.rnr_conv2d_masked(ctypes.byref(desc), s0, s1, _ptr(packed), _ptr(outd), _ptr(stats), N, H, W, _ptr(ws), wsb,
                                  _ptr(mask), _stream())
     else:
         rc = L.rnr_conv2d(ctypes.byref(desc), s0, s1, _ptr(packed), _ptr(outd), _ptr(stats), N, H, W, _ptr(ws), wsb, _stream())
     _lib.check(rc)
     torch.cuda.synchronize()
-    return outd.cpu(), stats.cpu() if stats is not None else None
+    res = (outd.cpu(), stats.cpu() if stats is not None else None)
+    return res + (ops.report(),) if guard else res
 
 
 def run_conv_fused(kind, srcs, weight, c_out, N, H, W, gamma=None, beta=None, flags=0, repeats=1, tile_mask=None, out=None,
-                   sync_out=None):
+                   sync_out=None, guard=False):
     """The product entry point rnr_conv2d_fused (convolution + BatchNorm finalise: in the launch, or a launch of its own behind split-K).
     Returns (out_raw, scale, shift, sync buffer) as CPU tensors; `repeats` > 1 re-runs the call on the same sync buffer.
-    tile_mask / out: as in run_conv.  sync_out: a list that receives the sync buffer (CPU) even when the call is refused."""
+    tile_mask / out: as in run_conv.  sync_out: a list that receives the sync buffer (CPU) even when the call is refused.
+    guard: as in run_conv (scale / shift are prefilled with the sentinel too); the guard report is returned as a fifth value."""
     from . import _lib
     from .ops import _ptr, _stream
-    L, desc, csrc, packed, keep = _conv_upload(kind, srcs, weight, c_out, N, H, W, flags)
-    outd = _conv_out(kind, N, H, W, desc.c_out_pad, out)
+    ops = _Operands(guard)
+    L, desc, csrc, packed, keep = _conv_upload(kind, srcs, weight, c_out, N, H, W, flags, ops)
+    outd = _conv_out(kind, N, H, W, desc.c_out_pad, out, ops)
     wsb = L.rnr_conv_workspace_bytes(ctypes.byref(desc), N, H, W)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
-    sync = torch.zeros(L.rnr_conv_sync_bytes(ctypes.byref(desc), N, H, W), dtype=torch.uint8, device=DEV)
-    scale = torch.full((N, desc.c_out_pad), float('nan'), device=DEV)
-    shift = torch.full((N, desc.c_out_pad), float('nan'), device=DEV)
+    ws = ops.new('workspace', (wsb,), torch.uint8, ALIGN_STRIDED, 'empty')
+    sync = ops.new('sync', (L.rnr_conv_sync_bytes(ctypes.byref(desc), N, H, W),), torch.uint8, ALIGN_SYNC, 'zero')
+    scale = ops.new('scale', (N, desc.c_out_pad), torch.float32, ALIGN_STRIDED, 'nan')
+    shift = ops.new('shift', (N, desc.c_out_pad), torch.float32, ALIGN_STRIDED, 'nan')
     cbn = None
     if gamma is not None:
-        g, b = gamma.to(DEV), beta.to(DEV)
+        g, b = ops.put('gamma', gamma, ALIGN_WORD), ops.put('beta', beta, ALIGN_WORD)
         keep += [g, b]
         cbn = _lib.RnrConvBn(g.data_ptr(), b.data_ptr(), scale.data_ptr(), shift.data_ptr(), 1e-5)
-    mask = _dev_mask(tile_mask)
+    mask = _dev_mask(tile_mask, ops)
     try:
         for _ in range(repeats):
             _lib.check(L.rnr_conv2d_fused(ctypes.byref(desc), ctypes.byref(csrc[0]), ctypes.byref(csrc[1]) if len(csrc) > 1 else None,
@@ -116,24 +234,27 @@ def run_conv_fused(kind, srcs, weight, c_out, N, H, W, gamma=None, beta=None, fl
         torch.cuda.synchronize()
         if sync_out is not None:
             sync_out.append(sync.cpu())
-    return outd.cpu(), scale.cpu(), shift.cpu(), sync.cpu()
+    res = (outd.cpu(), scale.cpu(), shift.cpu(), sync.cpu())
+    return res + (ops.report(),) if guard else res
 
 
-def run_conv_ray(srcs, weight, c_out, N, H, W, ray_w, bias, flags=0, tile_mask=None, kind=0):
+def run_conv_ray(srcs, weight, c_out, N, H, W, ray_w, bias, flags=0, tile_mask=None, kind=0, guard=False):
     """rnr_conv2d_ray: the 3x3 out layer whose epilogue writes the frame.  ray_w [N,H,W,c_out_pad] and bias are CPU tensors
     (bias of any length: the test chooses what the kernel may read).  The image is prefilled with NaN; returns it [N,3,H,W] on
-    the CPU.  kind: only 0 has the epilogue, the others are there to be refused."""
+    the CPU.  kind: only 0 has the epilogue, the others are there to be refused.  guard: as in run_conv; returns (image, guard
+    report)."""
     from . import _lib
     from .ops import _ptr, _stream
-    L, desc, csrc, packed, keep = _conv_upload(kind, srcs, weight, c_out, N, H, W, flags)
+    ops = _Operands(guard)
+    L, desc, csrc, packed, keep = _conv_upload(kind, srcs, weight, c_out, N, H, W, flags, ops)
     assert tuple(ray_w.shape) == (N, H, W, desc.c_out_pad)
-    wd, bd = ray_w.contiguous().to(DEV), bias.contiguous().to(DEV)
-    image = torch.full((N, 3, H, W), float('nan'), device=DEV)
-    mask = _dev_mask(tile_mask)
+    wd, bd = ops.put('ray_w', ray_w, ALIGN_STRIDED), ops.put('bias', bias, ALIGN_WORD)
+    image = ops.new('image', (N, 3, H, W), torch.float32, ALIGN_WORD, 'nan')
+    mask = _dev_mask(tile_mask, ops)
     _lib.check(L.rnr_conv2d_ray(ctypes.byref(desc), ctypes.byref(csrc[0]), ctypes.byref(csrc[1]) if len(csrc) > 1 else None,
                                 _ptr(packed), _ptr(wd), _ptr(bd), _ptr(image), N, H, W, _ptr(mask), _stream()))
     torch.cuda.synchronize()
-    return image.cpu()
+    return (image.cpu(), ops.report()) if guard else image.cpu()
 
 
 def conv_active_tiles(desc, alpha, N, H, W, guard=64, fill=0xAA):
