@@ -483,6 +483,34 @@ int rnr_ray_render(const float* unet_raw, int c_out_pad, const float* bias, cons
                    int albedo_diff_ch, int albedo_spec_ch, float* image, int num_views, int height,
                    int width, void* stream);
 
+/*
+ * The frame as the reference script presents it (test_rnr.py:376-393): 8-bit, channel-last, optionally composited over the
+ * light-probe background the object stands in front of (--save_img_bg), in ONE launch behind rnr_ray_render / rnr_conv2d_ray.
+ *   image [N,3,H,W] (may be NULL for RNR_PRESENT_BACKGROUND); alpha [N,H,W], read by RNR_PRESENT_COMPOSITE only;
+ *   proj_inv / R_inv [N,3,3] and lp [lp_h, lp_w, 3] (ONE probe, lp_h, lp_w >= 1, fewer than 2^24 floats): unused by
+ *   RNR_PRESENT_FRAME (may be NULL / 0 there);
+ *   out [N,H,W,3] uint8, row 0 = top as the frame already is; channel order B, G, R (what cv2.imwrite is given,
+ *   test_rnr.py:377), or R, G, B with RNR_PRESENT_RGB or-ed into mode.
+ *     RNR_PRESENT_FRAME       out = q(image)
+ *     RNR_PRESENT_BACKGROUND  out = q(background)
+ *     RNR_PRESENT_COMPOSITE   out = alpha > 0 ? q(image) : q(background)      (a NaN alpha shows the background)
+ *   q(v) = saturate_u8(round_half_even(v * 255.0f)): one float32 product; NaN -> 0, +inf -> 255, -inf -> 0.  This is what
+ *   cv::Mat::convertTo(CV_8U) does to the float array the script hands to imwrite; no test compares with cv2:
+ *   parity with OpenCV is unpinned (as for rnr_resize_area).
+ *   background = rnr_env_background's formula, computed only for the pixels that show it, with the fused path's arithmetic
+ *   (v_rsq normalisation, polynomial atan2 / acos, FMA blend — as rnr_ray_render's env-map taps): within float rounding of
+ *   rnr_env_background (tests/test_gpu_present.py derives the bound), same column on the seam z = +-0, same row at the poles.
+ * out needs no alignment.  When H * W is a multiple of 4, out is 4-byte aligned and the planes the mode reads (image, alpha)
+ * are 16-byte aligned, a thread handles four pixels (float4 loads, 12 bytes stored as three dwords); otherwise one pixel per
+ * thread with byte stores.  The bytes are the same either way.  Errors (unknown mode, a NULL pointer the mode reads, lp_h or
+ * lp_w < 1, sizes <= 0) are reported before any launch.
+ */
+enum { RNR_PRESENT_FRAME = 0, RNR_PRESENT_COMPOSITE = 1, RNR_PRESENT_BACKGROUND = 2 };
+#define RNR_PRESENT_RGB 8            /* or-ed into mode: channel order R,G,B instead of cv2's B,G,R */
+int rnr_present_u8(const float* image, const float* alpha, const float* proj_inv, const float* R_inv,
+                   const float* lp, int lp_h, int lp_w, int mode, uint8_t* out,
+                   int num_views, int height, int width, void* stream);
+
 /* ---- spherical harmonics (sph_harm.py:41-102) ---- */
 
 /* Real orthonormal SH without Condon-Shortley phase, columns (l, m=-l..l); dirs [n,3] (need not be unit),
@@ -514,6 +542,15 @@ int rnr_resize_area(const float* src, float* dst, int src_h, int src_w, int dst_
 /* camera.get_view_dir_map (camera.py:5-32): out_world/out_cam [N,H,W,3] (out_cam may be NULL). */
 int rnr_view_dir_map(const float* proj_inv, const float* R_inv, float* out_world, float* out_cam,
                      int num_views, int height, int width, void* stream);
+
+/* test_rnr.py:386-391 for one probe: out[n,y,x,:] = bilinear(lp[lp_n == 1 ? 0 : n],
+ *   min(u * lp_w, lp_w - 1), min(v * lp_h, lp_h - 1)),  (u, v) = spherical_mapping(-view_dir_world(n, y, x)).
+ * proj_inv / R_inv [N,3,3]; lp [lp_n, lp_h, lp_w, 3], lp_n = 1 or N (lp_h, lp_w >= 1, a probe of fewer than 2^24 floats);
+ * out [N,H,W,3] float32.  The directions are bit-identical to rnr_view_dir_map's out_world; the negation flips the sign bit
+ * (-(+0) = -0 reaches atan2f, which decides the seam by it); atan2f / acosf in the reference's operation order
+ * (render.py:96-102), taps and blend as rnr_interpolate_bilinear. */
+int rnr_env_background(const float* proj_inv, const float* R_inv, const float* lp, int lp_n, int lp_h, int lp_w,
+                       float* out, int num_views, int height, int width, void* stream);
 
 /* render.get_TBN_map (render.py:152-166) given per-face unit tangents: out [N,H,W,3,3], columns (T,B,N). */
 int rnr_tbn_map(const float* normal_map, const int32_t* face_index_map, const float* face_tangents,

@@ -7,6 +7,8 @@
 //                             (render.py:152-166, camera.py:5-45, test_rnr.py:303-356, network.py:67-91,
 //                              network.py:445-472, misc.py:5-42, sph_harm.py:41-71)
 //   ray_render_kernel         out-layer bias + tanh + RayRenderer (network.py:253, 481-527; test_rnr.py:357-359)
+//   present_u8_kernel         the frame as cv2.imwrite gets it: 8-bit, channel-last, over the light-probe background
+//                             (test_rnr.py:377, 386-393)
 //   sh_basis / sh_reconstruct / sh_fit / interpolate_bilinear / layout helpers
 //
 // Built with -ffp-contract=off: the integer tap indices of the bilinear sampler (misc.py:16-25) must be the
@@ -25,6 +27,8 @@
 //   Taps::blend / Taps::blend_fma     four-tap blend, plain | explicit-FMA chain               misc.py:42
 //   level_taps                        taps at the texture-level coordinates u (S-1), (S-1) - v (S-1)   network.py:71-85
 //   envmap_taps, envmap_texels        env-map taps min(u W, W-1); the four texel pointers      network.py:497, misc.py:5-42
+//   background_colour<Norm,Trig,FMA>  the light probe seen along -view_dir of a pixel           test_rnr.py:386-391
+//   quantise_u8                       saturate_u8(round_half_even(v * 255)): the float -> 8-bit conversion of cv2.imwrite
 //   finish_ray_api                    RayRenderer's group means, albedo choice, five stores    network.py:505-527
 //   RayLanes                          32-lanes-per-pixel layout, net_in row staging, alpha of ray_render / ray_weights
 //   view_offset                       view index and in-view offset from the workgroup quotient
@@ -303,6 +307,39 @@ __device__ __forceinline__ void envmap_texels(const float* lp, int lp_w3, const 
     l10 = lp + (r1 + q0);
     l01 = lp + (r0 + q1);
     l11 = lp + (r1 + q1);
+}
+
+// colour of the light probe lp [lp_h, lp_w, 3] behind pixel (row, col) of view n (test_rnr.py:386-391): the env-map taps of
+// (u, v) = spherical_mapping(-view_dir_world).  The negation flips the sign BIT (fneg, not 0 - x): -(+0) = -0 has to reach atan2,
+// which decides the seam by it (see fast_atan2f).  FMA selects Taps::blend_fma
+template <class Norm, class Trig, bool FMA>
+__device__ __forceinline__ void background_colour(const float* proj_inv, const float* R_inv, const float* lp, int lp_h, int lp_w,
+                                                  int n, int row, int col, float& c0, float& c1, float& c2) {
+    float3 dc, vd;
+    view_dir<Norm>(proj_inv, R_inv, n, row, col, dc, vd);
+    const float3 d = f3(-vd.x, -vd.y, -vd.z);
+    const Taps t = envmap_taps(Trig::u(d.z, d.x), Trig::v(d.y), lp_w, lp_h);
+    const float *l00, *l10, *l01, *l11;
+    envmap_texels(lp, lp_w * 3, t, l00, l10, l01, l11);
+    if (FMA) {
+        c0 = t.blend_fma(l00[0], l10[0], l01[0], l11[0]);
+        c1 = t.blend_fma(l00[1], l10[1], l01[1], l11[1]);
+        c2 = t.blend_fma(l00[2], l10[2], l01[2], l11[2]);
+    } else {
+        c0 = t.blend(l00[0], l10[0], l01[0], l11[0]);
+        c1 = t.blend(l00[1], l10[1], l01[1], l11[1]);
+        c2 = t.blend(l00[2], l10[2], l01[2], l11[2]);
+    }
+}
+
+// q(v) = saturate_u8(round_half_even(v * 255)): one float32 product, v_rndne_f32, then the clamp as two selects whose
+// comparisons are false for a NaN: NaN -> 0, +inf -> 255, -inf -> 0 (what cv::Mat::convertTo(CV_8U) does to the float array
+// test_rnr.py:377 hands to cv2.imwrite)
+__device__ __forceinline__ unsigned quantise_u8(float v) {
+    float t = __builtin_rintf(v * 255.0f);
+    t = t > 0.0f ? t : 0.0f;
+    t = t < 255.0f ? t : 255.0f;
+    return (unsigned)t;
 }
 
 constexpr int SH_PIX = 32;        // pixels per workgroup (32 beat 16 / 64 / 128 on the GPU: 17 KB of LDS, 9 workgroups per CU)
@@ -805,6 +842,85 @@ ray_weights_kernel(const RayWeightParams P) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Presenter: the float frame [N,3,H,W] as the 8-bit channel-last image cv2.imwrite makes of it (test_rnr.py:377), composited
+// over the light-probe background of test_rnr.py:386-391 where the mesh is not.  One launch behind the ray stage instead of
+// get_view_dir_map, spherical_mapping_batch, the Interpolater, a where, x255, round, clamp, cast and a channel flip.
+// PIX = 4: a thread owns four consecutive pixels of the flat [N H W] index (H W a multiple of 4, so they share a view, but
+// they may straddle a row: row and column are walked per pixel), reads its planes as three float4 and writes 12 bytes as
+// three dwords.  PIX = 1: one pixel, three byte stores (any H W, any alignment of out).  Memory-bound on foreground pixels
+// (12 + 4 bytes in, 3 out), transcendental-bound on background pixels, whose colour is computed only where it is shown:
+// polynomial atan2 / acos, v_rsq normalisation and the FMA blend, as ray_render_kernel uses for its taps.
+// ------------------------------------------------------------------------------------------------
+struct PresentParams {
+    const float* image; const float* alpha;
+    const float* proj_inv; const float* R_inv;
+    const float* lp; int lp_h, lp_w;
+    int mode, rgb;
+    uint8_t* out;
+    long npix; int H, W;
+};
+
+template <int PIX>      // 4 or 1
+__global__ void __launch_bounds__(256)
+present_u8_kernel(const PresentParams P) {
+    const long pix0 = ((long)blockIdx.x * 256 + threadIdx.x) * PIX;
+    if (pix0 >= P.npix) return;
+    const int hw = P.H * P.W;
+    const int n = (int)(pix0 / hw);
+    const int rem0 = (int)(pix0 - (long)n * hw);
+    float c[3][PIX];
+    bool bg[PIX];
+#pragma unroll
+    for (int k = 0; k < PIX; k++) bg[k] = P.mode == RNR_PRESENT_BACKGROUND;
+    if (P.mode != RNR_PRESENT_BACKGROUND) {
+        const float* plane = P.image + (long)n * 3 * hw + rem0;
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            if constexpr (PIX == 4) {
+                const float4 v = *reinterpret_cast<const float4*>(plane + (long)ch * hw);
+                c[ch][0] = v.x; c[ch][1] = v.y; c[ch][2] = v.z; c[ch][3] = v.w;
+            } else {
+                c[ch][0] = plane[(long)ch * hw];
+            }
+        }
+        if (P.mode == RNR_PRESENT_COMPOSITE) {
+            float a[PIX];
+            if constexpr (PIX == 4) {
+                const float4 v = *reinterpret_cast<const float4*>(P.alpha + pix0);
+                a[0] = v.x; a[1] = v.y; a[2] = v.z; a[3] = v.w;
+            } else {
+                a[0] = P.alpha[pix0];
+            }
+#pragma unroll
+            for (int k = 0; k < PIX; k++) bg[k] = !(a[k] > 0.0f);
+        }
+    }
+    int row = rem0 / P.W, col = rem0 - row * P.W;
+#pragma unroll
+    for (int k = 0; k < PIX; k++) {
+        if (bg[k]) background_colour<NormFast, TrigPoly, true>(P.proj_inv, P.R_inv, P.lp, P.lp_h, P.lp_w, n, row, col, c[0][k], c[1][k], c[2][k]);
+        if (++col == P.W) { col = 0; row++; }
+    }
+    // byte j of a pixel is channel 2 - j (cv2's B, G, R) or channel j (RNR_PRESENT_RGB)
+    unsigned b[3 * PIX];
+#pragma unroll
+    for (int k = 0; k < PIX; k++) {
+        const unsigned q0 = quantise_u8(c[0][k]), q1 = quantise_u8(c[1][k]), q2 = quantise_u8(c[2][k]);
+        b[3 * k + 0] = P.rgb ? q0 : q2;
+        b[3 * k + 1] = q1;
+        b[3 * k + 2] = P.rgb ? q2 : q0;
+    }
+    uint8_t* o = P.out + pix0 * 3;
+    if constexpr (PIX == 4) {
+        unsigned* o4 = reinterpret_cast<unsigned*>(o);      // 12 bytes per thread, 4-byte aligned (rnr_present_u8 checks out)
+#pragma unroll
+        for (int w = 0; w < 3; w++) o4[w] = b[4 * w] | (b[4 * w + 1] << 8) | (b[4 * w + 2] << 16) | (b[4 * w + 3] << 24);
+    } else {
+        o[0] = (uint8_t)b[0]; o[1] = (uint8_t)b[1]; o[2] = (uint8_t)b[2];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // spherical harmonics, float64 internally like the reference's numpy/pyshtools path
 // ------------------------------------------------------------------------------------------------
 constexpr int SH_LMAX_MAX = 16;
@@ -953,6 +1069,21 @@ view_dir_map_kernel(const float* __restrict__ proj_inv, const float* __restrict_
     view_dir<NormExact>(proj_inv, R_inv, n, row, col, dc, vd);
     out_world[pix * 3 + 0] = vd.x; out_world[pix * 3 + 1] = vd.y; out_world[pix * 3 + 2] = vd.z;
     if (out_cam) { out_cam[pix * 3 + 0] = dc.x; out_cam[pix * 3 + 1] = dc.y; out_cam[pix * 3 + 2] = dc.z; }
+}
+
+// test_rnr.py:386-391 for one probe: the background the object stands in front of, [N,H,W,3] float32.  The directions are
+// the bits view_dir_map_kernel writes (same view_dir<NormExact>), the mapping ocml's in the reference's operation order
+__global__ void __launch_bounds__(256)
+env_background_kernel(const float* __restrict__ proj_inv, const float* __restrict__ R_inv, const float* __restrict__ lp,
+                      int lp_n, int lp_h, int lp_w, float* __restrict__ out, long npix, int H, int W) {
+    const long pix = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= npix) return;
+    int n, row, col;
+    pixel_coords(pix, H, W, n, row, col);
+    const float* lpn = lp + (lp_n == 1 ? 0 : (size_t)n * lp_h * lp_w * 3);
+    float c0, c1, c2;
+    background_colour<NormExact, TrigOcml, false>(proj_inv, R_inv, lpn, lp_h, lp_w, n, row, col, c0, c1, c2);
+    out[pix * 3 + 0] = c0; out[pix * 3 + 1] = c1; out[pix * 3 + 2] = c2;
 }
 
 __global__ void __launch_bounds__(256)
@@ -1558,6 +1689,51 @@ extern "C" int rnr_view_dir_map(const float* proj_inv, const float* R_inv, float
     hipLaunchKernelGGL(view_dir_map_kernel, grid256(npix), dim3(256), 0, as_stream(stream),
                        proj_inv, R_inv, out_world, out_cam, npix, height, width);
     return check_launch("view_dir_map_kernel");
+}
+
+// envmap_texels addresses the probe with 24-bit multiplies
+static int probe_checks(const char* fn, int lp_h, int lp_w) {
+    RNR_REQUIRE(lp_h >= 1 && lp_w >= 1, "%s: bad light-probe size %d x %d", fn, lp_h, lp_w);
+    RNR_REQUIRE((long)lp_h * lp_w * 3 < (1L << 24), "%s: light probe %d x %d has 2^24 floats or more (24-bit texel offsets)", fn, lp_h, lp_w);
+    return 0;
+}
+
+extern "C" int rnr_env_background(const float* proj_inv, const float* R_inv, const float* lp, int lp_n, int lp_h, int lp_w,
+                                  float* out, int num_views, int height, int width, void* stream) {
+    RNR_REQUIRE(proj_inv && R_inv && lp && out, "rnr_env_background: null pointer argument");
+    RNR_REQUIRE(num_views > 0 && height > 0 && width > 0 && (long)height * width < (1L << 31), "rnr_env_background: bad sizes");
+    if (int e = probe_checks("rnr_env_background", lp_h, lp_w)) return e;
+    RNR_REQUIRE(lp_n == 1 || lp_n == num_views, "rnr_env_background: lp batch must be 1 or N");
+    const long npix = (long)num_views * height * width;
+    hipLaunchKernelGGL(env_background_kernel, grid256(npix), dim3(256), 0, as_stream(stream), proj_inv, R_inv, lp, lp_n, lp_h,
+                       lp_w, out, npix, height, width);
+    return check_launch("env_background_kernel");
+}
+
+extern "C" int rnr_present_u8(const float* image, const float* alpha, const float* proj_inv, const float* R_inv,
+                              const float* lp, int lp_h, int lp_w, int mode, uint8_t* out, int num_views, int height, int width,
+                              void* stream) {
+    const int m = mode & ~RNR_PRESENT_RGB;
+    RNR_REQUIRE(m == RNR_PRESENT_FRAME || m == RNR_PRESENT_COMPOSITE || m == RNR_PRESENT_BACKGROUND, "rnr_present_u8: unknown mode %d", mode);
+    RNR_REQUIRE(out, "rnr_present_u8: null pointer argument (out)");
+    RNR_REQUIRE(m == RNR_PRESENT_BACKGROUND || image, "rnr_present_u8: null pointer argument (image)");
+    RNR_REQUIRE(m != RNR_PRESENT_COMPOSITE || alpha, "rnr_present_u8: null pointer argument (alpha)");
+    RNR_REQUIRE(num_views > 0 && height > 0 && width > 0 && (long)height * width < (1L << 31), "rnr_present_u8: bad sizes");
+    if (m != RNR_PRESENT_FRAME) {
+        RNR_REQUIRE(proj_inv && R_inv && lp, "rnr_present_u8: null pointer argument (proj_inv, R_inv, lp)");
+        if (int e = probe_checks("rnr_present_u8", lp_h, lp_w)) return e;
+    }
+    PresentParams P;
+    P.image = image; P.alpha = alpha; P.proj_inv = proj_inv; P.R_inv = R_inv; P.lp = lp; P.lp_h = lp_h; P.lp_w = lp_w;
+    P.mode = m; P.rgb = (mode & RNR_PRESENT_RGB) ? 1 : 0; P.out = out;
+    P.npix = (long)num_views * height * width; P.H = height; P.W = width;
+    // four pixels per thread: whole groups inside a view, dword stores, float4 loads of the planes the mode reads
+    const bool vec = ((long)height * width) % 4 == 0 && (uintptr_t)out % 4 == 0 &&
+                     (m == RNR_PRESENT_BACKGROUND || (uintptr_t)image % 16 == 0) &&
+                     (m != RNR_PRESENT_COMPOSITE || (uintptr_t)alpha % 16 == 0);
+    if (vec) hipLaunchKernelGGL(present_u8_kernel<4>, grid256(P.npix / 4), dim3(256), 0, as_stream(stream), P);
+    else hipLaunchKernelGGL(present_u8_kernel<1>, grid256(P.npix), dim3(256), 0, as_stream(stream), P);
+    return check_launch("present_u8_kernel");
 }
 
 extern "C" int rnr_tbn_map(const float* normal_map, const int32_t* face_index_map, const float* face_tangents,

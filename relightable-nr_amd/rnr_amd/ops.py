@@ -405,6 +405,59 @@ def ray_weights(net_in, alpha, lp, num_spec, num_diff, c_w, albedo_diff_ch=0, al
     return out
 
 
+@_device_op
+def present_u8(image, alpha, proj_inv, R_inv, lp, mode='frame', rgb=False, out=None, img_hw=None):
+    """The frame as test_rnr.py:376-393 presents it (rnr_present_u8): [N,H,W,3] uint8, B,G,R (cv2's order) or R,G,B (rgb=True).
+    mode 'frame': q(image); 'background': q(the light probe seen along -view_dir); 'composite': the frame where alpha > 0, the
+    background elsewhere.  q(v) = saturate(round_half_even(v * 255)).  image [N,3,H,W] (None allowed for 'background': the size
+    then comes from alpha, out or img_hw); alpha [N,H,W] ('composite' only); proj_inv / R_inv [N,3,3] and lp [Hl,Wl,3] or
+    [1,Hl,Wl,3] (not read by 'frame': may be None).  out: any contiguous uint8 [N,H,W,3] view, no alignment needed."""
+    L = _lib.load()
+    if mode not in _lib.PRESENT_MODES:
+        raise ValueError("present_u8: mode must be 'frame', 'composite' or 'background', got %r" % (mode,))
+    m = _lib.PRESENT_MODES[mode]
+    if image is None and mode != 'background':
+        raise ValueError("present_u8: mode %r needs the frame" % mode)
+    if image is not None:
+        _chk(image, 'image')
+        if image.dim() != 4 or image.shape[1] != 3:
+            raise ValueError('present_u8: image must be [N,3,H,W], got %s' % (tuple(image.shape),))
+        N, H, W = image.shape[0], image.shape[2], image.shape[3]
+    elif alpha is not None:
+        N, H, W = alpha.shape
+    elif out is not None:
+        N, H, W = out.shape[:3]
+    elif img_hw is not None and proj_inv is not None:
+        N, H, W = proj_inv.shape[0], int(img_hw[0]), int(img_hw[1])
+    else:
+        raise ValueError("present_u8: mode 'background' without a frame needs alpha, out or img_hw for the size")
+    lp3 = None
+    if mode == 'composite':
+        _chk(alpha, 'alpha')
+        if tuple(alpha.shape) != (N, H, W):
+            raise ValueError('present_u8: alpha must be [%d,%d,%d], got %s' % (N, H, W, tuple(alpha.shape)))
+    if mode != 'frame':
+        _chk(proj_inv, 'proj_inv'); _chk(R_inv, 'R_inv'); _chk(lp, 'lp')
+        # the kernel indexes both by view: one 3x3 per view, or it reads out of bounds
+        if tuple(proj_inv.shape) != (N, 3, 3) or tuple(R_inv.shape) != (N, 3, 3):
+            raise ValueError('present_u8: proj_inv and R_inv must be [%d,3,3], got %s, %s' % (N, tuple(proj_inv.shape), tuple(R_inv.shape)))
+        if lp.dim() < 3 or lp.shape[-1] != 3 or lp.numel() != lp.shape[-3] * lp.shape[-2] * 3:
+            raise ValueError('present_u8: lp must be one [Hl,Wl,3] probe, got %s' % (tuple(lp.shape),))
+        lp3 = lp.reshape(lp.shape[-3], lp.shape[-2], 3)
+    dev = (image if image is not None else proj_inv if proj_inv is not None else out).device
+    if out is None:
+        out = torch.empty(N, H, W, 3, dtype=torch.uint8, device=dev)
+    else:
+        _chk(out, 'out', torch.uint8)
+        if tuple(out.shape) != (N, H, W, 3):
+            raise ValueError('present_u8: out must be [%d,%d,%d,3], got %s' % (N, H, W, tuple(out.shape)))
+    on = mode != 'frame'
+    check(L.rnr_present_u8(_ptr(image), _ptr(alpha if mode == 'composite' else None), _ptr(proj_inv if on else None),
+                           _ptr(R_inv if on else None), _ptr(lp3), lp3.shape[0] if on else 0, lp3.shape[1] if on else 0,
+                           m | (_lib.PRESENT_RGB if rgb else 0), _ptr(out), N, H, W, _stream()))
+    return out
+
+
 def calibrate_mfma_f32(device='cuda:0', seconds=0.1, waves_per_simd=2):
     """TFLOP/s this device sustains NOW in a register-resident v_mfma_f32_32x32x2_f32 loop on every SIMD
     (rnr_calibrate_mfma_f32; nominal 157.3): a probe call sizes the loop for about `seconds`.  Blocks."""
@@ -514,6 +567,29 @@ def view_dir_map(img_hw, proj_inv, R_inv):
     cam = torch.empty_like(world)
     check(L.rnr_view_dir_map(_ptr(proj_inv), _ptr(R_inv), _ptr(world), _ptr(cam), N, H, W, _stream()))
     return world, cam
+
+
+@_device_op
+def env_background(proj_inv, R_inv, lp, img_hw, out=None):
+    """The background of test_rnr.py:386-391 for one probe (rnr_env_background): the light probe lp [Hl,Wl,3] or [lp_n,Hl,Wl,3]
+    (lp_n = 1 or N) sampled along -view_dir of every pixel -> [N,H,W,3] float32, i.e. what get_view_dir_map ->
+    spherical_mapping_batch -> clamp -> Interpolater compute, in one launch (img_bg_sh / img_bg_lp by the probe given)."""
+    L = _lib.load()
+    _chk(proj_inv, 'proj_inv'); _chk(R_inv, 'R_inv'); _chk(lp, 'lp')
+    N, H, W = proj_inv.shape[0], int(img_hw[0]), int(img_hw[1])
+    if tuple(proj_inv.shape) != (N, 3, 3) or tuple(R_inv.shape) != (N, 3, 3):
+        raise ValueError('env_background: proj_inv and R_inv must be [N,3,3], got %s, %s' % (tuple(proj_inv.shape), tuple(R_inv.shape)))
+    if lp.dim() not in (3, 4) or lp.shape[-1] != 3:
+        raise ValueError('env_background: lp must be [Hl,Wl,3] or [lp_n,Hl,Wl,3], got %s' % (tuple(lp.shape),))
+    lp_n = 1 if lp.dim() == 3 else lp.shape[0]
+    if out is None:
+        out = torch.empty(N, H, W, 3, dtype=torch.float32, device=proj_inv.device)
+    else:
+        _chk(out, 'out')
+        if tuple(out.shape) != (N, H, W, 3):
+            raise ValueError('env_background: out must be [%d,%d,%d,3], got %s' % (N, H, W, tuple(out.shape)))
+    check(L.rnr_env_background(_ptr(proj_inv), _ptr(R_inv), _ptr(lp), lp_n, lp.shape[-3], lp.shape[-2], _ptr(out), N, H, W, _stream()))
+    return out
 
 
 @_device_op

@@ -16,6 +16,9 @@ Calling modes:
                                         the rasterizer and shading kernels of view i+1 and the tails of every short
                                         convolution launch run under the U-Net of view i.  submit() returns a FrameHandle;
                                         handle.wait() orders the current stream behind that frame.
+    RNRPipeline(present='composite')    every mode above also leaves the frame as the script saves it (test_rnr.py:376-393):
+                                        [N,S,S,3] uint8 over the light-probe background, one more launch behind the ray stage
+                                        (`pipeline.presented`, `FrameHandle.u8`); render() / submit() still return the floats.
 """
 import numpy as np
 import torch
@@ -25,10 +28,11 @@ from .unet import UNetPlan
 
 
 class FrameHandle:
-    """A frame submitted with RNRPipeline.submit: `image` [N,3,S,S] is complete once `event` has passed."""
+    """A frame submitted with RNRPipeline.submit: `image` [N,3,S,S] is complete once `event` has passed, and so is `u8`
+    [N,S,S,3] uint8 (RNRPipeline(present=...); None otherwise): read it after wait() / synchronize().  Same lifetime as `image`."""
 
-    def __init__(self, image, event):
-        self.image, self.event = image, event
+    def __init__(self, image, event, u8=None):
+        self.image, self.event, self.u8 = image, event, u8
 
     def wait(self):
         """Order the current HIP stream behind the frame (no host synchronisation) and return the image."""
@@ -48,7 +52,7 @@ class RNRPipeline:
     def __init__(self, mesh, img_size, textures, unet_state_dict, pivots_spec, pivots_diff, lp, nf0, num_down=5,
                  sh_start_ch=6, max_views=1, device='cuda:0', near=0.0, far=1e5, global_RT=None, sh_coeff=None, sh_lmax=10,
                  skip_background_tiles=True, streams=1, precision='f32', inflight=1, fuse_ray=False,
-                 conv_algo=None):
+                 conv_algo=None, present=None, background_probe=None, present_rgb=False):
         """
         mesh: dict v/vt/vn/f_v_idx/f_vt_idx/f_vn_idx (numpy or torch; global_RT applied here if given, as
               network.Rasterizer.__init__ does, network.py:126-128)
@@ -58,6 +62,12 @@ class RNRPipeline:
         lp: environment map [1,Hl,Wl,3] or [Hl,Wl,3] (LightingSH.reconstruct_lp output); may be None when
             sh_coeff [L,(lmax+1)^2,3] is given: then the probe is reconstructed from the coefficients on every call
             (like `lighting_model(lighting_idx, is_lp=True)` inside RayRenderer.forward, network.py:494-495)
+        present: None (no 8-bit output: no launch, no buffer), 'frame' (the frame as cv2.imwrite gets it, test_rnr.py:377) or
+            'composite' (that over the background of test_rnr.py:386-393 wherever alpha is 0): ops.present_u8 behind the ray
+            stage of every view group / call in flight.  The bytes of the last call: `self.presented` [N,S,S,3] uint8, B,G,R
+            (R,G,B with present_rgb), valid as long as the float frame it belongs to.
+        background_probe: [Hl,Wl,3] probe shown by 'composite' instead of the one the frame was lit with — LightingLP's
+            full-resolution probe (img_bg_lp) for a sharp background under smooth SH lighting (default: img_bg_sh).
         """
         self.dev = torch.device(device)
         # fuse_ray: the ray renderer split in two — ops.ray_weights (everything that does not depend on the U-Net) and the out
@@ -67,6 +77,14 @@ class RNRPipeline:
         # the ray renderer outputs exactly 0 on background pixels whatever the U-Net produced there (network.py:469-470,
         # 497): the out layer need not compute pixel tiles that contain no foreground pixel.  Frames are bit-identical.
         self.skip_background_tiles = bool(skip_background_tiles)
+        if present not in (None, 'frame', 'composite'):
+            raise ValueError("present must be None, 'frame' or 'composite', got %r" % (present,))
+        self.present, self.present_rgb = present, bool(present_rgb)
+        self.background_probe = None
+        if background_probe is not None:
+            bp = torch.as_tensor(background_probe, dtype=torch.float32)
+            self.background_probe = bp.reshape(bp.shape[-3], bp.shape[-2], 3).contiguous().to(self.dev)
+        self.presented = None
         # streams > 1: a batch is split into that many view groups rendered on separate HIP streams, so that the tail of
         # one group's kernel overlaps the next kernel of another group (+2 % at 8 views)
         self.n_streams = max(1, int(streams))
@@ -112,6 +130,8 @@ class RNRPipeline:
         self._net_in = torch.empty(N, S, S, self.unet.in_c_pad, dtype=torch.float32, device=self.dev)
         # two frame buffers: a caller that overlaps the all-gather of step k with the rendering of step k+1 alternates
         self._images = [torch.empty(N, 3, S, S, dtype=torch.float32, device=self.dev) for _ in range(2)]
+        # ... and their 8-bit companions (present=...): same alternation, same lifetime
+        self._u8 = [torch.empty(N, S, S, 3, dtype=torch.uint8, device=self.dev) if self.present else None for _ in range(2)]
         self._flip = 0
         ws_views = N if self.n_streams == 1 else (N + self.n_streams - 1) // self.n_streams
         self._lane_ws = [torch.empty(ops._lib.load().rnr_gbuffer_workspace_bytes(ws_views, self.mesh.num_faces, S),
@@ -137,6 +157,7 @@ class RNRPipeline:
             sl.gb = self._gb if i == 0 else {m: torch.empty_like(t) for m, t in self._gb.items()}
             sl.net_in = self._net_in if i == 0 else torch.empty_like(self._net_in)
             sl.images = [torch.empty(N, 3, S, S, dtype=torch.float32, device=self.dev) for _ in range(2)]
+            sl.u8 = [torch.empty(N, S, S, 3, dtype=torch.uint8, device=self.dev) if self.present else None for _ in range(2)]
             sl.flip = 0
             self._slots.append(sl)
 
@@ -169,7 +190,7 @@ class RNRPipeline:
 
     def render(self, proj, pose, proj_inv, R_inv, keep_intermediates=False, lighting_idx=0, stage_events=None, v_uvz=None):
         """proj/proj_inv/R_inv [N,3,3], pose [N,4,4] device float32 -> image [N,3,S,S].  The result is a view into one of
-        two internal buffers used alternately: it stays valid until the call after next.
+        two internal buffers used alternately: it stays valid until the call after next (and so does `self.presented`).
         stage_events: optional list; (name, torch.cuda.Event) pairs are appended at the stage boundaries
         (measurement only — bench.py's per-stage HBM figures).
         v_uvz: optional [N,nv,3] projected NDC vertices (u, v, z_cam) to rasterize INSTEAD of projecting `proj` / `pose`
@@ -192,7 +213,7 @@ class RNRPipeline:
                 image = self._render(proj, pose, proj_inv, R_inv, False, lighting_idx, None)
                 ev = torch.cuda.Event()
                 ev.record()
-                return FrameHandle(image, ev)
+                return FrameHandle(image, ev, self.presented)
             N = proj.shape[0]
             if N > self.max_views:
                 raise RuntimeError('pipeline built for max_views=%d, got %d poses' % (self.max_views, N))
@@ -204,16 +225,18 @@ class RNRPipeline:
                 # launch (ops.frame_prepare inside _render_group), outputs private to the slot
                 lp = self.lp if self.sh_lighting is None else ('sh', lighting_idx)
                 image = sl.images[sl.flip][:N]
+                u8 = sl.u8[sl.flip][:N] if self.present else None
                 sl.flip ^= 1
                 args = [t.contiguous() for t in (proj, pose, proj_inv, R_inv)]
                 for t in args:
                     # the caller's tensors are read by kernels of THIS stream: tell the caching allocator, or a caller that
                     # drops its pose tensors right after submit() gets their memory recycled under the running kernels
                     t.record_stream(sl.stream)
-                self._render_group(0, 0, N, *args, lp, image, lambda name: None, slot=sl, fused=True)
+                self._render_group(0, 0, N, *args, lp, image, lambda name: None, slot=sl, fused=True, u8=u8)
                 ev = torch.cuda.Event()
                 ev.record(sl.stream)
-            return FrameHandle(image, ev)
+            self.presented = u8
+            return FrameHandle(image, ev, u8)
 
     def _render(self, proj, pose, proj_inv, R_inv, keep_intermediates, lighting_idx, stage_events):
 
@@ -228,6 +251,8 @@ class RNRPipeline:
             raise RuntimeError('pipeline built for max_views=%d, got %d poses' % (self.max_views, N))
         proj, pose, proj_inv, R_inv = proj.contiguous(), pose.contiguous(), proj_inv.contiguous(), R_inv.contiguous()
         image = self._images[self._flip][:N]
+        u8 = self._u8[self._flip][:N] if self.present else None
+        self.presented = u8
         self._flip ^= 1
         lanes = 1 if (stage_events is not None or keep_intermediates or self._v_uvz_override is not None) else min(self.n_streams, N)
         fused = lanes == 1 and self._v_uvz_override is None
@@ -243,7 +268,7 @@ class RNRPipeline:
             if N > self._lane_unets[0].N:
                 raise RuntimeError('pipeline built with streams=%d: a single-stream call takes at most %d poses'
                                    % (self.n_streams, self._lane_unets[0].N))
-            inter = self._render_group(0, 0, N, proj, pose, proj_inv, R_inv, lp, image, mark, fused=fused)
+            inter = self._render_group(0, 0, N, proj, pose, proj_inv, R_inv, lp, image, mark, fused=fused, u8=u8)
             if keep_intermediates:
                 self.last = inter
             return image
@@ -257,14 +282,14 @@ class RNRPipeline:
             st = self._lane_streams[i]
             st.wait_stream(cur)
             with torch.cuda.stream(st):
-                self._render_group(i, lo, hi, proj, pose, proj_inv, R_inv, lp, image, lambda name: None)
+                self._render_group(i, lo, hi, proj, pose, proj_inv, R_inv, lp, image, lambda name: None, u8=u8)
         for st in self._lane_streams[:lanes]:
             cur.wait_stream(st)
         return image
 
-    def _render_group(self, lane, lo, hi, proj, pose, proj_inv, R_inv, lp, image, mark, slot=None, fused=False):
+    def _render_group(self, lane, lo, hi, proj, pose, proj_inv, R_inv, lp, image, mark, slot=None, fused=False, u8=None):
         """Views [lo, hi) of the batch on the current stream, with lane-private scratch and U-Net activations (or, for a
-        submitted call, everything private to its slot)."""
+        submitted call, everything private to its slot).  u8: the batch's [N,S,S,3] uint8 buffer (present=...) or None."""
         n = hi - lo
         unet = self._lane_unets[lane] if slot is None else slot.unet
         gbufs = self._gb if slot is None else slot.gb
@@ -310,4 +335,11 @@ class RNRPipeline:
             ops.ray_render(raw, unet.out_bias, sh['net_in'], gb['alpha'], lp, self.n_spec, self.n_diff, albedo_diff_ch=0,
                            albedo_spec_ch=3, image=image[lo:hi])
             mark('ray_render')
+        if u8 is not None:
+            # the probe the frame was lit with (img_bg_sh: with SH lighting the one frame_prepare reconstructed for this call)
+            # unless a background probe was given (img_bg_lp)
+            ops.present_u8(image[lo:hi], gb['alpha'], proj_inv[lo:hi], R_inv[lo:hi],
+                           lp if self.background_probe is None else self.background_probe, mode=self.present,
+                           rgb=self.present_rgb, out=u8[lo:hi])
+            mark('present')
         return {'v_uvz': v_uvz, 'gb': gb, 'net_in': sh['net_in'], 'unet_raw': raw}
