@@ -318,6 +318,18 @@ typedef struct rnr_conv_desc {
  * (F(2x2, .): 2 x 2 tiles of a 4 x 4 patch; direct: the outputs whose window contains it).  The F(4x4, 3x3) weight image is stored behind the F(2x2, 3x3) one (both flags when packing AND
  * convolving); shapes it does not cover run F(2x2, 3x3) / direct from the same buffer.  rnr_conv_algorithm reports 4. */
 #define RNR_CONV_WINOGRAD4 16
+/* (with RNR_CONV_WINOGRAD) F(4x4, 2x2) for the transposed 4x4 stride-2 convolutions whose input maps tile into 32 x 16 pixels,
+ * whose columns into 64s, whose input channels (both sources, padded) number at most 1024 and whose grid fills the chip: every
+ * output parity class as 25 multiplications per 4 x 4 outputs (1.5625 per output; F(2x2, 2x2): 2.25, direct: 4) on the
+ * interpolation points (0, +-3/4, 2, inf).  A flag of its own for the same reason as RNR_CONV_WINOGRAD4: the larger transforms round more
+ * (a float32 study of the point set: rms error ~3.8 x the direct form's, F(2x2, 2x2) 2.3 x, scripts/experiments/winograd_accuracy_study.py);
+ * the kernel measures 2.5 x the direct kernels' rms error and 2.5 x F(2x2, 2x2)'s on the U-Net's transposed layer shapes, at most 7.1e-6 of
+ * the output peak against a float64 convolution (profiles/r07_winograd_f4x4_2x2_accuracy.txt; tests bound it at 1e-4).
+ * Non-finite inputs: an inf / NaN activation reaches, in each parity class, every output of the 4 x 4 tiles whose 5 x 5 input
+ * patch contains it.  The 25-plane weight image is stored behind the F(2x2, 2x2) one (both flags when packing AND convolving);
+ * shapes it does not cover run F(2x2, 2x2) / direct from the same buffer.  rnr_conv_algorithm reports 2 for both forms (Winograd on
+ * the 2x2-tap decomposition); rnr_conv_winograd_tile tells them apart (4 / 2). */
+#define RNR_CONV_WINOGRAD42 32
 
 /* Floats in the packed weight of `d` ([taps][c_in0_pad + c_in1_pad][c_out_pad], x4 parity classes for convT). */
 size_t rnr_packed_weight_floats(const rnr_conv_desc* d);
@@ -327,10 +339,15 @@ int rnr_pack_conv_weight(const rnr_conv_desc* d, const float* weight, float* pac
 
 /* Which algorithm rnr_conv2d* runs for (desc, N, input H, input W): 0 = direct implicit GEMM, 1 = Winograd F(2x2, 3x3),
  * 3 = the same for the 80-column out layer (16 x 16 x 4 MFMA tiles), 2 = Winograd F(2x2, 2x2) (16 multiplications per 2 x 2
- * outputs instead of 36, resp. 9 instead of 16), 4 = Winograd F(4x4, 3x3) (RNR_CONV_WINOGRAD4); -1 = bad arguments.
+ * outputs instead of 36, resp. 9 instead of 16; with RNR_CONV_WINOGRAD42 the transposed convolution may run F(4x4, 2x2) under the
+ * same code: rnr_conv_winograd_tile), 4 = Winograd F(4x4, 3x3) (RNR_CONV_WINOGRAD4); -1 = bad arguments.
  * Non-zero only with RNR_CONV_WINOGRAD in desc->flags.
  * Masked launches (tile_mask != NULL) run 0 unless the plan is 3; rnr_conv2d_ray always runs 0. */
 int rnr_conv_algorithm(const rnr_conv_desc* d, int num_views, int in_h, int in_w);
+/* The output tile edge m of the Winograd algorithm F(m x m, r x r) that rnr_conv2d* runs for the same call: 0 = direct, 2 = F(2x2, 3x3)
+ * / F(2x2, 2x2), 4 = F(4x4, 3x3) / F(4x4, 2x2); -1 = bad arguments.  Multiplications per output and tap set follow from it: (m + r - 1)^2
+ * per m^2 outputs with r = 3 for the 3x3 convolution and r = 2 for the 2x2-tap correlations of the 4x4 stride-2 ones. */
+int rnr_conv_winograd_tile(const rnr_conv_desc* d, int num_views, int in_h, int in_w);
 
 /* Scratch bytes rnr_conv2d may need for (desc, N, input H, input W) (split-K partial slabs). */
 size_t rnr_conv_workspace_bytes(const rnr_conv_desc* d, int num_views, int in_h, int in_w);

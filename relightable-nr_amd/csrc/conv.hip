@@ -20,7 +20,8 @@
 // the small maps), conv_halo_emu_kernel (opt-in: fp32 emulated on the 16-bit matrix cores, RNR_CONV_F32_EMU_BF16X6 / _F16X3), and — the
 // product path since r03, RNR_CONV_WINOGRAD — the fp32 Winograd kernels of conv_wino.inc (F(2x2, 3x3): conv_wino_kernel),
 // conv_wino80.inc (the 80-column out layer), conv_wino2.inc / conv_wino2p.inc (F(2x2, 2x2): conv_wino2_kernel<1> for the
-// stride-2 convolution, conv_wino2p_kernel<2> for the transposed one) and conv_wino4.inc (F(4x4, 3x3), RNR_CONV_WINOGRAD4).
+// stride-2 convolution, conv_wino2p_kernel<2> for the transposed one), conv_wino4.inc (F(4x4, 3x3), RNR_CONV_WINOGRAD4) and
+// conv_wino42p.inc (F(4x4, 2x2) for the transposed convolution, RNR_CONV_WINOGRAD42).
 // Device side, shared: conv_stage.inc states tile decode, halo source / slot / prologue and the output-store preamble once for all of them.
 // Host side: CONV_TILES lists every instantiation of these kernels with its tile shape and launcher; plan_conv() tries the
 // candidates (try_wino80 ... try_gather) in priority order and returns the row, the grid and the split-K depth of one call.
@@ -76,6 +77,9 @@ constexpr int CTHREADS = 256;
 #ifndef RNR_WINO4_MIN_WGS
 #define RNR_WINO4_MIN_WGS 256        // fewer 32 x 16 pixel x 64 column tiles than this (one 12-wave workgroup per CU): F(2x2, 3x3)
 #endif
+#ifndef RNR_WINO42_MIN_WGS
+#define RNR_WINO42_MIN_WGS 256       // fewer (32 x 16 class positions x 64 columns x parity class) workgroups than this, one per CU: F(2x2, 2x2)
+#endif
 #ifndef RNR_WINO_MIN_WGS
 #define RNR_WINO_MIN_WGS 256         // fewer 16 x 8 pixel x 64 column tiles than this: the direct kernels (they split K)
 #endif
@@ -86,6 +90,7 @@ struct ConvTuning {
     int splitk_below, splitk_target;        // direct kernels: grids below `below` workgroups are split over K towards `target`
     int cfg4_max, cfg0_small_max;           // direct kernels: the 128 x 64 tiles (try_halo)
     int wino_min_wgs, wino2_min_wgs, wino4_min_wgs;     // smallest unsplit grid of F(2x2, 3x3), F(2x2, 2x2), F(4x4, 3x3)
+    int wino42_min_wgs;                     // smallest grid of F(4x4, 2x2) (it has no split-K form)
     int wino_splitk;                        // 0: no split-K Winograd grids
     int par_inner;                          // 0 / 1: order of the transposed convolution's parity classes, -1: by operand size (conv_params)
     int halo_slots;                         // > 0: workgroups per CU of the halo kernels (balanced_slots)
@@ -95,7 +100,8 @@ static const ConvTuning& tuning() {
     static const ConvTuning t = {env("RNR_SPLITK_BELOW", RNR_SPLITK_BELOW), env("RNR_SPLITK_TARGET", RNR_SPLITK_TARGET),
                                  env("RNR_CFG4_MAX", RNR_CFG4_MAX), env("RNR_CFG0_SMALL_MAX", RNR_CFG0_SMALL_MAX),
                                  env("RNR_WINO_MIN_WGS", RNR_WINO_MIN_WGS), env("RNR_WINO2_MIN_WGS", RNR_WINO2_MIN_WGS),
-                                 env("RNR_WINO4_MIN_WGS", RNR_WINO4_MIN_WGS), env("RNR_WINO_SPLITK", 1),
+                                 env("RNR_WINO4_MIN_WGS", RNR_WINO4_MIN_WGS), env("RNR_WINO42_MIN_WGS", RNR_WINO42_MIN_WGS),
+                                 env("RNR_WINO_SPLITK", 1),
                                  env("RNR_PAR_INNER", -1), env("RNR_HALO_SLOTS", 0)};
     return t;
 }
@@ -1531,6 +1537,7 @@ pack_weight_emu_kernel(rnr_conv_desc d, const float* __restrict__ w, char* __res
 #include "conv_wino2.inc"
 #include "conv_wino2p.inc"
 #include "conv_wino4.inc"
+#include "conv_wino42p.inc"
 
 // mask[tile] = any(alpha > 0) over the tw x th output pixels of the tile (tile order = the halo kernels' mt index)
 __global__ void __launch_bounds__(256) active_tile_kernel(const float* __restrict__ alpha, uint8_t* __restrict__ mask, int H,
@@ -1554,8 +1561,9 @@ __global__ void __launch_bounds__(256) zero_f64_kernel(double* __restrict__ p, l
 
 // ---- host side: one table from tile to kernel, one plan per call ---------------------------------------------------------
 
-enum ConvFamily { GATHER, HALO, HALO_EMU, WINO, WINO80, WINO2, WINO2T, WINO4 };
-static const int CONV_ALGORITHM[] = {0, 0, 0, 1, 3, 2, 2, 4};       // what rnr_conv_algorithm reports, by family
+enum ConvFamily { GATHER, HALO, HALO_EMU, WINO, WINO80, WINO2, WINO2T, WINO4, WINO42T };
+static const int CONV_ALGORITHM[] = {0, 0, 0, 1, 3, 2, 2, 4, 2};       // what rnr_conv_algorithm reports, by family
+static const int CONV_WINOGRAD_TILE[] = {0, 0, 0, 2, 2, 2, 2, 4, 4};   // ... and rnr_conv_winograd_tile: m of F(m x m, r x r)
 typedef void (*ConvLaunch)(const dim3, const ConvParams&, hipStream_t);
 
 // A kernel instantiation per (row, emulation format, kind).  The planner takes its tiles from CONV_TILES and the launch calls
@@ -1621,6 +1629,7 @@ static const ConvTile CONV_TILES[] = {
     {WINO, WINO_PW, WINO_PH, WINO_BN, {{launch_wino, nullptr, nullptr}, {}}},       // F(2x2, 3x3)
     {WINO2, WINO_PW, 16, 128, {{nullptr, launch_wino2, nullptr}, {}}},              // F(2x2, 2x2) stride 2: 16 x 16 output pixels
     {WINO2T, WINO_PW, WINO_PH, 64, {{nullptr, nullptr, launch_wino2p}, {}}},        // ... transposed: the four parity classes of 16 x 8 input pixels
+    {WINO42T, W42_PW, W42_PH, W42_BN, {{nullptr, nullptr, launch_wino42p}, {}}},    // F(4x4, 2x2) transposed: one parity class of 32 x 16 input pixels
 };
 
 static ConvLaunch tile_launcher(const ConvTile& t, const rnr_conv_desc* d) {
@@ -1646,12 +1655,12 @@ struct ConvPlan {
 enum ConvMode { CONV_PLAIN, CONV_MASKED, CONV_RAY };      // what the launch carries: nothing, a tile mask, the ray-renderer epilogue (+ a mask)
 
 // geometry `g` with the grid of one K slice on tile `t`: THE place tiles are counted.  The transposed convolution's four parity
-// classes are workgroups of their own in the direct kernels.
+// classes are workgroups of their own in the direct kernels and in the F(4x4, 2x2) one.
 static ConvPlan grid_of(const ConvTile& t, const rnr_conv_desc* d, ConvPlan g) {
     g.tile = &t;
     g.mtiles = t.family == GATHER ? (g.M + t.tw - 1) / t.tw : g.N * (g.Ho / t.th) * (g.Wo / t.tw);
     g.ntiles = (d->c_out_pad + t.bn - 1) / t.bn;
-    g.par = d->kind == RNR_CONVT4x4S2 && t.family <= HALO_EMU ? 4 : 1;
+    g.par = d->kind == RNR_CONVT4x4S2 && (t.family <= HALO_EMU || t.family == WINO42T) ? 4 : 1;
     return g;
 }
 // all pixels of a tile lie inside the map
@@ -1714,6 +1723,19 @@ static ConvChoice try_wino(const rnr_conv_desc* d, const ConvPlan& g) {
 static ConvChoice try_wino2(const rnr_conv_desc* d, const ConvPlan& g) {
     const ConvTile* t = d->kind == RNR_CONVT4x4S2 ? find_tile(WINO2T, d, WINO_PW, WINO_PH, 64) : find_tile(WINO2, d, WINO_PW, 16, 128);
     return wino_choice(t, d, g, tuning().wino2_min_wgs);
+}
+static size_t wino42_weight_floats(const rnr_conv_desc* d);
+// F(4x4, 2x2) for the transposed convolution (opt-in, RNR_CONV_WINOGRAD42): one parity class of 32 x 16 input pixels x 64
+// columns per 12-wave workgroup, one workgroup per CU — when the class maps tile, the BatchNorm table holds the input channels,
+// the weight image stays inside a 32-bit byte offset and the grid gives every CU a workgroup (RNR_WINO42_MIN_WGS).  No split-K
+// form: everything else falls through to F(2x2, 2x2).
+static ConvChoice try_wino42p(const rnr_conv_desc* d, const ConvPlan& g) {
+    if (!(d->flags & RNR_CONV_WINOGRAD) || !(d->flags & RNR_CONV_WINOGRAD42) || d->kind != RNR_CONVT4x4S2) return NO_CHOICE;
+    const ConvTile* t = find_tile(WINO42T, d, W42_PW, W42_PH, W42_BN);
+    if (!t || d->c_out_pad % t->bn != 0 || !fits(*t, g) || d->c_in0_pad + d->c_in1_pad > W4_BN_MAXC ||
+        wino42_weight_floats(d) * sizeof(float) >= (1ul << 31))
+        return NO_CHOICE;
+    return grid_of(*t, d, g).wgs() >= tuning().wino42_min_wgs ? ConvChoice{t, 1} : NO_CHOICE;
 }
 
 // the 4x4 stride-2 convolution runs on the 128-column configuration of the direct kernels whatever its column count
@@ -1802,6 +1824,7 @@ static const struct {
     {try_wino80, true, false, false},
     {try_wino4, false, false, false},
     {try_wino, false, false, false},
+    {try_wino42p, false, false, false},
     {try_wino2, false, false, false},
     {try_halo, true, true, false},
     {try_gather, true, true, true},
@@ -1844,10 +1867,13 @@ static int check_desc(const rnr_conv_desc* d, const char* who) {
                 "%s: c_in1 %d / pad %d", who, d->c_in1, d->c_in1_pad);
     RNR_REQUIRE(d->c_out > 0 && d->c_out_pad >= d->c_out && d->c_out_pad % BK == 0,
                 "%s: c_out %d / pad %d", who, d->c_out, d->c_out_pad);
-    RNR_REQUIRE((d->flags & ~(RNR_CONV_STATS_PREZEROED | RNR_CONV_F32_EMU_ANY | RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD4)) == 0,
+    RNR_REQUIRE((d->flags & ~(RNR_CONV_STATS_PREZEROED | RNR_CONV_F32_EMU_ANY | RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD4 |
+                              RNR_CONV_WINOGRAD42)) == 0,
                 "%s: unknown flags 0x%x", who, d->flags);
     RNR_REQUIRE(!(d->flags & RNR_CONV_WINOGRAD4) || (d->flags & RNR_CONV_WINOGRAD),
                 "%s: RNR_CONV_WINOGRAD4 goes with RNR_CONV_WINOGRAD (its fallback for the shapes it does not cover)", who);
+    RNR_REQUIRE(!(d->flags & RNR_CONV_WINOGRAD42) || (d->flags & RNR_CONV_WINOGRAD),
+                "%s: RNR_CONV_WINOGRAD42 goes with RNR_CONV_WINOGRAD (its fallback for the shapes it does not cover)", who);
     RNR_REQUIRE((d->flags & RNR_CONV_F32_EMU_ANY) != RNR_CONV_F32_EMU_ANY, "%s: choose ONE emulation format", who);
     RNR_REQUIRE(!(d->flags & RNR_CONV_WINOGRAD) || !(d->flags & RNR_CONV_F32_EMU_ANY),
                 "%s: RNR_CONV_WINOGRAD is an exact-fp32 algorithm, not combined with the emulation formats", who);
@@ -1877,6 +1903,14 @@ static size_t wino4_weight_floats(const rnr_conv_desc* d) {      // 0: this conv
     const size_t npairs = (size_t)(d->c_in0_pad + d->c_in1_pad) / 2;
     return (size_t)(d->c_out_pad / W4_BN) * (npairs + W4_BDIST) * W4_STEP_FLOATS;
 }
+namespace rnr {
+static size_t wino42_weight_floats(const rnr_conv_desc* d) {     // 0: this convolution has no F(4x4, 2x2) image
+    if (!(d->flags & RNR_CONV_WINOGRAD) || !(d->flags & RNR_CONV_WINOGRAD42) || d->kind != RNR_CONVT4x4S2 || d->c_out_pad % W42_BN)
+        return 0;
+    const size_t nsteps = (size_t)(d->c_in0_pad + d->c_in1_pad) / 2;
+    return (size_t)(d->c_out_pad / W42_BN) * (nsteps + W42_BDIST) * W42_STEP_FLOATS;
+}
+}  // namespace rnr
 static size_t packed_f32_floats(const rnr_conv_desc* d) {
     const size_t taps = d->kind == RNR_CONV3x3_REFLECT ? 9 : 16;          // 16 = 4x4 taps, or 4 parity classes x 4 taps
     return taps * (size_t)(d->c_in0_pad + d->c_in1_pad) * (size_t)weight_row_stride(d->c_out_pad);
@@ -1889,7 +1923,8 @@ extern "C" size_t rnr_packed_weight_floats(const rnr_conv_desc* d) {
     if (d->flags & RNR_CONV_F32_EMU_BF16X6) return f32 + EMU_HEADER_BYTES / 4 + (f32 * 6 + 3) / 4;
     if (d->flags & RNR_CONV_F32_EMU_F16X3) return f32 + EMU_HEADER_BYTES / 4 + f32;
     // Winograd image behind the fp32 image: 16 planes instead of 9 taps (and, with RNR_CONV_WINOGRAD4, the 36-plane image behind it)
-    return f32 + wino_weight_floats(d) + wino4_weight_floats(d);
+    // (with RNR_CONV_WINOGRAD42, the transposed convolution's 25-plane image in the same place)
+    return f32 + wino_weight_floats(d) + wino4_weight_floats(d) + wino42_weight_floats(d);
 }
 
 extern "C" int rnr_pack_conv_weight(const rnr_conv_desc* d, const float* weight, float* packed, void* stream) {
@@ -1932,6 +1967,11 @@ extern "C" int rnr_pack_conv_weight(const rnr_conv_desc* d, const float* weight,
                                weight, packed + total + nw, nw4);
             return check_launch("pack_weight_wino4_kernel");
         }
+        if (const long nw42 = (long)wino42_weight_floats(d)) {
+            hipLaunchKernelGGL(pack_weight_wino42p_kernel, dim3((unsigned)((nw42 + 255) / 256)), dim3(256), 0, as_stream(stream), *d,
+                               weight, packed + total + nw, nw42);
+            return check_launch("pack_weight_wino42p_kernel");
+        }
         return 0;
     }
     return 0;
@@ -1963,6 +2003,11 @@ extern "C" size_t rnr_conv_sync_bytes(const rnr_conv_desc* d, int max_views, int
 extern "C" int rnr_conv_algorithm(const rnr_conv_desc* d, int num_views, int in_h, int in_w) {
     if (!d || num_views <= 0 || d->kind < 0 || d->kind > 2) return -1;
     return CONV_ALGORITHM[plan_conv(d, num_views, in_h, in_w, CONV_PLAIN).tile->family];
+}
+
+extern "C" int rnr_conv_winograd_tile(const rnr_conv_desc* d, int num_views, int in_h, int in_w) {
+    if (!d || num_views <= 0 || d->kind < 0 || d->kind > 2) return -1;
+    return CONV_WINOGRAD_TILE[plan_conv(d, num_views, in_h, in_w, CONV_PLAIN).tile->family];
 }
 
 // (the tiles of a MASKED launch of this descriptor; the mask of a ray-epilogue launch is laid out like that of a masked
@@ -2029,7 +2074,7 @@ static ConvParams conv_params(const rnr_conv_desc* d, const rnr_conv_src* src0, 
     if (ray) { P.ray_w = ray->w; P.ray_bias = ray->bias; P.ray_image = ray->image; }
     const size_t f32 = packed_f32_floats(d);          // the images behind the fp32 one (rnr_packed_weight_floats)
     if (pl.tile->family == HALO_EMU) P.weight_emu = weight_packed + f32;
-    if (pl.tile->family >= WINO) P.weight_wino = weight_packed + f32 + (pl.tile->family == WINO4 ? wino_weight_floats(d) : 0);
+    if (pl.tile->family >= WINO) P.weight_wino = weight_packed + f32 + (pl.tile->family == WINO4 || pl.tile->family == WINO42T ? wino_weight_floats(d) : 0);
     if (pl.par > 1) {
         // Each parity class is its own workgroup and stages the same input halo.  With the class as the slowest tile index the
         // input is streamed from HBM four times (r02 PMC: 2.9x the compulsory bytes on the 64-column transposed conv); as

@@ -55,7 +55,10 @@ class UNetPlan:
         (include/rnr_hip.h, RNR_CONV_WINOGRAD; 'f32' only) — where the layer shape allows; 'winograd4' (the DEFAULT since r04): additionally
         F(4x4, 3x3) — 4x fewer multiplications than the direct form, ~3.5x the rounding error of F(2x2, 3x3) (~4.5x the direct
         form's rms; every layer shape <= 1e-4 of the output peak vs float64, all 720 spiral frames <= 1.6e-6 from the direct path) — for the 3x3
-        layers whose grid fills the chip (RNR_CONV_WINOGRAD4); 'direct': every convolution as a direct implicit GEMM.
+        layers whose grid fills the chip (RNR_CONV_WINOGRAD4), and since r07 F(4x4, 2x2) — 1.44x fewer multiplications than F(2x2, 2x2),
+        2.5x its rounding error (rms; <= 7.1e-6 of the output peak vs float64 on L14 - L20, all 720 frames unchanged at <= 1.85e-6 from the
+        direct path, profiles/r07_wino42p_ab.txt) — for the transposed layers whose class maps tile into 32 x 16 (RNR_CONV_WINOGRAD42);
+        'direct': every convolution as a direct implicit GEMM.
         None: $RNR_CONV_ALGO, else DEFAULT_CONV_ALGO.
         share_weights_with: another UNetPlan of the same network whose packed weights / BN parameters are reused
         (activations, statistics and scratch stay private) — one plan per HIP stream of RNRPipeline."""
@@ -123,6 +126,10 @@ class UNetPlan:
                 desc.flags |= _lib.CONV_WINOGRAD
             if conv_algo == 'winograd4' and kind == CONV3x3_REFLECT and desc.c_out_pad % 64 == 0:
                 desc.flags |= _lib.CONV_WINOGRAD4
+            # ... and F(4x4, 2x2) for the transposed convolutions (r07; measured faster on every layer that tiles, L14 - L20 of the
+            # benchmark network: profiles/r07_wino42p_ab.txt); conv_algo 'winograd' keeps them on F(2x2, 2x2).
+            if conv_algo == 'winograd4' and kind == CONVT4x4S2 and desc.c_out_pad % 64 == 0:
+                desc.flags |= _lib.CONV_WINOGRAD42
             if share_weights_with is not None:
                 packed = share_weights_with.steps[len(self.steps)]['packed']
                 if packed.numel() != self.L.rnr_packed_weight_floats(ctypes.byref(desc)):
@@ -218,7 +225,8 @@ class UNetPlan:
 
     def mfma_flops_per_view(self, n_views, masked_out_layer=True):
         """Multiply-add FLOPs the matrix cores execute per view when `n_views` are passed per call: the direct-form count of
-        every convolution (flops_per_view) divided by 2.25 / 1.78 where rnr_conv_algorithm says a Winograd kernel runs (the
+        every convolution (flops_per_view) divided by 2.25 / 1.78 / 4 / 2.56 where rnr_conv_algorithm says a Winograd kernel runs
+        (F(2x2, 3x3), F(2x2, 2x2), F(4x4, 3x3), F(4x4, 2x2): 25 multiplications per 4 x 4 outputs of a parity class instead of 64; the
         out layer runs direct when it is tile-masked)."""
         total = 0.0
         for i, s in enumerate(self.steps):
@@ -226,6 +234,9 @@ class UNetPlan:
             algo = self.L.rnr_conv_algorithm(ctypes.byref(d), int(n_views), h, w)
             if masked_out_layer and i == len(self.steps) - 1 and algo != 3:
                 algo = 0
+            if algo == 2 and self.L.rnr_conv_winograd_tile(ctypes.byref(d), int(n_views), h, w) == 4:
+                total += self._layer_flops(d, h, w) * 25.0 / 64.0       # F(4x4, 2x2): the same code, another tile
+                continue
             total += self._layer_flops(d, h, w) / {0: 1.0, 1: 36.0 / 16.0, 2: 16.0 / 9.0, 3: 36.0 / 16.0, 4: 4.0}[algo]
         return total
 

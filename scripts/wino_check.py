@@ -1,7 +1,7 @@
 """Winograd kernels (F(2x2, 3x3) for the 3x3 layers, F(2x2, 2x2) for the 4x4 stride-2 ones) against the direct exact-fp32
 kernels and a float64 convolution on U-Net layer shapes
 (GPU box): max |difference| relative to the rms of the output, statistics / BatchNorm scale-shift difference.
-Usage: python scripts/wino_check.py [--views 2] [--f4x4]"""
+Usage: python scripts/wino_check.py [--views 2] [--f4x4] [--f42 --views 4]"""
 import argparse
 import ctypes
 import os
@@ -48,13 +48,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--views', type=int, default=2)
     ap.add_argument('--f4x4', action='store_true', help='RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD4: F(4x4, 3x3) where the plan takes it (set RNR_WINO4_MIN_WGS=1 to force it)')
+    ap.add_argument('--f42', action='store_true', help='RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD42 on the U-Net\'s transposed layer shapes: F(4x4, 2x2) where the plan takes it (4 views fill the grid)')
     a = ap.parse_args()
     L = _lib.load()
     torch.manual_seed(1)
     V = a.views
     global WFLAGS
-    WFLAGS = _lib.CONV_WINOGRAD | (_lib.CONV_WINOGRAD4 if a.f4x4 else 0)
-    for kind, H, cins, cout in [(0, 64, (64,), 64), (0, 128, (108,), 64), (0, 64, (128,), 128), (0, 32, (256,), 256),
+    WFLAGS = _lib.CONV_WINOGRAD | (_lib.CONV_WINOGRAD4 if a.f4x4 else 0) | (_lib.CONV_WINOGRAD42 if a.f42 else 0)
+    # --f42: L14, L16, L18, L20 of the benchmark network, a one-tile-high map and a narrow one
+    f42_shapes = [(2, 32, (512, 512), 512), (2, 64, (512, 512), 256), (2, 128, (256, 256), 128), (2, 256, (128, 128), 64),
+                  (2, 32, (64, 64), 64), (2, 64, (128, 128), 64)]
+    for kind, H, cins, cout in f42_shapes if a.f42 else [(0, 64, (64,), 64), (0, 128, (108,), 64), (0, 64, (128,), 128), (0, 32, (256,), 256),
                                 (0, 32, (512,), 512), (0, 64, (64, 64), 64), (0, 128, (64, 64), 78), (0, 64, (112,), 78), (0, 16, (512,), 512), (0, 48, (32,), 192),
                                 (2, 16, (512,), 512), (2, 32, (64, 64), 64), (2, 64, (128, 128), 64), (2, 32, (256, 256), 128),
                                 (2, 16, (48,), 192), (1, 64, (64,), 128), (1, 128, (128,), 256), (1, 32, (512,), 512),
@@ -74,6 +78,7 @@ def main():
         gamma, beta = torch.rand(cout, device=DEV) + 0.5, torch.randn(cout, device=DEV)
         o_d, sc_d, sh_d = run(L, 0, kind, H, cins, cout, V, data, w, gamma, beta)
         o_w, sc_w, sh_w = run(L, WFLAGS, kind, H, cins, cout, V, data, w, gamma, beta)
+        o_2 = run(L, _lib.CONV_WINOGRAD, kind, H, cins, cout, V, data, w, gamma, beta)[0] if a.f42 else None      # F(2x2, 2x2) on the same data
         # float64 reference
         xs = []
         for j, C in enumerate(cins):
@@ -99,9 +104,15 @@ def main():
         dsc = _lib.RnrConvDesc(kind, cins[0], pad16(cins[0]), cins[1] if len(cins) > 1 else 0, pad16(cins[1]) if len(cins) > 1 else 0,
                                cout, pad16(cout), WFLAGS)
         algo = L.rnr_conv_algorithm(ctypes.byref(dsc), V, H, H)
-        print('algo %d  kind %d %4d^2 %-9s -> %3d  V=%d  max err / rms: direct %.2e winograd %.2e   rms err / rms: direct %.2e winograd %.2e   '
+        tile = L.rnr_conv_winograd_tile(ctypes.byref(dsc), V, H, H)
+        if a.f42:
+            r_2 = float((o_2[..., :cout].double() - ref).pow(2).mean().sqrt()) / rms
+            peak = float(ref.abs().max())
+            print('F(2x2, 2x2) rms err / rms %.2e (F(4x4, 2x2): %.2f x that, %.2f x the direct kernel\'s)   F(4x4, 2x2) max err / output peak %.2e' % (
+                r_2, r_w / r_2, r_w / r_d, float((o_w[..., :cout].double() - ref).abs().max()) / peak), end='   ')
+        print('algo %d tile %d  kind %d %4d^2 %-9s -> %3d  V=%d  max err / rms: direct %.2e winograd %.2e   rms err / rms: direct %.2e winograd %.2e   '
               'scale diff %.1e shift diff %.1e  pad cols zero %s  finite %s' % (
-                  algo, kind, H, '+'.join(map(str, cins)), cout, V, e_d, e_w, r_d, r_w, float((sc_d - sc_w).abs().max()),
+                  algo, tile, kind, H, '+'.join(map(str, cins)), cout, V, e_d, e_w, r_d, r_w, float((sc_d - sc_w).abs().max()),
                   float((sh_d - sh_w).abs().max()), pad_ok, bool(torch.isfinite(o_w).all())))
         sys.stdout.flush()
 
