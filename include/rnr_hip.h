@@ -330,6 +330,18 @@ typedef struct rnr_conv_desc {
  * shapes it does not cover run F(2x2, 2x2) / direct from the same buffer.  rnr_conv_algorithm reports 2 for both forms (Winograd on
  * the 2x2-tap decomposition); rnr_conv_winograd_tile tells them apart (4 / 2). */
 #define RNR_CONV_WINOGRAD42 32
+/* (with RNR_CONV_WINOGRAD) F(4x4, 3x3) for the 3x3 OUT LAYER: 65 - 80 output channels in 80 padded columns, which
+ * RNR_CONV_WINOGRAD4's 64-column tiles do not cover.  Taken when the map tiles into 16 x 16 pixels, the input channels (both
+ * sources, padded) number at most 1024 and the grid gives every CU a workgroup (256 tiles; RNR_WINO80F4_MIN_WGS in the
+ * environment); everything else runs the out layer's F(2x2, 3x3) kernel / the direct kernels from the same packed buffer (the
+ * 36-plane image is stored behind the F(2x2, 3x3) one: both flags when packing AND convolving).  Same algorithm, interpolation
+ * points and rounding behaviour as RNR_CONV_WINOGRAD4 (tests bound the error at 1e-4 of the output peak against a float64
+ * convolution); a flag of its own because callers that pass RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD4 with 80 columns rely on the
+ * 16 x 4 tiles of the F(2x2, 3x3) kernel.  Non-finite inputs: an inf / NaN activation reaches every output of the 4 x 4 tiles
+ * whose 6 x 6 patch contains it.  rnr_conv_algorithm keeps reporting 3 (the out layer's Winograd kernels, both take a tile
+ * mask); rnr_conv_winograd_tile tells them apart (4 / 2), and rnr_conv_tile_count / rnr_conv_active_tiles then describe
+ * 16 x 16 pixel tiles. */
+#define RNR_CONV_WINOGRAD4_OUT 64
 
 /* Floats in the packed weight of `d` ([taps][c_in0_pad + c_in1_pad][c_out_pad], x4 parity classes for convT). */
 size_t rnr_packed_weight_floats(const rnr_conv_desc* d);
@@ -338,7 +350,8 @@ size_t rnr_packed_weight_floats(const rnr_conv_desc* d);
 int rnr_pack_conv_weight(const rnr_conv_desc* d, const float* weight, float* packed, void* stream);
 
 /* Which algorithm rnr_conv2d* runs for (desc, N, input H, input W): 0 = direct implicit GEMM, 1 = Winograd F(2x2, 3x3),
- * 3 = the same for the 80-column out layer (16 x 16 x 4 MFMA tiles), 2 = Winograd F(2x2, 2x2) (16 multiplications per 2 x 2
+ * 3 = the same for the 80-column out layer (16 x 16 x 4 MFMA tiles; with RNR_CONV_WINOGRAD4_OUT it may run F(4x4, 3x3) under the
+ * same code: rnr_conv_winograd_tile), 2 = Winograd F(2x2, 2x2) (16 multiplications per 2 x 2
  * outputs instead of 36, resp. 9 instead of 16; with RNR_CONV_WINOGRAD42 the transposed convolution may run F(4x4, 2x2) under the
  * same code: rnr_conv_winograd_tile), 4 = Winograd F(4x4, 3x3) (RNR_CONV_WINOGRAD4); -1 = bad arguments.
  * Non-zero only with RNR_CONV_WINOGRAD in desc->flags.

@@ -21,10 +21,11 @@
 // product path since r03, RNR_CONV_WINOGRAD — the fp32 Winograd kernels of conv_wino.inc (F(2x2, 3x3): conv_wino_kernel),
 // conv_wino80.inc (the 80-column out layer), conv_wino2.inc / conv_wino2p.inc (F(2x2, 2x2): conv_wino2_kernel<1> for the
 // stride-2 convolution, conv_wino2p_kernel<2> for the transposed one), conv_wino4.inc (F(4x4, 3x3), RNR_CONV_WINOGRAD4) and
-// conv_wino42p.inc (F(4x4, 2x2) for the transposed convolution, RNR_CONV_WINOGRAD42).
+// conv_wino42p.inc (F(4x4, 2x2) for the transposed convolution, RNR_CONV_WINOGRAD42), conv_wino80f4.inc (F(4x4, 3x3) for the
+// 80-column out layer, RNR_CONV_WINOGRAD4_OUT).
 // Device side, shared: conv_stage.inc states tile decode, halo source / slot / prologue and the output-store preamble once for all of them.
 // Host side: CONV_TILES lists every instantiation of these kernels with its tile shape and launcher; plan_conv() tries the
-// candidates (try_wino80 ... try_gather) in priority order and returns the row, the grid and the split-K depth of one call.
+// candidates (try_wino80f4 ... try_gather) in priority order and returns the row, the grid and the split-K depth of one call.
 // Split-K grids write one partial-output slab per slice; splitk_reduce_kernel adds them in slice order.
 #include "rnr_internal.h"
 
@@ -80,6 +81,9 @@ constexpr int CTHREADS = 256;
 #ifndef RNR_WINO42_MIN_WGS
 #define RNR_WINO42_MIN_WGS 256       // fewer (32 x 16 class positions x 64 columns x parity class) workgroups than this, one per CU: F(2x2, 2x2)
 #endif
+#ifndef RNR_WINO80F4_MIN_WGS
+#define RNR_WINO80F4_MIN_WGS 256     // fewer 16 x 16 pixel x 80 column tiles than this (one 12-wave workgroup per CU): F(2x2, 3x3) on conv_wino80_kernel
+#endif
 #ifndef RNR_WINO_MIN_WGS
 #define RNR_WINO_MIN_WGS 256         // fewer 16 x 8 pixel x 64 column tiles than this: the direct kernels (they split K)
 #endif
@@ -91,6 +95,7 @@ struct ConvTuning {
     int cfg4_max, cfg0_small_max;           // direct kernels: the 128 x 64 tiles (try_halo)
     int wino_min_wgs, wino2_min_wgs, wino4_min_wgs;     // smallest unsplit grid of F(2x2, 3x3), F(2x2, 2x2), F(4x4, 3x3)
     int wino42_min_wgs;                     // smallest grid of F(4x4, 2x2) (it has no split-K form)
+    int wino80f4_min_wgs;                   // smallest grid of the out layer's F(4x4, 3x3) (no split-K form either)
     int wino_splitk;                        // 0: no split-K Winograd grids
     int par_inner;                          // 0 / 1: order of the transposed convolution's parity classes, -1: by operand size (conv_params)
     int halo_slots;                         // > 0: workgroups per CU of the halo kernels (balanced_slots)
@@ -101,6 +106,7 @@ static const ConvTuning& tuning() {
                                  env("RNR_CFG4_MAX", RNR_CFG4_MAX), env("RNR_CFG0_SMALL_MAX", RNR_CFG0_SMALL_MAX),
                                  env("RNR_WINO_MIN_WGS", RNR_WINO_MIN_WGS), env("RNR_WINO2_MIN_WGS", RNR_WINO2_MIN_WGS),
                                  env("RNR_WINO4_MIN_WGS", RNR_WINO4_MIN_WGS), env("RNR_WINO42_MIN_WGS", RNR_WINO42_MIN_WGS),
+                                 env("RNR_WINO80F4_MIN_WGS", RNR_WINO80F4_MIN_WGS),
                                  env("RNR_WINO_SPLITK", 1),
                                  env("RNR_PAR_INNER", -1), env("RNR_HALO_SLOTS", 0)};
     return t;
@@ -1538,6 +1544,7 @@ pack_weight_emu_kernel(rnr_conv_desc d, const float* __restrict__ w, char* __res
 #include "conv_wino2p.inc"
 #include "conv_wino4.inc"
 #include "conv_wino42p.inc"
+#include "conv_wino80f4.inc"
 
 // mask[tile] = any(alpha > 0) over the tw x th output pixels of the tile (tile order = the halo kernels' mt index)
 __global__ void __launch_bounds__(256) active_tile_kernel(const float* __restrict__ alpha, uint8_t* __restrict__ mask, int H,
@@ -1561,9 +1568,9 @@ __global__ void __launch_bounds__(256) zero_f64_kernel(double* __restrict__ p, l
 
 // ---- host side: one table from tile to kernel, one plan per call ---------------------------------------------------------
 
-enum ConvFamily { GATHER, HALO, HALO_EMU, WINO, WINO80, WINO2, WINO2T, WINO4, WINO42T };
-static const int CONV_ALGORITHM[] = {0, 0, 0, 1, 3, 2, 2, 4, 2};       // what rnr_conv_algorithm reports, by family
-static const int CONV_WINOGRAD_TILE[] = {0, 0, 0, 2, 2, 2, 2, 4, 4};   // ... and rnr_conv_winograd_tile: m of F(m x m, r x r)
+enum ConvFamily { GATHER, HALO, HALO_EMU, WINO, WINO80, WINO2, WINO2T, WINO4, WINO42T, WINO80F4 };
+static const int CONV_ALGORITHM[] = {0, 0, 0, 1, 3, 2, 2, 4, 2, 3};        // what rnr_conv_algorithm reports, by family
+static const int CONV_WINOGRAD_TILE[] = {0, 0, 0, 2, 2, 2, 2, 4, 4, 4};    // ... and rnr_conv_winograd_tile: m of F(m x m, r x r)
 typedef void (*ConvLaunch)(const dim3, const ConvParams&, hipStream_t);
 
 // A kernel instantiation per (row, emulation format, kind).  The planner takes its tiles from CONV_TILES and the launch calls
@@ -1630,6 +1637,7 @@ static const ConvTile CONV_TILES[] = {
     {WINO2, WINO_PW, 16, 128, {{nullptr, launch_wino2, nullptr}, {}}},              // F(2x2, 2x2) stride 2: 16 x 16 output pixels
     {WINO2T, WINO_PW, WINO_PH, 64, {{nullptr, nullptr, launch_wino2p}, {}}},        // ... transposed: the four parity classes of 16 x 8 input pixels
     {WINO42T, W42_PW, W42_PH, W42_BN, {{nullptr, nullptr, launch_wino42p}, {}}},    // F(4x4, 2x2) transposed: one parity class of 32 x 16 input pixels
+    {WINO80F4, W8F_PW, W8F_PH, 80, {{launch_wino80f4, nullptr, nullptr}, {}}},      // F(4x4, 3x3), the 80-column out layer: 16 x 16 output pixels
 };
 
 static ConvLaunch tile_launcher(const ConvTile& t, const rnr_conv_desc* d) {
@@ -1703,6 +1711,15 @@ static ConvChoice try_wino80(const rnr_conv_desc* d, const ConvPlan& g) {
     const ConvTile* t = find_tile(WINO80, d, W80_PW, W80_PH, 80);
     if (!(d->flags & RNR_CONV_WINOGRAD) || !t || d->c_out_pad != 80 || !fits(*t, g)) return NO_CHOICE;
     return grid_of(*t, d, g).wgs() >= tuning().wino_min_wgs ? ConvChoice{t, 1} : NO_CHOICE;
+}
+// F(4x4, 3x3) for the 80-column out layer (opt-in, RNR_CONV_WINOGRAD4_OUT): 16 x 16 pixel tiles x all 80 columns, one 12-wave
+// workgroup per CU — when the map tiles, the BatchNorm table holds the input channels and the grid gives every CU a workgroup
+// (RNR_WINO80F4_MIN_WGS).  No split-K form: everything else falls through to try_wino80.
+static ConvChoice try_wino80f4(const rnr_conv_desc* d, const ConvPlan& g) {
+    if (!(d->flags & RNR_CONV_WINOGRAD) || !(d->flags & RNR_CONV_WINOGRAD4_OUT) || d->kind != RNR_CONV3x3_REFLECT) return NO_CHOICE;
+    const ConvTile* t = find_tile(WINO80F4, d, W8F_PW, W8F_PH, 80);
+    if (!t || d->c_out_pad != 80 || !fits(*t, g) || d->c_in0_pad + d->c_in1_pad > W4_BN_MAXC) return NO_CHOICE;
+    return grid_of(*t, d, g).wgs() >= tuning().wino80f4_min_wgs ? ConvChoice{t, 1} : NO_CHOICE;
 }
 // F(4x4, 3x3) (opt-in, RNR_CONV_WINOGRAD4): 32 x 16 pixel tiles x 64 columns, one 12-wave workgroup per CU — when the grid gives
 // every CU a workgroup (RNR_WINO4_MIN_WGS).  Small grids are cut over K like the F(2x2, .) ones — slices of >=
@@ -1814,13 +1831,14 @@ static ConvChoice try_gather(const rnr_conv_desc* d, const ConvPlan& g) {
 }
 
 // The candidates in priority order; the first that qualifies runs.  The columns are THE rule for masked and ray-epilogue
-// launches: the out layer's own Winograd kernel takes a tile mask, the other Winograd kernels do not, and the ray-renderer
+// launches: the out layer's own Winograd kernels take a tile mask, the other Winograd kernels do not, and the ray-renderer
 // epilogue lives in the direct 80-column kernel — those calls run the direct kernels, on the direct kernels' tiles.  The halo and
 // Winograd kernels address a view with 32-bit element offsets: views of 2^30 elements and more are left to the gather kernel.
 static const struct {
     ConvChoice (*qualify)(const rnr_conv_desc*, const ConvPlan&);
     bool masked, ray, big_view;
 } CONV_CANDIDATES[] = {
+    {try_wino80f4, true, false, false},
     {try_wino80, true, false, false},
     {try_wino4, false, false, false},
     {try_wino, false, false, false},
@@ -1851,9 +1869,9 @@ static ConvPlan plan_conv(const rnr_conv_desc* d, int N, int H, int W, ConvMode 
     if (!c.tile) return p;
     p = grid_of(*c.tile, d, p);
     p.splitk = c.splitk;
-    // a tile mask has one entry per 32-pixel-wide halo tile, or 16 x 4 tile of the out layer's Winograd kernel, of an unsplit 3x3 grid
+    // a tile mask has one entry per 32-pixel-wide halo tile, or 16 x 4 / 16 x 16 tile of the out layer's Winograd kernels, of an unsplit 3x3 grid
     p.maskable = d->kind == RNR_CONV3x3_REFLECT && p.splitk == 1 &&
-                 (c.tile->family == WINO80 || ((c.tile->family == HALO || c.tile->family == HALO_EMU) && c.tile->tw == 32));
+                 (c.tile->family == WINO80 || c.tile->family == WINO80F4 || ((c.tile->family == HALO || c.tile->family == HALO_EMU) && c.tile->tw == 32));
     if (mode == CONV_RAY) p.splitk = 1;     // the ray-renderer epilogue needs the whole K sum in one workgroup (small maps would split)
     return p;
 }
@@ -1868,12 +1886,14 @@ static int check_desc(const rnr_conv_desc* d, const char* who) {
     RNR_REQUIRE(d->c_out > 0 && d->c_out_pad >= d->c_out && d->c_out_pad % BK == 0,
                 "%s: c_out %d / pad %d", who, d->c_out, d->c_out_pad);
     RNR_REQUIRE((d->flags & ~(RNR_CONV_STATS_PREZEROED | RNR_CONV_F32_EMU_ANY | RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD4 |
-                              RNR_CONV_WINOGRAD42)) == 0,
+                              RNR_CONV_WINOGRAD42 | RNR_CONV_WINOGRAD4_OUT)) == 0,
                 "%s: unknown flags 0x%x", who, d->flags);
     RNR_REQUIRE(!(d->flags & RNR_CONV_WINOGRAD4) || (d->flags & RNR_CONV_WINOGRAD),
                 "%s: RNR_CONV_WINOGRAD4 goes with RNR_CONV_WINOGRAD (its fallback for the shapes it does not cover)", who);
     RNR_REQUIRE(!(d->flags & RNR_CONV_WINOGRAD42) || (d->flags & RNR_CONV_WINOGRAD),
                 "%s: RNR_CONV_WINOGRAD42 goes with RNR_CONV_WINOGRAD (its fallback for the shapes it does not cover)", who);
+    RNR_REQUIRE(!(d->flags & RNR_CONV_WINOGRAD4_OUT) || (d->flags & RNR_CONV_WINOGRAD),
+                "%s: RNR_CONV_WINOGRAD4_OUT goes with RNR_CONV_WINOGRAD (its fallback for the shapes it does not cover)", who);
     RNR_REQUIRE((d->flags & RNR_CONV_F32_EMU_ANY) != RNR_CONV_F32_EMU_ANY, "%s: choose ONE emulation format", who);
     RNR_REQUIRE(!(d->flags & RNR_CONV_WINOGRAD) || !(d->flags & RNR_CONV_F32_EMU_ANY),
                 "%s: RNR_CONV_WINOGRAD is an exact-fp32 algorithm, not combined with the emulation formats", who);
@@ -1903,6 +1923,12 @@ static size_t wino4_weight_floats(const rnr_conv_desc* d) {      // 0: this conv
     const size_t npairs = (size_t)(d->c_in0_pad + d->c_in1_pad) / 2;
     return (size_t)(d->c_out_pad / W4_BN) * (npairs + W4_BDIST) * W4_STEP_FLOATS;
 }
+static size_t wino80f4_weight_floats(const rnr_conv_desc* d) {   // 0: this convolution has no out-layer F(4x4, 3x3) image
+    if (!(d->flags & RNR_CONV_WINOGRAD) || !(d->flags & RNR_CONV_WINOGRAD4_OUT) || d->kind != RNR_CONV3x3_REFLECT || d->c_out_pad != 80)
+        return 0;
+    const size_t nsteps = (size_t)(d->c_in0_pad + d->c_in1_pad) / 4;
+    return (nsteps + W8F_BDIST) * W8F_STEP_FLOATS;
+}
 namespace rnr {
 static size_t wino42_weight_floats(const rnr_conv_desc* d) {     // 0: this convolution has no F(4x4, 2x2) image
     if (!(d->flags & RNR_CONV_WINOGRAD) || !(d->flags & RNR_CONV_WINOGRAD42) || d->kind != RNR_CONVT4x4S2 || d->c_out_pad % W42_BN)
@@ -1923,8 +1949,9 @@ extern "C" size_t rnr_packed_weight_floats(const rnr_conv_desc* d) {
     if (d->flags & RNR_CONV_F32_EMU_BF16X6) return f32 + EMU_HEADER_BYTES / 4 + (f32 * 6 + 3) / 4;
     if (d->flags & RNR_CONV_F32_EMU_F16X3) return f32 + EMU_HEADER_BYTES / 4 + f32;
     // Winograd image behind the fp32 image: 16 planes instead of 9 taps (and, with RNR_CONV_WINOGRAD4, the 36-plane image behind it)
-    // (with RNR_CONV_WINOGRAD42, the transposed convolution's 25-plane image in the same place)
-    return f32 + wino_weight_floats(d) + wino4_weight_floats(d) + wino42_weight_floats(d);
+    // (with RNR_CONV_WINOGRAD42, the transposed convolution's 25-plane image in the same place; with RNR_CONV_WINOGRAD4_OUT, the
+    // 80-column out layer's 36-plane image; at most one of the three is present)
+    return f32 + wino_weight_floats(d) + wino4_weight_floats(d) + wino42_weight_floats(d) + wino80f4_weight_floats(d);
 }
 
 extern "C" int rnr_pack_conv_weight(const rnr_conv_desc* d, const float* weight, float* packed, void* stream) {
@@ -1971,6 +1998,11 @@ extern "C" int rnr_pack_conv_weight(const rnr_conv_desc* d, const float* weight,
             hipLaunchKernelGGL(pack_weight_wino42p_kernel, dim3((unsigned)((nw42 + 255) / 256)), dim3(256), 0, as_stream(stream), *d,
                                weight, packed + total + nw, nw42);
             return check_launch("pack_weight_wino42p_kernel");
+        }
+        if (const long nw8 = (long)wino80f4_weight_floats(d)) {
+            hipLaunchKernelGGL(pack_weight_wino80f4_kernel, dim3((unsigned)((nw8 + 255) / 256)), dim3(256), 0, as_stream(stream), *d,
+                               weight, packed + total + nw, nw8);
+            return check_launch("pack_weight_wino80f4_kernel");
         }
         return 0;
     }
@@ -2074,7 +2106,7 @@ static ConvParams conv_params(const rnr_conv_desc* d, const rnr_conv_src* src0, 
     if (ray) { P.ray_w = ray->w; P.ray_bias = ray->bias; P.ray_image = ray->image; }
     const size_t f32 = packed_f32_floats(d);          // the images behind the fp32 one (rnr_packed_weight_floats)
     if (pl.tile->family == HALO_EMU) P.weight_emu = weight_packed + f32;
-    if (pl.tile->family >= WINO) P.weight_wino = weight_packed + f32 + (pl.tile->family == WINO4 || pl.tile->family == WINO42T ? wino_weight_floats(d) : 0);
+    if (pl.tile->family >= WINO) P.weight_wino = weight_packed + f32 + (pl.tile->family == WINO4 || pl.tile->family == WINO42T || pl.tile->family == WINO80F4 ? wino_weight_floats(d) : 0);
     if (pl.par > 1) {
         // Each parity class is its own workgroup and stages the same input halo.  With the class as the slowest tile index the
         // input is streamed from HBM four times (r02 PMC: 2.9x the compulsory bytes on the 64-column transposed conv); as

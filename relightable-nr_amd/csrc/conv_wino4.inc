@@ -407,29 +407,8 @@ conv_wino4_kernel(const ConvParams P) {
 #endif
 }
 
-// Transformed weights U = G g G^T for the points (0, a, -a, b, -b, inf): G[j] = (1, p_j, p_j^2) / prod_{k != j} (p_j - p_k),
-// G[inf] = (0, 0, 1); computed in float64 and rounded once.  i enumerates
-// [64-column tile][K step][xi][column half][h][32 columns][6 planes nu]; K step = chunk * 8 + s holds the padded input channels
-// chunk * 16 + 2 s + h; the W4_BDIST K steps behind the last one are zeros.
-__global__ void __launch_bounds__(256)
-pack_weight_wino4_kernel(rnr_conv_desc d, const float* __restrict__ w, float* __restrict__ image, long total) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int nsteps = (d.c_in0_pad + d.c_in1_pad) / 2;
-    // block of a (K step, xi, column half): 384 floats
-    const int wb = (int)(i % 384);
-    long r = i / 384;
-    // [64 lanes][planes 0..3], then [64 lanes][planes 4, 5]; lane = h * 32 + column
-    const int ln = wb < 256 ? wb >> 2 : (wb - 256) >> 1;
-    const int nu = wb < 256 ? wb & 3 : 4 + ((wb - 256) & 1);
-    const int col = ln & 31, hh = ln >> 5;
-    const int nb = (int)(r & 1); r >>= 1;
-    const int xi = (int)(r % 6); r /= 6;
-    const int step = (int)(r % (nsteps + W4_BDIST));
-    const int nt = (int)(r / (nsteps + W4_BDIST));
-    if (step >= nsteps) { image[i] = 0.0f; return; }
-    const int c = (step >> 3) * 16 + 2 * (step & 7) + hh;
-    const int co = nt * W4_BN + nb * 32 + col;
+// element (xi, nu) of U = G g G^T for input channel c (padded index) and output column co: float64, rounded once
+__device__ __forceinline__ float w4_weight_u(const rnr_conv_desc& d, const float* __restrict__ w, int c, int co, int xi, int nu) {
     const double pts[5] = {0.0, 0.75, -0.75, 1.5, -1.5};
     double G[6][3];
 #pragma unroll
@@ -455,7 +434,33 @@ pack_weight_wino4_kernel(rnr_conv_desc d, const float* __restrict__ w, float* __
         for (int a = 0; a < 3; a++) row += G[xi][a] * g[a][b];
         u += row * G[nu][b];
     }
-    image[i] = (float)u;
+    return (float)u;
+}
+
+// Transformed weights U = G g G^T for the points (0, a, -a, b, -b, inf): G[j] = (1, p_j, p_j^2) / prod_{k != j} (p_j - p_k),
+// G[inf] = (0, 0, 1); computed in float64 and rounded once.  i enumerates
+// [64-column tile][K step][xi][column half][h][32 columns][6 planes nu]; K step = chunk * 8 + s holds the padded input channels
+// chunk * 16 + 2 s + h; the W4_BDIST K steps behind the last one are zeros.
+__global__ void __launch_bounds__(256)
+pack_weight_wino4_kernel(rnr_conv_desc d, const float* __restrict__ w, float* __restrict__ image, long total) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int nsteps = (d.c_in0_pad + d.c_in1_pad) / 2;
+    // block of a (K step, xi, column half): 384 floats
+    const int wb = (int)(i % 384);
+    long r = i / 384;
+    // [64 lanes][planes 0..3], then [64 lanes][planes 4, 5]; lane = h * 32 + column
+    const int ln = wb < 256 ? wb >> 2 : (wb - 256) >> 1;
+    const int nu = wb < 256 ? wb & 3 : 4 + ((wb - 256) & 1);
+    const int col = ln & 31, hh = ln >> 5;
+    const int nb = (int)(r & 1); r >>= 1;
+    const int xi = (int)(r % 6); r /= 6;
+    const int step = (int)(r % (nsteps + W4_BDIST));
+    const int nt = (int)(r / (nsteps + W4_BDIST));
+    if (step >= nsteps) { image[i] = 0.0f; return; }
+    const int c = (step >> 3) * 16 + 2 * (step & 7) + hh;
+    const int co = nt * W4_BN + nb * 32 + col;
+    image[i] = w4_weight_u(d, w, c, co, xi, nu);
 }
 
 static void launch_wino4(const dim3 grid, const ConvParams& P, hipStream_t st) {

@@ -57,7 +57,9 @@ class UNetPlan:
         form's rms; every layer shape <= 1e-4 of the output peak vs float64, all 720 spiral frames <= 1.6e-6 from the direct path) — for the 3x3
         layers whose grid fills the chip (RNR_CONV_WINOGRAD4), and since r07 F(4x4, 2x2) — 1.44x fewer multiplications than F(2x2, 2x2),
         2.5x its rounding error (rms; <= 7.1e-6 of the output peak vs float64 on L14 - L20, all 720 frames unchanged at <= 1.85e-6 from the
-        direct path, profiles/r07_wino42p_ab.txt) — for the transposed layers whose class maps tile into 32 x 16 (RNR_CONV_WINOGRAD42);
+        direct path, profiles/r07_wino42p_ab.txt) — for the transposed layers whose class maps tile into 32 x 16 (RNR_CONV_WINOGRAD42), and since r08
+        F(4x4, 3x3) for the 80-column out layer too where its map tiles into 16 x 16 (RNR_CONV_WINOGRAD4_OUT; 3x the rounding error of its F(2x2, 3x3)
+        kernel, <= 2.5e-6 of the output peak vs float64, all 720 frames <= 1.91e-6 from the direct path; profiles/r08_wino80f4_ab.txt);
         'direct': every convolution as a direct implicit GEMM.
         None: $RNR_CONV_ALGO, else DEFAULT_CONV_ALGO.
         share_weights_with: another UNetPlan of the same network whose packed weights / BN parameters are reused
@@ -130,6 +132,10 @@ class UNetPlan:
             # benchmark network: profiles/r07_wino42p_ab.txt); conv_algo 'winograd' keeps them on F(2x2, 2x2).
             if conv_algo == 'winograd4' and kind == CONVT4x4S2 and desc.c_out_pad % 64 == 0:
                 desc.flags |= _lib.CONV_WINOGRAD42
+            # ... and F(4x4, 3x3) for the 80-column out layer (r08, conv_wino80f4_kernel: profiles/r08_wino80f4_ab.txt); conv_algo
+            # 'winograd' keeps it on F(2x2, 3x3).
+            if conv_algo == 'winograd4' and kind == CONV3x3_REFLECT and desc.c_out_pad == 80:
+                desc.flags |= _lib.CONV_WINOGRAD4_OUT
             if share_weights_with is not None:
                 packed = share_weights_with.steps[len(self.steps)]['packed']
                 if packed.numel() != self.L.rnr_packed_weight_floats(ctypes.byref(desc)):
@@ -225,7 +231,7 @@ class UNetPlan:
 
     def mfma_flops_per_view(self, n_views, masked_out_layer=True):
         """Multiply-add FLOPs the matrix cores execute per view when `n_views` are passed per call: the direct-form count of
-        every convolution (flops_per_view) divided by 2.25 / 1.78 / 4 / 2.56 where rnr_conv_algorithm says a Winograd kernel runs
+        every convolution (flops_per_view) divided by 2.25 / 1.78 / 4 / 2.56 (the out layer under code 3: 2.25, or 4 with Winograd tile 4) where rnr_conv_algorithm says a Winograd kernel runs
         (F(2x2, 3x3), F(2x2, 2x2), F(4x4, 3x3), F(4x4, 2x2): 25 multiplications per 4 x 4 outputs of a parity class instead of 64; the
         out layer runs direct when it is tile-masked)."""
         total = 0.0
@@ -236,6 +242,9 @@ class UNetPlan:
                 algo = 0
             if algo == 2 and self.L.rnr_conv_winograd_tile(ctypes.byref(d), int(n_views), h, w) == 4:
                 total += self._layer_flops(d, h, w) * 25.0 / 64.0       # F(4x4, 2x2): the same code, another tile
+                continue
+            if algo == 3 and self.L.rnr_conv_winograd_tile(ctypes.byref(d), int(n_views), h, w) == 4:
+                total += self._layer_flops(d, h, w) / 4.0               # the out layer on F(4x4, 3x3): the same code, another tile
                 continue
             total += self._layer_flops(d, h, w) / {0: 1.0, 1: 36.0 / 16.0, 2: 16.0 / 9.0, 3: 36.0 / 16.0, 4: 4.0}[algo]
         return total
@@ -282,12 +291,12 @@ class UNetPlan:
         # the ray-renderer epilogue lives in the direct 80-column kernel: that call (and its tile mask) use the out layer's
         # descriptor without the Winograd flag (same packed buffer: the direct image comes first).  rnr_conv2d_ray itself plans
         # on the direct tiles whatever the flags, but rnr_conv_tile_count / rnr_conv_active_tiles have no mode argument and
-        # describe a MASKED launch, which with the flag runs the out layer's Winograd kernel on 16 x 4 tiles: the mask of a
+        # describe a MASKED launch, which with the flag runs the out layer's Winograd kernels on 16 x 4 / 16 x 16 tiles: the mask of a
         # ray launch has to be built from the stripped descriptor, so the strip stays here
         out_desc = last['desc']
         if ray is not None and (out_desc.flags & _lib.CONV_WINOGRAD):
             out_desc = RnrConvDesc(out_desc.kind, out_desc.c_in0, out_desc.c_in0_pad, out_desc.c_in1, out_desc.c_in1_pad,
-                                   out_desc.c_out, out_desc.c_out_pad, out_desc.flags & ~(_lib.CONV_WINOGRAD | _lib.CONV_WINOGRAD4))
+                                   out_desc.c_out, out_desc.c_out_pad, out_desc.flags & ~(_lib.CONV_WINOGRAD | _lib.CONV_WINOGRAD4 | _lib.CONV_WINOGRAD4_OUT))
         self._out_desc = out_desc
         if consumer_alpha is not None:
             h, w = last['in_hw']

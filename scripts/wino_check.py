@@ -1,7 +1,7 @@
 """Winograd kernels (F(2x2, 3x3) for the 3x3 layers, F(2x2, 2x2) for the 4x4 stride-2 ones) against the direct exact-fp32
 kernels and a float64 convolution on U-Net layer shapes
 (GPU box): max |difference| relative to the rms of the output, statistics / BatchNorm scale-shift difference.
-Usage: python scripts/wino_check.py [--views 2] [--f4x4] [--f42 --views 4]"""
+Usage: python scripts/wino_check.py [--views 2] [--f4x4] [--f42 --views 4] [--f4out --views 4]"""
 import argparse
 import ctypes
 import os
@@ -49,16 +49,19 @@ def main():
     ap.add_argument('--views', type=int, default=2)
     ap.add_argument('--f4x4', action='store_true', help='RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD4: F(4x4, 3x3) where the plan takes it (set RNR_WINO4_MIN_WGS=1 to force it)')
     ap.add_argument('--f42', action='store_true', help='RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD42 on the U-Net\'s transposed layer shapes: F(4x4, 2x2) where the plan takes it (4 views fill the grid)')
+    ap.add_argument('--f4out', action='store_true', help='RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD4_OUT on out-layer shapes (80 columns): F(4x4, 3x3) where the plan takes it (256 tiles of 16 x 16 fill the grid)')
     a = ap.parse_args()
     L = _lib.load()
     torch.manual_seed(1)
     V = a.views
     global WFLAGS
-    WFLAGS = _lib.CONV_WINOGRAD | (_lib.CONV_WINOGRAD4 if a.f4x4 else 0) | (_lib.CONV_WINOGRAD42 if a.f42 else 0)
+    WFLAGS = _lib.CONV_WINOGRAD | (_lib.CONV_WINOGRAD4 if a.f4x4 else 0) | (_lib.CONV_WINOGRAD42 if a.f42 else 0) | (_lib.CONV_WINOGRAD4_OUT if a.f4out else 0)
     # --f42: L14, L16, L18, L20 of the benchmark network, a one-tile-high map and a narrow one
     f42_shapes = [(2, 32, (512, 512), 512), (2, 64, (512, 512), 256), (2, 128, (256, 256), 128), (2, 256, (128, 128), 64),
                   (2, 32, (64, 64), 64), (2, 64, (128, 128), 64)]
-    for kind, H, cins, cout in f42_shapes if a.f42 else [(0, 64, (64,), 64), (0, 128, (108,), 64), (0, 64, (128,), 128), (0, 32, (256,), 256),
+    # --f4out: the benchmark's out layer (L22: 512^2, 64 + 64 -> 78) and the two out-layer shapes of the default sweep
+    f4out_shapes = [(0, 512, (64, 64), 78), (0, 128, (64, 64), 78), (0, 64, (112,), 78)]
+    for kind, H, cins, cout in f42_shapes if a.f42 else f4out_shapes if a.f4out else [(0, 64, (64,), 64), (0, 128, (108,), 64), (0, 64, (128,), 128), (0, 32, (256,), 256),
                                 (0, 32, (512,), 512), (0, 64, (64, 64), 64), (0, 128, (64, 64), 78), (0, 64, (112,), 78), (0, 16, (512,), 512), (0, 48, (32,), 192),
                                 (2, 16, (512,), 512), (2, 32, (64, 64), 64), (2, 64, (128, 128), 64), (2, 32, (256, 256), 128),
                                 (2, 16, (48,), 192), (1, 64, (64,), 128), (1, 128, (128,), 256), (1, 32, (512,), 512),
@@ -78,7 +81,7 @@ def main():
         gamma, beta = torch.rand(cout, device=DEV) + 0.5, torch.randn(cout, device=DEV)
         o_d, sc_d, sh_d = run(L, 0, kind, H, cins, cout, V, data, w, gamma, beta)
         o_w, sc_w, sh_w = run(L, WFLAGS, kind, H, cins, cout, V, data, w, gamma, beta)
-        o_2 = run(L, _lib.CONV_WINOGRAD, kind, H, cins, cout, V, data, w, gamma, beta)[0] if a.f42 else None      # F(2x2, 2x2) on the same data
+        o_2 = run(L, _lib.CONV_WINOGRAD, kind, H, cins, cout, V, data, w, gamma, beta)[0] if (a.f42 or a.f4out) else None      # F(2x2, .) on the same data
         # float64 reference
         xs = []
         for j, C in enumerate(cins):
@@ -110,6 +113,12 @@ def main():
             peak = float(ref.abs().max())
             print('F(2x2, 2x2) rms err / rms %.2e (F(4x4, 2x2): %.2f x that, %.2f x the direct kernel\'s)   F(4x4, 2x2) max err / output peak %.2e' % (
                 r_2, r_w / r_2, r_w / r_d, float((o_w[..., :cout].double() - ref).abs().max()) / peak), end='   ')
+        if a.f4out:
+            r_2 = float((o_2[..., :cout].double() - ref).pow(2).mean().sqrt()) / rms
+            peak = float(ref.abs().max())
+            print('vs float64, / output peak: max err direct %.2e F(2x2, 3x3) %.2e F(4x4, 3x3) %.2e (gate 1e-4)   rms err / rms: F(2x2, 3x3) %.2e (F(4x4, 3x3): %.2f x that, %.2f x the direct kernel\'s)' % (
+                float((o_d[..., :cout].double() - ref).abs().max()) / peak, float((o_2[..., :cout].double() - ref).abs().max()) / peak,
+                float((o_w[..., :cout].double() - ref).abs().max()) / peak, r_2, r_w / r_2, r_w / r_d), end='   ')
         print('algo %d tile %d  kind %d %4d^2 %-9s -> %3d  V=%d  max err / rms: direct %.2e winograd %.2e   rms err / rms: direct %.2e winograd %.2e   '
               'scale diff %.1e shift diff %.1e  pad cols zero %s  finite %s' % (
                   algo, tile, kind, H, '+'.join(map(str, cins)), cout, V, e_d, e_w, r_d, r_w, float((sc_d - sc_w).abs().max()),

@@ -46,6 +46,8 @@ def main():
             'layers_on_winograd_kernels': int(sum(x > 0 for x in algos)), 'layers_on_f4x4_3x3': int(sum(x == 4 for x in algos)),
             'layers_on_f4x4_2x2': int(sum(pw.unet.L.rnr_conv_winograd_tile(__import__('ctypes').byref(s['desc']), V, *s['in_hw']) == 4
                                           for s, x in zip(pw.unet.steps, algos) if x == 2)),
+            'out_layer_on_f4x4_3x3': int(sum(pw.unet.L.rnr_conv_winograd_tile(__import__('ctypes').byref(s['desc']), V, *s['in_hw']) == 4
+                                             for s, x in zip(pw.unet.steps, algos) if x == 3)),
             'max_abs_diff_winograd_vs_direct': {'max': float(m.max()), 'median': float(np.median(m)), 'p99': float(np.percentile(m, 99)),
                                                 'histogram': np.histogram(m, bins=edges)[0].tolist(), 'worst_view': int(m.argmax())},
             'psnr_db_winograd_vs_direct': {'min': float(q.min()), 'median': float(np.median(q)), 'p1': float(np.percentile(q, 1))},
