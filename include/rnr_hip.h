@@ -553,6 +553,12 @@ int rnr_sh_reconstruct(const float* basis, const float* coeff, float* out, int n
 int rnr_sh_fit(const float* samples, const float* basis, float* out, int num_samples, int num_basis,
                int num_channels, void* stream);
 
+/* Adjoint of rnr_sh_reconstruct in the coefficients: grad_coeff[b, c] = sum_s basis[s,b] * grad_out[s,c], grad_out [ns, nc]
+ * the gradient of rnr_sh_reconstruct's out.  rnr_sh_fit's kernel without the 4pi/num_samples factor: one workgroup per
+ * output and a fixed summation tree, so the result is deterministic.  grad_coeff [nb, nc] is overwritten. */
+int rnr_sh_reconstruct_backward(const float* basis, const float* grad_out, float* grad_coeff, int num_samples,
+                                int num_basis, int num_channels, void* stream);
+
 /* misc.interpolate_bilinear (misc.py:5-42): data [H,W,C], x/y [n] -> out [n,C]; optional tap index output
  * taps [n,4] int32 = (x0,y0,x1,y1) fetch indices (bit-exact integer part of the sampler). */
 int rnr_interpolate_bilinear(const float* data, int h, int w, int c, const float* x, const float* y,
@@ -615,6 +621,61 @@ int rnr_ray_renderer(const float* rays_uv, const float* rays_lt, const float* lp
                      float lp_scale_factor, float* out, float* out_specular, float* out_diffuse,
                      float* ltt_specular, float* ltt_diffuse, float* rays_color, int num_views, int height,
                      int width, void* stream);
+
+/*
+ * Adjoint of rnr_ray_renderer on the same API-shaped tensors: the path from the image loss to the light probe (and through
+ * rnr_sh_reconstruct_backward to LightingSH.coeff, train_rnr.py:376), to rays_lt and to the albedos.  The operator is linear in
+ * each of them.  No gradient for rays_uv: in the reference it comes from the rasterizer and carries none.
+ *   forward operands   rays_uv, rays_lt, lp, the albedos, the flags and lp_scale_factor exactly as given to rnr_ray_renderer;
+ *   upstream gradients g_out, g_out_specular, g_out_diffuse, g_ltt_specular, g_ltt_diffuse [N,C,H,W] and g_rays_color
+ *                      [N,R,C,H,W]; each may be NULL, meaning zero;
+ *   outputs            grad_rays_lt [N,R,C,H,W], grad_albedo_specular, grad_albedo_diffuse [N,C,H,W], grad_lp [lp_n,Hl,Wl,C];
+ *                      each may be NULL: not wanted, its work is skipped (grad_albedo_diffuse needs albedo_diffuse).
+ * With ns = R - num_ray_diffuse and a_s, a_d the albedo each group is multiplied by (1 with no_albedo):
+ *   G_os = g_out + g_out_specular,  G_od = g_out + g_out_diffuse,  G_ls = g_ltt_specular + G_os a_s,  G_ld = g_ltt_diffuse + G_od a_d;
+ *   per ray r: G_p = G_ls / ns (specular) or G_ld / num_ray_diffuse (diffuse);  grad_rays_lt[r] = G_p colour_r (the forward's
+ *   rays_color, recomputed);  G_col = g_rays_color[r] + G_p rays_lt[r];  each of the ray's four env-map taps adds
+ *   G_col * w_tap * lp_scale_factor to grad_lp at its texel;
+ *   grad_albedo_* = G_o* ltt_* (0 with no_albedo), both groups summed onto the specular albedo when the diffuse group uses it
+ *   (seperate_albedo == 0 or albedo_diffuse == NULL: grad_albedo_diffuse is then 0).  With num_ray_diffuse == 0 the diffuse
+ *   outputs are constants: g_out_diffuse and g_ltt_diffuse are ignored.
+ * Taps and weights are those of the forward (same code): the clamped indices, so no address leaves the probe whatever
+ * rays_uv holds, NaN included.  A contribution whose tap weight is 0 is never added: every ray of a background pixel
+ * (uv = -1) and every out-of-range coordinate.
+ * grad_lp is OVERWRITTEN: it is cleared on `stream` first, texels that no valid tap touches end at exactly 0, and with
+ * lp_n == 1 it is the sum over the views.  The sum is made with global float atomic adds, whose order of arrival is not
+ * fixed: grad_lp may differ in the last bits from run to run (the other outputs are deterministic).  For a texel that
+ * receives n contributions the deviation from the exact sum stays within about (n + 16) 2^-24 times the sum of their
+ * magnitudes (tests/test_gpu_ray_backward.py).
+ * Two kernel forms, chosen as in rnr_ray_renderer: channels <= 4 and num_rays <= 64 -> 64 pixels per workgroup with the uv
+ * rows through LDS; otherwise one lane per (pixel, channel).  lp_n * Hl * Wl * C < 2^31.
+ */
+int rnr_ray_renderer_backward(const float* rays_uv, const float* rays_lt, const float* lp, int lp_n, int lp_h,
+                              int lp_w, const float* albedo_specular, const float* albedo_diffuse, int channels,
+                              int num_rays, int num_ray_diffuse, int no_albedo, int seperate_albedo,
+                              float lp_scale_factor, const float* g_out, const float* g_out_specular,
+                              const float* g_out_diffuse, const float* g_ltt_specular, const float* g_ltt_diffuse,
+                              const float* g_rays_color, float* grad_rays_lt, float* grad_albedo_specular,
+                              float* grad_albedo_diffuse, float* grad_lp, int num_views, int height, int width,
+                              void* stream);
+
+/*
+ * The lighting-independent state of the fused ray stage (rnr_ray_render) unpacked into RayRenderer.forward's per-view tensors.
+ * Inputs as rnr_ray_render takes them (no probe).  Outputs:
+ *   rays_uv [N,H,W,2,R]   equirect uv of every ray, computed with rnr_ray_render's own arithmetic from the directions stored
+ *                         in net_in: the env-map taps of these uv are the fused frame's taps;
+ *   rays_lt [N,R,3,H,W]   tanh(raw + bias) + 1 with rnr_ray_render's tanh (absolute error ~1e-7);
+ *   albedo_specular, albedo_diffuse [N,3,H,W]   copies of net_in's albedo channels.
+ * Background pixels (alpha == 0) get uv = -1 and rays_lt = 0 by select, not multiply: unet_raw may hold non-finite values
+ * there (rnr_conv2d_masked skips background tiles).  Then, for any probe lp,
+ *   rnr_ray_renderer(rays_uv, rays_lt, lp, albedo_specular, albedo_diffuse, seperate_albedo = 1).out
+ * is rnr_ray_render's frame up to the order of the sums over the rays, and rnr_ray_renderer_backward is its adjoint.
+ * At most 16 specular and 16 diffuse rays; c_out_pad and c_pad multiples of 4.
+ */
+int rnr_ray_transport(const float* unet_raw, int c_out_pad, const float* bias, const float* net_in, int c_pad,
+                      const float* alpha, int num_spec, int num_diff, int albedo_diff_ch, int albedo_spec_ch,
+                      float* rays_uv, float* rays_lt, float* albedo_specular, float* albedo_diffuse,
+                      int num_views, int height, int width, void* stream);
 
 /* =====================================================================================================
  * 4. Host-side data front-end: Wavefront OBJ reader behind nr.load_obj(normalization=False, load_texture=False)

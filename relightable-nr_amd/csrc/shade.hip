@@ -842,6 +842,92 @@ ray_weights_kernel(const RayWeightParams P) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Ray transport (rnr_ray_transport): the lighting-independent state of ray_render_kernel unpacked into the tensors
+// RayRenderer.forward takes, so that the frame under ANY probe is rnr_ray_renderer of them (and its adjoint
+// rnr_ray_renderer_backward).  Same lane layout, staging and uv arithmetic as ray_render_kernel: the taps of the unpacked
+// uv are that kernel's taps.  Background pixels get uv = -1 and rays_lt = 0 by select (the out layer may have skipped their
+// tile and left non-finite values).  The outputs leave through LDS: uv rows are contiguous per pixel, rays_lt and the
+// albedos are written along the pixels of a plane.
+// ------------------------------------------------------------------------------------------------
+struct RayTransportParams {
+    const float* unet_raw; int c_out_pad;
+    const float* bias;
+    const float* net_in; int c_pad;
+    const float* alpha;
+    int n_spec, n_diff, alb_diff_ch, alb_spec_ch;
+    float* rays_uv;     // [N,H,W,2,R]
+    float* rays_lt;     // [N,R,3,H,W]
+    float* alb_spec;    // [N,3,H,W]
+    float* alb_diff;    // [N,3,H,W]
+    long npix; int hw;
+    int ni_need;
+};
+
+__global__ void __launch_bounds__(256)
+ray_transport_kernel(const RayTransportParams P) {
+    constexpr int PIX_PER_WG = RR_WG_PIX, LT_ROW = RR_WG_PIX + 1;
+    static_assert((PIX_PER_WG & (PIX_PER_WG - 1)) == 0, "the plane sweep splits its item index with a mask");
+    const long wg_pix0 = (long)blockIdx.x * PIX_PER_WG;
+    const RayLanes L(P.n_spec, P.n_diff, P.npix, wg_pix0);
+    const int lp0 = L.lp0, r = L.r, wg_valid = L.wg_valid;
+    const int R = P.n_spec + P.n_diff;
+    const long wg_n0 = wg_pix0 / P.hw;
+    const int wg_rem0 = (int)(wg_pix0 - wg_n0 * P.hw);
+    extern __shared__ __attribute__((aligned(16))) float rt_smem[];
+    const int ni_need = P.ni_need;
+    float* s_raw = rt_smem;                                 // [PIX_PER_WG][c_out_pad]
+    float* s_ni = s_raw + PIX_PER_WG * P.c_out_pad;         // [PIX_PER_WG][ni_need]
+    float* s_uv = s_ni + PIX_PER_WG * ni_need;              // [PIX_PER_WG][2 R]
+    float* s_lt = s_uv + PIX_PER_WG * 2 * R;                // [3 R][LT_ROW]
+    float al[RR_PIX];
+    L.load_alpha(P.alpha + wg_pix0, al);
+    {
+        const int q_raw = P.c_out_pad >> 2;
+        const float4* g_raw = reinterpret_cast<const float4*>(P.unet_raw + wg_pix0 * P.c_out_pad);
+        for (int i = threadIdx.x; i < wg_valid * q_raw; i += 256) reinterpret_cast<float4*>(s_raw)[i] = g_raw[i];
+        L.stage_net_in(s_ni, P.net_in + wg_pix0 * P.c_pad, P.c_pad, ni_need);
+    }
+    __syncthreads();
+    float b[3] = {0.f, 0.f, 0.f};
+    if (L.ray_live) { b[0] = P.bias[3 * r + 0]; b[1] = P.bias[3 * r + 1]; b[2] = P.bias[3 * r + 2]; }
+#pragma unroll
+    for (int k = 0; k < RR_PIX; k++) {
+        if (lp0 + k >= wg_valid || !L.ray_live) continue;
+        const float* d = s_ni + __mul24(lp0 + k, ni_need) + 3 * r;
+        const float* yr = s_raw + __mul24(lp0 + k, P.c_out_pad) + 3 * r;
+        float u, v;
+        ray_uv<TrigPoly>(f3(d[0], d[1], d[2]), al[k], u, v);
+        const bool bg = al[k] == 0.0f;
+        float* uv = s_uv + __mul24(lp0 + k, 2 * R);
+        uv[r] = bg ? -1.0f : u;
+        uv[R + r] = bg ? -1.0f : v;
+#pragma unroll
+        for (int c = 0; c < 3; c++) s_lt[(3 * r + c) * LT_ROW + lp0 + k] = bg ? 0.0f : fast_tanh_plus1f(yr[c] + b[c]);
+    }
+    __syncthreads();
+    {
+        float* dst = P.rays_uv + wg_pix0 * 2 * R;
+        for (int i = threadIdx.x; i < wg_valid * 2 * R; i += 256) dst[i] = s_uv[i];
+    }
+    // planes: item (row j, pixel px); rows 0 .. 3R-1 are rays_lt's (ray, channel) planes, then the two albedos' channels
+    for (int i = threadIdx.x; i < (3 * R + 6) * PIX_PER_WG; i += 256) {
+        const int px = i & (PIX_PER_WG - 1), j = i / PIX_PER_WG;
+        if (px >= wg_valid) continue;
+        int rem;
+        long n;
+        view_offset(wg_n0, wg_rem0 + px, P.hw, n, rem);
+        if (j < 3 * R) {
+            P.rays_lt[(n * 3 * R + j) * P.hw + rem] = s_lt[j * LT_ROW + px];
+        } else {
+            const int a = j - 3 * R, c = a % 3;
+            const float* ni = s_ni + __mul24(px, ni_need) + 3 * R + 6;
+            if (a < 3) P.alb_spec[(n * 3 + c) * P.hw + rem] = ni[P.alb_spec_ch + c];
+            else P.alb_diff[(n * 3 + c) * P.hw + rem] = ni[P.alb_diff_ch + c];
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Presenter: the float frame [N,3,H,W] as the 8-bit channel-last image cv2.imwrite makes of it (test_rnr.py:377), composited
 // over the light-probe background of test_rnr.py:386-391 where the mesh is not.  One launch behind the ray stage instead of
 // get_view_dir_map, spherical_mapping_batch, the Interpolater, a where, x255, round, clamp, cast and a channel flip.
@@ -1022,6 +1108,9 @@ frame_prepare_kernel(const FramePrepParams P) {
     }
 }
 
+// FIT: the uniform-quadrature projection of sph_harm.fit_sh_coeff (factor 4 pi / ns).  !FIT: the bare sum, which is the
+// adjoint of sh_reconstruct_kernel in the coefficients (rnr_sh_reconstruct_backward: samples = the upstream gradient)
+template <bool FIT>
 __global__ void __launch_bounds__(256)
 sh_fit_kernel(const float* __restrict__ samples, const float* __restrict__ basis, float* __restrict__ out,
               int ns, int nb, int nc) {
@@ -1036,7 +1125,7 @@ sh_fit_kernel(const float* __restrict__ samples, const float* __restrict__ basis
         if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
         __syncthreads();
     }
-    if (threadIdx.x == 0) out[o] = red[0] * (4.0f * RNR_PI_F / (float)ns);
+    if (threadIdx.x == 0) out[o] = FIT ? red[0] * (4.0f * RNR_PI_F / (float)ns) : red[0];
 }
 
 __global__ void __launch_bounds__(256)
@@ -1291,6 +1380,217 @@ ray_renderer_api_tiled_kernel(const RayApiParams P) {
         s_diff += ra_sm[((q4 * 2 + 1) * 4 + c) * 64 + lane];
     }
     finish_ray_api(P, (n * C + c) * P.hw + p, s_spec, s_diff);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Adjoint of the two kernels above (rnr_ray_renderer_backward).  With ns = R - n_diff and a_s, a_d the albedo each group is
+// multiplied by (1 with no_albedo), for output element (n, c, p):
+//     G_os = g_out + g_out_specular        G_ls = g_ltt_specular + G_os a_s
+//     G_od = g_out + g_out_diffuse         G_ld = g_ltt_diffuse  + G_od a_d
+// per ray r:  G_p = G_ls / ns (specular) or G_ld / n_diff (diffuse);  grad_rays_lt[r] = G_p colour_r;
+//     G_col = g_rays_color[r] + G_p rays_lt[r];  each of the four taps adds G_col w_tap lp_scale_factor to grad_lp at its texel;
+// grad_albedo = G_o ltt of its group (both groups onto the specular albedo when the diffuse group uses it too).
+// Taps, weights and the colour are the forward's own (envmap_taps, Taps::blend on lp * lp_scale): same indices, same bits.
+// The scatter is made of global float atomics (one per tap and channel, merged across a wave in the tiled form); a
+// contribution whose weight or G_col is 0 is never added, so texels no valid tap touches keep the 0 the entry point cleared
+// them to.
+// ------------------------------------------------------------------------------------------------
+struct RayApiBwdParams {
+    RayApiParams F;         // the forward's operands (its output pointers are unused)
+    const float *g_out, *g_out_spec, *g_out_diff, *g_ltt_spec, *g_ltt_diff;     // [N,C,H,W], NULL = zero
+    const float* g_rays_color;                                                  // [N,R,C,H,W], NULL = zero
+    float* grad_rays_lt;    // [N,R,C,H,W] or NULL
+    float *grad_alb_spec, *grad_alb_diff;   // [N,C,H,W] or NULL
+    float* grad_lp;         // [Nl,Hl,Wl,C] or NULL, cleared by the entry point
+};
+
+__device__ __forceinline__ float grad_or_zero(const float* g, size_t i) { return g ? g[i] : 0.0f; }
+
+// the upstream gradients of output element i = (n, c, pixel) folded onto its two outputs and, per ray, onto its group means
+__device__ __forceinline__ void ray_api_heads(const RayApiBwdParams& P, long i, float& G_os, float& G_od, float& gp_spec,
+                                              float& gp_diff) {
+    const RayApiParams& F = P.F;
+    const bool diff = F.n_diff > 0;         // without diffuse rays the diffuse outputs are constants
+    const float go = grad_or_zero(P.g_out, i);
+    G_os = go + grad_or_zero(P.g_out_spec, i);
+    G_od = diff ? go + grad_or_zero(P.g_out_diff, i) : 0.0f;
+    const float as = F.no_albedo ? 1.0f : F.alb_spec[i];
+    const float ad = F.no_albedo ? 1.0f : ((F.separate && F.alb_diff) ? F.alb_diff[i] : as);
+    const float G_ls = grad_or_zero(P.g_ltt_spec, i) + G_os * as;
+    const float G_ld = diff ? grad_or_zero(P.g_ltt_diff, i) + G_od * ad : 0.0f;
+    gp_spec = G_ls / (float)(F.R - F.n_diff);
+    gp_diff = diff ? G_ld / (float)F.n_diff : 0.0f;
+}
+
+// albedo gradients of output element i from the forward's sums over the specular and the diffuse rays
+__device__ __forceinline__ void finish_ray_api_bwd(const RayApiBwdParams& P, long i, float G_os, float G_od, float s_spec,
+                                                   float s_diff) {
+    const RayApiParams& F = P.F;
+    float gs = 0.f, gd = 0.f;
+    if (!F.no_albedo) {
+        gs = G_os * (s_spec / (float)(F.R - F.n_diff));
+        if (F.n_diff > 0) {
+            const float t = G_od * (s_diff / (float)F.n_diff);
+            if (F.separate && F.alb_diff) gd = t; else gs = gs + t;
+        }
+    }
+    if (P.grad_alb_spec) P.grad_alb_spec[i] = gs;
+    if (P.grad_alb_diff) P.grad_alb_diff[i] = gd;
+}
+
+__device__ __forceinline__ void scatter_tap(float* texel, float G_col, float w, float lp_scale) {
+    if (w != 0.0f && G_col != 0.0f) atomicAdd(texel, G_col * w * lp_scale);
+}
+
+// one lane per (pixel, channel), as ray_renderer_api_kernel
+__global__ void __launch_bounds__(256)
+ray_renderer_api_bwd_kernel(const RayApiBwdParams P) {
+    const RayApiParams& F = P.F;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;     // over N*C*hw
+    if (i >= F.npix * F.C) return;
+    const long n = i / ((long)F.C * F.hw);
+    const long rem = i % ((long)F.C * F.hw);
+    const int c = (int)(rem / F.hw);
+    const long p = rem % F.hw;
+    const long pix = n * F.hw + p;
+    const int n_spec = F.R - F.n_diff;
+    const size_t lp_off = F.lp_n == 1 ? 0 : (size_t)n * F.lp_h * F.lp_w * F.C;
+    const float* lp = F.lp + lp_off + c;
+    float* glp = P.grad_lp ? P.grad_lp + lp_off + c : nullptr;
+    float G_os, G_od, gp_spec, gp_diff;
+    ray_api_heads(P, i, G_os, G_od, gp_spec, gp_diff);
+    float ss = 0.f, sd = 0.f;
+    for (int r = 0; r < F.R; r++) {
+        const float u = F.rays_uv[(pix * 2 + 0) * F.R + r], v = F.rays_uv[(pix * 2 + 1) * F.R + r];
+        const Taps t = envmap_taps(u, v, F.lp_w, F.lp_h);
+        const size_t k00 = ((size_t)t.y0 * F.lp_w + t.x0) * F.C, k10 = ((size_t)t.y1 * F.lp_w + t.x0) * F.C;
+        const size_t k01 = ((size_t)t.y0 * F.lp_w + t.x1) * F.C, k11 = ((size_t)t.y1 * F.lp_w + t.x1) * F.C;
+        const float col = t.blend(lp[k00] * F.lp_scale, lp[k10] * F.lp_scale, lp[k01] * F.lp_scale, lp[k11] * F.lp_scale);
+        const size_t li = (((size_t)n * F.R + r) * F.C + c) * F.hw + p;
+        const float lt = F.rays_lt[li];
+        const float gp = r < n_spec ? gp_spec : gp_diff;
+        if (P.grad_rays_lt) P.grad_rays_lt[li] = gp * col;
+        const float prod = lt * col;
+        if (r < n_spec) ss += prod; else sd += prod;
+        if (glp) {
+            const float G_col = grad_or_zero(P.g_rays_color, li) + gp * lt;
+            scatter_tap(glp + k00, G_col, t.w00, F.lp_scale);
+            scatter_tap(glp + k10, G_col, t.w10, F.lp_scale);
+            scatter_tap(glp + k01, G_col, t.w01, F.lp_scale);
+            scatter_tap(glp + k11, G_col, t.w11, F.lp_scale);
+        }
+    }
+    if (P.grad_alb_spec || P.grad_alb_diff) finish_ray_api_bwd(P, i, G_os, G_od, ss, sd);
+}
+
+// <= 4 channels, <= 64 rays: the layout of ray_renderer_api_tiled_kernel (64 pixels per workgroup, thread (pixel lane, ray
+// quarter), uv rows through LDS, partial sums of a pixel meeting in LDS).  A wave's 64 lanes are 64 consecutive pixels on
+// ONE ray index, and on a probe of a few hundred columns neighbouring pixels mostly hit the same texels: before the atomic,
+// adjacent lanes holding the same texel add their contributions with a segmented shuffle reduction over the run, and the
+// run's first lane issues one add (3.8x faster than one add per lane, tap and channel at 16 x 512^2: DESIGN.md 3.4b;
+// the plain form is kept as scripts/experiments/ray_backward_atomic_per_tap.diff)
+__global__ void __launch_bounds__(256)
+ray_renderer_api_bwd_tiled_kernel(const RayApiBwdParams P) {
+    extern __shared__ float rb_sm[];
+    const RayApiParams& F = P.F;
+    const int R = F.R, C = F.C, n_spec = F.R - F.n_diff;
+    const long pix0 = (long)blockIdx.x * 64;
+    const int valid = (int)min((long)64, F.npix - pix0);
+    const int lane = threadIdx.x & 63, qtr = threadIdx.x >> 6;
+    const int urow = 2 * R + 1;
+    for (int i = threadIdx.x; i < valid * 2 * R; i += 256) {
+        const int px = i / (2 * R), k = i - px * 2 * R;
+        rb_sm[px * urow + k] = F.rays_uv[pix0 * 2 * R + i];
+    }
+    __syncthreads();
+    const long pix = pix0 + lane;
+    const bool live = lane < valid;
+    const long n = live ? pix / F.hw : 0, p = live ? pix % F.hw : 0;
+    const unsigned lp_off = F.lp_n == 1 ? 0u : (unsigned)n * (unsigned)(F.lp_h * F.lp_w * C);  // < 2^31 floats (entry point)
+    const float* lp = F.lp + lp_off;
+    float gp_spec[4] = {0.f, 0.f, 0.f, 0.f}, gp_diff[4] = {0.f, 0.f, 0.f, 0.f};
+    if (live) {
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            if (c >= C) break;
+            float G_os, G_od;
+            ray_api_heads(P, (n * C + c) * F.hw + p, G_os, G_od, gp_spec[c], gp_diff[c]);
+        }
+    }
+    float ss[4] = {0.f, 0.f, 0.f, 0.f}, sd[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int r = qtr; r < R; r += 4) {          // wave-uniform trip count: every lane reaches the shuffles
+        const float u = live ? rb_sm[lane * urow + r] : -1.0f, v = live ? rb_sm[lane * urow + R + r] : -1.0f;
+        const Taps t = envmap_taps(u, v, F.lp_w, F.lp_h);
+        const unsigned k[4] = {((unsigned)t.y0 * F.lp_w + t.x0) * C, ((unsigned)t.y1 * F.lp_w + t.x0) * C,
+                               ((unsigned)t.y0 * F.lp_w + t.x1) * C, ((unsigned)t.y1 * F.lp_w + t.x1) * C};
+        const float w[4] = {t.w00, t.w10, t.w01, t.w11};
+        float G_col[4] = {0.f, 0.f, 0.f, 0.f};
+        if (live) {
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                if (c >= C) break;
+                const float col = t.blend(lp[k[0] + c] * F.lp_scale, lp[k[1] + c] * F.lp_scale, lp[k[2] + c] * F.lp_scale,
+                                          lp[k[3] + c] * F.lp_scale);
+                const size_t li = (((size_t)n * R + r) * C + c) * F.hw + p;
+                const float lt = F.rays_lt[li];
+                const float gp = r < n_spec ? gp_spec[c] : gp_diff[c];
+                if (P.grad_rays_lt) P.grad_rays_lt[li] = gp * col;
+                const float prod = lt * col;
+                if (r < n_spec) ss[c] += prod; else sd[c] += prod;
+                if (P.grad_lp) G_col[c] = grad_or_zero(P.g_rays_color, li) + gp * lt;
+            }
+        }
+        if (!P.grad_lp) continue;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            // key: the texel's offset in grad_lp; -1 where there is nothing to add (such a lane is a run of its own)
+            const int key = (live && w[j] != 0.0f) ? (int)(lp_off + k[j]) : -1;
+            float val[4];
+#pragma unroll
+            for (int c = 0; c < 4; c++) val[c] = (key >= 0 && c < C) ? G_col[c] * w[j] * F.lp_scale : 0.0f;
+            const int prev = __shfl_up(key, 1, 64);
+            const bool head = lane == 0 || prev != key || key < 0;
+            const unsigned long long heads = __ballot(head);
+            const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
+            const int end = above ? lane + __ffsll((long long)above) - 1 : 63;      // last lane of this lane's run
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+#pragma unroll
+                for (int c = 0; c < 4; c++) {
+                    if (c >= C) break;
+                    const float o = __shfl_down(val[c], d, 64);
+                    if (lane + d <= end) val[c] += o;
+                }
+            }
+            if (head && key >= 0) {
+#pragma unroll
+                for (int c = 0; c < 4; c++) {
+                    if (c >= C) break;
+                    if (val[c] != 0.0f) atomicAdd(P.grad_lp + key + c, val[c]);
+                }
+            }
+        }
+    }
+    if (!P.grad_alb_spec && !P.grad_alb_diff) return;
+    __syncthreads();        // the uv tile is dead: the partial sums take its place, [quarter][spec | diff][channel][lane]
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        rb_sm[((qtr * 2 + 0) * 4 + c) * 64 + lane] = ss[c];
+        rb_sm[((qtr * 2 + 1) * 4 + c) * 64 + lane] = sd[c];
+    }
+    __syncthreads();
+    const int c = qtr;      // thread (lane, c) finishes channel c of its pixel
+    if (!live || c >= C) return;
+    float s_spec = 0.f, s_diff = 0.f;
+#pragma unroll
+    for (int q4 = 0; q4 < 4; q4++) {
+        s_spec += rb_sm[((q4 * 2 + 0) * 4 + c) * 64 + lane];
+        s_diff += rb_sm[((q4 * 2 + 1) * 4 + c) * 64 + lane];
+    }
+    const long i = (n * C + c) * F.hw + p;
+    float G_os, G_od, gs, gd;
+    ray_api_heads(P, i, G_os, G_od, gs, gd);
+    finish_ray_api_bwd(P, i, G_os, G_od, s_spec, s_diff);
 }
 
 // ---- layout helpers --------------------------------------------------------------------------------
@@ -1569,8 +1869,17 @@ extern "C" int rnr_sh_fit(const float* samples, const float* basis, float* out, 
                           int num_channels, void* stream) {
     RNR_REQUIRE(samples && basis && out && num_samples > 0 && num_basis > 0 && num_channels > 0,
                 "rnr_sh_fit: bad arguments");
-    hipLaunchKernelGGL(sh_fit_kernel, dim3(num_basis * num_channels), dim3(256), 0, as_stream(stream), samples,
+    hipLaunchKernelGGL(sh_fit_kernel<true>, dim3(num_basis * num_channels), dim3(256), 0, as_stream(stream), samples,
                        basis, out, num_samples, num_basis, num_channels);
+    return check_launch("sh_fit_kernel");
+}
+
+extern "C" int rnr_sh_reconstruct_backward(const float* basis, const float* grad_out, float* grad_coeff, int num_samples,
+                                           int num_basis, int num_channels, void* stream) {
+    RNR_REQUIRE(basis && grad_out && grad_coeff && num_samples > 0 && num_basis > 0 && num_channels > 0,
+                "rnr_sh_reconstruct_backward: bad arguments");
+    hipLaunchKernelGGL(sh_fit_kernel<false>, dim3(num_basis * num_channels), dim3(256), 0, as_stream(stream), grad_out,
+                       basis, grad_coeff, num_samples, num_basis, num_channels);
     return check_launch("sh_fit_kernel");
 }
 
@@ -1831,4 +2140,64 @@ extern "C" int rnr_ray_renderer(const float* rays_uv, const float* rays_lt, cons
         hipLaunchKernelGGL(ray_renderer_api_kernel, grid256(total), dim3(256), 0, as_stream(stream), P);
     }
     return check_launch("ray_renderer_api_kernel");
+}
+
+extern "C" int rnr_ray_renderer_backward(const float* rays_uv, const float* rays_lt, const float* lp, int lp_n, int lp_h,
+                                         int lp_w, const float* albedo_specular, const float* albedo_diffuse, int channels,
+                                         int num_rays, int num_ray_diffuse, int no_albedo, int seperate_albedo,
+                                         float lp_scale_factor, const float* g_out, const float* g_out_specular,
+                                         const float* g_out_diffuse, const float* g_ltt_specular,
+                                         const float* g_ltt_diffuse, const float* g_rays_color, float* grad_rays_lt,
+                                         float* grad_albedo_specular, float* grad_albedo_diffuse, float* grad_lp,
+                                         int num_views, int height, int width, void* stream) {
+    RNR_REQUIRE(rays_uv && rays_lt && lp && albedo_specular, "rnr_ray_renderer_backward: null pointer argument");
+    RNR_REQUIRE(num_rays > num_ray_diffuse && num_ray_diffuse >= 0, "rnr_ray_renderer_backward: bad ray counts");
+    RNR_REQUIRE(lp_n == 1 || lp_n == num_views, "rnr_ray_renderer_backward: lp batch must be 1 or N");
+    RNR_REQUIRE(num_views > 0 && height > 0 && width > 0 && channels > 0 && lp_h > 0 && lp_w > 0,
+                "rnr_ray_renderer_backward: bad sizes");
+    RNR_REQUIRE(!grad_albedo_diffuse || albedo_diffuse, "rnr_ray_renderer_backward: grad_albedo_diffuse without albedo_diffuse");
+    const size_t lp_floats = (size_t)lp_n * lp_h * lp_w * channels;
+    RNR_REQUIRE(lp_floats < ((size_t)1 << 31), "rnr_ray_renderer_backward: probe batch of 2^31 floats or more");
+    if (grad_lp) RNR_HIP(hipMemsetAsync(grad_lp, 0, lp_floats * sizeof(float), as_stream(stream)));
+    if (!grad_rays_lt && !grad_albedo_specular && !grad_albedo_diffuse && !grad_lp) return 0;
+    RayApiBwdParams P = {};
+    RayApiParams& F = P.F;
+    F.rays_uv = rays_uv; F.rays_lt = rays_lt; F.lp = lp; F.alb_spec = albedo_specular; F.alb_diff = albedo_diffuse;
+    F.lp_n = lp_n; F.lp_h = lp_h; F.lp_w = lp_w; F.C = channels; F.R = num_rays; F.n_diff = num_ray_diffuse;
+    F.no_albedo = no_albedo; F.separate = seperate_albedo; F.lp_scale = lp_scale_factor;
+    F.npix = (long)num_views * height * width; F.hw = height * width;
+    P.g_out = g_out; P.g_out_spec = g_out_specular; P.g_out_diff = g_out_diffuse; P.g_ltt_spec = g_ltt_specular;
+    P.g_ltt_diff = g_ltt_diffuse; P.g_rays_color = g_rays_color;
+    P.grad_rays_lt = grad_rays_lt; P.grad_alb_spec = grad_albedo_specular; P.grad_alb_diff = grad_albedo_diffuse;
+    P.grad_lp = grad_lp;
+    if (channels <= 4 && num_rays <= 64) {
+        const size_t lds = sizeof(float) * (size_t)std::max(64 * (2 * num_rays + 1), 4 * 2 * 4 * 64);
+        hipLaunchKernelGGL(ray_renderer_api_bwd_tiled_kernel, dim3((unsigned)((F.npix + 63) / 64)), dim3(256), lds, as_stream(stream), P);
+    } else {
+        hipLaunchKernelGGL(ray_renderer_api_bwd_kernel, grid256(F.npix * channels), dim3(256), 0, as_stream(stream), P);
+    }
+    return check_launch("ray_renderer_api_bwd_kernel");
+}
+
+extern "C" int rnr_ray_transport(const float* unet_raw, int c_out_pad, const float* bias, const float* net_in, int c_pad,
+                                 const float* alpha, int num_spec, int num_diff, int albedo_diff_ch, int albedo_spec_ch,
+                                 float* rays_uv, float* rays_lt, float* albedo_specular, float* albedo_diffuse,
+                                 int num_views, int height, int width, void* stream) {
+    RNR_REQUIRE(unet_raw && bias && net_in && alpha && rays_uv && rays_lt && albedo_specular && albedo_diffuse,
+                "rnr_ray_transport: null pointer argument");
+    RNR_REQUIRE(num_views > 0 && height > 0 && width > 0, "rnr_ray_transport: bad sizes");
+    RayTransportParams P;
+    // the lane layout of rnr_ray_render: 16 + 16 rays; no probe is read (the size arguments only pass the shared checks)
+    if (int e = ray_launch_checks("rnr_ray_transport", num_spec, num_diff, 16, 2, 2, albedo_diff_ch, albedo_spec_ch, c_pad, &P.ni_need))
+        return e;
+    RNR_REQUIRE(c_out_pad % 4 == 0 && c_out_pad >= 3 * (num_spec + num_diff), "rnr_ray_transport: c_out_pad must be a multiple of 4 covering the rays");
+    P.unet_raw = unet_raw; P.c_out_pad = c_out_pad; P.bias = bias; P.net_in = net_in; P.c_pad = c_pad; P.alpha = alpha;
+    P.n_spec = num_spec; P.n_diff = num_diff; P.alb_diff_ch = albedo_diff_ch; P.alb_spec_ch = albedo_spec_ch;
+    P.rays_uv = rays_uv; P.rays_lt = rays_lt; P.alb_spec = albedo_specular; P.alb_diff = albedo_diffuse;
+    P.npix = (long)num_views * height * width; P.hw = height * width;
+    const int R = num_spec + num_diff;
+    const size_t lds = sizeof(float) * ((size_t)RR_WG_PIX * (size_t)(c_out_pad + P.ni_need + 2 * R) + (size_t)3 * R * (RR_WG_PIX + 1));
+    RNR_REQUIRE(lds <= 64 * 1024, "rnr_ray_transport: rows too wide for the LDS staging (%zu bytes)", lds);
+    hipLaunchKernelGGL(ray_transport_kernel, ray_grid(P.npix), dim3(256), lds, as_stream(stream), P);
+    return check_launch("ray_transport_kernel");
 }

@@ -27,7 +27,7 @@ import render
 import sph_harm
 from pytorch_prototyping.pytorch_prototyping import *  # noqa: F401,F403  (the reference does the same, network.py:10)
 from pytorch_prototyping.pytorch_prototyping import Unet
-from rnr_amd import ops
+from rnr_amd import autograd, ops
 from rnr_amd.rays import ray_pivots as _ray_pivots
 
 
@@ -267,7 +267,9 @@ class RayRenderer(nn.Module):
         if lp is None:
             lp = self.lighting_model(lighting_idx, is_lp=True)
         lp_in = lp.float().contiguous()
-        out, o_s, o_d, l_s, l_d, color = ops.ray_renderer(
+        # differentiable in rays_lt, the albedos and lp (HIP backward, rnr_amd.autograd); under torch.no_grad(), or when no
+        # input requires grad, this is ops.ray_renderer itself
+        out, o_s, o_d, l_s, l_d, color = autograd.ray_renderer(
             rays_uv.float().contiguous(), rays_lt.float().contiguous(), lp_in, albedo_specular.float().contiguous(),
             albedo_diffuse.float().contiguous() if albedo_diffuse is not None else None, num_ray_diffuse, no_albedo,
             seperate_albedo, float(lp_scale_factor))
@@ -323,7 +325,7 @@ class LightingSH(nn.Module):
         self.coeff *= f[:, None, None]
 
     def reconstruct_lp(self, coeff):
-        lp = sph_harm.reconstruct_sh(coeff.detach(), self.basis_val_recon)
+        lp = sph_harm.reconstruct_sh(coeff, self.basis_val_recon)
         return lp.reshape(lp.shape[:-2] + (int(self.lp_recon_h), int(self.lp_recon_w), lp.shape[-1]))
 
 

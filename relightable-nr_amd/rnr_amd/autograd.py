@@ -1,0 +1,78 @@
+"""What is differentiable, and nothing else: the ray renderer in rays_lt, the albedos and the light probe, and the SH
+reconstruction in its coefficients — the path from an image loss to LightingSH.coeff (train_rnr.py:376).  Both backward passes
+are HIP kernels (rnr_ray_renderer_backward, rnr_sh_reconstruct_backward).
+
+`ray_renderer` and `sh_reconstruct` go through the autograd functions ONLY when grad mode is on and an input requires grad;
+otherwise they are ops.ray_renderer / ops.sh_reconstruct.  Either way the forward is the same launch and returns the same bits.
+"""
+import torch
+
+from . import ops
+
+
+def _c(g):
+    return None if g is None else g.float().contiguous()
+
+
+class RayRendererFn(torch.autograd.Function):
+    """ops.ray_renderer with the adjoint in rays_lt, lp and the albedos.  Saves its inputs; the backward kernel recomputes the
+    taps, the colours and the group sums (ltt_*) from them in the pass that has to read rays_lt anyway."""
+
+    @staticmethod
+    def forward(ctx, rays_uv, rays_lt, lp, albedo_specular, albedo_diffuse, num_ray_diffuse, no_albedo, seperate_albedo,
+                lp_scale_factor, want_rays_color):
+        ctx.save_for_backward(rays_uv, rays_lt, lp, albedo_specular, albedo_diffuse)
+        ctx.args = (num_ray_diffuse, no_albedo, seperate_albedo, lp_scale_factor)
+        outs = ops.ray_renderer(rays_uv, rays_lt, lp, albedo_specular, albedo_diffuse, num_ray_diffuse, no_albedo, seperate_albedo,
+                                lp_scale_factor, want_rays_color=want_rays_color)
+        return outs if want_rays_color else outs[:5]
+
+    @staticmethod
+    def backward(ctx, g_out, g_os, g_od, g_ls, g_ld, g_color=None):
+        rays_uv, rays_lt, lp, a_s, a_d = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g_lt, g_as, g_ad, g_lp = ops.ray_renderer_backward(
+            rays_uv, rays_lt, lp, a_s, a_d, *ctx.args, g_out=_c(g_out), g_out_specular=_c(g_os), g_out_diffuse=_c(g_od),
+            g_ltt_specular=_c(g_ls), g_ltt_diffuse=_c(g_ld), g_rays_color=_c(g_color), want_rays_lt=need[1], want_lp=need[2],
+            want_albedo_specular=need[3], want_albedo_diffuse=need[4])
+        return None, g_lt, g_lp, g_as, g_ad, None, None, None, None, None
+
+
+class SHReconstructFn(torch.autograd.Function):
+    """ops.sh_reconstruct with the adjoint in the coefficients."""
+
+    @staticmethod
+    def forward(ctx, basis, coeff):
+        ctx.save_for_backward(basis)
+        return ops.sh_reconstruct(basis, coeff)
+
+    @staticmethod
+    def backward(ctx, g):
+        basis, = ctx.saved_tensors
+        return None, (ops.sh_reconstruct_backward(basis, _c(g)) if ctx.needs_input_grad[1] else None)
+
+
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def ray_renderer(rays_uv, rays_lt, lp, albedo_specular, albedo_diffuse=None, num_ray_diffuse=0, no_albedo=False,
+                 seperate_albedo=False, lp_scale_factor=1.0, want_rays_color=True):
+    """ops.ray_renderer, differentiable in rays_lt, lp and the albedos.  rays_uv carries no gradient (in the reference it comes
+    from the rasterizer): one that requires grad raises NotImplementedError instead of yielding a silent zero."""
+    if torch.is_grad_enabled() and rays_uv.requires_grad:
+        raise NotImplementedError('ray_renderer has no gradient for rays_uv: the bilinear taps are not differentiated '
+                                  '(the reference\'s rays_uv come from the rasterizer and carry none); detach it')
+    if not _wants_grad(rays_lt, lp, albedo_specular, albedo_diffuse):
+        return ops.ray_renderer(rays_uv, rays_lt, lp, albedo_specular, albedo_diffuse, num_ray_diffuse, no_albedo,
+                                seperate_albedo, lp_scale_factor, want_rays_color=want_rays_color)
+    outs = RayRendererFn.apply(rays_uv, rays_lt, lp, albedo_specular, albedo_diffuse, int(num_ray_diffuse), bool(no_albedo),
+                               bool(seperate_albedo), float(lp_scale_factor), bool(want_rays_color))
+    return tuple(outs) if want_rays_color else tuple(outs) + (None,)
+
+
+def sh_reconstruct(basis, coeff):
+    """ops.sh_reconstruct, differentiable in coeff [nb,C] (basis is a constant)."""
+    if not _wants_grad(coeff):
+        return ops.sh_reconstruct(basis, coeff)
+    return SHReconstructFn.apply(basis.detach(), coeff)

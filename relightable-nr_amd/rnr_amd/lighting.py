@@ -6,11 +6,13 @@
                       INTER_AREA; that host-side resize is out of scope — pass the probe at the resolution you want.)
   SHLighting          LightingSH (network.py:534-627) reduced to what the frame path needs: basis on the 100x200
                       reconstruction grid, per-call reconstruction of the light probe from coefficients.
+  fit_sh_lighting     illumination estimation (what train_rnr.py:376 hands LightingSH.coeff to Adam for, reduced to the
+                      lighting alone): SH coefficients of the probe that makes a LightTransport's frames match photographs.
 """
 import numpy as np
 import torch
 
-from . import ops
+from . import autograd, ops
 
 
 def spherical_mapping(l_dir):
@@ -52,5 +54,51 @@ class SHLighting:
         self.basis_recon = ops.sh_basis(dirs.to(device), self.lmax)                                  # [h*w, nb]
 
     def light_probe(self, coeff):
-        """coeff [(lmax+1)^2, 3] -> [h,w,3]  (LightingSH.reconstruct_lp, network.py:622-627)."""
-        return ops.sh_reconstruct(self.basis_recon, coeff.float().contiguous()).reshape(self.h, self.w, -1)
+        """coeff [(lmax+1)^2, 3] -> [h,w,3]  (LightingSH.reconstruct_lp, network.py:622-627).  Differentiable in coeff."""
+        return autograd.sh_reconstruct(self.basis_recon, coeff.float().contiguous()).reshape(self.h, self.w, -1)
+
+
+def fit_sh_lighting(transport, targets, sh, coeff0=None, steps=100, make_optimizer=None, mask=None):
+    """Estimate the lighting of a capture: SH coefficients whose probe, rendered through `transport`, matches `targets`.
+
+    transport: pipeline.LightTransport of the views (the U-Net has run once; it is not run here)
+    targets:   [N,3,S,S] photographs of those views (device float32)
+    sh:        SHLighting — its lmax and reconstruction grid define the probe
+    coeff0:    [nb,3] start; default: every coefficient 0.1, the reference's initial fill (train_rnr.py:329)
+    make_optimizer(params): -> torch optimizer; default torch.optim.Adam(params, lr=1e-2) (a default to start from: nothing
+               here was tuned for it)
+    mask:      [N,3,S,S] or broadcastable to it, non-zero where the loss counts; default alpha > 0 over the three channels
+    Loss: mean squared error over the mask.  Returns (coeff [nb,3], losses [steps+1] device tensor: the loss before every
+    step and after the last — nothing is copied to the host, so the loop never waits for the GPU).
+    Each step launches rnr_sh_reconstruct, rnr_ray_renderer, rnr_ray_renderer_backward and rnr_sh_reconstruct_backward; the
+    elementwise loss and the optimizer are torch's."""
+    dev = targets.device
+    nb = (sh.lmax + 1) ** 2
+    if coeff0 is None:
+        coeff = torch.full((nb, 3), 0.1, dtype=torch.float32, device=dev)
+    else:
+        coeff = torch.as_tensor(coeff0, dtype=torch.float32).to(dev).clone()
+    if tuple(coeff.shape) != (nb, 3):
+        raise ValueError('coeff0 must be [%d, 3] for lmax %d, got %s' % (nb, sh.lmax, tuple(coeff.shape)))
+    coeff.requires_grad_(True)
+    opt = make_optimizer([coeff]) if make_optimizer is not None else torch.optim.Adam([coeff], lr=1e-2)
+    targets = targets.float()
+    if mask is None:
+        mask = (transport.alpha > 0)[:, None]
+    weight = (torch.as_tensor(mask, device=dev) != 0).expand_as(targets).float()
+    weight = weight / weight.sum()
+
+    def loss_of(c):
+        d = transport.render(sh.light_probe(c)) - targets
+        return (d * d * weight).sum()
+
+    losses = torch.empty(int(steps) + 1, dtype=torch.float32, device=dev)
+    for i in range(int(steps)):
+        opt.zero_grad(set_to_none=True)
+        loss = loss_of(coeff)
+        losses[i] = loss.detach()
+        loss.backward()
+        opt.step()
+    with torch.no_grad():
+        losses[int(steps)] = loss_of(coeff)
+    return coeff.detach(), losses

@@ -406,6 +406,32 @@ def ray_weights(net_in, alpha, lp, num_spec, num_diff, c_w, albedo_diff_ch=0, al
 
 
 @_device_op
+def ray_transport(unet_raw, bias, net_in, alpha, num_spec, num_diff, albedo_diff_ch=0, albedo_spec_ch=3, out=None):
+    """The lighting-independent state of ray_render as RayRenderer.forward's tensors (rnr_ray_transport):
+    -> (rays_uv [N,H,W,2,R], rays_lt [N,R,3,H,W], albedo_specular [N,3,H,W], albedo_diffuse [N,3,H,W]); background pixels get
+    uv = -1 and rays_lt = 0.  ray_renderer(rays_uv, rays_lt, lp, albedo_specular, albedo_diffuse, num_diff,
+    seperate_albedo=True)[0] is then ray_render's frame under lp.  out: the four tensors to fill, else they are allocated."""
+    L = _lib.load()
+    N, H, W, cop = unet_raw.shape
+    R = int(num_spec) + int(num_diff)
+    dev = unet_raw.device
+    if out is None:
+        out = (torch.empty(N, H, W, 2, R, dtype=torch.float32, device=dev), torch.empty(N, R, 3, H, W, dtype=torch.float32, device=dev),
+               torch.empty(N, 3, H, W, dtype=torch.float32, device=dev), torch.empty(N, 3, H, W, dtype=torch.float32, device=dev))
+    uv, lt, a_s, a_d = out
+    for t, name, shape in ((uv, 'rays_uv', (N, H, W, 2, R)), (lt, 'rays_lt', (N, R, 3, H, W)), (a_s, 'albedo_specular', (N, 3, H, W)),
+                           (a_d, 'albedo_diffuse', (N, 3, H, W))):
+        if tuple(_chk(t, name).shape) != shape:
+            raise RuntimeError('%s must be %s, got %s' % (name, shape, tuple(t.shape)))
+    if tuple(net_in.shape[:3]) != (N, H, W) or tuple(alpha.shape) != (N, H, W) or bias.numel() < 3 * R:
+        raise RuntimeError('ray_transport: net_in / alpha / bias do not match unet_raw %s' % (tuple(unet_raw.shape),))
+    check(L.rnr_ray_transport(_ptr(_chk(unet_raw, 'unet_raw')), cop, _ptr(_chk(bias, 'bias')), _ptr(_chk(net_in, 'net_in')),
+                              net_in.shape[-1], _ptr(_chk(alpha, 'alpha')), int(num_spec), int(num_diff), int(albedo_diff_ch),
+                              int(albedo_spec_ch), _ptr(uv), _ptr(lt), _ptr(a_s), _ptr(a_d), N, H, W, _stream()))
+    return uv, lt, a_s, a_d
+
+
+@_device_op
 def present_u8(image, alpha, proj_inv, R_inv, lp, mode='frame', rgb=False, out=None, img_hw=None):
     """The frame as test_rnr.py:376-393 presents it (rnr_present_u8): [N,H,W,3] uint8, B,G,R (cv2's order) or R,G,B (rgb=True).
     mode 'frame': q(image); 'background': q(the light probe seen along -view_dir); 'composite': the frame where alpha > 0, the
@@ -490,6 +516,19 @@ def sh_reconstruct(basis, coeff):
     out = torch.empty(basis.shape[0], coeff.shape[1], dtype=torch.float32, device=basis.device)
     check(L.rnr_sh_reconstruct(_ptr(basis), _ptr(coeff), _ptr(out), basis.shape[0], basis.shape[1], coeff.shape[1],
                                _stream()))
+    return out
+
+
+@_device_op
+def sh_reconstruct_backward(basis, grad_out):
+    """Adjoint of sh_reconstruct in the coefficients: basis [ns,nb], grad_out [ns,C] -> grad_coeff [nb,C] (deterministic)."""
+    L = _lib.load()
+    _chk(basis, 'basis'); _chk(grad_out, 'grad_out')
+    if grad_out.dim() != 2 or grad_out.shape[0] != basis.shape[0]:
+        raise RuntimeError('grad_out must be [%d, C], got %s' % (basis.shape[0], tuple(grad_out.shape)))
+    out = torch.empty(basis.shape[1], grad_out.shape[1], dtype=torch.float32, device=basis.device)
+    check(L.rnr_sh_reconstruct_backward(_ptr(basis), _ptr(grad_out), _ptr(out), basis.shape[0], basis.shape[1],
+                                        grad_out.shape[1], _stream()))
     return out
 
 
@@ -696,8 +735,9 @@ def texture_mapper(textures, uv_map, sh_basis_map=None, sh_start_ch=3):
 
 @_device_op
 def ray_renderer(rays_uv, rays_lt, lp, albedo_specular, albedo_diffuse=None, num_ray_diffuse=0, no_albedo=False,
-                 seperate_albedo=False, lp_scale_factor=1.0):
-    """network.RayRenderer.forward on API-shaped tensors -> (out, out_spec, out_diff, ltt_spec, ltt_diff, rays_color)."""
+                 seperate_albedo=False, lp_scale_factor=1.0, want_rays_color=True):
+    """network.RayRenderer.forward on API-shaped tensors -> (out, out_spec, out_diff, ltt_spec, ltt_diff, rays_color).
+    want_rays_color=False: rays_color [N,R,C,H,W] is neither allocated nor written (None in its place)."""
     L = _lib.load()
     _chk(rays_uv, 'rays_uv'); _chk(rays_lt, 'rays_lt'); _chk(lp, 'lp'); _chk(albedo_specular, 'albedo_specular')
     N, R, C, H, W = rays_lt.shape
@@ -706,9 +746,45 @@ def ray_renderer(rays_uv, rays_lt, lp, albedo_specular, albedo_diffuse=None, num
     dev = rays_lt.device
     mk = lambda: torch.empty(N, C, H, W, dtype=torch.float32, device=dev)
     out, o_s, o_d, l_s, l_d = mk(), mk(), mk(), mk(), mk()
-    color = torch.empty(N, R, C, H, W, dtype=torch.float32, device=dev)
+    color = torch.empty(N, R, C, H, W, dtype=torch.float32, device=dev) if want_rays_color else None
     check(L.rnr_ray_renderer(_ptr(rays_uv), _ptr(rays_lt), _ptr(lp), lp.shape[0], lp.shape[1], lp.shape[2],
                              _ptr(albedo_specular), _ptr(albedo_diffuse), C, R, int(num_ray_diffuse), int(bool(no_albedo)),
                              int(bool(seperate_albedo)), float(lp_scale_factor), _ptr(out), _ptr(o_s), _ptr(o_d), _ptr(l_s),
                              _ptr(l_d), _ptr(color), N, H, W, _stream()))
     return out, o_s, o_d, l_s, l_d, color
+
+
+@_device_op
+def ray_renderer_backward(rays_uv, rays_lt, lp, albedo_specular, albedo_diffuse=None, num_ray_diffuse=0, no_albedo=False,
+                          seperate_albedo=False, lp_scale_factor=1.0, g_out=None, g_out_specular=None, g_out_diffuse=None,
+                          g_ltt_specular=None, g_ltt_diffuse=None, g_rays_color=None, want_rays_lt=True,
+                          want_albedo_specular=True, want_albedo_diffuse=True, want_lp=True):
+    """Adjoint of ray_renderer (rnr_ray_renderer_backward).  Forward operands as given to ray_renderer; the upstream gradients
+    of its six outputs, None = zero -> (grad_rays_lt, grad_albedo_specular, grad_albedo_diffuse, grad_lp), None where not
+    wanted (or, for the diffuse albedo, not given).  grad_lp is summed with float atomics: last bits vary from run to run."""
+    L = _lib.load()
+    _chk(rays_uv, 'rays_uv'); _chk(rays_lt, 'rays_lt'); _chk(lp, 'lp'); _chk(albedo_specular, 'albedo_specular')
+    N, R, C, H, W = rays_lt.shape
+    if albedo_diffuse is not None:
+        _chk(albedo_diffuse, 'albedo_diffuse')
+    for g, name in ((g_out, 'g_out'), (g_out_specular, 'g_out_specular'), (g_out_diffuse, 'g_out_diffuse'),
+                    (g_ltt_specular, 'g_ltt_specular'), (g_ltt_diffuse, 'g_ltt_diffuse')):
+        if g is not None and tuple(_chk(g, name).shape) != (N, C, H, W):
+            raise RuntimeError('%s must be %s, got %s' % (name, (N, C, H, W), tuple(g.shape)))
+    if g_rays_color is not None and tuple(_chk(g_rays_color, 'g_rays_color').shape) != (N, R, C, H, W):
+        raise RuntimeError('g_rays_color must be %s, got %s' % ((N, R, C, H, W), tuple(g_rays_color.shape)))
+    if tuple(rays_uv.shape) != (N, H, W, 2, R) or lp.dim() != 4 or lp.shape[3] != C or lp.shape[0] not in (1, N):
+        raise RuntimeError('ray_renderer_backward: rays_uv %s / lp %s do not match rays_lt %s'
+                           % (tuple(rays_uv.shape), tuple(lp.shape), tuple(rays_lt.shape)))
+    dev = rays_lt.device
+    mk = lambda: torch.empty(N, C, H, W, dtype=torch.float32, device=dev)
+    g_lt = torch.empty_like(rays_lt) if want_rays_lt else None
+    g_as = mk() if want_albedo_specular else None
+    g_ad = mk() if (want_albedo_diffuse and albedo_diffuse is not None) else None
+    g_lp = torch.empty_like(lp) if want_lp else None
+    check(L.rnr_ray_renderer_backward(_ptr(rays_uv), _ptr(rays_lt), _ptr(lp), lp.shape[0], lp.shape[1], lp.shape[2],
+                                      _ptr(albedo_specular), _ptr(albedo_diffuse), C, R, int(num_ray_diffuse),
+                                      int(bool(no_albedo)), int(bool(seperate_albedo)), float(lp_scale_factor), _ptr(g_out),
+                                      _ptr(g_out_specular), _ptr(g_out_diffuse), _ptr(g_ltt_specular), _ptr(g_ltt_diffuse),
+                                      _ptr(g_rays_color), _ptr(g_lt), _ptr(g_as), _ptr(g_ad), _ptr(g_lp), N, H, W, _stream()))
+    return g_lt, g_as, g_ad, g_lp

@@ -23,7 +23,7 @@ Calling modes:
 import numpy as np
 import torch
 
-from . import ops
+from . import autograd, ops
 from .unet import UNetPlan
 
 
@@ -42,6 +42,26 @@ class FrameHandle:
     def synchronize(self):
         self.event.synchronize()
         return self.image
+
+
+class LightTransport:
+    """Everything about a set of views that does not depend on the lighting, as RayRenderer.forward's tensors
+    (RNRPipeline.light_transport): rays_uv [N,S,S,2,R], rays_lt [N,R,3,S,S], albedo_specular, albedo_diffuse [N,3,S,S] and the
+    coverage alpha [N,S,S].  The object owns the five tensors (none aliases a pipeline buffer).  render(lp) is the frame
+    under any probe without another U-Net pass."""
+
+    def __init__(self, rays_uv, rays_lt, albedo_specular, albedo_diffuse, alpha, num_diff):
+        self.rays_uv, self.rays_lt = rays_uv, rays_lt
+        self.albedo_specular, self.albedo_diffuse, self.alpha = albedo_specular, albedo_diffuse, alpha
+        self.num_diff = int(num_diff)
+
+    def render(self, lp):
+        """lp [Hl,Wl,3] or [1,Hl,Wl,3] -> frames [N,3,S,S]: RNRPipeline.render's frame under lp up to the order of the sums over
+        the rays (same taps).  Differentiable in lp — and in rays_lt and the albedos when requires_grad is set on those
+        attributes — through the HIP backward (rnr_amd.autograd.ray_renderer)."""
+        lp4 = lp.float().reshape(1, lp.shape[-3], lp.shape[-2], 3).contiguous()
+        return autograd.ray_renderer(self.rays_uv, self.rays_lt, lp4, self.albedo_specular, self.albedo_diffuse, self.num_diff,
+                                     no_albedo=False, seperate_albedo=True, lp_scale_factor=1.0, want_rays_color=False)[0]
 
 
 class _Slot:
@@ -202,6 +222,31 @@ class RNRPipeline:
                 return self._render(proj, pose, proj_inv, R_inv, keep_intermediates, lighting_idx, stage_events)
             finally:
                 self._v_uvz_override = None
+
+    def light_transport(self, proj, pose, proj_inv, R_inv):
+        """Rasterizer, shading and the U-Net ONCE for the poses [N,...] (any N: in groups the pipeline's buffers hold), then ops.ray_transport:
+        -> LightTransport, whose render(lp) gives the frames under any probe and is differentiable in it (illumination
+        estimation: lighting.fit_sh_lighting).  Needs the unfused ray stage, which keeps the out layer's raw output:
+        fuse_ray=True raises ValueError.
+        Memory: the transport keeps 2 R + 3 R + 6 floats per pixel, 1.6 GB + 0.6 GB, about 2.2 GB, for 16 views of 512 x 512
+        with 26 rays."""
+        if self.fuse_ray:
+            raise ValueError('light_transport needs the raw output of the out layer: build the pipeline with fuse_ray=False')
+        with ops.on_device(self.dev):
+            N, S, R = proj.shape[0], self.S, self.n_spec + self.n_diff
+            f32 = dict(dtype=torch.float32, device=self.dev)
+            out = (torch.empty(N, S, S, 2, R, **f32), torch.empty(N, R, 3, S, S, **f32), torch.empty(N, 3, S, S, **f32),
+                   torch.empty(N, 3, S, S, **f32))
+            alpha = torch.empty(N, S, S, **f32)
+            group, kept = self._lane_unets[0].N, self.last      # a single-stream call takes one lane's views
+            for lo in range(0, N, group):
+                hi = min(N, lo + group)
+                self.render(proj[lo:hi], pose[lo:hi], proj_inv[lo:hi], R_inv[lo:hi], keep_intermediates=True)
+                inter, self.last = self.last, kept
+                alpha[lo:hi].copy_(inter['gb']['alpha'])
+                ops.ray_transport(inter['unet_raw'], self.unet.out_bias, inter['net_in'], inter['gb']['alpha'], self.n_spec,
+                                  self.n_diff, albedo_diff_ch=0, albedo_spec_ch=3, out=tuple(t[lo:hi] for t in out))
+            return LightTransport(*out, alpha, self.n_diff)
 
     def submit(self, proj, pose, proj_inv, R_inv, lighting_idx=0):
         """One call of the reference's per-view loop (test_rnr.py:265-377), asynchronous: the poses [N <= max_views] are

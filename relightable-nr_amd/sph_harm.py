@@ -5,7 +5,7 @@ import os
 import numpy as np
 import torch
 
-from rnr_amd import ops
+from rnr_amd import autograd, ops
 
 
 def cart2sph(x, y, z):
@@ -133,12 +133,13 @@ def fit_sh_coeff(samples, sh_basis_val):
 
 
 def reconstruct_sh(sh_coeff, sh_basis_val):
-    """sph_harm.py:91-102.  coeff [nb,C] or [L,nb,C], basis [ns,nb] -> [ns,C] or [L,ns,C]."""
+    """sph_harm.py:91-102.  coeff [nb,C] or [L,nb,C], basis [ns,nb] -> [ns,C] or [L,ns,C].  The tensor branch is
+    differentiable in the coefficients (rnr_amd.autograd.sh_reconstruct), not in the basis."""
     if not torch.is_tensor(sh_coeff):
         if sh_coeff.ndim == 2:
             return (sh_basis_val[..., None] * sh_coeff[None, :]).sum(-2)
         return (sh_basis_val[None, :, :, None] * sh_coeff[:, None, :, :]).sum(-2)
     b = sh_basis_val.float().contiguous()
     if sh_coeff.dim() == 2:
-        return ops.sh_reconstruct(b, sh_coeff.float().contiguous())
-    return torch.stack([ops.sh_reconstruct(b, c.float().contiguous()) for c in sh_coeff])
+        return autograd.sh_reconstruct(b, sh_coeff.float().contiguous())
+    return torch.stack([autograd.sh_reconstruct(b, c.float().contiguous()) for c in sh_coeff])
