@@ -342,6 +342,17 @@ typedef struct rnr_conv_desc {
  * mask); rnr_conv_winograd_tile tells them apart (4 / 2), and rnr_conv_tile_count / rnr_conv_active_tiles then describe
  * 16 x 16 pixel tiles. */
 #define RNR_CONV_WINOGRAD4_OUT 64
+/* (with RNR_CONV_WINOGRAD) F(4x4, 2x2) for the 4x4 stride-2 CONVOLUTIONS (RNR_CONV4x4S2_REFLECT; RNR_CONV_WINOGRAD42 is the
+ * transposed ones' and is ignored by this kind): taken when the OUTPUT map tiles into 32 x 16 pixels, the columns into 64s, the
+ * input channels (both sources, padded) number at most 1024, the 25-plane weight image stays below 2^31 bytes and the grid gives
+ * every CU a workgroup (256 tiles; RNR_WINO42S_MIN_WGS in the environment).  The four input parity phases of a 4 x 4 output tile
+ * cost 25 multiplications each where F(2x2, 2x2) takes 36; same interpolation points and rounding behaviour as
+ * RNR_CONV_WINOGRAD42 (tests bound the error at 1e-4 of the output peak against a float64 convolution).  Everything else runs
+ * F(2x2, 2x2) / the direct kernels from the same packed buffer (the 25-plane image, 6.25 x the direct one, is stored behind the
+ * F(2x2, 2x2) image: both flags when packing AND convolving).  Non-finite inputs: an inf / NaN activation reaches every output
+ * of the 4 x 4 tiles whose 5 x 5 patch of a phase image contains it.  rnr_conv_algorithm keeps reporting 2;
+ * rnr_conv_winograd_tile tells the two forms apart (4 / 2). */
+#define RNR_CONV_WINOGRAD42S 128
 
 /* Floats in the packed weight of `d` ([taps][c_in0_pad + c_in1_pad][c_out_pad], x4 parity classes for convT). */
 size_t rnr_packed_weight_floats(const rnr_conv_desc* d);

@@ -21,7 +21,8 @@
 // product path since r03, RNR_CONV_WINOGRAD — the fp32 Winograd kernels of conv_wino.inc (F(2x2, 3x3): conv_wino_kernel),
 // conv_wino80.inc (the 80-column out layer), conv_wino2.inc / conv_wino2p.inc (F(2x2, 2x2): conv_wino2_kernel<1> for the
 // stride-2 convolution, conv_wino2p_kernel<2> for the transposed one), conv_wino4.inc (F(4x4, 3x3), RNR_CONV_WINOGRAD4) and
-// conv_wino42p.inc (F(4x4, 2x2) for the transposed convolution, RNR_CONV_WINOGRAD42), conv_wino80f4.inc (F(4x4, 3x3) for the
+// conv_wino42p.inc (F(4x4, 2x2) for the transposed convolution, RNR_CONV_WINOGRAD42), conv_wino42s.inc (the same for the stride-2
+// convolution, RNR_CONV_WINOGRAD42S; both include the kernel body conv_wino42_body.inc), conv_wino80f4.inc (F(4x4, 3x3) for the
 // 80-column out layer, RNR_CONV_WINOGRAD4_OUT).
 // Device side, shared: conv_stage.inc states tile decode, halo source / slot / prologue and the output-store preamble once for all of them.
 // Host side: CONV_TILES lists every instantiation of these kernels with its tile shape and launcher; plan_conv() tries the
@@ -81,6 +82,9 @@ constexpr int CTHREADS = 256;
 #ifndef RNR_WINO42_MIN_WGS
 #define RNR_WINO42_MIN_WGS 256       // fewer (32 x 16 class positions x 64 columns x parity class) workgroups than this, one per CU: F(2x2, 2x2)
 #endif
+#ifndef RNR_WINO42S_MIN_WGS
+#define RNR_WINO42S_MIN_WGS 256      // fewer 32 x 16 output pixel x 64 column tiles than this (one 12-wave workgroup per CU): F(2x2, 2x2) on conv_wino2_kernel<1>
+#endif
 #ifndef RNR_WINO80F4_MIN_WGS
 #define RNR_WINO80F4_MIN_WGS 256     // fewer 16 x 16 pixel x 80 column tiles than this (one 12-wave workgroup per CU): F(2x2, 3x3) on conv_wino80_kernel
 #endif
@@ -95,6 +99,7 @@ struct ConvTuning {
     int cfg4_max, cfg0_small_max;           // direct kernels: the 128 x 64 tiles (try_halo)
     int wino_min_wgs, wino2_min_wgs, wino4_min_wgs;     // smallest unsplit grid of F(2x2, 3x3), F(2x2, 2x2), F(4x4, 3x3)
     int wino42_min_wgs;                     // smallest grid of F(4x4, 2x2) (it has no split-K form)
+    int wino42s_min_wgs;                    // ... of F(4x4, 2x2) for the stride-2 convolution (no split-K form either)
     int wino80f4_min_wgs;                   // smallest grid of the out layer's F(4x4, 3x3) (no split-K form either)
     int wino_splitk;                        // 0: no split-K Winograd grids
     int par_inner;                          // 0 / 1: order of the transposed convolution's parity classes, -1: by operand size (conv_params)
@@ -106,6 +111,7 @@ static const ConvTuning& tuning() {
                                  env("RNR_CFG4_MAX", RNR_CFG4_MAX), env("RNR_CFG0_SMALL_MAX", RNR_CFG0_SMALL_MAX),
                                  env("RNR_WINO_MIN_WGS", RNR_WINO_MIN_WGS), env("RNR_WINO2_MIN_WGS", RNR_WINO2_MIN_WGS),
                                  env("RNR_WINO4_MIN_WGS", RNR_WINO4_MIN_WGS), env("RNR_WINO42_MIN_WGS", RNR_WINO42_MIN_WGS),
+                                 env("RNR_WINO42S_MIN_WGS", RNR_WINO42S_MIN_WGS),
                                  env("RNR_WINO80F4_MIN_WGS", RNR_WINO80F4_MIN_WGS),
                                  env("RNR_WINO_SPLITK", 1),
                                  env("RNR_PAR_INNER", -1), env("RNR_HALO_SLOTS", 0)};
@@ -1544,6 +1550,7 @@ pack_weight_emu_kernel(rnr_conv_desc d, const float* __restrict__ w, char* __res
 #include "conv_wino2p.inc"
 #include "conv_wino4.inc"
 #include "conv_wino42p.inc"
+#include "conv_wino42s.inc"
 #include "conv_wino80f4.inc"
 
 // mask[tile] = any(alpha > 0) over the tw x th output pixels of the tile (tile order = the halo kernels' mt index)
@@ -1568,9 +1575,9 @@ __global__ void __launch_bounds__(256) zero_f64_kernel(double* __restrict__ p, l
 
 // ---- host side: one table from tile to kernel, one plan per call ---------------------------------------------------------
 
-enum ConvFamily { GATHER, HALO, HALO_EMU, WINO, WINO80, WINO2, WINO2T, WINO4, WINO42T, WINO80F4 };
-static const int CONV_ALGORITHM[] = {0, 0, 0, 1, 3, 2, 2, 4, 2, 3};        // what rnr_conv_algorithm reports, by family
-static const int CONV_WINOGRAD_TILE[] = {0, 0, 0, 2, 2, 2, 2, 4, 4, 4};    // ... and rnr_conv_winograd_tile: m of F(m x m, r x r)
+enum ConvFamily { GATHER, HALO, HALO_EMU, WINO, WINO80, WINO2, WINO2T, WINO4, WINO42T, WINO80F4, WINO42S };
+static const int CONV_ALGORITHM[] = {0, 0, 0, 1, 3, 2, 2, 4, 2, 3, 2};     // what rnr_conv_algorithm reports, by family
+static const int CONV_WINOGRAD_TILE[] = {0, 0, 0, 2, 2, 2, 2, 4, 4, 4, 4}; // ... and rnr_conv_winograd_tile: m of F(m x m, r x r)
 typedef void (*ConvLaunch)(const dim3, const ConvParams&, hipStream_t);
 
 // A kernel instantiation per (row, emulation format, kind).  The planner takes its tiles from CONV_TILES and the launch calls
@@ -1638,6 +1645,7 @@ static const ConvTile CONV_TILES[] = {
     {WINO2T, WINO_PW, WINO_PH, 64, {{nullptr, nullptr, launch_wino2p}, {}}},        // ... transposed: the four parity classes of 16 x 8 input pixels
     {WINO42T, W42_PW, W42_PH, W42_BN, {{nullptr, nullptr, launch_wino42p}, {}}},    // F(4x4, 2x2) transposed: one parity class of 32 x 16 input pixels
     {WINO80F4, W8F_PW, W8F_PH, 80, {{launch_wino80f4, nullptr, nullptr}, {}}},      // F(4x4, 3x3), the 80-column out layer: 16 x 16 output pixels
+    {WINO42S, W42_PW, W42_PH, W42_BN, {{nullptr, launch_wino42s, nullptr}, {}}},    // F(4x4, 2x2) stride 2: 32 x 16 output pixels
 };
 
 static ConvLaunch tile_launcher(const ConvTile& t, const rnr_conv_desc* d) {
@@ -1754,6 +1762,19 @@ static ConvChoice try_wino42p(const rnr_conv_desc* d, const ConvPlan& g) {
         return NO_CHOICE;
     return grid_of(*t, d, g).wgs() >= tuning().wino42_min_wgs ? ConvChoice{t, 1} : NO_CHOICE;
 }
+static size_t wino42s_weight_floats(const rnr_conv_desc* d);
+// F(4x4, 2x2) for the 4x4 stride-2 convolution (opt-in, RNR_CONV_WINOGRAD42S): 32 x 16 output pixels x 64 columns per 12-wave
+// workgroup, one workgroup per CU — when the output map tiles, the BatchNorm table holds the input channels, the weight image
+// stays inside a 32-bit byte offset and the grid gives every CU a workgroup (RNR_WINO42S_MIN_WGS).  No split-K form and no tile
+// mask: everything else falls through to F(2x2, 2x2).
+static ConvChoice try_wino42s(const rnr_conv_desc* d, const ConvPlan& g) {
+    if (!(d->flags & RNR_CONV_WINOGRAD) || !(d->flags & RNR_CONV_WINOGRAD42S) || d->kind != RNR_CONV4x4S2_REFLECT) return NO_CHOICE;
+    const ConvTile* t = find_tile(WINO42S, d, W42_PW, W42_PH, W42_BN);
+    if (!t || d->c_out_pad % t->bn != 0 || !fits(*t, g) || d->c_in0_pad + d->c_in1_pad > W4_BN_MAXC ||
+        wino42s_weight_floats(d) * sizeof(float) >= (1ul << 31))
+        return NO_CHOICE;
+    return grid_of(*t, d, g).wgs() >= tuning().wino42s_min_wgs ? ConvChoice{t, 1} : NO_CHOICE;
+}
 
 // the 4x4 stride-2 convolution runs on the 128-column configuration of the direct kernels whatever its column count
 static bool wide_columns(const rnr_conv_desc* d, const ConvPlan& g) {
@@ -1843,6 +1864,7 @@ static const struct {
     {try_wino4, false, false, false},
     {try_wino, false, false, false},
     {try_wino42p, false, false, false},
+    {try_wino42s, false, false, false},
     {try_wino2, false, false, false},
     {try_halo, true, true, false},
     {try_gather, true, true, true},
@@ -1886,12 +1908,14 @@ static int check_desc(const rnr_conv_desc* d, const char* who) {
     RNR_REQUIRE(d->c_out > 0 && d->c_out_pad >= d->c_out && d->c_out_pad % BK == 0,
                 "%s: c_out %d / pad %d", who, d->c_out, d->c_out_pad);
     RNR_REQUIRE((d->flags & ~(RNR_CONV_STATS_PREZEROED | RNR_CONV_F32_EMU_ANY | RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD4 |
-                              RNR_CONV_WINOGRAD42 | RNR_CONV_WINOGRAD4_OUT)) == 0,
+                              RNR_CONV_WINOGRAD42 | RNR_CONV_WINOGRAD4_OUT | RNR_CONV_WINOGRAD42S)) == 0,
                 "%s: unknown flags 0x%x", who, d->flags);
     RNR_REQUIRE(!(d->flags & RNR_CONV_WINOGRAD4) || (d->flags & RNR_CONV_WINOGRAD),
                 "%s: RNR_CONV_WINOGRAD4 goes with RNR_CONV_WINOGRAD (its fallback for the shapes it does not cover)", who);
     RNR_REQUIRE(!(d->flags & RNR_CONV_WINOGRAD42) || (d->flags & RNR_CONV_WINOGRAD),
                 "%s: RNR_CONV_WINOGRAD42 goes with RNR_CONV_WINOGRAD (its fallback for the shapes it does not cover)", who);
+    RNR_REQUIRE(!(d->flags & RNR_CONV_WINOGRAD42S) || (d->flags & RNR_CONV_WINOGRAD),
+                "%s: RNR_CONV_WINOGRAD42S goes with RNR_CONV_WINOGRAD (its fallback for the shapes it does not cover)", who);
     RNR_REQUIRE(!(d->flags & RNR_CONV_WINOGRAD4_OUT) || (d->flags & RNR_CONV_WINOGRAD),
                 "%s: RNR_CONV_WINOGRAD4_OUT goes with RNR_CONV_WINOGRAD (its fallback for the shapes it does not cover)", who);
     RNR_REQUIRE((d->flags & RNR_CONV_F32_EMU_ANY) != RNR_CONV_F32_EMU_ANY, "%s: choose ONE emulation format", who);
@@ -1936,6 +1960,12 @@ static size_t wino42_weight_floats(const rnr_conv_desc* d) {     // 0: this conv
     const size_t nsteps = (size_t)(d->c_in0_pad + d->c_in1_pad) / 2;
     return (size_t)(d->c_out_pad / W42_BN) * (nsteps + W42_BDIST) * W42_STEP_FLOATS;
 }
+static size_t wino42s_weight_floats(const rnr_conv_desc* d) {    // 0: this convolution has no stride-2 F(4x4, 2x2) image
+    if (!(d->flags & RNR_CONV_WINOGRAD) || !(d->flags & RNR_CONV_WINOGRAD42S) || d->kind != RNR_CONV4x4S2_REFLECT || d->c_out_pad % W42_BN)
+        return 0;
+    const size_t nsteps = (size_t)(d->c_in0_pad + d->c_in1_pad) / 2 * 4;       // the four phases
+    return (size_t)(d->c_out_pad / W42_BN) * (nsteps + W42_BDIST) * W42S_STEP_FLOATS;
+}
 }  // namespace rnr
 static size_t packed_f32_floats(const rnr_conv_desc* d) {
     const size_t taps = d->kind == RNR_CONV3x3_REFLECT ? 9 : 16;          // 16 = 4x4 taps, or 4 parity classes x 4 taps
@@ -1950,8 +1980,10 @@ extern "C" size_t rnr_packed_weight_floats(const rnr_conv_desc* d) {
     if (d->flags & RNR_CONV_F32_EMU_F16X3) return f32 + EMU_HEADER_BYTES / 4 + f32;
     // Winograd image behind the fp32 image: 16 planes instead of 9 taps (and, with RNR_CONV_WINOGRAD4, the 36-plane image behind it)
     // (with RNR_CONV_WINOGRAD42, the transposed convolution's 25-plane image in the same place; with RNR_CONV_WINOGRAD4_OUT, the
-    // 80-column out layer's 36-plane image; at most one of the three is present)
-    return f32 + wino_weight_floats(d) + wino4_weight_floats(d) + wino42_weight_floats(d) + wino80f4_weight_floats(d);
+    // 80-column out layer's 36-plane image; with RNR_CONV_WINOGRAD42S, the stride-2 convolution's 25-plane image; at most one of
+    // the four is present)
+    return f32 + wino_weight_floats(d) + wino4_weight_floats(d) + wino42_weight_floats(d) + wino80f4_weight_floats(d) +
+           wino42s_weight_floats(d);
 }
 
 extern "C" int rnr_pack_conv_weight(const rnr_conv_desc* d, const float* weight, float* packed, void* stream) {
@@ -2004,7 +2036,13 @@ extern "C" int rnr_pack_conv_weight(const rnr_conv_desc* d, const float* weight,
                                weight, packed + total + nw, nw8);
             return check_launch("pack_weight_wino80f4_kernel");
         }
-        return 0;
+        if (!wino42s_weight_floats(d)) return 0;
+    }
+    // (64 k columns that are no multiple of 128 have no F(2x2, 2x2) image in front of this one)
+    if (const long nw42s = (long)wino42s_weight_floats(d)) {
+        hipLaunchKernelGGL(pack_weight_wino42s_kernel, dim3((unsigned)((nw42s + 255) / 256)), dim3(256), 0, as_stream(stream), *d,
+                           weight, packed + total + (long)wino_weight_floats(d), nw42s);
+        return check_launch("pack_weight_wino42s_kernel");
     }
     return 0;
 }
@@ -2106,7 +2144,7 @@ static ConvParams conv_params(const rnr_conv_desc* d, const rnr_conv_src* src0, 
     if (ray) { P.ray_w = ray->w; P.ray_bias = ray->bias; P.ray_image = ray->image; }
     const size_t f32 = packed_f32_floats(d);          // the images behind the fp32 one (rnr_packed_weight_floats)
     if (pl.tile->family == HALO_EMU) P.weight_emu = weight_packed + f32;
-    if (pl.tile->family >= WINO) P.weight_wino = weight_packed + f32 + (pl.tile->family == WINO4 || pl.tile->family == WINO42T || pl.tile->family == WINO80F4 ? wino_weight_floats(d) : 0);
+    if (pl.tile->family >= WINO) P.weight_wino = weight_packed + f32 + (pl.tile->family == WINO4 || pl.tile->family == WINO42T || pl.tile->family == WINO80F4 || pl.tile->family == WINO42S ? wino_weight_floats(d) : 0);
     if (pl.par > 1) {
         // Each parity class is its own workgroup and stages the same input halo.  With the class as the slowest tile index the
         // input is streamed from HBM four times (r02 PMC: 2.9x the compulsory bytes on the 64-column transposed conv); as

@@ -59,7 +59,9 @@ class UNetPlan:
         2.5x its rounding error (rms; <= 7.1e-6 of the output peak vs float64 on L14 - L20, all 720 frames unchanged at <= 1.85e-6 from the
         direct path, profiles/r07_wino42p_ab.txt) — for the transposed layers whose class maps tile into 32 x 16 (RNR_CONV_WINOGRAD42), and since r08
         F(4x4, 3x3) for the 80-column out layer too where its map tiles into 16 x 16 (RNR_CONV_WINOGRAD4_OUT; 3x the rounding error of its F(2x2, 3x3)
-        kernel, <= 2.5e-6 of the output peak vs float64, all 720 frames <= 1.91e-6 from the direct path; profiles/r08_wino80f4_ab.txt);
+        kernel, <= 2.5e-6 of the output peak vs float64, all 720 frames <= 1.91e-6 from the direct path; profiles/r08_wino80f4_ab.txt), and since r09
+        F(4x4, 2x2) for the 4x4 stride-2 convolutions whose output maps tile into 32 x 16 (RNR_CONV_WINOGRAD42S; 2.1x the rms error of
+        F(2x2, 2x2), <= 9.3e-6 of the output peak vs float64 on L3 - L9, all 720 frames <= 2.03e-6 from the direct path; profiles/r09_wino42s_ab.txt);
         'direct': every convolution as a direct implicit GEMM.
         None: $RNR_CONV_ALGO, else DEFAULT_CONV_ALGO.
         share_weights_with: another UNetPlan of the same network whose packed weights / BN parameters are reused
@@ -132,6 +134,10 @@ class UNetPlan:
             # benchmark network: profiles/r07_wino42p_ab.txt); conv_algo 'winograd' keeps them on F(2x2, 2x2).
             if conv_algo == 'winograd4' and kind == CONVT4x4S2 and desc.c_out_pad % 64 == 0:
                 desc.flags |= _lib.CONV_WINOGRAD42
+            # ... and F(4x4, 2x2) for the stride-2 convolutions whose output map tiles into 32 x 16 (r09, conv_wino42s_kernel:
+            # profiles/r09_wino42s_ab.txt); conv_algo 'winograd' keeps them on F(2x2, 2x2).
+            if conv_algo == 'winograd4' and kind == CONV4x4S2_REFLECT and desc.c_out_pad % 64 == 0:
+                desc.flags |= _lib.CONV_WINOGRAD42S
             # ... and F(4x4, 3x3) for the 80-column out layer (r08, conv_wino80f4_kernel: profiles/r08_wino80f4_ab.txt); conv_algo
             # 'winograd' keeps it on F(2x2, 3x3).
             if conv_algo == 'winograd4' and kind == CONV3x3_REFLECT and desc.c_out_pad == 80:

@@ -1,7 +1,7 @@
 """Winograd kernels (F(2x2, 3x3) for the 3x3 layers, F(2x2, 2x2) for the 4x4 stride-2 ones) against the direct exact-fp32
 kernels and a float64 convolution on U-Net layer shapes
 (GPU box): max |difference| relative to the rms of the output, statistics / BatchNorm scale-shift difference.
-Usage: python scripts/wino_check.py [--views 2] [--f4x4] [--f42 --views 4] [--f4out --views 4]"""
+Usage: python scripts/wino_check.py [--views 2] [--f4x4] [--f42 --views 4] [--f42s --views 16] [--f4out --views 4]"""
 import argparse
 import ctypes
 import os
@@ -49,19 +49,22 @@ def main():
     ap.add_argument('--views', type=int, default=2)
     ap.add_argument('--f4x4', action='store_true', help='RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD4: F(4x4, 3x3) where the plan takes it (set RNR_WINO4_MIN_WGS=1 to force it)')
     ap.add_argument('--f42', action='store_true', help='RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD42 on the U-Net\'s transposed layer shapes: F(4x4, 2x2) where the plan takes it (4 views fill the grid)')
+    ap.add_argument('--f42s', action='store_true', help='RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD42S on the U-Net\'s stride-2 layer shapes L3, L5, L7, L9: F(4x4, 2x2) where the plan takes it (16 views fill the grid of L9)')
     ap.add_argument('--f4out', action='store_true', help='RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD4_OUT on out-layer shapes (80 columns): F(4x4, 3x3) where the plan takes it (256 tiles of 16 x 16 fill the grid)')
     a = ap.parse_args()
     L = _lib.load()
     torch.manual_seed(1)
     V = a.views
     global WFLAGS
-    WFLAGS = _lib.CONV_WINOGRAD | (_lib.CONV_WINOGRAD4 if a.f4x4 else 0) | (_lib.CONV_WINOGRAD42 if a.f42 else 0) | (_lib.CONV_WINOGRAD4_OUT if a.f4out else 0)
+    WFLAGS = _lib.CONV_WINOGRAD | (_lib.CONV_WINOGRAD4 if a.f4x4 else 0) | (_lib.CONV_WINOGRAD42 if a.f42 else 0) | (_lib.CONV_WINOGRAD42S if a.f42s else 0) | (_lib.CONV_WINOGRAD4_OUT if a.f4out else 0)
     # --f42: L14, L16, L18, L20 of the benchmark network, a one-tile-high map and a narrow one
     f42_shapes = [(2, 32, (512, 512), 512), (2, 64, (512, 512), 256), (2, 128, (256, 256), 128), (2, 256, (128, 128), 64),
                   (2, 32, (64, 64), 64), (2, 64, (128, 128), 64)]
+    # --f42s: L3, L5, L7, L9 of the benchmark network
+    f42s_shapes = [(1, 512, (64,), 128), (1, 256, (128,), 256), (1, 128, (256,), 512), (1, 64, (512,), 512)]
     # --f4out: the benchmark's out layer (L22: 512^2, 64 + 64 -> 78) and the two out-layer shapes of the default sweep
     f4out_shapes = [(0, 512, (64, 64), 78), (0, 128, (64, 64), 78), (0, 64, (112,), 78)]
-    for kind, H, cins, cout in f42_shapes if a.f42 else f4out_shapes if a.f4out else [(0, 64, (64,), 64), (0, 128, (108,), 64), (0, 64, (128,), 128), (0, 32, (256,), 256),
+    for kind, H, cins, cout in f42_shapes if a.f42 else f42s_shapes if a.f42s else f4out_shapes if a.f4out else [(0, 64, (64,), 64), (0, 128, (108,), 64), (0, 64, (128,), 128), (0, 32, (256,), 256),
                                 (0, 32, (512,), 512), (0, 64, (64, 64), 64), (0, 128, (64, 64), 78), (0, 64, (112,), 78), (0, 16, (512,), 512), (0, 48, (32,), 192),
                                 (2, 16, (512,), 512), (2, 32, (64, 64), 64), (2, 64, (128, 128), 64), (2, 32, (256, 256), 128),
                                 (2, 16, (48,), 192), (1, 64, (64,), 128), (1, 128, (128,), 256), (1, 32, (512,), 512),
@@ -81,7 +84,7 @@ def main():
         gamma, beta = torch.rand(cout, device=DEV) + 0.5, torch.randn(cout, device=DEV)
         o_d, sc_d, sh_d = run(L, 0, kind, H, cins, cout, V, data, w, gamma, beta)
         o_w, sc_w, sh_w = run(L, WFLAGS, kind, H, cins, cout, V, data, w, gamma, beta)
-        o_2 = run(L, _lib.CONV_WINOGRAD, kind, H, cins, cout, V, data, w, gamma, beta)[0] if (a.f42 or a.f4out) else None      # F(2x2, .) on the same data
+        o_2 = run(L, _lib.CONV_WINOGRAD, kind, H, cins, cout, V, data, w, gamma, beta)[0] if (a.f42 or a.f42s or a.f4out) else None      # F(2x2, .) on the same data
         # float64 reference
         xs = []
         for j, C in enumerate(cins):
@@ -108,7 +111,7 @@ def main():
                                cout, pad16(cout), WFLAGS)
         algo = L.rnr_conv_algorithm(ctypes.byref(dsc), V, H, H)
         tile = L.rnr_conv_winograd_tile(ctypes.byref(dsc), V, H, H)
-        if a.f42:
+        if a.f42 or a.f42s:
             r_2 = float((o_2[..., :cout].double() - ref).pow(2).mean().sqrt()) / rms
             peak = float(ref.abs().max())
             print('F(2x2, 2x2) rms err / rms %.2e (F(4x4, 2x2): %.2f x that, %.2f x the direct kernel\'s)   F(4x4, 2x2) max err / output peak %.2e' % (
