@@ -552,6 +552,44 @@ int rnr_present_u8(const float* image, const float* alpha, const float* proj_inv
                    const float* lp, int lp_h, int lp_w, int mode, uint8_t* out,
                    int num_views, int height, int width, void* stream);
 
+/*
+ * The score of frames against photographs: the twelve per-view numbers of metric.compute_err_metrics (metric.py:19-84), for
+ * N views in three launches (sums and box per band of rows; SSIM per tile of 32 x 32 windows; one finaliser per view).
+ *   est, gt [N,3,H,W] (layout RNR_METRIC_PLANAR) or [N,H,W,3] (RNR_METRIC_CHANNELS_LAST); neither is written (the reference
+ *   zeroes its arguments in place outside the mask);
+ *   mask [N,H,W]: a pixel is valid where mask == 1 exactly (metric.py:29; 0.5 and NaN are not valid); NULL = every pixel valid;
+ *   every value is x = float32(v * scale) (ONE float32 product, as the reference's callers do with `* 255.0`; scale = 1 for
+ *   inputs already on the 0..255 scale) where the pixel is valid and 0 elsewhere — a select, so a NaN or an infinity outside
+ *   the mask never enters the arithmetic — then widened to double: all moments and sums are float64, no atomics, and two
+ *   calls on the same inputs give bit-identical outputs;
+ *   out [N,12] float64 in the order of the enum below; box [N,5] int32 (xmin, xmax+1, ymin, ymax+1, count) of the mask, may
+ *   be NULL; workspace: rnr_image_metrics_workspace_bytes(N, H, W) bytes, 8-byte aligned like out, every word that is read
+ *   is written earlier in the same call.
+ * With d = x_est - x_gt, S1 = sum |d|, S2 = sum d^2 over the three channels:
+ *     mae = S1 / (3 H W)        mae_bb = S1 / (3 box area)        mae_valid = S1 / (3 count);     mse* likewise from S2;
+ *     psnr* = 100 if mse* / 255^2 < 1e-10 else -10 log10(mse* / 255^2);
+ *     ssim: per channel a separable 11-tap Gaussian (sigma 1.5, float64 weights exp(-k^2/4.5) / sum) as a VALID convolution of
+ *       X, Y, X^2, Y^2, XY; C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2;
+ *       map = (2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1) * (2 s12 + C2) / (s1^2 + s2^2 + C2); mean over the map and the channels.
+ *       This is the definition pytorch_msssim.ssim(X, Y, data_range=255, size_average=False) documents; that library is not
+ *       available here and no test compares with it: parity with pytorch_msssim is unpinned (as with OpenCV above);
+ *     ssim_bb: the same on the crop to the box = the mean of the image's map over the windows that lie inside the box
+ *       (top-left corner in [ymin, ymax+1-10) x [xmin, xmax+1-10));
+ *     ssim_valid = ssim_bb: metric.py:79-82 copies ground truth over estimate pixels outside the mask, which both are 0 already.
+ * Edge cases: an empty mask gives box = 0 0 0 0 0, NaN in the six _bb / _valid error outputs and the two box SSIMs, and the
+ * whole-image outputs as usual (0, 0, 100, 1 for equal images); H < 11 or W < 11 gives ssim = NaN, a box side below 11
+ * ssim_bb = ssim_valid = NaN; compute_ssim == 0 skips the SSIM launch and gives NaN in the three SSIM outputs; a NaN inside a
+ * view's mask propagates to that view's outputs only.  Errors (NULL est, gt, out or workspace; sizes <= 0;
+ * N * 3 * H * W >= 2^31; unknown layout; misaligned out or workspace) are reported before any launch.
+ */
+enum { RNR_METRIC_PLANAR = 0, RNR_METRIC_CHANNELS_LAST = 1 };
+enum { RNR_METRIC_MAE = 0, RNR_METRIC_MAE_BB, RNR_METRIC_MAE_VALID, RNR_METRIC_MSE, RNR_METRIC_MSE_BB, RNR_METRIC_MSE_VALID,
+       RNR_METRIC_PSNR, RNR_METRIC_PSNR_BB, RNR_METRIC_PSNR_VALID, RNR_METRIC_SSIM, RNR_METRIC_SSIM_BB, RNR_METRIC_SSIM_VALID };
+size_t rnr_image_metrics_workspace_bytes(int num_views, int height, int width);
+int rnr_image_metrics(const float* est, const float* gt, const float* mask, int layout, float scale,
+                      int compute_ssim, double* out, int32_t* box, void* workspace,
+                      int num_views, int height, int width, void* stream);
+
 /* ---- spherical harmonics (sph_harm.py:41-102) ---- */
 
 /* Real orthonormal SH without Condon-Shortley phase, columns (l, m=-l..l); dirs [n,3] (need not be unit),

@@ -62,6 +62,10 @@ EMU_FLAGS = {'f32': 0, 'bf16x6': CONV_F32_EMU_BF16X6, 'f16x3': CONV_F32_EMU_F16X
 CONV3x3_REFLECT, CONV4x4S2_REFLECT, CONVT4x4S2 = 0, 1, 2
 PRESENT_MODES = {'frame': 0, 'composite': 1, 'background': 2}     # RNR_PRESENT_*
 PRESENT_RGB = 8
+METRIC_PLANAR, METRIC_CHANNELS_LAST = 0, 1                        # RNR_METRIC_* layouts
+# RNR_METRIC_* outputs, in the order of rnr_image_metrics' out columns
+METRIC_KEYS = ('mae', 'mae_bb', 'mae_valid', 'mse', 'mse_bb', 'mse_valid', 'psnr', 'psnr_bb', 'psnr_valid', 'ssim', 'ssim_bb',
+               'ssim_valid')
 
 P = ctypes.POINTER
 # name -> (restype, argtypes); must list every symbol of include/rnr_hip.h (tests/test_abi.py checks it)
@@ -127,6 +131,9 @@ SIGNATURES = {
     'rnr_view_dir_map': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     'rnr_env_background': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     'rnr_present_u8': (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'rnr_image_metrics_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'rnr_image_metrics': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                  c_int, c_void_p]),
     'rnr_tbn_map': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     'rnr_tbn_matvec': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_long, c_int, c_void_p]),
     'rnr_ray_sampler': (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -484,6 +484,48 @@ def present_u8(image, alpha, proj_inv, R_inv, lp, mode='frame', rgb=False, out=N
     return out
 
 
+_METRIC_WORKSPACES = {}
+
+
+@_device_op
+def image_metrics(est, gt, mask=None, scale=1.0, compute_ssim=True, channels_last=False, out=None, return_box=False):
+    """The score of frames against photographs (rnr_image_metrics; metric.compute_err_metrics, metric.py:19-84, for N views):
+    -> [N,12] float64 device tensor, columns in the order of _lib.METRIC_KEYS (mae, mae_bb, mae_valid, mse, mse_bb, mse_valid,
+    psnr, psnr_bb, psnr_valid, ssim, ssim_bb, ssim_valid); with return_box also [N,5] int32 (xmin, xmax+1, ymin, ymax+1, count).
+    est, gt [N,3,H,W], or [N,H,W,3] with channels_last; mask [N,H,W], valid where == 1, None = every pixel; every value is
+    float32(v * scale) on the 0..255 scale (scale=255 for frames in [0,1]).  Nothing is copied to the host and the inputs are
+    not written.  compute_ssim=False skips the SSIM launch: NaN in the last three columns.  The workspace is cached per
+    (device, N, H, W): calls of one shape on different streams of a device must not overlap."""
+    L = _lib.load()
+    _chk(est, 'est'); _chk(gt, 'gt')
+    if est.dim() != 4 or est.shape[-1 if channels_last else 1] != 3:
+        raise ValueError('image_metrics: est must be %s, got %s' % ('[N,H,W,3]' if channels_last else '[N,3,H,W]', tuple(est.shape)))
+    if gt.shape != est.shape:
+        raise ValueError('image_metrics: gt must be %s like est, got %s' % (tuple(est.shape), tuple(gt.shape)))
+    N = est.shape[0]
+    H, W = (est.shape[1], est.shape[2]) if channels_last else (est.shape[2], est.shape[3])
+    if min(N, H, W) <= 0 or N * 3 * H * W >= 2 ** 31:
+        raise ValueError('image_metrics: %d views of %d x %d: sizes must be positive and N*3*H*W below 2^31' % (N, H, W))
+    if mask is not None:
+        _chk(mask, 'mask')
+        if tuple(mask.shape) != (N, H, W):
+            raise ValueError('image_metrics: mask must be [%d,%d,%d], got %s' % (N, H, W, tuple(mask.shape)))
+    if out is None:
+        out = torch.empty(N, 12, dtype=torch.float64, device=est.device)
+    else:
+        _chk(out, 'out', torch.float64)
+        if tuple(out.shape) != (N, 12):
+            raise ValueError('image_metrics: out must be [%d,12], got %s' % (N, tuple(out.shape)))
+    box = torch.empty(N, 5, dtype=torch.int32, device=est.device) if return_box else None
+    key = (est.device.index, N, H, W)
+    ws = _METRIC_WORKSPACES.get(key)
+    if ws is None:
+        ws = _METRIC_WORKSPACES[key] = torch.empty(L.rnr_image_metrics_workspace_bytes(N, H, W), dtype=torch.uint8, device=est.device)
+    check(L.rnr_image_metrics(_ptr(est), _ptr(gt), _ptr(mask), _lib.METRIC_CHANNELS_LAST if channels_last else _lib.METRIC_PLANAR,
+                              float(scale), 1 if compute_ssim else 0, _ptr(out), _ptr(box), _ptr(ws), N, H, W, _stream()))
+    return (out, box) if return_box else out
+
+
 def calibrate_mfma_f32(device='cuda:0', seconds=0.1, waves_per_simd=2):
     """TFLOP/s this device sustains NOW in a register-resident v_mfma_f32_32x32x2_f32 loop on every SIMD
     (rnr_calibrate_mfma_f32; nominal 157.3): a probe call sizes the loop for about `seconds`.  Blocks."""

@@ -23,7 +23,7 @@ Calling modes:
 import numpy as np
 import torch
 
-from . import autograd, ops
+from . import autograd, metrics, ops
 from .unet import UNetPlan
 
 
@@ -62,6 +62,15 @@ class LightTransport:
         lp4 = lp.float().reshape(1, lp.shape[-3], lp.shape[-2], 3).contiguous()
         return autograd.ray_renderer(self.rays_uv, self.rays_lt, lp4, self.albedo_specular, self.albedo_diffuse, self.num_diff,
                                      no_albedo=False, seperate_albedo=True, lp_scale_factor=1.0, want_rays_color=False)[0]
+
+    def score(self, lp, targets, mask=None, compute_ssim=True):
+        """How well the views under lp match photographs: targets [N,3,S,S] in [0,1] -> dict of metrics.KEYS (mae, mae_bb,
+        mae_valid, mse*, psnr*, ssim*: the reference's per-view numbers, train_rnr.py:627-633), each a device [N] float64 tensor.
+        The frames are rendered without recording gradients; mask [N,S,S] or [N,1,S,S], valid where == 1, default the coverage
+        alpha.  What to call on held-out views after lighting.fit_sh_lighting.  Nothing is copied to the host."""
+        with torch.no_grad():
+            frames = self.render(lp)
+        return metrics.score_frames(frames, targets, self.alpha if mask is None else mask, compute_ssim=compute_ssim)
 
 
 class _Slot:
