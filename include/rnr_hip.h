@@ -661,6 +661,33 @@ int rnr_texture_mapper(const float* uv_map, const float* sh_basis_map, const flo
                        const int* tex_sizes_host, int num_levels, int tex_channels, int sh_start_ch,
                        float* out, int num_views, int height, int width, void* stream);
 
+/*
+ * Adjoint of rnr_texture_mapper in the textures: the path from an image loss to the neural texture (TextureMapper.textures,
+ * train_rnr.py:376).  The operator is linear in them, so no texture value is needed.  No gradient for uv_map or sh_basis_map: in
+ * the reference they come from the data loader and carry none.
+ *   forward operands   uv_map [N,H,W,2], sh_basis_map [N,H,W,9] or NULL, tex_sizes_host, num_levels, tex_channels, sh_start_ch
+ *                      exactly as given to rnr_texture_mapper (a level may also be 1 x 1 here);
+ *   upstream gradient  grad_out [N,C,H,W];
+ *   outputs            grad_textures_host: HOST array of num_levels device pointers, level l [S_l,S_l,C].
+ * With f_c(n,p) = sh_basis_map[n,p,c - sh_start_ch] on the nine SH channels (when the map is given) and 1 elsewhere, every
+ * bilinear tap (y, x) of weight w of pixel (n,p) on level l adds
+ *   (grad_out[n,c,p] * f_c(n,p)) * w      (in that product order)
+ * to grad_textures[l][y, x, c].  Taps and weights are those of the forward (same code, same bits): the clamped indices, so no
+ * address leaves a level whatever uv_map holds.  uv_map must be finite: as the forward yields NaN for a NaN uv (NaN weights on
+ * texel (0, 0)), the adjoint adds NaN there.  A contribution whose weight or whose grad_out * f is 0 is never added:
+ * out-of-range uv, background pixels under a masked loss, -0.
+ * Every level is OVERWRITTEN: it is cleared on `stream` first and texels that nothing reaches end at exactly 0.  The sums are
+ * made with float atomic adds (in LDS per workgroup, then global), whose order of arrival is not fixed: the gradients may
+ * differ in the last bits from run to run.  For a texel and channel that receives n contributions the deviation from the
+ * exact sum stays within (n + 6) 2^-24 times the sum of their magnitudes (tests/test_gpu_texture_backward.py).
+ * Two kernel forms: images of 16 x 16 pixels or more -> a workgroup per 16 x 16-pixel tile that accumulates each level's
+ * texel footprint in LDS and flushes it with one global add per entry; otherwise one lane per (pixel, channel) and one
+ * global add per tap.  1 <= num_levels <= 8; sh_start_ch + 9 <= tex_channels when sh_basis_map is given.
+ */
+int rnr_texture_mapper_backward(const float* uv_map, const float* sh_basis_map, const float* grad_out,
+                                float* const* grad_textures_host, const int* tex_sizes_host, int num_levels,
+                                int tex_channels, int sh_start_ch, int num_views, int height, int width, void* stream);
+
 /* network.RayRenderer.forward (network.py:481-527) on API-shaped tensors: rays_uv [N,H,W,2,R],
  * rays_lt [N,R,C,H,W], lp [lp_n,Hl,Wl,C] (lp_n = 1 or N), albedos [N,C,H,W] (albedo_diffuse may be NULL).
  * Outputs [N,C,H,W] (out required, others optional) and rays_color [N,R,C,H,W] (optional). */

@@ -1263,6 +1263,183 @@ texture_mapper_kernel(const TexMapParams P) {
     P.out[i] = acc;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Adjoint of texture_mapper_kernel in the textures (rnr_texture_mapper_backward).  The forward is linear in them:
+//     out[n,c,p] = f_c(n,p) sum_levels sum_taps w T_l[y, x, c],    f_c = sh[n,p,c - sh_start] on the nine SH channels, else 1
+// so with gf = g[n,c,p] * f_c(n,p) every tap adds gf * w (in that product order) to grad_T_l[y, x, c]; no texture value is read.
+// Taps and weights are the forward's own (level_taps): same clamped indices, so no address leaves a level whatever uv_map
+// holds, and the same weight bits.  A contribution whose weight or whose gf is 0 is never added (out-of-range uv, background
+// pixels under a masked loss, -0), and a wave whose lanes all hold gf = 0 issues nothing; the entry point clears every level
+// first, so untouched texels hold exactly 0.  Lanes are (pixel, channel) with the channel fastest in both forms: one wave
+// instruction adds to whole texel records (64 / C texels of 4 C contiguous bytes).  Texel offsets are 64-bit.
+// ------------------------------------------------------------------------------------------------
+struct TexMapBwdParams {
+    const float* uv_map; const float* sh;   // sh may be NULL
+    const float* g;                          // grad_out [N,C,H,W]
+    float* grad[MAX_LEVELS];                 // [S_l,S_l,C] each, cleared by the entry point
+    int tex_size[MAX_LEVELS];
+    int num_levels, C, sh_start;
+    long npix; int hw, H, W;
+};
+
+// gf of channel c at pixel p of view n
+__device__ __forceinline__ float texbwd_gf(const TexMapBwdParams& P, long n, long p, int c) {
+    const float g = P.g[(n * P.C + c) * P.hw + p];
+    return (P.sh && c >= P.sh_start && c < P.sh_start + 9) ? g * P.sh[(n * P.hw + p) * 9 + (c - P.sh_start)] : g;
+}
+__device__ __forceinline__ void texbwd_scatter_tap(float* level_c, int s, int C, int x, int y, float gf, float w) {
+    if (w != 0.0f) atomicAdd(level_c + ((size_t)y * s + x) * C, gf * w);
+}
+
+constexpr int TB_PIX = 64;      // form A: pixels per workgroup
+constexpr int TB_CH = 64;       //         channels per pass through the LDS tile
+
+// Form A, any shape: 64 consecutive pixels per workgroup.  grad_out is NCHW, so a pass stages gf of 64 pixels x up to 64 channels
+// through LDS (read along the pixels of a channel, row stride 65) and then walks the tile with the channel fastest; one global
+// atomicAdd per tap and channel.
+__global__ void __launch_bounds__(256)
+texture_mapper_bwd_kernel(const TexMapBwdParams P) {
+    __shared__ float gf_sm[TB_PIX * (TB_CH + 1)];
+    __shared__ float uv_sm[TB_PIX * 2];
+    const long pix0 = (long)blockIdx.x * TB_PIX;
+    const int valid = (int)min((long)TB_PIX, P.npix - pix0);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if ((int)threadIdx.x < valid * 2) uv_sm[threadIdx.x] = P.uv_map[pix0 * 2 + threadIdx.x];
+    const bool live = lane < valid;
+    const long n = live ? (pix0 + lane) / P.hw : 0, p = live ? (pix0 + lane) % P.hw : 0;
+    for (int c0 = 0; c0 < P.C; c0 += TB_CH) {
+        const int cw = min(TB_CH, P.C - c0);
+        __syncthreads();        // the previous pass has been read (first pass: uv_sm is written)
+        for (int ch = wv; ch < cw; ch += 4) gf_sm[lane * (TB_CH + 1) + ch] = live ? texbwd_gf(P, n, p, c0 + ch) : 0.0f;
+        __syncthreads();
+        for (int i = threadIdx.x; i < valid * cw; i += 256) {
+            const int px = i / cw, ch = i - px * cw;
+            const float gf = gf_sm[px * (TB_CH + 1) + ch];
+            if (__ballot(gf != 0.0f) == 0ull) continue;
+            if (gf == 0.0f) continue;
+            const float u = uv_sm[px * 2 + 0], v = uv_sm[px * 2 + 1];
+            for (int l = 0; l < P.num_levels; l++) {
+                const int s = P.tex_size[l];
+                const Taps t = level_taps(u, v, s);
+                float* gl = P.grad[l] + c0 + ch;
+                texbwd_scatter_tap(gl, s, P.C, t.x0, t.y0, gf, t.w00);
+                texbwd_scatter_tap(gl, s, P.C, t.x0, t.y1, gf, t.w10);
+                texbwd_scatter_tap(gl, s, P.C, t.x1, t.y0, gf, t.w01);
+                texbwd_scatter_tap(gl, s, P.C, t.x1, t.y1, gf, t.w11);
+            }
+        }
+    }
+}
+
+constexpr int TT = 16;          // form B: the workgroup's image tile is TT x TT pixels, one thread per pixel
+constexpr int TT_CH = 16;       //         channels per pass
+constexpr int TT_BOX = 8192;    //         floats of the LDS accumulator (32 KB): 512 texels of 16 channels
+
+// Form B, the tile form.  Per pass of up to 16 channels the workgroup stages gf of its 16 x 16 pixels; per level every thread
+// writes its pixel's taps to LDS and the workgroup reduces the bounding box of the texels its live pixels touch (live: some gf
+// != 0 and some weight != 0).  When box x channels fits TT_BOX floats the whole footprint is accumulated there with LDS float
+// adds and each non-zero entry is flushed with ONE global atomicAdd; when it does not (a uv seam, a silhouette, random uv) a
+// box of that capacity is laid around the texel of the tile's first live pixel and the taps outside it go straight to global
+// atomics.  LDS: 17 KB gf + 8 KB taps + 32 KB box = 57 KB, two workgroups per CU.
+__global__ void __launch_bounds__(256)
+texture_mapper_bwd_tile_kernel(const TexMapBwdParams P, int tiles_x, int tiles_y) {
+    __shared__ float gf_sm[TT * TT * (TT_CH + 1)];
+    __shared__ int4 tap_xy[TT * TT];
+    __shared__ float4 tap_w[TT * TT];
+    __shared__ float box_sm[TT_BOX];
+    __shared__ int red_sm[5];           // min x0, min y0, max x1, max y1 over the live pixels, and the first live thread
+    const int t = threadIdx.x, lane = t & 63;
+    const int tile = blockIdx.x % (tiles_x * tiles_y);
+    const long n = blockIdx.x / (tiles_x * tiles_y);
+    const int row = (tile / tiles_x) * TT + t / TT, col = (tile % tiles_x) * TT + t % TT;
+    const bool inimg = row < P.H && col < P.W;
+    const long p = inimg ? (long)row * P.W + col : 0;
+    const float u = inimg ? P.uv_map[(n * P.hw + p) * 2 + 0] : 0.0f, v = inimg ? P.uv_map[(n * P.hw + p) * 2 + 1] : 0.0f;
+    for (int c0 = 0; c0 < P.C; c0 += TT_CH) {
+        const int cw = min(TT_CH, P.C - c0);
+        const int cap = TT_BOX / cw;                    // texels the box can hold
+        bool any = false;
+        __syncthreads();        // the previous pass has been read
+        for (int ch = 0; ch < cw; ch++) {
+            const float gf = inimg ? texbwd_gf(P, n, p, c0 + ch) : 0.0f;
+            gf_sm[t * (TT_CH + 1) + ch] = gf;
+            any = any || gf != 0.0f;
+        }
+        if (!__syncthreads_or(any)) continue;           // nothing to add from this tile and these channels
+        for (int l = 0; l < P.num_levels; l++) {
+            const int s = P.tex_size[l];
+            const Taps tp = level_taps(u, v, s);
+            const bool live = any && (tp.w00 != 0.0f || tp.w10 != 0.0f || tp.w01 != 0.0f || tp.w11 != 0.0f);
+            __syncthreads();    // the previous level's taps, box and bounds have been read
+            if (t < 4) red_sm[t] = t < 2 ? 0x7fffffff : -1;
+            if (t == 4) red_sm[4] = 0x7fffffff;
+            tap_xy[t] = make_int4(tp.x0, tp.y0, tp.x1, tp.y1);
+            tap_w[t] = make_float4(tp.w00, tp.w10, tp.w01, tp.w11);
+            int mnx = live ? tp.x0 : 0x7fffffff, mny = live ? tp.y0 : 0x7fffffff, mxx = live ? tp.x1 : -1, mxy = live ? tp.y1 : -1;
+            int first = live ? t : 0x7fffffff;
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                mnx = min(mnx, __shfl_xor(mnx, d, 64)); mny = min(mny, __shfl_xor(mny, d, 64));
+                mxx = max(mxx, __shfl_xor(mxx, d, 64)); mxy = max(mxy, __shfl_xor(mxy, d, 64));
+                first = min(first, __shfl_xor(first, d, 64));
+            }
+            __syncthreads();    // red_sm is initialised
+            if (lane == 0 && first != 0x7fffffff) {
+                atomicMin(&red_sm[0], mnx); atomicMin(&red_sm[1], mny);
+                atomicMax(&red_sm[2], mxx); atomicMax(&red_sm[3], mxy);
+                atomicMin(&red_sm[4], first);
+            }
+            __syncthreads();
+            const int anchor = red_sm[4];
+            if (anchor == 0x7fffffff) continue;         // no live pixel on this level (every uv out of range)
+            int bx0 = red_sm[0], by0 = red_sm[1];
+            int bw = red_sm[2] - bx0 + 1, bh = red_sm[3] - by0 + 1;
+            if (bw > cap / bh) {                        // does not fit: a box of the capacity around the anchor's texel
+                const int ex = bx0 + bw, ey = by0 + bh; // one past the footprint
+                int side = (int)sqrtf((float)cap);
+                while (side * side > cap) side--;
+                bw = min(bw, side);
+                bh = min(bh, cap / bw);
+                bw = min(ex - bx0, cap / bh);
+                const int4 a = tap_xy[anchor];
+                bx0 = min(max(a.x - bw / 2, bx0), ex - bw);
+                by0 = min(max(a.y - bh / 2, by0), ey - bh);
+            }
+            const int nbox = bw * bh * cw;
+            for (int i = t; i < nbox; i += 256) box_sm[i] = 0.0f;
+            __syncthreads();
+            float* gl = P.grad[l] + c0;
+            for (int i = t; i < TT * TT * cw; i += 256) {       // cw rounds for every thread
+                const int px = i / cw, ch = i - px * cw;
+                const float gf = gf_sm[px * (TT_CH + 1) + ch];
+                if (__ballot(gf != 0.0f) == 0ull) continue;
+                if (gf == 0.0f) continue;
+                const int4 xy = tap_xy[px];
+                const float4 w = tap_w[px];
+                const int xs[4] = {xy.x, xy.x, xy.z, xy.z}, ys[4] = {xy.y, xy.w, xy.y, xy.w};
+                const float ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    if (ws[j] == 0.0f) continue;
+                    const int rx = xs[j] - bx0, ry = ys[j] - by0;
+                    if ((unsigned)rx < (unsigned)bw && (unsigned)ry < (unsigned)bh)
+                        atomicAdd(&box_sm[(ry * bw + rx) * cw + ch], gf * ws[j]);
+                    else
+                        atomicAdd(gl + ((size_t)ys[j] * s + xs[j]) * P.C + ch, gf * ws[j]);
+                }
+            }
+            __syncthreads();
+            for (int i = t; i < nbox; i += 256) {
+                const float val = box_sm[i];
+                if (val == 0.0f) continue;
+                const int q = i / cw, ch = i - q * cw;
+                const int ry = q / bw, rx = q - ry * bw;
+                atomicAdd(gl + ((size_t)(by0 + ry) * s + (bx0 + rx)) * P.C + ch, val);
+            }
+        }
+    }
+}
+
 // RayRenderer.forward with API-shaped inputs (network.py:481-527): one lane per (pixel, channel)
 struct RayApiParams {
     const float* rays_uv;    // [N,H,W,2,R]
@@ -1681,12 +1858,14 @@ static void transpose_pivots(float* dst, const float* src_host, int num_rays) {
         for (int k = 0; k < 3; k++) dst[r * 3 + k] = src_host[k * num_rays + r];
 }
 
-// texture-level table of a kernel parameter block.  max_level_bytes > 0 bounds a level's size: the buffer-resource path of
-// shade_inputs_kernel addresses texels with 32-bit offsets
-static int fill_texture_levels(const char* fn, const float** tex, int* tex_size, const float* const* textures_host,
-                               const int* tex_sizes_host, int num_levels, int tex_channels, size_t max_level_bytes) {
+// texture-level table of a kernel parameter block (F = const float for the forward kernels, float for the gradient levels of
+// rnr_texture_mapper_backward, which also takes a 1 x 1 level: min_size).  max_level_bytes > 0 bounds a level's size: the
+// buffer-resource path of shade_inputs_kernel addresses texels with 32-bit offsets
+template <class F>
+static int fill_texture_levels(const char* fn, F** tex, int* tex_size, F* const* textures_host, const int* tex_sizes_host,
+                               int num_levels, int tex_channels, size_t max_level_bytes, int min_size = 2) {
     for (int l = 0; l < num_levels; l++) {
-        RNR_REQUIRE(textures_host[l] && tex_sizes_host[l] >= 2, "%s: bad texture level %d", fn, l);
+        RNR_REQUIRE(textures_host[l] && tex_sizes_host[l] >= min_size, "%s: bad texture level %d", fn, l);
         RNR_REQUIRE(!max_level_bytes || (size_t)tex_sizes_host[l] * tex_sizes_host[l] * tex_channels * sizeof(float) < max_level_bytes,
                     "%s: texture level %d exceeds 2 GiB (32-bit texel offsets)", fn, l);
         tex[l] = textures_host[l];
@@ -2113,6 +2292,47 @@ extern "C" int rnr_texture_mapper(const float* uv_map, const float* sh_basis_map
     const long total = P.npix * tex_channels;
     hipLaunchKernelGGL(texture_mapper_kernel, grid256(total), dim3(256), 0, as_stream(stream), P);
     return check_launch("texture_mapper_kernel");
+}
+
+// RNR_TEXTURE_BWD_FORM=a / b forces a form (scripts/texture_backward_time.py times both in one process); read on every call
+static int texture_bwd_forced_form() {
+    const char* e = getenv("RNR_TEXTURE_BWD_FORM");
+    return !e ? 0 : (e[0] == 'a' || e[0] == 'A') ? 1 : (e[0] == 'b' || e[0] == 'B') ? 2 : 0;
+}
+
+extern "C" int rnr_texture_mapper_backward(const float* uv_map, const float* sh_basis_map, const float* grad_out,
+                                           float* const* grad_textures_host, const int* tex_sizes_host, int num_levels,
+                                           int tex_channels, int sh_start_ch, int num_views, int height, int width,
+                                           void* stream) {
+    RNR_REQUIRE(uv_map && grad_out && grad_textures_host && tex_sizes_host, "rnr_texture_mapper_backward: null pointer argument");
+    RNR_REQUIRE(num_levels >= 1 && num_levels <= MAX_LEVELS && tex_channels > 0 && num_views > 0 && height > 0 && width > 0,
+                "rnr_texture_mapper_backward: bad sizes");
+    RNR_REQUIRE(!sh_basis_map || (sh_start_ch >= 0 && sh_start_ch + 9 <= tex_channels),
+                "rnr_texture_mapper_backward: sh_start_ch + 9 > channels");
+    TexMapBwdParams P = {};
+    P.uv_map = uv_map; P.sh = sh_basis_map; P.g = grad_out;
+    // 64-bit texel offsets, as the forward: no size bound.  A 1 x 1 level is a texture like any other to the adjoint
+    if (int e = fill_texture_levels("rnr_texture_mapper_backward", P.grad, P.tex_size, grad_textures_host, tex_sizes_host, num_levels,
+                                    tex_channels, 0, 1))
+        return e;
+    P.num_levels = num_levels; P.C = tex_channels; P.sh_start = sh_start_ch;
+    P.npix = (long)num_views * height * width; P.hw = height * width; P.H = height; P.W = width;
+    for (int l = 0; l < num_levels; l++)
+        RNR_HIP(hipMemsetAsync(P.grad[l], 0, (size_t)P.tex_size[l] * P.tex_size[l] * tex_channels * sizeof(float), as_stream(stream)));
+    // the tile form (7.53 against 8.09 ms on the bench scene at 16 x 512^2 with every channel live, 2.30 against 3.36 ms with the
+    // six albedo channels alone: DESIGN.md 3.4d) wherever an image holds a whole 16 x 16 tile; one lane per (pixel, channel)
+    // for smaller images, whose tiles would be mostly empty
+    const int tiles_x = (width + TT - 1) / TT, tiles_y = (height + TT - 1) / TT;
+    const long tiles = (long)num_views * tiles_x * tiles_y;
+    const int forced = texture_bwd_forced_form();
+    const bool tile_form = forced ? forced == 2 : (height >= TT && width >= TT);
+    RNR_REQUIRE(tiles < ((long)1 << 31) && (P.npix + TB_PIX - 1) / TB_PIX < ((long)1 << 31), "rnr_texture_mapper_backward: too many pixels");
+    if (tile_form) {
+        hipLaunchKernelGGL(texture_mapper_bwd_tile_kernel, dim3((unsigned)tiles), dim3(256), 0, as_stream(stream), P, tiles_x, tiles_y);
+        return check_launch("texture_mapper_bwd_tile_kernel");
+    }
+    hipLaunchKernelGGL(texture_mapper_bwd_kernel, dim3((unsigned)((P.npix + TB_PIX - 1) / TB_PIX)), dim3(256), 0, as_stream(stream), P);
+    return check_launch("texture_mapper_bwd_kernel");
 }
 
 extern "C" int rnr_ray_renderer(const float* rays_uv, const float* rays_lt, const float* lp, int lp_n, int lp_h,

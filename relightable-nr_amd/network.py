@@ -14,6 +14,9 @@ Intentional deviations from the reference classes (all invisible to the scripts'
   * LightingSH.reconstruct_lp detaches `coeff` (inference build: no gradient flows through the HIP kernels) and returns
     [..., lp_recon_h, lp_recon_w, C]; a 2-D `init_coeff` is expanded to [num_lighting, nb, C] (the reference assigns
     the 2-D tensor and breaks its own indexing); `l_samples` is computed from the coefficients at init.
+  * Gradients: TextureMapper (in its textures), RayRenderer and LightingSH.coeff are differentiable through HIP backward
+    kernels (rnr_amd.autograd); RenderingNet / Unet are inference-only and raise NotImplementedError on an input that
+    requires grad in grad mode (the reference's U-Net is differentiable) instead of cutting the graph silently.
   * render.get_TBN_map does not raise on NaN by default (the reference's check costs three host syncs per view).
 """
 import numpy as np
@@ -57,9 +60,14 @@ class TextureMapper(nn.Module):
                 p.requires_grad = False
 
     def forward(self, uv_map, sh_basis_map=None, sh_start_ch=3):
-        """uv_map [N,H,W,2], sh_basis_map [N,H,W,9] -> [N,C,H,W] (network.py:67-91)."""
+        """uv_map [N,H,W,2], sh_basis_map [N,H,W,9] -> [N,C,H,W] (network.py:67-91).  Differentiable in the textures (HIP
+        backward, rnr_amd.autograd): gradients arrive on self.textures[l].grad; under torch.no_grad(), or with fix_texture=True,
+        this is ops.texture_mapper itself.  uv_map and sh_basis_map carry no gradient: one that requires grad raises."""
+        if torch.is_grad_enabled() and (uv_map.requires_grad or (sh_basis_map is not None and sh_basis_map.requires_grad)):
+            raise NotImplementedError('TextureMapper has no gradient for uv_map / sh_basis_map (the reference\'s come from the data '
+                                      'loader and carry none); detach them')
         sh = sh_basis_map.float().contiguous() if (sh_basis_map is not None and self._apply_sh_flag()) else None
-        return ops.texture_mapper([p.detach() for p in self.textures], uv_map.float().contiguous(), sh, sh_start_ch)
+        return autograd.texture_mapper(list(self.textures), uv_map.float().contiguous(), sh, sh_start_ch)
 
     def _apply_sh_flag(self):
         """bool(self.apply_sh) without a device -> host read per call: the buffer lives on the GPU after `.to(device)` and the

@@ -194,6 +194,9 @@ class Unet(nn.Module):
         return self.forward_fused(x, apply_tanh=False)
 
     def forward_fused(self, x, apply_tanh):
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise NotImplementedError('inference-only: the HIP U-Net has no backward and would cut the graph of its input silently; '
+                                      'detach the input or use torch.no_grad()')
         n, _, h, w = x.shape
         plan = self._plan(n, h, w, x.device)
         raw = plan.forward(ops.nchw_to_nhwc(x.float().contiguous(), plan.in_c_pad))

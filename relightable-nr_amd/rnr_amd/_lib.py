@@ -140,6 +140,8 @@ SIGNATURES = {
                                 ctypes.c_long, c_void_p]),
     'rnr_texture_mapper': (c_int, [c_void_p, c_void_p, P(c_void_p), P(c_int), c_int, c_int, c_int, c_void_p, c_int,
                                    c_int, c_int, c_void_p]),
+    'rnr_texture_mapper_backward': (c_int, [c_void_p, c_void_p, c_void_p, P(c_void_p), P(c_int), c_int, c_int, c_int, c_int,
+                                            c_int, c_int, c_void_p]),
     'rnr_ray_renderer': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                  c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_int, c_int, c_int, c_void_p]),

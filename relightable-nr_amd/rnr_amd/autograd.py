@@ -1,9 +1,14 @@
-"""What is differentiable, and nothing else: the ray renderer in rays_lt, the albedos and the light probe, and the SH
-reconstruction in its coefficients — the path from an image loss to LightingSH.coeff (train_rnr.py:376).  Both backward passes
-are HIP kernels (rnr_ray_renderer_backward, rnr_sh_reconstruct_backward).
+"""What is differentiable, and nothing else:
+  * the ray renderer in rays_lt, the albedos and the light probe, and the SH reconstruction in its coefficients — the path from
+    an image loss to LightingSH.coeff (train_rnr.py:376);
+  * the texture mapper in its textures — the path from the albedo channels of the neural image (train_rnr.py:513-514, through
+    the ray renderer's albedo gradients) or from any other gradient of the neural image to TextureMapper.textures.
+The backward passes are HIP kernels (rnr_ray_renderer_backward, rnr_sh_reconstruct_backward, rnr_texture_mapper_backward).
+The U-Net is not differentiable: RenderingNet / Unet raise on an input that requires grad.
 
-`ray_renderer` and `sh_reconstruct` go through the autograd functions ONLY when grad mode is on and an input requires grad;
-otherwise they are ops.ray_renderer / ops.sh_reconstruct.  Either way the forward is the same launch and returns the same bits.
+`ray_renderer`, `sh_reconstruct` and `texture_mapper` go through the autograd functions ONLY when grad mode is on and an input
+requires grad; otherwise they are ops.ray_renderer / ops.sh_reconstruct / ops.texture_mapper.  Either way the forward is the same
+launch and returns the same bits.
 """
 import torch
 
@@ -52,6 +57,29 @@ class SHReconstructFn(torch.autograd.Function):
         return None, (ops.sh_reconstruct_backward(basis, _c(g)) if ctx.needs_input_grad[1] else None)
 
 
+class TextureMapperFn(torch.autograd.Function):
+    """ops.texture_mapper with the adjoint in the textures.  The operator is linear in them: only uv_map and the SH map are
+    saved, and the backward computes the levels that need a gradient and no others."""
+
+    @staticmethod
+    def forward(ctx, uv_map, sh_basis_map, sh_start_ch, *textures):
+        ctx.save_for_backward(uv_map, sh_basis_map)
+        ctx.sh_start_ch = sh_start_ch
+        ctx.tex_shapes = [tuple(t.shape) for t in textures]
+        return ops.texture_mapper(list(textures), uv_map, sh_basis_map, sh_start_ch)
+
+    @staticmethod
+    def backward(ctx, g):
+        uv_map, sh_basis_map = ctx.saved_tensors
+        want = [l for l, need in enumerate(ctx.needs_input_grad[3:]) if need]
+        grads = [None] * len(ctx.tex_shapes)
+        if want:
+            got = ops.texture_mapper_backward(uv_map, sh_basis_map, _c(g), [ctx.tex_shapes[l][-2] for l in want], ctx.sh_start_ch)
+            for l, gl in zip(want, got):
+                grads[l] = gl.reshape(ctx.tex_shapes[l])
+        return (None, None, None) + tuple(grads)
+
+
 def _wants_grad(*tensors):
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
@@ -76,3 +104,17 @@ def sh_reconstruct(basis, coeff):
     if not _wants_grad(coeff):
         return ops.sh_reconstruct(basis, coeff)
     return SHReconstructFn.apply(basis.detach(), coeff)
+
+
+def texture_mapper(textures, uv_map, sh_basis_map=None, sh_start_ch=3):
+    """ops.texture_mapper, differentiable in the textures (a list of [1,S_l,S_l,C] or [S_l,S_l,C]).  uv_map and sh_basis_map carry
+    no gradient (in the reference they come from the data loader): one that requires grad raises NotImplementedError instead
+    of yielding a silent zero."""
+    if torch.is_grad_enabled():
+        for t, name in ((uv_map, 'uv_map'), (sh_basis_map, 'sh_basis_map')):
+            if t is not None and t.requires_grad:
+                raise NotImplementedError('texture_mapper has no gradient for %s: the bilinear taps and the SH factors are not '
+                                          'differentiated (the reference\'s come from the data loader and carry none); detach it' % name)
+    if not _wants_grad(*textures):
+        return ops.texture_mapper([t.detach() for t in textures], uv_map, sh_basis_map, sh_start_ch)
+    return TextureMapperFn.apply(uv_map, sh_basis_map, int(sh_start_ch), *textures)

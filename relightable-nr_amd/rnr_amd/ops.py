@@ -776,6 +776,28 @@ def texture_mapper(textures, uv_map, sh_basis_map=None, sh_start_ch=3):
 
 
 @_device_op
+def texture_mapper_backward(uv_map, sh_basis_map, grad_out, tex_sizes, sh_start_ch=3):
+    """Adjoint of texture_mapper in the textures (rnr_texture_mapper_backward): uv_map [N,H,W,2], sh_basis_map [N,H,W,9] or
+    None, grad_out [N,C,H,W], tex_sizes the side S_l of every level -> a list of [S_l,S_l,C] gradients.  Summed with float
+    atomics: last bits vary from run to run."""
+    L = _lib.load()
+    _chk(uv_map, 'uv_map'); _chk(grad_out, 'grad_out')
+    N, H, W = uv_map.shape[:3]
+    C = int(grad_out.shape[1])
+    if tuple(uv_map.shape) != (N, H, W, 2) or tuple(grad_out.shape) != (N, C, H, W):
+        raise RuntimeError('texture_mapper_backward: grad_out %s does not match uv_map %s' % (tuple(grad_out.shape), tuple(uv_map.shape)))
+    if sh_basis_map is not None and tuple(_chk(sh_basis_map, 'sh_basis_map').shape) != (N, H, W, 9):
+        raise RuntimeError('sh_basis_map must be %s, got %s' % ((N, H, W, 9), tuple(sh_basis_map.shape)))
+    nl = len(tex_sizes)
+    grads = [torch.empty(int(s), int(s), C, dtype=torch.float32, device=uv_map.device) for s in tex_sizes]
+    ptrs = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in grads])
+    sizes = (ctypes.c_int * nl)(*[int(s) for s in tex_sizes])
+    check(L.rnr_texture_mapper_backward(_ptr(uv_map), _ptr(sh_basis_map), _ptr(grad_out), ptrs, sizes, nl, C, int(sh_start_ch),
+                                        N, H, W, _stream()))
+    return grads
+
+
+@_device_op
 def ray_renderer(rays_uv, rays_lt, lp, albedo_specular, albedo_diffuse=None, num_ray_diffuse=0, no_albedo=False,
                  seperate_albedo=False, lp_scale_factor=1.0, want_rays_color=True):
     """network.RayRenderer.forward on API-shaped tensors -> (out, out_spec, out_diff, ltt_spec, ltt_diff, rays_color).
