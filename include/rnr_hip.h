@@ -503,6 +503,95 @@ int rnr_bn_finalize_batch(double* stats, const float* gamma, const float* beta, 
                           float* running_mean, float* running_var, float momentum, int num_views, int channels,
                           int c_pad, double count_per_view, float eps, void* stream);
 
+/* ---- U-Net backward (train_rnr.py:376 optimises RenderingNet's 22 convolutions and 17 BatchNorms): exact fp32 only ----
+ *
+ * Per layer, with y the raw convolution output, v = a[n,c] * y + b[n,c] (BatchNorm's scale / shift, or identity / bias) and
+ * z = act(v) what the consumers read (rnr_conv_src), the backward runs
+ *   rnr_conv_out_backward          g_z (the sum over the consumers of z) -> g_y, g_gamma / g_beta or g_bias
+ *   rnr_conv2d_weight_backward     g_y, the layer's sources -> grad_weight
+ *   per source s: rnr_conv2d(rnr_conv_backward_desc(d, s)) on g_y, then rnr_conv2d_input_backward_ring -> the gradient of s's z
+ * No entry point of this section uses atomics: every output is bit-reproducible run to run (the data gradient inherits
+ * rnr_conv2d's reproducibility, called with stats == NULL).  Emulation flags (RNR_CONV_F32_EMU_*) in a descriptor are refused.
+ */
+
+/* rnr_bn_finalize_reset (whole_batch == 0: one group per view, running_mean / running_var must be NULL) or rnr_bn_finalize_batch
+ * (whole_batch != 0: one group for the call) that also writes what the backward needs:
+ *   saved [groups, c_pad, 2] float64 = (mean, 1 / sqrt(var_biased + eps)) of every group; channels >= `channels` get (0, 0).
+ * scale / shift, the running statistics and the reset of stats are those entry points', bit for bit. */
+int rnr_bn_finalize_saved(double* stats, const float* gamma, const float* beta, float* scale, float* shift,
+                          float* running_mean, float* running_var, float momentum, double* saved, int whole_batch,
+                          int num_views, int channels, int c_pad, double count_per_view, float eps, void* stream);
+
+/* BatchNorm modes of rnr_conv_out_backward: statistics per view (UNetPlan's 'batch'), over the whole call (torch's train mode,
+ * 'batch_all'), or the running statistics (eval mode, 'running'). */
+enum { RNR_BN_BWD_BATCH = 0, RNR_BN_BWD_BATCH_ALL = 1, RNR_BN_BWD_RUNNING = 2 };
+
+/*
+ * Activation + BatchNorm (or bias) backward of one layer, in two launches (reduce, apply).
+ *   y [N,h,w,c_pad] raw convolution output; scale / shift [N,c_pad] the affine its consumers apply (NULL = 1 / 0); act RNR_ACT_*;
+ *   g_z0 [N,h,w,c_pad] upstream gradient of z, g_z1 the second consumer's (NULL = none), added to it;
+ *   gamma [channels] BatchNorm weight, NULL = no BatchNorm behind this convolution; mode RNR_BN_BWD_* (ignored without gamma);
+ *   saved [groups,c_pad,2] float64 (mean, 1 / sqrt(var + eps)): as rnr_bn_finalize_saved wrote it (groups = N for
+ *   RNR_BN_BWD_BATCH, 1 for RNR_BN_BWD_BATCH_ALL), or the running statistics in that form (1 group) for RNR_BN_BWD_RUNNING.
+ * With g_v = (g_z0 + g_z1) * (v > 0 ? 1 : slope), slope 0.2 / 0 / 1 (torch's convention at v == 0), and per group of m pixels
+ *   S1 = sum g_v,  S2 = sum g_v y,  D = r (S2 - mu S1)        (float64; (mu, r) from saved):
+ *   train modes   g_beta = sum over groups S1, g_gamma = sum over groups D, g_y = gamma r (g_v - S1/m - (y - mu) r D/m), evaluated
+ *                 in float64 per element and rounded once;
+ *   running       g_beta = S1, g_gamma = D (one group: the call), g_y = scale * g_v;
+ *   no BatchNorm  g_beta = S1 (the bias gradient), g_y = g_v; g_gamma is not written.
+ * Outputs: g_y [N,h,w,c_pad], channels >= `channels` exactly 0; g_gamma, g_beta [channels] float32, OVERWRITTEN (either may be
+ * NULL: not wanted).  The sums are float64 over per-workgroup partials in `workspace`, added in workgroup order.
+ * workspace: rnr_conv_out_backward_workspace_bytes(N, h, w, c_pad) bytes, 8-byte aligned.  c_pad: a multiple of 16, <= 1024.
+ */
+size_t rnr_conv_out_backward_workspace_bytes(int num_views, int h, int w, int c_pad);
+int rnr_conv_out_backward(const float* y, const float* scale, const float* shift, int act, const float* g_z0,
+                          const float* g_z1, const float* gamma, const double* saved, int mode, float* g_y,
+                          float* g_gamma, float* g_beta, int num_views, int h, int w, int channels, int c_pad,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Weight gradient of rnr_conv2d for the three kinds and one or two sources:
+ *   grad_weight[co, ci, tap] = sum over views and output pixels o of  g_y[n, o, co] * value(src)[n, pad(o, tap), ci]
+ * with value() the consumer-side value of rnr_conv_src, recomputed from raw + scale / shift / act while staging, exactly as the
+ * forward stages it.  (in_h, in_w), d, src0, src1 as given to rnr_conv2d; g_y [N,Ho,Wo,c_out_pad].
+ * grad_weight is written in torch's layout — [c_out, c_in0 + c_in1, k, k], or [c_in0 + c_in1, c_out, 4, 4] for RNR_CONVT4x4S2
+ * — live channels only, OVERWRITTEN.  An implicit GEMM on v_mfma_f32_32x32x2_f32 with M = output channels, N = input channels
+ * of one tap and K = pixels; K is split over pixel ranges so that the grid fills the chip, every range writes a partial slab
+ * into `workspace` and a second launch adds the slabs in range order: no float atomics, bit-reproducible.
+ * workspace: rnr_conv2d_weight_backward_workspace_bytes(d, N, in_h, in_w) bytes, 16-byte aligned.
+ */
+size_t rnr_conv2d_weight_backward_workspace_bytes(const rnr_conv_desc* d, int num_views, int in_h, int in_w);
+int rnr_conv2d_weight_backward(const rnr_conv_desc* d, const rnr_conv_src* src0, const rnr_conv_src* src1,
+                               const float* g_y, float* grad_weight, int num_views, int in_h, int in_w,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * The data gradient of a convolution is one of the forward kernels run on g_y, except on a border ring:
+ *   RNR_CONV3x3_REFLECT    rnr_conv2d of the same kind with W'[ci, co, ky, kx] = W[co, ci, 2 - ky, 2 - kx]; it reflects g_y where the
+ *                          adjoint wants zero and lacks the fold of the padding: rows {0, 1, H-2, H-1} and columns {0, 1, W-2, W-1};
+ *   RNR_CONV4x4S2_REFLECT  RNR_CONVT4x4S2 with the forward weight read as [in, out, 4, 4]; lacks the fold: rows {1, H-2}, columns
+ *                          {1, W-2};
+ *   RNR_CONVT4x4S2         RNR_CONV4x4S2_REFLECT with the forward weight read as [out, in, 4, 4]; reflects where zero is wanted:
+ *                          rows {0, H-1}, columns {0, W-1}.
+ * rnr_conv_backward_desc fills the descriptor of that convolution for source `source` (0 / 1) of forward descriptor d: one
+ * source of c_out (c_out_pad) channels — g_y, no affine, RNR_ACT_NONE —, c_in_s (c_in_s_pad) output columns, and the forward's
+ * algorithm choice: RNR_CONV_WINOGRAD if d has it, plus the F(4x4, .) flag of the gradient's own kind, under that flag's
+ * column rule, if d has any of them.  Its weight (sliced on the input-channel axis for two sources) is packed with
+ * rnr_pack_conv_weight like any other.
+ * rnr_conv2d_input_backward_ring then OVERWRITES the ring pixels of grad_in [N,H,W,c_in_s_pad] (H, W = the forward's input map)
+ * with the exact adjoint, the defining sum over the (output pixel, tap) pairs that read the pixel, as an fmaf chain over
+ * (co, oy, ky, ox, kx) in that order; padding channels of those pixels get 0.  weight: the FORWARD weight in torch's layout,
+ * all sources.  Correct for every size the forward accepts, including H = 2 and H = 3 where the fold rows coincide.
+ */
+int rnr_conv_backward_desc(const rnr_conv_desc* d, int source, rnr_conv_desc* out);
+int rnr_conv2d_input_backward_ring(const rnr_conv_desc* d, int source, const float* g_y, const float* weight,
+                                   float* grad_in, int num_views, int in_h, int in_w, void* stream);
+
+/* Adjoint of rnr_nhwc_to_nchw: g_raw[n,h,w,c] = g_out[n,c,h,w] * (apply_tanh ? 1 - out[n,c,h,w]^2 : 1), out the forward's result;
+ * g_raw [n,h,w,c_pad] with channels >= c exactly 0.  (The bias gradient is rnr_conv_out_backward's g_beta on g_raw.) */
+int rnr_unet_out_backward(const float* g_out, const float* out, int apply_tanh, float* g_raw, int n, int c, int h,
+                          int w, int c_pad, void* stream);
+
 /* Layout helpers for the drop-in RenderingNet.forward (NCHW in / NCHW out). */
 int rnr_nchw_to_nhwc(const float* in, float* out, int n, int c, int h, int w, int c_pad, void* stream);
 /* out[n,c,h,w] = f(in[n,h,w,c] + bias[c]) with bias optional (NULL) and f = tanhf when apply_tanh != 0 */

@@ -216,6 +216,11 @@ class RenderingNet(nn.Module):
                         out_channels_gcn=out_channels_gcn, use_gcn=use_gcn, outermost_highway_mode=outermost_highway_mode)
         self.tanh = nn.Tanh()
 
+    def enable_hip_backward(self, flag=True):
+        """Train this network on the HIP backward (pytorch_prototyping.Unet.enable_hip_backward)."""
+        self.net.enable_hip_backward(flag)
+        return self
+
     def forward(self, input, v_fea):
         return self.net.forward_fused(input, apply_tanh=True)      # tanh fused into the layout epilogue
 

@@ -114,6 +114,7 @@ class Unet(nn.Module):
         self.out_layer = nn.Sequential(Conv2dSame(2 * nf0, out_channels, kernel_size=3, bias=True))
         self.out_layer_weight = self.out_layer[0].weight
         self._plans, self._plan_versions = {}, {}
+        self._hip_backward = False
         self.register_load_state_dict_post_hook(lambda m, k: m._plans.clear())
 
     def _apply(self, fn, *a, **k):     # .to()/.cuda() moves the weights: plans are rebuilt lazily
@@ -193,10 +194,77 @@ class Unet(nn.Module):
         pass is not executed here, so those side effects are absent (outputs are unaffected)."""
         return self.forward_fused(x, apply_tanh=False)
 
+    def enable_hip_backward(self, flag=True):
+        """Opt in to (or out of) training on the HIP backward (rnr_amd.autograd.UNetFn): a call in grad mode whose input or any
+        live parameter requires grad then records itself in the autograd graph — parameters get `.grad`, the input's graph
+        continues.  Off (the default) nothing changes: such an input is refused as before.  Exact fp32; Dropout2d modules must be
+        in eval mode (train-mode dropout has no HIP form yet); `fuse.*` and v_fea never reach the output and get no gradient."""
+        self._hip_backward = bool(flag)
+        return self
+
+    def _live_params(self):
+        """(state-dict key, parameter) of the live path, one entry per tensor (aliases such as in_layer.0.weight dropped)."""
+        seen, res = set(), []
+        for k, p in self.state_dict(keep_vars=True).items():
+            if isinstance(p, nn.Parameter) and '.fuse.' not in '.' + k and id(p) not in seen:
+                seen.add(id(p))
+                res.append((k, p))
+        return res
+
+    def _train_plan(self, n, h, w, device):
+        st = self._structure()
+        if any(m.training for m in st['dropout']):
+            raise NotImplementedError('Dropout2d in training mode has no HIP backward yet: put the Dropout2d modules in eval mode '
+                                      '(for m in net.modules(): isinstance(m, nn.Dropout2d) and m.eval())')
+        bn_train = [m.training for m in st['bn']]
+        if len(set(bn_train)) > 1:
+            raise NotImplementedError('mixed BatchNorm train/eval modes')
+        mode = 'batch_all' if (bn_train and bn_train[0]) else 'running'
+        for m in self._live_batchnorms():
+            if m.eps != 1e-5 or m.momentum != 0.1:
+                raise NotImplementedError('Unet: BatchNorm2d(eps=%r, momentum=%r) — the HIP U-Net implements the reference\'s '
+                                          'eps=1e-5, momentum=0.1 only' % (m.eps, m.momentum))
+        key = (h, w, str(device), mode, 'train')
+        ver = self._weights_version()
+        plan = self._plans.get(key)
+        sd = None
+        if plan is None or plan.N < n:
+            cin, cout, nf0, nd = self.cfg
+            sd = {'net.' + k: v for k, v in self.state_dict().items()}
+            self._plans.pop(key, None)
+            plan = UNetPlan(sd, cin, cout, nf0, nd, (h, w), max(n, plan.N if plan is not None else 0), device, bn_mode=mode,
+                            update_running_stats=(mode == 'batch_all'), training=True)
+            self._plans[key] = plan
+        elif self._plan_versions.get(key) != ver:
+            # an optimiser step moved the weights: refresh them in place, the plan and its buffers stay
+            plan.repack({'net.' + k: v for k, v in self.state_dict().items()})
+        self._plan_versions[key] = ver
+        return plan
+
+    def _forward_train(self, x, apply_tanh):
+        from rnr_amd.autograd import UNetFn
+        n, _, h, w = x.shape
+        plan = self._train_plan(n, h, w, x.device)
+        sdv = self.state_dict(keep_vars=True)       # the plan names every live tensor by ONE of its state-dict keys
+        keys = tuple(plan.param_keys)
+        out = UNetFn.apply(x, plan, keys, bool(apply_tanh), *[sdv[k[len('net.'):]] for k in keys])
+        if plan.bn_mode == 'batch_all':
+            for k in [k for k in self._plans if k[3] == 'running']:
+                del self._plans[k]
+            tracked = [m.num_batches_tracked for m in self._live_batchnorms() if m.num_batches_tracked is not None]
+            if tracked:
+                torch._foreach_add_(tracked, 1)
+            # the running buffers moved in place (version counters do not see a kernel's write): nothing to repack for them
+        return out
+
     def forward_fused(self, x, apply_tanh):
+        if self._hip_backward and torch.is_grad_enabled() and \
+                (x.requires_grad or any(p.requires_grad for _, p in self._live_params())):
+            return self._forward_train(x, apply_tanh)
         if torch.is_grad_enabled() and x.requires_grad:
-            raise NotImplementedError('inference-only: the HIP U-Net has no backward and would cut the graph of its input silently; '
-                                      'detach the input or use torch.no_grad()')
+            raise NotImplementedError('inference-only: without enable_hip_backward() the HIP U-Net records no backward and would cut '
+                                      'the graph of its input silently; call enable_hip_backward() to train, or detach the input '
+                                      'or use torch.no_grad()')
         n, _, h, w = x.shape
         plan = self._plan(n, h, w, x.device)
         raw = plan.forward(ops.nchw_to_nhwc(x.float().contiguous(), plan.in_c_pad))

@@ -60,6 +60,7 @@ CONV_WINOGRAD42S = 128   # with CONV_WINOGRAD: F(4x4, 2x2) for the 4x4 stride-2 
 CONV_WINOGRAD4_OUT = 64  # with CONV_WINOGRAD: F(4x4, 3x3) for the 80-column out layer where the shape allows (rnr_conv_algorithm 3, rnr_conv_winograd_tile 4; include/rnr_hip.h)
 EMU_FLAGS = {'f32': 0, 'bf16x6': CONV_F32_EMU_BF16X6, 'f16x3': CONV_F32_EMU_F16X3}
 CONV3x3_REFLECT, CONV4x4S2_REFLECT, CONVT4x4S2 = 0, 1, 2
+BN_BWD_MODES = {'batch': 0, 'batch_all': 1, 'running': 2}         # RNR_BN_BWD_*
 PRESENT_MODES = {'frame': 0, 'composite': 1, 'background': 2}     # RNR_PRESENT_*
 PRESENT_RGB = 8
 METRIC_PLANAR, METRIC_CHANNELS_LAST = 0, 1                        # RNR_METRIC_* layouts
@@ -114,6 +115,17 @@ SIGNATURES = {
     'rnr_bn_finalize': (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_double, c_float, c_void_p]),
     'rnr_bn_finalize_reset': (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_double, c_float, c_void_p]),
     'rnr_bn_finalize_batch': (c_int, [c_void_p] * 7 + [c_float, c_int, c_int, c_int, c_double, c_float, c_void_p]),
+    # U-Net backward (csrc/unet_bwd.hip)
+    'rnr_bn_finalize_saved': (c_int, [c_void_p] * 7 + [c_float, c_void_p, c_int, c_int, c_int, c_int, c_double, c_float, c_void_p]),
+    'rnr_conv_out_backward_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'rnr_conv_out_backward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                      c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    'rnr_conv2d_weight_backward_workspace_bytes': (c_size_t, [P(RnrConvDesc), c_int, c_int, c_int]),
+    'rnr_conv2d_weight_backward': (c_int, [P(RnrConvDesc), P(RnrConvSrc), P(RnrConvSrc), c_void_p, c_void_p, c_int, c_int, c_int,
+                                           c_void_p, c_size_t, c_void_p]),
+    'rnr_conv_backward_desc': (c_int, [P(RnrConvDesc), c_int, P(RnrConvDesc)]),
+    'rnr_conv2d_input_backward_ring': (c_int, [P(RnrConvDesc), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'rnr_unet_out_backward': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'rnr_nchw_to_nhwc': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'rnr_nhwc_to_nchw': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'rnr_ray_render': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,

@@ -3,8 +3,13 @@
     an image loss to LightingSH.coeff (train_rnr.py:376);
   * the texture mapper in its textures — the path from the albedo channels of the neural image (train_rnr.py:513-514, through
     the ray renderer's albedo gradients) or from any other gradient of the neural image to TextureMapper.textures.
-The backward passes are HIP kernels (rnr_ray_renderer_backward, rnr_sh_reconstruct_backward, rnr_texture_mapper_backward).
-The U-Net is not differentiable: RenderingNet / Unet raise on an input that requires grad.
+  * the U-Net (RenderingNet) in its input and in every parameter of the live path — the 22 convolutions, 17 BatchNorms and the
+    biases (train_rnr.py:376) —, which also carries the gradient of the ray renderer's rays_lt on to the feature channels of the
+    neural texture.  Opt-in: `Unet.enable_hip_backward()` / `RenderingNet.enable_hip_backward()`; without it RenderingNet / Unet
+    keep raising on an input that requires grad.
+The backward passes are HIP kernels (rnr_ray_renderer_backward, rnr_sh_reconstruct_backward, rnr_texture_mapper_backward; for the
+U-Net rnr_conv_out_backward, rnr_conv2d_weight_backward and the forward's own convolution kernels run on the gradient with
+rnr_conv2d_input_backward_ring for the border, UNetPlan.backward).
 
 `ray_renderer`, `sh_reconstruct` and `texture_mapper` go through the autograd functions ONLY when grad mode is on and an input
 requires grad; otherwise they are ops.ray_renderer / ops.sh_reconstruct / ops.texture_mapper.  Either way the forward is the same
@@ -78,6 +83,34 @@ class TextureMapperFn(torch.autograd.Function):
             for l, gl in zip(want, got):
                 grads[l] = gl.reshape(ctx.tex_shapes[l])
         return (None, None, None) + tuple(grads)
+
+
+class UNetFn(torch.autograd.Function):
+    """A training UNetPlan's forward (+ bias, optional tanh, NCHW) with UNetPlan.backward as its adjoint.  The activations live in
+    the plan: a backward must follow ITS forward before the plan runs another one (checked).  `params` are the live parameters
+    in the order of `keys` (state-dict keys of the plan); dead ones (`fuse.*`) are not passed and get no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, plan, keys, apply_tanh, *params):
+        raw = plan.forward(ops.nchw_to_nhwc(x.detach().float().contiguous(), plan.in_c_pad))
+        out = ops.nhwc_to_nchw(raw, plan.out_channels, bias=plan.out_bias, apply_tanh=apply_tanh)
+        plan._fwd_token = token = object()
+        ctx.plan, ctx.keys, ctx.apply_tanh, ctx.token = plan, keys, bool(apply_tanh), token
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        plan = ctx.plan
+        if plan._fwd_token is not ctx.token:
+            raise RuntimeError('UNetFn.backward: the plan has run another forward since this one; its activations are gone '
+                               '(call backward() before the next forward of the same module and image size)')
+        out, = ctx.saved_tensors
+        g_raw = ops.unet_out_backward(_c(g), out, ctx.apply_tanh, plan.out.c_pad)
+        g_in, grads = plan.backward(g_raw, want_input_grad=ctx.needs_input_grad[0])
+        gx = ops.nhwc_to_nchw(g_in.contiguous(), plan.in_channels) if g_in is not None else None
+        gp = tuple(grads[k].clone() if need else None for k, need in zip(ctx.keys, ctx.needs_input_grad[4:]))
+        return (gx, None, None, None) + gp
 
 
 def _wants_grad(*tensors):

@@ -635,6 +635,21 @@ def nhwc_to_nchw(x, c, bias=None, apply_tanh=False):
     return out
 
 
+@_device_op
+def unet_out_backward(g_out, out, apply_tanh, c_pad):
+    """Adjoint of nhwc_to_nchw (rnr_unet_out_backward): g_out, out [N,C,H,W] -> the gradient of the raw channel-last tensor
+    [N,H,W,c_pad] (times 1 - out^2 with apply_tanh), padding channels 0."""
+    L = _lib.load()
+    _chk(g_out, 'g_out')
+    if apply_tanh:
+        _chk(out, 'out')
+    n, c, h, w = g_out.shape
+    g_raw = torch.empty(n, h, w, int(c_pad), dtype=torch.float32, device=g_out.device)
+    check(L.rnr_unet_out_backward(_ptr(g_out), _ptr(out if apply_tanh else None), int(apply_tanh), _ptr(g_raw), n, c, h, w,
+                                  int(c_pad), _stream()))
+    return g_raw
+
+
 # ---------------------------------------------------------------------------------------------------
 # stand-alone operators behind the drop-in Python API
 # ---------------------------------------------------------------------------------------------------

@@ -38,7 +38,7 @@ DEFAULT_CONV_ALGO = 'winograd4'
 class UNetPlan:
     def __init__(self, state_dict, in_channels, out_channels, nf0, num_down, img_hw, max_views, device,
                  prefix='net.', in_c_pad=None, bn_mode='batch', share_weights_with=None, precision='f32',
-                 update_running_stats=False, check_finite=None, conv_algo=None):
+                 update_running_stats=False, check_finite=None, conv_algo=None, training=False):
         """bn_mode 'batch': BatchNorm2d in train mode with PER-VIEW batch statistics — what test_rnr.py:229-233 forces,
         evaluated the way the reference evaluates it (one view per call); a batch of N poses is N independent frames.
         'batch_all': train-mode BatchNorm2d exactly as torch computes it for ONE call with an [N,C,H,W] input: statistics
@@ -65,7 +65,16 @@ class UNetPlan:
         'direct': every convolution as a direct implicit GEMM.
         None: $RNR_CONV_ALGO, else DEFAULT_CONV_ALGO.
         share_weights_with: another UNetPlan of the same network whose packed weights / BN parameters are reused
-        (activations, statistics and scratch stay private) — one plan per HIP stream of RNRPipeline."""
+        (activations, statistics and scratch stay private) — one plan per HIP stream of RNRPipeline.
+        training: the plan can run `backward` after a `forward` (include/rnr_hip.h, "U-Net backward"): exact
+        fp32 only (any conv_algo, all three bn_modes), the unfused launches with rnr_bn_finalize_saved, the torch-layout weights
+        and the gradient convolutions' packed weights kept next to the forward's, every gradient buffer allocated here once.
+        `repack(state_dict)` refreshes the weights in place after an optimiser step."""
+        if training and precision != 'f32':
+            raise NotImplementedError("UNetPlan(training=True) is exact fp32 only: the backward kernels have no emulated form "
+                                      "(precision %r)" % (precision,))
+        if training and share_weights_with is not None:
+            raise NotImplementedError('UNetPlan(training=True) owns its weights (share_weights_with)')
         if precision not in _lib.EMU_FLAGS:
             raise ValueError("precision must be one of %s" % sorted(_lib.EMU_FLAGS))
         if bn_mode not in ('batch', 'batch_all', 'running'):
@@ -112,11 +121,12 @@ class UNetPlan:
         # One launch per convolution (rnr_conv2d_fused): the BatchNorm behind it is finalised by the last workgroup of each
         # view and shallow split-K slices meet inside the launch.  'batch_all' (whole-batch statistics, running buffers)
         # keeps the separate rnr_bn_finalize_batch launch; RNR_UNET_UNFUSED=1 runs the separate launches everywhere (A/B).
-        self.fused = bn_mode != 'batch_all' and os.environ.get('RNR_UNET_UNFUSED') != '1'
+        self.training = bool(training)
+        self.fused = bn_mode != 'batch_all' and os.environ.get('RNR_UNET_UNFUSED') != '1' and not training
         # ... except that a ONE-view call of a 'batch_all' plan is the same arithmetic (whole batch = the view): it takes the fused
         # launches too, the running statistics updated by the launch that finalises the layer (rnr_conv_bn.running_mean / _var;
         # r05: the drop-in RenderingNet of the reference's one-view loop, 2.65 -> 2.3 ms)
-        self.fused_single = bn_mode == 'batch_all' and os.environ.get('RNR_UNET_UNFUSED') != '1'
+        self.fused_single = bn_mode == 'batch_all' and os.environ.get('RNR_UNET_UNFUSED') != '1' and not training
         self._tile_mask = None
         self._keep = []
 
@@ -160,7 +170,8 @@ class UNetPlan:
             out = _Act(c_out, desc.c_out_pad, oh, ow, act)
             out.data = torch.empty(self.N, oh, ow, desc.c_out_pad, dtype=torch.float32, device=device)
             step = {'desc': desc, 'packed': packed, 'srcs': srcs, 'out': out, 'in_hw': (s0.h, s0.w), 'bn': None, 'sync': None,
-                    'cbn': None}
+                    'cbn': None, 'keys': (wkey, bn_key if bn_key is not None and has(bn_key + '.weight') else None,
+                                          bias_key if bias_key is not None and has(bias_key) else None)}
             if self.fused or self.fused_single:       # arrival counters + statistics shards: zero now, left at zero by every call
                 step['sync'] = torch.zeros(self.L.rnr_conv_sync_bytes(ctypes.byref(desc), self.N, s0.h, s0.w),
                                            dtype=torch.uint8, device=device)
@@ -232,8 +243,184 @@ class UNetPlan:
         self.out_bias = torch.zeros(out.c_pad, dtype=torch.float32, device=device)
         if has('out_layer.0.net.1.bias'):
             self.out_bias[:self.out_channels] = g('out_layer.0.net.1.bias')
+        self._prefix = prefix
+        if training:
+            self._init_training(sd)
         self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=device)
         self.flops_per_view = self._count_flops()
+
+    # ---- training (include/rnr_hip.h, "U-Net backward") ----
+    def _init_training(self, sd):
+        """Everything `backward` needs, allocated once: per layer the torch-layout weight, the gradient convolutions' descriptors
+        and packed weights (one per source), the saved BatchNorm statistics, one gradient buffer per (layer, source) — an
+        activation with two consumers (down conv and skip concat) owns two, which rnr_conv_out_backward adds — and the parameter
+        gradients; shared by all layers: one g_y buffer and the two workspaces."""
+        L, dev, N = self.L, self.dev, self.N
+        pre = self._prefix
+        for a in [self.input] + [s['out'] for s in self.steps]:
+            a.grads = []
+        self.grads = {}
+        gy_floats, wg_bytes, ob_bytes = 0, 256, 256
+        for s in self.steps:
+            d, (h, w), out = s['desc'], s['in_hw'], s['out']
+            wkey, bn_key, bias_key = s['keys']
+            s['w'] = sd[pre + wkey].detach().to(device=dev, dtype=torch.float32).contiguous().clone()
+            self.grads[pre + wkey] = torch.zeros_like(s['w'])
+            if s['bn'] is not None or (bn_key is not None and self.bn_mode == 'running'):
+                if s['bn'] is None:         # 'running': forward folds the statistics; the backward wants gamma and (mean, r)
+                    s['bn'] = {'gamma': sd[pre + bn_key + '.weight'].detach().to(device=dev, dtype=torch.float32).contiguous().clone(),
+                               'beta': None, 'stats': None, 'running_mean': None, 'running_var': None}
+                if self.bn_mode == 'running':
+                    s['_running'] = tuple(sd[pre + bn_key + k].detach().to(device=dev, dtype=torch.float32) for k in ('.running_mean', '.running_var'))
+                groups = N if self.bn_mode == 'batch' else 1
+                s['bn']['saved'] = torch.zeros(groups, d.c_out_pad, 2, dtype=torch.float64, device=dev)
+                self.grads[pre + bn_key + '.weight'] = torch.zeros(out.c, dtype=torch.float32, device=dev)
+                self.grads[pre + bn_key + '.bias'] = torch.zeros(out.c, dtype=torch.float32, device=dev)
+            elif bias_key is not None:
+                self.grads[pre + bias_key] = torch.zeros(out.c, dtype=torch.float32, device=dev)
+            s['bwd'] = []
+            for i, a in enumerate(s['srcs']):
+                bd = RnrConvDesc()
+                check(L.rnr_conv_backward_desc(ctypes.byref(d), i, ctypes.byref(bd)))
+                packed = torch.empty(L.rnr_packed_weight_floats(ctypes.byref(bd)), dtype=torch.float32, device=dev)
+                g = torch.zeros(N, a.h, a.w, a.c_pad, dtype=torch.float32, device=dev)
+                a.grads.append(g)
+                s['bwd'].append({'desc': bd, 'packed': packed, 'grad': g})
+                for n_views in range(1, N + 1):
+                    self.ws_bytes = max(self.ws_bytes, L.rnr_conv_workspace_bytes(ctypes.byref(bd), n_views, out.h, out.w))
+            gy_floats = max(gy_floats, N * out.h * out.w * out.c_pad)
+            for n_views in range(1, N + 1):
+                wg_bytes = max(wg_bytes, L.rnr_conv2d_weight_backward_workspace_bytes(ctypes.byref(d), n_views, h, w))
+                ob_bytes = max(ob_bytes, L.rnr_conv_out_backward_workspace_bytes(n_views, out.h, out.w, out.c_pad))
+        if (pre + 'out_layer.0.net.1.bias') in sd:
+            self.grads[pre + 'out_layer.0.net.1.bias'] = torch.zeros(self.out_channels, dtype=torch.float32, device=dev)
+        self._gy = torch.zeros(gy_floats, dtype=torch.float32, device=dev)
+        self._wg_ws = torch.empty(wg_bytes, dtype=torch.uint8, device=dev)
+        self._ob_ws = torch.empty(ob_bytes, dtype=torch.uint8, device=dev)
+        self._fwd_n = None
+        self.param_keys = sorted(self.grads)
+        self._pack_backward()
+
+    def _pack_backward(self):
+        """Gradient-convolution weights from the torch-layout ones (include/rnr_hip.h, rnr_conv_backward_desc): flipped and
+        transposed for the 3x3 kind, the same tensor read the other way for the two 4x4 kinds; sliced per source."""
+        with on_device(self.dev):
+            for s in self.steps:
+                d, w, off = s['desc'], s['w'], 0
+                for b, a in zip(s['bwd'], s['srcs']):
+                    if d.kind == CONV3x3_REFLECT:
+                        wb = w[:, off:off + a.c].flip(2, 3).transpose(0, 1).contiguous()
+                    elif d.kind == CONV4x4S2_REFLECT:
+                        wb = w[:, off:off + a.c].contiguous()
+                    else:
+                        wb = w[off:off + a.c].contiguous()
+                    check(self.L.rnr_pack_conv_weight(ctypes.byref(b['desc']), _ptr(wb), _ptr(b['packed']), _stream()))
+                    off += a.c
+                if s['bn'] is not None and self.bn_mode == 'running':
+                    # eval mode: (running mean, 1 / sqrt(running var + eps)) in rnr_bn_finalize_saved's form
+                    rm, rv = s['_running']
+                    s['bn']['saved'][0, :s['out'].c, 0] = rm.double()
+                    s['bn']['saved'][0, :s['out'].c, 1] = 1.0 / torch.sqrt(rv.double() + 1e-5)
+
+    def repack(self, state_dict):
+        """Refresh the packed weights, BatchNorm parameters and biases IN PLACE from `state_dict` (same keys and shapes as at
+        construction): what a training step does after the optimiser moved the parameters.  No buffer is reallocated."""
+        pre, dev = self._prefix, self.dev
+        g = lambda k: state_dict[pre + k].detach().to(device=dev, dtype=torch.float32)
+        with on_device(dev):
+            for s in self.steps:
+                wkey, bn_key, bias_key = s['keys']
+                out = s['out']
+                if self.training:
+                    s['w'].copy_(g(wkey))
+                    w = s['w']
+                else:
+                    w = g(wkey).contiguous()
+                check(self.L.rnr_pack_conv_weight(ctypes.byref(s['desc']), _ptr(w), _ptr(s['packed']), _stream()))
+                if bn_key is not None and self.bn_mode == 'running':
+                    gamma, beta = g(bn_key + '.weight'), g(bn_key + '.bias')
+                    rm, rv = g(bn_key + '.running_mean'), g(bn_key + '.running_var')
+                    sc = gamma / torch.sqrt(rv + 1e-5)
+                    out.scale[:, :out.c] = sc
+                    out.shift[:, :out.c] = beta - rm * sc
+                    if self.training:
+                        s['bn']['gamma'].copy_(gamma)
+                        s['_running'] = (rm, rv)
+                elif bn_key is not None:
+                    s['bn']['gamma'].copy_(g(bn_key + '.weight'))
+                    s['bn']['beta'].copy_(g(bn_key + '.bias'))
+                elif bias_key is not None:
+                    s['bias'][:out.c] = g(bias_key)
+                    out.shift.copy_(s['bias'][None].expand_as(out.shift))
+            if (pre + 'out_layer.0.net.1.bias') in state_dict:
+                self.out_bias[:self.out_channels] = g('out_layer.0.net.1.bias')
+        if self.training:
+            self._pack_backward()
+
+    def backward(self, grad_raw, want_input_grad=True):
+        """The adjoint of the last `forward` (same number of views; its activations are still in the plan): grad_raw
+        [n,H,W,out_c_pad] the gradient of forward's result -> (gradient of net_in [n,H,W,in_c_pad] or None, {state-dict key:
+        gradient}) for the convolution weights, BatchNorm weight / bias and convolution biases of the live path.  The returned
+        tensors are the plan's own buffers, overwritten by the next call."""
+        if not self.training:
+            raise RuntimeError('UNetPlan.backward needs a plan built with training=True')
+        n = self._fwd_n
+        if n is None:
+            raise RuntimeError('UNetPlan.backward: no forward to differentiate')
+        if tuple(grad_raw.shape) != (n, self.H, self.W, self.out.c_pad) or grad_raw.dtype != torch.float32 or \
+                not grad_raw.is_contiguous():
+            raise RuntimeError('grad_raw must be a contiguous float32 %s, got %s' % ((n, self.H, self.W, self.out.c_pad),
+                                                                                    tuple(grad_raw.shape)))
+        with on_device(self.dev):
+            st = _stream()
+            for s in reversed(self.steps):
+                self._bwd_out(s, n, grad_raw, st)
+                self._bwd_weight(s, n, st)
+                for i, a in enumerate(s['srcs']):
+                    if a is self.input and not want_input_grad:
+                        continue
+                    self._bwd_data(s, i, n, st)
+                    self._bwd_ring(s, i, n, st)
+        return (self.input.grads[0][:n] if want_input_grad else None), self.grads
+
+    # the four launches of one layer's backward (scripts/unet_backward_time.py times them one by one)
+    def _bwd_out(self, s, n, grad_raw, st):
+        """g_z (grad_raw for the out layer, else the consumers' gradient buffers) -> g_y in self._gy, BatchNorm / bias gradients."""
+        out, bn, pre = s['out'], s['bn'], self._prefix
+        _, bn_key, bias_key = s['keys']
+        last = s is self.steps[-1]
+        gz0 = grad_raw if last else out.grads[0]
+        gz1 = out.grads[1] if (not last and len(out.grads) > 1) else None
+        if last:
+            g_gamma, g_beta = None, self.grads.get(pre + 'out_layer.0.net.1.bias')
+        elif bn is not None:
+            g_gamma, g_beta = self.grads[pre + bn_key + '.weight'], self.grads[pre + bn_key + '.bias']
+        else:
+            g_gamma, g_beta = None, (self.grads.get(pre + bias_key) if bias_key else None)
+        check(self.L.rnr_conv_out_backward(_ptr(out.data), _ptr(out.scale), _ptr(out.shift), out.act, _ptr(gz0), _ptr(gz1),
+                                           _ptr(bn['gamma']) if bn else None, _ptr(bn['saved']) if bn else None,
+                                           _lib.BN_BWD_MODES[self.bn_mode], _ptr(self._gy), _ptr(g_gamma), _ptr(g_beta), n, out.h,
+                                           out.w, out.c, out.c_pad, _ptr(self._ob_ws), self._ob_ws.numel(), st))
+
+    def _bwd_weight(self, s, n, st):
+        srcs, (h, w) = s['srcs'], s['in_hw']
+        s0 = self._src(srcs[0], n)
+        s1 = self._src(srcs[1], n) if len(srcs) > 1 else None
+        check(self.L.rnr_conv2d_weight_backward(ctypes.byref(s['desc']), ctypes.byref(s0), ctypes.byref(s1) if s1 else None,
+                                                _ptr(self._gy), _ptr(self.grads[self._prefix + s['keys'][0]]), n, h, w,
+                                                _ptr(self._wg_ws), self._wg_ws.numel(), st))
+
+    def _bwd_data(self, s, i, n, st):
+        """The forward kernel of the adjoint's kind on g_y -> the gradient buffer of source i (exact off the border ring)."""
+        out, b = s['out'], s['bwd'][i]
+        gsrc = RnrConvSrc(self._gy.data_ptr(), None, None, out.c_pad, ACT_NONE)
+        check(self.L.rnr_conv2d(ctypes.byref(b['desc']), ctypes.byref(gsrc), None, _ptr(b['packed']), _ptr(b['grad']), None, n,
+                                out.h, out.w, _ptr(self.workspace), self.ws_bytes, st))
+
+    def _bwd_ring(self, s, i, n, st):
+        h, w = s['in_hw']
+        check(self.L.rnr_conv2d_input_backward_ring(ctypes.byref(s['desc']), i, _ptr(self._gy), _ptr(s['w']),
+                                                    _ptr(s['bwd'][i]['grad']), n, h, w, st))
 
     def mfma_flops_per_view(self, n_views, masked_out_layer=True):
         """Multiply-add FLOPs the matrix cores execute per view when `n_views` are passed per call: the direct-form count of
@@ -291,6 +478,10 @@ class UNetPlan:
             raise RuntimeError('net_in shape %s does not match plan (H=%d W=%d c_pad=%d)' %
                                (tuple(net_in.shape), self.H, self.W, self.in_c_pad))
         self.input.data = net_in
+        if self.training:
+            if consumer_alpha is not None or ray is not None:
+                raise NotImplementedError('UNetPlan(training=True): the masked and the fused-ray out layer have no backward')
+            self._fwd_n = n
         L, st = self.L, _stream()
         last = self.steps[-1]
         mask = None
@@ -358,13 +549,19 @@ class UNetPlan:
                                          _ptr(mask) if s is last else None, st))
                 continue
             check(L.rnr_conv2d_masked(ctypes.byref(s['desc']), ctypes.byref(s0), ctypes.byref(s1) if s1 else None,
-                                      _ptr(s['packed']), _ptr(out.data), _ptr(bn['stats']) if bn else None, n, h, w,
+                                      _ptr(s['packed']), _ptr(out.data), _ptr(bn['stats']) if bn and bn['stats'] is not None else None, n, h, w,
                                       _ptr(self.workspace), self.ws_bytes, _ptr(mask) if s is last else None, st))
-            if bn and self.bn_mode == 'batch_all':
+            if bn and self.training and bn['stats'] is not None:
+                whole = self.bn_mode == 'batch_all'
+                check(L.rnr_bn_finalize_saved(_ptr(bn['stats']), _ptr(bn['gamma']), _ptr(bn['beta']), _ptr(out.scale),
+                                              _ptr(out.shift), _ptr(bn['running_mean']) if whole else None,
+                                              _ptr(bn['running_var']) if whole else None, 0.1, _ptr(bn['saved']), int(whole), n,
+                                              out.c, out.c_pad, float(out.h * out.w), 1e-5, st))
+            elif bn and self.bn_mode == 'batch_all':
                 check(L.rnr_bn_finalize_batch(_ptr(bn['stats']), _ptr(bn['gamma']), _ptr(bn['beta']), _ptr(out.scale),
                                               _ptr(out.shift), _ptr(bn['running_mean']), _ptr(bn['running_var']), 0.1, n,
                                               out.c, out.c_pad, float(out.h * out.w), 1e-5, st))
-            elif bn:
+            elif bn and bn['stats'] is not None:
                 check(L.rnr_bn_finalize_reset(_ptr(bn['stats']), _ptr(bn['gamma']), _ptr(bn['beta']), _ptr(out.scale),
                                         _ptr(out.shift), n, out.c, out.c_pad, float(out.h * out.w), 1e-5, st))
         return self.out.data[:n]
