@@ -679,6 +679,58 @@ int rnr_image_metrics(const float* est, const float* gt, const float* mask, int 
                       int compute_ssim, double* out, int32_t* box, void* workspace,
                       int num_views, int height, int width, void* stream);
 
+/*
+ * The two per-pixel terms of train_rnr.py's objective (csrc/loss.hip), each a streaming pass plus a one-workgroup finalise
+ * forward and one streaming pass backward.  Inputs and gradients are float32; the per-pixel arithmetic and every sum are
+ * float64 and a gradient is rounded to float32 once (the reference's float32 `1 - c . mh` cancels to 1.7e-5 relative on
+ * gradient elements where the chromaticities agree, which is where training converges to).  No atomics and fixed-order sums:
+ * two calls on the same inputs give the same bits.  Every workspace word that is read is written earlier in the same call.
+ * Nothing syncs with the host: the backward passes read g_loss (one float32) and the forward's loss_out from device memory.
+ *
+ * Ray chromaticity loss (network.RaysLTChromLoss, network.py:391-411):
+ *   rays_lt [N,R,3,H,W], alpha [N,1,H,W], img [N,3,H,W] or NULL.  With x_r the 3-vector of ray r at a pixel and
+ *   eps = 1e-12 (F.normalize's default):
+ *     n_r = |x_r|;  c_r = x_r / max(n_r, eps);  S = sum_r c_r;  m = S / R;  M = |m|;  mh = m / max(M, eps)
+ *     w = min(20 |img|, 1)  (1 when img is NULL; a NaN stays NaN);   d_r = (1 - c_r . mh) alpha w
+ *     loss = sum d / sum alpha / R,   the per-pixel sum taken as sum_r d_r = alpha w (R - S . mh)
+ *   loss_out [2] float64: loss, sum alpha.  The optional float32 maps (each written only when its pointer is not NULL; all
+ *   NULL is the training call and never forms them): chrom [N,R,3,H,W] = c_r, chrom_mean [N,1,3,H,W] = mh,
+ *   chrom_diff [N,R,H,W] = d_r.  workspace: rnr_rays_chrom_loss_workspace_bytes(N, R, H, W) bytes, 8-byte aligned like loss_out.
+ *   Backward, with g = *g_loss, k = g alpha w / (sum alpha R):
+ *     t    = (S - (S . mh) mh) / M / R   if M >= eps,    else S / eps / R
+ *     gc   = -k (mh + t)                                  (the same for every ray of the pixel)
+ *     gx_r = (gc - (gc . c_r) c_r) / n_r  if n_r >= eps,  else gc / eps
+ *   grad_rays_lt [N,R,3,H,W] is overwritten; c, S and mh are recomputed from rays_lt (at R = 26 the pixel's 78 values stay in
+ *   registers between the two sweeps, at other ray counts the second sweep reads them again).
+ *   Edge cases: a pixel with alpha w == 0 contributes exactly 0, gets an exactly zero gradient and exactly zero chrom_diff, and
+ *   its rays are not read by the training call — a select, so a NaN ray under alpha = 0 does not reach the loss (DEVIATION: the
+ *   reference multiplies, so there such a NaN poisons the loss); sum alpha == 0 gives loss = NaN as in the reference, the
+ *   gradient is then unspecified; a zero or sub-eps ray, and M < eps, follow the formulas above, which is what torch's
+ *   normalize and its autograd give (the gradient at a zero ray is of order k / eps).  Errors (a NULL required pointer,
+ *   N, H, W < 1, R < 1, N R 3 H W >= 2^31, misaligned loss_out or workspace) are reported before any launch.
+ *
+ * Cropped L1 (train_rnr.py:564-569, 581-585): est, gt [N,C,H,W], alpha [N,1,H,W], b = border >= 0:
+ *     loss = mean over N C (H - 2b) (W - 2b) of |fl32(est alpha) - fl32(gt alpha)|     on the crop [b, H-b) x [b, W-b)
+ *   (the two products rounded to float32 as the reference rounds them, then widened); loss_out [1] float64;
+ *   workspace: rnr_masked_l1_loss_workspace_bytes(N, H, W) bytes, 8-byte aligned.
+ *   Backward: grad_est [N,C,H,W] = g sign(fl32(est alpha) - fl32(gt alpha)) alpha / count inside the crop, sign(0) = 0, and
+ *   exactly 0 in the border; gt and alpha get no gradient.
+ *   Errors: as above, C < 1, N C H W >= 2^31, border < 0, and H <= 2b or W <= 2b (DEVIATION: the reference's mean over an
+ *   empty crop is NaN).
+ */
+size_t rnr_rays_chrom_loss_workspace_bytes(int num_views, int num_rays, int height, int width);
+int rnr_rays_chrom_loss(const float* rays_lt, const float* alpha, const float* img, double* loss_out, float* chrom,
+                        float* chrom_mean, float* chrom_diff, void* workspace, int num_views, int num_rays, int height,
+                        int width, void* stream);
+int rnr_rays_chrom_loss_backward(const float* rays_lt, const float* alpha, const float* img, const double* loss_out,
+                                 const float* g_loss, float* grad_rays_lt, int num_views, int num_rays, int height, int width,
+                                 void* stream);
+size_t rnr_masked_l1_loss_workspace_bytes(int num_views, int height, int width);
+int rnr_masked_l1_loss(const float* est, const float* gt, const float* alpha, int border, double* loss_out, void* workspace,
+                       int num_views, int channels, int height, int width, void* stream);
+int rnr_masked_l1_loss_backward(const float* est, const float* gt, const float* alpha, int border, const float* g_loss,
+                                float* grad_est, int num_views, int channels, int height, int width, void* stream);
+
 /* ---- spherical harmonics (sph_harm.py:41-102) ---- */
 
 /* Real orthonormal SH without Condon-Shortley phase, columns (l, m=-l..l); dirs [n,3] (need not be unit),

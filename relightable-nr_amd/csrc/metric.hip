@@ -50,18 +50,7 @@ __device__ __forceinline__ long pixel_index(int layout, int n, int c, int y, int
     return layout == RNR_METRIC_PLANAR ? (((long)n * 3 + c) * H + y) * W + x : (((long)n * H + y) * W + x) * 3 + c;
 }
 
-// Sum of v over the workgroup in a fixed order (shuffle tree per wave, then the waves in order); the result is valid in
-// thread 0.  `sh` holds WAVES doubles; the leading barrier lets consecutive calls share it.
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < WAVES; i++) t += sh[i];
-    return t;
-}
+__device__ __forceinline__ double block_sum(double v, double* sh) { return rnr::block_sum<WAVES>(v, sh); }
 
 __device__ __forceinline__ int block_sum_int(int v, int* sh) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);

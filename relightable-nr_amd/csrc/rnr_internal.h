@@ -39,6 +39,20 @@ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
     } while (0)
 
 #if defined(__HIPCC__)
+// Sum of v over a workgroup of WAVES full waves in a fixed order (shuffle tree per wave, then the waves in order); the result is
+// valid in thread 0.  `sh` holds WAVES doubles; the leading barrier lets consecutive calls share it.  (metric.hip, loss.hip)
+template <int WAVES>
+__device__ __forceinline__ double block_sum(double v, double* sh) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = 0.0;
+    if (threadIdx.x == 0)
+        for (int i = 0; i < WAVES; i++) t += sh[i];
+    return t;
+}
+
 // tanh(x) + 1 = 2 - 2 / (e^{2x} + 1) on v_exp_f32 / v_rcp_f32 (the light transport factor of the ray renderer): absolute
 // error ~1e-7, exact limits at +-inf; ocml's tanhf costs ~25 instructions and this kernel is VALU-bound.
 __device__ __forceinline__ float fast_tanh_plus1f(float x) {

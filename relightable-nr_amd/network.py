@@ -1,10 +1,10 @@
 """Drop-in `network` (reference: network.py): the nn.Module classes test_rnr.py / test_dnr.py construct, with the same
 constructor / forward signatures, buffers and state-dict keys, computing on librnr_hip.so.
 
-In scope: TextureMapper, Rasterizer, RenderingNet, Interpolater, RaySampler, RayRenderer, LightingSH.
+In scope: TextureMapper, Rasterizer, RenderingNet, Interpolater, RaySampler, RayRenderer, LightingSH, RaysLTChromLoss.
 In scope as "next" rows: LightingLP (HIP area resize instead of cv2), Mesh (host bookkeeping).
 Out of scope (raise on construction): DenseDeepGCN (train-time only; its cached output `v_feature` is loaded from the
-checkpoint and is dead at the output anyway), InterpolaterVertexAttr, RaysLTChromLoss (loss).
+checkpoint and is dead at the output anyway), InterpolaterVertexAttr.
 With these, test_dnr.py and test_rnr.py construct every module they need, provided the inference flags keep
 DenseDeepGCN unused (test_rnr.py only builds it when the checkpoint lacks a cached `v_feature`).
 
@@ -14,9 +14,12 @@ Intentional deviations from the reference classes (all invisible to the scripts'
   * LightingSH.reconstruct_lp detaches `coeff` (inference build: no gradient flows through the HIP kernels) and returns
     [..., lp_recon_h, lp_recon_w, C]; a 2-D `init_coeff` is expanded to [num_lighting, nb, C] (the reference assigns
     the 2-D tensor and breaks its own indexing); `l_samples` is computed from the coefficients at init.
-  * Gradients: TextureMapper (in its textures), RayRenderer and LightingSH.coeff are differentiable through HIP backward
-    kernels (rnr_amd.autograd); RenderingNet / Unet are inference-only and raise NotImplementedError on an input that
-    requires grad in grad mode (the reference's U-Net is differentiable) instead of cutting the graph silently.
+  * Gradients: TextureMapper (in its textures), RayRenderer, LightingSH.coeff and RaysLTChromLoss (in rays_lt) are
+    differentiable through HIP backward kernels (rnr_amd.autograd); so are RenderingNet / Unet after
+    `enable_hip_backward()` — without that opt-in they raise NotImplementedError on an input that requires grad in grad
+    mode (the reference's U-Net is differentiable) instead of cutting the graph silently.
+  * RaysLTChromLoss computes per pixel in float64 and selects on the mask (a NaN ray under alpha = 0 does not reach the loss,
+    where the reference multiplies); `return_maps=False` skips the three maps train_rnr.py never uses.
   * render.get_TBN_map does not raise on NaN by default (the reference's check costs three host syncs per view).
 """
 import numpy as np
@@ -352,7 +355,23 @@ def _out_of_scope(name, why):
 
 DenseDeepGCN = _out_of_scope('DenseDeepGCN', 'train-time only; inference loads its cached output v_feature, which is dead at the output')
 InterpolaterVertexAttr = _out_of_scope('InterpolaterVertexAttr', 'unused at inference')
-RaysLTChromLoss = _out_of_scope('RaysLTChromLoss', 'training loss')
+
+
+class RaysLTChromLoss(nn.Module):
+    """network.py:391-411: the spread of the rays' light-transport chromaticities around their mean direction, per pixel, weighted
+    by alpha and (with img) by min(20 |img|, 1).  forward -> (loss, rays_lt_chrom [N,R,C,H,W], rays_lt_chrom_mean [N,1,C,H,W],
+    rays_lt_chrom_diff [N,R,H,W]) as the reference; the loss is a float32 scalar, differentiable in rays_lt through one HIP pass
+    each way (rnr_rays_chrom_loss, float64 per pixel), the maps carry no graph.  return_maps=False: the maps are None and never
+    computed (train_rnr.py:589 drops all three).  alpha_map and img are constants: one that requires grad raises."""
+
+    def __init__(self, return_maps=True):
+        super().__init__()
+        self.return_maps = bool(return_maps)
+
+    def forward(self, rays_lt, alpha_map, img=None):
+        outs = autograd.rays_chrom_loss(rays_lt.float().contiguous(), alpha_map.float().contiguous(),
+                                        img.float().contiguous() if img is not None else None, return_maps=self.return_maps)
+        return tuple(outs) if self.return_maps else (outs, None, None, None)
 
 
 class Mesh(nn.Module):

@@ -146,6 +146,13 @@ SIGNATURES = {
     'rnr_image_metrics_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'rnr_image_metrics': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                   c_int, c_void_p]),
+    # training losses (csrc/loss.hip)
+    'rnr_rays_chrom_loss_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'rnr_rays_chrom_loss': (c_int, [c_void_p] * 8 + [c_int, c_int, c_int, c_int, c_void_p]),
+    'rnr_rays_chrom_loss_backward': (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_int, c_void_p]),
+    'rnr_masked_l1_loss_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'rnr_masked_l1_loss': (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    'rnr_masked_l1_loss_backward': (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'rnr_tbn_map': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     'rnr_tbn_matvec': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_long, c_int, c_void_p]),
     'rnr_ray_sampler': (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

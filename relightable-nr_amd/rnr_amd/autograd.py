@@ -7,6 +7,8 @@
     biases (train_rnr.py:376) —, which also carries the gradient of the ray renderer's rays_lt on to the feature channels of the
     neural texture.  Opt-in: `Unet.enable_hip_backward()` / `RenderingNet.enable_hip_backward()`; without it RenderingNet / Unet
     keep raising on an input that requires grad.
+  * the two per-pixel terms of train_rnr.py's objective: the ray chromaticity loss in rays_lt and the cropped, alpha-weighted L1
+    in the estimate (rnr_rays_chrom_loss_backward, rnr_masked_l1_loss_backward; rnr_amd.losses composes the objective).
 The backward passes are HIP kernels (rnr_ray_renderer_backward, rnr_sh_reconstruct_backward, rnr_texture_mapper_backward; for the
 U-Net rnr_conv_out_backward, rnr_conv2d_weight_backward and the forward's own convolution kernels run on the gradient with
 rnr_conv2d_input_backward_ring for the border, UNetPlan.backward).
@@ -113,6 +115,45 @@ class UNetFn(torch.autograd.Function):
         return (gx, None, None, None) + gp
 
 
+class RaysChromLossFn(torch.autograd.Function):
+    """ops.rays_chrom_loss with the adjoint in rays_lt.  Saves its inputs and the device loss_out (the backward reads sum alpha
+    from it); returns the loss as a float32 scalar and, with want_maps, the three maps, marked non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, rays_lt, alpha, img, want_maps):
+        outs = ops.rays_chrom_loss(rays_lt, alpha, img, return_maps=want_maps)
+        loss_out = outs[0] if want_maps else outs
+        ctx.has_img = img is not None
+        ctx.save_for_backward(*((rays_lt, alpha, loss_out) + ((img,) if ctx.has_img else ())))
+        loss = loss_out[0].float()
+        if not want_maps:
+            return loss
+        ctx.mark_non_differentiable(*outs[1:])
+        return (loss,) + tuple(outs[1:])
+
+    @staticmethod
+    def backward(ctx, g, *g_maps):
+        rays_lt, alpha, loss_out = ctx.saved_tensors[:3]
+        img = ctx.saved_tensors[3] if ctx.has_img else None
+        return ops.rays_chrom_loss_backward(rays_lt, alpha, img, loss_out, _c(g).reshape(1)), None, None, None
+
+
+class MaskedL1LossFn(torch.autograd.Function):
+    """ops.masked_l1_loss with the adjoint in est; returns the loss as a float32 scalar."""
+
+    @staticmethod
+    def forward(ctx, est, gt, alpha, border):
+        loss_out = ops.masked_l1_loss(est, gt, alpha, border)
+        ctx.save_for_backward(est, gt, alpha, loss_out)
+        ctx.border = border
+        return loss_out[0].float()
+
+    @staticmethod
+    def backward(ctx, g):
+        est, gt, alpha, _ = ctx.saved_tensors
+        return ops.masked_l1_loss_backward(est, gt, alpha, ctx.border, _c(g).reshape(1)), None, None, None
+
+
 def _wants_grad(*tensors):
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
@@ -151,3 +192,30 @@ def texture_mapper(textures, uv_map, sh_basis_map=None, sh_start_ch=3):
     if not _wants_grad(*textures):
         return ops.texture_mapper([t.detach() for t in textures], uv_map, sh_basis_map, sh_start_ch)
     return TextureMapperFn.apply(uv_map, sh_basis_map, int(sh_start_ch), *textures)
+
+
+def _no_grad_for(who, why, **tensors):
+    if torch.is_grad_enabled():
+        for name, t in tensors.items():
+            if t is not None and t.requires_grad:
+                raise NotImplementedError('%s has no gradient for %s: %s; detach it' % (who, name, why))
+
+
+def rays_chrom_loss(rays_lt, alpha, img=None, return_maps=False):
+    """ops.rays_chrom_loss as a float32 scalar tensor, differentiable in rays_lt; with return_maps -> (loss, chrom, chrom_mean,
+    chrom_diff), the maps without a graph.  alpha and img carry no gradient (in the reference they come from the rasterizer and
+    the data loader): one that requires grad raises NotImplementedError instead of yielding a silent zero."""
+    _no_grad_for('rays_chrom_loss', 'the mask and the photograph are constants of the loss', alpha=alpha, img=img)
+    if not _wants_grad(rays_lt):
+        outs = ops.rays_chrom_loss(rays_lt.detach(), alpha, img, return_maps=return_maps)
+        return (outs[0][0].float(),) + tuple(outs[1:]) if return_maps else outs[0].float()
+    return RaysChromLossFn.apply(rays_lt, alpha, img, bool(return_maps))
+
+
+def masked_l1_loss(est, gt, alpha, border=5):
+    """ops.masked_l1_loss as a float32 scalar tensor, differentiable in est.  gt and alpha carry no gradient: one that requires
+    grad raises NotImplementedError instead of yielding a silent zero."""
+    _no_grad_for('masked_l1_loss', 'the photograph and the mask are constants of the loss', gt=gt, alpha=alpha)
+    if not _wants_grad(est):
+        return ops.masked_l1_loss(est.detach(), gt, alpha, border)[0].float()
+    return MaskedL1LossFn.apply(est, gt, alpha, int(border))

@@ -526,6 +526,115 @@ def image_metrics(est, gt, mask=None, scale=1.0, compute_ssim=True, channels_las
     return (out, box) if return_box else out
 
 
+# ---------------------------------------------------------------------------------------------------
+# training losses (csrc/loss.hip)
+# ---------------------------------------------------------------------------------------------------
+_LOSS_WORKSPACES = {}
+
+
+def _loss_workspace(kind, device, nbytes, *shape):
+    key = (kind, device.index) + shape
+    ws = _LOSS_WORKSPACES.get(key)
+    if ws is None:
+        ws = _LOSS_WORKSPACES[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
+def _chrom_args(rays_lt, alpha, img, who):
+    _chk(rays_lt, 'rays_lt'); _chk(alpha, 'alpha')
+    if rays_lt.dim() != 5 or rays_lt.shape[2] != 3:
+        raise ValueError('%s: rays_lt must be [N,R,3,H,W], got %s' % (who, tuple(rays_lt.shape)))
+    N, R, _, H, W = rays_lt.shape
+    if min(N, R, H, W) <= 0 or rays_lt.numel() >= 2 ** 31:
+        raise ValueError('%s: rays_lt %s: sizes must be positive and N*R*3*H*W below 2^31' % (who, tuple(rays_lt.shape)))
+    if tuple(alpha.shape) != (N, 1, H, W):
+        raise ValueError('%s: alpha must be [%d,1,%d,%d], got %s' % (who, N, H, W, tuple(alpha.shape)))
+    if img is not None:
+        _chk(img, 'img')
+        if tuple(img.shape) != (N, 3, H, W):
+            raise ValueError('%s: img must be [%d,3,%d,%d], got %s' % (who, N, H, W, tuple(img.shape)))
+    return N, R, H, W
+
+
+@_device_op
+def rays_chrom_loss(rays_lt, alpha, img=None, return_maps=False):
+    """The ray chromaticity loss (rnr_rays_chrom_loss; network.RaysLTChromLoss, network.py:391-411): rays_lt [N,R,3,H,W],
+    alpha [N,1,H,W], img [N,3,H,W] or None -> loss_out, a float64 device tensor [2] = (loss, sum alpha), which
+    rays_chrom_loss_backward takes; with return_maps also the float32 maps chrom [N,R,3,H,W], chrom_mean [N,1,3,H,W] and
+    chrom_diff [N,R,H,W] (without, they are never formed).  Nothing is copied to the host.  The workspace is cached per
+    (device, N, R, H, W): calls of one shape on different streams of a device must not overlap."""
+    L = _lib.load()
+    N, R, H, W = _chrom_args(rays_lt, alpha, img, 'rays_chrom_loss')
+    dev = rays_lt.device
+    out = torch.empty(2, dtype=torch.float64, device=dev)
+    maps = (torch.empty_like(rays_lt), torch.empty(N, 1, 3, H, W, dtype=torch.float32, device=dev),
+            torch.empty(N, R, H, W, dtype=torch.float32, device=dev)) if return_maps else (None, None, None)
+    ws = _loss_workspace('chrom', dev, L.rnr_rays_chrom_loss_workspace_bytes(N, R, H, W), N, R, H, W)
+    check(L.rnr_rays_chrom_loss(_ptr(rays_lt), _ptr(alpha), _ptr(img), _ptr(out), _ptr(maps[0]), _ptr(maps[1]), _ptr(maps[2]),
+                                _ptr(ws), N, R, H, W, _stream()))
+    return (out,) + maps if return_maps else out
+
+
+@_device_op
+def rays_chrom_loss_backward(rays_lt, alpha, img, loss_out, g_loss):
+    """Adjoint of rays_chrom_loss in rays_lt (rnr_rays_chrom_loss_backward): loss_out is the forward's [2] float64 tensor, g_loss a
+    float32 device tensor of one element (the gradient of the loss); both are read on the device.  -> grad_rays_lt [N,R,3,H,W]."""
+    L = _lib.load()
+    N, R, H, W = _chrom_args(rays_lt, alpha, img, 'rays_chrom_loss_backward')
+    _chk(loss_out, 'loss_out', torch.float64); _chk(g_loss, 'g_loss')
+    if loss_out.numel() != 2 or g_loss.numel() != 1:
+        raise ValueError('rays_chrom_loss_backward: loss_out must hold 2 elements and g_loss 1, got %d and %d'
+                         % (loss_out.numel(), g_loss.numel()))
+    grad = torch.empty_like(rays_lt)
+    check(L.rnr_rays_chrom_loss_backward(_ptr(rays_lt), _ptr(alpha), _ptr(img), _ptr(loss_out), _ptr(g_loss), _ptr(grad), N, R, H, W,
+                                         _stream()))
+    return grad
+
+
+def _l1_args(est, gt, alpha, border, who):
+    _chk(est, 'est'); _chk(gt, 'gt'); _chk(alpha, 'alpha')
+    if est.dim() != 4:
+        raise ValueError('%s: est must be [N,C,H,W], got %s' % (who, tuple(est.shape)))
+    N, C, H, W = est.shape
+    if gt.shape != est.shape:
+        raise ValueError('%s: gt must be %s like est, got %s' % (who, tuple(est.shape), tuple(gt.shape)))
+    if tuple(alpha.shape) != (N, 1, H, W):
+        raise ValueError('%s: alpha must be [%d,1,%d,%d], got %s' % (who, N, H, W, tuple(alpha.shape)))
+    border = int(border)
+    if min(N, C, H, W) <= 0 or est.numel() >= 2 ** 31:
+        raise ValueError('%s: est %s: sizes must be positive and N*C*H*W below 2^31' % (who, tuple(est.shape)))
+    if border < 0 or H <= 2 * border or W <= 2 * border:
+        raise ValueError('%s: a border of %d leaves nothing of %d x %d' % (who, border, H, W))
+    return N, C, H, W, border
+
+
+@_device_op
+def masked_l1_loss(est, gt, alpha, border=5):
+    """The alpha-weighted L1 on the central crop (rnr_masked_l1_loss; train_rnr.py:564-569, 581-585): est, gt [N,C,H,W],
+    alpha [N,1,H,W] -> float64 device tensor [1], the mean of |fl32(est alpha) - fl32(gt alpha)| over the crop that leaves
+    `border` pixels on every side.  A crop with no pixel raises (the reference's empty mean is NaN)."""
+    L = _lib.load()
+    N, C, H, W, border = _l1_args(est, gt, alpha, border, 'masked_l1_loss')
+    out = torch.empty(1, dtype=torch.float64, device=est.device)
+    ws = _loss_workspace('l1', est.device, L.rnr_masked_l1_loss_workspace_bytes(N, H, W), N, H, W)
+    check(L.rnr_masked_l1_loss(_ptr(est), _ptr(gt), _ptr(alpha), border, _ptr(out), _ptr(ws), N, C, H, W, _stream()))
+    return out
+
+
+@_device_op
+def masked_l1_loss_backward(est, gt, alpha, border, g_loss):
+    """Adjoint of masked_l1_loss in est (rnr_masked_l1_loss_backward): g_loss a float32 device tensor of one element ->
+    grad_est [N,C,H,W], exactly 0 in the border."""
+    L = _lib.load()
+    N, C, H, W, border = _l1_args(est, gt, alpha, border, 'masked_l1_loss_backward')
+    _chk(g_loss, 'g_loss')
+    if g_loss.numel() != 1:
+        raise ValueError('masked_l1_loss_backward: g_loss must hold 1 element, got %d' % g_loss.numel())
+    grad = torch.empty_like(est)
+    check(L.rnr_masked_l1_loss_backward(_ptr(est), _ptr(gt), _ptr(alpha), border, _ptr(g_loss), _ptr(grad), N, C, H, W, _stream()))
+    return grad
+
+
 def calibrate_mfma_f32(device='cuda:0', seconds=0.1, waves_per_simd=2):
     """TFLOP/s this device sustains NOW in a register-resident v_mfma_f32_32x32x2_f32 loop on every SIMD
     (rnr_calibrate_mfma_f32; nominal 157.3): a probe call sizes the loop for about `seconds`.  Blocks."""
