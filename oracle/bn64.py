@@ -1,6 +1,6 @@
 """ORACLE (test infrastructure, not product): float64 BatchNorm statistics of a convolution's written output, for tests that
 compare the statistics the convolution kernels of conv.hip publish (per-view sum / sum of squares) and the BatchNorm scale /
-shift derived from them (bn_finalize_views, bn_finalize_kernel, bn_finalize_batch_kernel) with a high-precision reference.
+shift derived from them (bn_finalize_views, bn_finalize_kernel) with a high-precision reference.
 
 The input is the float32 raw output the kernel actually WROTE (NHWC, channels padded), not a CPU convolution: the statistics
 path is tested on its own, free of the convolution's rounding (the output itself is tested against float64 convolutions in

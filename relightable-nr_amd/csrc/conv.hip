@@ -28,7 +28,7 @@
 // Host side: CONV_TILES lists every instantiation of these kernels with its tile shape and launcher; plan_conv() tries the
 // candidates (try_wino80f4 ... try_gather) in priority order and returns the row, the grid and the split-K depth of one call.
 // Split-K grids write one partial-output slab per slice; splitk_reduce_kernel adds them in slice order.
-#include "rnr_internal.h"
+#include "conv_common.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -39,7 +39,6 @@ namespace rnr {
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
-constexpr int BK = 16;
 constexpr int CTHREADS = 256;
 #ifndef RNR_SPLITK_BELOW
 #define RNR_SPLITK_BELOW 257        // one workgroup per CU (a single wave per SIMD) is split two ways: 146 vs 156 ... 266 vs 304 us on the
@@ -185,19 +184,6 @@ __device__ __forceinline__ void tile_coords(const ConvParams& P, int& mt, int& n
     }
 }
 
-__device__ __forceinline__ int reflect1(int i, int n) {   // ReflectionPad2d(1)
-    i = i < 0 ? -i : i;
-    return i >= n ? 2 * n - 2 - i : i;
-}
-
-// act(v) = max(v, slope * v) with slope = 1 (none), 0.2 (LeakyReLU 0.2), 0 (ReLU): branch-free, wave-uniform slope
-__device__ __forceinline__ float act_slope(int act) {
-    return act == RNR_ACT_LRELU02 ? 0.2f : (act == RNR_ACT_RELU ? 0.0f : 1.0f);
-}
-__device__ __forceinline__ float apply_act(float v, int act) {
-    return fmaxf(v, act_slope(act) * v);
-}
-
 #include "conv_stage.inc"
 
 // ------------------------------------------------------------------------------------------------
@@ -285,26 +271,9 @@ struct StatScratch {
     }
 };
 
-// BatchNorm's affine from a channel's statistics: biased variance clamped at 0, float64, one rounding to float32
-struct BnAffine { double mean, var; float scale, shift; };
-__device__ __forceinline__ BnAffine bn_affine(double s1, double s2, double count, float gamma, float beta, float eps) {
-    const double mean = s1 / count;
-    double var = s2 / count - mean * mean;
-    var = var < 0.0 ? 0.0 : var;
-    const double g = (double)gamma / sqrt(var + (double)eps);
-    return {mean, var, (float)g, (float)((double)beta - mean * g)};
-}
-// torch.nn.BatchNorm2d in train mode also moves its running statistics: momentum, UNBIASED variance
-__device__ __forceinline__ void bn_update_running(const BnAffine& a, double count, float momentum, float* running_mean,
-                                                  float* running_var, int c) {
-    if (running_mean) running_mean[c] = (float)((1.0 - (double)momentum) * (double)running_mean[c] + (double)momentum * a.mean);
-    if (running_var) {
-        const double unb = count > 1.0 ? a.var * count / (count - 1.0) : a.var;
-        running_var[c] = (float)((1.0 - (double)momentum) * (double)running_var[c] + (double)momentum * unb);
-    }
-}
-
-// scale / shift of views [n_first, n_first + n_views) from the summed shards (the arithmetic of bn_finalize_kernel).
+// BatchNorm's affine (bn_affine, bn_update_running) is conv_common.h's: the fused finalise here and the stand-alone
+// bn_finalize_kernel below evaluate the same expression, and the backward reads what they kept.
+// scale / shift of views [n_first, n_first + n_views) from the summed shards.
 // The (sum, sum of squares) pair of a channel is one 16-byte sc1 load per shard — L1-bypassing like the 8-byte agent-scope
 // atomic load, but all STAT_SHARDS of them are in flight at once (a chain of __hip_atomic_load is issued one at a time:
 // 16 round trips, 20 us at the end of a 150 us kernel) — and one 16-byte sc1 store of zeros.
@@ -1398,64 +1367,59 @@ bn_finalize_shards_kernel(const ConvParams P) {
     bn_finalize_views(P, blockIdx.x, 1, threadIdx.x, (int)(blockIdx.y * blockDim.x), (int)(gridDim.y * blockDim.x));
 }
 
-template <bool RESET>
+// The finalise on its own, for statistics that rnr_conv2d left in plain [view][channel] form (bn_finalize_views' arithmetic):
+// the one kernel behind rnr_bn_finalize, rnr_bn_finalize_reset, rnr_bn_finalize_batch and rnr_bn_finalize_saved.
+// One lane per (group, channel), where a group is a view, or with WHOLE the whole call: torch's train-mode BatchNorm2d over
+// (N,H,W) (pytorch_prototyping.py via nn.BatchNorm2d) sums the per-view partial sums, writes the same scale / shift to every
+// view and moves running_mean / running_var where given.  reset: statistics are left at zero.  saved (or NULL): per (group,
+// channel) the (mean, 1 / sqrt(var + eps)) that rnr_conv_out_backward reads, float64.
+template <bool WHOLE>
 __global__ void __launch_bounds__(256)
 bn_finalize_kernel(double* __restrict__ stats, const float* __restrict__ gamma, const float* __restrict__ beta,
-                   float* __restrict__ scale, float* __restrict__ shift, int nviews, int channels, int c_pad,
-                   double count, float eps) {
+                   float* __restrict__ scale, float* __restrict__ shift, float* __restrict__ running_mean,
+                   float* __restrict__ running_var, float momentum, double* __restrict__ saved, int reset, int nviews,
+                   int channels, int c_pad, double count_per_view, float eps) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nviews * c_pad) return;
+    if (i >= (WHOLE ? 1 : nviews) * c_pad) return;
     const int c = i % c_pad;
-    float sc = 0.f, sh = 0.f;
-    if (c < channels) {
-        const BnAffine a = bn_affine(stats[2 * (size_t)i + 0], stats[2 * (size_t)i + 1], count, gamma[c], beta[c], eps);
-        sc = a.scale;
-        sh = a.shift;
-    }
-    scale[i] = sc;
-    shift[i] = sh;
-    if (RESET) { stats[2 * (size_t)i + 0] = 0.0; stats[2 * (size_t)i + 1] = 0.0; }
-}
-
-// Whole-batch statistics (torch's train-mode BatchNorm2d over (N,H,W), pytorch_prototyping.py via nn.BatchNorm2d):
-// one lane per channel sums the per-view partial sums, writes the same scale/shift to every view and optionally
-// updates running_mean / running_var (momentum m, UNBIASED variance, as torch does).  Always resets stats.
-__global__ void __launch_bounds__(256)
-bn_finalize_batch_kernel(double* __restrict__ stats, const float* __restrict__ gamma, const float* __restrict__ beta,
-                         float* __restrict__ scale, float* __restrict__ shift, float* __restrict__ running_mean,
-                         float* __restrict__ running_var, float momentum, int nviews, int channels, int c_pad,
-                         double count_per_view, float eps) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= c_pad) return;
-    double s1 = 0.0, s2 = 0.0;
-    for (int n = 0; n < nviews; n++) {
-        const size_t i = (size_t)n * c_pad + c;
-        s1 += stats[2 * i + 0];
-        s2 += stats[2 * i + 1];
-        stats[2 * i + 0] = 0.0;
-        stats[2 * i + 1] = 0.0;
+    double s1, s2, count;
+    if (WHOLE) {
+        s1 = 0.0; s2 = 0.0;
+        for (int n = 0; n < nviews; n++) {
+            const size_t j = (size_t)n * c_pad + c;
+            s1 += stats[2 * j + 0];
+            s2 += stats[2 * j + 1];
+            if (reset) { stats[2 * j + 0] = 0.0; stats[2 * j + 1] = 0.0; }
+        }
+        count = count_per_view * (double)nviews;
+    } else {
+        s1 = stats[2 * (size_t)i + 0];
+        s2 = stats[2 * (size_t)i + 1];
+        if (reset) { stats[2 * (size_t)i + 0] = 0.0; stats[2 * (size_t)i + 1] = 0.0; }
+        count = count_per_view;
     }
     float sc = 0.f, sh = 0.f;
+    double mean = 0.0, rstd = 0.0;
     if (c < channels) {
-        const double count = count_per_view * (double)nviews;
         const BnAffine a = bn_affine(s1, s2, count, gamma[c], beta[c], eps);
         sc = a.scale;
         sh = a.shift;
-        bn_update_running(a, count, momentum, running_mean, running_var, c);
+        mean = a.mean;
+        rstd = 1.0 / sqrt(a.var + (double)eps);
+        if (WHOLE) bn_update_running(a, count, momentum, running_mean, running_var, c);
     }
-    for (int n = 0; n < nviews; n++) {
-        scale[(size_t)n * c_pad + c] = sc;
-        shift[(size_t)n * c_pad + c] = sh;
+    for (int n = 0; n < (WHOLE ? nviews : 1); n++) {       // WHOLE: i = c, the same affine for every view
+        scale[(size_t)n * c_pad + i] = sc;
+        shift[(size_t)n * c_pad + i] = sh;
     }
+    if (saved) { saved[2 * (size_t)i + 0] = mean; saved[2 * (size_t)i + 1] = rstd; }
 }
 
 __host__ __device__ __forceinline__ int weight_row_stride(int c_out_pad) { return (c_out_pad + 127) / 128 * 128; }
 
 // value of the (parity, tap, padded input channel c, output column co) entry of the implicit-GEMM weight matrix
 __device__ __forceinline__ float gemm_weight(const rnr_conv_desc& d, const float* __restrict__ w, int par, int tp, int c, int co) {
-    int ci = -1;
-    if (c < d.c_in0_pad) { if (c < d.c_in0) ci = c; }
-    else { const int c1 = c - d.c_in0_pad; if (c1 < d.c_in1) ci = d.c_in0 + c1; }
+    const int ci = live_channel(c, d.c_in0, d.c_in0_pad, d.c_in1);
     if (ci < 0 || co >= d.c_out) return 0.0f;
     const int cin = d.c_in0 + d.c_in1;
     if (d.kind == RNR_CONV3x3_REFLECT) return w[((size_t)co * cin + ci) * 9 + tp];
@@ -1876,8 +1840,8 @@ static ConvPlan plan_conv(const rnr_conv_desc* d, int N, int H, int W, ConvMode 
     const bool s2 = d->kind == RNR_CONV4x4S2_REFLECT, transposed = d->kind == RNR_CONVT4x4S2;
     p.N = N;
     p.taps = d->kind == RNR_CONV3x3_REFLECT ? 9 : (s2 ? 16 : 4);
-    p.Ho = s2 ? H / 2 : H; p.Wo = s2 ? W / 2 : W;
-    p.OH = transposed ? 2 * H : p.Ho; p.OW = transposed ? 2 * W : p.Wo;
+    p.OH = conv_out_size(d->kind, H); p.OW = conv_out_size(d->kind, W);
+    p.Ho = transposed ? H : p.OH; p.Wo = transposed ? W : p.OW;     // the transposed kind: per parity class
     p.M = N * p.Ho * p.Wo;
     p.chunks_per_tap = (d->c_in0_pad + d->c_in1_pad) / BK;
     p.kt_total = p.taps * p.chunks_per_tap;
@@ -1896,32 +1860,6 @@ static ConvPlan plan_conv(const rnr_conv_desc* d, int N, int H, int W, ConvMode 
                  (c.tile->family == WINO80 || c.tile->family == WINO80F4 || ((c.tile->family == HALO || c.tile->family == HALO_EMU) && c.tile->tw == 32));
     if (mode == CONV_RAY) p.splitk = 1;     // the ray-renderer epilogue needs the whole K sum in one workgroup (small maps would split)
     return p;
-}
-
-static int check_desc(const rnr_conv_desc* d, const char* who) {
-    RNR_REQUIRE(d, "%s: null descriptor", who);
-    RNR_REQUIRE(d->kind >= 0 && d->kind <= 2, "%s: unknown kind %d", who, d->kind);
-    RNR_REQUIRE(d->c_in0 > 0 && d->c_in0_pad >= d->c_in0 && d->c_in0_pad % BK == 0,
-                "%s: c_in0 %d / pad %d (pad must be a multiple of %d)", who, d->c_in0, d->c_in0_pad, BK);
-    RNR_REQUIRE(d->c_in1 >= 0 && d->c_in1_pad >= d->c_in1 && d->c_in1_pad % BK == 0,
-                "%s: c_in1 %d / pad %d", who, d->c_in1, d->c_in1_pad);
-    RNR_REQUIRE(d->c_out > 0 && d->c_out_pad >= d->c_out && d->c_out_pad % BK == 0,
-                "%s: c_out %d / pad %d", who, d->c_out, d->c_out_pad);
-    RNR_REQUIRE((d->flags & ~(RNR_CONV_STATS_PREZEROED | RNR_CONV_F32_EMU_ANY | RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD4 |
-                              RNR_CONV_WINOGRAD42 | RNR_CONV_WINOGRAD4_OUT | RNR_CONV_WINOGRAD42S)) == 0,
-                "%s: unknown flags 0x%x", who, d->flags);
-    RNR_REQUIRE(!(d->flags & RNR_CONV_WINOGRAD4) || (d->flags & RNR_CONV_WINOGRAD),
-                "%s: RNR_CONV_WINOGRAD4 goes with RNR_CONV_WINOGRAD (its fallback for the shapes it does not cover)", who);
-    RNR_REQUIRE(!(d->flags & RNR_CONV_WINOGRAD42) || (d->flags & RNR_CONV_WINOGRAD),
-                "%s: RNR_CONV_WINOGRAD42 goes with RNR_CONV_WINOGRAD (its fallback for the shapes it does not cover)", who);
-    RNR_REQUIRE(!(d->flags & RNR_CONV_WINOGRAD42S) || (d->flags & RNR_CONV_WINOGRAD),
-                "%s: RNR_CONV_WINOGRAD42S goes with RNR_CONV_WINOGRAD (its fallback for the shapes it does not cover)", who);
-    RNR_REQUIRE(!(d->flags & RNR_CONV_WINOGRAD4_OUT) || (d->flags & RNR_CONV_WINOGRAD),
-                "%s: RNR_CONV_WINOGRAD4_OUT goes with RNR_CONV_WINOGRAD (its fallback for the shapes it does not cover)", who);
-    RNR_REQUIRE((d->flags & RNR_CONV_F32_EMU_ANY) != RNR_CONV_F32_EMU_ANY, "%s: choose ONE emulation format", who);
-    RNR_REQUIRE(!(d->flags & RNR_CONV_WINOGRAD) || !(d->flags & RNR_CONV_F32_EMU_ANY),
-                "%s: RNR_CONV_WINOGRAD is an exact-fp32 algorithm, not combined with the emulation formats", who);
-    return 0;
 }
 
 }  // namespace rnr
@@ -2110,11 +2048,7 @@ static int check_call(const rnr_conv_desc* d, const rnr_conv_src* src0, const rn
                 src0->channels, d->c_in0_pad);
     RNR_REQUIRE(d->c_in1_pad == 0 || (src1 && src1->data && src1->channels == d->c_in1_pad),
                 "rnr_conv2d: second source missing or channel mismatch");
-    const int min_hw = d->kind == RNR_CONVT4x4S2 ? 1 : 2;   // ReflectionPad2d(1) needs >= 2 pixels
-    RNR_REQUIRE(num_views > 0 && in_h >= min_hw && in_w >= min_hw, "rnr_conv2d: bad sizes N=%d H=%d W=%d", num_views,
-                in_h, in_w);
-    RNR_REQUIRE(d->kind != RNR_CONV4x4S2_REFLECT || (in_h % 2 == 0 && in_w % 2 == 0),
-                "rnr_conv2d: stride-2 conv needs even input size");
+    if (int e = check_size(d, num_views, in_h, in_w, "rnr_conv2d")) return e;
     if (bn && bn->gamma) {
         RNR_REQUIRE(bn->beta && bn->scale && bn->shift, "rnr_conv2d_fused: null BatchNorm pointer");
         RNR_REQUIRE(!(bn->running_mean || bn->running_var) || num_views == 1,
@@ -2283,39 +2217,45 @@ extern "C" int rnr_conv2d_fused(const rnr_conv_desc* d, const rnr_conv_src* src0
                       workspace_bytes, tile_mask, nullptr, stream);
 }
 
-static int bn_finalize_impl(double* stats, const float* gamma, const float* beta, float* scale, float* shift,
-                            int num_views, int channels, int c_pad, double count, float eps, bool reset, void* stream) {
-    RNR_REQUIRE(stats && gamma && beta && scale && shift, "rnr_bn_finalize: null pointer argument");
-    RNR_REQUIRE(num_views > 0 && channels > 0 && c_pad >= channels && count > 0, "rnr_bn_finalize: bad sizes");
-    const int total = num_views * c_pad;
-    if (reset)
-        hipLaunchKernelGGL(bn_finalize_kernel<true>, dim3((total + 255) / 256), dim3(256), 0, as_stream(stream), stats, gamma,
-                           beta, scale, shift, num_views, channels, c_pad, count, eps);
-    else
-        hipLaunchKernelGGL(bn_finalize_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, as_stream(stream), stats, gamma,
-                           beta, scale, shift, num_views, channels, c_pad, count, eps);
+// the stand-alone finalise behind its four entry points
+static int bn_finalize_launch(const char* who, double* stats, const float* gamma, const float* beta, float* scale, float* shift,
+                              float* running_mean, float* running_var, float momentum, double* saved, bool whole, bool reset,
+                              int num_views, int channels, int c_pad, double count_per_view, float eps, void* stream) {
+    RNR_REQUIRE(stats && gamma && beta && scale && shift, "%s: null pointer argument", who);
+    RNR_REQUIRE(num_views > 0 && channels > 0 && c_pad >= channels && count_per_view > 0, "%s: bad sizes", who);
+    const int total = (whole ? 1 : num_views) * c_pad;
+    hipLaunchKernelGGL(whole ? bn_finalize_kernel<true> : bn_finalize_kernel<false>, dim3((total + 255) / 256), dim3(256), 0,
+                       as_stream(stream), stats, gamma, beta, scale, shift, running_mean, running_var, momentum, saved, (int)reset,
+                       num_views, channels, c_pad, count_per_view, eps);
     return check_launch("bn_finalize_kernel");
 }
 
 extern "C" int rnr_bn_finalize(const double* stats, const float* gamma, const float* beta, float* scale,
                                float* shift, int num_views, int channels, int c_pad, double count, float eps,
                                void* stream) {
-    return bn_finalize_impl(const_cast<double*>(stats), gamma, beta, scale, shift, num_views, channels, c_pad, count, eps,
-                            false, stream);
+    return bn_finalize_launch("rnr_bn_finalize", const_cast<double*>(stats) /* reset = false: only read */, gamma, beta, scale,
+                              shift, nullptr, nullptr, 0.f, nullptr, false, false, num_views, channels, c_pad, count, eps, stream);
 }
 
 extern "C" int rnr_bn_finalize_reset(double* stats, const float* gamma, const float* beta, float* scale, float* shift,
                                      int num_views, int channels, int c_pad, double count, float eps, void* stream) {
-    return bn_finalize_impl(stats, gamma, beta, scale, shift, num_views, channels, c_pad, count, eps, true, stream);
+    return bn_finalize_launch("rnr_bn_finalize_reset", stats, gamma, beta, scale, shift, nullptr, nullptr, 0.f, nullptr, false,
+                              true, num_views, channels, c_pad, count, eps, stream);
 }
 
 extern "C" int rnr_bn_finalize_batch(double* stats, const float* gamma, const float* beta, float* scale, float* shift,
                                      float* running_mean, float* running_var, float momentum, int num_views,
                                      int channels, int c_pad, double count_per_view, float eps, void* stream) {
-    RNR_REQUIRE(stats && gamma && beta && scale && shift, "rnr_bn_finalize_batch: null pointer argument");
-    RNR_REQUIRE(num_views > 0 && channels > 0 && c_pad >= channels && count_per_view > 0, "rnr_bn_finalize_batch: bad sizes");
-    hipLaunchKernelGGL(bn_finalize_batch_kernel, dim3((c_pad + 255) / 256), dim3(256), 0, as_stream(stream), stats, gamma,
-                       beta, scale, shift, running_mean, running_var, momentum, num_views, channels, c_pad, count_per_view,
-                       eps);
-    return check_launch("bn_finalize_batch_kernel");
+    return bn_finalize_launch("rnr_bn_finalize_batch", stats, gamma, beta, scale, shift, running_mean, running_var, momentum,
+                              nullptr, true, true, num_views, channels, c_pad, count_per_view, eps, stream);
+}
+
+extern "C" int rnr_bn_finalize_saved(double* stats, const float* gamma, const float* beta, float* scale, float* shift,
+                                     float* running_mean, float* running_var, float momentum, double* saved, int whole_batch,
+                                     int num_views, int channels, int c_pad, double count_per_view, float eps, void* stream) {
+    RNR_REQUIRE(saved, "rnr_bn_finalize_saved: null pointer argument");
+    RNR_REQUIRE(whole_batch || !(running_mean || running_var),
+                "rnr_bn_finalize_saved: running statistics follow the whole batch (whole_batch = 1)");
+    return bn_finalize_launch("rnr_bn_finalize_saved", stats, gamma, beta, scale, shift, running_mean, running_var, momentum, saved,
+                              whole_batch != 0, true, num_views, channels, c_pad, count_per_view, eps, stream);
 }

@@ -91,9 +91,8 @@ __device__ __forceinline__ float4 halo_load(const HaloSrc& cs, unsigned pixel, i
 }
 
 // ---- what does the consumer apply on the way in ----
-// the producer's BatchNorm (+ bias) and activation; ZERO_OUTSIDE: the transposed conv's halo is exactly 0 outside the map
+// the producer's BatchNorm (+ bias) and activation (normalize1, conv_common.h); ZERO_OUTSIDE: the transposed conv's halo is exactly 0 outside the map
 // (mask = 0), not act(shift)
-__device__ __forceinline__ float normalize1(float x, float sc, float sh, int act) { return apply_act(x * sc + sh, act); }
 template <bool ZERO_OUTSIDE>
 __device__ __forceinline__ float4 normalize4(float4 v, const float4& sc, const float4& sh, int act, float mask = 1.f) {
     float x = normalize1(v.x, sc.x, sh.x, act);

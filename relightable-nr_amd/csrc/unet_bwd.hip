@@ -1,14 +1,15 @@
 // Backward of the U-Net convolution stack (include/rnr_hip.h, "U-Net backward"), exact fp32 only.
-//   * rnr_bn_finalize_saved            BatchNorm finalise that also keeps (mean, 1 / sqrt(var + eps)) for the backward
 //   * rnr_conv_out_backward            activation + BatchNorm (or bias) backward of one layer: reduce, then apply
 //   * rnr_conv2d_weight_backward       the weight gradient as an implicit GEMM on v_mfma_f32_32x32x2_f32, split over pixels
 //   * rnr_conv2d_input_backward_ring   the border pixels of the data gradient, where the forward kernels run on the upstream
 //                                      gradient do not give the adjoint of ReflectionPad2d / zero padding
 //   * rnr_conv_backward_desc           descriptor of that gradient convolution
 //   * rnr_unet_out_backward            tanh backward + NCHW -> padded channel-last
-// No kernel of the forward is touched: the data gradients themselves are launches of rnr_conv2d.  No atomics, no scratch
-// memory; every sum has a fixed order.
-#include "rnr_internal.h"
+// The data gradients themselves are launches of rnr_conv2d, and the statistics the BatchNorm backward reads are kept by the
+// forward's finalise (conv.hip, rnr_bn_finalize_saved).  What has to equal the forward bit for bit — reflection, the
+// consumer-side value, descriptor checks, map sizes — is conv_common.h's.  No atomics, no scratch memory; every sum has a
+// fixed order.
+#include "conv_common.h"
 
 #include <algorithm>
 
@@ -17,91 +18,6 @@ using namespace rnr;
 namespace {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ int reflect1(int i, int n) {   // ReflectionPad2d(1)
-    i = i < 0 ? -i : i;
-    return i >= n ? 2 * n - 2 - i : i;
-}
-__device__ __forceinline__ float act_slope(int act) {
-    return act == RNR_ACT_LRELU02 ? 0.2f : (act == RNR_ACT_RELU ? 0.0f : 1.0f);
-}
-// the forward's consumer-side value (conv_stage.inc, normalize1): act(v) = max(v, slope * v), v = x * sc + sh
-__device__ __forceinline__ float normalize1(float x, float sc, float sh, float slope) {
-    const float v = x * sc + sh;
-    return fmaxf(v, slope * v);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// BatchNorm finalise with saved statistics.  The affine is bn_finalize_kernel's / bn_finalize_batch_kernel's expression
-// (conv.hip, bn_affine), statement for statement, and this file is compiled with conv.hip's flags: the same bits.
-// ---------------------------------------------------------------------------------------------------------------------
-struct BnAffine { double mean, var; float scale, shift; };
-__device__ __forceinline__ BnAffine bn_affine(double s1, double s2, double count, float gamma, float beta, float eps) {
-    const double mean = s1 / count;
-    double var = s2 / count - mean * mean;
-    var = var < 0.0 ? 0.0 : var;
-    const double g = (double)gamma / sqrt(var + (double)eps);
-    return {mean, var, (float)g, (float)((double)beta - mean * g)};
-}
-__device__ __forceinline__ void bn_update_running(const BnAffine& a, double count, float momentum, float* running_mean,
-                                                  float* running_var, int c) {
-    if (running_mean) running_mean[c] = (float)((1.0 - (double)momentum) * (double)running_mean[c] + (double)momentum * a.mean);
-    if (running_var) {
-        const double unb = count > 1.0 ? a.var * count / (count - 1.0) : a.var;
-        running_var[c] = (float)((1.0 - (double)momentum) * (double)running_var[c] + (double)momentum * unb);
-    }
-}
-
-// one lane per (group, channel): group = view, or the whole call with WHOLE
-template <bool WHOLE>
-__global__ void __launch_bounds__(256)
-bn_finalize_saved_kernel(double* __restrict__ stats, const float* __restrict__ gamma, const float* __restrict__ beta,
-                         float* __restrict__ scale, float* __restrict__ shift, float* __restrict__ running_mean,
-                         float* __restrict__ running_var, float momentum, double* __restrict__ saved, int nviews, int channels,
-                         int c_pad, double count_per_view, float eps) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (WHOLE ? 1 : nviews) * c_pad) return;
-    const int c = i % c_pad;
-    double s1, s2, count;
-    if (WHOLE) {
-        s1 = 0.0; s2 = 0.0;
-        for (int n = 0; n < nviews; n++) {
-            const size_t j = (size_t)n * c_pad + c;
-            s1 += stats[2 * j + 0];
-            s2 += stats[2 * j + 1];
-            stats[2 * j + 0] = 0.0;
-            stats[2 * j + 1] = 0.0;
-        }
-        count = count_per_view * (double)nviews;
-    } else {
-        s1 = stats[2 * (size_t)i + 0];
-        s2 = stats[2 * (size_t)i + 1];
-        stats[2 * (size_t)i + 0] = 0.0;
-        stats[2 * (size_t)i + 1] = 0.0;
-        count = count_per_view;
-    }
-    float sc = 0.f, sh = 0.f;
-    double mean = 0.0, rstd = 0.0;
-    if (c < channels) {
-        const BnAffine a = bn_affine(s1, s2, count, gamma[c], beta[c], eps);
-        sc = a.scale;
-        sh = a.shift;
-        mean = a.mean;
-        rstd = 1.0 / sqrt(a.var + (double)eps);
-        if (WHOLE) bn_update_running(a, count, momentum, running_mean, running_var, c);
-    }
-    if (WHOLE) {
-        for (int n = 0; n < nviews; n++) {
-            scale[(size_t)n * c_pad + c] = sc;
-            shift[(size_t)n * c_pad + c] = sh;
-        }
-    } else {
-        scale[i] = sc;
-        shift[i] = sh;
-    }
-    saved[2 * (size_t)i + 0] = mean;
-    saved[2 * (size_t)i + 1] = rstd;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // rnr_conv_out_backward: g_v = (g_z0 + g_z1) * act'(v);  reduce S1 = sum g_v, S2 = sum g_v * y per (group, channel) in
@@ -373,8 +289,8 @@ wg_kernel(const WgParams P) {
                 if (P.src_scale[s]) sc = *reinterpret_cast<const float4*>(P.src_scale[s] + (size_t)n * C + cc);
                 if (P.src_shift[s]) sh = *reinterpret_cast<const float4*>(P.src_shift[s] + (size_t)n * C + cc);
                 const float slope = act_slope(P.src_act[s]);
-                v = make_float4(normalize1(v.x, sc.x, sh.x, slope), normalize1(v.y, sc.y, sh.y, slope),
-                                normalize1(v.z, sc.z, sh.z, slope), normalize1(v.w, sc.w, sh.w, slope));
+                v = make_float4(normalize1_slope(v.x, sc.x, sh.x, slope), normalize1_slope(v.y, sc.y, sh.y, slope),
+                                normalize1_slope(v.z, sc.z, sh.z, slope), normalize1_slope(v.w, sc.w, sh.w, slope));
             }
             breg[r] = v;
         }
@@ -441,9 +357,7 @@ wg_reduce_kernel(const float* __restrict__ slabs, float* __restrict__ grad_weigh
     const int col = (int)(idx % cin_pad);
     const int co = (int)((idx / cin_pad) % c_out_pad);
     const int tap = (int)(idx / ((long)cin_pad * c_out_pad));
-    int ci = -1;
-    if (col < c_in0_pad) { if (col < c_in0) ci = col; }
-    else if (col - c_in0_pad < c_in1) ci = c_in0 + col - c_in0_pad;
+    const int ci = live_channel(col, c_in0, c_in0_pad, c_in1);
     if (ci < 0 || co >= c_out) return;
     float s = 0.f;
     for (int k = 0; k < slices; k++) s += slabs[(size_t)k * total + idx];
@@ -462,9 +376,9 @@ static WgPlan wg_plan(const rnr_conv_desc* d, int num_views, int in_h, int in_w)
     p.wn = p.cin_pad > 64 ? 2 : 1;
     p.mtiles = (d->c_out_pad + 64 * p.wm - 1) / (64 * p.wm);
     p.ntiles = (p.cin_pad + 64 * p.wn - 1) / (64 * p.wn);
-    if (d->kind == RNR_CONV3x3_REFLECT) { p.OH = in_h; p.OW = in_w; p.AH = in_h; p.AW = in_w; }
-    else if (d->kind == RNR_CONV4x4S2_REFLECT) { p.OH = in_h / 2; p.OW = in_w / 2; p.AH = p.OH; p.AW = p.OW; }
-    else { p.OH = 2 * in_h; p.OW = 2 * in_w; p.AH = in_h; p.AW = in_w; }
+    p.OH = conv_out_size(d->kind, in_h); p.OW = conv_out_size(d->kind, in_w);
+    // anchor pixels: the output map, for the transposed kind the input map
+    p.AH = d->kind == RNR_CONVT4x4S2 ? in_h : p.OH; p.AW = d->kind == RNR_CONVT4x4S2 ? in_w : p.OW;
     p.P = (long)num_views * p.AH * p.AW;
     // split the pixels until the grid holds ~4 workgroups per CU (256 CUs); a slice is a whole number of chunks
     const long tiles = (long)p.mtiles * p.ntiles * p.taps;
@@ -586,47 +500,18 @@ unet_out_backward_kernel(const float* __restrict__ g_out, const float* __restric
 }
 
 static int check_bwd_desc(const rnr_conv_desc* d, const char* who) {
-    RNR_REQUIRE(d, "%s: null descriptor", who);
-    RNR_REQUIRE(d->kind >= 0 && d->kind <= 2, "%s: unknown kind %d", who, d->kind);
-    RNR_REQUIRE(d->c_in0 > 0 && d->c_in0_pad >= d->c_in0 && d->c_in0_pad % 16 == 0, "%s: c_in0 %d / pad %d", who, d->c_in0,
-                d->c_in0_pad);
-    RNR_REQUIRE(d->c_in1 >= 0 && d->c_in1_pad >= d->c_in1 && d->c_in1_pad % 16 == 0, "%s: c_in1 %d / pad %d", who, d->c_in1,
-                d->c_in1_pad);
-    RNR_REQUIRE(d->c_out > 0 && d->c_out_pad >= d->c_out && d->c_out_pad % 16 == 0, "%s: c_out %d / pad %d", who, d->c_out,
-                d->c_out_pad);
+    if (int e = check_desc(d, who)) return e;
     RNR_REQUIRE(!(d->flags & RNR_CONV_F32_EMU_ANY), "%s: the backward is exact fp32 only (emulation flags 0x%x)", who,
                 d->flags & RNR_CONV_F32_EMU_ANY);
     return 0;
 }
 static int check_bwd_size(const rnr_conv_desc* d, int num_views, int in_h, int in_w, const char* who) {
-    const int min_hw = d->kind == RNR_CONVT4x4S2 ? 1 : 2;
-    RNR_REQUIRE(num_views > 0 && in_h >= min_hw && in_w >= min_hw, "%s: bad sizes N=%d H=%d W=%d", who, num_views, in_h, in_w);
-    RNR_REQUIRE(d->kind != RNR_CONV4x4S2_REFLECT || (in_h % 2 == 0 && in_w % 2 == 0), "%s: stride-2 conv needs even input size",
-                who);
+    if (int e = check_size(d, num_views, in_h, in_w, who)) return e;
     RNR_REQUIRE((long)in_h * in_w * 4 < (1L << 31) && (long)num_views * in_h * in_w * 4 < (1L << 40), "%s: too large", who);
     return 0;
 }
 
 }  // namespace
-
-extern "C" int rnr_bn_finalize_saved(double* stats, const float* gamma, const float* beta, float* scale, float* shift,
-                                     float* running_mean, float* running_var, float momentum, double* saved, int whole_batch,
-                                     int num_views, int channels, int c_pad, double count_per_view, float eps, void* stream) {
-    RNR_REQUIRE(stats && gamma && beta && scale && shift && saved, "rnr_bn_finalize_saved: null pointer argument");
-    RNR_REQUIRE(num_views > 0 && channels > 0 && c_pad >= channels && count_per_view > 0, "rnr_bn_finalize_saved: bad sizes");
-    RNR_REQUIRE(whole_batch || !(running_mean || running_var),
-                "rnr_bn_finalize_saved: running statistics follow the whole batch (whole_batch = 1)");
-    const int total = (whole_batch ? 1 : num_views) * c_pad;
-    if (whole_batch)
-        hipLaunchKernelGGL(bn_finalize_saved_kernel<true>, dim3((total + 255) / 256), dim3(256), 0, as_stream(stream), stats, gamma,
-                           beta, scale, shift, running_mean, running_var, momentum, saved, num_views, channels, c_pad,
-                           count_per_view, eps);
-    else
-        hipLaunchKernelGGL(bn_finalize_saved_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, as_stream(stream), stats, gamma,
-                           beta, scale, shift, running_mean, running_var, momentum, saved, num_views, channels, c_pad,
-                           count_per_view, eps);
-    return check_launch("bn_finalize_saved_kernel");
-}
 
 extern "C" size_t rnr_conv_out_backward_workspace_bytes(int num_views, int h, int w, int c_pad) {
     if (num_views <= 0 || h <= 0 || w <= 0 || c_pad <= 0) return 0;
@@ -749,8 +634,7 @@ extern "C" int rnr_conv2d_input_backward_ring(const rnr_conv_desc* d, int source
     RingParams P = {};
     P.gy = g_y; P.weight = weight; P.grad_in = grad_in;
     P.kind = d->kind; P.N = num_views; P.H = in_h; P.W = in_w;
-    P.OH = d->kind == 0 ? in_h : (d->kind == 1 ? in_h / 2 : 2 * in_h);
-    P.OW = d->kind == 0 ? in_w : (d->kind == 1 ? in_w / 2 : 2 * in_w);
+    P.OH = conv_out_size(d->kind, in_h); P.OW = conv_out_size(d->kind, in_w);
     P.c_out = d->c_out; P.c_out_pad = d->c_out_pad;
     P.cs = source ? d->c_in1 : d->c_in0;
     P.cs_pad = source ? d->c_in1_pad : d->c_in0_pad;

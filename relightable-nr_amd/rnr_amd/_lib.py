@@ -115,7 +115,7 @@ SIGNATURES = {
     'rnr_bn_finalize': (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_double, c_float, c_void_p]),
     'rnr_bn_finalize_reset': (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_double, c_float, c_void_p]),
     'rnr_bn_finalize_batch': (c_int, [c_void_p] * 7 + [c_float, c_int, c_int, c_int, c_double, c_float, c_void_p]),
-    # U-Net backward (csrc/unet_bwd.hip)
+    # U-Net backward (csrc/unet_bwd.hip; rnr_bn_finalize_saved: csrc/conv.hip)
     'rnr_bn_finalize_saved': (c_int, [c_void_p] * 7 + [c_float, c_void_p, c_int, c_int, c_int, c_int, c_double, c_float, c_void_p]),
     'rnr_conv_out_backward_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
     'rnr_conv_out_backward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,

@@ -18,8 +18,33 @@ from ._lib import (ACT_LRELU02, ACT_NONE, ACT_RELU, CONV3x3_REFLECT, CONV4x4S2_R
 from .ops import _ptr, _stream, on_device
 
 
+BN_EPS = 1e-5           # torch.nn.BatchNorm2d's defaults, which the reference keeps
+BN_MOMENTUM = 0.1
+
+
 def _pad16(c):
     return (int(c) + 15) // 16 * 16
+
+
+def _out_hw(kind, h, w):
+    """Output map of a convolution of `kind` on an h x w input."""
+    return {CONV3x3_REFLECT: (h, w), CONV4x4S2_REFLECT: (h // 2, w // 2), CONVT4x4S2: (2 * h, 2 * w)}[kind]
+
+
+def _fetch(sd, key, device):
+    """A state-dict entry as a contiguous float32 tensor on `device` (the entry itself where it already is one)."""
+    return sd[key].detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def _running_affine(gamma, beta, running_mean, running_var):
+    """Eval-mode BatchNorm as the (scale, shift) a consumer applies."""
+    sc = gamma / torch.sqrt(running_var + BN_EPS)
+    return sc, beta - running_mean * sc
+
+
+def _max_over_views(max_views, query):
+    """Largest query(n_views) over 1 .. max_views: a plan, hence its scratch, depends on the views actually passed per call."""
+    return max(query(n) for n in range(1, max_views + 1))
 
 
 class _Act:
@@ -114,7 +139,7 @@ class UNetPlan:
         self.in_channels, self.out_channels = int(in_channels), int(out_channels)
         self.in_c_pad = _pad16(in_channels) if in_c_pad is None else int(in_c_pad)
         sd = {k: v for k, v in state_dict.items()}
-        g = lambda k: sd[prefix + k].detach().to(device=device, dtype=torch.float32).contiguous()
+        g = lambda k: _fetch(sd, prefix + k, device)
         has = lambda k: (prefix + k) in sd
         self.steps = []
         self.ws_bytes = 256
@@ -161,12 +186,7 @@ class UNetPlan:
                 packed = torch.empty(self.L.rnr_packed_weight_floats(ctypes.byref(desc)), dtype=torch.float32, device=device)
                 with on_device(device):
                     check(self.L.rnr_pack_conv_weight(ctypes.byref(desc), _ptr(w), _ptr(packed), _stream()))
-            if kind == CONV3x3_REFLECT:
-                oh, ow = s0.h, s0.w
-            elif kind == CONV4x4S2_REFLECT:
-                oh, ow = s0.h // 2, s0.w // 2
-            else:
-                oh, ow = s0.h * 2, s0.w * 2
+            oh, ow = _out_hw(kind, s0.h, s0.w)
             out = _Act(c_out, desc.c_out_pad, oh, ow, act)
             out.data = torch.empty(self.N, oh, ow, desc.c_out_pad, dtype=torch.float32, device=device)
             step = {'desc': desc, 'packed': packed, 'srcs': srcs, 'out': out, 'in_hw': (s0.h, s0.w), 'bn': None, 'sync': None,
@@ -176,9 +196,7 @@ class UNetPlan:
                 step['sync'] = torch.zeros(self.L.rnr_conv_sync_bytes(ctypes.byref(desc), self.N, s0.h, s0.w),
                                            dtype=torch.uint8, device=device)
             if bn_key is not None and has(bn_key + '.weight') and bn_mode == 'running':
-                gamma, beta = g(bn_key + '.weight'), g(bn_key + '.bias')
-                sc = gamma / torch.sqrt(g(bn_key + '.running_var') + 1e-5)
-                sh = beta - g(bn_key + '.running_mean') * sc
+                sc, sh = _running_affine(*(g(bn_key + k) for k in ('.weight', '.bias', '.running_mean', '.running_var')))
                 pad = lambda t: torch.cat([t, torch.zeros(desc.c_out_pad - c_out, device=device)])[None].repeat(self.N, 1)
                 out.scale, out.shift = pad(sc).contiguous(), pad(sh).contiguous()
             elif bn_key is not None and has(bn_key + '.weight'):
@@ -191,7 +209,7 @@ class UNetPlan:
                               'stats': None if self.fused else
                               torch.zeros(self.N, desc.c_out_pad, 2, dtype=torch.float64, device=device)}
                 if self.fused:
-                    step['cbn'] = RnrConvBn(gamma.data_ptr(), beta.data_ptr(), out.scale.data_ptr(), out.shift.data_ptr(), 1e-5)
+                    step['cbn'] = RnrConvBn(gamma.data_ptr(), beta.data_ptr(), out.scale.data_ptr(), out.shift.data_ptr(), BN_EPS)
                 if bn_mode == 'batch_all' and update_running_stats and has(bn_key + '.running_mean'):
                     rm, rv = sd[prefix + bn_key + '.running_mean'], sd[prefix + bn_key + '.running_var']
                     if not (rm.is_cuda and rm.dtype == torch.float32 and rm.is_contiguous() and
@@ -200,16 +218,17 @@ class UNetPlan:
                     step['bn']['running_mean'], step['bn']['running_var'] = rm, rv      # updated IN PLACE
                 if self.fused_single:
                     rm, rv = step['bn']['running_mean'], step['bn']['running_var']
-                    step['cbn'] = RnrConvBn(gamma.data_ptr(), beta.data_ptr(), out.scale.data_ptr(), out.shift.data_ptr(), 1e-5,
-                                            rm.data_ptr() if rm is not None else None, rv.data_ptr() if rv is not None else None, 0.1)
+                    step['cbn'] = RnrConvBn(gamma.data_ptr(), beta.data_ptr(), out.scale.data_ptr(), out.shift.data_ptr(), BN_EPS,
+                                            rm.data_ptr() if rm is not None else None, rv.data_ptr() if rv is not None else None,
+                                            BN_MOMENTUM)
             elif bias_key is not None and has(bias_key):
                 b = torch.zeros(desc.c_out_pad, dtype=torch.float32, device=device)
                 b[:c_out] = g(bias_key)
                 out.shift = b[None].repeat(self.N, 1).contiguous()
                 step['bias'] = b
             # split-K depends on the number of views actually passed at call time: size the scratch for every n <= N
-            for n_views in range(1, self.N + 1):
-                self.ws_bytes = max(self.ws_bytes, self.L.rnr_conv_workspace_bytes(ctypes.byref(desc), n_views, s0.h, s0.w))
+            self.ws_bytes = max(self.ws_bytes, _max_over_views(
+                self.N, lambda n: self.L.rnr_conv_workspace_bytes(ctypes.byref(desc), n, s0.h, s0.w)))
             self.steps.append(step)
             return out
 
@@ -264,14 +283,14 @@ class UNetPlan:
         for s in self.steps:
             d, (h, w), out = s['desc'], s['in_hw'], s['out']
             wkey, bn_key, bias_key = s['keys']
-            s['w'] = sd[pre + wkey].detach().to(device=dev, dtype=torch.float32).contiguous().clone()
+            s['w'] = _fetch(sd, pre + wkey, dev).clone()
             self.grads[pre + wkey] = torch.zeros_like(s['w'])
             if s['bn'] is not None or (bn_key is not None and self.bn_mode == 'running'):
                 if s['bn'] is None:         # 'running': forward folds the statistics; the backward wants gamma and (mean, r)
-                    s['bn'] = {'gamma': sd[pre + bn_key + '.weight'].detach().to(device=dev, dtype=torch.float32).contiguous().clone(),
-                               'beta': None, 'stats': None, 'running_mean': None, 'running_var': None}
+                    s['bn'] = {'gamma': _fetch(sd, pre + bn_key + '.weight', dev).clone(), 'beta': None, 'stats': None,
+                               'running_mean': None, 'running_var': None}
                 if self.bn_mode == 'running':
-                    s['_running'] = tuple(sd[pre + bn_key + k].detach().to(device=dev, dtype=torch.float32) for k in ('.running_mean', '.running_var'))
+                    s['_running'] = tuple(_fetch(sd, pre + bn_key + k, dev) for k in ('.running_mean', '.running_var'))
                 groups = N if self.bn_mode == 'batch' else 1
                 s['bn']['saved'] = torch.zeros(groups, d.c_out_pad, 2, dtype=torch.float64, device=dev)
                 self.grads[pre + bn_key + '.weight'] = torch.zeros(out.c, dtype=torch.float32, device=dev)
@@ -286,12 +305,13 @@ class UNetPlan:
                 g = torch.zeros(N, a.h, a.w, a.c_pad, dtype=torch.float32, device=dev)
                 a.grads.append(g)
                 s['bwd'].append({'desc': bd, 'packed': packed, 'grad': g})
-                for n_views in range(1, N + 1):
-                    self.ws_bytes = max(self.ws_bytes, L.rnr_conv_workspace_bytes(ctypes.byref(bd), n_views, out.h, out.w))
+                self.ws_bytes = max(self.ws_bytes, _max_over_views(
+                    N, lambda n: L.rnr_conv_workspace_bytes(ctypes.byref(bd), n, out.h, out.w)))
             gy_floats = max(gy_floats, N * out.h * out.w * out.c_pad)
-            for n_views in range(1, N + 1):
-                wg_bytes = max(wg_bytes, L.rnr_conv2d_weight_backward_workspace_bytes(ctypes.byref(d), n_views, h, w))
-                ob_bytes = max(ob_bytes, L.rnr_conv_out_backward_workspace_bytes(n_views, out.h, out.w, out.c_pad))
+            wg_bytes = max(wg_bytes, _max_over_views(
+                N, lambda n: L.rnr_conv2d_weight_backward_workspace_bytes(ctypes.byref(d), n, h, w)))
+            ob_bytes = max(ob_bytes, _max_over_views(
+                N, lambda n: L.rnr_conv_out_backward_workspace_bytes(n, out.h, out.w, out.c_pad)))
         if (pre + 'out_layer.0.net.1.bias') in sd:
             self.grads[pre + 'out_layer.0.net.1.bias'] = torch.zeros(self.out_channels, dtype=torch.float32, device=dev)
         self._gy = torch.zeros(gy_floats, dtype=torch.float32, device=dev)
@@ -320,13 +340,13 @@ class UNetPlan:
                     # eval mode: (running mean, 1 / sqrt(running var + eps)) in rnr_bn_finalize_saved's form
                     rm, rv = s['_running']
                     s['bn']['saved'][0, :s['out'].c, 0] = rm.double()
-                    s['bn']['saved'][0, :s['out'].c, 1] = 1.0 / torch.sqrt(rv.double() + 1e-5)
+                    s['bn']['saved'][0, :s['out'].c, 1] = 1.0 / torch.sqrt(rv.double() + BN_EPS)
 
     def repack(self, state_dict):
         """Refresh the packed weights, BatchNorm parameters and biases IN PLACE from `state_dict` (same keys and shapes as at
         construction): what a training step does after the optimiser moved the parameters.  No buffer is reallocated."""
         pre, dev = self._prefix, self.dev
-        g = lambda k: state_dict[pre + k].detach().to(device=dev, dtype=torch.float32)
+        g = lambda k: _fetch(state_dict, pre + k, dev)
         with on_device(dev):
             for s in self.steps:
                 wkey, bn_key, bias_key = s['keys']
@@ -335,14 +355,12 @@ class UNetPlan:
                     s['w'].copy_(g(wkey))
                     w = s['w']
                 else:
-                    w = g(wkey).contiguous()
+                    w = g(wkey)
                 check(self.L.rnr_pack_conv_weight(ctypes.byref(s['desc']), _ptr(w), _ptr(s['packed']), _stream()))
                 if bn_key is not None and self.bn_mode == 'running':
                     gamma, beta = g(bn_key + '.weight'), g(bn_key + '.bias')
                     rm, rv = g(bn_key + '.running_mean'), g(bn_key + '.running_var')
-                    sc = gamma / torch.sqrt(rv + 1e-5)
-                    out.scale[:, :out.c] = sc
-                    out.shift[:, :out.c] = beta - rm * sc
+                    out.scale[:, :out.c], out.shift[:, :out.c] = _running_affine(gamma, beta, rm, rv)
                     if self.training:
                         s['bn']['gamma'].copy_(gamma)
                         s['_running'] = (rm, rv)
@@ -445,11 +463,9 @@ class UNetPlan:
     @staticmethod
     def _layer_flops(d, h, w):
         cin = d.c_in0 + d.c_in1
-        if d.kind == CONV3x3_REFLECT:
-            return 2 * h * w * 9 * cin * d.c_out
-        if d.kind == CONV4x4S2_REFLECT:
-            return 2 * (h // 2) * (w // 2) * 16 * cin * d.c_out
-        return 2 * (2 * h) * (2 * w) * 4 * cin * d.c_out
+        oh, ow = _out_hw(d.kind, h, w)
+        taps = {CONV3x3_REFLECT: 9, CONV4x4S2_REFLECT: 16, CONVT4x4S2: 4}[d.kind]      # per output pixel
+        return 2 * oh * ow * taps * cin * d.c_out
 
     def _count_flops(self):
         return sum(self._layer_flops(s['desc'], *s['in_hw']) for s in self.steps)
@@ -551,17 +567,24 @@ class UNetPlan:
             check(L.rnr_conv2d_masked(ctypes.byref(s['desc']), ctypes.byref(s0), ctypes.byref(s1) if s1 else None,
                                       _ptr(s['packed']), _ptr(out.data), _ptr(bn['stats']) if bn and bn['stats'] is not None else None, n, h, w,
                                       _ptr(self.workspace), self.ws_bytes, _ptr(mask) if s is last else None, st))
-            if bn and self.training and bn['stats'] is not None:
-                whole = self.bn_mode == 'batch_all'
-                check(L.rnr_bn_finalize_saved(_ptr(bn['stats']), _ptr(bn['gamma']), _ptr(bn['beta']), _ptr(out.scale),
-                                              _ptr(out.shift), _ptr(bn['running_mean']) if whole else None,
-                                              _ptr(bn['running_var']) if whole else None, 0.1, _ptr(bn['saved']), int(whole), n,
-                                              out.c, out.c_pad, float(out.h * out.w), 1e-5, st))
-            elif bn and self.bn_mode == 'batch_all':
-                check(L.rnr_bn_finalize_batch(_ptr(bn['stats']), _ptr(bn['gamma']), _ptr(bn['beta']), _ptr(out.scale),
-                                              _ptr(out.shift), _ptr(bn['running_mean']), _ptr(bn['running_var']), 0.1, n,
-                                              out.c, out.c_pad, float(out.h * out.w), 1e-5, st))
-            elif bn and bn['stats'] is not None:
-                check(L.rnr_bn_finalize_reset(_ptr(bn['stats']), _ptr(bn['gamma']), _ptr(bn['beta']), _ptr(out.scale),
-                                        _ptr(out.shift), n, out.c, out.c_pad, float(out.h * out.w), 1e-5, st))
+            self._finalize_bn(s, n, st)
         return self.out.data[:n]
+
+    def _finalize_bn(self, s, n, st):
+        """The BatchNorm behind an unfused convolution: scale / shift from the statistics the launch left, which go back to
+        zero; a training plan also keeps (mean, 1 / sqrt(var + eps)) for the backward.  (One entry point per case, one kernel.)"""
+        out, bn, L = s['out'], s['bn'], self.L
+        if not bn or bn['stats'] is None:
+            return
+        whole = self.bn_mode == 'batch_all'
+        rm, rv = (_ptr(bn['running_mean']), _ptr(bn['running_var'])) if whole else (None, None)
+        if self.training:
+            check(L.rnr_bn_finalize_saved(_ptr(bn['stats']), _ptr(bn['gamma']), _ptr(bn['beta']), _ptr(out.scale), _ptr(out.shift),
+                                          rm, rv, BN_MOMENTUM, _ptr(bn['saved']), int(whole), n, out.c, out.c_pad,
+                                          float(out.h * out.w), BN_EPS, st))
+        elif whole:
+            check(L.rnr_bn_finalize_batch(_ptr(bn['stats']), _ptr(bn['gamma']), _ptr(bn['beta']), _ptr(out.scale), _ptr(out.shift),
+                                          rm, rv, BN_MOMENTUM, n, out.c, out.c_pad, float(out.h * out.w), BN_EPS, st))
+        else:
+            check(L.rnr_bn_finalize_reset(_ptr(bn['stats']), _ptr(bn['gamma']), _ptr(bn['beta']), _ptr(out.scale), _ptr(out.shift),
+                                          n, out.c, out.c_pad, float(out.h * out.w), BN_EPS, st))

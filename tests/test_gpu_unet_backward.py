@@ -339,10 +339,23 @@ def test_conv_out_backward(hw):
 
 @pytest.mark.parametrize('whole', [0, 1])
 def test_bn_finalize_saved_has_the_existing_bits(whole):
+    """One stand-alone finalise kernel sits behind rnr_bn_finalize, _reset, _batch and _saved: the same bits from each, statistics
+    reset by all but the first."""
+    _bn_finalize_case(whole, 3, 7, 16)
+
+
+@pytest.mark.parametrize('whole', [0, 1])
+def test_bn_finalize_saved_on_more_than_one_workgroup(whole):
+    """N=2, c=260, c_pad=272: the smallest shape with more than one 256-lane workgroup and a ragged tail in both grids (272
+    lanes for the whole batch, 544 per view)."""
+    _bn_finalize_case(whole, 2, 260, 272)
+
+
+def _bn_finalize_case(whole, N, c, c_pad):
     from rnr_amd import ops
     L = _L()
     g = torch.Generator().manual_seed(3 + whole)
-    N, c, c_pad, count = 3, 7, 16, 35.0
+    count = 35.0
     y = torch.randn(N, c, 35, generator=g, dtype=D) * 2 + 1
     stats = torch.zeros(N, c_pad, 2, dtype=D)
     stats[:, :c, 0], stats[:, :c, 1] = y.sum(2), (y * y).sum(2)
@@ -357,6 +370,10 @@ def test_bn_finalize_saved_has_the_existing_bits(whole):
         _check(L.rnr_bn_finalize_batch(ops._ptr(st0), ops._ptr(gamma), ops._ptr(beta), ops._ptr(sc0), ops._ptr(sh0), ops._ptr(rm0),
                                        ops._ptr(rv0), 0.1, N, c, c_pad, count, 1e-5, ops._stream()))
     else:
+        # plain rnr_bn_finalize first: the same affine, the statistics untouched
+        st2, (sc2, sh2) = stats.to(DEV), mk()
+        _check(L.rnr_bn_finalize(ops._ptr(st2), ops._ptr(gamma), ops._ptr(beta), ops._ptr(sc2), ops._ptr(sh2), N, c, c_pad, count,
+                                 1e-5, ops._stream()))
         _check(L.rnr_bn_finalize_reset(ops._ptr(st0), ops._ptr(gamma), ops._ptr(beta), ops._ptr(sc0), ops._ptr(sh0), N, c, c_pad,
                                        count, 1e-5, ops._stream()))
     _check(L.rnr_bn_finalize_saved(ops._ptr(st1), ops._ptr(gamma), ops._ptr(beta), ops._ptr(sc1), ops._ptr(sh1),
@@ -364,13 +381,16 @@ def test_bn_finalize_saved_has_the_existing_bits(whole):
                                    N, c, c_pad, count, 1e-5, ops._stream()))
     torch.cuda.synchronize()
     assert torch.equal(sc0, sc1) and torch.equal(sh0, sh1) and torch.equal(rm0, rm1) and torch.equal(rv0, rv1)
-    assert (st1 == 0).all()
+    assert (st0 == 0).all() and (st1 == 0).all()
+    if not whole:
+        assert torch.equal(sc2, sc1) and torch.equal(sh2, sh1) and torch.equal(st2.cpu(), stats)
     yy = y.permute(1, 0, 2).reshape(c, -1)[None] if whole else y
     mu, var = yy.mean(2), yy.var(2, unbiased=False)
     sv = saved.cpu()
     torch.testing.assert_close(sv[:, :c, 0], mu, rtol=1e-12, atol=1e-12)
     torch.testing.assert_close(sv[:, :c, 1], 1 / torch.sqrt(var + 1e-5), rtol=1e-10, atol=0)
     assert (sv[:, c:] == 0).all()
+    assert (sc1[:, c:] == 0).all() and (sh1[:, c:] == 0).all()
 
 
 # ------------------------------------------------------------------------------------------------
