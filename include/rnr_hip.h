@@ -797,7 +797,8 @@ int rnr_ray_sampler(int reflect, const float* pivots_host, int num_rays, const f
                     float* rays_dir_tangent, long num_pixels, void* stream);
 
 /* network.TextureMapper.forward (network.py:67-91) for any channel count: uv_map [N,H,W,2],
- * sh_basis_map [N,H,W,9] or NULL, textures[level] [S_l,S_l,C] -> out [N,C,H,W]. */
+ * sh_basis_map [N,H,W,9] or NULL, textures[level] [S_l,S_l,C] -> out [N,C,H,W].  Refuses what its adjoint refuses: sizes <= 0,
+ * more than 8 levels, sh_start_ch + 9 > tex_channels with an SH map. */
 int rnr_texture_mapper(const float* uv_map, const float* sh_basis_map, const float* const* textures_host,
                        const int* tex_sizes_host, int num_levels, int tex_channels, int sh_start_ch,
                        float* out, int num_views, int height, int width, void* stream);
@@ -831,7 +832,8 @@ int rnr_texture_mapper_backward(const float* uv_map, const float* sh_basis_map, 
 
 /* network.RayRenderer.forward (network.py:481-527) on API-shaped tensors: rays_uv [N,H,W,2,R],
  * rays_lt [N,R,C,H,W], lp [lp_n,Hl,Wl,C] (lp_n = 1 or N), albedos [N,C,H,W] (albedo_diffuse may be NULL).
- * Outputs [N,C,H,W] (out required, others optional) and rays_color [N,R,C,H,W] (optional). */
+ * Outputs [N,C,H,W] (out required, others optional) and rays_color [N,R,C,H,W] (optional).  Refuses what its adjoint refuses:
+ * sizes <= 0, num_rays <= num_ray_diffuse, a probe batch of 2^31 floats or more. */
 int rnr_ray_renderer(const float* rays_uv, const float* rays_lt, const float* lp, int lp_n, int lp_h,
                      int lp_w, const float* albedo_specular, const float* albedo_diffuse, int channels,
                      int num_rays, int num_ray_diffuse, int no_albedo, int seperate_albedo,

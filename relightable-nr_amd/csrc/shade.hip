@@ -25,14 +25,19 @@
 //   reflect_ray<Norm>, tbn_ray<Norm>  reflected ray in tangent space; normalise(TBN . lt)      camera.py:43, network.py:455-465
 //   ray_uv<Trig>                      rays_uv from a direction, alpha, the background -1       render.py:96-102, network.py:469-470
 //   Taps::blend / Taps::blend_fma     four-tap blend, plain | explicit-FMA chain               misc.py:42
+//   Taps::x / y / w / texel<I>, texel_offset<I>   tap j of the four; texel offsets in the calling kernel's index width
 //   level_taps                        taps at the texture-level coordinates u (S-1), (S-1) - v (S-1)   network.py:71-85
 //   envmap_taps, envmap_texels        env-map taps min(u W, W-1); the four texel pointers      network.py:497, misc.py:5-42
 //   background_colour<Norm,Trig,FMA>  the light probe seen along -view_dir of a pixel           test_rnr.py:386-391
 //   quantise_u8                       saturate_u8(round_half_even(v * 255)): the float -> 8-bit conversion of cv2.imwrite
-//   finish_ray_api                    RayRenderer's group means, albedo choice, five stores    network.py:505-527
+//   element_coords                    (n, c, p, pix) of element i of an [N,C,hw] map: the drop-in operators' one lane per element
+//   sh_scaled, texbwd_idle, texbwd_scatter_tap   TextureMapper's SH factor; its adjoint's skip rule and tap scatter, both forms
+//   probe_colour<I>, ray_n_spec .. ray_group_albedo   RayRenderer and its adjoint: a ray's colour; the group rule   network.py:497-527
+//   RA_PIX, RA_QTR, RA_CH, RayTile    the tiled form of both: prologue (uv staging), epilogue (partial sums in LDS), launch_ray_api
 //   RayLanes                          32-lanes-per-pixel layout, net_in row staging, alpha of ray_render / ray_weights
 //   view_offset                       view index and in-view offset from the workgroup quotient
-// Host side: grid256 / ray_grid, transpose_pivots, fill_texture_levels, ray_launch_checks (ni_need and the shared checks).
+// Host side: grid256 / ray_grid, transpose_pivots, fill_texture_levels, ray_launch_checks (ni_need and the shared checks),
+// texture_mapper_operands / ray_renderer_operands (checks and parameter block of a forward and its adjoint), launch_ray_api.
 // One exception: ray_render_kernel keeps the text of envmap_texels and Taps::blend_fma in its own body (sharing them changed
 // its register allocation); the comment there names what it mirrors.
 #include "rnr_internal.h"
@@ -252,6 +257,8 @@ face_tangents_kernel(rnr_mesh mesh, float* __restrict__ out) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// offset of texel (x, y) of a channel-last [rows, width, C] map, in the index type I of the calling kernel
+template <class I> __device__ __forceinline__ I texel_offset(int x, int y, int width, int C) { return ((I)y * width + x) * C; }
 // bilinear taps of misc.interpolate_bilinear (misc.py:14-40)
 struct Taps {
     int x0, y0, x1, y1;
@@ -264,6 +271,11 @@ struct Taps {
     __device__ __forceinline__ float blend_fma(float i00, float i10, float i01, float i11) const {
         return __builtin_fmaf(i11, w11, __builtin_fmaf(i01, w01, __builtin_fmaf(i10, w10, i00 * w00)));
     }
+    // tap j of (w00, w10, w01, w11): its column, row, weight and the offset of its texel in a [rows, width, C] map
+    __device__ __forceinline__ int x(int j) const { return j < 2 ? x0 : x1; }
+    __device__ __forceinline__ int y(int j) const { return (j & 1) ? y1 : y0; }
+    __device__ __forceinline__ float w(int j) const { return j == 0 ? w00 : j == 1 ? w10 : j == 2 ? w01 : w11; }
+    template <class I> __device__ __forceinline__ I texel(int j, int width, int C) const { return texel_offset<I>(x(j), y(j), width, C); }
 };
 __device__ __forceinline__ Taps bilinear_taps(float x, float y, int W, int H) {
     Taps t;
@@ -283,6 +295,16 @@ __device__ __forceinline__ Taps bilinear_taps(float x, float y, int W, int H) {
     t.w01 = (x - x0w) * (y1f - y) * valid;
     t.w11 = (x - x0w) * (y - y0w) * valid;
     return t;
+}
+// colour of the probe channel lp [Hl, Wl, C] points at under t: the four texels times lp_scale, then the blend (network.py:497-503)
+template <class I> __device__ __forceinline__ float probe_colour(const Taps& t, const float* lp, int lp_w, int C, float lp_scale) {
+    return t.blend(lp[t.texel<I>(0, lp_w, C)] * lp_scale, lp[t.texel<I>(1, lp_w, C)] * lp_scale, lp[t.texel<I>(2, lp_w, C)] * lp_scale,
+                   lp[t.texel<I>(3, lp_w, C)] * lp_scale);
+}
+// element i of an [N, C, hw] map: view n, channel c, pixel p of the view, pixel pix of the batch
+__device__ __forceinline__ void element_coords(long i, int C, int hw, long& n, int& c, long& p, long& pix) {
+    const long rem = i % ((long)C * hw);
+    n = i / ((long)C * hw); c = (int)(rem / hw); p = rem % hw; pix = n * hw + p;
 }
 // taps of a square texture level of size s at uv (TextureMapper.forward, network.py:71-85): x = u (s-1), y = (s-1) - v (s-1)
 __device__ __forceinline__ Taps level_taps(float u, float v, int s) {
@@ -1230,65 +1252,67 @@ ray_sampler_kernel(const RaySamplerParams P) {
     P.rays_uv[(pix * 2 + 1) * R + r] = v;
 }
 
-struct TexMapParams {
+struct TexMapCommon {                         // what texture_mapper_kernel and its adjoint both take
     const float* uv_map; const float* sh;   // sh may be NULL
-    const float* tex[MAX_LEVELS];
-    int tex_size[MAX_LEVELS];
-    int num_levels, C, sh_start;
-    float* out;                              // [N,C,H,W]
+    int tex_size[MAX_LEVELS], num_levels, C, sh_start;
     long npix; int hw;
 };
+struct TexMapParams : TexMapCommon {
+    const float* tex[MAX_LEVELS];
+    float* out;                              // [N,C,H,W]
+};
+
+// val times the factor f_c of channel c at batch pixel pix: the SH basis value sh[pix, c - sh_start] on the nine SH channels,
+// else 1 (network.py:87-91); sh may be NULL.  The forward scales its sum with it, the adjoint the upstream gradient
+__device__ __forceinline__ float sh_scaled(const float* sh, int sh_start, long pix, int c, float val) {
+    return (sh && c >= sh_start && c < sh_start + 9) ? val * sh[pix * 9 + (c - sh_start)] : val;
+}
 
 // any channel count (DNR uses C = 30): one lane per (channel, pixel), pixel fastest so the NCHW store coalesces
 __global__ void __launch_bounds__(256)
 texture_mapper_kernel(const TexMapParams P) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P.npix * P.C) return;
-    const long n = i / ((long)P.C * P.hw);
-    const long rem = i % ((long)P.C * P.hw);
-    const int c = (int)(rem / P.hw);
-    const long p = rem % P.hw;
-    const long pix = n * P.hw + p;
+    long n, p, pix; int c;
+    element_coords(i, P.C, P.hw, n, c, p, pix);
     const float u = P.uv_map[pix * 2 + 0], v = P.uv_map[pix * 2 + 1];
     float acc = 0.f;
     for (int l = 0; l < P.num_levels; l++) {
         const int s = P.tex_size[l];
         const Taps t = level_taps(u, v, s);
-        const float* tex = P.tex[l];
-        const float lv = t.blend(tex[((size_t)t.y0 * s + t.x0) * P.C + c], tex[((size_t)t.y1 * s + t.x0) * P.C + c],
-                                 tex[((size_t)t.y0 * s + t.x1) * P.C + c], tex[((size_t)t.y1 * s + t.x1) * P.C + c]);
+        const float* tex = P.tex[l] + c;
+        const float lv = t.blend(tex[t.texel<size_t>(0, s, P.C)], tex[t.texel<size_t>(1, s, P.C)], tex[t.texel<size_t>(2, s, P.C)],
+                                 tex[t.texel<size_t>(3, s, P.C)]);
         acc = (l == 0) ? lv : acc + lv;
     }
-    if (P.sh && c >= P.sh_start && c < P.sh_start + 9) acc *= P.sh[pix * 9 + (c - P.sh_start)];
-    P.out[i] = acc;
+    P.out[i] = sh_scaled(P.sh, P.sh_start, pix, c, acc);
 }
 
 // ------------------------------------------------------------------------------------------------
 // Adjoint of texture_mapper_kernel in the textures (rnr_texture_mapper_backward).  The forward is linear in them:
 //     out[n,c,p] = f_c(n,p) sum_levels sum_taps w T_l[y, x, c],    f_c = sh[n,p,c - sh_start] on the nine SH channels, else 1
 // so with gf = g[n,c,p] * f_c(n,p) every tap adds gf * w (in that product order) to grad_T_l[y, x, c]; no texture value is read.
-// Taps and weights are the forward's own (level_taps): same clamped indices, so no address leaves a level whatever uv_map
-// holds, and the same weight bits.  A contribution whose weight or whose gf is 0 is never added (out-of-range uv, background
-// pixels under a masked loss, -0), and a wave whose lanes all hold gf = 0 issues nothing; the entry point clears every level
-// first, so untouched texels hold exactly 0.  Lanes are (pixel, channel) with the channel fastest in both forms: one wave
+// Taps, weights, offsets and f_c are the forward's own (level_taps, texel_offset, sh_scaled): same clamped indices, so no address
+// leaves a level whatever uv_map holds, and the same weight bits.  A contribution whose weight or whose gf is 0 is never added
+// (texbwd_scatter_tap, texbwd_idle: out-of-range uv, background pixels under a masked loss, -0); the entry point clears every
+// level first, so untouched texels hold exactly 0.  Lanes are (pixel, channel) with the channel fastest in both forms: one wave
 // instruction adds to whole texel records (64 / C texels of 4 C contiguous bytes).  Texel offsets are 64-bit.
 // ------------------------------------------------------------------------------------------------
-struct TexMapBwdParams {
-    const float* uv_map; const float* sh;   // sh may be NULL
+struct TexMapBwdParams : TexMapCommon {
     const float* g;                          // grad_out [N,C,H,W]
     float* grad[MAX_LEVELS];                 // [S_l,S_l,C] each, cleared by the entry point
-    int tex_size[MAX_LEVELS];
-    int num_levels, C, sh_start;
-    long npix; int hw, H, W;
+    int H, W;
 };
 
 // gf of channel c at pixel p of view n
 __device__ __forceinline__ float texbwd_gf(const TexMapBwdParams& P, long n, long p, int c) {
-    const float g = P.g[(n * P.C + c) * P.hw + p];
-    return (P.sh && c >= P.sh_start && c < P.sh_start + 9) ? g * P.sh[(n * P.hw + p) * 9 + (c - P.sh_start)] : g;
+    return sh_scaled(P.sh, P.sh_start, n * P.hw + p, c, P.g[(n * P.C + c) * P.hw + p]);
 }
-__device__ __forceinline__ void texbwd_scatter_tap(float* level_c, int s, int C, int x, int y, float gf, float w) {
-    if (w != 0.0f) atomicAdd(level_c + ((size_t)y * s + x) * C, gf * w);
+// a lane whose gf is 0 adds nothing, and a wave none of whose lanes has anything skips together
+__device__ __forceinline__ bool texbwd_idle(float gf) { return __ballot(gf != 0.0f) == 0ull || gf == 0.0f; }
+// tap j of t adds gf * w to its texel of channel plane level_c of a level of size s, unless its weight is 0
+__device__ __forceinline__ void texbwd_scatter_tap(float* level_c, int s, int C, const Taps& t, int j, float gf) {
+    if (t.w(j) != 0.0f) atomicAdd(level_c + t.texel<size_t>(j, s, C), gf * t.w(j));
 }
 
 constexpr int TB_PIX = 64;      // form A: pixels per workgroup
@@ -1315,17 +1339,13 @@ texture_mapper_bwd_kernel(const TexMapBwdParams P) {
         for (int i = threadIdx.x; i < valid * cw; i += 256) {
             const int px = i / cw, ch = i - px * cw;
             const float gf = gf_sm[px * (TB_CH + 1) + ch];
-            if (__ballot(gf != 0.0f) == 0ull) continue;
-            if (gf == 0.0f) continue;
+            if (texbwd_idle(gf)) continue;
             const float u = uv_sm[px * 2 + 0], v = uv_sm[px * 2 + 1];
             for (int l = 0; l < P.num_levels; l++) {
                 const int s = P.tex_size[l];
                 const Taps t = level_taps(u, v, s);
-                float* gl = P.grad[l] + c0 + ch;
-                texbwd_scatter_tap(gl, s, P.C, t.x0, t.y0, gf, t.w00);
-                texbwd_scatter_tap(gl, s, P.C, t.x0, t.y1, gf, t.w10);
-                texbwd_scatter_tap(gl, s, P.C, t.x1, t.y0, gf, t.w01);
-                texbwd_scatter_tap(gl, s, P.C, t.x1, t.y1, gf, t.w11);
+#pragma unroll
+                for (int j = 0; j < 4; j++) texbwd_scatter_tap(P.grad[l] + c0 + ch, s, P.C, t, j, gf);
             }
         }
     }
@@ -1412,20 +1432,17 @@ texture_mapper_bwd_tile_kernel(const TexMapBwdParams P, int tiles_x, int tiles_y
             for (int i = t; i < TT * TT * cw; i += 256) {       // cw rounds for every thread
                 const int px = i / cw, ch = i - px * cw;
                 const float gf = gf_sm[px * (TT_CH + 1) + ch];
-                if (__ballot(gf != 0.0f) == 0ull) continue;
-                if (gf == 0.0f) continue;
+                if (texbwd_idle(gf)) continue;
                 const int4 xy = tap_xy[px];
                 const float4 w = tap_w[px];
-                const int xs[4] = {xy.x, xy.x, xy.z, xy.z}, ys[4] = {xy.y, xy.w, xy.y, xy.w};
-                const float ws[4] = {w.x, w.y, w.z, w.w};
+                const Taps tq = {xy.x, xy.y, xy.z, xy.w, w.x, w.y, w.z, w.w};
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
-                    if (ws[j] == 0.0f) continue;
-                    const int rx = xs[j] - bx0, ry = ys[j] - by0;
-                    if ((unsigned)rx < (unsigned)bw && (unsigned)ry < (unsigned)bh)
-                        atomicAdd(&box_sm[(ry * bw + rx) * cw + ch], gf * ws[j]);
+                    const int rx = tq.x(j) - bx0, ry = tq.y(j) - by0;
+                    if (tq.w(j) != 0.0f && (unsigned)rx < (unsigned)bw && (unsigned)ry < (unsigned)bh)
+                        atomicAdd(&box_sm[(ry * bw + rx) * cw + ch], gf * tq.w(j));
                     else
-                        atomicAdd(gl + ((size_t)ys[j] * s + xs[j]) * P.C + ch, gf * ws[j]);
+                        texbwd_scatter_tap(gl + ch, s, P.C, tq, j, gf);     // outside the box (or weight 0: nothing)
                 }
             }
             __syncthreads();
@@ -1434,7 +1451,7 @@ texture_mapper_bwd_tile_kernel(const TexMapBwdParams P, int tiles_x, int tiles_y
                 if (val == 0.0f) continue;
                 const int q = i / cw, ch = i - q * cw;
                 const int ry = q / bw, rx = q - ry * bw;
-                atomicAdd(gl + ((size_t)(by0 + ry) * s + (bx0 + rx)) * P.C + ch, val);
+                atomicAdd(gl + texel_offset<size_t>(bx0 + rx, by0 + ry, s, P.C) + ch, val);
             }
         }
     }
@@ -1453,17 +1470,29 @@ struct RayApiParams {
     long npix; int hw;
 };
 
-// output element i = (n, c, pixel) from its sums over the specular and the diffuse rays: group means, albedo choice and the
-// optional outputs of RayRenderer.forward (network.py:505-527)
+// The group rule of RayRenderer.forward (network.py:505-527), for the forward and its adjoint: the first R - n_diff rays are specular,
+// the rest diffuse; without diffuse rays the diffuse outputs are constants (0, no gradient); the diffuse group is multiplied by its
+// own albedo map only when asked and given one, else by the specular map
+__device__ __forceinline__ int ray_n_spec(const RayApiParams& P) { return P.R - P.n_diff; }
+__device__ __forceinline__ bool ray_has_diffuse(const RayApiParams& P) { return P.n_diff > 0; }
+__device__ __forceinline__ bool ray_own_diffuse_albedo(const RayApiParams& P) { return P.separate && P.alb_diff; }
+// s / ray count of each group: the means of the forward's sums, and of the adjoint's group gradients per ray
+__device__ __forceinline__ void ray_group_means(const RayApiParams& P, float s_spec, float s_diff, float& m_spec, float& m_diff) {
+    m_spec = s_spec / (float)ray_n_spec(P);
+    m_diff = ray_has_diffuse(P) ? s_diff / (float)P.n_diff : 0.0f;
+}
+// the albedo each group is multiplied by at output element i (1 with no_albedo: the product is then exact)
+__device__ __forceinline__ void ray_group_albedo(const RayApiParams& P, long i, float& as, float& ad) {
+    as = P.no_albedo ? 1.0f : P.alb_spec[i];
+    ad = P.no_albedo ? 1.0f : (ray_own_diffuse_albedo(P) ? P.alb_diff[i] : as);
+}
+
+// output element i = (n, c, pixel) from its sums over the specular and the diffuse rays: the group rule, then the five stores
 __device__ __forceinline__ void finish_ray_api(const RayApiParams& P, long i, float s_spec, float s_diff) {
-    const float ls = s_spec / (float)(P.R - P.n_diff);
-    const float as = P.alb_spec[i];
-    const float os = P.no_albedo ? ls : as * ls;
-    float ld = 0.f, od = 0.f;
-    if (P.n_diff > 0) {
-        ld = s_diff / (float)P.n_diff;
-        od = P.no_albedo ? ld : ((P.separate && P.alb_diff) ? P.alb_diff[i] : as) * ld;
-    }
+    float ls, ld, as, ad;
+    ray_group_means(P, s_spec, s_diff, ls, ld);
+    ray_group_albedo(P, i, as, ad);
+    const float os = as * ls, od = ray_has_diffuse(P) ? ad * ld : 0.0f;
     P.out[i] = os + od;
     if (P.out_spec) P.out_spec[i] = os;
     if (P.out_diff) P.out_diff[i] = od;
@@ -1475,21 +1504,15 @@ __global__ void __launch_bounds__(256)
 ray_renderer_api_kernel(const RayApiParams P) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;     // over N*C*hw
     if (i >= P.npix * P.C) return;
-    const long n = i / ((long)P.C * P.hw);
-    const long rem = i % ((long)P.C * P.hw);
-    const int c = (int)(rem / P.hw);
-    const long p = rem % P.hw;
-    const long pix = n * P.hw + p;
-    const int n_spec = P.R - P.n_diff;
+    long n, p, pix; int c;
+    element_coords(i, P.C, P.hw, n, c, p, pix);
+    const int n_spec = ray_n_spec(P);
     const float* lp = P.lp + (P.lp_n == 1 ? 0 : (size_t)n * P.lp_h * P.lp_w * P.C);
     float ss = 0.f, sd = 0.f;
     for (int r = 0; r < P.R; r++) {
         const float u = P.rays_uv[(pix * 2 + 0) * P.R + r], v = P.rays_uv[(pix * 2 + 1) * P.R + r];
         const Taps t = envmap_taps(u, v, P.lp_w, P.lp_h);
-        const float col = t.blend(lp[((size_t)t.y0 * P.lp_w + t.x0) * P.C + c] * P.lp_scale,
-                                  lp[((size_t)t.y1 * P.lp_w + t.x0) * P.C + c] * P.lp_scale,
-                                  lp[((size_t)t.y0 * P.lp_w + t.x1) * P.C + c] * P.lp_scale,
-                                  lp[((size_t)t.y1 * P.lp_w + t.x1) * P.C + c] * P.lp_scale);
+        const float col = probe_colour<size_t>(t, lp + c, P.lp_w, P.C, P.lp_scale);
         const size_t li = (((size_t)n * P.R + r) * P.C + c) * P.hw + p;
         if (P.rays_color) P.rays_color[li] = col;
         const float prod = P.rays_lt[li] * col;
@@ -1498,65 +1521,77 @@ ray_renderer_api_kernel(const RayApiParams P) {
     finish_ray_api(P, i, ss, sd);
 }
 
-// The same operator for <= 4 colour channels (the repo's probes have 3): a workgroup owns 64 consecutive pixels; thread (pixel lane,
-// ray quarter q) takes the rays q, q + 4, ... of its pixel for ALL channels — the taps of a (pixel, ray) are computed once, rays_lt /
-// rays_color are touched along the pixels (128-byte rows per wave instruction), the uv rows come through an LDS tile (row stride
-// 2 R + 1: conflict-free) — and the four partial sums of a pixel meet in LDS.  Sums over the rays are four interleaved partial
-// sums instead of one chain: <= 1e-6 from the one-thread-per-(channel, pixel) form above (which reads uv with a stride of 2 R floats
-// and recomputes the taps per channel).
-__global__ void __launch_bounds__(256)
+// ---- the tiled form of the operator and of its adjoint: one layout for both kernels and for launch_ray_api on the host ----
+constexpr int RA_PIX = 64;      // pixels per workgroup: a wave holds the tile's 64 pixels on one ray quarter
+constexpr int RA_QTR = 4;       // ray quarters: thread (pixel lane, quarter q) takes the rays q, q + RA_QTR, ... of its pixel
+constexpr int RA_CH = 4;        // channel limit: thread (lane, c = its quarter) finishes channel c of its pixel
+constexpr int RA_MAX_RAYS = 64; // ray limit: the uv tile stays at 33 KB
+static_assert(RA_PIX == 64 && RA_CH <= RA_QTR, "a wave per ray quarter, a quarter per channel");
+
+struct RayTile {
+    int lane, qtr, urow;        // pixel lane, ray quarter, row stride of the uv tile (2 R + 1: conflict-free)
+    bool live; long n, p;       // whether the lane holds a pixel of the batch; its view and its pixel of the view (0 where not)
+    // workgroup prologue: the uv rows of the tile's pixels go to sm; ends with a barrier
+    __device__ __forceinline__ RayTile(const RayApiParams& P, float* sm) {
+        const long pix0 = (long)blockIdx.x * RA_PIX;
+        const int R = P.R, valid = (int)min((long)RA_PIX, P.npix - pix0);
+        lane = threadIdx.x & (RA_PIX - 1); qtr = threadIdx.x / RA_PIX; urow = 2 * R + 1;
+        for (int i = threadIdx.x; i < valid * 2 * R; i += RA_PIX * RA_QTR) {
+            const int px = i / (2 * R), k = i - px * 2 * R;
+            sm[px * urow + k] = P.rays_uv[pix0 * 2 * R + i];
+        }
+        __syncthreads();
+        live = lane < valid;
+        n = live ? (pix0 + lane) / P.hw : 0; p = live ? (pix0 + lane) % P.hw : 0;
+    }
+    // uv of ray r of the lane's pixel; a lane without a pixel gets the background's -1, which has no tap
+    __device__ __forceinline__ float2 uv(const float* sm, int R, int r) const {
+        return live ? make_float2(sm[lane * urow + r], sm[lane * urow + R + r]) : make_float2(-1.0f, -1.0f);
+    }
+    // workgroup epilogue: the quarters' partial sums meet in sm, which the uv tile has left, as [quarter][spec | diff][channel][lane];
+    // a thread (lane, c = qtr) that finishes a channel gets true and the sums of channel c over all rays of its pixel
+    __device__ __forceinline__ int slot(int q, int group, int c) const { return ((q * 2 + group) * RA_CH + c) * RA_PIX + lane; }
+    __device__ __forceinline__ bool sums(float* sm, int C, const float (&ss)[RA_CH], const float (&sd)[RA_CH], float& s_spec, float& s_diff) const {
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < RA_CH; c++) { sm[slot(qtr, 0, c)] = ss[c]; sm[slot(qtr, 1, c)] = sd[c]; }
+        __syncthreads();
+        if (!live || qtr >= C) return false;
+        s_spec = 0.f; s_diff = 0.f;
+#pragma unroll
+        for (int q = 0; q < RA_QTR; q++) { s_spec += sm[slot(q, 0, qtr)]; s_diff += sm[slot(q, 1, qtr)]; }
+        return true;
+    }
+};
+
+// The same operator for <= RA_CH colour channels (the repo's probes have 3) in the RayTile layout: the taps of a (pixel, ray) are
+// computed once for ALL channels, rays_lt / rays_color are touched along the pixels (128-byte rows per wave instruction), the uv rows
+// come through LDS.  Sums over the rays are four interleaved partial sums instead of one chain: <= 1e-6 from the
+// one-thread-per-(channel, pixel) form above (which reads uv with a stride of 2 R floats and recomputes the taps per channel).
+__global__ void __launch_bounds__(RA_PIX * RA_QTR)
 ray_renderer_api_tiled_kernel(const RayApiParams P) {
     extern __shared__ float ra_sm[];
-    const int R = P.R, C = P.C, n_spec = P.R - P.n_diff;
-    const long pix0 = (long)blockIdx.x * 64;
-    const int valid = (int)min((long)64, P.npix - pix0);
-    const int lane = threadIdx.x & 63, qtr = threadIdx.x >> 6;
-    const int urow = 2 * R + 1;
-    for (int i = threadIdx.x; i < valid * 2 * R; i += 256) {
-        const int px = i / (2 * R), k = i - px * 2 * R;
-        ra_sm[px * urow + k] = P.rays_uv[pix0 * 2 * R + i];
-    }
-    __syncthreads();
-    const long pix = pix0 + lane;
-    const bool live = lane < valid;
-    const long n = live ? pix / P.hw : 0, p = live ? pix % P.hw : 0;
-    const float* lp = P.lp + (P.lp_n == 1 ? 0 : (size_t)n * P.lp_h * P.lp_w * C);
-    float ss[4] = {0.f, 0.f, 0.f, 0.f}, sd[4] = {0.f, 0.f, 0.f, 0.f};
-    if (live) {
-        for (int r = qtr; r < R; r += 4) {
-            const float u = ra_sm[lane * urow + r], v = ra_sm[lane * urow + R + r];
-            const Taps t = envmap_taps(u, v, P.lp_w, P.lp_h);
-            const float* l00 = lp + ((size_t)t.y0 * P.lp_w + t.x0) * C;
-            const float* l10 = lp + ((size_t)t.y1 * P.lp_w + t.x0) * C;
-            const float* l01 = lp + ((size_t)t.y0 * P.lp_w + t.x1) * C;
-            const float* l11 = lp + ((size_t)t.y1 * P.lp_w + t.x1) * C;
+    const int R = P.R, C = P.C, n_spec = ray_n_spec(P);
+    const RayTile T(P, ra_sm);
+    const float* lp = P.lp + (P.lp_n == 1 ? 0 : (size_t)T.n * P.lp_h * P.lp_w * C);
+    float ss[RA_CH] = {0.f, 0.f, 0.f, 0.f}, sd[RA_CH] = {0.f, 0.f, 0.f, 0.f};
+    if (T.live) {
+        for (int r = T.qtr; r < R; r += RA_QTR) {
+            const float2 uv = T.uv(ra_sm, R, r);
+            const Taps t = envmap_taps(uv.x, uv.y, P.lp_w, P.lp_h);
 #pragma unroll
-            for (int c = 0; c < 4; c++) {
+            for (int c = 0; c < RA_CH; c++) {
                 if (c >= C) break;
-                const float col = t.blend(l00[c] * P.lp_scale, l10[c] * P.lp_scale, l01[c] * P.lp_scale, l11[c] * P.lp_scale);
-                const size_t li = (((size_t)n * R + r) * C + c) * P.hw + p;
+                const float col = probe_colour<size_t>(t, lp + c, P.lp_w, C, P.lp_scale);
+                const size_t li = (((size_t)T.n * R + r) * C + c) * P.hw + T.p;
                 if (P.rays_color) P.rays_color[li] = col;
                 const float prod = P.rays_lt[li] * col;
                 if (r < n_spec) ss[c] += prod; else sd[c] += prod;
             }
         }
     }
-    __syncthreads();        // the uv tile is dead: the partial sums take its place, [quarter][spec | diff][channel][lane]
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        ra_sm[((qtr * 2 + 0) * 4 + c) * 64 + lane] = ss[c];
-        ra_sm[((qtr * 2 + 1) * 4 + c) * 64 + lane] = sd[c];
-    }
-    __syncthreads();
-    const int c = qtr;      // thread (lane, c) finishes channel c of its pixel
-    if (!live || c >= C) return;
-    float s_spec = 0.f, s_diff = 0.f;
-#pragma unroll
-    for (int q4 = 0; q4 < 4; q4++) {
-        s_spec += ra_sm[((q4 * 2 + 0) * 4 + c) * 64 + lane];
-        s_diff += ra_sm[((q4 * 2 + 1) * 4 + c) * 64 + lane];
-    }
-    finish_ray_api(P, (n * C + c) * P.hw + p, s_spec, s_diff);
+    float s_spec, s_diff;
+    if (T.sums(ra_sm, C, ss, sd, s_spec, s_diff)) finish_ray_api(P, (T.n * C + T.qtr) * P.hw + T.p, s_spec, s_diff);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1567,10 +1602,9 @@ ray_renderer_api_tiled_kernel(const RayApiParams P) {
 // per ray r:  G_p = G_ls / ns (specular) or G_ld / n_diff (diffuse);  grad_rays_lt[r] = G_p colour_r;
 //     G_col = g_rays_color[r] + G_p rays_lt[r];  each of the four taps adds G_col w_tap lp_scale_factor to grad_lp at its texel;
 // grad_albedo = G_o ltt of its group (both groups onto the specular albedo when the diffuse group uses it too).
-// Taps, weights and the colour are the forward's own (envmap_taps, Taps::blend on lp * lp_scale): same indices, same bits.
-// The scatter is made of global float atomics (one per tap and channel, merged across a wave in the tiled form); a
-// contribution whose weight or G_col is 0 is never added, so texels no valid tap touches keep the 0 the entry point cleared
-// them to.
+// Taps, offsets, colour and the group rule are the forward's own (envmap_taps, tap_offsets, probe_colour, ray_group_*): same
+// indices, same bits.  The scatter is made of global float atomics (one per tap and channel, merged across a wave in the tiled
+// form); a contribution whose weight or G_col is 0 is never added, so untouched texels keep the 0 the entry point cleared them to.
 // ------------------------------------------------------------------------------------------------
 struct RayApiBwdParams {
     RayApiParams F;         // the forward's operands (its output pointers are unused)
@@ -1582,33 +1616,30 @@ struct RayApiBwdParams {
 };
 
 __device__ __forceinline__ float grad_or_zero(const float* g, size_t i) { return g ? g[i] : 0.0f; }
-
 // the upstream gradients of output element i = (n, c, pixel) folded onto its two outputs and, per ray, onto its group means
-__device__ __forceinline__ void ray_api_heads(const RayApiBwdParams& P, long i, float& G_os, float& G_od, float& gp_spec,
-                                              float& gp_diff) {
+__device__ __forceinline__ void ray_api_heads(const RayApiBwdParams& P, long i, float& G_os, float& G_od, float& gp_spec, float& gp_diff) {
     const RayApiParams& F = P.F;
-    const bool diff = F.n_diff > 0;         // without diffuse rays the diffuse outputs are constants
+    const bool diff = ray_has_diffuse(F);
     const float go = grad_or_zero(P.g_out, i);
     G_os = go + grad_or_zero(P.g_out_spec, i);
     G_od = diff ? go + grad_or_zero(P.g_out_diff, i) : 0.0f;
-    const float as = F.no_albedo ? 1.0f : F.alb_spec[i];
-    const float ad = F.no_albedo ? 1.0f : ((F.separate && F.alb_diff) ? F.alb_diff[i] : as);
+    float as, ad;
+    ray_group_albedo(F, i, as, ad);
     const float G_ls = grad_or_zero(P.g_ltt_spec, i) + G_os * as;
     const float G_ld = diff ? grad_or_zero(P.g_ltt_diff, i) + G_od * ad : 0.0f;
-    gp_spec = G_ls / (float)(F.R - F.n_diff);
-    gp_diff = diff ? G_ld / (float)F.n_diff : 0.0f;
+    ray_group_means(F, G_ls, G_ld, gp_spec, gp_diff);
 }
 
 // albedo gradients of output element i from the forward's sums over the specular and the diffuse rays
-__device__ __forceinline__ void finish_ray_api_bwd(const RayApiBwdParams& P, long i, float G_os, float G_od, float s_spec,
-                                                   float s_diff) {
+__device__ __forceinline__ void finish_ray_api_bwd(const RayApiBwdParams& P, long i, float G_os, float G_od, float s_spec, float s_diff) {
     const RayApiParams& F = P.F;
-    float gs = 0.f, gd = 0.f;
+    float gs = 0.f, gd = 0.f, ls, ld;
+    ray_group_means(F, s_spec, s_diff, ls, ld);
     if (!F.no_albedo) {
-        gs = G_os * (s_spec / (float)(F.R - F.n_diff));
-        if (F.n_diff > 0) {
-            const float t = G_od * (s_diff / (float)F.n_diff);
-            if (F.separate && F.alb_diff) gd = t; else gs = gs + t;
+        gs = G_os * ls;
+        if (ray_has_diffuse(F)) {
+            const float t = G_od * ld;
+            if (ray_own_diffuse_albedo(F)) gd = t; else gs = gs + t;
         }
     }
     if (P.grad_alb_spec) P.grad_alb_spec[i] = gs;
@@ -1625,12 +1656,9 @@ ray_renderer_api_bwd_kernel(const RayApiBwdParams P) {
     const RayApiParams& F = P.F;
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;     // over N*C*hw
     if (i >= F.npix * F.C) return;
-    const long n = i / ((long)F.C * F.hw);
-    const long rem = i % ((long)F.C * F.hw);
-    const int c = (int)(rem / F.hw);
-    const long p = rem % F.hw;
-    const long pix = n * F.hw + p;
-    const int n_spec = F.R - F.n_diff;
+    long n, p, pix; int c;
+    element_coords(i, F.C, F.hw, n, c, p, pix);
+    const int n_spec = ray_n_spec(F);
     const size_t lp_off = F.lp_n == 1 ? 0 : (size_t)n * F.lp_h * F.lp_w * F.C;
     const float* lp = F.lp + lp_off + c;
     float* glp = P.grad_lp ? P.grad_lp + lp_off + c : nullptr;
@@ -1640,9 +1668,7 @@ ray_renderer_api_bwd_kernel(const RayApiBwdParams P) {
     for (int r = 0; r < F.R; r++) {
         const float u = F.rays_uv[(pix * 2 + 0) * F.R + r], v = F.rays_uv[(pix * 2 + 1) * F.R + r];
         const Taps t = envmap_taps(u, v, F.lp_w, F.lp_h);
-        const size_t k00 = ((size_t)t.y0 * F.lp_w + t.x0) * F.C, k10 = ((size_t)t.y1 * F.lp_w + t.x0) * F.C;
-        const size_t k01 = ((size_t)t.y0 * F.lp_w + t.x1) * F.C, k11 = ((size_t)t.y1 * F.lp_w + t.x1) * F.C;
-        const float col = t.blend(lp[k00] * F.lp_scale, lp[k10] * F.lp_scale, lp[k01] * F.lp_scale, lp[k11] * F.lp_scale);
+        const float col = probe_colour<size_t>(t, lp, F.lp_w, F.C, F.lp_scale);
         const size_t li = (((size_t)n * F.R + r) * F.C + c) * F.hw + p;
         const float lt = F.rays_lt[li];
         const float gp = r < n_spec ? gp_spec : gp_diff;
@@ -1651,64 +1677,45 @@ ray_renderer_api_bwd_kernel(const RayApiBwdParams P) {
         if (r < n_spec) ss += prod; else sd += prod;
         if (glp) {
             const float G_col = grad_or_zero(P.g_rays_color, li) + gp * lt;
-            scatter_tap(glp + k00, G_col, t.w00, F.lp_scale);
-            scatter_tap(glp + k10, G_col, t.w10, F.lp_scale);
-            scatter_tap(glp + k01, G_col, t.w01, F.lp_scale);
-            scatter_tap(glp + k11, G_col, t.w11, F.lp_scale);
+#pragma unroll
+            for (int j = 0; j < 4; j++) scatter_tap(glp + t.texel<size_t>(j, F.lp_w, F.C), G_col, t.w(j), F.lp_scale);
         }
     }
     if (P.grad_alb_spec || P.grad_alb_diff) finish_ray_api_bwd(P, i, G_os, G_od, ss, sd);
 }
 
-// <= 4 channels, <= 64 rays: the layout of ray_renderer_api_tiled_kernel (64 pixels per workgroup, thread (pixel lane, ray
-// quarter), uv rows through LDS, partial sums of a pixel meeting in LDS).  A wave's 64 lanes are 64 consecutive pixels on
-// ONE ray index, and on a probe of a few hundred columns neighbouring pixels mostly hit the same texels: before the atomic,
-// adjacent lanes holding the same texel add their contributions with a segmented shuffle reduction over the run, and the
-// run's first lane issues one add (3.8x faster than one add per lane, tap and channel at 16 x 512^2: DESIGN.md 3.4b;
-// the plain form is kept as scripts/experiments/ray_backward_atomic_per_tap.diff)
-__global__ void __launch_bounds__(256)
+// The RayTile form.  A wave's 64 lanes are 64 consecutive pixels on ONE ray index, and on a probe of a few hundred columns neighbouring
+// pixels mostly hit the same texels: before the atomic, adjacent lanes holding the same texel add their contributions with a segmented
+// shuffle reduction over the run, and the run's first lane issues one add (3.8x faster than one add per lane, tap and channel at
+// 16 x 512^2: DESIGN.md 3.4b; the plain form is kept as scripts/experiments/ray_backward_atomic_per_tap.diff).  32-bit probe offsets.
+__global__ void __launch_bounds__(RA_PIX * RA_QTR)
 ray_renderer_api_bwd_tiled_kernel(const RayApiBwdParams P) {
     extern __shared__ float rb_sm[];
     const RayApiParams& F = P.F;
-    const int R = F.R, C = F.C, n_spec = F.R - F.n_diff;
-    const long pix0 = (long)blockIdx.x * 64;
-    const int valid = (int)min((long)64, F.npix - pix0);
-    const int lane = threadIdx.x & 63, qtr = threadIdx.x >> 6;
-    const int urow = 2 * R + 1;
-    for (int i = threadIdx.x; i < valid * 2 * R; i += 256) {
-        const int px = i / (2 * R), k = i - px * 2 * R;
-        rb_sm[px * urow + k] = F.rays_uv[pix0 * 2 * R + i];
-    }
-    __syncthreads();
-    const long pix = pix0 + lane;
-    const bool live = lane < valid;
-    const long n = live ? pix / F.hw : 0, p = live ? pix % F.hw : 0;
-    const unsigned lp_off = F.lp_n == 1 ? 0u : (unsigned)n * (unsigned)(F.lp_h * F.lp_w * C);  // < 2^31 floats (entry point)
+    const int R = F.R, C = F.C, n_spec = ray_n_spec(F);
+    const RayTile T(F, rb_sm);
+    const unsigned lp_off = F.lp_n == 1 ? 0u : (unsigned)T.n * (unsigned)(F.lp_h * F.lp_w * C);    // < 2^31 floats (entry point)
     const float* lp = F.lp + lp_off;
-    float gp_spec[4] = {0.f, 0.f, 0.f, 0.f}, gp_diff[4] = {0.f, 0.f, 0.f, 0.f};
-    if (live) {
+    float gp_spec[RA_CH] = {0.f, 0.f, 0.f, 0.f}, gp_diff[RA_CH] = {0.f, 0.f, 0.f, 0.f};
+    if (T.live) {
 #pragma unroll
-        for (int c = 0; c < 4; c++) {
+        for (int c = 0; c < RA_CH; c++) {
             if (c >= C) break;
             float G_os, G_od;
-            ray_api_heads(P, (n * C + c) * F.hw + p, G_os, G_od, gp_spec[c], gp_diff[c]);
+            ray_api_heads(P, (T.n * C + c) * F.hw + T.p, G_os, G_od, gp_spec[c], gp_diff[c]);
         }
     }
-    float ss[4] = {0.f, 0.f, 0.f, 0.f}, sd[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int r = qtr; r < R; r += 4) {          // wave-uniform trip count: every lane reaches the shuffles
-        const float u = live ? rb_sm[lane * urow + r] : -1.0f, v = live ? rb_sm[lane * urow + R + r] : -1.0f;
-        const Taps t = envmap_taps(u, v, F.lp_w, F.lp_h);
-        const unsigned k[4] = {((unsigned)t.y0 * F.lp_w + t.x0) * C, ((unsigned)t.y1 * F.lp_w + t.x0) * C,
-                               ((unsigned)t.y0 * F.lp_w + t.x1) * C, ((unsigned)t.y1 * F.lp_w + t.x1) * C};
-        const float w[4] = {t.w00, t.w10, t.w01, t.w11};
-        float G_col[4] = {0.f, 0.f, 0.f, 0.f};
-        if (live) {
+    float ss[RA_CH] = {0.f, 0.f, 0.f, 0.f}, sd[RA_CH] = {0.f, 0.f, 0.f, 0.f};
+    for (int r = T.qtr; r < R; r += RA_QTR) {   // wave-uniform trip count: every lane reaches the shuffles
+        const float2 uv = T.uv(rb_sm, R, r);
+        const Taps t = envmap_taps(uv.x, uv.y, F.lp_w, F.lp_h);
+        float G_col[RA_CH] = {0.f, 0.f, 0.f, 0.f};
+        if (T.live) {
 #pragma unroll
-            for (int c = 0; c < 4; c++) {
+            for (int c = 0; c < RA_CH; c++) {
                 if (c >= C) break;
-                const float col = t.blend(lp[k[0] + c] * F.lp_scale, lp[k[1] + c] * F.lp_scale, lp[k[2] + c] * F.lp_scale,
-                                          lp[k[3] + c] * F.lp_scale);
-                const size_t li = (((size_t)n * R + r) * C + c) * F.hw + p;
+                const float col = probe_colour<unsigned>(t, lp + c, F.lp_w, C, F.lp_scale);
+                const size_t li = (((size_t)T.n * R + r) * C + c) * F.hw + T.p;
                 const float lt = F.rays_lt[li];
                 const float gp = r < n_spec ? gp_spec[c] : gp_diff[c];
                 if (P.grad_rays_lt) P.grad_rays_lt[li] = gp * col;
@@ -1721,27 +1728,27 @@ ray_renderer_api_bwd_tiled_kernel(const RayApiBwdParams P) {
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             // key: the texel's offset in grad_lp; -1 where there is nothing to add (such a lane is a run of its own)
-            const int key = (live && w[j] != 0.0f) ? (int)(lp_off + k[j]) : -1;
-            float val[4];
+            const int key = (T.live && t.w(j) != 0.0f) ? (int)(lp_off + t.texel<unsigned>(j, F.lp_w, C)) : -1;
+            float val[RA_CH];
 #pragma unroll
-            for (int c = 0; c < 4; c++) val[c] = (key >= 0 && c < C) ? G_col[c] * w[j] * F.lp_scale : 0.0f;
+            for (int c = 0; c < RA_CH; c++) val[c] = (key >= 0 && c < C) ? G_col[c] * t.w(j) * F.lp_scale : 0.0f;
             const int prev = __shfl_up(key, 1, 64);
-            const bool head = lane == 0 || prev != key || key < 0;
+            const bool head = T.lane == 0 || prev != key || key < 0;
             const unsigned long long heads = __ballot(head);
-            const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
-            const int end = above ? lane + __ffsll((long long)above) - 1 : 63;      // last lane of this lane's run
+            const unsigned long long above = T.lane == 63 ? 0ull : heads >> (T.lane + 1);
+            const int end = above ? T.lane + __ffsll((long long)above) - 1 : 63;      // last lane of this lane's run
 #pragma unroll
             for (int d = 1; d < 64; d <<= 1) {
 #pragma unroll
-                for (int c = 0; c < 4; c++) {
+                for (int c = 0; c < RA_CH; c++) {
                     if (c >= C) break;
                     const float o = __shfl_down(val[c], d, 64);
-                    if (lane + d <= end) val[c] += o;
+                    if (T.lane + d <= end) val[c] += o;
                 }
             }
             if (head && key >= 0) {
 #pragma unroll
-                for (int c = 0; c < 4; c++) {
+                for (int c = 0; c < RA_CH; c++) {
                     if (c >= C) break;
                     if (val[c] != 0.0f) atomicAdd(P.grad_lp + key + c, val[c]);
                 }
@@ -1749,22 +1756,9 @@ ray_renderer_api_bwd_tiled_kernel(const RayApiBwdParams P) {
         }
     }
     if (!P.grad_alb_spec && !P.grad_alb_diff) return;
-    __syncthreads();        // the uv tile is dead: the partial sums take its place, [quarter][spec | diff][channel][lane]
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        rb_sm[((qtr * 2 + 0) * 4 + c) * 64 + lane] = ss[c];
-        rb_sm[((qtr * 2 + 1) * 4 + c) * 64 + lane] = sd[c];
-    }
-    __syncthreads();
-    const int c = qtr;      // thread (lane, c) finishes channel c of its pixel
-    if (!live || c >= C) return;
-    float s_spec = 0.f, s_diff = 0.f;
-#pragma unroll
-    for (int q4 = 0; q4 < 4; q4++) {
-        s_spec += rb_sm[((q4 * 2 + 0) * 4 + c) * 64 + lane];
-        s_diff += rb_sm[((q4 * 2 + 1) * 4 + c) * 64 + lane];
-    }
-    const long i = (n * C + c) * F.hw + p;
+    float s_spec, s_diff;
+    if (!T.sums(rb_sm, C, ss, sd, s_spec, s_diff)) return;
+    const long i = (T.n * C + T.qtr) * F.hw + T.p;
     float G_os, G_od, gs, gd;
     ray_api_heads(P, i, G_os, G_od, gs, gd);
     finish_ray_api_bwd(P, i, G_os, G_od, s_spec, s_diff);
@@ -2275,22 +2269,28 @@ extern "C" int rnr_ray_sampler(int reflect, const float* pivots_host, int num_ra
     return check_launch("ray_sampler_kernel");
 }
 
+// What rnr_texture_mapper and rnr_texture_mapper_backward check alike, and what their parameter blocks share (levels: the block's
+// textures or gradient levels).  No size bound on a level: both address texels with 64-bit offsets
+template <class F>
+static int texture_mapper_operands(const char* fn, TexMapCommon& p, F** levels, const float* uv_map, const float* sh, const void* other,
+                                   F* const* levels_host, const int* sizes, int num_levels, int C, int sh_start, int min_size, int N, int H, int W) {
+    RNR_REQUIRE(uv_map && other && levels_host && sizes, "%s: null pointer argument", fn);
+    RNR_REQUIRE(num_levels >= 1 && num_levels <= MAX_LEVELS && C > 0 && N > 0 && H > 0 && W > 0, "%s: bad sizes", fn);
+    RNR_REQUIRE(!sh || (sh_start >= 0 && sh_start + 9 <= C), "%s: sh_start_ch + 9 > channels", fn);
+    if (int e = fill_texture_levels(fn, levels, p.tex_size, levels_host, sizes, num_levels, C, 0, min_size)) return e;
+    p.uv_map = uv_map; p.sh = sh; p.num_levels = num_levels; p.C = C; p.sh_start = sh_start; p.npix = (long)N * H * W; p.hw = H * W;
+    return 0;
+}
+
 extern "C" int rnr_texture_mapper(const float* uv_map, const float* sh_basis_map, const float* const* textures_host,
                                   const int* tex_sizes_host, int num_levels, int tex_channels, int sh_start_ch,
                                   float* out, int num_views, int height, int width, void* stream) {
-    RNR_REQUIRE(uv_map && textures_host && tex_sizes_host && out, "rnr_texture_mapper: null pointer argument");
-    RNR_REQUIRE(num_levels >= 1 && num_levels <= MAX_LEVELS && tex_channels > 0, "rnr_texture_mapper: bad sizes");
-    RNR_REQUIRE(!sh_basis_map || (sh_start_ch >= 0 && sh_start_ch + 9 <= tex_channels),
-                "rnr_texture_mapper: sh_start_ch + 9 > channels");
     TexMapParams P = {};
-    P.uv_map = uv_map; P.sh = sh_basis_map;
-    // no size bound here: texture_mapper_kernel addresses texels with 64-bit offsets
-    if (int e = fill_texture_levels("rnr_texture_mapper", P.tex, P.tex_size, textures_host, tex_sizes_host, num_levels, tex_channels, 0))
+    if (int e = texture_mapper_operands("rnr_texture_mapper", P, P.tex, uv_map, sh_basis_map, out, textures_host, tex_sizes_host,
+                                        num_levels, tex_channels, sh_start_ch, 2, num_views, height, width))
         return e;
-    P.num_levels = num_levels; P.C = tex_channels; P.sh_start = sh_start_ch; P.out = out;
-    P.npix = (long)num_views * height * width; P.hw = height * width;
-    const long total = P.npix * tex_channels;
-    hipLaunchKernelGGL(texture_mapper_kernel, grid256(total), dim3(256), 0, as_stream(stream), P);
+    P.out = out;
+    hipLaunchKernelGGL(texture_mapper_kernel, grid256(P.npix * tex_channels), dim3(256), 0, as_stream(stream), P);
     return check_launch("texture_mapper_kernel");
 }
 
@@ -2304,19 +2304,12 @@ extern "C" int rnr_texture_mapper_backward(const float* uv_map, const float* sh_
                                            float* const* grad_textures_host, const int* tex_sizes_host, int num_levels,
                                            int tex_channels, int sh_start_ch, int num_views, int height, int width,
                                            void* stream) {
-    RNR_REQUIRE(uv_map && grad_out && grad_textures_host && tex_sizes_host, "rnr_texture_mapper_backward: null pointer argument");
-    RNR_REQUIRE(num_levels >= 1 && num_levels <= MAX_LEVELS && tex_channels > 0 && num_views > 0 && height > 0 && width > 0,
-                "rnr_texture_mapper_backward: bad sizes");
-    RNR_REQUIRE(!sh_basis_map || (sh_start_ch >= 0 && sh_start_ch + 9 <= tex_channels),
-                "rnr_texture_mapper_backward: sh_start_ch + 9 > channels");
     TexMapBwdParams P = {};
-    P.uv_map = uv_map; P.sh = sh_basis_map; P.g = grad_out;
-    // 64-bit texel offsets, as the forward: no size bound.  A 1 x 1 level is a texture like any other to the adjoint
-    if (int e = fill_texture_levels("rnr_texture_mapper_backward", P.grad, P.tex_size, grad_textures_host, tex_sizes_host, num_levels,
-                                    tex_channels, 0, 1))
+    // a 1 x 1 level is a texture like any other to the adjoint
+    if (int e = texture_mapper_operands("rnr_texture_mapper_backward", P, P.grad, uv_map, sh_basis_map, grad_out, grad_textures_host,
+                                        tex_sizes_host, num_levels, tex_channels, sh_start_ch, 1, num_views, height, width))
         return e;
-    P.num_levels = num_levels; P.C = tex_channels; P.sh_start = sh_start_ch;
-    P.npix = (long)num_views * height * width; P.hw = height * width; P.H = height; P.W = width;
+    P.g = grad_out; P.H = height; P.W = width;
     for (int l = 0; l < num_levels; l++)
         RNR_HIP(hipMemsetAsync(P.grad[l], 0, (size_t)P.tex_size[l] * P.tex_size[l] * tex_channels * sizeof(float), as_stream(stream)));
     // the tile form (7.53 against 8.09 ms on the bench scene at 16 x 512^2 with every channel live, 2.30 against 3.36 ms with the
@@ -2335,31 +2328,50 @@ extern "C" int rnr_texture_mapper_backward(const float* uv_map, const float* sh_
     return check_launch("texture_mapper_bwd_kernel");
 }
 
+// What rnr_ray_renderer and rnr_ray_renderer_backward check alike, and the forward's operands in the parameter block.  The probe
+// batch stays below 2^31 floats: ray_renderer_api_bwd_tiled_kernel addresses it with 32-bit offsets
+static int ray_renderer_operands(const char* fn, RayApiParams& F, const float* rays_uv, const float* rays_lt, const float* lp, int lp_n, int lp_h,
+                                 int lp_w, const float* alb_spec, const float* alb_diff, int C, int R, int n_diff, int no_albedo, int separate,
+                                 float lp_scale, int N, int H, int W) {
+    RNR_REQUIRE(rays_uv && rays_lt && lp && alb_spec, "%s: null pointer argument", fn);
+    RNR_REQUIRE(R > n_diff && n_diff >= 0, "%s: bad ray counts", fn);
+    RNR_REQUIRE(lp_n == 1 || lp_n == N, "%s: lp batch must be 1 or N", fn);
+    RNR_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && lp_h > 0 && lp_w > 0, "%s: bad sizes", fn);
+    RNR_REQUIRE((size_t)lp_n * lp_h * lp_w * C < ((size_t)1 << 31), "%s: probe batch of 2^31 floats or more", fn);
+    F.rays_uv = rays_uv; F.rays_lt = rays_lt; F.lp = lp; F.alb_spec = alb_spec; F.alb_diff = alb_diff; F.lp_n = lp_n; F.lp_h = lp_h; F.lp_w = lp_w;
+    F.C = C; F.R = R; F.n_diff = n_diff; F.no_albedo = no_albedo; F.separate = separate; F.lp_scale = lp_scale;
+    F.npix = (long)N * H * W; F.hw = H * W;
+    return 0;
+}
+// The tiled kernel where the shape allows (r05: 0.48 -> ms per 512^2 view in the drop-in loop), else the one with a lane per (pixel,
+// channel); the launch is reported under the name of the kernel that ran
+template <class P>
+static int launch_ray_api(void (*tiled)(P), const char* tiled_name, void (*plain)(P), const char* plain_name, const P& p,
+                          const RayApiParams& F, void* stream) {
+    if (F.C <= RA_CH && F.R <= RA_MAX_RAYS) {        // LDS: the uv tile, then in its place the partial sums (RayTile)
+        const size_t lds = sizeof(float) * (size_t)std::max(RA_PIX * (2 * F.R + 1), RA_QTR * 2 * RA_CH * RA_PIX);
+        hipLaunchKernelGGL(tiled, dim3((unsigned)((F.npix + RA_PIX - 1) / RA_PIX)), dim3(RA_PIX * RA_QTR), lds, as_stream(stream), p);
+        return check_launch(tiled_name);
+    }
+    hipLaunchKernelGGL(plain, grid256(F.npix * F.C), dim3(256), 0, as_stream(stream), p);
+    return check_launch(plain_name);
+}
+
 extern "C" int rnr_ray_renderer(const float* rays_uv, const float* rays_lt, const float* lp, int lp_n, int lp_h,
                                 int lp_w, const float* albedo_specular, const float* albedo_diffuse, int channels,
                                 int num_rays, int num_ray_diffuse, int no_albedo, int seperate_albedo,
                                 float lp_scale_factor, float* out, float* out_specular, float* out_diffuse,
                                 float* ltt_specular, float* ltt_diffuse, float* rays_color, int num_views, int height,
                                 int width, void* stream) {
-    RNR_REQUIRE(rays_uv && rays_lt && lp && albedo_specular && out, "rnr_ray_renderer: null pointer argument");
-    RNR_REQUIRE(num_rays > num_ray_diffuse && num_ray_diffuse >= 0, "rnr_ray_renderer: bad ray counts");
-    RNR_REQUIRE(lp_n == 1 || lp_n == num_views, "rnr_ray_renderer: lp batch must be 1 or N");
-    RayApiParams P;
-    P.rays_uv = rays_uv; P.rays_lt = rays_lt; P.lp = lp; P.alb_spec = albedo_specular; P.alb_diff = albedo_diffuse;
-    P.lp_n = lp_n; P.lp_h = lp_h; P.lp_w = lp_w; P.C = channels; P.R = num_rays; P.n_diff = num_ray_diffuse;
-    P.no_albedo = no_albedo; P.separate = seperate_albedo; P.lp_scale = lp_scale_factor;
-    P.out = out; P.out_spec = out_specular; P.out_diff = out_diffuse; P.ltt_spec = ltt_specular; P.ltt_diff = ltt_diffuse;
-    P.rays_color = rays_color; P.npix = (long)num_views * height * width; P.hw = height * width;
-    const long total = P.npix * channels;
-    if (channels <= 4 && num_rays <= 64) {
-        // r05: 64 pixels per workgroup, (pixel, ray quarter) per thread: uv rows staged through LDS, taps once per (pixel, ray) for
-        // all channels, every global access coalesced along the pixels (0.48 -> ms per 512^2 view in the drop-in loop)
-        const size_t lds = sizeof(float) * (size_t)std::max(64 * (2 * num_rays + 1), 4 * 2 * 4 * 64);
-        hipLaunchKernelGGL(ray_renderer_api_tiled_kernel, dim3((unsigned)((P.npix + 63) / 64)), dim3(256), lds, as_stream(stream), P);
-    } else {
-        hipLaunchKernelGGL(ray_renderer_api_kernel, grid256(total), dim3(256), 0, as_stream(stream), P);
-    }
-    return check_launch("ray_renderer_api_kernel");
+    RNR_REQUIRE(out, "rnr_ray_renderer: null pointer argument");
+    RayApiParams P = {};
+    if (int e = ray_renderer_operands("rnr_ray_renderer", P, rays_uv, rays_lt, lp, lp_n, lp_h, lp_w, albedo_specular, albedo_diffuse,
+                                      channels, num_rays, num_ray_diffuse, no_albedo, seperate_albedo, lp_scale_factor, num_views,
+                                      height, width))
+        return e;
+    P.out = out; P.out_spec = out_specular; P.out_diff = out_diffuse; P.ltt_spec = ltt_specular; P.ltt_diff = ltt_diffuse; P.rays_color = rays_color;
+    return launch_ray_api(ray_renderer_api_tiled_kernel, "ray_renderer_api_tiled_kernel", ray_renderer_api_kernel,
+                          "ray_renderer_api_kernel", P, P, stream);
 }
 
 extern "C" int rnr_ray_renderer_backward(const float* rays_uv, const float* rays_lt, const float* lp, int lp_n, int lp_h,
@@ -2370,33 +2382,19 @@ extern "C" int rnr_ray_renderer_backward(const float* rays_uv, const float* rays
                                          const float* g_ltt_diffuse, const float* g_rays_color, float* grad_rays_lt,
                                          float* grad_albedo_specular, float* grad_albedo_diffuse, float* grad_lp,
                                          int num_views, int height, int width, void* stream) {
-    RNR_REQUIRE(rays_uv && rays_lt && lp && albedo_specular, "rnr_ray_renderer_backward: null pointer argument");
-    RNR_REQUIRE(num_rays > num_ray_diffuse && num_ray_diffuse >= 0, "rnr_ray_renderer_backward: bad ray counts");
-    RNR_REQUIRE(lp_n == 1 || lp_n == num_views, "rnr_ray_renderer_backward: lp batch must be 1 or N");
-    RNR_REQUIRE(num_views > 0 && height > 0 && width > 0 && channels > 0 && lp_h > 0 && lp_w > 0,
-                "rnr_ray_renderer_backward: bad sizes");
-    RNR_REQUIRE(!grad_albedo_diffuse || albedo_diffuse, "rnr_ray_renderer_backward: grad_albedo_diffuse without albedo_diffuse");
-    const size_t lp_floats = (size_t)lp_n * lp_h * lp_w * channels;
-    RNR_REQUIRE(lp_floats < ((size_t)1 << 31), "rnr_ray_renderer_backward: probe batch of 2^31 floats or more");
-    if (grad_lp) RNR_HIP(hipMemsetAsync(grad_lp, 0, lp_floats * sizeof(float), as_stream(stream)));
-    if (!grad_rays_lt && !grad_albedo_specular && !grad_albedo_diffuse && !grad_lp) return 0;
     RayApiBwdParams P = {};
-    RayApiParams& F = P.F;
-    F.rays_uv = rays_uv; F.rays_lt = rays_lt; F.lp = lp; F.alb_spec = albedo_specular; F.alb_diff = albedo_diffuse;
-    F.lp_n = lp_n; F.lp_h = lp_h; F.lp_w = lp_w; F.C = channels; F.R = num_rays; F.n_diff = num_ray_diffuse;
-    F.no_albedo = no_albedo; F.separate = seperate_albedo; F.lp_scale = lp_scale_factor;
-    F.npix = (long)num_views * height * width; F.hw = height * width;
-    P.g_out = g_out; P.g_out_spec = g_out_specular; P.g_out_diff = g_out_diffuse; P.g_ltt_spec = g_ltt_specular;
-    P.g_ltt_diff = g_ltt_diffuse; P.g_rays_color = g_rays_color;
-    P.grad_rays_lt = grad_rays_lt; P.grad_alb_spec = grad_albedo_specular; P.grad_alb_diff = grad_albedo_diffuse;
+    if (int e = ray_renderer_operands("rnr_ray_renderer_backward", P.F, rays_uv, rays_lt, lp, lp_n, lp_h, lp_w, albedo_specular,
+                                      albedo_diffuse, channels, num_rays, num_ray_diffuse, no_albedo, seperate_albedo, lp_scale_factor,
+                                      num_views, height, width))
+        return e;
+    RNR_REQUIRE(!grad_albedo_diffuse || albedo_diffuse, "rnr_ray_renderer_backward: grad_albedo_diffuse without albedo_diffuse");
+    if (grad_lp) RNR_HIP(hipMemsetAsync(grad_lp, 0, (size_t)lp_n * lp_h * lp_w * channels * sizeof(float), as_stream(stream)));
+    if (!grad_rays_lt && !grad_albedo_specular && !grad_albedo_diffuse && !grad_lp) return 0;
+    P.g_out = g_out; P.g_out_spec = g_out_specular; P.g_out_diff = g_out_diffuse; P.g_ltt_spec = g_ltt_specular; P.g_ltt_diff = g_ltt_diffuse;
+    P.g_rays_color = g_rays_color; P.grad_rays_lt = grad_rays_lt; P.grad_alb_spec = grad_albedo_specular; P.grad_alb_diff = grad_albedo_diffuse;
     P.grad_lp = grad_lp;
-    if (channels <= 4 && num_rays <= 64) {
-        const size_t lds = sizeof(float) * (size_t)std::max(64 * (2 * num_rays + 1), 4 * 2 * 4 * 64);
-        hipLaunchKernelGGL(ray_renderer_api_bwd_tiled_kernel, dim3((unsigned)((F.npix + 63) / 64)), dim3(256), lds, as_stream(stream), P);
-    } else {
-        hipLaunchKernelGGL(ray_renderer_api_bwd_kernel, grid256(F.npix * channels), dim3(256), 0, as_stream(stream), P);
-    }
-    return check_launch("ray_renderer_api_bwd_kernel");
+    return launch_ray_api(ray_renderer_api_bwd_tiled_kernel, "ray_renderer_api_bwd_tiled_kernel", ray_renderer_api_bwd_kernel,
+                          "ray_renderer_api_bwd_kernel", P, P.F, stream);
 }
 
 extern "C" int rnr_ray_transport(const float* unet_raw, int c_out_pad, const float* bias, const float* net_in, int c_pad,

@@ -61,13 +61,7 @@ def _device_op(fn):
     @functools.wraps(fn)
     def wrapper(*args, **kwargs):
         dev = None
-        for a in args:
-            for t in _cuda_tensors(a):
-                if dev is None:
-                    dev = t.device
-                elif t.device != dev:
-                    raise RuntimeError('%s: arguments live on different devices (%s and %s)' % (fn.__name__, dev, t.device))
-        for a in kwargs.values():
+        for a in args + tuple(kwargs.values()):
             for t in _cuda_tensors(a):
                 if dev is None:
                     dev = t.device
@@ -110,6 +104,14 @@ def side_streams(device, n):
 
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def _level_tables(levels, sizes):       # what a C entry point takes for texture levels: device pointers and sides S_l
+    return (ctypes.c_void_p * len(levels))(*[t.data_ptr() for t in levels]), (ctypes.c_int * len(levels))(*[int(s) for s in sizes])
+
+
+def _probe3(lp):                        # one three-channel probe, [Hl,Wl,3] or [1,Hl,Wl,3], as [Hl,Wl,3]
+    return lp.reshape(lp.shape[-3], lp.shape[-2], 3)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -362,8 +364,7 @@ def shade_inputs(gb, mesh, proj_inv, R_inv, textures, pivots_spec, pivots_diff, 
         raise ValueError('shade_inputs: neural_img must be a contiguous float32 [N,C,H,W] tensor')
     sh = torch.empty(N, H, W, 9, dtype=torch.float32, device=dev) if want_sh else None
     nl = len(textures)
-    tex_ptrs = (ctypes.c_void_p * nl)(*[_chk(t, 'texture').data_ptr() for t in textures])
-    tex_sizes = (ctypes.c_int * nl)(*[int(t.shape[-2]) for t in textures])
+    tex_ptrs, tex_sizes = _level_tables([_chk(t, 'texture') for t in textures], [t.shape[-2] for t in textures])
     ps = pivots_spec.detach().cpu().contiguous().float()
     pd = pivots_diff.detach().cpu().contiguous().float()
     rays = RnrRays(ps.data_ptr(), pd.data_ptr(), ns, nd)
@@ -382,7 +383,7 @@ def ray_render(unet_raw, bias, net_in, alpha, lp, num_spec, num_diff, albedo_dif
     N, H, W, cop = unet_raw.shape
     if image is None:
         image = torch.empty(N, 3, H, W, dtype=torch.float32, device=unet_raw.device)
-    lp3 = lp.reshape(lp.shape[-3], lp.shape[-2], 3)
+    lp3 = _probe3(lp)
     check(L.rnr_ray_render(_ptr(_chk(unet_raw, 'unet_raw')), cop, _ptr(_chk(bias, 'bias')), _ptr(_chk(net_in, 'net_in')),
                            net_in.shape[-1], _ptr(_chk(alpha, 'alpha')), _ptr(_chk(lp3, 'lp')), lp3.shape[0],
                            lp3.shape[1], int(num_spec), int(num_diff), int(albedo_diff_ch), int(albedo_spec_ch),
@@ -398,7 +399,7 @@ def ray_weights(net_in, alpha, lp, num_spec, num_diff, c_w, albedo_diff_ch=0, al
     N, H, W, cp = net_in.shape
     if out is None:
         out = torch.empty(N, H, W, int(c_w), dtype=torch.float32, device=net_in.device)
-    lp3 = lp.reshape(lp.shape[-3], lp.shape[-2], 3)
+    lp3 = _probe3(lp)
     check(L.rnr_ray_weights(_ptr(_chk(net_in, 'net_in')), cp, _ptr(_chk(alpha, 'alpha')), _ptr(_chk(lp3, 'lp')), lp3.shape[0],
                             lp3.shape[1], int(num_spec), int(num_diff), int(albedo_diff_ch), int(albedo_spec_ch), _ptr(out),
                             int(c_w), N, H, W, _stream()))
@@ -469,7 +470,7 @@ def present_u8(image, alpha, proj_inv, R_inv, lp, mode='frame', rgb=False, out=N
             raise ValueError('present_u8: proj_inv and R_inv must be [%d,3,3], got %s, %s' % (N, tuple(proj_inv.shape), tuple(R_inv.shape)))
         if lp.dim() < 3 or lp.shape[-1] != 3 or lp.numel() != lp.shape[-3] * lp.shape[-2] * 3:
             raise ValueError('present_u8: lp must be one [Hl,Wl,3] probe, got %s' % (tuple(lp.shape),))
-        lp3 = lp.reshape(lp.shape[-3], lp.shape[-2], 3)
+        lp3 = _probe3(lp)
     dev = (image if image is not None else proj_inv if proj_inv is not None else out).device
     if out is None:
         out = torch.empty(N, H, W, 3, dtype=torch.uint8, device=dev)
@@ -888,13 +889,11 @@ def texture_mapper(textures, uv_map, sh_basis_map=None, sh_start_ch=3):
     N, H, W = uv_map.shape[:3]
     tex = [_chk(t.reshape(t.shape[-3], t.shape[-2], t.shape[-1]).contiguous(), 'texture') for t in textures]
     C = tex[0].shape[-1]
-    nl = len(tex)
-    ptrs = (ctypes.c_void_p * nl)(*[t.data_ptr() for t in tex])
-    sizes = (ctypes.c_int * nl)(*[int(t.shape[0]) for t in tex])
+    ptrs, sizes = _level_tables(tex, [t.shape[0] for t in tex])
     out = torch.empty(N, C, H, W, dtype=torch.float32, device=uv_map.device)
     if sh_basis_map is not None:
         _chk(sh_basis_map, 'sh_basis_map')
-    check(L.rnr_texture_mapper(_ptr(uv_map), _ptr(sh_basis_map), ptrs, sizes, nl, C, int(sh_start_ch), _ptr(out), N, H, W,
+    check(L.rnr_texture_mapper(_ptr(uv_map), _ptr(sh_basis_map), ptrs, sizes, len(tex), C, int(sh_start_ch), _ptr(out), N, H, W,
                                _stream()))
     return out
 
@@ -912,13 +911,22 @@ def texture_mapper_backward(uv_map, sh_basis_map, grad_out, tex_sizes, sh_start_
         raise RuntimeError('texture_mapper_backward: grad_out %s does not match uv_map %s' % (tuple(grad_out.shape), tuple(uv_map.shape)))
     if sh_basis_map is not None and tuple(_chk(sh_basis_map, 'sh_basis_map').shape) != (N, H, W, 9):
         raise RuntimeError('sh_basis_map must be %s, got %s' % ((N, H, W, 9), tuple(sh_basis_map.shape)))
-    nl = len(tex_sizes)
     grads = [torch.empty(int(s), int(s), C, dtype=torch.float32, device=uv_map.device) for s in tex_sizes]
-    ptrs = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in grads])
-    sizes = (ctypes.c_int * nl)(*[int(s) for s in tex_sizes])
-    check(L.rnr_texture_mapper_backward(_ptr(uv_map), _ptr(sh_basis_map), _ptr(grad_out), ptrs, sizes, nl, C, int(sh_start_ch),
+    ptrs, sizes = _level_tables(grads, tex_sizes)
+    check(L.rnr_texture_mapper_backward(_ptr(uv_map), _ptr(sh_basis_map), _ptr(grad_out), ptrs, sizes, len(grads), C, int(sh_start_ch),
                                         N, H, W, _stream()))
     return grads
+
+
+def _ray_renderer_args(rays_uv, rays_lt, lp, albedo_specular, albedo_diffuse, who):
+    _chk(rays_uv, 'rays_uv'); _chk(rays_lt, 'rays_lt'); _chk(lp, 'lp'); _chk(albedo_specular, 'albedo_specular')
+    if albedo_diffuse is not None:
+        _chk(albedo_diffuse, 'albedo_diffuse')
+    N, R, C, H, W = rays_lt.shape
+    # the kernels index rays_uv by (pixel, ray) and the probe by (view, channel): another shape is read out of bounds
+    if tuple(rays_uv.shape) != (N, H, W, 2, R) or lp.dim() != 4 or lp.shape[3] != C or lp.shape[0] not in (1, N):
+        raise RuntimeError('%s: rays_uv %s / lp %s do not match rays_lt %s' % (who, tuple(rays_uv.shape), tuple(lp.shape), tuple(rays_lt.shape)))
+    return N, R, C, H, W
 
 
 @_device_op
@@ -927,10 +935,7 @@ def ray_renderer(rays_uv, rays_lt, lp, albedo_specular, albedo_diffuse=None, num
     """network.RayRenderer.forward on API-shaped tensors -> (out, out_spec, out_diff, ltt_spec, ltt_diff, rays_color).
     want_rays_color=False: rays_color [N,R,C,H,W] is neither allocated nor written (None in its place)."""
     L = _lib.load()
-    _chk(rays_uv, 'rays_uv'); _chk(rays_lt, 'rays_lt'); _chk(lp, 'lp'); _chk(albedo_specular, 'albedo_specular')
-    N, R, C, H, W = rays_lt.shape
-    if albedo_diffuse is not None:
-        _chk(albedo_diffuse, 'albedo_diffuse')
+    N, R, C, H, W = _ray_renderer_args(rays_uv, rays_lt, lp, albedo_specular, albedo_diffuse, 'ray_renderer')
     dev = rays_lt.device
     mk = lambda: torch.empty(N, C, H, W, dtype=torch.float32, device=dev)
     out, o_s, o_d, l_s, l_d = mk(), mk(), mk(), mk(), mk()
@@ -951,21 +956,14 @@ def ray_renderer_backward(rays_uv, rays_lt, lp, albedo_specular, albedo_diffuse=
     of its six outputs, None = zero -> (grad_rays_lt, grad_albedo_specular, grad_albedo_diffuse, grad_lp), None where not
     wanted (or, for the diffuse albedo, not given).  grad_lp is summed with float atomics: last bits vary from run to run."""
     L = _lib.load()
-    _chk(rays_uv, 'rays_uv'); _chk(rays_lt, 'rays_lt'); _chk(lp, 'lp'); _chk(albedo_specular, 'albedo_specular')
-    N, R, C, H, W = rays_lt.shape
-    if albedo_diffuse is not None:
-        _chk(albedo_diffuse, 'albedo_diffuse')
+    N, R, C, H, W = _ray_renderer_args(rays_uv, rays_lt, lp, albedo_specular, albedo_diffuse, 'ray_renderer_backward')
     for g, name in ((g_out, 'g_out'), (g_out_specular, 'g_out_specular'), (g_out_diffuse, 'g_out_diffuse'),
                     (g_ltt_specular, 'g_ltt_specular'), (g_ltt_diffuse, 'g_ltt_diffuse')):
         if g is not None and tuple(_chk(g, name).shape) != (N, C, H, W):
             raise RuntimeError('%s must be %s, got %s' % (name, (N, C, H, W), tuple(g.shape)))
     if g_rays_color is not None and tuple(_chk(g_rays_color, 'g_rays_color').shape) != (N, R, C, H, W):
         raise RuntimeError('g_rays_color must be %s, got %s' % ((N, R, C, H, W), tuple(g_rays_color.shape)))
-    if tuple(rays_uv.shape) != (N, H, W, 2, R) or lp.dim() != 4 or lp.shape[3] != C or lp.shape[0] not in (1, N):
-        raise RuntimeError('ray_renderer_backward: rays_uv %s / lp %s do not match rays_lt %s'
-                           % (tuple(rays_uv.shape), tuple(lp.shape), tuple(rays_lt.shape)))
-    dev = rays_lt.device
-    mk = lambda: torch.empty(N, C, H, W, dtype=torch.float32, device=dev)
+    mk = lambda: torch.empty(N, C, H, W, dtype=torch.float32, device=rays_lt.device)
     g_lt = torch.empty_like(rays_lt) if want_rays_lt else None
     g_as = mk() if want_albedo_specular else None
     g_ad = mk() if (want_albedo_diffuse and albedo_diffuse is not None) else None

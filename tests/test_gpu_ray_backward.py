@@ -173,6 +173,58 @@ def test_ray_renderer_backward_untouched_texels_stay_zero():
     _check_backward(uv, lt, lp, a_s, a_d, nd, False, True, 1.0, g)
 
 
+def test_ray_renderer_argument_errors_launch_nothing():
+    """ops.ray_renderer refuses, before the entry point is called (the message is the shim's own), what would make the forward
+    kernels read out of bounds: N = 2 views of 3 x 5, R = 2, C = 3; rays_uv of R + 1 rays, a probe of C + 1 channels, a probe
+    batch of 3.  The same operands with matching shapes pass."""
+    from rnr_amd import ops
+    N, H, W, R, C = 2, 3, 5, 2, 3
+    z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=DEV)
+    lt, a_s = z(N, R, C, H, W), z(N, C, H, W)
+    assert ops.ray_renderer(z(N, H, W, 2, R), lt, z(1, 4, 8, C), a_s)[0].shape == (N, C, H, W)
+    for uv, lp in ((z(N, H, W, 2, R + 1), z(1, 4, 8, C)), (z(N, H, W, 2, R), z(1, 4, 8, C + 1)), (z(N, H, W, 2, R), z(3, 4, 8, C))):
+        with pytest.raises(RuntimeError, match='ray_renderer: rays_uv .* do not match rays_lt'):
+            ops.ray_renderer(uv, lt, lp, a_s)
+
+
+def test_forward_entry_points_refuse_empty_sizes_and_launch_nothing():
+    """rnr_ray_renderer with num_views = 0 and with lp_h = 0, rnr_texture_mapper with num_views = 0: each returns an error code,
+    names the sizes in rnr_last_error, and leaves the NaN-filled output buffers as they were (no launch); the same calls with
+    the true sizes succeed and write every element."""
+    from rnr_amd import _lib, ops
+    L, P = _lib.load(), ops._ptr
+    N, H, W, R, C = 2, 3, 5, 2, 3
+    rng = np.random.default_rng(5)
+    uv, lt, lp, a_s, a_d = [_dev(T(t)) for t in _renderer_inputs(rng, C, R, N, H, W, 1)]
+    untouched = lambda bufs: all(bool(torch.isnan(t).all()) for t in bufs)
+
+    def render(num_views, lp_h):
+        outs = [_nan(N, C, H, W) for _ in range(5)] + [_nan(N, R, C, H, W)]
+        rc = L.rnr_ray_renderer(P(uv), P(lt), P(lp), 1, lp_h, lp.shape[2], P(a_s), P(a_d), C, R, 1, 0, 1, 1.0, *[P(t) for t in outs],
+                                num_views, H, W, ops._stream())
+        torch.cuda.synchronize()
+        return rc, outs
+    for num_views, lp_h in ((0, lp.shape[1]), (N, 0)):
+        rc, outs = render(num_views, lp_h)
+        assert rc != 0 and untouched(outs) and 'rnr_ray_renderer: bad sizes' in L.rnr_last_error().decode(), (num_views, lp_h)
+    rc, outs = render(N, lp.shape[1])
+    assert rc == 0 and all(bool(torch.isfinite(t).all()) for t in outs)
+
+    tex = [_dev(T(rng.random((s, s, 4)).astype(np.float32))) for s in (8, 4)]
+    ptrs, sizes = ops._level_tables(tex, [8, 4])
+    uv_map = _dev(T(rng.random((N, H, W, 2)).astype(np.float32)))
+
+    def texture(num_views):
+        out = _nan(N, 4, H, W)
+        rc = L.rnr_texture_mapper(P(uv_map), P(None), ptrs, sizes, 2, 4, 0, P(out), num_views, H, W, ops._stream())
+        torch.cuda.synchronize()
+        return rc, out
+    rc, out = texture(0)
+    assert rc != 0 and untouched([out]) and 'rnr_texture_mapper: bad sizes' in L.rnr_last_error().decode()
+    rc, out = texture(N)
+    assert rc == 0 and bool(torch.isfinite(out).all())
+
+
 # ------------------------------------------------------------------------------------------------
 # 2. contention
 # ------------------------------------------------------------------------------------------------
