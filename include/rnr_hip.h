@@ -731,6 +731,71 @@ int rnr_masked_l1_loss(const float* est, const float* gt, const float* alpha, in
 int rnr_masked_l1_loss_backward(const float* est, const float* gt, const float* alpha, int border, const float* g_loss,
                                 float* grad_est, int num_views, int channels, int height, int width, void* stream);
 
+/*
+ * Adam step (csrc/optim.hip): torch.optim.Adam (train_rnr.py:376; no amsgrad, no maximize, L2 weight_decay in torch's default,
+ * coupled form) for every tensor of a step in ONE launch, adam_multi_kernel, 256 threads per workgroup.  Workgroup b handles
+ * chunk chunks[b]: elements [chunk * RNR_ADAM_CHUNK, min(n, (chunk + 1) * RNR_ADAM_CHUNK)) of tensors[chunks[b].tensor].  Per
+ * element, in float32, every operation rounded once and none contracted, sqrt and / correctly rounded:
+ *     g  = grad                      (+ wd * p            when wd != 0)
+ *     m  = b1 * m + omb1 * g         (omb1 = float32(1 - b1), the subtraction made in double)
+ *     v  = b2 * v + (omb2 * g) * g   (omb2 = float32(1 - b2))
+ *     d  = sqrt(v) / bc2s + eps
+ *     p  = p - step_size * (m / d)
+ *   with step_size = float32(lr / (1 - b1^t)) and bc2s = float32(sqrt(1 - b2^t)) formed by the caller in double for the step
+ *   count t the tensor has AFTER this step.  torch keeps t per parameter and lr, betas, eps, weight_decay per group, so b1 .. wd
+ *   stand in the tensor's table entry, and (step_size, bc2s), which change every step, come from scalars[tensor.slot]: a HOST
+ *   array of num_scalars <= RNR_ADAM_MAX_SLOTS entries that travels by value in the kernel arguments.  The call therefore
+ *   neither synchronises nor copies on the stream; `tensors` and `chunks` are DEVICE arrays the caller builds once per
+ *   parameter set and keeps alive until the launch has run.  Two calls on the same inputs give the same bits.
+ *   p, g, m, v need 4-byte alignment only: a chunk whose four streams are 16-byte aligned moves float4s, any other chunk one
+ *   element per thread (a parameter may be a view at an odd storage offset).  A tensor with n == 0 has no chunk; n < 2^31.
+ * Mirrors: the new p is also stored through the tensor's num_mirrors <= 3 descriptors, each a strided scatter.  `shape` is the
+ *   parameter as a 4-D array (leading dimensions 1); element (i0, i1, i2, i3) goes, when lo <= i_dim < hi, to
+ *     dst[i0 stride[0] + i1 stride[1] + i2 stride[2] + i3 stride[3] + q repeat_stride]     for q = 0 .. repeat - 1
+ *   Strides are in elements and may be negative; dst is the address index (0, 0, 0, 0) maps to, which lies outside the
+ *   destination buffer when the range starts above 0 or a stride is negative.  These express what a U-Net training plan builds
+ *   from its weights (rnr_conv_backward_desc): the identity copy of the forward staging, w[:, off:off+c].flip(2, 3).transpose(0, 1)
+ *   of a 3x3 gradient convolution, the channel slices of the two 4x4 kinds, the padded BatchNorm / bias vectors and every row
+ *   (repeat) of a consumer's shift.  A mirror with the parameter's own contiguous strides and its range on dimension 0 is stored
+ *   as float4s where the chunk is.  The kernel cannot check a descriptor: the caller guarantees that every address it produces
+ *   lies in a live buffer, and that no two descriptors of a launch write one address.
+ * Errors (negative counts, num_scalars outside 1 .. RNR_ADAM_MAX_SLOTS, NULL tables with chunks to run) are reported before the
+ * launch; num_chunks == 0 launches nothing.
+ */
+#define RNR_ADAM_CHUNK 4096
+#define RNR_ADAM_MAX_SLOTS 64
+typedef struct rnr_adam_mirror {
+    float* dst;
+    int64_t stride[4];
+    int64_t repeat_stride;
+    int dim, lo, hi, repeat;
+} rnr_adam_mirror;
+typedef struct rnr_adam_tensor {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    int64_t n;
+    float b1, omb1, b2, omb2, eps, wd;
+    int slot, num_mirrors;
+    int shape[4];
+    int reserved[2];            /* 0 */
+    rnr_adam_mirror mirror[3];
+} rnr_adam_tensor;
+typedef struct rnr_adam_chunk {
+    int tensor, chunk;
+} rnr_adam_chunk;
+typedef struct rnr_adam_scalars {
+    float step_size, bc2s;
+} rnr_adam_scalars;
+int rnr_adam_step(const rnr_adam_tensor* tensors, int num_tensors, const rnr_adam_chunk* chunks, int num_chunks,
+                  const rnr_adam_scalars* scalars, int num_scalars, void* stream);
+
+/* rnr_pack_conv_weight for descs[i], weights[i], packed[i], i = 0 .. count - 1, in that order on `stream`: the same kernels and
+ * the same bytes, one call for a whole network (what follows rnr_adam_step in a training step).  Stops at the first error. */
+int rnr_pack_conv_weights(const rnr_conv_desc* descs, const float* const* weights, float* const* packed, int count,
+                          void* stream);
+
 /* ---- spherical harmonics (sph_harm.py:41-102) ---- */
 
 /* Real orthonormal SH without Condon-Shortley phase, columns (l, m=-l..l); dirs [n,3] (need not be unit),

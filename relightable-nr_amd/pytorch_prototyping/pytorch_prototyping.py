@@ -241,6 +241,16 @@ class Unet(nn.Module):
         self._plan_versions[key] = ver
         return plan
 
+    def _mark_plan_current(self, plan):
+        """Record that `plan` (one of self._plans) holds the weights as they are now: what rnr_amd.optim.Adam calls after it
+        stored the stepped parameters into the plan's staging and packed them, so that `_train_plan` neither rebuilds nor
+        repacks.  The caller vouches for the plan's contents."""
+        for key, p in self._plans.items():
+            if p is plan:
+                self._plan_versions[key] = self._weights_version()
+                return
+        raise ValueError('not a plan of this network')
+
     def _forward_train(self, x, apply_tanh):
         from rnr_amd.autograd import UNetFn
         n, _, h, w = x.shape

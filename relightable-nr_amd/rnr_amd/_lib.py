@@ -49,6 +49,28 @@ class RnrConvBn(ctypes.Structure):
                 ('running_mean', c_void_p), ('running_var', c_void_p), ('momentum', c_float)]      # NULL / 0: no running-statistics update
 
 
+class RnrAdamMirror(ctypes.Structure):
+    _fields_ = [('dst', c_void_p), ('stride', ctypes.c_int64 * 4), ('repeat_stride', ctypes.c_int64), ('dim', c_int), ('lo', c_int),
+                ('hi', c_int), ('repeat', c_int)]
+
+
+class RnrAdamTensor(ctypes.Structure):
+    _fields_ = [('p', c_void_p), ('g', c_void_p), ('m', c_void_p), ('v', c_void_p), ('n', ctypes.c_int64), ('b1', c_float),
+                ('omb1', c_float), ('b2', c_float), ('omb2', c_float), ('eps', c_float), ('wd', c_float), ('slot', c_int),
+                ('num_mirrors', c_int), ('shape', c_int * 4), ('reserved', c_int * 2), ('mirror', RnrAdamMirror * 3)]
+
+
+class RnrAdamChunk(ctypes.Structure):
+    _fields_ = [('tensor', c_int), ('chunk', c_int)]
+
+
+class RnrAdamScalars(ctypes.Structure):
+    _fields_ = [('step_size', c_float), ('bc2s', c_float)]
+
+
+ADAM_CHUNK = 4096        # RNR_ADAM_CHUNK: elements per workgroup of rnr_adam_step
+ADAM_MAX_SLOTS = 64      # RNR_ADAM_MAX_SLOTS: distinct (step_size, bc2s) pairs per launch
+ADAM_MAX_MIRRORS = 3
 ACT_NONE, ACT_LRELU02, ACT_RELU = 0, 1, 2
 CONV_STATS_PREZEROED = 1
 CONV_F32_EMU_BF16X6 = 2
@@ -153,6 +175,9 @@ SIGNATURES = {
     'rnr_masked_l1_loss_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'rnr_masked_l1_loss': (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'rnr_masked_l1_loss_backward': (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    # optimiser (csrc/optim.hip)
+    'rnr_adam_step': (c_int, [c_void_p, c_int, c_void_p, c_int, P(RnrAdamScalars), c_int, c_void_p]),
+    'rnr_pack_conv_weights': (c_int, [P(RnrConvDesc), P(c_void_p), P(c_void_p), c_int, c_void_p]),
     'rnr_tbn_map': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     'rnr_tbn_matvec': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_long, c_int, c_void_p]),
     'rnr_ray_sampler': (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

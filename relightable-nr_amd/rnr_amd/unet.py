@@ -42,6 +42,57 @@ def _running_affine(gamma, beta, running_mean, running_var):
     return sc, beta - running_mean * sc
 
 
+def _backward_weight(kind, w, off, c):
+    """The weight of the gradient convolution for the source at input channels [off, off + c) of forward weight `w` (include/
+    rnr_hip.h, rnr_conv_backward_desc): flipped and transposed for the 3x3 kind, the same tensor read the other way for the two 4x4
+    kinds.  A view; `backward_mirrors` states the same maps as strides."""
+    if kind == CONV3x3_REFLECT:
+        return w[:, off:off + c].flip(2, 3).transpose(0, 1)
+    if kind == CONV4x4S2_REFLECT:
+        return w[:, off:off + c]
+    return w[off:off + c]
+
+
+def _contiguous_strides(shape):
+    st, acc = [], 1
+    for d in reversed(shape):
+        st.append(acc)
+        acc *= int(d)
+    return tuple(reversed(st))
+
+
+def identity_mirror(shape, repeat=1, repeat_stride=0):
+    """Mirror descriptor (include/rnr_hip.h, "Adam step") that copies a parameter of `shape` (at most four dimensions) to the
+    front of a buffer, `repeat` times at `repeat_stride` elements."""
+    shape4 = (1,) * (4 - len(shape)) + tuple(int(d) for d in shape)
+    return {'shape': shape4, 'dst_shape': shape4, 'base': 0, 'stride': _contiguous_strides(shape4), 'dim': 0, 'lo': 0, 'hi': shape4[0],
+            'repeat': int(repeat), 'repeat_stride': int(repeat_stride)}
+
+
+def backward_mirrors(kind, w_shape, src_channels):
+    """Mirror descriptors that scatter a forward weight of `w_shape` into the contiguous gradient-convolution weights of its
+    sources (`_backward_weight(...).contiguous()`), one per source of src_channels[i] input channels: element (i0, i1, i2, i3)
+    of the weight ('shape')
+    with lo <= i_dim < hi goes to element base + sum i_k stride[k] of a buffer of 'dst_shape'.  Pure host code."""
+    d0, d1, d2, d3 = (int(d) for d in w_shape)
+    res, off = [], 0
+    for c in src_channels:
+        c = int(c)
+        if kind == CONV3x3_REFLECT:         # dst[i1 - off, i0, 2 - i2, 2 - i3] of [c, c_out, 3, 3]
+            m = {'dst_shape': (c, d0, d2, d3), 'stride': (d2 * d3, d0 * d2 * d3, -d3, -1), 'dim': 1,
+                 'base': -off * d0 * d2 * d3 + (d2 - 1) * d3 + (d3 - 1)}
+        elif kind == CONV4x4S2_REFLECT:     # dst[i0, i1 - off, i2, i3] of [c_out, c, 4, 4]
+            m = {'dst_shape': (d0, c, d2, d3), 'stride': (c * d2 * d3, d2 * d3, d3, 1), 'dim': 1, 'base': -off * d2 * d3}
+        else:                               # dst[i0 - off, i1, i2, i3] of [c, c_out, 4, 4]
+            m = {'dst_shape': (c, d1, d2, d3), 'stride': (d1 * d2 * d3, d2 * d3, d3, 1), 'dim': 0, 'base': -off * d1 * d2 * d3}
+        m.update(shape=(d0, d1, d2, d3), lo=off, hi=off + c, repeat=1, repeat_stride=0)
+        if off == 0 and c == (d0, d1)[m['dim']]:      # one source takes every element: said on dimension 0, where a contiguous
+            m.update(dim=0, lo=0, hi=d0)              # descriptor qualifies for the kernel's float4 stores
+        res.append(m)
+        off += c
+    return res
+
+
 def _max_over_views(max_views, query):
     """Largest query(n_views) over 1 .. max_views: a plan, hence its scratch, depends on the views actually passed per call."""
     return max(query(n) for n in range(1, max_views + 1))
@@ -328,12 +379,12 @@ class UNetPlan:
             for s in self.steps:
                 d, w, off = s['desc'], s['w'], 0
                 for b, a in zip(s['bwd'], s['srcs']):
-                    if d.kind == CONV3x3_REFLECT:
-                        wb = w[:, off:off + a.c].flip(2, 3).transpose(0, 1).contiguous()
-                    elif d.kind == CONV4x4S2_REFLECT:
-                        wb = w[:, off:off + a.c].contiguous()
+                    wb = _backward_weight(d.kind, w, off, a.c)
+                    if 'w' in b:        # the persistent staging of `_ensure_staging`: kept current, and packed from
+                        b['w'].copy_(wb)
+                        wb = b['w']
                     else:
-                        wb = w[off:off + a.c].contiguous()
+                        wb = wb.contiguous()
                     check(self.L.rnr_pack_conv_weight(ctypes.byref(b['desc']), _ptr(wb), _ptr(b['packed']), _stream()))
                     off += a.c
                 if s['bn'] is not None and self.bn_mode == 'running':
@@ -374,6 +425,71 @@ class UNetPlan:
                 self.out_bias[:self.out_channels] = g('out_layer.0.net.1.bias')
         if self.training:
             self._pack_backward()
+
+    # ---- what rnr_amd.optim.Adam.bind keeps current instead of `repack` (include/rnr_hip.h, "Adam step") ----
+    def _ensure_staging(self):
+        """The gradient convolutions' weights as persistent buffers next to s['w'] (`_pack_backward` forms them as temporaries),
+        filled from s['w'] here and by every later `_pack_backward` (so a `repack` leaves them current too); the argument arrays of
+        the batched pack."""
+        if not self.training:
+            raise RuntimeError('UNetPlan.staging_table / pack_staged need a plan built with training=True')
+        if getattr(self, '_pack_args', None) is not None:
+            return
+        jobs = []
+        with on_device(self.dev):
+            for s in self.steps:
+                jobs.append((s['desc'], s['w'], s['packed']))
+                off = 0
+                for b, a in zip(s['bwd'], s['srcs']):
+                    b['w'] = _backward_weight(s['desc'].kind, s['w'], off, a.c).contiguous()
+                    if b['w'].data_ptr() == s['w'].data_ptr():      # one source: contiguous() returned the forward staging itself
+                        b['w'] = b['w'].clone()
+                    jobs.append((b['desc'], b['w'], b['packed']))
+                    off += a.c
+        n = len(jobs)
+        self._pack_args = ((RnrConvDesc * n)(*[j[0] for j in jobs]), (ctypes.c_void_p * n)(*[j[1].data_ptr() for j in jobs]),
+                           (ctypes.c_void_p * n)(*[j[2].data_ptr() for j in jobs]), n)
+
+    def staging_table(self):
+        """{state-dict key: [mirror descriptors]} of a training plan: where the new value of every live parameter has to be
+        stored for `pack_staged` (and the forward's BatchNorm / bias reads) to see it — `identity_mirror` / `backward_mirrors`
+        dictionaries with 'dst', the destination tensor, added.  In 'running' mode BatchNorm's bias has no staged copy (the
+        forward reads the folded scale / shift, which `pack_staged` recomputes)."""
+        self._ensure_staging()
+        pre, table = self._prefix, {}
+        vec = lambda dst, n, **k: dict(identity_mirror((n,), **k), dst=dst)
+        for s in self.steps:
+            wkey, bn_key, bias_key = s['keys']
+            out, shape = s['out'], tuple(s['w'].shape)
+            table[pre + wkey] = [dict(identity_mirror(shape), dst=s['w'])] + \
+                [dict(m, dst=b['w']) for m, b in zip(backward_mirrors(s['desc'].kind, shape, [a.c for a in s['srcs']]), s['bwd'])]
+            if bn_key is not None:
+                table[pre + bn_key + '.weight'] = [vec(s['bn']['gamma'], out.c)]
+                table[pre + bn_key + '.bias'] = [] if self.bn_mode == 'running' else [vec(s['bn']['beta'], out.c)]
+            elif bias_key is not None:
+                table[pre + bias_key] = [vec(s['bias'], out.c),
+                                         vec(out.shift, out.c, repeat=out.shift.shape[0], repeat_stride=out.shift.shape[1])]
+        if (pre + 'out_layer.0.net.1.bias') in self.grads:
+            table[pre + 'out_layer.0.net.1.bias'] = [vec(self.out_bias, self.out_channels)]
+        return table
+
+    def pack_staged(self, state_dict=None):
+        """Pack every forward and gradient-convolution weight from the staging buffers: one rnr_pack_conv_weights call, the bytes
+        `repack` produces once the staging holds the state-dict's values.  'running' mode folds BatchNorm into the consumers'
+        scale / shift from two parameters each: `state_dict` (the keys `repack` takes) is needed there and refolded as `repack` does."""
+        self._ensure_staging()
+        descs, weights, packed, n = self._pack_args
+        with on_device(self.dev):
+            check(self.L.rnr_pack_conv_weights(descs, weights, packed, n, _stream()))
+            if self.bn_mode == 'running':
+                if state_dict is None:
+                    raise ValueError("UNetPlan.pack_staged: bn_mode 'running' needs the state dict to fold BatchNorm from")
+                g = lambda k: _fetch(state_dict, self._prefix + k, self.dev)
+                for s in self.steps:
+                    bn_key, out = s['keys'][1], s['out']
+                    if bn_key is not None:
+                        out.scale[:, :out.c], out.shift[:, :out.c] = _running_affine(
+                            g(bn_key + '.weight'), g(bn_key + '.bias'), *s['_running'])
 
     def backward(self, grad_raw, want_input_grad=True):
         """The adjoint of the last `forward` (same number of views; its activations are still in the plan): grad_raw
