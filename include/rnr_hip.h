@@ -732,6 +732,63 @@ int rnr_masked_l1_loss_backward(const float* est, const float* gt, const float* 
                                 float* grad_est, int num_views, int channels, int height, int width, void* stream);
 
 /*
+ * The stitched light probe (stitch_lp.py) and what train_rnr.py:288-295 does to it before use (csrc/stitch.hip): the scatter
+ * direction of rnr_env_background's geometry.  Nothing syncs with the host, there are no float atomics, every sum has a fixed
+ * order: two runs on the same inputs give the same bits.
+ *
+ * rnr_background_mask (in place of stitch_lp.py:135-140): alpha [N,H,W] float32, 0 <= radius <= 32 -> background [N,H,W] uint8,
+ *   background = 1 iff no pixel with alpha > 0 lies within Chebyshev distance radius inside the image (a NaN alpha counts as
+ *   not covered, as in rnr_present_u8): the complement of a (2 radius + 1)^2 dilation of the rasterizer's coverage.  One 32 x 32
+ *   tile and its halo per workgroup in LDS, row maximum, then column maximum.  Floor: 5 N H W bytes (4 read, 1 written).
+ *   UNPINNED against OpenCV: the reference fills the projected triangles with cv2.fillPoly on integer-truncated vertices,
+ *   resizes to 512 x 512 bilinearly, dilates 17 x 17 and resizes back; cv2 is not available here.  The two masks differ in a thin
+ *   band along the dilated silhouette.  radius = ceil(8 max(H, W) / 512) is that window at the image's own resolution.
+ *
+ * rnr_stitch_accumulate (stitch_lp.py:142-150): images [N,3,H,W] float32, or [N,H,W,3] with channels_last != 0;
+ *   background [N,H,W] uint8 (non-zero = stitch this pixel); proj_inv, R_inv [N,3,3] FLOAT64 (K^-1 and R^-1 as the reference
+ *   forms them); state sum [lp_h,lp_w,3] float64 and count [lp_h,lp_w] int32, zero before the first call;
+ *   workspace: rnr_stitch_workspace_bytes(N, lp_h, lp_w) = 4 N lp_h lp_w bytes, 4-byte aligned, ALL ZERO before the first call;
+ *   every call leaves it all zero again.  workspace_bytes is what the caller allocated: less than needed is an error.
+ *   For every background pixel (x, y) of view n, in float64:
+ *     d = normalize(R_inv[n] (proj_inv[n] (x + 0.5, y + 0.5, 1)))         = -view_dir of rnr_view_dir_map
+ *     u = atan2(d.z, d.x) * 0.5 / pi + 0.5;   v = acos(d.y) / pi
+ *     row = rint(min(v lp_h, lp_h - 1));   col = rint(min(u lp_w, lp_w - 1))          (half to even, as np.round)
+ *   numpy's fancy-index `+=` does not accumulate over repeated indices, so per view a texel takes the value of the pixel with
+ *   the HIGHEST row-major index that maps to it, sum[row, col] += (double)that pixel's three floats, count[row, col] += 1;
+ *   views add up in view order, within a call and across successive calls, so any split of the views over calls gives the same
+ *   bits.  Pass 1 (per pixel) finds the winners with an integer atomicMax of pixel index + 1 into workspace[n][texel]; pass 2
+ *   (per texel) walks the call's views in order, adds, counts and clears the winners.  The products are not contracted to FMAs;
+ *   a texel index agrees with the reference's wherever u lp_w and v lp_h are farther from a rounding tie than the float64
+ *   error of atan2 / acos (~1e-16 lp_w).  A pixel whose direction is not finite (singular matrices) is skipped (the reference
+ *   raises an index error there).  Limits: lp_h lp_w < 2^31 / 3, H W < 2^32 - 1.
+ *
+ * rnr_stitch_finalize (stitch_lp.py:152-153, 157): mask [lp_h,lp_w] uint8 = count > 0; lp [lp_h,lp_w,3] float32 =
+ *   (float)(sum / count) where the mask is set and 0 elsewhere.  The state is not written: more views can follow.
+ *
+ * rnr_probe_prepare (train_rnr.py:288-295): lp [lp_h,lp_w,3] float32, mask [lp_h,lp_w] uint8 -> out [lp_h,lp_w,3] (may be lp):
+ *     x = NaN -> 0;   x = (float)pow((double)x, gamma)  (one rounding; gamma == 1 leaves the bits alone);
+ *     per channel, every texel with mask == 0 gets (float)(mean of x over the texels with mask != 0)
+ *   The mean is a float64 sum in a fixed order (one partial record per workgroup, then one workgroup).  An empty mask gives NaN
+ *   in every texel, as the reference's mean of nothing does; no error is raised (that would need a host sync).  A negative
+ *   value under a fractional gamma is NaN as in numpy.  The reference swaps cv2's B,G,R to R,G,B first; here the channels keep
+ *   the order of the images that were stitched.  workspace: rnr_probe_prepare_workspace_bytes(lp_h, lp_w) bytes, 8-byte
+ *   aligned; every word that is read is written earlier in the same call.
+ *
+ * Errors (a NULL pointer, sizes <= 0, radius outside 0..32, a limit above, a workspace too small, misalignment) are reported
+ * before any launch.
+ */
+#define RNR_BACKGROUND_MASK_MAX_RADIUS 32
+int rnr_background_mask(const float* alpha, int radius, uint8_t* background, int num_views, int height, int width, void* stream);
+size_t rnr_stitch_workspace_bytes(int num_views, int lp_h, int lp_w);
+int rnr_stitch_accumulate(const float* images, int channels_last, const uint8_t* background, const double* proj_inv,
+                          const double* R_inv, double* sum, int32_t* count, void* workspace, size_t workspace_bytes,
+                          int num_views, int height, int width, int lp_h, int lp_w, void* stream);
+int rnr_stitch_finalize(const double* sum, const int32_t* count, float* lp, uint8_t* mask, int lp_h, int lp_w, void* stream);
+size_t rnr_probe_prepare_workspace_bytes(int lp_h, int lp_w);
+int rnr_probe_prepare(const float* lp, const uint8_t* mask, double gamma, float* out, void* workspace, int lp_h, int lp_w,
+                      void* stream);
+
+/*
  * Adam step (csrc/optim.hip): torch.optim.Adam (train_rnr.py:376; no amsgrad, no maximize, L2 weight_decay in torch's default,
  * coupled form) for every tensor of a step in ONE launch, adam_multi_kernel, 256 threads per workgroup.  Workgroup b handles
  * chunk chunks[b]: elements [chunk * RNR_ADAM_CHUNK, min(n, (chunk + 1) * RNR_ADAM_CHUNK)) of tensors[chunks[b].tensor].  Per

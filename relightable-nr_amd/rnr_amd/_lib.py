@@ -85,6 +85,7 @@ CONV3x3_REFLECT, CONV4x4S2_REFLECT, CONVT4x4S2 = 0, 1, 2
 BN_BWD_MODES = {'batch': 0, 'batch_all': 1, 'running': 2}         # RNR_BN_BWD_*
 PRESENT_MODES = {'frame': 0, 'composite': 1, 'background': 2}     # RNR_PRESENT_*
 PRESENT_RGB = 8
+BACKGROUND_MASK_MAX_RADIUS = 32                                   # RNR_BACKGROUND_MASK_MAX_RADIUS
 METRIC_PLANAR, METRIC_CHANNELS_LAST = 0, 1                        # RNR_METRIC_* layouts
 # RNR_METRIC_* outputs, in the order of rnr_image_metrics' out columns
 METRIC_KEYS = ('mae', 'mae_bb', 'mae_valid', 'mse', 'mse_bb', 'mse_valid', 'psnr', 'psnr_bb', 'psnr_valid', 'ssim', 'ssim_bb',
@@ -175,6 +176,13 @@ SIGNATURES = {
     'rnr_masked_l1_loss_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'rnr_masked_l1_loss': (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'rnr_masked_l1_loss_backward': (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    # stitched light probe (csrc/stitch.hip)
+    'rnr_background_mask': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'rnr_stitch_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'rnr_stitch_accumulate': (c_int, [c_void_p, c_int] + [c_void_p] * 6 + [c_size_t, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    'rnr_stitch_finalize': (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p]),
+    'rnr_probe_prepare_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'rnr_probe_prepare': (c_int, [c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     # optimiser (csrc/optim.hip)
     'rnr_adam_step': (c_int, [c_void_p, c_int, c_void_p, c_int, P(RnrAdamScalars), c_int, c_void_p]),
     'rnr_pack_conv_weights': (c_int, [P(RnrConvDesc), P(c_void_p), P(c_void_p), c_int, c_void_p]),

@@ -974,3 +974,144 @@ def ray_renderer_backward(rays_uv, rays_lt, lp, albedo_specular, albedo_diffuse=
                                       _ptr(g_out_specular), _ptr(g_out_diffuse), _ptr(g_ltt_specular), _ptr(g_ltt_diffuse),
                                       _ptr(g_rays_color), _ptr(g_lt), _ptr(g_as), _ptr(g_ad), _ptr(g_lp), N, H, W, _stream()))
     return g_lt, g_as, g_ad, g_lp
+
+
+# ---------------------------------------------------------------------------------------------------
+# stitched light probe (csrc/stitch.hip)
+# ---------------------------------------------------------------------------------------------------
+def _typed(t, name, who, dtypes, dims):
+    """dtype and rank of an argument, before anything touches a device: ValueError naming the argument."""
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError('%s: %s must be a torch.Tensor' % (who, name))
+    dtypes = dtypes if isinstance(dtypes, tuple) else (dtypes,)
+    if t.dtype not in dtypes:
+        raise ValueError('%s: %s must be %s, got %s' % (who, name, ' or '.join(str(d) for d in dtypes), t.dtype))
+    if t.dim() != dims:
+        raise ValueError('%s: %s must have %d dimensions, got %s' % (who, name, dims, tuple(t.shape)))
+    return t
+
+
+def _shaped(t, name, who, shape):
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError('%s: %s must be %s, got %s' % (who, name, list(shape), tuple(t.shape)))
+    return t
+
+
+def _probe_size(lp_h, lp_w, who):
+    if lp_h <= 0 or lp_w <= 0 or lp_h * lp_w * 3 >= 2 ** 31:
+        raise ValueError('%s: a probe of %d x %d: sizes must be positive and lp_h*lp_w below 2^31/3' % (who, lp_h, lp_w))
+
+
+@_device_op
+def background_mask(alpha, radius, out=None):
+    """rnr_background_mask: alpha [N,H,W] float32 -> [N,H,W] uint8, 1 where no pixel with alpha > 0 lies within Chebyshev
+    distance `radius` (0..32) inside the image: the complement of the rasterizer's coverage dilated by (2 radius + 1)^2, in place of
+    stitch_lp.py:135-140's OpenCV mask (unpinned against it; include/rnr_hip.h).  A NaN alpha counts as not covered."""
+    radius = int(radius)
+    if radius < 0 or radius > _lib.BACKGROUND_MASK_MAX_RADIUS:
+        raise ValueError('background_mask: radius must be in 0..%d, got %d' % (_lib.BACKGROUND_MASK_MAX_RADIUS, radius))
+    _typed(alpha, 'alpha', 'background_mask', torch.float32, 3)
+    if min(alpha.shape) <= 0:
+        raise ValueError('background_mask: alpha %s: sizes must be positive' % (tuple(alpha.shape),))
+    if out is not None:
+        _shaped(_typed(out, 'out', 'background_mask', torch.uint8, 3), 'out', 'background_mask', alpha.shape)
+    _chk(alpha, 'alpha')
+    L = _lib.load()
+    N, H, W = alpha.shape
+    if out is None:
+        out = torch.empty(N, H, W, dtype=torch.uint8, device=alpha.device)
+    else:
+        _chk(out, 'out', torch.uint8)
+    check(L.rnr_background_mask(_ptr(alpha), radius, _ptr(out), N, H, W, _stream()))
+    return out
+
+
+def stitch_workspace_bytes(num_views, lp_h, lp_w):
+    """rnr_stitch_workspace_bytes: 4 * num_views * lp_h * lp_w, the winner table of one stitch_accumulate call."""
+    return int(_lib.load().rnr_stitch_workspace_bytes(int(num_views), int(lp_h), int(lp_w)))
+
+
+@_device_op
+def stitch_accumulate(images, background, proj_inv, R_inv, sum, count, workspace, channels_last=False):
+    """rnr_stitch_accumulate (stitch_lp.py:142-150): the background pixels of images [N,3,H,W] float32 (or [N,H,W,3] with
+    channels_last) scattered into the state sum [lp_h,lp_w,3] float64 / count [lp_h,lp_w] int32, in place.  background [N,H,W]
+    uint8; proj_inv / R_inv [N,3,3] float64 (float32 is promoted exactly).  Per view a texel takes its LAST pixel in row-major
+    order (numpy's fancy-index +=) and views add up in order, within and across calls: the same bits on every run.
+    workspace: an all-zero device buffer of at least stitch_workspace_bytes(N, lp_h, lp_w) bytes (any integer dtype whose
+    storage is 4-byte aligned); it is all zero again afterwards.  The state starts at zero."""
+    who = 'stitch_accumulate'
+    _typed(images, 'images', who, torch.float32, 4)
+    N = images.shape[0]
+    H, W, C = (images.shape[1], images.shape[2], images.shape[3]) if channels_last else (images.shape[2], images.shape[3], images.shape[1])
+    if C != 3 or min(N, H, W) <= 0 or H * W >= 2 ** 32 - 1:
+        raise ValueError('%s: images must be %s with positive sizes and H*W below 2^32-1, got %s'
+                         % (who, '[N,H,W,3]' if channels_last else '[N,3,H,W]', tuple(images.shape)))
+    _shaped(_typed(background, 'background', who, torch.uint8, 3), 'background', who, (N, H, W))
+    _shaped(_typed(proj_inv, 'proj_inv', who, (torch.float64, torch.float32), 3), 'proj_inv', who, (N, 3, 3))
+    _shaped(_typed(R_inv, 'R_inv', who, (torch.float64, torch.float32), 3), 'R_inv', who, (N, 3, 3))
+    _typed(sum, 'sum', who, torch.float64, 3)
+    lp_h, lp_w = int(sum.shape[0]), int(sum.shape[1])
+    _shaped(sum, 'sum', who, (lp_h, lp_w, 3))
+    _probe_size(lp_h, lp_w, who)
+    _shaped(_typed(count, 'count', who, torch.int32, 2), 'count', who, (lp_h, lp_w))
+    if not isinstance(workspace, torch.Tensor) or workspace.dtype.is_floating_point:
+        raise ValueError('%s: workspace must be an integer tensor' % who)
+    _chk(images, 'images'); _chk(background, 'background', torch.uint8); _chk(sum, 'sum', torch.float64)
+    _chk(count, 'count', torch.int32); _chk(workspace, 'workspace', workspace.dtype)
+    proj_inv = _chk(proj_inv.double().contiguous(), 'proj_inv', torch.float64)
+    R_inv = _chk(R_inv.double().contiguous(), 'R_inv', torch.float64)
+    L = _lib.load()
+    check(L.rnr_stitch_accumulate(_ptr(images), 1 if channels_last else 0, _ptr(background), _ptr(proj_inv), _ptr(R_inv), _ptr(sum),
+                                  _ptr(count), _ptr(workspace), workspace.numel() * workspace.element_size(), N, H, W, lp_h, lp_w,
+                                  _stream()))
+
+
+@_device_op
+def stitch_finalize(sum, count, lp=None, mask=None):
+    """rnr_stitch_finalize (stitch_lp.py:152-153): the state -> (lp [lp_h,lp_w,3] float32 = float32(sum / count) where count > 0
+    and 0 elsewhere, mask [lp_h,lp_w] uint8 = count > 0).  The state is not written."""
+    who = 'stitch_finalize'
+    _typed(sum, 'sum', who, torch.float64, 3)
+    lp_h, lp_w = int(sum.shape[0]), int(sum.shape[1])
+    _shaped(sum, 'sum', who, (lp_h, lp_w, 3))
+    _probe_size(lp_h, lp_w, who)
+    _shaped(_typed(count, 'count', who, torch.int32, 2), 'count', who, (lp_h, lp_w))
+    if lp is not None:
+        _shaped(_typed(lp, 'lp', who, torch.float32, 3), 'lp', who, (lp_h, lp_w, 3))
+    if mask is not None:
+        _shaped(_typed(mask, 'mask', who, torch.uint8, 2), 'mask', who, (lp_h, lp_w))
+    _chk(sum, 'sum', torch.float64); _chk(count, 'count', torch.int32)
+    L = _lib.load()
+    lp = torch.empty(lp_h, lp_w, 3, dtype=torch.float32, device=sum.device) if lp is None else _chk(lp, 'lp')
+    mask = torch.empty(lp_h, lp_w, dtype=torch.uint8, device=sum.device) if mask is None else _chk(mask, 'mask', torch.uint8)
+    check(L.rnr_stitch_finalize(_ptr(sum), _ptr(count), _ptr(lp), _ptr(mask), lp_h, lp_w, _stream()))
+    return lp, mask
+
+
+@_device_op
+def probe_prepare(lp, mask, gamma=1.0, out=None, workspace=None):
+    """rnr_probe_prepare (train_rnr.py:288-295): lp [lp_h,lp_w,3] float32, mask [lp_h,lp_w] uint8 (or bool) -> [lp_h,lp_w,3]:
+    NaN -> 0, then x ** gamma (a float64 pow rounded once; gamma == 1 leaves the bits alone), then per channel every texel
+    outside the mask gets the mean over the texels inside it (float64 sum in a fixed order).  An empty mask gives NaN
+    everywhere, as the reference's mean of nothing; nothing is raised, since that would need a host sync.  out may be lp.
+    workspace: a device buffer of rnr_probe_prepare_workspace_bytes(lp_h, lp_w) bytes, 8-byte aligned (default: cached per
+    device and size — calls of one size on different streams of a device must not overlap)."""
+    who = 'probe_prepare'
+    _typed(lp, 'lp', who, torch.float32, 3)
+    lp_h, lp_w = int(lp.shape[0]), int(lp.shape[1])
+    _shaped(lp, 'lp', who, (lp_h, lp_w, 3))
+    _probe_size(lp_h, lp_w, who)
+    _shaped(_typed(mask, 'mask', who, (torch.uint8, torch.bool), 2), 'mask', who, (lp_h, lp_w))
+    if out is not None:
+        _shaped(_typed(out, 'out', who, torch.float32, 3), 'out', who, (lp_h, lp_w, 3))
+    _chk(lp, 'lp'); _chk(mask, 'mask', mask.dtype)
+    L = _lib.load()
+    mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    out = torch.empty_like(lp) if out is None else _chk(out, 'out')
+    need = L.rnr_probe_prepare_workspace_bytes(lp_h, lp_w)
+    if workspace is None:
+        workspace = _loss_workspace('probe_prepare', lp.device, need, lp_h, lp_w)
+    elif _chk(workspace, 'workspace', workspace.dtype).numel() * workspace.element_size() < need:
+        raise ValueError('%s: workspace of %d bytes, %d needed' % (who, workspace.numel() * workspace.element_size(), need))
+    check(L.rnr_probe_prepare(_ptr(lp), _ptr(mask), float(gamma), _ptr(out), _ptr(workspace), lp_h, lp_w, _stream()))
+    return out
