@@ -821,6 +821,7 @@ int rnr_probe_prepare(const float* lp, const uint8_t* mask, double gamma, float*
  */
 #define RNR_ADAM_CHUNK 4096
 #define RNR_ADAM_MAX_SLOTS 64
+#define RNR_ADAM_MAX_MIRRORS 3
 typedef struct rnr_adam_mirror {
     float* dst;
     int64_t stride[4];
@@ -837,7 +838,7 @@ typedef struct rnr_adam_tensor {
     int slot, num_mirrors;
     int shape[4];
     int reserved[2];            /* 0 */
-    rnr_adam_mirror mirror[3];
+    rnr_adam_mirror mirror[RNR_ADAM_MAX_MIRRORS];
 } rnr_adam_tensor;
 typedef struct rnr_adam_chunk {
     int tensor, chunk;

@@ -1,213 +1,222 @@
-"""ctypes binding of librnr_hip.so (the C ABI declared in include/rnr_hip.h).
+"""ctypes binding of librnr_hip.so, derived from the C ABI's own declaration, include/rnr_hip.h.
+
+The header is parsed once at import: its `typedef struct` blocks become the ctypes.Structure classes (RnrMesh, RnrConvDesc, ...),
+its `#define RNR_X` / `enum` constants the module's integers (the RNR_ prefix dropped: CONV_WINOGRAD, ADAM_CHUNK, ...) and its
+prototypes SIGNATURES and PARAMS.  A new entry point is declared there and nowhere here.
 
 The HIP library is the product: there is no CPU fallback.  If the shared object is missing or a symbol
 cannot be resolved this module raises — callers never silently route elsewhere.
 """
+import collections
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RNR_HIP_LIB: load another build of the same library (kernel ablation experiments); default is the in-tree build
 LIB_PATH = os.environ.get('RNR_HIP_LIB') or os.path.join(os.path.dirname(_HERE), 'librnr_hip.so')
-
-c_void_p, c_int, c_float, c_size_t, c_double = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t,
-                                                ctypes.c_double)
-
-
-class RnrMesh(ctypes.Structure):
-    _fields_ = [('v', c_void_p), ('vt', c_void_p), ('vn', c_void_p), ('f_v_idx', c_void_p),
-                ('f_vt_idx', c_void_p), ('f_vn_idx', c_void_p), ('num_vertices', c_int),
-                ('num_texcoords', c_int), ('num_normals', c_int), ('num_faces', c_int)]
-
-
-class RnrGbuffer(ctypes.Structure):
-    _fields_ = [(n, c_void_p) for n in ['face_index_map', 'alpha', 'depth', 'weight_map', 'raw_weight_map',
-                                        'uv_map', 'normal_map', 'normal_map_cam', 'position_map',
-                                        'position_map_cam']]
-
-
-class RnrObjCounts(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_long) for n in ['num_vertices', 'num_normals', 'num_texcoords', 'num_faces']]
-
-
-class RnrRays(ctypes.Structure):
-    _fields_ = [('pivots_spec_host', c_void_p), ('pivots_diff_host', c_void_p), ('num_spec', c_int),
-                ('num_diff', c_int)]
-
-
-class RnrConvSrc(ctypes.Structure):
-    _fields_ = [('data', c_void_p), ('scale', c_void_p), ('shift', c_void_p), ('channels', c_int), ('act', c_int)]
-
-
-class RnrConvDesc(ctypes.Structure):
-    _fields_ = [('kind', c_int), ('c_in0', c_int), ('c_in0_pad', c_int), ('c_in1', c_int), ('c_in1_pad', c_int),
-                ('c_out', c_int), ('c_out_pad', c_int), ('flags', c_int)]
-
-
-class RnrConvBn(ctypes.Structure):
-    _fields_ = [('gamma', c_void_p), ('beta', c_void_p), ('scale', c_void_p), ('shift', c_void_p), ('eps', c_float),
-                ('running_mean', c_void_p), ('running_var', c_void_p), ('momentum', c_float)]      # NULL / 0: no running-statistics update
-
-
-class RnrAdamMirror(ctypes.Structure):
-    _fields_ = [('dst', c_void_p), ('stride', ctypes.c_int64 * 4), ('repeat_stride', ctypes.c_int64), ('dim', c_int), ('lo', c_int),
-                ('hi', c_int), ('repeat', c_int)]
-
-
-class RnrAdamTensor(ctypes.Structure):
-    _fields_ = [('p', c_void_p), ('g', c_void_p), ('m', c_void_p), ('v', c_void_p), ('n', ctypes.c_int64), ('b1', c_float),
-                ('omb1', c_float), ('b2', c_float), ('omb2', c_float), ('eps', c_float), ('wd', c_float), ('slot', c_int),
-                ('num_mirrors', c_int), ('shape', c_int * 4), ('reserved', c_int * 2), ('mirror', RnrAdamMirror * 3)]
-
-
-class RnrAdamChunk(ctypes.Structure):
-    _fields_ = [('tensor', c_int), ('chunk', c_int)]
-
-
-class RnrAdamScalars(ctypes.Structure):
-    _fields_ = [('step_size', c_float), ('bc2s', c_float)]
-
-
-ADAM_CHUNK = 4096        # RNR_ADAM_CHUNK: elements per workgroup of rnr_adam_step
-ADAM_MAX_SLOTS = 64      # RNR_ADAM_MAX_SLOTS: distinct (step_size, bc2s) pairs per launch
-ADAM_MAX_MIRRORS = 3
-ACT_NONE, ACT_LRELU02, ACT_RELU = 0, 1, 2
-CONV_STATS_PREZEROED = 1
-CONV_F32_EMU_BF16X6 = 2
-CONV_F32_EMU_F16X3 = 4
-CONV_WINOGRAD = 8        # Winograd F(2x2, 3x3) for the 3x3 convolutions (exact-fp32 operands, include/rnr_hip.h)
-CONV_WINOGRAD4 = 16      # with CONV_WINOGRAD: F(4x4, 3x3) where the shape allows (set by UNetPlan's default conv_algo 'winograd4'; include/rnr_hip.h)
-CONV_WINOGRAD42 = 32     # with CONV_WINOGRAD: F(4x4, 2x2) for the transposed convolutions where the shape allows (rnr_conv_winograd_tile 4; include/rnr_hip.h)
-CONV_WINOGRAD42S = 128   # with CONV_WINOGRAD: F(4x4, 2x2) for the 4x4 stride-2 convolutions where the shape allows (rnr_conv_algorithm 2, rnr_conv_winograd_tile 4; include/rnr_hip.h)
-CONV_WINOGRAD4_OUT = 64  # with CONV_WINOGRAD: F(4x4, 3x3) for the 80-column out layer where the shape allows (rnr_conv_algorithm 3, rnr_conv_winograd_tile 4; include/rnr_hip.h)
-EMU_FLAGS = {'f32': 0, 'bf16x6': CONV_F32_EMU_BF16X6, 'f16x3': CONV_F32_EMU_F16X3}
-CONV3x3_REFLECT, CONV4x4S2_REFLECT, CONVT4x4S2 = 0, 1, 2
-BN_BWD_MODES = {'batch': 0, 'batch_all': 1, 'running': 2}         # RNR_BN_BWD_*
-PRESENT_MODES = {'frame': 0, 'composite': 1, 'background': 2}     # RNR_PRESENT_*
-PRESENT_RGB = 8
-BACKGROUND_MASK_MAX_RADIUS = 32                                   # RNR_BACKGROUND_MASK_MAX_RADIUS
-METRIC_PLANAR, METRIC_CHANNELS_LAST = 0, 1                        # RNR_METRIC_* layouts
-# RNR_METRIC_* outputs, in the order of rnr_image_metrics' out columns
-METRIC_KEYS = ('mae', 'mae_bb', 'mae_valid', 'mse', 'mse_bb', 'mse_valid', 'psnr', 'psnr_bb', 'psnr_valid', 'ssim', 'ssim_bb',
-               'ssim_valid')
-
-P = ctypes.POINTER
-# name -> (restype, argtypes); must list every symbol of include/rnr_hip.h (tests/test_abi.py checks it)
-SIGNATURES = {
-    'rnr_abi_version': (c_int, []),
-    'rnr_last_error': (ctypes.c_char_p, []),
-    'rnr_raster_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
-    'rnr_forward_face_index_map': (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_float, c_float, c_int, c_int,
-                                                            c_int, c_void_p, c_void_p]),
-    'rnr_forward_texture_sampling': (c_int, [c_void_p] * 8 + [c_int, c_int, c_int, c_int, c_float, c_void_p]),
-    'rnr_backward_pixel_map': (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_float, c_int, c_int, c_void_p]),
-    'rnr_backward_textures': (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_void_p]),
-    'rnr_backward_depth_map': (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_void_p]),
-    'rnr_load_textures': (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
-    'rnr_create_texture_image': (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_float, c_void_p]),
-    'rnr_project_vertices': (c_int, [c_void_p] * 8 + [c_int, c_int, c_float, c_float, c_void_p]),
-    'rnr_gbuffer_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
-    'rnr_rasterize_gbuffer': (c_int, [P(RnrMesh), c_void_p, c_void_p, c_int, c_int, c_float, c_float, P(RnrGbuffer),
-                                      c_void_p, c_void_p]),
-    'rnr_rasterize_gbuffer_prepared': (c_int, [P(RnrMesh), c_void_p, c_void_p, c_int, c_int, c_float, c_float, P(RnrGbuffer),
-                                               c_void_p, c_void_p]),
-    'rnr_frame_prepare': (c_int, [P(RnrMesh), c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    'rnr_face_tangents': (c_int, [P(RnrMesh), c_void_p, c_void_p]),
-    'rnr_shade_inputs': (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_void_p, P(c_void_p), P(c_int), c_int, c_int,
-                                                  c_int, P(RnrRays), c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                                  c_int, c_int, c_int, c_void_p]),
-    'rnr_packed_weight_floats': (c_size_t, [P(RnrConvDesc)]),
-    'rnr_pack_conv_weight': (c_int, [P(RnrConvDesc), c_void_p, c_void_p, c_void_p]),
-    'rnr_conv_workspace_bytes': (c_size_t, [P(RnrConvDesc), c_int, c_int, c_int]),
-    'rnr_conv2d': (c_int, [P(RnrConvDesc), P(RnrConvSrc), P(RnrConvSrc), c_void_p, c_void_p, c_void_p, c_int, c_int,
-                           c_int, c_void_p, c_size_t, c_void_p]),
-    'rnr_conv_tile_count': (c_size_t, [P(RnrConvDesc), c_int, c_int, c_int]),
-    'rnr_conv_algorithm': (c_int, [P(RnrConvDesc), c_int, c_int, c_int]),
-    'rnr_conv_winograd_tile': (c_int, [P(RnrConvDesc), c_int, c_int, c_int]),
-    'rnr_conv_active_tiles': (c_int, [P(RnrConvDesc), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    'rnr_conv2d_masked': (c_int, [P(RnrConvDesc), P(RnrConvSrc), P(RnrConvSrc), c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                  c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
-    'rnr_conv_sync_bytes': (c_size_t, [P(RnrConvDesc), c_int, c_int, c_int]),
-    'rnr_conv2d_fused': (c_int, [P(RnrConvDesc), P(RnrConvSrc), P(RnrConvSrc), c_void_p, c_void_p, P(RnrConvBn), c_int, c_int,
-                                 c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p]),
-    'rnr_ray_weights': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
-                                c_int, c_int, c_int, c_void_p]),
-    'rnr_conv2d_ray': (c_int, [P(RnrConvDesc), P(RnrConvSrc), P(RnrConvSrc), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                               c_int, c_void_p, c_void_p]),
-    'rnr_bn_finalize': (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_double, c_float, c_void_p]),
-    'rnr_bn_finalize_reset': (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_double, c_float, c_void_p]),
-    'rnr_bn_finalize_batch': (c_int, [c_void_p] * 7 + [c_float, c_int, c_int, c_int, c_double, c_float, c_void_p]),
-    # U-Net backward (csrc/unet_bwd.hip; rnr_bn_finalize_saved: csrc/conv.hip)
-    'rnr_bn_finalize_saved': (c_int, [c_void_p] * 7 + [c_float, c_void_p, c_int, c_int, c_int, c_int, c_double, c_float, c_void_p]),
-    'rnr_conv_out_backward_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
-    'rnr_conv_out_backward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
-                                      c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    'rnr_conv2d_weight_backward_workspace_bytes': (c_size_t, [P(RnrConvDesc), c_int, c_int, c_int]),
-    'rnr_conv2d_weight_backward': (c_int, [P(RnrConvDesc), P(RnrConvSrc), P(RnrConvSrc), c_void_p, c_void_p, c_int, c_int, c_int,
-                                           c_void_p, c_size_t, c_void_p]),
-    'rnr_conv_backward_desc': (c_int, [P(RnrConvDesc), c_int, P(RnrConvDesc)]),
-    'rnr_conv2d_input_backward_ring': (c_int, [P(RnrConvDesc), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    'rnr_unet_out_backward': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    'rnr_nchw_to_nhwc': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    'rnr_nhwc_to_nchw': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    'rnr_ray_render': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
-                               c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
-    'rnr_sh_basis': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    'rnr_sh_reconstruct': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    'rnr_sh_fit': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    'rnr_sh_reconstruct_backward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    'rnr_interpolate_bilinear': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                         c_int, c_void_p]),
-    'rnr_resize_area': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    'rnr_calibrate_mfma_f32': (c_int, [c_int, c_int, c_void_p, P(ctypes.c_double), P(ctypes.c_double), c_void_p]),
-    'rnr_obj_scan': (c_int, [ctypes.c_char_p, c_size_t, P(RnrObjCounts)]),
-    'rnr_obj_parse': (c_int, [ctypes.c_char_p, c_size_t, P(RnrObjCounts)] + [c_void_p] * 6),
-    'rnr_view_dir_map': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    'rnr_env_background': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
-    'rnr_present_u8': (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
-    'rnr_image_metrics_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
-    'rnr_image_metrics': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                  c_int, c_void_p]),
-    # training losses (csrc/loss.hip)
-    'rnr_rays_chrom_loss_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
-    'rnr_rays_chrom_loss': (c_int, [c_void_p] * 8 + [c_int, c_int, c_int, c_int, c_void_p]),
-    'rnr_rays_chrom_loss_backward': (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_int, c_void_p]),
-    'rnr_masked_l1_loss_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
-    'rnr_masked_l1_loss': (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    'rnr_masked_l1_loss_backward': (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    # stitched light probe (csrc/stitch.hip)
-    'rnr_background_mask': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
-    'rnr_stitch_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
-    'rnr_stitch_accumulate': (c_int, [c_void_p, c_int] + [c_void_p] * 6 + [c_size_t, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    'rnr_stitch_finalize': (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p]),
-    'rnr_probe_prepare_workspace_bytes': (c_size_t, [c_int, c_int]),
-    'rnr_probe_prepare': (c_int, [c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    # optimiser (csrc/optim.hip)
-    'rnr_adam_step': (c_int, [c_void_p, c_int, c_void_p, c_int, P(RnrAdamScalars), c_int, c_void_p]),
-    'rnr_pack_conv_weights': (c_int, [P(RnrConvDesc), P(c_void_p), P(c_void_p), c_int, c_void_p]),
-    'rnr_tbn_map': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
-    'rnr_tbn_matvec': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_long, c_int, c_void_p]),
-    'rnr_ray_sampler': (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                ctypes.c_long, c_void_p]),
-    'rnr_texture_mapper': (c_int, [c_void_p, c_void_p, P(c_void_p), P(c_int), c_int, c_int, c_int, c_void_p, c_int,
-                                   c_int, c_int, c_void_p]),
-    'rnr_texture_mapper_backward': (c_int, [c_void_p, c_void_p, c_void_p, P(c_void_p), P(c_int), c_int, c_int, c_int, c_int,
-                                            c_int, c_int, c_void_p]),
-    'rnr_ray_renderer': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
-                                 c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                 c_void_p, c_int, c_int, c_int, c_void_p]),
-    'rnr_ray_renderer_backward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
-                                          c_int, c_int, c_int, c_float] + [c_void_p] * 10 + [c_int, c_int, c_int, c_void_p]),
-    'rnr_ray_transport': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
-                                  c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-}
-
-_lib = None
+# where csrc/ includes it from: ../../include/rnr_hip.h
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), 'include', 'rnr_hip.h')
 
 
 class RnrError(RuntimeError):
     pass
+
+
+# ---------------------------------------------------------------------------------------------------
+# the header as data
+# ---------------------------------------------------------------------------------------------------
+SCALAR_TYPES = ('int', 'float', 'double', 'size_t', 'long', 'int32_t', 'int64_t', 'uint8_t', 'char', 'void')
+
+# one declared name: a struct field, a parameter or a function (its return type).  pointer: number of `*`; count: array length
+Decl = collections.namedtuple('Decl', 'name type pointer count')
+# structs: name -> [Decl]; protos: name -> (Decl of the function, [Decl of the parameters]); constants: RNR_X -> int, defines and
+# enumerators; enums: the enumerator names of every `enum { }`, in order
+Header = collections.namedtuple('Header', 'structs protos constants enums')
+
+
+def parse_header(text):
+    """The C subset rnr_hip.h is written in -> Header.  Strict: whatever is not a comment, an include guard, `#define RNR_X
+    <integer expression>`, `enum { }`, `typedef struct x { } x;` or a prototype over SCALAR_TYPES and the header's own structs
+    raises RnrError naming the line, rather than being skipped."""
+    structs, protos, constants, enums = {}, {}, {}, []
+
+    def fail(pos, why):
+        raise RnrError('rnr_hip.h line %d: %s' % (text.count('\n', 0, pos) + 1, why))
+
+    def value(expr, pos):
+        if not re.fullmatch(r'[\w\s|&()+\-*<>~]+', expr):
+            fail(pos, 'not an integer expression: %r' % expr.strip())
+        try:
+            v = eval(expr, {'__builtins__': {}}, dict(constants))
+        except Exception:
+            v = None
+        if type(v) is not int:
+            fail(pos, 'cannot evaluate %r' % expr.strip())
+        return v
+
+    def declare(decl, pos):
+        """`[const] type declarator {, declarator}` with declarator = {* | const} name [[length]]"""
+        toks = re.findall(r'\w+|\[[^\]]*\]|\S', decl)
+        shown = ' '.join(decl.split())
+        if toks[:1] == ['const']:
+            toks.pop(0)
+        if not toks or (toks[0] not in SCALAR_TYPES and toks[0] not in structs):
+            fail(pos, 'unknown type in %r' % shown)
+        base, out, i = toks[0], [], 1
+        while True:
+            depth = 0
+            while i < len(toks) and toks[i] in ('*', 'const'):
+                depth += toks[i] == '*'
+                i += 1
+            if i == len(toks) or not re.fullmatch(r'[A-Za-z_]\w*', toks[i]) or toks[i] in SCALAR_TYPES or toks[i] in structs:
+                fail(pos, 'expected a name in %r' % shown)
+            name, count, i = toks[i], None, i + 1
+            if i < len(toks) and toks[i][0] == '[':
+                count, i = value(toks[i][1:-1], pos), i + 1
+            if base == 'void' and not depth:
+                fail(pos, 'a void value in %r' % shown)
+            out.append(Decl(name, base, depth, count))
+            if i == len(toks):
+                return out
+            if toks[i] != ',':
+                fail(pos, 'cannot parse %r' % shown)
+            i += 1
+
+    blank = lambda m: re.sub(r'[^\n]', ' ', m.group(0))         # keeps every offset and line number
+    code = re.sub(r'//[^\n]*', blank, re.sub(r'/\*.*?\*/', blank, text, flags=re.S))
+    # preprocessor lines: the include guard, the includes, the extern "C" bracket and the constants
+    cplusplus = False
+    for m in list(re.finditer(r'^[^\n]*$', code, flags=re.M)):
+        line = m.group(0).strip()
+        if cplusplus or line.startswith('#'):
+            code = code[:m.start()] + ' ' * len(m.group(0)) + code[m.end():]
+        if not line.startswith('#'):
+            continue
+        if re.fullmatch(r'#\s*ifdef\s+__cplusplus', line):
+            cplusplus = True
+        elif re.fullmatch(r'#\s*endif', line):
+            cplusplus = False
+        elif re.fullmatch(r'#\s*(ifndef\s+\w+|define\s+\w+|include\s*<\w+\.h>)', line):
+            pass
+        else:
+            d = re.fullmatch(r'#\s*define\s+(RNR_\w+)\s+(.+)', line)
+            if d is None:
+                fail(m.start(), 'unsupported preprocessor line %r' % line)
+            constants[d.group(1)] = value(d.group(2), m.start())
+    # statements: everything up to a `;` outside braces
+    start = depth = 0
+    for pos, ch in enumerate(code):
+        depth += (ch == '{') - (ch == '}')
+        if ch != ';' or depth:
+            continue
+        stmt, at = code[start:pos].strip(), start + len(code[start:pos]) - len(code[start:pos].lstrip())
+        start = pos + 1
+        s = re.fullmatch(r'typedef\s+struct\s+(\w+)\s*\{(.*)\}\s*(\w+)', stmt, flags=re.S)
+        e = re.fullmatch(r'enum\s*\{(.*)\}', stmt, flags=re.S)
+        f = re.fullmatch(r'([^()]*?)\b(rnr_\w+)\s*\(([^()]*)\)', stmt, flags=re.S)
+        if s is not None:
+            if s.group(1) != s.group(3) or s.group(1) in structs:
+                fail(at, 'struct %s: tag and typedef name must agree and be new' % s.group(1))
+            fields, offset = [], at + stmt.index('{') + 1
+            for part in s.group(2).split(';'):
+                if part.strip():
+                    fields += declare(part, offset + len(part) - len(part.lstrip()))
+                offset += len(part) + 1
+            structs[s.group(1)] = fields
+        elif e is not None:
+            names, nxt = [], 0
+            for part in e.group(1).split(','):
+                n = re.fullmatch(r'\s*(RNR_\w+)\s*(?:=(.*))?', part, flags=re.S)
+                if n is None:
+                    fail(at, 'cannot parse enumerator %r' % part.strip())
+                nxt = constants[n.group(1)] = (value(n.group(2), at) if n.group(2) else nxt)
+                nxt += 1
+                names.append(n.group(1))
+            enums.append(tuple(names))
+        elif f is not None and f.group(2) not in protos:
+            params = [] if f.group(3).strip() == 'void' else [declare(p, at) for p in f.group(3).split(',')]
+            if any(len(p) != 1 or p[0].count is not None for p in params):
+                fail(at, 'cannot parse the parameters of %s' % f.group(2))
+            protos[f.group(2)] = (declare('%s %s' % (f.group(1), f.group(2)), at)[0], [p[0] for p in params])
+        else:
+            fail(at, 'not a struct, an enum or an rnr_* prototype: %r' % ' '.join(stmt.split())[:80])
+    if code[start:].strip():
+        fail(start + len(code[start:]) - len(code[start:].lstrip()), 'unterminated declaration')
+    return Header(structs, protos, constants, enums)
+
+
+try:
+    with open(HEADER_PATH) as _f:
+        HEADER = parse_header(_f.read())
+except OSError as _e:
+    raise RnrError('the C ABI declaration %s cannot be read (%s): the binding is derived from it' % (HEADER_PATH, _e))
+
+# ---------------------------------------------------------------------------------------------------
+# ... as ctypes
+# ---------------------------------------------------------------------------------------------------
+_CTYPES = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double, 'size_t': ctypes.c_size_t,
+           'long': ctypes.c_long, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'uint8_t': ctypes.c_uint8,
+           'char': ctypes.c_char}
+STRUCTS = {}        # header name -> ctypes.Structure class; also module attributes in CamelCase (rnr_conv_desc -> RnrConvDesc)
+
+
+def _value_type(d):
+    return STRUCTS.get(d.type) or _CTYPES[d.type]
+
+
+def _field_type(d):             # pointer fields are plain addresses: callers fill them with tensor.data_ptr() or None
+    t = ctypes.c_void_p if d.pointer else _value_type(d)
+    return t * d.count if d.count else t
+
+
+for _name, _fields in HEADER.structs.items():
+    STRUCTS[_name] = type(''.join(w.capitalize() for w in _name.split('_')), (ctypes.Structure,),
+                          {'_fields_': [(d.name, _field_type(d)) for d in _fields]})
+globals().update((c.__name__, c) for c in STRUCTS.values())
+
+# RNR_X -> X
+CONSTANTS = {k[len('RNR_'):]: v for k, v in HEADER.constants.items()}
+globals().update(CONSTANTS)
+
+
+def _enum_keys(first):          # the enum that starts with RNR_<first>, as lower-case keys without their common prefix
+    names = next(e for e in HEADER.enums if e[0] == 'RNR_' + first)
+    cut = len(os.path.commonprefix(names))
+    return tuple(n[cut:].lower() for n in names)
+
+
+EMU_FLAGS = {'f32': 0, 'bf16x6': CONSTANTS['CONV_F32_EMU_BF16X6'], 'f16x3': CONSTANTS['CONV_F32_EMU_F16X3']}
+BN_BWD_MODES = {k: CONSTANTS['BN_BWD_' + k.upper()] for k in _enum_keys('BN_BWD_BATCH')}
+PRESENT_MODES = {k: CONSTANTS['PRESENT_' + k.upper()] for k in _enum_keys('PRESENT_FRAME')}
+# RNR_METRIC_* outputs, in the order of rnr_image_metrics' out columns
+METRIC_KEYS = _enum_keys('METRIC_MAE')
+
+# The one place where the binding does not follow the header: these two tables of rnr_adam_step live in DEVICE memory and are
+# passed as integer addresses (tensor.data_ptr()), which a POINTER(struct) argtype refuses.
+_ARGTYPE_OVERRIDES = {('rnr_adam_step', 'tensors'): ctypes.c_void_p, ('rnr_adam_step', 'chunks'): ctypes.c_void_p}
+
+
+def _argtype(fn, d):
+    if (fn, d.name) in _ARGTYPE_OVERRIDES:
+        return _ARGTYPE_OVERRIDES[fn, d.name]
+    if not d.pointer:
+        return _value_type(d)
+    if d.pointer == 1 and d.type == 'char':
+        return ctypes.c_char_p
+    if d.pointer == 1 and d.type in STRUCTS:
+        return ctypes.POINTER(STRUCTS[d.type])
+    if d.pointer > 1:               # `T* const*`: a host table of addresses, (c_void_p * n)(...)
+        return ctypes.POINTER(ctypes.c_void_p)
+    return ctypes.c_void_p
+
+
+# name -> (restype, argtypes) of every entry point the header declares
+SIGNATURES = {name: (_argtype(name, ret), [_argtype(name, p) for p in params]) for name, (ret, params) in HEADER.protos.items()}
+# name -> the parameters as the header declares them (Decl: name, pointee type, pointer depth); rnr_amd.ops checks tensors by them
+PARAMS = {name: tuple(params) for name, (ret, params) in HEADER.protos.items()}
+
+_lib = None
 
 
 def _build_from_source():
@@ -259,8 +268,8 @@ def load():
         fn.restype = res
         fn.argtypes = args
     ver = lib.rnr_abi_version()
-    if ver != 1:
-        raise RnrError('librnr_hip.so ABI version %d, python binding expects 1' % ver)
+    if ver != CONSTANTS['ABI_VERSION']:
+        raise RnrError('librnr_hip.so ABI version %d, python binding expects %d' % (ver, CONSTANTS['ABI_VERSION']))
     _lib = lib
     return lib
 

@@ -28,7 +28,9 @@ def test_header_declares_and_lib_binds_the_backward():
     assert code.index('rnr_texture_mapper(') < code.index('rnr_texture_mapper_backward(') < code.index('rnr_ray_renderer(')
     restype, argtypes = _lib.SIGNATURES['rnr_texture_mapper_backward']
     assert restype is ctypes.c_int and len(argtypes) == 12
-    assert argtypes[3] == ctypes.POINTER(ctypes.c_void_p) and argtypes[4] == ctypes.POINTER(ctypes.c_int)
+    # the host table of level pointers, and the host array of level sizes: `const int*` is a plain address like every scalar pointer
+    assert argtypes[3] == ctypes.POINTER(ctypes.c_void_p) and argtypes[4] is ctypes.c_void_p
+    assert _lib.PARAMS['rnr_texture_mapper_backward'][4][:3] == ('tex_sizes_host', 'int', 1)
     # the comment says what a caller has to know
     doc = hdr[hdr.index('Adjoint of rnr_texture_mapper'):hdr.index('int rnr_texture_mapper_backward')]
     assert 'run to run' in doc and 'finite' in doc and 'OVERWRITTEN' in doc
