@@ -512,6 +512,12 @@ int rnr_bn_finalize_batch(double* stats, const float* gamma, const float* beta, 
  *   per source s: rnr_conv2d(rnr_conv_backward_desc(d, s)) on g_y, then rnr_conv2d_input_backward_ring -> the gradient of s's z
  * No entry point of this section uses atomics: every output is bit-reproducible run to run (the data gradient inherits
  * rnr_conv2d's reproducibility, called with stats == NULL).  Emulation flags (RNR_CONV_F32_EMU_*) in a descriptor are refused.
+ * Alignment: the channel-last tensors and per-view vectors rnr_conv_out_backward and rnr_conv2d_weight_backward take (y, scale,
+ * shift, g_z0, g_z1, g_y; the sources' data / scale / shift) are read and written in 16-byte pieces and need 16-byte alignment,
+ * like the forward's; `saved` needs its element's 8 bytes; gamma, g_gamma, g_beta, grad_weight, the unpacked weight, and every
+ * operand of rnr_conv2d_input_backward_ring and rnr_unet_out_backward (moved one float at a time) their element's 4 bytes.  The
+ * workspaces: as stated with each entry point.  No entry point reads or writes outside the extents stated here
+ * (tests/test_gpu_unet_backward_guard.py).
  */
 
 /* rnr_bn_finalize_reset (whole_batch == 0: one group per view, running_mean / running_var must be NULL) or rnr_bn_finalize_batch
@@ -558,6 +564,8 @@ int rnr_conv_out_backward(const float* y, const float* scale, const float* shift
  * — live channels only, OVERWRITTEN.  An implicit GEMM on v_mfma_f32_32x32x2_f32 with M = output channels, N = input channels
  * of one tap and K = pixels; K is split over pixel ranges so that the grid fills the chip, every range writes a partial slab
  * into `workspace` and a second launch adds the slabs in range order: no float atomics, bit-reproducible.
+ * A non-finite g_y or source value surfaces in exactly the (co, ci, tap) whose sum holds a term with it: for RNR_CONVT4x4S2 a tap
+ * that falls outside the output map at some pixel has no term there, and the source value of that pixel does not enter it.
  * workspace: rnr_conv2d_weight_backward_workspace_bytes(d, N, in_h, in_w) bytes, 16-byte aligned.
  */
 size_t rnr_conv2d_weight_backward_workspace_bytes(const rnr_conv_desc* d, int num_views, int in_h, int in_w);

@@ -291,6 +291,12 @@ wg_kernel(const WgParams P) {
                 const float slope = act_slope(P.src_act[s]);
                 v = make_float4(normalize1_slope(v.x, sc.x, sh.x, slope), normalize1_slope(v.y, sc.y, sh.y, slope),
                                 normalize1_slope(v.z, sc.z, sh.z, slope), normalize1_slope(v.w, sc.w, sh.w, slope));
+                // transposed kind: a tap that falls outside the output map has no term.  X becomes 0 like g_y above, or a
+                // non-finite X would surface as 0 * X in a tap that never reads it
+                if (P.kind == 2) {
+                    const unsigned oy = 2 * ay - 1 + ky, ox = 2 * ax - 1 + kx;
+                    if (oy >= (unsigned)P.OH || ox >= (unsigned)P.OW) v = make_float4(0.f, 0.f, 0.f, 0.f);
+                }
             }
             breg[r] = v;
         }

@@ -30,6 +30,8 @@ ALIGN_SYNC = (256, 0)           # rnr_conv2d_fused's sync buffer: 256-byte align
 ALIGN_STRIDED = (128, 64)       # channel-strided tensors: where view n > 0 or a row slice of a channel-last tensor may start
 ALIGN_WORD = (8, 4)             # [c_out] vectors, the unpacked weight, the frame: a float, nothing more
 ALIGN_BYTE = (2, 1)             # the tile mask: bytes
+ALIGN_QUAD = (32, 16)           # the U-Net backward's float4 operands and the weight gradient's workspace: 16 bytes, nothing more
+ALIGN_DOUBLE = (16, 8)          # `saved` and rnr_conv_out_backward's workspace: a float64, nothing more
 
 
 def guard_bytes(payload_bytes):
@@ -269,3 +271,109 @@ def conv_active_tiles(desc, alpha, N, H, W, guard=64, fill=0xAA):
     _lib.check(L.rnr_conv_active_tiles(ctypes.byref(desc), _ptr(ad), _ptr(buf), N, H, W, _stream()))
     torch.cuda.synchronize()
     return buf.cpu()
+
+
+# ---- the U-Net backward (include/rnr_hip.h, "U-Net backward"): one call of an entry point from CPU tensors in torch's layouts ----
+# Operands sit at the weakest alignment that section grants: ALIGN_QUAD for what the kernels move as float4, ALIGN_DOUBLE for
+# float64, ALIGN_WORD for the rest; workspaces have exactly the size their *_workspace_bytes function returns.  Outputs start
+# as NaN; guarded, outputs and workspaces start as the sentinel NaN.
+
+def channel_last(x, c_pad=None):
+    """[N,C,H,W] -> float32 [N,H,W,c_pad] on the CPU, padding channels 0."""
+    n, c, h, w = x.shape
+    out = torch.zeros(n, h, w, c_pad or pad16(c), dtype=torch.float32)
+    out[..., :c] = x.permute(0, 2, 3, 1)
+    return out
+
+
+def _pad_cols(v, c_pad):
+    if v is None:
+        return None
+    out = torch.zeros(v.shape[0], c_pad, dtype=torch.float32)
+    out[:, :v.shape[1]] = v
+    return out
+
+
+def run_weight_backward(kind, srcs, gy, c_out, N, H, W, guard=False):
+    """rnr_conv2d_weight_backward.  srcs: list of (raw NCHW, scale [N,C] or None, shift [N,C] or None, act); gy [N,c_out,Ho,Wo].
+    Returns grad_weight in torch's layout on the CPU (with guard: and the guard report)."""
+    from . import _lib
+    from .ops import _ptr, _stream
+    L, ops = _lib.load(), _Operands(guard)
+    cins = [raw.shape[1] for raw, _, _, _ in srcs]
+    desc = conv_desc(kind, cins, c_out)
+    keep, csrc = [], []
+    for i, (raw, sc, sh, act) in enumerate(srcs):
+        cp = pad16(raw.shape[1])
+        d = ops.put('src%d.data' % i, channel_last(raw), ALIGN_QUAD)
+        scd = ops.put('src%d.scale' % i, _pad_cols(sc, cp), ALIGN_QUAD)
+        shd = ops.put('src%d.shift' % i, _pad_cols(sh, cp), ALIGN_QUAD)
+        keep += [d, scd, shd]
+        csrc.append(_lib.RnrConvSrc(d.data_ptr(), scd.data_ptr() if scd is not None else None,
+                                    shd.data_ptr() if shd is not None else None, cp, act))
+    gyd = ops.put('g_y', channel_last(gy), ALIGN_QUAD)
+    k = 3 if kind == 0 else 4
+    shape = (sum(cins), c_out, k, k) if kind == 2 else (c_out, sum(cins), k, k)
+    out = ops.new('grad_weight', shape, torch.float32, ALIGN_WORD, 'nan')
+    wsb = L.rnr_conv2d_weight_backward_workspace_bytes(ctypes.byref(desc), N, H, W)
+    ws = ops.new('workspace', (wsb,), torch.uint8, ALIGN_QUAD, 'empty')
+    _lib.check(L.rnr_conv2d_weight_backward(ctypes.byref(desc), ctypes.byref(csrc[0]), ctypes.byref(csrc[1]) if len(csrc) > 1 else None,
+                                            _ptr(gyd), _ptr(out), N, H, W, _ptr(ws), wsb, _stream()))
+    torch.cuda.synchronize()
+    return (out.cpu(), ops.report()) if guard else out.cpu()
+
+
+def run_input_backward_ring(kind, cins, c_out, source, gy, weight, grad_in, N, H, W, guard=False):
+    """rnr_conv2d_input_backward_ring alone, on a caller's grad_in [N,H,W,c_s_pad] (CPU float32 or int32 bit patterns; copied):
+    gy [N,c_out,Ho,Wo], weight the forward weight in torch's layout.  Returns grad_in on the CPU (with guard: and the report)."""
+    from . import _lib
+    from .ops import _ptr, _stream
+    L, ops = _lib.load(), _Operands(guard)
+    desc = conv_desc(kind, cins, c_out)
+    assert tuple(grad_in.shape) == (N, H, W, pad16(cins[source]))
+    gyd = ops.put('g_y', channel_last(gy), ALIGN_WORD)
+    wd = ops.put('weight', weight, ALIGN_WORD)
+    gin = ops.put('grad_in', grad_in.view(torch.float32), ALIGN_WORD)
+    _lib.check(L.rnr_conv2d_input_backward_ring(ctypes.byref(desc), source, _ptr(gyd), _ptr(wd), _ptr(gin), N, H, W, _stream()))
+    torch.cuda.synchronize()
+    return (gin.cpu(), ops.report()) if guard else gin.cpu()
+
+
+def run_conv_out_backward(y, scale, shift, act, gz0, gz1, gamma, saved, mode, c_pad=None, guard=False):
+    """rnr_conv_out_backward.  y, gz0, gz1 (or None) [N,c,h,w]; scale / shift [N,c] or None; gamma [c] or None; saved
+    [groups,c_pad,2] float64 or None.  Returns (g_y [N,h,w,c_pad], g_gamma [c], g_beta [c]) on the CPU (with guard: and the
+    report)."""
+    from . import _lib
+    from .ops import _ptr, _stream
+    L, ops = _lib.load(), _Operands(guard)
+    N, c, h, w = y.shape
+    c_pad = c_pad or pad16(c)
+    yd = ops.put('y', channel_last(y, c_pad), ALIGN_QUAD)
+    g0 = ops.put('g_z0', channel_last(gz0, c_pad), ALIGN_QUAD)
+    g1 = ops.put('g_z1', channel_last(gz1, c_pad) if gz1 is not None else None, ALIGN_QUAD)
+    sc, sh = ops.put('scale', _pad_cols(scale, c_pad), ALIGN_QUAD), ops.put('shift', _pad_cols(shift, c_pad), ALIGN_QUAD)
+    ga, sv = ops.put('gamma', gamma, ALIGN_WORD), ops.put('saved', saved, ALIGN_DOUBLE)
+    o_gy = ops.new('g_y', (N, h, w, c_pad), torch.float32, ALIGN_QUAD, 'nan')
+    o_gg = ops.new('g_gamma', (c,), torch.float32, ALIGN_WORD, 'nan')
+    o_gb = ops.new('g_beta', (c,), torch.float32, ALIGN_WORD, 'nan')
+    wsb = L.rnr_conv_out_backward_workspace_bytes(N, h, w, c_pad)
+    ws = ops.new('workspace', (wsb,), torch.uint8, ALIGN_DOUBLE, 'empty')
+    _lib.check(L.rnr_conv_out_backward(_ptr(yd), _ptr(sc), _ptr(sh), act, _ptr(g0), _ptr(g1), _ptr(ga), _ptr(sv), mode, _ptr(o_gy),
+                                       _ptr(o_gg), _ptr(o_gb), N, h, w, c, c_pad, _ptr(ws), wsb, _stream()))
+    torch.cuda.synchronize()
+    res = (o_gy.cpu(), o_gg.cpu(), o_gb.cpu())
+    return res + (ops.report(),) if guard else res
+
+
+def run_unet_out_backward(g_out, out, apply_tanh, c_pad, guard=False):
+    """rnr_unet_out_backward: g_out, out (None allowed without tanh) [n,c,h,w] -> g_raw [n,h,w,c_pad] on the CPU (with guard: and the
+    report)."""
+    from . import _lib
+    from .ops import _ptr, _stream
+    L, ops = _lib.load(), _Operands(guard)
+    n, c, h, w = g_out.shape
+    gd, od = ops.put('g_out', g_out, ALIGN_WORD), ops.put('out', out, ALIGN_WORD)
+    raw = ops.new('g_raw', (n, h, w, c_pad), torch.float32, ALIGN_WORD, 'nan')
+    _lib.check(L.rnr_unet_out_backward(_ptr(gd), _ptr(od), int(apply_tanh), _ptr(raw), n, c, h, w, c_pad, _stream()))
+    torch.cuda.synchronize()
+    return (raw.cpu(), ops.report()) if guard else raw.cpu()

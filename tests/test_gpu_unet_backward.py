@@ -6,7 +6,10 @@ Bounds come from the arithmetic, never from a measured error:
   * sums made in float64 (BatchNorm / bias gradients): 4 2^-24 sum|terms|; g_y: 16 roundings of the formula's term magnitudes;
   * interior pixels of the data gradient, which the forward kernels compute: those kernels' own bound, 1e-4 of the output peak;
   * whole network: relative rms error per tensor at most RATIO x that of torch's float32 autograd on the CPU (computed here);
-    the issue's condition is 8, tightened to twice the largest measured ratio as it asks (see RATIO).
+    the issue's condition is 8, tightened to twice the largest measured ratio as it asks (see RATIO); the cases at production
+    width (nf0 = 64) keep the derived 8.
+The `*_wide` tests and test_unet_out_backward take their shapes from oracle/unet_bwd_cases.py: the channel widths of the trained
+network on maps of a few pixels, with the same bounds — they do not depend on width.
 Every direct call of the C ABI starts from outputs filled with NaN and is repeated: the second result must have the same bits."""
 import ctypes
 
@@ -14,6 +17,7 @@ import pytest
 import torch
 
 import unet_bwd_ref as ub
+from oracle import unet_bwd_cases as uc
 from unet_bwd_ref import EPS
 
 pytestmark = pytest.mark.gpu
@@ -33,10 +37,8 @@ def _L():
 
 def _nhwc(x, c_pad=None):
     """[N,C,H,W] (CPU) -> float32 [N,H,W,c_pad] on the device, padding channels 0."""
-    n, c, h, w = x.shape
-    out = torch.zeros(n, h, w, c_pad or _pad16(c), dtype=torch.float32)
-    out[..., :c] = x.permute(0, 2, 3, 1)
-    return out.to(DEV).contiguous()
+    from rnr_amd.testing import channel_last
+    return channel_last(x, c_pad).to(DEV)
 
 
 def _nchw(t, c):
@@ -85,6 +87,19 @@ WG_SHAPES = [(2, 6, 10, (5, 3), 7), (1, 2, 2, (5, 3), 7), (2, 32, 16, (64,), 64)
 @pytest.mark.parametrize('kind', [0, 1, 2])
 @pytest.mark.parametrize('N,H,W,cins,cout', WG_SHAPES, ids=lambda v: str(v).replace(' ', ''))
 def test_weight_gradient_vs_float64_autograd(N, H, W, cins, cout, kind):
+    _check_weight_gradient(N, H, W, cins, cout, kind)
+
+
+WG_WIDE = [(c, k) for c in uc.WG_CASES for k in c['kinds']]
+
+
+@pytest.mark.parametrize('case,kind', WG_WIDE, ids=['%s-k%d' % (c['id'], k) for c, k in WG_WIDE])
+def test_weight_gradient_wide(case, kind):
+    """oracle/unet_bwd_cases.py: every wave tile of wg_kernel, more than one tile per axis, ragged slices, production width."""
+    _check_weight_gradient(case['N'], case['H'], case['W'], case['cins'], case['c_out'], kind)
+
+
+def _check_weight_gradient(N, H, W, cins, cout, kind):
     from rnr_amd import ops
     L = _L()
     g = torch.Generator().manual_seed(1000 * kind + H * W + cout)
@@ -202,6 +217,12 @@ def test_data_gradient_vs_float64_autograd(kind, hw):
     _check_data_gradient(kind, 2, hw[0], hw[1], (5, 3), 7)
 
 
+@pytest.mark.parametrize('kind,N,H,W,cins,cout', uc.DG_CASES, ids=lambda v: str(v).replace(' ', ''))
+def test_data_gradient_wide(kind, N, H, W, cins, cout):
+    """144 gradient-input columns from sources of 72 and 60 live channels; the 1 x 1 input of the transposed kind."""
+    _check_data_gradient(kind, N, H, W, cins, cout)
+
+
 WINO_CANDIDATES = [(1, 64, 64), (2, 64, 64), (1, 128, 128), (2, 128, 128), (1, 256, 256), (2, 256, 256), (1, 512, 512), (2, 512, 512)]
 
 
@@ -262,13 +283,20 @@ def _out_backward_draw(g, N, h, w, c, c_pad, mode, bn, two):
     return y, gz0, gz1, gamma, saved, scale, shift, mu, r, v
 
 
-def _out_backward_case(L, g, N, h, w, c, mode, act, bn, two):
-    from rnr_amd import ops
-    c_pad = _pad16(c)
-    for _ in range(100):        # CPU draws, deterministic: the first one without a pre-activation next to the kink
+def _out_backward_find(g, N, h, w, c, c_pad, mode, bn, two):
+    """CPU draws, deterministic: the first one without a pre-activation next to the kink -> (draw, number of draws)."""
+    for tries in range(1, 101):
         case = _out_backward_draw(g, N, h, w, c, c_pad, mode, bn, two)
         if float(case[-1].abs().min()) > 1e-4:
             break
+    return case, tries
+
+
+def _out_backward_case(L, g, N, h, w, c, mode, act, bn, two, c_pad=None):
+    """-> worst error / bound of (g_y, g_beta, g_gamma); 0 for g_gamma without BatchNorm."""
+    from rnr_amd import ops
+    c_pad = c_pad or _pad16(c)
+    case, _ = _out_backward_find(g, N, h, w, c, c_pad, mode, bn, two)
     y, gz0, gz1, gamma, saved, scale, shift, mu, r, v = case
     y64 = y.double()
     assert float(v.abs().min()) > 1e-4, 'a pre-activation too close to the kink'
@@ -294,7 +322,7 @@ def _out_backward_case(L, g, N, h, w, c, mode, act, bn, two):
         ref_gy, mag_gy, ref_gg, mag_gg = gv, gv_mag, None, None
     ref_gb, mag_gb = gv.sum((0, 2, 3)), gv_mag.sum((0, 2, 3))
 
-    d_y, d_g0, d_g1 = _nhwc(y), _nhwc(gz0), (_nhwc(gz1) if two else None)
+    d_y, d_g0, d_g1 = _nhwc(y, c_pad), _nhwc(gz0, c_pad), (_nhwc(gz1, c_pad) if two else None)
     d_sc = _padc(scale, c_pad) if scale is not None else None
     d_sh = _padc(shift, c_pad)
     d_gamma = gamma.to(DEV) if bn else None
@@ -315,15 +343,19 @@ def _out_backward_case(L, g, N, h, w, c, mode, act, bn, two):
     assert (o_gy[..., c:] == 0).all(), 'padding channels must be 0'
     tag = 'mode %d act %d bn %d two %d' % (mode, act, bn, two)
     e = (_nchw(o_gy, c).double() - ref_gy).abs()
-    assert (e <= 16 * EPS * mag_gy).all(), (tag, float((e / (16 * EPS * mag_gy).clamp_min(1e-300)).max()))
+    worst = [float((e / (16 * EPS * mag_gy).clamp_min(1e-300)).max()), 0.0, 0.0]
+    assert (e <= 16 * EPS * mag_gy).all(), (tag, worst[0])
     e = (o_gb.double() - ref_gb).abs()
-    assert (e <= 4 * EPS * mag_gb).all(), (tag, 'g_beta', float((e / (4 * EPS * mag_gb)).max()))
+    worst[1] = float((e / (4 * EPS * mag_gb).clamp_min(1e-300)).max())
+    assert (e <= 4 * EPS * mag_gb).all(), (tag, 'g_beta', worst[1])
     if bn:
         assert torch.equal(runs[0][1], runs[1][1])
         e = (o_gg.double() - ref_gg).abs()
-        assert (e <= 4 * EPS * mag_gg).all(), (tag, 'g_gamma', float((e / (4 * EPS * mag_gg)).max()))
+        worst[2] = float((e / (4 * EPS * mag_gg).clamp_min(1e-300)).max())
+        assert (e <= 4 * EPS * mag_gg).all(), (tag, 'g_gamma', worst[2])
     else:
         assert torch.isnan(o_gg).all(), 'g_gamma must not be written without BatchNorm'
+    return worst
 
 
 @pytest.mark.parametrize('hw', [(5, 7), (16, 16)], ids=lambda s: '%dx%d' % s)
@@ -335,6 +367,80 @@ def test_conv_out_backward(hw):
             for mode in (0, 1, 2):
                 _out_backward_case(L, g, 3, hw[0], hw[1], 7, mode, act, True, two)
             _out_backward_case(L, g, 3, hw[0], hw[1], 7, 0, act, False, two)
+
+
+def out_backward_wide_seed(case):
+    return case['c_pad'] * 131 + case['h'] * 31 + case['w']
+
+
+@pytest.mark.parametrize('case', uc.OB_CASES, ids=[c['id'] for c in uc.OB_CASES])
+def test_conv_out_backward_wide(case):
+    """oracle/unet_bwd_cases.py: idle lanes in the reduce workgroup, parameter gradients in two workgroups, OB_MAX_CPAD, ragged
+    parts and apply workgroups — over the grid of test_conv_out_backward (uc.OB_GRID, the bias-only form included)."""
+    L = _L()
+    g = torch.Generator().manual_seed(out_backward_wide_seed(case))
+    worst = [0.0, 0.0, 0.0]
+    for act, two, mode, bn in uc.OB_GRID:
+        got = _out_backward_case(L, g, case['N'], case['h'], case['w'], case['c'], mode, act, bn, two, case['c_pad'])
+        worst = [max(a, b) for a, b in zip(worst, got)]
+    print('conv_out_backward %s: worst error / bound g_y %.3f, g_beta %.3f, g_gamma %.3f' % ((case['id'],) + tuple(worst)))
+
+
+def test_conv_out_backward_refuses_more_than_1024_columns():
+    """c_pad = 1040: an error that names the limit, before any launch (the outputs keep their NaN)."""
+    from rnr_amd import _lib, ops
+    L = _L()
+    N, h, w, c_pad = 1, 2, 2, uc.OB_REFUSED_CPAD
+    c = c_pad - 3
+    y, gz = torch.randn(N, h, w, c_pad, device=DEV), torch.randn(N, h, w, c_pad, device=DEV)
+    o_gy = torch.full((N, h, w, c_pad), float('nan'), device=DEV)
+    o_gb = torch.full((c,), float('nan'), device=DEV)
+    nbytes = L.rnr_conv_out_backward_workspace_bytes(N, h, w, c_pad)
+    ws = torch.full((nbytes // 4,), float('nan'), device=DEV)
+    with pytest.raises(_lib.RnrError, match=r'at most %d\b' % uc.OB_MAX_CPAD):
+        null = ops._ptr(None)
+        _check(L.rnr_conv_out_backward(ops._ptr(y), null, null, 1, ops._ptr(gz), null, null, null, 0, ops._ptr(o_gy), null,
+                                       ops._ptr(o_gb), N, h, w, c, c_pad, ops._ptr(ws), nbytes, ops._stream()))
+    torch.cuda.synchronize()
+    assert torch.isnan(o_gy).all() and torch.isnan(o_gb).all() and torch.isnan(ws).all(), 'a refused call launched something'
+
+
+# ------------------------------------------------------------------------------------------------
+# 3b. rnr_unet_out_backward
+# ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('apply_tanh', [0, 1])
+@pytest.mark.parametrize('n,c,h,w,c_pad', uc.UO_CASES, ids=lambda v: str(v))
+def test_unet_out_backward(n, c, h, w, c_pad, apply_tanh):
+    """g_raw[n,h,w,ch] = g_out[n,ch,h,w] (1 - out^2) against float64 from the float32 operands.  The kernel rounds o^2, 1 - o^2
+    and the product: three roundings of the term magnitude |g| (1 + o^2); without tanh it copies, so the bits are g_out's and
+    `out` may be NULL.  Padding channels exactly 0."""
+    from rnr_amd import ops
+    L = _L()
+    g = torch.Generator().manual_seed(n * 1000 + c)
+    g_out = torch.randn(n, c, h, w, generator=g)
+    out = torch.tanh(torch.randn(n, c, h, w, generator=g) * 1.5)
+    assert (n * h * w * c_pad) % 256 != 0
+    d_g, d_o = g_out.to(DEV), (out.to(DEV) if apply_tanh else None)
+    runs = []
+    for _ in range(2):
+        raw = torch.full((n, h, w, c_pad), float('nan'), device=DEV)
+        _check(L.rnr_unet_out_backward(ops._ptr(d_g), ops._ptr(d_o), apply_tanh, ops._ptr(raw), n, c, h, w, c_pad, ops._stream()))
+        torch.cuda.synchronize()
+        runs.append(raw.cpu())
+    assert torch.equal(runs[0], runs[1]), 'two runs differ'
+    got = runs[0]
+    assert torch.isfinite(got).all(), 'output not overwritten everywhere'
+    assert (got[..., c:] == 0).all(), 'padding channels must be 0'
+    if apply_tanh:
+        ref = g_out.double() * (1 - out.double() ** 2)
+        bound = 3 * EPS * g_out.double().abs() * (1 + out.double() ** 2)
+        err = (_nchw(got, c).double() - ref).abs()
+        worst = float((err / bound.clamp_min(1e-300)).max())
+        print('unet_out_backward %s tanh: worst error / bound = %.3f' % ((n, c, h, w, c_pad), worst))
+        assert (err <= bound).all(), worst
+    else:
+        assert torch.equal(_nchw(got, c), g_out), 'without tanh the gradient is copied'
+        print('unet_out_backward %s no tanh: bitwise copy' % ((n, c, h, w, c_pad),))
 
 
 @pytest.mark.parametrize('whole', [0, 1])
@@ -402,12 +508,17 @@ NET_SEEDS = {(2, 2, 32, 32, True): 14, (5, 2, 32, 32, True): 3, (2, 1, 64, 32, T
 # The issue's condition is 8 (4.5 x rms rounding of F(4x4, .) over the direct form, plus another summation order); the measured
 # ratios came out at 1.3 .. 2.55 (profiles/unet_backward_accuracy.txt), so the constant is tightened to twice the largest, 2.552.
 RATIO = 5.1
+# Production width, nf0 = 64 with three levels: weights up to [512,128,4,4] and [256,256,.,.] on maps of 8 x 8 down to 1 x 1.
+# (nf0, num_down, N, H, W, bn train mode) -> seed, found on the CPU under the same condition.  RATIO was tightened from
+# measurements at nf0 = 4 and is not assumed at this width: these cases keep the derived condition, 8.
+WIDE_NET_SEEDS = {(64, 3, 1, 8, 8, True): 57, (64, 3, 2, 8, 8, True): 38, (64, 3, 2, 8, 8, False): 1729}
+RATIO_WIDE = 8.0
 
 
-def _make_net(num_down, seed, use_gcn=False):
+def _make_net(num_down, seed, use_gcn=False, nf0=4):
     import network
     torch.manual_seed(seed)
-    net = network.RenderingNet(nf0=4, in_channels=16, out_channels=6, num_down_unet=num_down, use_gcn=use_gcn)
+    net = network.RenderingNet(nf0=nf0, in_channels=16, out_channels=6, num_down_unet=num_down, use_gcn=use_gcn)
     g = torch.Generator().manual_seed(seed + 1)
     for m in net.modules():
         if isinstance(m, torch.nn.BatchNorm2d):
@@ -430,12 +541,47 @@ def _ref_grads(sd, num_down, x, lw, bn_train, dtype):
     return xx.grad, {k: p.grad for k, p in ref.p.items()}, ref.min_abs_preact
 
 
-@pytest.mark.parametrize('num_down,N,H,W,bn_train', [(2, 2, 32, 32, True), (5, 2, 32, 32, True), (2, 1, 64, 32, True),
-                                                      (5, 1, 64, 32, True), (2, 2, 32, 32, False), (5, 2, 32, 32, False)],
-                         ids=lambda v: str(v))
-def test_whole_network_vs_float64_and_float32_autograd(num_down, N, H, W, bn_train):
-    seed = NET_SEEDS[(num_down, N, H, W, bn_train)]
-    net = _make_net(num_down, seed)
+def _hip_grads(net, x, lw, bn_train, input_grad=True):
+    """One forward / backward of the opted-in module on the device -> (gradient of x or None, {state-dict key: gradient}) on the
+    CPU; parameter gradients are cleared first."""
+    net.train(bn_train)
+    for m in net.modules():
+        if isinstance(m, torch.nn.Dropout2d):
+            m.eval()
+    net.zero_grad(set_to_none=True)
+    dx = x.to(DEV)
+    if input_grad:
+        dx.requires_grad_()
+    (net(dx, None) * lw.to(DEV)).sum().backward()
+    torch.cuda.synchronize()
+    sdv = net.net.state_dict(keep_vars=True)
+    return (dx.grad.cpu() if input_grad else None), {k: v.grad.cpu() for k, v in sdv.items() if v.grad is not None}
+
+
+def _assert_ratios(gx, gp, gx64, gp64, gx32, gp32, limit):
+    """Per tensor e_hip / max(e_t32, 2^-23) <= limit -> the worst ratio."""
+    worst = 0.0
+    rows = [('input', gx, gx64, gx32)] + [(k, gp.get(k), gp64[k], gp32[k]) for k in sorted(gp64)]
+    for name, got, r64, r32 in rows:
+        assert got is not None, name
+        e_hip, e_t32 = ub.rel_rms(got, r64), ub.rel_rms(r32, r64)
+        ratio = e_hip / max(e_t32, 2.0 ** -23)
+        worst = max(worst, ratio)
+        assert ratio <= limit, (name, e_hip, e_t32)
+    return worst
+
+
+NET_CASES = [(4, 2, 2, 32, 32, True), (4, 5, 2, 32, 32, True), (4, 2, 1, 64, 32, True), (4, 5, 1, 64, 32, True),
+             (4, 2, 2, 32, 32, False), (4, 5, 2, 32, 32, False)] + sorted(WIDE_NET_SEEDS)
+
+
+@pytest.mark.parametrize('nf0,num_down,N,H,W,bn_train', NET_CASES,
+                         ids=['-'.join(str(v) for v in c[1:]) if c[0] == 4 else 'nf%d-' % c[0] + '-'.join(str(v) for v in c[1:])
+                              for c in NET_CASES])
+def test_whole_network_vs_float64_and_float32_autograd(nf0, num_down, N, H, W, bn_train):
+    wide = nf0 != 4
+    seed = WIDE_NET_SEEDS[(nf0, num_down, N, H, W, bn_train)] if wide else NET_SEEDS[(num_down, N, H, W, bn_train)]
+    net = _make_net(num_down, seed, nf0=nf0)
     x, lw = _net_inputs(seed, N, H, W)
     sd = {k: v.clone() for k, v in net.state_dict().items()}
     gx64, gp64, min_v = _ref_grads(sd, num_down, x, lw, bn_train, torch.float64)
@@ -443,23 +589,48 @@ def test_whole_network_vs_float64_and_float32_autograd(num_down, N, H, W, bn_tra
     gx32, gp32, _ = _ref_grads(sd, num_down, x, lw, bn_train, torch.float32)
 
     net = net.to(DEV).enable_hip_backward()
-    net.train(bn_train)
-    for m in net.modules():
-        if isinstance(m, torch.nn.Dropout2d):
-            m.eval()
-    dx = x.to(DEV).requires_grad_()
-    (net(dx, None) * lw.to(DEV)).sum().backward()
-    torch.cuda.synchronize()
-    sdv = net.net.state_dict(keep_vars=True)
-    worst = 0.0
-    rows = [('input', dx.grad.cpu(), gx64, gx32)] + [(k, sdv[k].grad.cpu(), gp64[k], gp32[k]) for k in sorted(gp64)]
-    for name, got, r64, r32 in rows:
-        assert got is not None, name
-        e_hip, e_t32 = ub.rel_rms(got, r64), ub.rel_rms(r32, r64)
-        ratio = e_hip / max(e_t32, 2.0 ** -23)
-        worst = max(worst, ratio)
-        assert ratio <= RATIO, (name, e_hip, e_t32)
-    print('whole network %s: worst e_hip / max(e_t32, 2^-23) = %.3f' % ((num_down, N, H, W, bn_train), worst))
+    gx, gp = _hip_grads(net, x, lw, bn_train)
+    worst = _assert_ratios(gx, gp, gx64, gp64, gx32, gp32, RATIO_WIDE if wide else RATIO)
+    print('whole network %s%s: worst e_hip / max(e_t32, 2^-23) = %.3f'
+          % ('nf0 %d ' % nf0 if wide else '', (num_down, N, H, W, bn_train), worst))
+
+
+def test_frozen_input_leaves_the_parameter_gradients_bitwise():
+    """UNetPlan.backward(want_input_grad=False) skips the data gradient of the first layer and nothing else: the same net and data
+    with and without x.requires_grad_() give every parameter gradient the same bits."""
+    key = (2, 2, 32, 32, True)
+    net = _make_net(2, NET_SEEDS[key]).to(DEV).enable_hip_backward()
+    x, lw = _net_inputs(NET_SEEDS[key], 2, 32, 32)
+    gx, with_x = _hip_grads(net, x, lw, True)
+    none, frozen = _hip_grads(net, x, lw, True, input_grad=False)
+    assert gx is not None and torch.isfinite(gx).all() and none is None
+    assert set(frozen) == set(with_x) and len(frozen) >= 20
+    for k in sorted(with_x):
+        assert torch.equal(frozen[k].view(torch.int32), with_x[k].view(torch.int32)), k
+
+
+def test_fewer_views_than_the_plan_holds():
+    """The ordinary last batch: one module runs a training step at N = 2, then one at N = 1 on the SAME plan (built for two
+    views).  The N = 1 gradients meet the float64 condition of a fresh N = 1 run (the case (2, 1, 64, 32, True) and its seed)."""
+    key = (2, 1, 64, 32, True)
+    seed = NET_SEEDS[key]
+    net = _make_net(2, seed)
+    x, lw = _net_inputs(seed, 1, 64, 32)
+    sd = {k: v.clone() for k, v in net.state_dict().items()}
+    gx64, gp64, min_v = _ref_grads(sd, 2, x, lw, True, torch.float64)
+    assert min_v >= 2e-5, 'seed %d: a pre-activation of the oracle lies at %.2e from its kink' % (seed, min_v)
+    gx32, gp32, _ = _ref_grads(sd, 2, x, lw, True, torch.float32)
+    net = net.to(DEV).enable_hip_backward()
+    x2, lw2 = _net_inputs(seed + 100, 2, 64, 32)
+    _hip_grads(net, x2, lw2, True)
+    plans = [v for k, v in net.net._plans.items() if len(k) == 5]
+    assert len(plans) == 1 and plans[0].N == 2
+    gx, gp = _hip_grads(net, x, lw, True)
+    now = [v for k, v in net.net._plans.items() if len(k) == 5]
+    assert len(now) == 1 and now[0] is plans[0] and now[0].N == 2, 'the training plan was rebuilt for the smaller batch'
+    assert tuple(gx.shape) == (1, 16, 64, 32)
+    worst = _assert_ratios(gx, gp, gx64, gp64, gx32, gp32, RATIO)
+    print('whole network (2, 1, 64, 32, True) on a plan for two views: worst e_hip / max(e_t32, 2^-23) = %.3f' % worst)
 
 
 def test_dead_parameters_get_no_gradient():
