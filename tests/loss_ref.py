@@ -103,10 +103,19 @@ def chrom_grad_tol(ref_grad, scale, R):
 
 
 ALPHAS = ('full', 'binary', 'fractional')
-CHROM_SHAPES = [(1, 1, 1, 1), (1, 2, 5, 13), (2, 9, 37, 29), (3, 26, 64, 64), (1, 39, 17, 66)]
+# 2 x 129 x 255 = 65790 pixels: 257 workgroups of 256, so the finalise loop over their records (256 threads) runs a second pass
+CHROM_SHAPES = [(1, 1, 1, 1), (1, 2, 5, 13), (2, 9, 37, 29), (3, 26, 64, 64), (1, 39, 17, 66), (2, 3, 129, 255)]
+CHROM_SHAPE_257 = CHROM_SHAPES[-1]
+TAIL_START = 256 * 256            # the first pixel of workgroup 256, whose record only the second pass of a finalise loop reads
+_ALPHA_SEEDS = ALPHAS + ('tail',)
 
 
 def make_alpha(rng, kind, N, H, W):
+    if kind == 'tail':            # non-zero only at flat pixel indices >= 65536: the loss and sum alpha come from record 256 alone
+        assert N * H * W > TAIL_START
+        a = np.zeros(N * H * W, np.float32)
+        a[TAIL_START:] = (0.25 + 0.75 * rng.random(N * H * W - TAIL_START)).astype(np.float32)
+        return a.reshape(N, 1, H, W)
     if kind == 'full':
         return np.ones((N, 1, H, W), np.float32)
     if kind == 'binary':
@@ -122,7 +131,7 @@ def chrom_case(shape, alpha_kind, with_img):
     """Inputs as float32 host tensors: rays in [0.5, 2.5) per component (RenderingNet's (tanh + 1) range, away from 0), the
     photograph partly dark (|img| below and above 1/20, so that both sides of the clamp occur)."""
     N, R, H, W = shape
-    rng = np.random.default_rng(1000 * R + 10 * H + ALPHAS.index(alpha_kind) + (5 if with_img else 0))
+    rng = np.random.default_rng(1000 * R + 10 * H + _ALPHA_SEEDS.index(alpha_kind) + (5 if with_img else 0))
     rays = (0.5 + 2.0 * rng.random((N, R, 3, H, W))).astype(np.float32)
     alpha = make_alpha(rng, alpha_kind, N, H, W)
     img = (rng.random((N, 3, H, W)) * 0.06).astype(np.float32) if with_img else None
@@ -171,19 +180,24 @@ def l1(est, gt, alpha, border, g=1.0):
     return float(loss.detach()), grad, diff.numel()
 
 
+# partials257: 2 x 130 x 253 = 65780 pixels, 257 workgroups, border 0 so that the pixels of the last one lie in the crop;
+# partials257_crop: 257 x 256 pixels are exactly 257 workgroups, the last one wholly inside the border
 L1_CASES = {'one_pixel': ((1, 3, 11, 11), 5), 'two_views': ((2, 3, 24, 37), 5), 'one_channel': ((1, 1, 64, 64), 5),
-            'no_border': ((2, 3, 9, 14), 0)}
+            'no_border': ((2, 3, 9, 14), 0), 'partials257': ((2, 3, 130, 253), 0), 'partials257_crop': ((1, 1, 257, 256), 5)}
+_L1_SEEDS = ('no_border', 'one_channel', 'one_pixel', 'two_views', 'partials257', 'partials257_crop')   # a case keeps its seed
 
 
 def l1_case(name, alpha_kind='fractional'):
-    """est, gt in [0, 1), one crop element with est == gt (the sign there is 0) -> float32 host tensors and the border."""
+    """est, gt in [0, 1), one crop element with est == gt (the sign there is 0; its alpha is 1 unless the kind is `tail`, which
+    stays zero before pixel 65536) -> float32 host tensors and the border."""
     (N, C, H, W), b = L1_CASES[name]
-    rng = np.random.default_rng(sorted(L1_CASES).index(name) + 40)
+    rng = np.random.default_rng(_L1_SEEDS.index(name) + 40)
     est = rng.random((N, C, H, W)).astype(np.float32)
     gt = rng.random((N, C, H, W)).astype(np.float32)
     alpha = make_alpha(rng, alpha_kind, N, H, W)
     gt[0, 0, H // 2, W // 2] = est[0, 0, H // 2, W // 2]
-    alpha[0, 0, H // 2, W // 2] = 1.0
+    if alpha_kind != 'tail':
+        alpha[0, 0, H // 2, W // 2] = 1.0
     return T(est), T(gt), T(alpha), b
 
 

@@ -206,13 +206,37 @@ def case(name):
     elif name == 'no_mask':
         est, gt = noise_images(2, 21, 26, 11)
         mask = None
+    # the smallest sizes at which a second-level loop of csrc/metric.hip runs a second pass (SECOND_PASS below); the data that
+    # only the later pass sees decides the result
+    elif name == 'wide300':                        # 13 x 300: sums_kernel's x loop runs twice (W > 256)
+        est, gt = noise_images(2, 13, 300, 12)
+        ragged = rect_mask(13, 300, 1, 13, 200, 290) * (np.random.default_rng(13).random((13, 300)) > 0.1)
+        ragged[1, 200] = ragged[12, 289] = 1       # the box is rows 1..12, columns 200..289: it crosses column 256
+        mask = np.stack([rect_mask(13, 300, 0, 13, 260, 300), ragged.astype(np.float32)])   # view 0: second x pass only
+    elif name == 'bands256':                       # 2048 x 12: 256 bands of 8 rows, exactly one pass of view_box
+        est, gt = noise_images(2, 2048, 12, 14)
+        mask = np.stack([blob_mask(2048, 12, 15), rect_mask(2048, 12, 2040, 2048, 0, 12)])
+    elif name == 'bands9':                         # 2049 x 12: band_rows 9, 228 bands, the last one 6 rows
+        est, gt = noise_images(2, 2049, 12, 16)
+        mask = np.stack([rect_mask(2049, 12, 2040, 2049, 0, 12), np.ones((2049, 12), np.float32)])   # view 0: a box 9 high
+    elif name == 'tiles257':                       # 8203 x 13: 257 tiles per view (the last holds one row of windows), band_rows 33
+        est, gt = noise_images(2, 8203, 13, 17)
+        mask = np.stack([np.ones((8203, 13), np.float32), rect_mask(8203, 13, 8100, 8203, 0, 13)])
     else:
         raise KeyError(name)
     ref, box = batch(est, gt, mask)
     return {'est': est, 'gt': gt, 'mask': mask, 'ref': ref, 'box': box}
 
 
-CASES = ['one_window', '10x13', '13x10', 'four_masks', 'four_masks_bright', 'boxes', 'tiles', 'tiles_wide', 'disc128', 'no_mask']
+CASES = ['one_window', '10x13', '13x10', 'four_masks', 'four_masks_bright', 'boxes', 'tiles', 'tiles_wide', 'disc128', 'no_mask',
+         'wide300', 'bands256', 'bands9', 'tiles257']
+
+# name -> (H, W, Band records per view, Tile records per view) of the second-pass cases: what csrc/metric.hip's make_plan gives
+# them (bands of max(8, ceil(H / 256)) rows, tiles of 32 x 32 windows).  test_metric_ref_cpu.py asserts these counts against
+# rnr_image_metrics_workspace_bytes, so a case cannot drift off its threshold unnoticed.
+SECOND_PASS = {'wide300': (13, 300, 2, 10), 'bands256': (2048, 12, 256, 64), 'bands9': (2049, 12, 228, 64),
+               'tiles257': (8203, 13, 249, 257)}
+BAND_BYTES, TILE_BYTES = 40, 16
 
 # bounds of the GPU tests against this yardstick (both sides float64)
 #   sums: n 2^-53 for n = 3 x 512^2 terms in any summation order = 8.7e-11

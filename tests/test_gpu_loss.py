@@ -20,7 +20,9 @@ Bounds, derived; both sides compute every pixel in float64 (u = 2^-53):
 A wrong term, divisor or sign shows at 1e-3 or more of the value.  Every comparison prints its figures before it asserts.
 
 Shapes (loss_ref.CHROM_SHAPES): one pixel; 65 pixels (a ragged second wave); 2 x 37 x 29 (nine workgroups, the last ragged, two
-views); 3 x 26 x 64 x 64 (the ray count whose backward keeps the rays in registers); R = 39 odd, W = 66.
+views); 3 x 26 x 64 x 64 (the ray count whose backward keeps the rays in registers); R = 39 odd, W = 66; 2 x 3 x 129 x 255 and,
+for the L1, 2 x 3 x 130 x 253 and 1 x 1 x 257 x 256: 257 workgroups, the smallest count at which the finalise kernels' loops over
+the workgroups' records (256 threads) run a second pass, also with an alpha that is non-zero in the last record alone.
 """
 import ctypes
 import os
@@ -99,6 +101,20 @@ def test_chrom_loss_against_the_float64_yardstick(shape, alpha_kind, with_img):
         assert abs(float(out[0])) <= 1e-15 and float(grad.abs().max()) <= 1e-15
     else:
         assert ref['loss'] > 1e-3 and float(grad.abs().max()) > 0
+
+
+@pytest.mark.parametrize('with_img', [True, False], ids=['img', 'noimg'])
+def test_chrom_loss_from_the_last_record_alone(with_img):
+    """2 x 3 x 129 x 255 is 257 workgroups; alpha is non-zero only from pixel 65536 on, so the loss and sum alpha come through
+    record 256, which only the second pass of chrom_finalise_kernel's loop reads.  The backward divides by loss_out[1]: a
+    dropped record shows in every gradient element.  Same bounds as every other shape (they scale with the pixel count)."""
+    from rnr_amd import _lib
+    N, R, H, W = lr.CHROM_SHAPE_257
+    assert _lib.load().rnr_rays_chrom_loss_workspace_bytes(N, R, H, W) == 257 * 16
+    x, a, i = lr.chrom_case(lr.CHROM_SHAPE_257, 'tail', with_img)
+    assert not bool(a.reshape(-1)[:lr.TAIL_START].any()) and bool((a.reshape(-1)[lr.TAIL_START:] > 0).all())
+    out, grad, ref = _check_chrom(x, a, i, '%s tail %s' % (_ids(lr.CHROM_SHAPE_257), 'img' if with_img else 'noimg'))
+    assert ref['loss'] > 1e-3 and ref['sum_alpha'] > 0 and float(grad.abs().max()) > 0
 
 
 def test_chrom_loss_degenerate_pixels():
@@ -183,6 +199,19 @@ def test_l1_against_the_float64_yardstick(name, alpha_kind):
     H, W = est.shape[2:]
     assert float(est[0, 0, H // 2, W // 2]) == float(gt[0, 0, H // 2, W // 2]) and float(a[0, 0, H // 2, W // 2]) == 1
     assert float(grad[0, 0, H // 2, W // 2]) == 0 and float(grad_ref[0, 0, H // 2, W // 2]) == 0       # sign(0) = 0
+    assert float(grad.abs().max()) > 0
+
+
+def test_l1_from_the_last_record_alone():
+    """partials257 (2 x 3 x 130 x 253, border 0) with alpha non-zero only from pixel 65536 on: the whole loss comes through
+    partial 256, which only the second pass of l1_finalise_kernel's loop reads.  Same bound as every other case."""
+    from rnr_amd import _lib
+    (N, C, H, W), b = lr.L1_CASES['partials257']
+    assert _lib.load().rnr_masked_l1_loss_workspace_bytes(N, H, W) == 257 * 8
+    est, gt, a, b = lr.l1_case('partials257', 'tail')
+    flat = a.reshape(-1)
+    assert not bool(flat[:lr.TAIL_START].any()) and bool((flat[lr.TAIL_START:] > 0).all())
+    grad, _ = _check_l1(est, gt, a, b, 'partials257 tail border %d' % b)
     assert float(grad.abs().max()) > 0
 
 

@@ -12,7 +12,11 @@ A wrong tap, weight, window range or divisor shows at 1e-5 or more.
 
 Sizes are the smallest at which each piece can go wrong (metric_ref.case): one window; no window; 37 x 29 with a full, a ragged,
 a one-pixel and an empty mask; boxes of 11 x 11, 11 x 12, 10 x 40; 75 x 53 and 53 x 85 (two full 32-window tiles and a
-remainder on either axis); 128 x 128 with a disc.  Every comparison prints its figures before it asserts."""
+remainder on either axis); 128 x 128 with a disc; and the smallest sizes at which a second-level loop of the kernels runs a
+second pass, masked so that the later pass decides the result: 13 x 300 (sums_kernel's x loop, W > 256), 2048 x 12 and
+2049 x 12 (256 bands of 8 rows; band_rows 9 with a short last band), 8203 x 13 (257 tiles per view, band_rows 33: the tile
+loop of finalise_kernel).  The largest of them has 3 x 8203 x 13 = 3.2e5 terms and 2.5e4 windows per view, below the
+3 x 512^2 terms and 2.5e5 windows the bounds above are derived for.  Every comparison prints its figures before it asserts."""
 import ctypes
 import os
 import sys
@@ -137,9 +141,10 @@ def test_compute_ssim_false():
     assert np.array_equal(box, c['box']) and np.isfinite(full).all()
 
 
-def test_two_calls_same_bits_and_inputs_untouched():
+@pytest.mark.parametrize('name', ['disc128', 'tiles257'])
+def test_two_calls_same_bits_and_inputs_untouched(name):
     from rnr_amd import ops
-    c = mr.case('disc128')
+    c = mr.case(name)
     e, g, m = T(c['est']).to(DEV), T(c['gt']).to(DEV), T(c['mask']).to(DEV)
     a = ops.image_metrics(e, g, m).clone()
     b = ops.image_metrics(e, g, m)
@@ -153,13 +158,15 @@ def test_two_calls_same_bits_and_inputs_untouched():
 # ------------------------------------------------------------------------------------------------
 # 4. guard bands
 # ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('channels_last', [False, True], ids=['planar', 'channels_last'])
-def test_guard_bands(channels_last):
+@pytest.mark.parametrize('name,channels_last', [('tiles', False), ('tiles', True), ('tiles257', False), ('tiles257', True)],
+                         ids=['planar', 'channels_last', 'tiles257-planar', 'tiles257-channels_last'])
+def test_guard_bands(name, channels_last):
     """est, gt and mask carved out of NaN-filled buffers, out, box and the workspace out of sentinel-filled ones, through the C
-    ABI: the results are the plain call's (no NaN picked up), nothing outside out, box and the workspace is written."""
+    ABI: the results are the plain call's (no NaN picked up), nothing outside out, box and the workspace is written.  At
+    8203 x 13 the Tile records start 2 x 249 x 40 bytes into the workspace and there are 257 of them per view."""
     from rnr_amd import _lib
     L = _lib.load()
-    c = mr.case('tiles')
+    c = mr.case(name)
     N, _, H, W = c['est'].shape
     G = 64                                                   # guard elements on either side
     p = lambda t: ctypes.c_void_p(t.data_ptr())
@@ -179,7 +186,7 @@ def test_guard_bands(channels_last):
     _lib.check(L.rnr_image_metrics(p(e), p(g), p(m), 1 if channels_last else 0, 1.0, 1, p(out), p(box), p(ws), N, H, W,
                                    ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
     torch.cuda.synchronize()
-    mr.compare(out.cpu().numpy().reshape(N, 12), box.cpu().numpy().reshape(N, 5), c['ref'], c['box'], 'guarded')
+    mr.compare(out.cpu().numpy().reshape(N, 12), box.cpu().numpy().reshape(N, 5), c['ref'], c['box'], 'guarded %s' % name)
     plain, _ = _run(c['est'], c['gt'], c['mask'], channels_last)
     assert np.array_equal(_bits(out.cpu().numpy().reshape(N, 12)), _bits(plain))
     assert (out_buf[:G] == -12345.0).all() and (out_buf[G + N * 12:] == -12345.0).all()

@@ -1,6 +1,8 @@
 """-m gpu: rnr_amd.optim.Adam (csrc/optim.hip) — bit equality with the float32 restatement of tests/optim_ref.py (pinned against
 torch.optim.Adam on the CPU by tests/test_optim_cpu.py), the mirrors and batched packs of a bound step against a training plan
-built from scratch, no stale weights on any path, the whole chain training, rnr_pack_conv_weights against single packs.
+built from scratch, the mirror contract of include/rnr_hip.h through the C ABI on hand-built tables (partial ranges, misaligned
+destinations, negative strides, repeats, the scalar path) against optim_ref.apply_mirror, no stale weights on any path, the
+whole chain training, rnr_pack_conv_weights against single packs.
 Every comparison is torch.equal: IEEE operations in a fixed order without contraction leave nothing to a tolerance."""
 import ctypes
 
@@ -204,6 +206,83 @@ def test_bound_step_leaves_the_plan_as_a_fresh_one(num_down, bn_train):
     net(x, None)
     assert _train_plans(net) == [plan] and not calls, 'the next forward rebuilt or repacked the plan'
     del plan.repack
+
+
+def test_mirrors_through_the_c_abi():
+    """rnr_adam_tensor / rnr_adam_chunk / scalar tables built by hand (as Adam._build_batch and fill_mirror build them) for the
+    rows of optim_ref.mirror_rows, ONE rnr_adam_step: p, m, v bit-equal to the float32 restatement, every destination buffer
+    bit-equal, guards included, to optim_ref.apply_mirror on a sentinel-filled array (whose `count` asserts on the reference
+    side that no address is written twice).  A bound RenderingNet at nf0 = 4 reaches none of these: there every dimension-0
+    stride is a multiple of 4, every destination 16-byte aligned and no parameter at an odd storage offset."""
+    from rnr_amd import _lib
+    from rnr_amd._lib import ADAM_CHUNK, RnrAdamScalars, RnrAdamTensor
+    from rnr_amd.ops import _stream
+    from rnr_amd.optim import fill_mirror, step_scalars
+    G, SENT = optim_ref.GUARD, np.float32(-7777.0)
+    rng = np.random.default_rng(23)
+    rows = optim_ref.mirror_rows(ADAM_CHUNK)
+    tensors = (RnrAdamTensor * len(rows))()
+    slots, chunks, keep, want = {}, [], [], []
+
+    def stream_buffer(values, offset):
+        """`values` between guards of G sentinels, its first element `offset` elements off a 16-byte boundary."""
+        host = np.full(G + offset + values.size + G, SENT, np.float32)
+        host[G + offset:G + offset + values.size] = values
+        dev = torch.from_numpy(host).to(DEV)
+        assert dev.data_ptr() % 16 == 0
+        return host, dev, dev.data_ptr() + 4 * (G + offset)
+
+    for i, r in enumerate(rows):
+        n, h = r['n'], optim_ref.HYPER[r['group']]
+        p0, g = rng.standard_normal(n).astype(np.float32), _grad(rng, n)
+        m0 = (rng.standard_normal(n) * 0.1).astype(np.float32) if r['t'] > 1 else np.zeros(n, np.float32)
+        v0 = (rng.random(n) * 0.01).astype(np.float32) if r['t'] > 1 else np.zeros(n, np.float32)
+        p1, m1, v1 = optim_ref.adam_step(p0, g, m0, v0, r['t'], dtype=np.float32, **h)
+        e = tensors[i]
+        streams = []
+        for values, new in ((p0, p1), (g, g), (m0, m1), (v0, v1)):
+            host, dev, ptr = stream_buffer(values, r['p_offset'])
+            host[G + r['p_offset']:G + r['p_offset'] + n] = new
+            streams.append((host, dev))
+            keep.append(ptr)
+        e.p, e.g, e.m, e.v = keep[-4:]
+        assert (e.p % 16 != 0) == (r['p_offset'] % 4 != 0)
+        e.n = n
+        b1, b2 = h['betas']
+        e.b1, e.omb1, e.b2, e.omb2, e.eps, e.wd = b1, 1.0 - b1, b2, 1.0 - b2, h['eps'], h['weight_decay']
+        e.slot = slots.setdefault((r['group'], r['t']), len(slots))
+        e.shape[:] = r['shape']
+        e.num_mirrors = len(r['mirrors'])
+        dsts = []
+        for k, (desc, off, n_dst) in enumerate(r['mirrors']):
+            front, back = optim_ref.guards_for(desc, n_dst)
+            host = np.full(front + off + n_dst + back, SENT, np.float32)
+            dev = torch.from_numpy(host).to(DEV)
+            assert dev.data_ptr() % 16 == 0
+            fill_mirror(e.mirror[k], dict(desc, dst=dev[front + off:]))
+            count = np.zeros(host.size, np.int64)
+            optim_ref.apply_mirror(dict(desc, base=desc['base'] + front + off), p1, host, count)
+            assert count.max() == 1 and count[:front + off].sum() == 0 and count[front + off + n_dst:].sum() == 0, r['name']
+            dsts.append((host, dev))
+        want.append((r['name'], streams, dsts))
+        chunks += [(i, c) for c in range((n + ADAM_CHUNK - 1) // ADAM_CHUNK)]
+    assert len(slots) == 2 and any(optim_ref.HYPER[r['group']]['weight_decay'] != 0 for r in rows)
+    sc = (RnrAdamScalars * len(slots))()
+    for (group, t), s in slots.items():
+        h = optim_ref.HYPER[group]
+        sc[s].step_size, sc[s].bc2s = step_scalars(h['lr'], h['betas'][0], h['betas'][1], t)
+    table = torch.from_numpy(np.frombuffer(bytes(tensors), np.uint8).copy()).to(DEV)
+    chunk_table = torch.from_numpy(np.array(chunks, np.int32)).to(DEV)
+    _lib.check(_lib.load().rnr_adam_step(table.data_ptr(), len(rows), chunk_table.data_ptr(), len(chunks), sc, len(slots), _stream()))
+    torch.cuda.synchronize()
+    for name, streams, dsts in want:
+        for what, (host, dev) in zip('pgmv', streams):
+            assert np.array_equal(dev.cpu().numpy().view(np.int32), host.view(np.int32)), '%s: %s or its guards' % (name, what)
+        for k, (host, dev) in enumerate(dsts):
+            got = dev.cpu().numpy()
+            bad = np.flatnonzero(got.view(np.int32) != host.view(np.int32))
+            print('%-20s mirror %d: %d of %d elements stored, %d differ' % (name, k, int((host != SENT).sum()), host.size, bad.size))
+            assert bad.size == 0, '%s: mirror %d differs at %s' % (name, k, bad[:8])
 
 
 # ------------------------------------------------------------------------------------------------

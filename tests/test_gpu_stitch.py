@@ -200,15 +200,25 @@ def _alpha(H, W, seed):
     a[1, 0, W // 2], a[1, H - 1, W // 3], a[1, H // 2, 0], a[1, H // 3, W - 1] = 1.0, 0.5, 1e-30, 2.0   # each edge of the image
     a[1, H // 2, W // 2] = np.nan                                                                     # not covered
     a[2] = np.where(rng.rand(H, W) < 0.02, 1.0, np.where(rng.rand(H, W) < 0.1, -1.0, 0.0))           # negatives: not covered
+    ty, tx = (H + 31) // 32, (W + 31) // 32
+    if ty >= 3 and tx >= 3:         # the top-left corner of the middle 32 x 32 tile: at radius 32 its dilation reaches all eight
+        a[1, (ty // 2) * 32, (tx // 2) * 32] = 1.0                                                     # neighbouring tiles
     return a
 
 
-@pytest.mark.parametrize('hw', [(1, 1), (7, 5), (37, 53), (64, 64)])
+@pytest.mark.parametrize('hw', [(1, 1), (7, 5), (37, 53), (64, 64), (70, 130), (33, 97)])
 @pytest.mark.parametrize('radius', [0, 1, 8, 32])
 def test_background_mask(hw, radius):
+    """Tile grids of 1 x 1 and 2 x 2, and two whose sides differ, which the block -> (tile x, tile y, view) decode needs to be
+    told apart: 70 x 130 (3 x 5 tiles) and 33 x 97 (2 x 4, the last tile row one pixel high)."""
     from rnr_amd import ops
     H, W = hw
     a = _alpha(H, W, H * 100 + radius)
+    if hw == (70, 130) and radius == 32:
+        lone = np.zeros_like(a[1])
+        lone[32, 64] = 1.0
+        reach = sr.background_mask(lone[None], 32)[0] == 0
+        assert {(y // 32, x // 32) for y, x in np.argwhere(reach)} == {(i, j) for i in range(3) for j in (1, 2, 3)}
     out = Guarded((3, H, W), torch.uint8)
     ops.background_mask(T(a).to(DEV), radius, out=out.t)
     assert out.intact()
@@ -256,23 +266,34 @@ def ulp32(x):
     return np.spacing(np.abs(np.asarray(x, np.float32))).astype(np.float64)
 
 
-@pytest.mark.parametrize('mask_kind', ['full', 'single', 'random', 'empty'])
-@pytest.mark.parametrize('gamma', [1.0, 2.2])
-def test_probe_prepare(mask_kind, gamma):
+# 17 x 31 under its earlier ids; 257 x 256 texels are 257 workgroups of 256, the smallest probe at which prepare_mean_kernel's
+# loop over the workgroups' records runs a second pass, there also with the `tail` mask
+PREPARE_CASES = [pytest.param(g, k, (17, 31), id='%s-%s' % (g, k)) for k in ('full', 'single', 'random', 'empty') for g in (1.0, 2.2)]
+PREPARE_CASES += [pytest.param(g, k, (257, 256), id='%s-%s-257x256' % (g, k))
+                  for k in ('full', 'single', 'random', 'empty', 'tail') for g in (1.0, 2.2)]
+
+
+@pytest.mark.parametrize('gamma,mask_kind,size', PREPARE_CASES)
+def test_probe_prepare(mask_kind, gamma, size):
     """NaN -> 0; gamma = 1 leaves the bits; gamma = 2.2 within 1 float32 ulp of the float64 power (one rounding of a float64 pow
     that may itself be an ulp of float64 off); the fill within one float32 rounding of the float64 mean of the values the
-    kernel wrote inside the mask (half an ulp, plus n 2^-53 |mean| for the order of the float64 sum); an empty mask gives NaN."""
+    kernel wrote inside the mask (half an ulp, plus n 2^-53 |mean| for the order of the float64 sum); an empty mask gives NaN.
+    Mask kind `tail` covers the texels from 65536 on only: the fill is the mean of the last record alone."""
     from rnr_amd import ops
     from rnr_amd._lib import load
-    h, w = 17, 31
+    h, w = size
     rng = np.random.RandomState(3)
     lp = (rng.rand(h, w, 3) * 3).astype(np.float32)
     lp[rng.rand(h, w, 3) < 0.05] = np.nan
     lp[0, 0] = 0.0
     mask = {'full': np.ones((h, w), bool), 'single': np.zeros((h, w), bool), 'random': rng.rand(h, w) < 0.5,
-            'empty': np.zeros((h, w), bool)}[mask_kind]
+            'empty': np.zeros((h, w), bool), 'tail': np.arange(h * w).reshape(h, w) >= 65536}[mask_kind]
     if mask_kind == 'single':
         mask[5, 7] = True
+    if mask_kind == 'tail':
+        assert 0 < int(mask.sum()) <= 256
+    groups = -(-h * w // 256)               # a 32-byte record per workgroup behind the 32 bytes of the mean
+    assert load().rnr_probe_prepare_workspace_bytes(h, w) == 32 * groups + 32 and groups == (3 if size == (17, 31) else 257)
     out = Guarded((h, w, 3), torch.float32)
     ws = Guarded((load().rnr_probe_prepare_workspace_bytes(h, w) // 8,), torch.float64)
     src = T(lp).to(DEV)

@@ -150,3 +150,24 @@ def test_argument_errors_launch_nothing():
     assert L.rnr_masked_l1_loss_backward(p, p, p, -1, p, p, 1, 3, 10, 12, null) != 0
     assert L.rnr_rays_chrom_loss_workspace_bytes(16, 26, 512, 512) == 16 * 512 * 512 // 256 * 16
     assert L.rnr_masked_l1_loss_workspace_bytes(1, 11, 11) == 8 and L.rnr_masked_l1_loss_workspace_bytes(0, 11, 11) == 0
+
+
+def test_second_pass_shapes_have_257_workgroups():
+    """16 and 8 bytes of workspace per workgroup of 256 pixels: the shapes added for the second pass of the finalise loops
+    have at least 257, and the `tail` alpha lies wholly in the last one."""
+    from rnr_amd import _lib
+    L = _lib.load()
+    N, R, H, W = lr.CHROM_SHAPE_257
+    assert L.rnr_rays_chrom_loss_workspace_bytes(N, R, H, W) // 16 == 257 and lr.CHROM_SHAPE_257 in lr.CHROM_SHAPES
+    for name in ('partials257', 'partials257_crop'):
+        (n, c, h, w), b = lr.L1_CASES[name]
+        assert L.rnr_masked_l1_loss_workspace_bytes(n, h, w) // 8 >= 257, name
+    x, a, i = lr.chrom_case(lr.CHROM_SHAPE_257, 'tail', True)
+    flat = a.reshape(-1)
+    assert flat.numel() - lr.TAIL_START <= 256 and not bool(flat[:lr.TAIL_START].any()) and bool((flat[lr.TAIL_START:] > 0).all())
+    ref = lr.chrom(x, a, i)
+    assert ref['loss'] > 1e-3 and abs(ref['sum_alpha'] - float(flat.double().sum())) == 0
+    est, gt, al, b = lr.l1_case('partials257', 'tail')
+    loss, grad, count = lr.l1(est, gt, al, b)
+    assert b == 0 and loss > 0 and count == 2 * 3 * 130 * 253
+    assert float(grad.reshape(2, 3, -1)[0].abs().max()) == 0          # view 0 holds no tail pixel

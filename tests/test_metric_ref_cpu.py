@@ -97,6 +97,39 @@ def test_yardstick_edge_cases():
         assert np.isnan(r[:, 9:]).all() and np.isfinite(r[:, :9]).all()
 
 
+@pytest.mark.parametrize('name', sorted(mr.SECOND_PASS))
+def test_second_pass_cases_sit_on_their_thresholds(name):
+    """rnr_image_metrics_workspace_bytes(N, H, W) / N is 40 x bands + 16 x tiles: each second-pass case has the record counts
+    it is named for, and the data that decides its result lies where only the later pass reads it."""
+    from rnr_amd import _lib
+    L = _lib.load()
+    H, W, bands, tiles = mr.SECOND_PASS[name]
+    c = mr.case(name)
+    N = c['est'].shape[0]
+    assert c['est'].shape == (N, 3, H, W) and c['mask'].shape == (N, H, W) and N == 2
+    per_view = L.rnr_image_metrics_workspace_bytes(N, H, W) // N
+    assert L.rnr_image_metrics_workspace_bytes(N, H, W) % N == 0 and per_view == mr.BAND_BYTES * bands + mr.TILE_BYTES * tiles
+    band_rows = max(8, -(-H // 256))
+    assert -(-H // band_rows) == bands
+    assert tiles == -(-(H - 10) // 32) * -(-(W - 10) // 32)
+    ref, box = c['ref'], c['box']
+    if name == 'wide300':
+        assert W > 256 and box[0].tolist() == [260, 300, 0, 13, 13 * 40]             # view 0: the second x pass alone
+        assert box[1, 0] < 256 < box[1, 1] and np.isfinite(ref).all()
+    elif name == 'bands256':
+        assert bands == 256 and band_rows == 8 and box[1, 2:4].tolist() == [2040, 2048]  # view 1: the 256th band alone
+        assert np.isnan(ref[1, 10:]).all() and np.isfinite(ref[1, :10]).all() and np.isfinite(ref[0]).all()
+    elif name == 'bands9':
+        assert band_rows == 9 and H - (bands - 1) * band_rows == 6                   # the last band is short
+        assert box[0].tolist() == [0, 12, 2040, 2049, 9 * 12]                        # a box 9 high: no window
+        assert np.isnan(ref[0, 10:]).all() and np.isfinite(ref[0, :10]).all() and np.isfinite(ref[1]).all()
+        assert box[1].tolist() == [0, 12, 0, 2049, 2049 * 12]
+    else:
+        assert tiles == 257 and band_rows == 33 and (H - 10) - 256 * 32 == 1         # the 257th tile: one row of windows
+        assert box[1, 2:4].tolist() == [8100, 8203] and box[1, 2] // 32 == 253        # in-box windows: tiles 253..256 alone
+        assert np.isfinite(ref).all()
+
+
 def test_dropin_signatures_equal_the_references():
     """Parameter names, order and defaults of psnr, compute_err_metrics, compute_err_metrics_batch as recorded from the reference."""
     import metric

@@ -117,6 +117,46 @@ def test_vector_mirror_repeats_rows():
     assert np.array_equal(dst.reshape(3, 16), want) and count.sum() == 15 and count.max() == 1
 
 
+def test_rows_of_the_c_abi_mirror_test():
+    """optim_ref.mirror_rows, which tests/test_gpu_optim.py sends through rnr_adam_step: every descriptor stays inside its
+    destination and writes no address twice, the guards hold what a kernel that ignored a range would address, and the rows
+    have the properties they are there for (restated from csrc/optim.hip: a mirror is `linear` when it has the parameter's own
+    contiguous strides, its range on dimension 0 and no repeat)."""
+    from rnr_amd._lib import ADAM_CHUNK, ADAM_MAX_MIRRORS
+    rows = {r['name']: r for r in optim_ref.mirror_rows(ADAM_CHUNK)}
+
+    def linear(d):
+        s = d['shape']
+        return d['dim'] == 0 and d['repeat'] == 1 and tuple(d['stride']) == (s[1] * s[2] * s[3], s[2] * s[3], s[3], 1)
+
+    for r in rows.values():
+        assert 1 <= len(r['mirrors']) <= ADAM_MAX_MIRRORS and r['n'] == int(np.prod(r['shape']))
+        for desc, off, n_dst in r['mirrors']:
+            assert tuple(desc['shape']) == r['shape']
+            front, back = optim_ref.guards_for(desc, n_dst)
+            assert front % 4 == 0 and front >= optim_ref.GUARD and back >= optim_ref.GUARD
+            dst, count = np.zeros(n_dst, np.float32), np.zeros(n_dst, np.int64)
+            optim_ref.apply_mirror(desc, np.arange(r['n'], dtype=np.float32), dst, count)      # asserts the addresses
+            assert count.max() == 1 and count.sum() > 0, r['name']
+            below, above = optim_ref.mirror_extent(desc, n_dst)
+            assert below <= front and above <= back
+    kinds = lambda name: [linear(d) for d, _, _ in rows[name]['mirrors']]
+    assert kinds('identity') == [True] and rows['identity']['n'] % ADAM_CHUNK == 6 and rows['identity']['n'] > 2 * ADAM_CHUNK
+    assert kinds('identity_misaligned') == [True] and rows['identity_misaligned']['mirrors'][0][1] % 4 != 0
+    for name, lo_straddles in (('range', False), ('range_both_ends', True)):
+        d = rows[name]['mirrors'][0][0]
+        assert kinds(name) == [True] and d['stride'][0] == 6 and d['base'] % 4 == 0
+        assert (d['lo'] * 6 % 4 != 0) == lo_straddles and d['hi'] * 6 % 4 != 0 and d['hi'] < 7
+    assert kinds('flip3x3') == [False, False] and rows['flip3x3']['n'] == 4320 > ADAM_CHUNK
+    assert all(min(d['stride']) < 0 for d, _, _ in rows['flip3x3']['mirrors'])
+    assert kinds('split4x4') == [False, False] and kinds('split4x4_transposed') == [True, True]
+    assert kinds('repeat') == [False] and rows['repeat']['mirrors'][0][0]['repeat'] == 3 and rows['repeat']['n'] % 4 == 1
+    assert kinds('three_kinds') == [True, True, False]
+    assert kinds('scalar_path') == [True, False, False] and rows['scalar_path']['p_offset'] % 4 != 0
+    assert all(r['p_offset'] == 0 for n, r in rows.items() if n != 'scalar_path')
+    assert {(r['group'], r['t']) for r in rows.values()} == {(0, 1), (1, 3)} and optim_ref.HYPER[1]['weight_decay'] != 0
+
+
 # ------------------------------------------------------------------------------------------------
 # symbols
 # ------------------------------------------------------------------------------------------------
