@@ -11,6 +11,10 @@ generator of inputs whose convolution is EXACT in float32.
                    divides by 2 and 4) and the bf16x6 / f16x3 operand splits (small dyadic operands sit entirely in the leading
                    term; the f16x3 weight prescale is a power of two) give the same float32 bits: a kernel is compared with
                    conv64(...).float() BITWISE, which no tolerance-based test can do
+  magnitude64      A = conv64 of |input| and |weight|: the per-element scale a rounding error of the convolution is measured in
+  wino4_f32        float32 numpy EMULATION of Winograd F(4x4, 3x3) on the points (0, +-3/4, +-3/2, inf), restated from the
+                   Cook-Toom construction: what float32 arithmetic alone costs that algorithm — the yardstick of the
+                   per-element bound tests/test_gpu_conv_exact_sweep.py holds the F(4x4, 3x3) kernels to
   nan_must / nan_may   where ONE non-finite input pixel must / may surface in out_raw (rnr_hip.h, "Non-finite inputs"): boolean
                    maps from integer index arithmetic alone (tests/test_conv_guard_cpu.py pins them to brute-force loops)
 tests/test_conv_mask_cpu.py pins conv64 to a four-loop numpy convolution, tile_mask64 to a hand-written example and the
@@ -90,6 +94,88 @@ def exact_conv_case(rng, kind, N, H, W, cins, c_out):
     shape = (cin, c_out, 4, 4) if kind == 2 else (c_out, cin, 3 if kind == 0 else 4, 3 if kind == 0 else 4)
     weight = torch.from_numpy((rng.integers(-2, 3, size=shape) * 0.125).astype(np.float32))
     return srcs, weight
+
+
+def magnitude64(kind, srcs, weight):
+    """A [N, c_out, Ho, Wo] float64 = conv64 of |conv_input(srcs)| with |weight|: sum over taps and channels of |x| |w|, the
+    scale of every term a kernel adds up for that output.  A == 0 means every product of the output is zero."""
+    return conv64(kind, [(conv_input(srcs).abs(), None, None, ACT_NONE)], weight.abs())
+
+
+# ---- float32 emulation of Winograd F(4x4, 3x3) ----
+W4_POINTS = ('0', '3/4', '-3/4', '3/2', '-3/2')     # + infinity
+
+
+def cook_toom(points, m, r):
+    """Cook-Toom matrices of F(m, r) on the n - 1 = m + r - 2 finite `points` plus infinity, in exact rationals, returned as
+    float64 arrays AT [m, n], G [n, r], BT [n, n]:  y = AT ((G g) * (BT d)) is the correlation y_i = sum_k d_{i+k} g_k.
+      G[j]  = (1, p_j, .., p_j^(r-1)) / prod_{k != j} (p_j - p_k)       (the Lagrange denominators live in the weights),
+      BT[j] = coefficients of M(x) / (x - p_j), M(x) = prod_k (x - p_k) (monic);  AT[i][j] = p_j^i;
+    the row of infinity: G = (0, .., 0, 1), BT = coefficients of M(x), AT = (0, .., 0, 1)."""
+    from fractions import Fraction as Fr
+    n = m + r - 1
+    pts = [Fr(p) for p in points]
+    assert len(pts) == n - 1 and len(set(pts)) == n - 1
+
+    def times_x_minus(q, p):                    # q(x) * (x - p), coefficients ascending
+        out = [Fr(0)] * (len(q) + 1)
+        for i, c in enumerate(q):
+            out[i] -= p * c
+            out[i + 1] += c
+        return out
+
+    def product(skip):
+        q = [Fr(1)]
+        for k, p in enumerate(pts):
+            if k != skip:
+                q = times_x_minus(q, p)
+        return q + [Fr(0)] * (n - len(q))
+
+    AT = [[pts[j] ** i for j in range(n - 1)] + [Fr(int(i == m - 1))] for i in range(m)]
+    G, BT = [], []
+    for j, p in enumerate(pts):
+        den = Fr(1)
+        for k, q in enumerate(pts):
+            if k != j:
+                den *= p - q
+        G.append([p ** i / den for i in range(r)])
+        BT.append(product(j))
+    G.append([Fr(0)] * (r - 1) + [Fr(1)])
+    BT.append(product(None))
+    f = lambda rows: np.array([[float(v) for v in row] for row in rows], np.float64)
+    return f(AT), f(G), f(BT)
+
+
+def wino4_f32(x, weight, chunk=2):
+    """Winograd F(4x4, 3x3) of the 3x3 convolution under ReflectionPad2d(1) in FLOAT32: x [N,C,H,W] float32 (conv_input;
+    H, W multiples of 4), weight [K,C,3,3] -> float32 [N,K,H,W].  U = G g G^T is computed in float64 and rounded once; the
+    input transform B^T d B, the products, the accumulation over channels (`chunk` channels per step, the steps added in
+    sequence) and the output transform A^T M A run in float32, one matrix product at a time.  B^T and A^T are multiples of 2^-6
+    and exact in float32."""
+    x = np.ascontiguousarray(torch.as_tensor(x).numpy(), np.float32)
+    g = torch.as_tensor(weight).numpy().astype(np.float64)
+    N, C, H, W = x.shape
+    K = g.shape[0]
+    assert H % 4 == 0 and W % 4 == 0 and g.shape[1:] == (C, 3, 3)
+    AT, G, BT = cook_toom(W4_POINTS, 4, 3)
+    AT32, BT32 = AT.astype(np.float32), BT.astype(np.float32)
+    assert (AT32 == AT).all() and (BT32 == BT).all()
+    U = np.einsum('ia,kcab,jb->ijck', G, g, G).astype(np.float32).reshape(36, C, K)
+    ty, tx = H // 4, W // 4
+    xp = np.pad(x, ((0, 0), (0, 0), (1, 1), (1, 1)), mode='reflect')
+    iy = 4 * np.arange(ty)[:, None] + np.arange(6)[None]
+    ix = 4 * np.arange(tx)[:, None] + np.arange(6)[None]
+    d = xp[:, :, iy][:, :, :, :, ix]                                        # [N, C, ty, 6, tx, 6]
+    V = np.einsum('ia,ncyaxb->ncyixb', BT32, d, dtype=np.float32)
+    V = np.einsum('jb,ncyixb->ijnyxc', BT32, V, dtype=np.float32)           # [6, 6, N, ty, tx, C]
+    V = np.ascontiguousarray(V).reshape(36, N * ty * tx, C)
+    M = np.zeros((36, N * ty * tx, K), np.float32)
+    for c in range(0, C, chunk):
+        M += np.matmul(V[:, :, c:c + chunk], U[:, c:c + chunk, :])
+    M = M.reshape(6, 6, N, ty, tx, K)
+    Y = np.einsum('ai,ijnyxk->ajnyxk', AT32, M, dtype=np.float32)
+    Y = np.einsum('bj,ajnyxk->nkyaxb', AT32, Y, dtype=np.float32)           # [N, K, ty, 4, tx, 4]
+    return torch.from_numpy(np.ascontiguousarray(Y).reshape(N, K, H, W))
 
 
 # ---- the footprint of one non-finite input pixel (include/rnr_hip.h, "Non-finite inputs") ----

@@ -5,7 +5,8 @@ descriptors without bounds, so an index slip neither faults nor — next to fres
                     of a sentinel-filled allocation of its own at the weakest alignment the header grants, out_raw / workspace /
                     the packed weight prefilled with the sentinel NaN: guards intact, output finite and BITWISE the unguarded
                     run's, statistics / scale / shift at the bound of test_conv_fused_equals_separate_launches, sync zero.  No
-                    float64 reference: the values are bounded elsewhere.
+                    float64 reference here: tests/test_gpu_conv_exact_sweep.py compares the values of every one of these cases
+                    with a float64 convolution, bit for bit (the F(4x4, 3x3) rows: within a per-element bound).
   (b) NaN tracer    one NaN in `raw`: it must surface in every output whose window contains it and may surface only where
                     rnr_hip.h ("Non-finite inputs") allows for the algorithm that runs — a pure index property, the sharpest
                     probe of halo staging, reflection and tile decode; everything outside is bitwise the clean run.
