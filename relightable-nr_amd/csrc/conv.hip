@@ -166,9 +166,10 @@ constexpr int STAT_SHARDS = 8;  // one per XCD: at one view per call every workg
 // private 4 MiB L2.  Give every XCD a contiguous run of logical tiles so that vertically adjacent pixel tiles (which
 // share their 3x3 halo rows) and the column tiles of one pixel tile (which share the whole A operand) meet in the same
 // L2.  Bijective for any tile count (cdna_hip_programming.md, "XCD swizzle must be bijective").
-__device__ __forceinline__ void tile_coords(const ConvParams& P, int& mt, int& nt, int& z) {
+// block_coords: the tile of an arbitrary linear block id b < total (the next-tile touch asks for a successor's: conv_tile_of_block);
+// tile_coords: this workgroup's.
+__device__ __forceinline__ void block_coords(const ConvParams& P, int b, int& mt, int& nt, int& z) {
     const int total = P.mtiles * P.ntiles * P.zdim;
-    const int b = blockIdx.x;
     const int q = total >> 3, r = total & 7;
     const int xcd = b & 7, idx = b >> 3;
     const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
@@ -183,6 +184,7 @@ __device__ __forceinline__ void tile_coords(const ConvParams& P, int& mt, int& n
         z = t / P.mtiles;
     }
 }
+__device__ __forceinline__ void tile_coords(const ConvParams& P, int& mt, int& nt, int& z) { block_coords(P, (int)blockIdx.x, mt, nt, z); }
 
 #include "conv_stage.inc"
 

@@ -56,6 +56,47 @@ __device__ __forceinline__ ConvTileId conv_tile(const ConvParams& P) {
     T.c_begin = r.begin; T.c_end = r.end;
     return T;
 }
+// The tile of linear block `b` (< mtiles * ntiles * zdim), decoded as that block will decode its own: parity class and origin; no
+// chunk range (the kernels that ask have no split-K form).  For the next-tile touch of the one-workgroup-per-CU kernels.
+template <int TW, int TH, bool PARITY_IN_Z>
+__device__ __forceinline__ ConvTileId conv_tile_of_block(const ConvParams& P, int b) {
+    ConvTileId T;
+    block_coords(P, b, T.mt, T.nt, T.z);
+    T.par = PARITY_IN_Z ? (T.z & 3) : 0;
+    T.split = PARITY_IN_Z ? (T.z >> 2) : T.z;
+    T.py = T.par >> 1; T.px = T.par & 1;
+    tile_origin<TW, TH>(P, T.mt, T.n, T.y0, T.x0);
+    T.c_begin = T.c_end = 0;
+    return T;
+}
+// What the next-tile touch reads of the parameter block — the grid, the tile order, the map and source 0 — fetched again from the
+// kernel-argument segment (the block is the kernels' only argument: offset 0), everything else zero.  The touch sits behind a K
+// loop that has no register to spare: held in SGPRs from the kernel's start these fields cost conv_wino80f4_kernel 116 bytes of
+// scratch and conv_wino42p_kernel 20 SGPR spill moves, some of them inside the K loop; the volatile reads are issued where the
+// touch runs and the K loops keep their allocation (profiles/r10_tile_touch_ab.txt (1)).
+__device__ __forceinline__ ConvParams touch_params() {
+    typedef const volatile __attribute__((address_space(4))) ConvParams* KernArg;
+    KernArg A = (KernArg)__builtin_amdgcn_kernarg_segment_ptr();
+    ConvParams Q = {};
+    Q.mtiles = A->mtiles; Q.ntiles = A->ntiles; Q.zdim = A->zdim; Q.par_inner = A->par_inner;
+    Q.H = A->H; Q.W = A->W; Q.Ho = A->Ho; Q.Wo = A->Wo;
+    Q.src_c[0] = A->src_c[0]; Q.src_data[0] = A->src_data[0];
+    return Q;
+}
+// Next-tile touch (conv_wino4.inc, "Next-tile prefetch"): TOUCH dwords of pixel `pixel` (index inside view n) of source 0, 128
+// bytes apart from the first chunk's channel offset, clamped to the pixel's last dword.  The resource covers exactly the view
+// (plan_conv keeps H * W * C below 2^30), so the hardware drops an offset outside it instead of faulting; the values are never
+// used and the caller pins pf[] to the kernel's end.
+template <int TOUCH>
+__device__ __forceinline__ void touch_pixel(const ConvParams& P, int n, unsigned pixel, unsigned (&pf)[TOUCH]) {
+    const unsigned C = (unsigned)P.src_c[0];
+    const unsigned view = (unsigned)(P.H * P.W) * C;            // floats per view
+    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.src_data[0] + (size_t)n * view), 0,
+                                                                        (int)(view * 4u), 0x27000);
+#pragma unroll
+    for (int j = 0; j < TOUCH; j++)
+        pf[j] = __builtin_amdgcn_raw_buffer_load_b32(r, (int)(pixel * C * 4u + min(128u * j, C * 4u - 4u)), 0, 0);
+}
 
 // ---- which source and channel chunk feeds this K step ----
 // K step = chunk * NPH + input parity phase (NPH = 4 for the 4x4 stride-2 convolution, else 1).  The chunk selects the source

@@ -1,6 +1,7 @@
 // The body of the two F(4x4, 2x2) kernels, conv_wino42p_kernel (conv_wino42p.inc) and conv_wino42s_kernel (conv_wino42s.inc):
 // included inside the kernel behind `typedef W42Kind<KIND> K;` (text, not a function: a wrapper changed the register allocation
-// of conv_wino42p_kernel).  Mapping, staging scheme and epilogue are described in conv_wino42p.inc.
+// of conv_wino42p_kernel).  Mapping, wave placement (W42_ROLE_SIMD), staging scheme and epilogue are described in conv_wino42p.inc;
+// the next-tile touch behind the K loop (K::PREFETCH, off in both kernels) below.
     constexpr int STEP_FLOATS = K::NSETS * W42_WAVE_FLOATS;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* As = smem;                       // [2][W42_CHUNK]; the epilogue's exchange buffers afterwards
@@ -8,7 +9,14 @@
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#if W42_ROLE_SIMD
+    // waves land on SIMD wave % 4: SIMDs 0 / 1 carry the full-row wave, the column wave and row wave 0 of half 0 / 1 (13 MFMAs per K
+    // step, two staging waves), SIMDs 2 / 3 the row waves 1 - 3 of half 0 / 1 (12 MFMAs, three staging waves)
+    const int nbh = wave & 1;                               // column half
+    const int wr = (wave & 2) ? (wave >> 2) + 1 : (wave < 4 ? 4 : (wave < 8 ? 5 : 0));     // role: 0..3 row wave xi = r + 1, 4 full-row wave xi = 0, 5 column wave
+#else
     const int nbh = wave / 6, wr = wave - 6 * nbh;          // column half, role: 0..3 row wave xi = r + 1, 4 full-row wave xi = 0, 5 column wave
+#endif
     const bool colw = wr == 5;
     const int xi = wr < 4 ? wr + 1 : (colw ? 1 : 0);         // plane row (the column wave: its first)
     const int fid = colw ? 5 : xi;                          // place in the epilogue's exchange: plane row, or 5
@@ -19,7 +27,11 @@
     const int n = T.n, y0 = T.y0, x0 = T.x0;
 
     // staging item of this thread: (tile row sty, staged column shx, channel quad q); the row waves' threads take them in order
+#if W42_ROLE_SIMD
+    const int sidx = (wave - (wave > 5 ? 2 : 0)) * 64 + lane;      // the column waves are waves 4 and 5
+#else
     const int sidx = (wave - (wave > 5 ? 1 : 0)) * 64 + lane;
+#endif
     const int q = sidx & 3;
     const bool stager = !colw && sidx < W42_ITEMS;
     const int sit = stager ? sidx >> 2 : 0;
@@ -202,6 +214,24 @@
     else if (wr == 4) k_loop(std::integral_constant<int, 1>{});
     else k_loop(std::integral_constant<int, 0>{});
 
+    // Next-tile touch (r10, conv_wino4_kernel's of r05).  One workgroup per CU: the first staged image of a tile is a cold read that
+    // every CU asks for at the same moment, right behind the previous round's output stores.  The workgroup that holds the CU before
+    // — block b - K::PREFETCH: blocks are handed out in order and block_coords gives an XCD consecutive ids, so it ran on the same XCD
+    // = the same L2 — touches that image here, directly behind its K loop, so that the epilogue's LDS rounds cover the returns: one
+    // pixel per thread (17 x 33 of the 768), W42_PF_TOUCH dwords of source 0's first chunk(s) each.  The successor's tile, view, class
+    // and origin come from the decode it will run itself (conv_tile_of_block), par_inner order included.  The values are never used;
+    // the registers stay pinned until the kernel ends so that a late return cannot land in a register given to something else.
+    unsigned pf[W42_PF_TOUCH] = {};
+    if constexpr (K::PREFETCH > 0) {
+        const int b2 = (int)blockIdx.x + K::PREFETCH;
+        const ConvParams Q = touch_params();
+        if (b2 < Q.mtiles * Q.ntiles * Q.zdim && tid < W42_PF_ROWS * W42_COLS) {
+            const ConvTileId T2 = conv_tile_of_block<W42_PW, W42_PH, K::PARITY_IN_Z>(Q, b2);
+            const int hy = tid / W42_COLS, hx = tid - hy * W42_COLS;
+            touch_pixel(Q, T2.n, K::first_image_pixel(Q, T2, hy, hx), pf);
+        }
+    }
+
     // ---- epilogue: Y = A^T M A per (tile, column), statistics, BatchNorm arrival, stores ----
     // C layout of a 32 x 32 block: column = lane % 32, row (= tile) = (g & 3) + 8 (g >> 2) + 4 h: tile row g >> 2, tile column
     // (g & 3) + 4 h.  The column wave hands plane (xi, 4) to row wave xi = 1..4
@@ -282,8 +312,8 @@
         s1 += __shfl_xor(s1, 32, 64);
         s2 += __shfl_xor(s2, 32, 64);
         if (h == 0) {
-            red[(wave * 32 + l31) * 2 + 0] = s1;
-            red[(wave * 32 + l31) * 2 + 1] = s2;
+            red[((6 * nbh + wr) * 32 + l31) * 2 + 0] = s1;      // slot: half, role (the sums' order does not depend on the placement)
+            red[((6 * nbh + wr) * 32 + l31) * 2 + 1] = s2;
         }
         // the six waves of column half tid >> 5
         W4Stats::publish<W42_BN>(P, red, n, nt_ * W42_BN, tid, [tid](int j) { return (tid >> 5) * 6 + j; });
@@ -308,3 +338,7 @@
         }
     }
     if (bn) bn_complete(P, arr, n, tid, W4Stats::flag(red));
+    if constexpr (K::PREFETCH > 0) {
+#pragma unroll
+        for (int j = 0; j < W42_PF_TOUCH; j++) asm volatile("" :: "v"(pf[j]));
+    }

@@ -13,15 +13,19 @@
 //
 // Mapping.  A workgroup is 12 waves, three per SIMD, one workgroup per CU, and ALL TWELVE ISSUE MFMAs.  It owns 32 x 16
 // positions of ONE parity class (= input pixels) = 32 tiles (8 x 4) of 4 x 4 outputs x 64 output columns: 25 planes (xi, nu) x 2
-// column halves = 50 accumulator blocks of 32 x 32.  Wave w = 6 half + r:
+// column halves = 50 accumulator blocks of 32 x 32.  The six roles r of a half:
 //   r = 0..3  "row wave" xi = r + 1:  planes (xi, nu = 0..3) of its half — 4 blocks, 64 accumulator registers;
 //   r = 4     "full-row wave" xi = 0: planes (0, nu = 0..4)            — 5 blocks, 80 accumulator registers;
 //   r = 5     "column wave":          planes (xi = 1..4, nu = 4)       — 4 blocks, 64 accumulator registers.
 // Ten waves x 4 + two waves x 5 = 50.  A wave whose planes share xi needs ONE row segment per K step and the column wave four,
 // so the plane row that keeps its fifth plane is the price of one light wave more, and the column wave holds four blocks, not
-// five.  Waves go to SIMD w % 4: each SIMD carries two row waves and one of the four special waves — 13 / 12 / 13 / 12 MFMAs
-// per K step, the 13 on the SIMDs of the (light) full-row waves, the 12 on those of the (heavy) column waves (the first form
-// of the kernel: 15 / 15 / 10 / 10).
+// five.  Which wave takes which role (W42_ROLE_SIMD, r10; the roles, their accumulators, weight offsets and epilogue places do
+// not depend on it, so the output is bit-identical).  Waves go to SIMD w % 4.  Until r09, w = 6 half + r: each SIMD carried two
+// row waves and one special wave — 13 / 12 / 13 / 12 MFMAs per K step, but THREE staging waves beside every full-row wave and two
+// beside every column wave, and the barrier at the end of a chunk paces all four SIMDs by the slowest.  Now half = w & 1 and SIMD
+// 0 / 1 carry the full-row wave (w = 0 / 1), the column wave (4 / 5) and row wave 0 (8 / 9) of half 0 / 1 — 13 MFMAs and TWO
+// staging waves — and SIMD 2 / 3 the row waves 1 - 3 (w = 2, 6, 10 / 3, 7, 11) — 12 MFMAs and three staging waves: -1.7 ... -3.1 %
+// on every layer of both kernels (profiles/r10_tile_touch_ab.txt (3); the first form of the kernel: 15 / 15 / 10 / 10 MFMAs).
 //   * staging (no dedicated waves): as in conv_wino4_kernel the VERTICAL half of the input transform happens on the way into
 //     LDS.  An item (tile row, column, channel quad) loads the five input rows 4 ty + py - 1 .. + 3 of its column (zero outside
 //     the map, the producer's BatchNorm + activation applied), runs B^T down the column and stores T[xi]: image
@@ -78,6 +82,34 @@ constexpr int W42_XCHG = 10 * 14 * 64 * 2;          // floats of one exchange ro
 #ifndef W42_SGB_ST
 #define W42_SGB_ST 14               // ... in the K steps that also stage one channel of the next chunk
 #endif
+// Next-tile touch (r10; conv_wino4_kernel's W4_PREFETCH / W4_PF_TOUCH, described in conv_wino42_body.inc).  > 0: behind the K loop
+// a workgroup touches the first staged image of block + PREFETCH's tile; 0: off, and the kernel is the one without the code.
+// One macro per kernel, because each kernel's default is what its own check decided (profiles/r10_tile_touch_ab.txt (1), (2)); both
+// are OFF:
+//   conv_wino42p_kernel keeps its registers with the touch (145 VGPRs, 96 SGPRs, no scratch) and misses its layer gate: the four
+//     layers -0.03 % in sum with L14 / L16 not faster under the old wave placement, +0.1 ... +8 % under W42_ROLE_SIMD 1 (the
+//     classes of a pixel tile already share their input through L2, DESIGN 3.3);
+//   conv_wino42s_kernel fails the register check: 143 -> 147 VGPRs in its K loop and its 99 SGPRs at the cap of 100 in every form
+//     tried (parameters held or re-read, 1 or 2 dwords, lane index recomputed, block id carried through LDS), and that build
+//     measured 0 ... +1.7 % on L3 - L9.
+#ifndef W42_PREFETCH
+#define W42_PREFETCH 0              // both kernels' at once (an A/B build: -DW42_PREFETCH=256)
+#endif
+#ifndef W42P_PREFETCH
+#define W42P_PREFETCH W42_PREFETCH
+#endif
+#ifndef W42S_PREFETCH
+#define W42S_PREFETCH W42_PREFETCH
+#endif
+#ifndef W42_PF_TOUCH
+#define W42_PF_TOUCH 2              // dwords touched per pixel, 128 bytes apart
+#endif
+#ifndef W42_ROLE_SIMD
+#define W42_ROLE_SIMD 1             // 1: a half's full-row and column wave share a SIMD (r10: -1.7 ... -3.1 % on every layer of both kernels,
+                                    // profiles/r10_tile_touch_ab.txt (3)); 0: wave = 6 half + role, the placement of r07 - r09
+#endif
+constexpr int W42_PF_ROWS = W42_PH + 1;             // rows of a staged image: 17 x W42_COLS pixels, one per thread
+static_assert(W42_PF_ROWS * W42_COLS <= W42_THREADS, "one touched pixel per thread");
 static_assert(W42_ITEMS <= 10 * 64, "one staging item per thread of the row waves");
 static_assert(2 * W42_CHUNK >= W42_XCHG && 2 * W42_CHUNK >= W42_XM4, "the exchange buffers of the epilogue live in the T buffers");
 static_assert(W42_CHUNK < (1 << 14), "the staging destination is packed into 14 bits");
@@ -141,6 +173,12 @@ template <> struct W42Kind<2> {
         if (r == 4) return (flags & (1u << 15)) ? spix1 + 2u * (unsigned)P.W : spix1 + 3u * (unsigned)P.W;
         return spix1 + (unsigned)((r - 1) * P.W);
     }
+    // pixel (hy < 17, hx < 33) of the input pixels tile T stages per chunk, clamped to the map as item() / pixel() clamp them
+    static __device__ __forceinline__ unsigned first_image_pixel(const ConvParams& P, const ConvTileId& T, int hy, int hx) {
+        const int iy = min(max(T.y0 + T.py - 1 + hy, 0), P.H - 1), ix = min(max(T.x0 + T.px - 1 + hx, 0), P.W - 1);
+        return (unsigned)(iy * P.W + ix);
+    }
+    static constexpr int PREFETCH = W42P_PREFETCH;
 };
 
 __global__ void __launch_bounds__(W42_THREADS)

@@ -50,6 +50,11 @@ template <> struct W42Kind<1> {
         if (cs.phy) return r == 0 ? ((flags & (1u << 14)) ? p + W : p - W) : p + (unsigned)(2 * r - 1) * W;
         return r == 4 ? ((flags & (1u << 15)) ? p + 6u * W : p + 8u * W) : p + (unsigned)(2 * r) * W;
     }
+    // pixel (hy < 17, hx < 33) of phase image 0 of tile T, the first image it stages: D_0[y0 + hy][x0 + hx]
+    static __device__ __forceinline__ unsigned first_image_pixel(const ConvParams& P, const ConvTileId& T, int hy, int hx) {
+        return (unsigned)(reflect1(2 * (T.y0 + hy), P.H) * P.W + reflect1(2 * (T.x0 + hx), P.W));
+    }
+    static constexpr int PREFETCH = W42S_PREFETCH;
 };
 
 __global__ void __launch_bounds__(W42_THREADS)

@@ -46,6 +46,14 @@
 // slots of columns 64 - 79; BatchNorm arrival / finalise as everywhere.  Columns >= c_out are zero because their weights are.
 // Pixel tiles whose tile_mask is 0 are skipped (rnr_conv2d_masked).
 // LDS: 2 x 50.3 KB of T images + 8 KB BatchNorm table + 5 KB statistics scratch = 114 KB of 160.
+// Next-tile touch (r10, W8F_PREFETCH / W8F_PF_TOUCH; conv_wino4_kernel's of r05).  With 42 us per tile and one workgroup per CU the
+// cold first halo image is a large part of what a tile cannot hide.  Directly behind its K loop — the weight ring and the staging
+// registers are dead, the epilogue's LDS rounds cover the returns — workgroup b touches the 18 x 18 halo pixels of block b + 256's
+// tile, one pixel per thread, two dwords 128 bytes apart of source 0; block_coords gives that block's tile as it will decode it
+// itself (same XCD, same L2, very likely this CU).  What the touch reads of the parameter block it fetches again from the kernel
+// arguments (touch_params, conv_stage.inc): held in SGPRs across the K loop the fields cost 116 bytes of scratch at this kernel's
+// 168 VGPRs; re-read, the kernel keeps 168 VGPRs, 87 SGPRs, no scratch, and its MFMA / LDS counts, with two more VMEM instructions.
+// L22 -2.5 ... -2.8 % at 16 views, -1 % at one; one dword per pixel -2.3 ... -2.5 % (profiles/r10_tile_touch_ab.txt (2) - (4)).
 
 constexpr int W8F_THREADS = 768;
 constexpr int W8F_PW = 16, W8F_PH = 16;             // output pixels per workgroup tile (4 x 4 tiles of 4 x 4)
@@ -67,7 +75,14 @@ constexpr int W8F_BRING = W8F_BDIST == 1 ? 2 : 4;
 #ifndef W8F_SGB_ST
 #define W8F_SGB_ST 3                // ... in the K steps that also stage one channel of the next chunk
 #endif
-constexpr int W8F_WAVE_FLOATS = 64 * 15;            // weight floats of a wave per K step
+#ifndef W8F_PREFETCH
+#define W8F_PREFETCH 256            // > 0: behind the K loop a workgroup touches the halo of block + W8F_PREFETCH's tile (W4_PREFETCH); 0: off
+#endif
+#ifndef W8F_PF_TOUCH
+#define W8F_PF_TOUCH 2              // dwords touched per halo pixel, 128 bytes apart (profiles/r10_tile_touch_ab.txt)
+#endif
+static_assert(W8F_HW * W8F_HW <= W8F_THREADS, "one touched pixel per thread");
+constexpr int W8F_WAVE_FLOATS = 64 * 15;           // weight floats of a wave per K step
 constexpr int W8F_STEP_FLOATS = 12 * W8F_WAVE_FLOATS;       // weight image per K step: 36 planes x 4 channels x 80 columns
 constexpr int W8F_XHALF = 12 * 15 * 64 * 2;         // floats of the nu-half swap: [wave][nu'][block][lane][2 registers]
 constexpr int W8F_XCHG = 12 * 9 * 64 * 2;           // floats of one exchange round: [wave][<= 9 items it does not finish][lane][2]
@@ -269,6 +284,23 @@ conv_wino80f4_kernel(const ConvParams P) {
     else if (stager) k_loop(std::true_type{}, std::integral_constant<int, 1>{});
     else k_loop(std::false_type{}, std::integral_constant<int, 1>{});
 
+#if W8F_PREFETCH
+    // Next-tile touch (r10; conv_wino4_kernel's of r05, the reasoning in conv_wino4.inc): behind its K loop a workgroup touches the 18 x 18
+    // halo pixels of block + W8F_PREFETCH's tile — the workgroup that gets this CU next, on the same XCD's L2 — one pixel per thread,
+    // W8F_PF_TOUCH dwords of source 0's first chunk(s) each, reflected as the staging reflects.  A masked-out successor wastes a touch.
+    // The values are never used; the registers stay pinned until the kernel ends.
+    unsigned pf[W8F_PF_TOUCH] = {};
+    {
+        const int b2 = (int)blockIdx.x + W8F_PREFETCH;
+        const ConvParams Q = touch_params();
+        if (b2 < Q.mtiles * Q.ntiles * Q.zdim && tid < W8F_HW * W8F_HW) {
+            const ConvTileId T2 = conv_tile_of_block<W8F_PW, W8F_PH, false>(Q, b2);
+            const int hy = tid / W8F_HW, hx = tid - hy * W8F_HW;
+            touch_pixel(Q, T2.n, (unsigned)(reflect1(T2.y0 - 1 + hy, Q.H) * Q.W + reflect1(T2.x0 - 1 + hx, Q.W)), pf);
+        }
+    }
+#endif
+
     // ---- epilogue: Y = A^T M A per (tile, column), statistics, BatchNorm arrival, stores ----
     // (1) the nu-halves of a plane row swap registers: this wave keeps registers 2 nh, 2 nh + 1 of every block and hands the
     // other two of its three planes to its partner (xi, 1 - nh)
@@ -397,6 +429,10 @@ conv_wino80f4_kernel(const ConvParams P) {
         }
     }
     if (bn) bn_complete(P, arr, n, tid, W8FStats::flag(red));
+#if W8F_PREFETCH
+#pragma unroll
+    for (int j = 0; j < W8F_PF_TOUCH; j++) asm volatile("" :: "v"(pf[j]));
+#endif
 }
 
 // Transformed weights U = G g G^T (w4_weight_u, as pack_weight_wino4_kernel) in the layout of conv_wino80f4_kernel: i enumerates
