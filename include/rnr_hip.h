@@ -133,9 +133,22 @@ int rnr_create_texture_image(const float* vertices_all, const float* textures, f
  * ===================================================================================================== */
 
 /*
+ * Alignment of the operands of the shading and G-buffer entry points (this section's rnr_project_vertices ... rnr_shade_inputs,
+ * rnr_ray_weights, rnr_ray_render, the layout helpers, the spherical-harmonics and resampling operators, and all of section 3):
+ * every pointer operand needs the width of the widest access its kernel makes through it.  Unless the entry point's own
+ * "Alignment:" line says otherwise that is its element's 4 bytes (float, int32_t); the operands named there are read or written
+ * in 16-byte pieces and need 16-byte alignment.  HOST tables (textures_host, tex_sizes_host, pivots, rnr_mesh, rnr_gbuffer, rnr_rays)
+ * are plain C arrays / structs; the device pointers they hold follow the same rule.  Every entry point checks this, and that its
+ * sizes are positive, before any launch: a pointer that misses its alignment or a size <= 0 returns an error
+ * (rnr_last_error names the entry point and the operands), and nothing is written (tests/test_gpu_shade_guard.py,
+ * tests/test_gpu_gbuffer_guard.py).
+ */
+
+/*
  * nr.projection (neural_renderer/projection.py:6-53) for a shared mesh.
  *   vertices [nv, 3] world; K [N,3,3]; R [N,3,3]; t [N,3]; dist_coeffs [N,5] or NULL (= zeros);
  *   offset/scale [N,2] or both NULL; out [N, nv, 3] = (u_ndc, v_ndc, z_cam).
+ * Alignment: every operand its element's 4 bytes.
  */
 int rnr_project_vertices(const float* vertices, const float* K, const float* R, const float* t,
                          const float* dist_coeffs, const float* offset, const float* scale,
@@ -143,7 +156,7 @@ int rnr_project_vertices(const float* vertices, const float* K, const float* R, 
                          void* stream);
 
 /* Mesh description shared by the G-buffer kernels (all device pointers, int32 indices 0-based as produced
- * by load_obj.py:176-178). */
+ * by load_obj.py:176-178).  Alignment: every array its element's 4 bytes. */
 typedef struct rnr_mesh {
     const float* v;          /* [nv, 3] world positions (global_RT applied, network.py:127) */
     const float* vt;         /* [nvt, 2] */
@@ -155,7 +168,8 @@ typedef struct rnr_mesh {
 } rnr_mesh;
 
 /* Outputs of network.Rasterizer.forward (network.py:156-216) that are per-pixel maps; any pointer may be
- * NULL to skip that map.  Rows are already flipped (row 0 = top), as rasterize_rgbad returns them. */
+ * NULL to skip that map.  Rows are already flipped (row 0 = top), as rasterize_rgbad returns them.
+ * Alignment: every map its element's 4 bytes. */
 typedef struct rnr_gbuffer {
     int32_t* face_index_map; /* [N,S,S]   -1 = background */
     float* alpha;            /* [N,S,S]   {0,1} */
@@ -176,6 +190,10 @@ size_t rnr_gbuffer_workspace_bytes(int num_views, int num_faces, int image_size)
  * renderer.py:244-257 + rasterize.py:255-340 + network.py:156-214 in one pass (no texture kernel: the hot
  * path feeds it an all-zero texture and discards rgb, network.py:140-142,157).
  *   v_uvz [N, nv, 3] from rnr_project_vertices; pose [N,4,4] (for the *_cam maps; may be NULL if unused).
+ *   workspace: rnr_gbuffer_workspace_bytes(num_views, mesh->num_faces, image_size) bytes; nothing beyond them is touched.
+ * Alignment: workspace is cleared in 16-byte pieces and holds 16-byte face records and 64-bit depth keys, each region a multiple
+ * of 256 bytes from its start: it needs 16-byte alignment; the mesh arrays, v_uvz, pose and the maps of `out` their element's
+ * 4 bytes.  Refused before any launch: a misaligned operand, num_views or image_size <= 0.
  */
 int rnr_rasterize_gbuffer(const rnr_mesh* mesh, const float* v_uvz, const float* pose, int num_views,
                           int image_size, float near_, float far_, const rnr_gbuffer* out,
@@ -197,12 +215,17 @@ int rnr_rasterize_gbuffer_prepared(const rnr_mesh* mesh, const float* v_uvz, con
  *   lp_basis [lp_samples, lp_num_basis], lp_coeff [lp_num_basis, lp_channels] -> light_probe [lp_samples, lp_channels];
  *   gbuffer_workspace: an rnr_gbuffer_workspace_bytes(num_views, mesh->num_faces, image_size) buffer -> cleared for
  *   rnr_rasterize_gbuffer_prepared.
+ * Alignment: gbuffer_workspace is cleared in 16-byte pieces and needs 16-byte alignment; every other operand its element's
+ * 4 bytes.  The two cleared regions (bin counters to 0, depth keys to ~0) lie in the MIDDLE of the workspace's layout, each
+ * followed by a region the rasterizer fills: the clear does not end at rnr_gbuffer_workspace_bytes, and an over-long clear
+ * would damage no neighbour of the buffer — tests/test_gpu_gbuffer_guard.py reads the workspace back instead.
  */
 int rnr_frame_prepare(const rnr_mesh* mesh, const float* K, const float* pose, int num_views, int image_size, float eps,
                       float* v_uvz, float* tangents, const float* lp_basis, const float* lp_coeff, float* light_probe,
                       int lp_samples, int lp_num_basis, int lp_channels, void* gbuffer_workspace, void* stream);
 
-/* Per-face unit tangents of render.get_TBN_map (render.py:135-150); static per mesh.  out [nf,3]. */
+/* Per-face unit tangents of render.get_TBN_map (render.py:135-150); static per mesh.  out [nf,3].
+ * Alignment: the mesh arrays and out their element's 4 bytes. */
 int rnr_face_tangents(const rnr_mesh* mesh, float* out, void* stream);
 
 /* Ray-sampler constants (network.RaySampler buffers `pivots_dir`, network.py:441-443), HOST pointers. */
@@ -222,6 +245,10 @@ typedef struct rnr_rays {
  *           view_dir (3), neural texture (C); channels >= Cin are zero-filled
  *   rays_uv [N, H, W, 2, num_spec+num_diff] or NULL; neural_img [N, C, H, W] or NULL (API copies)
  *   sh_basis_map [N,H,W,9] or NULL (written when non-NULL)
+ * Alignment: net_in is written, and every texture level read, in 16-byte pieces (four channels of a pixel / a texel): net_in and
+ * each textures_host[level] need 16-byte alignment — what every view n > 0 of net_in has, c_pad being a multiple of 4, and every
+ * texel, tex_channels being one; every other operand its element's 4 bytes.  Refused before any launch: a misaligned operand,
+ * num_views, height, width or num_faces <= 0.
  */
 int rnr_shade_inputs(const int32_t* face_index_map, const float* alpha, const float* uv_map,
                      const float* normal_map, const float* face_tangents, int num_faces,
@@ -476,6 +503,10 @@ int rnr_conv2d_fused(const rnr_conv_desc* d, const rnr_conv_src* src0, const rnr
  *                    tile; entries >= c_out reach no output, whatever they hold.
  *                    ray_w [N, H, W, c_out_pad] as written by rnr_ray_weights; a pixel whose weights are all 0 gives exactly 0.
  * Differs from rnr_ray_render in summation order only (<= 1e-6 on frames in [0, 2]).
+ * Alignment of rnr_ray_weights' operands: net_in is read and ray_w written in 16-byte pieces (whole rows of a workgroup's pixels,
+ * c_pad and c_w being multiples of 4): both need 16-byte alignment; alpha and lp their element's 4 bytes.  Refused before any
+ * launch: a misaligned operand, num_views, height or width <= 0, rows too wide for the 64 KiB LDS staging
+ * (32 * (staged net_in floats + c_w) floats).
  */
 int rnr_ray_weights(const float* net_in, int c_pad, const float* alpha, const float* lp, int lp_h, int lp_w, int num_spec,
                     int num_diff, int albedo_diff_ch, int albedo_spec_ch, float* ray_w, int c_w, int num_views, int height,
@@ -600,7 +631,8 @@ int rnr_conv2d_input_backward_ring(const rnr_conv_desc* d, int source, const flo
 int rnr_unet_out_backward(const float* g_out, const float* out, int apply_tanh, float* g_raw, int n, int c, int h,
                           int w, int c_pad, void* stream);
 
-/* Layout helpers for the drop-in RenderingNet.forward (NCHW in / NCHW out). */
+/* Layout helpers for the drop-in RenderingNet.forward (NCHW in / NCHW out).  Alignment: every operand its element's 4 bytes;
+ * n, c, h, w <= 0 are refused before any launch. */
 int rnr_nchw_to_nhwc(const float* in, float* out, int n, int c, int h, int w, int c_pad, void* stream);
 /* out[n,c,h,w] = f(in[n,h,w,c] + bias[c]) with bias optional (NULL) and f = tanhf when apply_tanh != 0 */
 int rnr_nhwc_to_nchw(const float* in, float* out, const float* bias, int apply_tanh,
@@ -615,6 +647,14 @@ int rnr_nhwc_to_nchw(const float* in, float* out, const float* bias, int apply_t
  *   bias [3*(num_spec+num_diff)]; net_in as written by rnr_shade_inputs; alpha [N,H,W]
  *   lp [Hl, Wl, 3] environment map (LightingSH.reconstruct_lp, network.py:622-627)
  *   image [N,3,H,W]
+ * Read: of unet_raw the first 3 * (num_spec + num_diff) columns, of net_in the ray directions (channels < 3 rays), normal / view
+ * (the next 6) and the two albedo triples; whole rows are staged in 16-byte pieces, so the other columns and channels are loaded
+ * but reach no output, whatever they hold.  On a background pixel (alpha == 0) the unet_raw row and the ray directions reach no
+ * output either (the ray sums are set to 0 by select: rnr_conv2d_masked leaves skipped tiles unwritten), but the two albedo
+ * triples are still multiplied with those zero sums, as RayRenderer.forward's albedo * ltt is (network.py:515-522): they must
+ * be finite there, as rnr_shade_inputs writes them.  A workgroup of 32 pixels that are all background reads neither tensor.
+ * Alignment: unet_raw and net_in are read in 16-byte pieces and need 16-byte alignment; bias, alpha, lp and image their
+ * element's 4 bytes.  Refused before any launch: a misaligned operand, num_views, height or width <= 0.
  */
 int rnr_ray_render(const float* unet_raw, int c_out_pad, const float* bias, const float* net_in, int c_pad,
                    const float* alpha, const float* lp, int lp_h, int lp_w, int num_spec, int num_diff,
@@ -864,6 +904,8 @@ int rnr_pack_conv_weights(const rnr_conv_desc* descs, const float* const* weight
 
 /* ---- spherical harmonics (sph_harm.py:41-102) ---- */
 
+/* Alignment of the four SH operators' operands, rnr_interpolate_bilinear's and rnr_resize_area's: every operand its element's
+ * 4 bytes. */
 /* Real orthonormal SH without Condon-Shortley phase, columns (l, m=-l..l); dirs [n,3] (need not be unit),
  * out [n, (lmax+1)^2].  lmax <= 16. */
 int rnr_sh_basis(const float* dirs, float* out, int n, int lmax, void* stream);
@@ -894,6 +936,9 @@ int rnr_resize_area(const float* src, float* dst, int src_h, int src_w, int dst_
 /* =====================================================================================================
  * 3. Stand-alone operators for the drop-in Python API (one reference function each).  The fused entry
  *    points above compute the same quantities without the intermediate HBM round trips.
+ *    Alignment: every device operand of this section its element's 4 bytes (no kernel here moves more than one element at a
+ *    time), the levels of textures_host / grad_textures_host included — except rnr_ray_transport's unet_raw and net_in (16, see
+ *    there).  Sizes <= 0 and misaligned operands are refused before any launch.
  * ===================================================================================================== */
 
 /* camera.get_view_dir_map (camera.py:5-32): out_world/out_cam [N,H,W,3] (out_cam may be NULL). */
@@ -964,7 +1009,10 @@ int rnr_texture_mapper_backward(const float* uv_map, const float* sh_basis_map, 
 /* network.RayRenderer.forward (network.py:481-527) on API-shaped tensors: rays_uv [N,H,W,2,R],
  * rays_lt [N,R,C,H,W], lp [lp_n,Hl,Wl,C] (lp_n = 1 or N), albedos [N,C,H,W] (albedo_diffuse may be NULL).
  * Outputs [N,C,H,W] (out required, others optional) and rays_color [N,R,C,H,W] (optional).  Refuses what its adjoint refuses:
- * sizes <= 0, num_rays <= num_ray_diffuse, a probe batch of 2^31 floats or more. */
+ * sizes <= 0, num_rays <= num_ray_diffuse, a probe batch of 2^31 floats or more.
+ * A NaN in rays_uv PROPAGATES, as through torch.clamp(max=) and the reference's blend: the tap coordinate min(u Wl, Wl - 1) is the
+ * NaN-propagating minimum, the indices clamp to column / row 0 and the four weights are NaN, so that ray's colour and what sums
+ * it are NaN (rnr_ray_render, rnr_ray_weights and rnr_env_background share the code; tests/test_gpu_shade_guard.py). */
 int rnr_ray_renderer(const float* rays_uv, const float* rays_lt, const float* lp, int lp_n, int lp_h,
                      int lp_w, const float* albedo_specular, const float* albedo_diffuse, int channels,
                      int num_rays, int num_ray_diffuse, int no_albedo, int seperate_albedo,
@@ -1021,6 +1069,8 @@ int rnr_ray_renderer_backward(const float* rays_uv, const float* rays_lt, const 
  *   rnr_ray_renderer(rays_uv, rays_lt, lp, albedo_specular, albedo_diffuse, seperate_albedo = 1).out
  * is rnr_ray_render's frame up to the order of the sums over the rays, and rnr_ray_renderer_backward is its adjoint.
  * At most 16 specular and 16 diffuse rays; c_out_pad and c_pad multiples of 4.
+ * Alignment: unet_raw and net_in are read in 16-byte pieces (whole rows, as by rnr_ray_render) and need 16-byte alignment; bias,
+ * alpha and the four outputs their element's 4 bytes.
  */
 int rnr_ray_transport(const float* unet_raw, int c_out_pad, const float* bias, const float* net_in, int c_pad,
                       const float* alpha, int num_spec, int num_diff, int albedo_diff_ch, int albedo_spec_ch,

@@ -1013,6 +1013,13 @@ static int rasterize_gbuffer_impl(const rnr_mesh* mesh, const float* v_uvz, cons
     RNR_REQUIRE(!(out->normal_map_cam || out->position_map_cam) || pose,
                 "rnr_rasterize_gbuffer: camera-space maps need pose");
     RNR_REQUIRE(num_views > 0 && image_size > 0 && image_size <= 16384, "rnr_rasterize_gbuffer: bad sizes");
+    // the clear and the wide-face records move uint4 / float4, the keys are 64-bit: every region starts a multiple of 256 bytes in
+    RNR_REQUIRE(aligned_to(16, {workspace}), "rnr_rasterize_gbuffer: workspace must be 16-byte aligned");
+    RNR_REQUIRE(aligned_to(4, {mesh->v, mesh->vt, mesh->vn, mesh->f_v_idx, mesh->f_vt_idx, mesh->f_vn_idx, v_uvz, pose}),
+                "rnr_rasterize_gbuffer: the mesh arrays, v_uvz and pose must be 4-byte aligned");
+    RNR_REQUIRE(aligned_to(4, {out->face_index_map, out->alpha, out->depth, out->weight_map, out->raw_weight_map, out->uv_map,
+                               out->normal_map, out->normal_map_cam, out->position_map, out->position_map_cam}),
+                "rnr_rasterize_gbuffer: every map of out must be 4-byte aligned");
     hipStream_t st = as_stream(stream);
     const int nf = mesh->num_faces;
     const RasterWorkspace W(workspace, num_views, nf, image_size, true);

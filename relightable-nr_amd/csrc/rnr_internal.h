@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <initializer_list>
 
 #include "../../include/rnr_hip.h"
 
@@ -26,6 +27,14 @@ void gbuffer_clear_regions(void* workspace, int num_views, int num_faces, int im
                            uint4** keys, long* key_vec);
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// every pointer of the list (NULL: an optional operand left out) is a multiple of `bytes`: the alignment contract of rnr_hip.h,
+// checked by the entry points before any launch
+inline bool aligned_to(size_t bytes, std::initializer_list<const void*> ptrs) {
+    uintptr_t bits = 0;
+    for (const void* p : ptrs) bits |= (uintptr_t)p;
+    return bits % bytes == 0;
+}
 
 #define RNR_REQUIRE(cond, ...)                     \
     do {                                           \

@@ -313,10 +313,12 @@ __device__ __forceinline__ Taps level_taps(float u, float v, int s) {
     const float y = sm1 - v * sm1;
     return bilinear_taps(x, y, s, s);
 }
-// env-map taps of a ray (network.py:497; misc.py:5-42): clamp(max=) only, then the validity mask zeroes uv = -1
+// env-map taps of a ray (network.py:497; misc.py:5-42): clamp(max=) only, then the validity mask zeroes uv = -1.  The minimum
+// is the NaN-propagating one, as torch.clamp is: fminf gave a NaN coordinate the last column / row, a valid
+// tap, and the NaN never reached the colour (tests/test_gpu_shade_guard.py plants one); now the weights are NaN, as level_taps' are
 __device__ __forceinline__ Taps envmap_taps(float u, float v, int lp_w, int lp_h) {
-    const float x = fminf(u * (float)lp_w, (float)(lp_w - 1));
-    const float y = fminf(v * (float)lp_h, (float)(lp_h - 1));
+    const float x = __builtin_elementwise_minimum(u * (float)lp_w, (float)(lp_w - 1));
+    const float y = __builtin_elementwise_minimum(v * (float)lp_h, (float)(lp_h - 1));
     return bilinear_taps(x, y, lp_w, lp_h);
 }
 // the four texels of a three-channel env map (lp_w3 = 3 lp_w) under the taps t.  Texel offsets with 24-bit multiplies (full
@@ -1890,6 +1892,8 @@ extern "C" int rnr_project_vertices(const float* vertices, const float* K, const
     RNR_REQUIRE(vertices && K && R && t && out, "rnr_project_vertices: null pointer argument");
     RNR_REQUIRE((offset == nullptr) == (scale == nullptr), "rnr_project_vertices: offset and scale go together");
     RNR_REQUIRE(num_views > 0 && num_vertices > 0, "rnr_project_vertices: bad sizes");
+    RNR_REQUIRE(aligned_to(4, {vertices, K, R, t, dist_coeffs, offset, scale, out}),
+                "rnr_project_vertices: vertices, K, R, t, dist_coeffs, offset, scale and out must be 4-byte aligned");
     const long total = (long)num_views * num_vertices;
     hipLaunchKernelGGL(project_vertices_kernel, grid256(total), dim3(256), 0,
                        as_stream(stream), vertices, K, R, t, dist_coeffs, offset, scale, out, num_views,
@@ -1900,6 +1904,8 @@ extern "C" int rnr_project_vertices(const float* vertices, const float* K, const
 extern "C" int rnr_face_tangents(const rnr_mesh* mesh, float* out, void* stream) {
     RNR_REQUIRE(mesh && out && mesh->v && mesh->vt && mesh->f_v_idx && mesh->f_vt_idx && mesh->num_faces > 0,
                 "rnr_face_tangents: incomplete mesh");
+    RNR_REQUIRE(aligned_to(4, {mesh->v, mesh->vt, mesh->vn, mesh->f_v_idx, mesh->f_vt_idx, mesh->f_vn_idx, out}),
+                "rnr_face_tangents: the mesh arrays and out must be 4-byte aligned");
     hipLaunchKernelGGL(face_tangents_kernel, dim3((mesh->num_faces + 255) / 256), dim3(256), 0,
                        as_stream(stream), *mesh, out);
     return check_launch("face_tangents_kernel");
@@ -1925,6 +1931,13 @@ extern "C" int rnr_shade_inputs(const int32_t* face_index_map, const float* alph
     RNR_REQUIRE((3 * (rays->num_spec + rays->num_diff) + 6) % 4 == 0,
                 "rnr_shade_inputs: 3*rays+6 must be a multiple of 4 (texture channels are written as float4)");
     RNR_REQUIRE(sh_start_ch < 0 || sh_start_ch + 9 <= tex_channels, "rnr_shade_inputs: sh_start_ch + 9 > channels");
+    RNR_REQUIRE(num_views > 0 && height > 0 && width > 0 && num_faces > 0, "rnr_shade_inputs: bad sizes");
+    RNR_REQUIRE(aligned_to(16, {net_in}), "rnr_shade_inputs: net_in must be 16-byte aligned");
+    RNR_REQUIRE(aligned_to(4, {face_index_map, alpha, uv_map, normal_map, face_tangents, proj_inv, R_inv, rays_uv, neural_img, sh_basis_map}),
+                "rnr_shade_inputs: face_index_map, alpha, uv_map, normal_map, face_tangents, proj_inv, R_inv, rays_uv, neural_img and "
+                "sh_basis_map must be 4-byte aligned");
+    for (int l = 0; l < num_levels; l++)
+        RNR_REQUIRE(aligned_to(16, {textures_host[l]}), "rnr_shade_inputs: textures_host[%d] must be 16-byte aligned", l);
     ShadeParams P = {};
     P.face_index_map = face_index_map; P.alpha = alpha; P.uv_map = uv_map; P.normal_map = normal_map;
     P.tangents = face_tangents; P.num_faces = num_faces; P.proj_inv = proj_inv; P.R_inv = R_inv;
@@ -1949,6 +1962,9 @@ extern "C" int rnr_ray_render(const float* unet_raw, int c_out_pad, const float*
                               int num_diff, int albedo_diff_ch, int albedo_spec_ch, float* image, int num_views,
                               int height, int width, void* stream) {
     RNR_REQUIRE(unet_raw && bias && net_in && alpha && lp && image, "rnr_ray_render: null pointer argument");
+    RNR_REQUIRE(num_views > 0 && height > 0 && width > 0, "rnr_ray_render: bad sizes");
+    RNR_REQUIRE(aligned_to(16, {unet_raw, net_in}), "rnr_ray_render: unet_raw and net_in must be 16-byte aligned");
+    RNR_REQUIRE(aligned_to(4, {bias, alpha, lp, image}), "rnr_ray_render: bias, alpha, lp and image must be 4-byte aligned");
     RayParams P;
     // 16 diffuse rays: one per lane of the second 16-lane segment
     if (int e = ray_launch_checks("rnr_ray_render", num_spec, num_diff, 16, lp_h, lp_w, albedo_diff_ch, albedo_spec_ch, c_pad, &P.ni_need))
@@ -1968,6 +1984,9 @@ extern "C" int rnr_ray_weights(const float* net_in, int c_pad, const float* alph
                                int num_spec, int num_diff, int albedo_diff_ch, int albedo_spec_ch, float* ray_w, int c_w,
                                int num_views, int height, int width, void* stream) {
     RNR_REQUIRE(net_in && alpha && lp && ray_w, "rnr_ray_weights: null pointer argument");
+    RNR_REQUIRE(num_views > 0 && height > 0 && width > 0, "rnr_ray_weights: bad sizes");
+    RNR_REQUIRE(aligned_to(16, {net_in, ray_w}), "rnr_ray_weights: net_in and ray_w must be 16-byte aligned");
+    RNR_REQUIRE(aligned_to(4, {alpha, lp}), "rnr_ray_weights: alpha and lp must be 4-byte aligned");
     RayWeightParams P;
     // 15 diffuse rays: lane 31 never holds a ray, it writes the padding columns
     if (int e = ray_launch_checks("rnr_ray_weights", num_spec, num_diff, 15, lp_h, lp_w, albedo_diff_ch, albedo_spec_ch, c_pad, &P.ni_need))
@@ -1978,6 +1997,7 @@ extern "C" int rnr_ray_weights(const float* net_in, int c_pad, const float* alph
     P.ray_w = ray_w; P.c_w = c_w; P.npix = (long)num_views * height * width;
     RNR_REQUIRE(c_w % 4 == 0, "rnr_ray_weights: c_w must be a multiple of 4");
     const size_t lds = (size_t)RR_WG_PIX * (size_t)(P.ni_need + c_w) * sizeof(float);
+    RNR_REQUIRE(lds <= 64 * 1024, "rnr_ray_weights: rows too wide for the LDS staging (%zu bytes)", lds);
     hipLaunchKernelGGL(ray_weights_kernel, ray_grid(P.npix), dim3(256), lds, as_stream(stream), P);
     return check_launch("ray_weights_kernel");
 }
@@ -1985,6 +2005,7 @@ extern "C" int rnr_ray_weights(const float* net_in, int c_pad, const float* alph
 extern "C" int rnr_sh_basis(const float* dirs, float* out, int n, int lmax, void* stream) {
     RNR_REQUIRE(dirs && out && n > 0, "rnr_sh_basis: bad arguments");
     RNR_REQUIRE(lmax >= 0 && lmax <= SH_LMAX_MAX, "rnr_sh_basis: lmax %d not in [0,%d]", lmax, SH_LMAX_MAX);
+    RNR_REQUIRE(aligned_to(4, {dirs, out}), "rnr_sh_basis: dirs and out must be 4-byte aligned");
     hipLaunchKernelGGL(sh_basis_kernel, dim3((n + 127) / 128), dim3(128), 0, as_stream(stream), dirs, out, n, lmax);
     return check_launch("sh_basis_kernel");
 }
@@ -1993,6 +2014,7 @@ extern "C" int rnr_sh_reconstruct(const float* basis, const float* coeff, float*
                                   int num_basis, int num_channels, void* stream) {
     RNR_REQUIRE(basis && coeff && out && num_samples > 0 && num_basis > 0 && num_channels > 0,
                 "rnr_sh_reconstruct: bad arguments");
+    RNR_REQUIRE(aligned_to(4, {basis, coeff, out}), "rnr_sh_reconstruct: basis, coeff and out must be 4-byte aligned");
     const size_t lds = (size_t)(SHR_ROWS * num_basis + num_basis * num_channels) * sizeof(float);
     RNR_REQUIRE(lds <= 64 * 1024, "rnr_sh_reconstruct: num_basis * (64 + num_channels) floats must fit 64 KiB of LDS");
     hipLaunchKernelGGL(sh_reconstruct_kernel, dim3((unsigned)((num_samples + SHR_ROWS - 1) / SHR_ROWS)), dim3(256), lds,
@@ -2010,6 +2032,10 @@ extern "C" int rnr_frame_prepare(const rnr_mesh* mesh, const float* K, const flo
     RNR_REQUIRE(!tangents || (mesh->vt && mesh->f_v_idx && mesh->f_vt_idx), "rnr_frame_prepare: tangents need vt and the index arrays");
     RNR_REQUIRE(!light_probe || (lp_basis && lp_coeff && lp_samples > 0 && lp_num_basis > 0 && lp_channels > 0),
                 "rnr_frame_prepare: the light probe needs basis, coefficients and sizes");
+    RNR_REQUIRE(aligned_to(16, {gbuffer_workspace}), "rnr_frame_prepare: gbuffer_workspace must be 16-byte aligned");
+    RNR_REQUIRE(aligned_to(4, {mesh->v, mesh->vt, mesh->vn, mesh->f_v_idx, mesh->f_vt_idx, mesh->f_vn_idx, K, pose, v_uvz, tangents, lp_basis,
+                               lp_coeff, light_probe}),
+                "rnr_frame_prepare: the mesh arrays, K, pose, v_uvz, tangents, lp_basis, lp_coeff and light_probe must be 4-byte aligned");
     FramePrepParams P = {};
     P.mesh = *mesh; P.K = K; P.pose = pose; P.v_uvz = v_uvz; P.nviews = num_views; P.orig_size = (float)image_size; P.eps = eps;
     P.tangents = tangents;
@@ -2042,6 +2068,7 @@ extern "C" int rnr_sh_fit(const float* samples, const float* basis, float* out, 
                           int num_channels, void* stream) {
     RNR_REQUIRE(samples && basis && out && num_samples > 0 && num_basis > 0 && num_channels > 0,
                 "rnr_sh_fit: bad arguments");
+    RNR_REQUIRE(aligned_to(4, {samples, basis, out}), "rnr_sh_fit: samples, basis and out must be 4-byte aligned");
     hipLaunchKernelGGL(sh_fit_kernel<true>, dim3(num_basis * num_channels), dim3(256), 0, as_stream(stream), samples,
                        basis, out, num_samples, num_basis, num_channels);
     return check_launch("sh_fit_kernel");
@@ -2051,6 +2078,8 @@ extern "C" int rnr_sh_reconstruct_backward(const float* basis, const float* grad
                                            int num_basis, int num_channels, void* stream) {
     RNR_REQUIRE(basis && grad_out && grad_coeff && num_samples > 0 && num_basis > 0 && num_channels > 0,
                 "rnr_sh_reconstruct_backward: bad arguments");
+    RNR_REQUIRE(aligned_to(4, {basis, grad_out, grad_coeff}),
+                "rnr_sh_reconstruct_backward: basis, grad_out and grad_coeff must be 4-byte aligned");
     hipLaunchKernelGGL(sh_fit_kernel<false>, dim3(num_basis * num_channels), dim3(256), 0, as_stream(stream), grad_out,
                        basis, grad_coeff, num_samples, num_basis, num_channels);
     return check_launch("sh_fit_kernel");
@@ -2059,6 +2088,7 @@ extern "C" int rnr_sh_reconstruct_backward(const float* basis, const float* grad
 extern "C" int rnr_interpolate_bilinear(const float* data, int h, int w, int c, const float* x, const float* y,
                                         float* out, int32_t* taps, int n, void* stream) {
     RNR_REQUIRE(data && x && y && out && h > 0 && w > 0 && c > 0 && n > 0, "rnr_interpolate_bilinear: bad arguments");
+    RNR_REQUIRE(aligned_to(4, {data, x, y, out, taps}), "rnr_interpolate_bilinear: data, x, y, out and taps must be 4-byte aligned");
     const long total = (long)n * c;
     hipLaunchKernelGGL(interpolate_bilinear_kernel, grid256(total), dim3(256), 0,
                        as_stream(stream), data, h, w, c, x, y, out, taps, n);
@@ -2131,6 +2161,7 @@ resize_area_kernel(const float* __restrict__ src, float* __restrict__ dst, int s
 extern "C" int rnr_resize_area(const float* src, float* dst, int src_h, int src_w, int dst_h, int dst_w, int channels,
                                void* stream) {
     RNR_REQUIRE(src && dst && src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0 && channels > 0, "rnr_resize_area: bad arguments");
+    RNR_REQUIRE(aligned_to(4, {src, dst}), "rnr_resize_area: src and dst must be 4-byte aligned");
     const long total = (long)dst_h * dst_w * channels;
     hipLaunchKernelGGL(resize_area_kernel, grid256(total), dim3(256), 0, as_stream(stream), src, dst,
                        src_h, src_w, dst_h, dst_w, channels);
@@ -2139,6 +2170,8 @@ extern "C" int rnr_resize_area(const float* src, float* dst, int src_h, int src_
 
 extern "C" int rnr_nchw_to_nhwc(const float* in, float* out, int n, int c, int h, int w, int c_pad, void* stream) {
     RNR_REQUIRE(in && out && n > 0 && c > 0 && c_pad >= c, "rnr_nchw_to_nhwc: bad arguments");
+    RNR_REQUIRE(h > 0 && w > 0, "rnr_nchw_to_nhwc: bad sizes");
+    RNR_REQUIRE(aligned_to(4, {in, out}), "rnr_nchw_to_nhwc: in and out must be 4-byte aligned");
     const long total = (long)n * h * w * c_pad;
     const long npix = (long)n * h * w;
     if (c_pad <= 240)       // 64-pixel x c_pad tile in LDS (<= 62.4 KB)
@@ -2153,6 +2186,8 @@ extern "C" int rnr_nchw_to_nhwc(const float* in, float* out, int n, int c, int h
 extern "C" int rnr_nhwc_to_nchw(const float* in, float* out, const float* bias, int apply_tanh, int n, int c,
                                 int h, int w, int c_pad, void* stream) {
     RNR_REQUIRE(in && out && n > 0 && c > 0 && c_pad >= c, "rnr_nhwc_to_nchw: bad arguments");
+    RNR_REQUIRE(h > 0 && w > 0, "rnr_nhwc_to_nchw: bad sizes");
+    RNR_REQUIRE(aligned_to(4, {in, out, bias}), "rnr_nhwc_to_nchw: in, out and bias must be 4-byte aligned");
     const long total = (long)n * c * h * w;
     const long npix = (long)n * h * w;
     if (c_pad <= 240)
@@ -2167,6 +2202,8 @@ extern "C" int rnr_nhwc_to_nchw(const float* in, float* out, const float* bias, 
 extern "C" int rnr_view_dir_map(const float* proj_inv, const float* R_inv, float* out_world, float* out_cam,
                                 int num_views, int height, int width, void* stream) {
     RNR_REQUIRE(proj_inv && R_inv && out_world && num_views > 0 && height > 0 && width > 0, "rnr_view_dir_map: bad arguments");
+    RNR_REQUIRE(aligned_to(4, {proj_inv, R_inv, out_world, out_cam}),
+                "rnr_view_dir_map: proj_inv, R_inv, out_world and out_cam must be 4-byte aligned");
     const long npix = (long)num_views * height * width;
     hipLaunchKernelGGL(view_dir_map_kernel, grid256(npix), dim3(256), 0, as_stream(stream),
                        proj_inv, R_inv, out_world, out_cam, npix, height, width);
@@ -2186,6 +2223,7 @@ extern "C" int rnr_env_background(const float* proj_inv, const float* R_inv, con
     RNR_REQUIRE(num_views > 0 && height > 0 && width > 0 && (long)height * width < (1L << 31), "rnr_env_background: bad sizes");
     if (int e = probe_checks("rnr_env_background", lp_h, lp_w)) return e;
     RNR_REQUIRE(lp_n == 1 || lp_n == num_views, "rnr_env_background: lp batch must be 1 or N");
+    RNR_REQUIRE(aligned_to(4, {proj_inv, R_inv, lp, out}), "rnr_env_background: proj_inv, R_inv, lp and out must be 4-byte aligned");
     const long npix = (long)num_views * height * width;
     hipLaunchKernelGGL(env_background_kernel, grid256(npix), dim3(256), 0, as_stream(stream), proj_inv, R_inv, lp, lp_n, lp_h,
                        lp_w, out, npix, height, width);
@@ -2221,6 +2259,9 @@ extern "C" int rnr_present_u8(const float* image, const float* alpha, const floa
 extern "C" int rnr_tbn_map(const float* normal_map, const int32_t* face_index_map, const float* face_tangents,
                            int num_faces, float* out, int num_views, int height, int width, void* stream) {
     RNR_REQUIRE(normal_map && face_index_map && face_tangents && out && num_faces > 0, "rnr_tbn_map: bad arguments");
+    RNR_REQUIRE(num_views > 0 && height > 0 && width > 0, "rnr_tbn_map: bad sizes");
+    RNR_REQUIRE(aligned_to(4, {normal_map, face_index_map, face_tangents, out}),
+                "rnr_tbn_map: normal_map, face_index_map, face_tangents and out must be 4-byte aligned");
     const long npix = (long)num_views * height * width;
     hipLaunchKernelGGL(tbn_map_kernel, grid256(npix), dim3(256), 0, as_stream(stream), normal_map,
                        face_index_map, face_tangents, num_faces, out, npix);
@@ -2248,6 +2289,7 @@ tbn_matvec_kernel(const float* __restrict__ tbn, const float* __restrict__ v, fl
 
 extern "C" int rnr_tbn_matvec(const float* tbn, const float* vec, float* out, long num_pixels, int transposed, void* stream) {
     RNR_REQUIRE(tbn && vec && out && num_pixels > 0, "rnr_tbn_matvec: bad arguments");
+    RNR_REQUIRE(aligned_to(4, {tbn, vec, out}), "rnr_tbn_matvec: tbn, vec and out must be 4-byte aligned");
     hipLaunchKernelGGL(tbn_matvec_kernel, grid256(num_pixels), dim3(256), 0, as_stream(stream), tbn, vec, out,
                        num_pixels, transposed);
     return check_launch("tbn_matvec_kernel");
@@ -2259,6 +2301,9 @@ extern "C" int rnr_ray_sampler(int reflect, const float* pivots_host, int num_ra
     RNR_REQUIRE(pivots_host && tbn && alpha && rays_dir && rays_uv, "rnr_ray_sampler: null pointer argument");
     RNR_REQUIRE(!reflect || view_tangent, "rnr_ray_sampler: reflect mode needs view_tangent");
     RNR_REQUIRE(num_rays >= 1 && num_rays <= MAX_RAYS, "rnr_ray_sampler: 1..%d rays", MAX_RAYS);
+    RNR_REQUIRE(num_pixels > 0, "rnr_ray_sampler: bad sizes");
+    RNR_REQUIRE(aligned_to(4, {tbn, view_tangent, alpha, rays_dir, rays_uv, rays_dir_tangent}),
+                "rnr_ray_sampler: tbn, view_tangent, alpha, rays_dir, rays_uv and rays_dir_tangent must be 4-byte aligned");
     RaySamplerParams P;
     P.tbn = tbn; P.view_tangent = view_tangent; P.alpha = alpha; P.rays_dir = rays_dir; P.rays_uv = rays_uv;
     P.rays_dir_tangent = reflect ? rays_dir_tangent : nullptr;
@@ -2272,12 +2317,14 @@ extern "C" int rnr_ray_sampler(int reflect, const float* pivots_host, int num_ra
 // What rnr_texture_mapper and rnr_texture_mapper_backward check alike, and what their parameter blocks share (levels: the block's
 // textures or gradient levels).  No size bound on a level: both address texels with 64-bit offsets
 template <class F>
-static int texture_mapper_operands(const char* fn, TexMapCommon& p, F** levels, const float* uv_map, const float* sh, const void* other,
+static int texture_mapper_operands(const char* fn, TexMapCommon& p, F** levels, const float* uv_map, const float* sh, const void* other, const char* other_name,
                                    F* const* levels_host, const int* sizes, int num_levels, int C, int sh_start, int min_size, int N, int H, int W) {
     RNR_REQUIRE(uv_map && other && levels_host && sizes, "%s: null pointer argument", fn);
     RNR_REQUIRE(num_levels >= 1 && num_levels <= MAX_LEVELS && C > 0 && N > 0 && H > 0 && W > 0, "%s: bad sizes", fn);
     RNR_REQUIRE(!sh || (sh_start >= 0 && sh_start + 9 <= C), "%s: sh_start_ch + 9 > channels", fn);
+    RNR_REQUIRE(aligned_to(4, {uv_map, sh, other}), "%s: uv_map, sh_basis_map and %s must be 4-byte aligned", fn, other_name);
     if (int e = fill_texture_levels(fn, levels, p.tex_size, levels_host, sizes, num_levels, C, 0, min_size)) return e;
+    for (int l = 0; l < num_levels; l++) RNR_REQUIRE(aligned_to(4, {levels_host[l]}), "%s: texture level %d must be 4-byte aligned", fn, l);
     p.uv_map = uv_map; p.sh = sh; p.num_levels = num_levels; p.C = C; p.sh_start = sh_start; p.npix = (long)N * H * W; p.hw = H * W;
     return 0;
 }
@@ -2286,7 +2333,7 @@ extern "C" int rnr_texture_mapper(const float* uv_map, const float* sh_basis_map
                                   const int* tex_sizes_host, int num_levels, int tex_channels, int sh_start_ch,
                                   float* out, int num_views, int height, int width, void* stream) {
     TexMapParams P = {};
-    if (int e = texture_mapper_operands("rnr_texture_mapper", P, P.tex, uv_map, sh_basis_map, out, textures_host, tex_sizes_host,
+    if (int e = texture_mapper_operands("rnr_texture_mapper", P, P.tex, uv_map, sh_basis_map, out, "out", textures_host, tex_sizes_host,
                                         num_levels, tex_channels, sh_start_ch, 2, num_views, height, width))
         return e;
     P.out = out;
@@ -2306,7 +2353,7 @@ extern "C" int rnr_texture_mapper_backward(const float* uv_map, const float* sh_
                                            void* stream) {
     TexMapBwdParams P = {};
     // a 1 x 1 level is a texture like any other to the adjoint
-    if (int e = texture_mapper_operands("rnr_texture_mapper_backward", P, P.grad, uv_map, sh_basis_map, grad_out, grad_textures_host,
+    if (int e = texture_mapper_operands("rnr_texture_mapper_backward", P, P.grad, uv_map, sh_basis_map, grad_out, "grad_out", grad_textures_host,
                                         tex_sizes_host, num_levels, tex_channels, sh_start_ch, 1, num_views, height, width))
         return e;
     P.g = grad_out; P.H = height; P.W = width;
@@ -2338,6 +2385,8 @@ static int ray_renderer_operands(const char* fn, RayApiParams& F, const float* r
     RNR_REQUIRE(lp_n == 1 || lp_n == N, "%s: lp batch must be 1 or N", fn);
     RNR_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && lp_h > 0 && lp_w > 0, "%s: bad sizes", fn);
     RNR_REQUIRE((size_t)lp_n * lp_h * lp_w * C < ((size_t)1 << 31), "%s: probe batch of 2^31 floats or more", fn);
+    RNR_REQUIRE(aligned_to(4, {rays_uv, rays_lt, lp, alb_spec, alb_diff}),
+                "%s: rays_uv, rays_lt, lp, albedo_specular and albedo_diffuse must be 4-byte aligned", fn);
     F.rays_uv = rays_uv; F.rays_lt = rays_lt; F.lp = lp; F.alb_spec = alb_spec; F.alb_diff = alb_diff; F.lp_n = lp_n; F.lp_h = lp_h; F.lp_w = lp_w;
     F.C = C; F.R = R; F.n_diff = n_diff; F.no_albedo = no_albedo; F.separate = separate; F.lp_scale = lp_scale;
     F.npix = (long)N * H * W; F.hw = H * W;
@@ -2369,6 +2418,8 @@ extern "C" int rnr_ray_renderer(const float* rays_uv, const float* rays_lt, cons
                                       channels, num_rays, num_ray_diffuse, no_albedo, seperate_albedo, lp_scale_factor, num_views,
                                       height, width))
         return e;
+    RNR_REQUIRE(aligned_to(4, {out, out_specular, out_diffuse, ltt_specular, ltt_diffuse, rays_color}),
+                "rnr_ray_renderer: out, out_specular, out_diffuse, ltt_specular, ltt_diffuse and rays_color must be 4-byte aligned");
     P.out = out; P.out_spec = out_specular; P.out_diff = out_diffuse; P.ltt_spec = ltt_specular; P.ltt_diff = ltt_diffuse; P.rays_color = rays_color;
     return launch_ray_api(ray_renderer_api_tiled_kernel, "ray_renderer_api_tiled_kernel", ray_renderer_api_kernel,
                           "ray_renderer_api_kernel", P, P, stream);
@@ -2388,6 +2439,10 @@ extern "C" int rnr_ray_renderer_backward(const float* rays_uv, const float* rays
                                       num_views, height, width))
         return e;
     RNR_REQUIRE(!grad_albedo_diffuse || albedo_diffuse, "rnr_ray_renderer_backward: grad_albedo_diffuse without albedo_diffuse");
+    RNR_REQUIRE(aligned_to(4, {g_out, g_out_specular, g_out_diffuse, g_ltt_specular, g_ltt_diffuse, g_rays_color, grad_rays_lt,
+                               grad_albedo_specular, grad_albedo_diffuse, grad_lp}),
+                "rnr_ray_renderer_backward: the upstream gradients, grad_rays_lt, grad_albedo_specular, grad_albedo_diffuse and grad_lp "
+                "must be 4-byte aligned");
     if (grad_lp) RNR_HIP(hipMemsetAsync(grad_lp, 0, (size_t)lp_n * lp_h * lp_w * channels * sizeof(float), as_stream(stream)));
     if (!grad_rays_lt && !grad_albedo_specular && !grad_albedo_diffuse && !grad_lp) return 0;
     P.g_out = g_out; P.g_out_spec = g_out_specular; P.g_out_diff = g_out_diffuse; P.g_ltt_spec = g_ltt_specular; P.g_ltt_diff = g_ltt_diffuse;
@@ -2404,6 +2459,9 @@ extern "C" int rnr_ray_transport(const float* unet_raw, int c_out_pad, const flo
     RNR_REQUIRE(unet_raw && bias && net_in && alpha && rays_uv && rays_lt && albedo_specular && albedo_diffuse,
                 "rnr_ray_transport: null pointer argument");
     RNR_REQUIRE(num_views > 0 && height > 0 && width > 0, "rnr_ray_transport: bad sizes");
+    RNR_REQUIRE(aligned_to(16, {unet_raw, net_in}), "rnr_ray_transport: unet_raw and net_in must be 16-byte aligned");
+    RNR_REQUIRE(aligned_to(4, {bias, alpha, rays_uv, rays_lt, albedo_specular, albedo_diffuse}),
+                "rnr_ray_transport: bias, alpha, rays_uv, rays_lt, albedo_specular and albedo_diffuse must be 4-byte aligned");
     RayTransportParams P;
     // the lane layout of rnr_ray_render: 16 + 16 rays; no probe is read (the size arguments only pass the shared checks)
     if (int e = ray_launch_checks("rnr_ray_transport", num_spec, num_diff, 16, 2, 2, albedo_diff_ch, albedo_spec_ch, c_pad, &P.ni_need))

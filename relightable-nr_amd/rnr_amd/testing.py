@@ -377,3 +377,188 @@ def run_unet_out_backward(g_out, out, apply_tanh, c_pad, guard=False):
     _lib.check(L.rnr_unet_out_backward(_ptr(gd), _ptr(od), int(apply_tanh), _ptr(raw), n, c, h, w, c_pad, _stream()))
     torch.cuda.synchronize()
     return (raw.cpu(), ops.report()) if guard else raw.cpu()
+
+
+# ---- the shading and G-buffer entry points (include/rnr_hip.h sections 2 and 3): one table-driven driver ----
+# A call is written as keyword arguments by the header's parameter names; _lib.PARAMS says which are pointers.  Every device
+# operand goes through _Operands: guarded, it sits at the weakest alignment the header's "Alignment" paragraphs grant it —
+# ALIGN_QUAD for the operands listed here (their kernels move 16 bytes through them), else its element's: ALIGN_DOUBLE for
+# float64, ALIGN_BYTE for bytes, ALIGN_WORD for the rest.
+QUAD_OPERANDS = frozenset([
+    ('rnr_shade_inputs', 'net_in'), ('rnr_shade_inputs', 'textures_host'),
+    ('rnr_ray_render', 'unet_raw'), ('rnr_ray_render', 'net_in'),
+    ('rnr_ray_weights', 'net_in'), ('rnr_ray_weights', 'ray_w'),
+    ('rnr_ray_transport', 'unet_raw'), ('rnr_ray_transport', 'net_in'),
+    ('rnr_frame_prepare', 'gbuffer_workspace'),
+    ('rnr_rasterize_gbuffer', 'workspace'), ('rnr_rasterize_gbuffer_prepared', 'workspace'),
+])
+
+
+def operand_align(fn, param, dtype=torch.float32):
+    """The weakest alignment the header grants operand `param` (for a struct or a table: any of its device pointers) of `fn`."""
+    if (fn, param) in QUAD_OPERANDS:
+        return ALIGN_QUAD
+    return {torch.float64: ALIGN_DOUBLE, torch.uint8: ALIGN_BYTE}.get(dtype, ALIGN_WORD)
+
+
+class In:
+    """An input operand: a CPU tensor in the documented layout.  align: only for a test of the entry point's refusal."""
+    def __init__(self, tensor, align=None):
+        self.tensor, self.align = tensor, align
+
+
+class Out:
+    """An output or scratch operand.  fill: 'nan' (the sentinel when guarded), 'zero' (the header says: zero on entry) or a CPU
+    tensor of the operand's shape to start from.  align: as for In."""
+    def __init__(self, shape, dtype=torch.float32, fill='nan', align=None):
+        self.shape, self.dtype, self.fill, self.align = tuple(shape), dtype, fill, align
+
+
+class Workspace:
+    """A workspace of exactly the bytes its size query returns: Workspace('rnr_gbuffer_workspace_bytes', N, nf, S)."""
+    def __init__(self, query, *sizes, align=None):
+        self.query, self.sizes, self.align = query, sizes, align
+
+
+class Levels(list):
+    """A HOST table of device pointers (textures_host, grad_textures_host): a list of In / Out, each an operand of its own."""
+
+
+class HostInts(list):
+    """A HOST int array (tex_sizes_host)."""
+
+
+class HostFloats:
+    """A HOST float array (pivots_host, the pivots of rnr_rays), from a CPU tensor."""
+    def __init__(self, tensor):
+        self.tensor = tensor.contiguous().float()
+
+
+class Struct(dict):
+    """A struct passed by pointer (rnr_mesh, rnr_gbuffer, rnr_rays): field name -> In / Out / HostFloats / number / None."""
+
+
+class EntryCalls:
+    """A sequence of entry-point calls on operands that live as long as the object.  call() uploads what it is given as In,
+    allocates Out and Workspace, and keeps every device tensor in self.dev by operand name ('net_in', 'textures_host[2]',
+    'out.uv_map'; a name a later call uses again gets '#2', '#3'); a later call may pass self.dev[...] on (the workspace rnr_frame_prepare cleared, to the rasterizer).
+    guard: every operand a Guarded allocation; report() says whether the guards still hold the sentinel."""
+
+    def __init__(self, guard=False):
+        self.ops, self.dev, self.outputs, self.workspaces, self.keep = _Operands(guard), {}, [], [], []
+
+    def _operand(self, fn, param, name, v):
+        """-> the address to pass for operand value v (None -> NULL)."""
+        if v is None:
+            return None
+        if isinstance(v, str):              # '@name': the device operand `name` of an earlier call ('@name+4': 4 bytes into it)
+            name, _, off = v[1:].partition('+')
+            return self.dev[name].data_ptr() + int(off or 0)
+        if isinstance(v, torch.Tensor):
+            if not v.is_cuda:
+                v = In(v)
+            else:
+                return v.data_ptr()
+        k = 2
+        while name in self.dev:             # the same parameter name in a later call: 'v_uvz', then 'v_uvz#2'
+            name, k = '%s#%d' % (name.split('#')[0], k), k + 1
+        if getattr(v, 'align', None) is not None:
+            # a refusal test's operand below its contract: bytes at that address (no typed view of a misaligned payload)
+            assert self.ops.guard, 'an alignment override needs guarded operands'
+            if isinstance(v, In):
+                g = self.ops._carve(name, v.tensor.numel() * v.tensor.element_size(), v.align, 'sentinel').put(v.tensor)
+            elif isinstance(v, Workspace):
+                from . import _lib
+                g = self.ops._carve(name, getattr(_lib.load(), v.query)(*v.sizes), v.align, 'sentinel')
+            else:
+                n = torch.empty(v.shape, dtype=v.dtype, device='meta').numel() * torch.empty((), dtype=v.dtype).element_size()
+                g = self.ops._carve(name, n, v.align, 'sentinel')
+            (self.workspaces if isinstance(v, Workspace) else self.outputs if isinstance(v, Out) else []).append(name)
+            self.dev[name] = g.payload()
+            return g.ptr()
+        if isinstance(v, In):
+            t = self.ops.put(name, v.tensor, operand_align(fn, param, v.tensor.dtype))
+        elif isinstance(v, Workspace):
+            from . import _lib
+            nbytes = getattr(_lib.load(), v.query)(*v.sizes)
+            t = self.ops.new(name, (nbytes,), torch.uint8, operand_align(fn, param), 'empty')
+            self.workspaces.append(name)
+        elif isinstance(v, Out):
+            align = operand_align(fn, param, v.dtype)
+            if isinstance(v.fill, torch.Tensor):
+                assert tuple(v.fill.shape) == v.shape and v.fill.dtype == v.dtype
+                t = self.ops.put(name, v.fill, align)
+            else:
+                integer = v.fill == 'nan' and not v.dtype.is_floating_point      # unguarded too: the sentinel's bit pattern
+                t = self.ops.new(name, v.shape, v.dtype, align, 'empty' if integer else v.fill)
+                if integer and not self.ops.guard:
+                    t.view(-1).view(torch.uint8).copy_(_sentinel_bytes(t.numel() * t.element_size()))
+            self.outputs.append(name)
+        else:
+            raise TypeError('%s: %r' % (name, v))
+        self.dev[name] = t
+        return t.data_ptr()
+
+    def call(self, fn, check=True, **args):
+        """Call entry point `fn` with the header's parameters by name (the stream is added).  -> its return code; with `check`
+        a failure raises RnrError."""
+        from . import _lib
+        from .ops import _stream
+        L = _lib.load()
+        params = [p for p in _lib.PARAMS[fn] if p.name != 'stream']
+        assert set(args) == set(p.name for p in params), (fn, sorted(set(args) ^ set(p.name for p in params)))
+        argv = []
+        for p in params:
+            v = args[p.name]
+            if not p.pointer:
+                argv.append(v)
+            elif isinstance(v, Struct):
+                cls, fields = _lib.STRUCTS[p.type], {}
+                for f in _lib.HEADER.structs[p.type]:
+                    x = v.get(f.name)
+                    if isinstance(x, HostFloats):
+                        arr = (ctypes.c_float * max(x.tensor.numel(), 1))(*x.tensor.reshape(-1).tolist())
+                        self.keep.append(arr)
+                        fields[f.name] = ctypes.cast(arr, ctypes.c_void_p).value
+                    elif f.pointer:
+                        fields[f.name] = self._operand(fn, p.name, '%s.%s' % (p.name, f.name), x)
+                    else:
+                        fields[f.name] = x
+                s = cls(**fields)
+                self.keep.append(s)
+                argv.append(ctypes.byref(s))
+            elif isinstance(v, Levels):
+                ptrs = [self._operand(fn, p.name, '%s[%d]' % (p.name, l), x) for l, x in enumerate(v)]
+                arr = (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
+                self.keep.append(arr)
+                argv.append(arr)
+            elif isinstance(v, HostInts):
+                arr = (ctypes.c_int * max(len(v), 1))(*[int(x) for x in v])
+                self.keep.append(arr)
+                argv.append(ctypes.cast(arr, ctypes.c_void_p))
+            elif isinstance(v, HostFloats):
+                arr = (ctypes.c_float * max(v.tensor.numel(), 1))(*v.tensor.reshape(-1).tolist())
+                self.keep.append(arr)
+                argv.append(ctypes.cast(arr, ctypes.c_void_p))
+            else:
+                argv.append(ctypes.c_void_p(self._operand(fn, p.name, p.name, v) or 0))
+        rc = getattr(L, fn)(*argv, _stream())
+        torch.cuda.synchronize()
+        if check:
+            _lib.check(rc)
+        return rc
+
+    def results(self):
+        """Every Out operand of the calls so far, on the CPU, by operand name."""
+        return {n: self.dev[n].cpu() for n in self.outputs}
+
+    def report(self):
+        return self.ops.report()
+
+
+def run_entry(fn, guard=False, **args):
+    """One call of a shading or G-buffer entry point from CPU tensors -> {Out operand name: CPU tensor} (with guard: and the
+    guard report)."""
+    c = EntryCalls(guard)
+    c.call(fn, **args)
+    return (c.results(), c.report()) if guard else c.results()
