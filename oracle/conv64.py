@@ -213,24 +213,24 @@ def _may1_3x3(n, i, t):
     return o
 
 
-def _may1_wino2(kind, n, i, p):
-    """F(2x2, 2x2), one input parity phase p (stride 2) resp. output parity class p (transposed): the two outputs of that
-    phase / class of every tile whose 3-pixel patch contains input row i.
-      stride 2:   phase image D_p[r] = pad(in)[2 r - p]; tile t (outputs 2t, 2t + 1) reads D_p[2t .. 2t + 2];
-      transposed: class p, out[2 y + p] = sum_a in[y + p - 1 + a] g[a]; tile t (y = 2t, 2t + 1) reads in[2t + p - 1 .. 2t + p + 1],
-                  zero outside the map."""
+def _may1_2x2(kind, n, i, p, m):
+    """F(m x m, 2x2), one input parity phase p (stride 2) resp. output parity class p (transposed): the m outputs of that
+    phase / class of every tile whose (m + 1)-pixel patch contains input row i.
+      stride 2:   phase image D_p[r] = pad(in)[2 r - p]; tile t (outputs m t .. m t + m - 1) reads D_p[m t .. m t + m];
+      transposed: class p, out[2 y + p] = sum_a in[y + p - 1 + a] g[a]; tile t (y = m t .. m t + m - 1) reads
+                  in[m t + p - 1 .. m t + p + m - 1], zero outside the map."""
     on = _out_size(kind, n)
     o = np.zeros(on, bool)
     if kind == 1:
-        assert on % 2 == 0
-        for t in range(on // 2):
-            if any(_reflect1(2 * (2 * t + k) - p, n) == i for k in range(3)):
-                o[2 * t:2 * t + 2] = True
+        assert on % m == 0
+        for t in range(on // m):
+            if any(_reflect1(2 * (m * t + k) - p, n) == i for k in range(m + 1)):
+                o[m * t:m * t + m] = True
     else:
-        assert n % 2 == 0
-        for t in range(n // 2):
-            if 2 * t + p - 1 <= i <= 2 * t + p + 1:
-                o[2 * (2 * t) + p] = o[2 * (2 * t + 1) + p] = True
+        assert n % m == 0
+        for t in range(n // m):
+            if m * t + p - 1 <= i <= m * t + p + m - 1:
+                o[[2 * (m * t + k) + p for k in range(m)]] = True
     return o
 
 
@@ -240,20 +240,18 @@ def nan_must(kind, H, W, i, j):
     return np.outer(_must1(kind, H, i), _must1(kind, W, j))
 
 
-def nan_may(kind, algo, H, W, i, j):
-    """bool [Ho, Wo]: the header's bound on where a non-finite input pixel (i, j) may surface under algorithm `algo`
-    (rnr_conv_algorithm): 0 the window (= nan_must); 1 and 3 the 2 x 2 tiles whose 4 x 4 patch contains it; 4 the 4 x 4 tiles
-    whose 6 x 6 patch contains it; 2 the 2 x 2 tiles, per input parity phase (stride 2) resp. per output parity class
-    (transposed), whose 3 x 3 patch in that phase / class contains it."""
-    if algo == 0:
+def nan_may(kind, m, H, W, i, j):
+    """bool [Ho, Wo]: the header's bound on where a non-finite input pixel (i, j) may surface under a plan whose Winograd tile
+    is `m` (rnr_conv_winograd_tile: the m of F(m x m, .), 0 for a direct plan): 0 the window (= nan_must); kind 0 the m x m
+    tiles whose (m + 2) x (m + 2) patch contains it; kinds 1 and 2 the m x m tiles, per input parity phase (stride 2) resp. per
+    output parity class (transposed), whose (m + 1) x (m + 1) patch in that phase / class contains it."""
+    if m == 0:
         return nan_must(kind, H, W, i, j)
-    if algo in (1, 3, 4):
-        assert kind == 0
-        t = 4 if algo == 4 else 2
-        return np.outer(_may1_3x3(H, i, t), _may1_3x3(W, j, t))
-    assert algo == 2 and kind in (1, 2)
-    m = np.zeros((_out_size(kind, H), _out_size(kind, W)), bool)
+    assert m in (2, 4)
+    if kind == 0:
+        return np.outer(_may1_3x3(H, i, m), _may1_3x3(W, j, m))
+    o = np.zeros((_out_size(kind, H), _out_size(kind, W)), bool)
     for py in range(2):
         for px in range(2):
-            m |= np.outer(_may1_wino2(kind, H, i, py), _may1_wino2(kind, W, j, px))
-    return m
+            o |= np.outer(_may1_2x2(kind, H, i, py, m), _may1_2x2(kind, W, j, px, m))
+    return o

@@ -1,13 +1,30 @@
-"""ORACLE (test infrastructure): the shapes of the guard-band and NaN-tracer tests of the convolutions — ONE table for the
-CPU planner check (tests/test_conv_guard_cpu.py) and the GPU runs (tests/test_gpu_conv_guard.py).
+"""ORACLE (test infrastructure): the plan table of the convolution tests — ONE table for the CPU planner check
+(tests/test_conv_guard_cpu.py), the guard-band sweep and NaN tracer (tests/test_gpu_conv_guard.py) and the value sweep on exact
+inputs (tests/test_gpu_conv_exact_sweep.py, CPU twin tests/test_conv_exact_cpu.py).
 
 Together the cases reach every launcher of CONV_TILES (conv.hip) for every kind it is instantiated for, the emulation rows in
-both formats, and the features FEATURES lists.  The C ABI reveals the algorithm, the split depth (workspace bytes) and, for a
-maskable plan, the tile count — not the CONV_TILES row of a plan that cannot be masked.  direct_row() below therefore restates
-the tile-size arithmetic of try_halo / try_gather (default thresholds); the CPU test holds it against everything the ABI does
-reveal (split depth of every case — it depends on the tile count —, tile count where maskable), and each case names the row
-it is there for.  Channel counts are the smallest that still land on the row (16 - 64 inputs wherever the thresholds allow);
-the Winograd plans need 256 workgroups unsplit (stride 2 / transposed: 200) and 4 chunks per split-K slice.
+both formats, and the features FEATURES lists.  The eleven families, by the lower-case names of conv.hip's ConvFamily:
+  gather    conv_mfma_kernel          direct, any map                      GATHER_ROWS
+  halo      conv_halo_kernel          direct, exact fp32                   HALO_ROWS
+  emu       conv_halo_emu_kernel      direct, bf16x6 / f16x3 (HALO_EMU)    EMU_ROWS
+  wino      conv_wino_kernel          F(2x2, 3x3)                          WINO_TILES, FAMILY: (algorithm, m)
+  wino80    conv_wino80_kernel        F(2x2, 3x3), the 80-column out layer
+  wino2     conv_wino2_kernel         F(2x2, 2x2), stride 2
+  wino2t    conv_wino2p_kernel        F(2x2, 2x2), transposed
+  wino4     conv_wino4_kernel         F(4x4, 3x3)
+  wino42t   conv_wino42p_kernel       F(4x4, 2x2), transposed              (RNR_CONV_WINOGRAD42)
+  wino80f4  conv_wino80f4_kernel      F(4x4, 3x3), the 80-column out layer (RNR_CONV_WINOGRAD4_OUT)
+  wino42s   conv_wino42s_kernel       F(4x4, 2x2), stride 2                (RNR_CONV_WINOGRAD42S)
+A family is the pair (rnr_conv_algorithm, rnr_conv_winograd_tile): the F(4x4, .) kernels share the algorithm codes 2 and 3
+with the F(2x2, .) ones, and only m — the m of F(m x m, .), 0 for a direct plan — tells them apart.
+
+The C ABI reveals the algorithm, m, the split depth (workspace bytes) and, for a maskable plan, the tile count — not the
+CONV_TILES row of a plan that cannot be masked.  direct_row() below therefore restates the tile-size arithmetic of try_halo /
+try_gather (default thresholds); the CPU test holds it against everything the ABI does reveal (split depth of every case — it
+depends on the tile count —, tile count where maskable), and each case names the row it is there for.  Channel counts are the
+smallest that still land on the row (16 - 64 inputs wherever the thresholds allow); the Winograd plans need 256 workgroups
+unsplit (F(2x2, 2x2): 200) and 4 chunks per split-K slice; the three F(4x4, .) kernels behind a flag of their own have no
+split-K form.
 
 UNREACHABLE instantiations (the planner never selects them, whatever the shape; at most 3 — the CPU test holds that cap):
   halo 32 x 8 x 64, kind 1    the narrow-column branch of try_halo needs a 4x4 stride-2 call that is NOT wide_columns(), i.e.
@@ -15,8 +32,13 @@ UNREACHABLE instantiations (the planner never selects them, whatever the shape; 
   halo 32 x 4 x 64, kind 1    the gather kernel.  (32 x 4 x 64 is otherwise reached through the narrow branch, kinds 0 and 2,
                               or through RNR_CFG4_MAX, kind 0 only.)
 """
+import ctypes
+
 pad16 = lambda c: (c + 15) // 16 * 16
+# RNR_CONV_* of include/rnr_hip.h (tests/test_conv_guard_cpu.py holds every CONV_* name here against rnr_amd._lib's)
 CONV_F32_EMU_BF16X6, CONV_F32_EMU_F16X3, CONV_WINOGRAD, CONV_WINOGRAD4 = 2, 4, 8, 16
+CONV_WINOGRAD42, CONV_WINOGRAD4_OUT, CONV_WINOGRAD42S = 32, 64, 128
+EMU_FORMATS = CONV_F32_EMU_BF16X6 | CONV_F32_EMU_F16X3
 
 # the direct rows of CONV_TILES: (pixel tile width, height, columns) -> kinds that have a launcher
 HALO_ROWS = {(32, 8, 64): (0, 1, 2), (32, 8, 80): (0, 1, 2), (32, 8, 128): (0, 1, 2), (32, 4, 128): (0, 1, 2),
@@ -30,7 +52,7 @@ def direct_row(kind, N, H, W, cins, c_out, flags=0):
     """The CONV_TILES row try_halo / try_gather of conv.hip select for a call that runs the direct kernels, restated from
     their tile-size arithmetic with the default thresholds: {'family', 'tile' (tw, th, bn), 'mtiles', 'wgs', 'splitk',
     'maskable'}."""
-    emu = bool(flags & (CONV_F32_EMU_BF16X6 | CONV_F32_EMU_F16X3))
+    emu = bool(flags & EMU_FORMATS)
     s2 = kind == 1
     c = pad16(c_out)
     Ho, Wo = (H // 2, W // 2) if s2 else (H, W)
@@ -86,13 +108,20 @@ FEATURES = ('splitk_direct', 'splitk_wino', 'splitk_wino2', 'splitk_wino4', 'two
             'tiles_straddle_views', 'pad_in_20_32', 'pad_out_78_80', 'pad_out_72_80', 'one_tile_per_view')
 
 B, F, W, W4 = CONV_F32_EMU_BF16X6, CONV_F32_EMU_F16X3, CONV_WINOGRAD, CONV_WINOGRAD | CONV_WINOGRAD4
-WINO_TILES = {'wino80': (16, 4, 80), 'wino4': (32, 16, 64), 'wino': (16, 8, 64), 'wino2': (16, 16, 128), 'wino2t': (16, 8, 64)}
-WINO_ALGO = {'wino80': 3, 'wino4': 4, 'wino': 1, 'wino2': 2, 'wino2t': 2}
+W42T, W42S, W4OUT = W | CONV_WINOGRAD42, W | CONV_WINOGRAD42S, W4 | CONV_WINOGRAD4_OUT
+# the Winograd rows of CONV_TILES: family -> (pixel tile width, height, columns), and what the C ABI reports for the family:
+# (rnr_conv_algorithm, rnr_conv_winograd_tile); WINO_KIND: the one kind a family is instantiated for where that is not 0.
+WINO_TILES = {'wino80': (16, 4, 80), 'wino4': (32, 16, 64), 'wino': (16, 8, 64), 'wino2': (16, 16, 128), 'wino2t': (16, 8, 64),
+              'wino42t': (32, 16, 64), 'wino42s': (32, 16, 64), 'wino80f4': (16, 16, 80)}
+FAMILY = {'wino80': (3, 2), 'wino4': (4, 4), 'wino': (1, 2), 'wino2': (2, 2), 'wino2t': (2, 2),
+          'wino42t': (2, 4), 'wino42s': (2, 4), 'wino80f4': (3, 4)}
+WINO_KIND = {'wino2': 1, 'wino42s': 1, 'wino2t': 2, 'wino42t': 2}
 
 
 def _case(kind, N, H, W_, cins, c_out, flags, family, tile, split, feats=(), tracer=False):
+    algo, m = FAMILY.get(family, (0, 0))
     return dict(kind=kind, N=N, H=H, W=W_, cins=list(cins), c_out=c_out, flags=flags, family=family, tile=tile, split=split,
-                algo=WINO_ALGO.get(family, 0), feats=tuple(feats), tracer=tracer,
+                algo=algo, m=m, feats=tuple(feats), tracer=tracer,
                 id='k%d-%dx%dx%d-%s-%d-f%d' % (kind, N, H, W_, '+'.join(str(c) for c in cins), c_out, flags))
 
 
@@ -179,11 +208,37 @@ CASES += [
     _case(1, 2, 128, 128, [128], 512, W, 'wino2', (16, 16, 128), 2, ['splitk_wino2'], tracer=True),      # 128 workgroups, 8 chunks
     _case(2, 13, 32, 64, [16, 32], 64, W, 'wino2t', (16, 8, 64), 1, ['two_sources_unequal'], tracer=True),       # 13 x 16 = 208
     _case(2, 1, 64, 64, [80, 48], 256, W, 'wino2t', (16, 8, 64), 2, ['two_sources_unequal', 'splitk_wino2'], tracer=True),   # 128 workgroups; slice 1 straddles the concat
+    # F(4x4, 2x2) transposed: one parity class of 32 x 16 input pixels, 256 workgroups (tiles x column tiles x 4 classes)
+    _case(2, 16, 32, 64, [16, 32], 64, W42T, 'wino42t', (32, 16, 64), 1, ['two_sources_unequal'], tracer=True),      # 16 x 4 tiles x 4 classes = 256
+    _case(2, 64, 16, 32, [16], 64, W42T, 'wino42t', (32, 16, 64), 1, ['one_tile_per_view', 'one_tile_high'], tracer=True),
+    _case(2, 64, 16, 32, [16, 16], 64, W42T, 'wino42t', (32, 16, 64), 1),                    # the value sweep's case (C)
+    # F(4x4, 2x2) stride 2: 32 x 16 output pixels
+    _case(1, 64, 32, 64, [16], 256, W42S, 'wino42s', (32, 16, 64), 1, ['one_tile_per_view', 'one_tile_high'], tracer=True),   # 64 x 4 column tiles = 256; value sweep (C)
+    _case(1, 32, 64, 128, [16, 32], 128, W42S, 'wino42s', (32, 16, 64), 1, ['two_sources_unequal'], tracer=True),            # 32 x 4 tiles x 2 = 256
+    # F(4x4, 3x3) of the out layer: 256 tiles of 16 x 16 output pixels, maskable
+    _case(0, 256, 16, 16, [16, 32], 78, W4OUT, 'wino80f4', (16, 16, 80), 1, ['one_tile_per_view', 'two_sources_unequal', 'pad_out_78_80'], tracer=True),
+    _case(0, 4, 128, 128, [20], 78, W4OUT, 'wino80f4', (16, 16, 80), 1, ['pad_in_20_32', 'pad_out_78_80'], tracer=True),
+    _case(0, 256, 16, 16, [16, 16], 78, W4OUT, 'wino80f4', (16, 16, 80), 1),                 # the value sweep's case (B)
 ]
 
 # (c) ReLU and NaN: one 3x3 shape every family runs — direct, F(2x2, 3x3), F(4x4, 3x3), both emulation formats
 RELU_NAN_SHAPE = (0, 16, 64, 64, [16], 128)
-RELU_NAN_FLAGS = ((0, 0), (W, 1), (W4, 4), (B, 0), (F, 0))          # (flags, algorithm the planner must report)
+RELU_NAN_FLAGS = ((0, 0, 0), (W, 1, 2), (W4, 4, 4), (B, 0, 0), (F, 0, 0))   # (flags, algorithm and m the planner must report)
+
+
+def desc(c):
+    """rnr_conv_desc of a case."""
+    from rnr_amd.testing import conv_desc
+    return conv_desc(c['kind'], c['cins'], c['c_out'], c['flags'])
+
+
+def split_depth(L, c):
+    """The split-K depth of a case's plan, from the workspace the host planner of library handle `L` asks for: 256 bytes
+    unsplit, otherwise one float32 slab of the padded output per slice."""
+    d = desc(c)
+    ws = L.rnr_conv_workspace_bytes(ctypes.byref(d), c['N'], c['H'], c['W'])
+    oh, ow = out_hw(c['kind'], c['H'], c['W'])
+    return 1 if ws == 256 else ws // (c['N'] * oh * ow * d.c_out_pad * 4)
 
 
 def out_hw(kind, H, W_):
@@ -192,9 +247,8 @@ def out_hw(kind, H, W_):
 
 def mask_tile(c):
     """(tile width, height) of the MASKED launch of a case (rnr_conv_tile_count describes that launch): the out layer's
-    Winograd kernel takes the mask on its own 16 x 4 tiles, every other Winograd plan runs the direct kernels when masked."""
-    if c['family'] == 'wino80':
-        return (16, 4)
-    if c['family'] in ('halo', 'emu'):
+    Winograd kernels take the mask on their own 16 x 4 resp. 16 x 16 tiles, every other Winograd plan runs the direct kernels
+    when masked."""
+    if c['family'] in ('halo', 'emu', 'wino80', 'wino80f4'):
         return c['tile'][:2]
     return direct_row(c['kind'], c['N'], c['H'], c['W'], c['cins'], c['c_out'], 0)['tile'][:2]

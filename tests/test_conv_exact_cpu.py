@@ -14,10 +14,9 @@ import torch.nn.functional as F
 from oracle import conv64 as o64
 from oracle import conv_guard_cases as cg
 from rnr_amd import _lib
-from rnr_amd.testing import conv_desc
-from test_conv_guard_cpu import test_case_gets_the_plan_it_names as check_table_case
-from test_gpu_conv_exact_sweep import (ALL_CASES, BITWISE_CASES, EPS, F4_CASES, F42_CASES, emulation_ratio, exact_inputs, locate,
-                                       ratio_map, split_depth, spread)
+from test_conv_guard_cpu import launcher_key, test_case_gets_the_plan_it_names as check_table_case, wanted_launchers
+from test_gpu_conv_exact_sweep import (ALL_CASES, BITWISE_CASES, EPS, F4_CASES, F42_CASES, NOT_VALUE_SWEPT, emulation_ratio,
+                                       exact_inputs, locate, ratio_map, spread)
 
 ids = lambda cases: [c['id'] for c in cases]
 
@@ -55,51 +54,40 @@ def test_exact_inputs_are_exact_in_float32(c):
 
 @pytest.mark.parametrize('c', ALL_CASES, ids=ids(ALL_CASES))
 def test_case_lands_on_the_row_it_names(c):
-    """Table rows: everything tests/test_conv_guard_cpu.py holds a row to.  The three cases from the F(4x4, .) kernels' own
-    modules: algorithm, Winograd tile 4, no split-K, and a map the kernel's workgroup tile divides."""
-    if any(c is t for t in cg.CASES):
-        check_table_case(c)
-        return
-    L = _lib.load()
-    d = conv_desc(c['kind'], c['cins'], c['c_out'], c['flags'])
-    assert L.rnr_conv_algorithm(ctypes.byref(d), c['N'], c['H'], c['W']) == c['algo']
-    assert L.rnr_conv_winograd_tile(ctypes.byref(d), c['N'], c['H'], c['W']) == 4
-    assert split_depth(L, c) == c['split'] == 1
-    oh, ow = cg.out_hw(c['kind'], c['H'], c['W'])
-    gh, gw = (c['H'], c['W']) if c['kind'] == 2 else (oh, ow)
-    assert gh % c['tile'][1] == 0 and gw % c['tile'][0] == 0 and d.c_out_pad % c['tile'][2] == 0
+    """Everything tests/test_conv_guard_cpu.py holds a table row to."""
+    check_table_case(c)
 
 
 def test_table_rows_have_the_winograd_tile_their_family_names():
-    """rnr_conv_winograd_tile of the table's Winograd rows: 4 for wino4, 2 for the F(2x2, .) families (the F(4x4, .) flags of
-    the out layer and of the stride-2 / transposed kernels are not set in the table)."""
+    """rnr_conv_winograd_tile of every table row: the m its family names — 4 for the F(4x4, .) families, 2 for the F(2x2, .)
+    ones, 0 for a direct plan."""
     L = _lib.load()
     for c in cg.CASES:
-        d = conv_desc(c['kind'], c['cins'], c['c_out'], c['flags'])
-        want = 0 if c['algo'] == 0 else (4 if c['family'] == 'wino4' else 2)
-        assert L.rnr_conv_winograd_tile(ctypes.byref(d), c['N'], c['H'], c['W']) == want, c['id']
+        assert L.rnr_conv_winograd_tile(ctypes.byref(cg.desc(c)), c['N'], c['H'], c['W']) == c['m'], c['id']
 
 
 def test_the_two_sweeps_cover_every_reachable_launcher():
-    """Every (CONV_TILES row, kind, emulation format) that has a launcher and is reachable sits in exactly one of the sweeps —
-    bitwise (A) or bounded (B) — and every row of the table has exactly one id."""
-    key = lambda c: (c['family'], c['tile'], c['kind'], c['flags'] & 6)
-    bitwise, bounded = {key(c) for c in BITWISE_CASES}, {key(c) for c in F4_CASES + F42_CASES}
-    want = set()
-    for fam, rows, fmts in (('gather', cg.GATHER_ROWS, (0,)), ('halo', cg.HALO_ROWS, (0,)), ('emu', cg.EMU_ROWS, (2, 4))):
-        want |= {(fam, t, k, f) for t, kinds in rows.items() for k in kinds for f in fmts}
-    want -= {(fam, t, k, 0) for fam, t, k in cg.UNREACHABLE}
-    kind_of = {'wino80': 0, 'wino4': 0, 'wino': 0, 'wino2': 1, 'wino2t': 2}
-    assert set(kind_of) == set(cg.WINO_TILES)
-    want |= {(fam, t, kind_of[fam], 0) for fam, t in cg.WINO_TILES.items()}
-    assert len(want) == 3 * 3 + (8 * 3 - 3) + 2 * 14 + 5
+    """Every (CONV_TILES row, kind, emulation format) that has a launcher and is reachable has a value test — bitwise (A),
+    bounded (B) or at the gate (C) — and every row of the table sits in exactly one of the three or is an F(4x4, .) row named
+    in NOT_VALUE_SWEPT."""
+    bitwise, bounded = {launcher_key(c) for c in BITWISE_CASES}, {launcher_key(c) for c in F4_CASES + F42_CASES}
+    want = wanted_launchers()
     assert bitwise & bounded == set()
     assert want - (bitwise | bounded) == set(), sorted(want - (bitwise | bounded))
-    assert bitwise <= want and {k for k in bounded if k[0] in cg.WINO_TILES} == {('wino4', (32, 16, 64), 0, 0)}
-    assert {c['family'] for c in F4_CASES + F42_CASES} == {'wino4', 'wino80f4', 'wino42p', 'wino42s'}
+    assert bitwise | bounded <= want
+    f4 = {f for f, (_, m) in cg.FAMILY.items() if m == 4}
+    assert {k[0] for k in bounded} == f4 == {'wino4', 'wino80f4', 'wino42t', 'wino42s'}, f4 - {k[0] for k in bounded}
+    assert ALL_CASES is cg.CASES
     all_ids = ids(ALL_CASES)
-    assert len(set(all_ids)) == len(all_ids) == len(cg.CASES) + 3
-    assert {c['id'] for c in cg.CASES} <= set(all_ids)
+    assert len(set(all_ids)) == len(all_ids) == len(ALL_CASES) == len(cg.CASES)
+    swept = ids(BITWISE_CASES) + ids(F4_CASES) + ids(F42_CASES)
+    assert len(set(swept)) == len(swept)
+    assert sum(len(v) for v in NOT_VALUE_SWEPT.values()) == 5
+    for fam in {c['family'] for c in cg.CASES} | set(NOT_VALUE_SWEPT):
+        rest = sorted(c['id'] for c in cg.CASES if c['family'] == fam and c['id'] not in swept)
+        assert rest == sorted(NOT_VALUE_SWEPT.get(fam, ())), '%s: rows without a value test %s, listed as such %s' % (
+            fam, rest, NOT_VALUE_SWEPT.get(fam, ()))
+        assert not rest or cg.FAMILY[fam][1] == 4
     assert {c['split'] >= 2 for c in F4_CASES} == {False, True}
     feats = {f for c in BITWISE_CASES for f in c['feats']}
     assert {'splitk_direct', 'splitk_wino', 'splitk_wino2', 'two_sources_unequal'} <= feats

@@ -104,26 +104,25 @@ def test_operands_carve_inputs_and_outputs_on_cpu():
 
 # ---- the case table against the host planner ----
 
-def _desc(c):
-    return T.conv_desc(c['kind'], c['cins'], c['c_out'], c['flags'])
-
-
-def _split_depth(L, c):
-    d = _desc(c)
-    ws = L.rnr_conv_workspace_bytes(ctypes.byref(d), c['N'], c['H'], c['W'])
-    oh, ow = cg.out_hw(c['kind'], c['H'], c['W'])
-    return 1 if ws == 256 else ws // (c['N'] * oh * ow * d.c_out_pad * 4)
+def test_flag_values_are_the_library_s():
+    """Every CONV_* flag oracle/conv_guard_cases.py names has the value of include/rnr_hip.h's RNR_CONV_* (as rnr_amd._lib reads
+    it from the header)."""
+    names = [n for n in dir(cg) if n.startswith('CONV_')]
+    assert {'CONV_WINOGRAD42', 'CONV_WINOGRAD4_OUT', 'CONV_WINOGRAD42S'} <= set(names)
+    for n in names:
+        assert getattr(cg, n) == getattr(_lib, n), n
 
 
 @pytest.mark.parametrize('c', cg.CASES, ids=[c['id'] for c in cg.CASES])
 def test_case_gets_the_plan_it_names(c):
-    """Algorithm, split depth (workspace bytes / output bytes) and — where the masked launch is maskable — the tile count of
-    every case, from the host planner; for the direct kernels also that the restated tile-size arithmetic (direct_row) names
-    the case's row and agrees with the planner's split depth, which is a function of the row's tile count."""
+    """Algorithm, Winograd tile, split depth (workspace bytes / output bytes) and — where the masked launch is maskable — the
+    tile count of every case, from the host planner; for the direct kernels also that the restated tile-size arithmetic
+    (direct_row) names the case's row and agrees with the planner's split depth, which is a function of the row's tile count."""
     L = _lib.load()
-    d = _desc(c)
+    d = cg.desc(c)
     assert L.rnr_conv_algorithm(ctypes.byref(d), c['N'], c['H'], c['W']) == c['algo']
-    assert _split_depth(L, c) == c['split']
+    assert L.rnr_conv_winograd_tile(ctypes.byref(d), c['N'], c['H'], c['W']) == c['m']
+    assert cg.split_depth(L, c) == c['split']
     assert L.rnr_conv_sync_bytes(ctypes.byref(d), c['N'], c['H'], c['W']) >= 256 + 16 * 8 * c['N'] * d.c_out_pad
     tiles = L.rnr_conv_tile_count(ctypes.byref(d), c['N'], c['H'], c['W'])
     if c['algo'] == 0:
@@ -133,7 +132,8 @@ def test_case_gets_the_plan_it_names(c):
         rows = {'halo': cg.HALO_ROWS, 'emu': cg.EMU_ROWS, 'gather': cg.GATHER_ROWS}[c['family']]
         assert c['kind'] in rows[c['tile']]
     else:
-        assert c['tile'] == cg.WINO_TILES[c['family']] and c['algo'] == cg.WINO_ALGO[c['family']]
+        assert c['tile'] == cg.WINO_TILES[c['family']] and (c['algo'], c['m']) == cg.FAMILY[c['family']]
+        assert c['kind'] == cg.WINO_KIND.get(c['family'], 0)
         oh, ow = cg.out_hw(c['kind'], c['H'], c['W'])
         gh, gw = (oh, ow) if c['kind'] != 2 else (c['H'], c['W'])
         assert gh % c['tile'][1] == 0 and gw % c['tile'][0] == 0 and d.c_out_pad % c['tile'][2] == 0
@@ -163,6 +163,23 @@ def test_case_gets_the_plan_it_names(c):
         assert c['c_out'] == 72
 
 
+def wanted_launchers():
+    """Every (family, tile, kind, emulation format) of CONV_TILES that has a launcher the planner can reach: the direct rows
+    without the documented unreachable ones, and one entry per Winograd family of WINO_TILES."""
+    want = set()
+    for fam, rows, fmts in (('gather', cg.GATHER_ROWS, (0,)), ('halo', cg.HALO_ROWS, (0,)),
+                            ('emu', cg.EMU_ROWS, (cg.CONV_F32_EMU_BF16X6, cg.CONV_F32_EMU_F16X3))):
+        want |= {(fam, t, k, f) for t, kinds in rows.items() for k in kinds for f in fmts if (fam, t, k) not in cg.UNREACHABLE}
+    want |= {(fam, t, cg.WINO_KIND.get(fam, 0), 0) for fam, t in cg.WINO_TILES.items()}
+    assert len(cg.GATHER_ROWS) == 3 and len(cg.HALO_ROWS) == 8 and len(cg.EMU_ROWS) == 6 and len(cg.WINO_TILES) == 8
+    assert set(cg.FAMILY) == set(cg.WINO_TILES) and set(cg.WINO_KIND) <= set(cg.WINO_TILES)
+    assert len(want) == 3 * 3 + (8 * 3 - 3) + 2 * 14 + 8
+    return want
+
+
+launcher_key = lambda c: (c['family'], c['tile'], c['kind'], c['flags'] & cg.EMU_FORMATS)
+
+
 def test_cases_reach_every_launcher_and_feature():
     """Every (CONV_TILES row, kind, emulation format) that has a launcher is named by a case, except the documented
     unreachable ones — at most 3; every feature is named; split-K is reached on a direct, an F(2x2, 3x3), both F(2x2, 2x2)
@@ -170,26 +187,28 @@ def test_cases_reach_every_launcher_and_feature():
     assert len(cg.UNREACHABLE) <= 3
     for fam, tile, kind in cg.UNREACHABLE:
         assert fam in cg.__doc__ and ('%d x %d x %d, kind %d' % (tile + (kind,))) in cg.__doc__
-    have = {(c['family'], c['tile'], c['kind'], c['flags'] & 6) for c in cg.CASES}
-    want = set()
-    for fam, rows, fmts in (('gather', cg.GATHER_ROWS, (0,)), ('halo', cg.HALO_ROWS, (0,)), ('emu', cg.EMU_ROWS, (2, 4))):
-        want |= {(fam, t, k, f) for t, kinds in rows.items() for k in kinds for f in fmts if (fam, t, k) not in cg.UNREACHABLE}
-    want |= {('wino80', (16, 4, 80), 0, 0), ('wino4', (32, 16, 64), 0, 0), ('wino', (16, 8, 64), 0, 0),
-             ('wino2', (16, 16, 128), 1, 0), ('wino2t', (16, 8, 64), 2, 0)}
-    assert len(cg.GATHER_ROWS) == 3 and len(cg.HALO_ROWS) == 8 and len(cg.EMU_ROWS) == 6
+    for fam in list(cg.WINO_TILES) + ['gather', 'halo', 'emu']:
+        assert '\n  %s ' % fam in cg.__doc__, fam
+    have = {launcher_key(c) for c in cg.CASES}
+    want = wanted_launchers()
     assert want - have == set(), sorted(want - have)
     named = {f for c in cg.CASES for f in c['feats']}
     assert named == set(cg.FEATURES)
     split = {(c['family'], c['kind']) for c in cg.CASES if c['split'] >= 2}
     assert {('wino', 0), ('wino2', 1), ('wino2t', 2), ('wino4', 0)} <= split and any(f in ('halo', 'gather') for f, _ in split)
-    # the tracer runs: every algorithm, split and unsplit where the table has both, both emulation formats
-    tr = {(c['algo'], c['split'] >= 2, c['flags'] & 6) for c in cg.CASES if c['tracer']}
-    assert {(a, s, 0) for a in (0, 1, 2, 4) for s in (False, True)} | {(3, False, 0)} <= tr
-    assert {f for a, _, f in tr if a == 0} == {0, 2, 4}
+    # the tracer runs: every (algorithm, m) pair, split and unsplit where the table has both, both emulation formats
+    tr = {(c['algo'], c['m'], c['split'] >= 2, c['flags'] & cg.EMU_FORMATS) for c in cg.CASES if c['tracer']}
+    assert {(a, m, s, 0) for a, m in ((0, 0), (1, 2), (2, 2), (4, 4)) for s in (False, True)} <= tr
+    assert {(3, 2, False, 0), (2, 4, False, 0), (3, 4, False, 0)} <= tr
+    assert {(a, m) for a, m, _, _ in tr} == set(cg.FAMILY.values()) | {(0, 0)}
+    assert {f for a, _, _, f in tr if a == 0} == {0, cg.CONV_F32_EMU_BF16X6, cg.CONV_F32_EMU_F16X3}
+    # every Winograd family has a tracer run of its own (wino2 and wino2t, wino42s and wino42t share their pair)
+    assert {c['family'] for c in cg.CASES if c['tracer']} >= set(cg.WINO_TILES)
     L = _lib.load()
     kind, N, H, W, cins, c_out = cg.RELU_NAN_SHAPE
-    for flags, algo in cg.RELU_NAN_FLAGS:
-        assert L.rnr_conv_algorithm(ctypes.byref(T.conv_desc(kind, cins, c_out, flags)), N, H, W) == algo
+    for flags, algo, m in cg.RELU_NAN_FLAGS:
+        d = T.conv_desc(kind, cins, c_out, flags)
+        assert L.rnr_conv_algorithm(ctypes.byref(d), N, H, W) == algo and L.rnr_conv_winograd_tile(ctypes.byref(d), N, H, W) == m
 
 
 # ---- the footprint of one non-finite pixel ----
@@ -213,11 +232,11 @@ def _brute_must(kind, H, W, i, j):
     return m
 
 
-def _brute_may(kind, algo, H, W, i, j):
+def _brute_may(kind, t, H, W, i, j):
+    """Winograd tile t: loops over every tile's patch."""
     oh, ow = cg.out_hw(kind, H, W)
     m = np.zeros((oh, ow), bool)
-    if algo in (1, 3, 4):
-        t = 4 if algo == 4 else 2
+    if kind == 0:
         for ty in range(H // t):
             for tx in range(W // t):
                 patch = {(_reflect(t * ty - 1 + a, H), _reflect(t * tx - 1 + b, W)) for a in range(t + 2) for b in range(t + 2)}
@@ -226,37 +245,38 @@ def _brute_may(kind, algo, H, W, i, j):
         return m
     for py in range(2):
         for px in range(2):
-            if kind == 1:       # phase image D[r][c] = pad(in)[2 r - py][2 c - px]; tile (ty, tx) reads D[2 ty .. 2 ty + 2][2 tx .. 2 tx + 2]
-                for ty in range(oh // 2):
-                    for tx in range(ow // 2):
-                        patch = {(_reflect(2 * (2 * ty + a) - py, H), _reflect(2 * (2 * tx + b) - px, W))
-                                 for a in range(3) for b in range(3)}
+            if kind == 1:       # phase image D[r][c] = pad(in)[2 r - py][2 c - px]; tile (ty, tx) reads D[t ty .. t ty + t][t tx .. t tx + t]
+                for ty in range(oh // t):
+                    for tx in range(ow // t):
+                        patch = {(_reflect(2 * (t * ty + a) - py, H), _reflect(2 * (t * tx + b) - px, W))
+                                 for a in range(t + 1) for b in range(t + 1)}
                         if (i, j) in patch:
-                            m[2 * ty:2 * ty + 2, 2 * tx:2 * tx + 2] = True
-            else:               # class (py, px): out[2 y + py][2 x + px], tile = y in {2 ty, 2 ty + 1}, reads in[2 ty + py - 1 .. + 1]
-                for ty in range(H // 2):
-                    for tx in range(W // 2):
-                        if 2 * ty + py - 1 <= i <= 2 * ty + py + 1 and 2 * tx + px - 1 <= j <= 2 * tx + px + 1:
-                            for dy in range(2):
-                                for dx in range(2):
-                                    m[2 * (2 * ty + dy) + py, 2 * (2 * tx + dx) + px] = True
+                            m[t * ty:t * ty + t, t * tx:t * tx + t] = True
+            else:               # class (py, px): out[2 y + py][2 x + px], tile = y in t ty .. t ty + t - 1, reads in[t ty + py - 1 .. + t - 1]
+                for ty in range(H // t):
+                    for tx in range(W // t):
+                        if t * ty + py - 1 <= i <= t * ty + py + t - 1 and t * tx + px - 1 <= j <= t * tx + px + t - 1:
+                            for dy in range(t):
+                                for dx in range(t):
+                                    m[2 * (t * ty + dy) + py, 2 * (t * tx + dx) + px] = True
     return m
 
 
-@pytest.mark.parametrize('kind,algo,H,W', [(0, 0, 5, 6), (1, 0, 6, 8), (2, 0, 3, 5), (0, 1, 4, 8), (0, 3, 6, 4), (0, 4, 8, 12),
-                                           (1, 2, 8, 12), (2, 2, 4, 6), (0, 0, 2, 2), (1, 0, 2, 4)])
-def test_nan_footprints_match_brute_force(kind, algo, H, W):
+@pytest.mark.parametrize('kind,m,H,W', [(0, 0, 5, 6), (1, 0, 6, 8), (2, 0, 3, 5), (0, 2, 4, 8), (0, 2, 6, 4), (0, 4, 8, 12),
+                                        (1, 2, 8, 12), (2, 2, 4, 6), (0, 0, 2, 2), (1, 0, 2, 4),
+                                        (1, 4, 16, 24), (2, 4, 8, 12), (1, 4, 8, 16)])
+def test_nan_footprints_match_brute_force(kind, m, H, W):
     """nan_must / nan_may (separable index arithmetic) against loops over every output's window resp. every tile's patch, for
-    EVERY input pixel of a small map; and the sandwich must <= may, with equality for the direct algorithm."""
+    EVERY input pixel of a small map; and the sandwich must <= may, with equality for a direct plan."""
     for i in range(H):
         for j in range(W):
-            must, may = nan_must(kind, H, W, i, j), nan_may(kind, algo, H, W, i, j)
+            must, may = nan_must(kind, H, W, i, j), nan_may(kind, m, H, W, i, j)
             assert must.shape == cg.out_hw(kind, H, W) and must.any()
             assert (must == _brute_must(kind, H, W, i, j)).all(), (i, j)
-            if algo == 0:
+            if m == 0:
                 assert (may == must).all()
             else:
-                assert (may == _brute_may(kind, algo, H, W, i, j)).all(), (i, j)
+                assert (may == _brute_may(kind, m, H, W, i, j)).all(), (i, j)
                 assert (may | ~must).all(), (i, j)
 
 

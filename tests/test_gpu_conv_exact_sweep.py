@@ -4,28 +4,36 @@ straddles the concat included), on the EXACT inputs of oracle.conv64.exact_conv_
 oracle.conv64.conv64.  tests/test_conv_exact_cpu.py proves on the CPU what this module rests on: that the inputs are exact on
 every case used, that every case lands on the row it names, and that the two sweeps below cover every reachable launcher.
 
-(A) BITWISE — gather, halo, emu (both formats), wino, wino80, wino2, wino2t.  Integer activations in [-3, 3], scales in
-    {1/2, 1, 2}, shifts multiples of 1/2, weights multiples of 2^-3: every product is a multiple of 2^-4 and every partial sum
-    fits float32's significand, so any summation order, the F(2x2, 3x3) and F(2x2, 2x2) transforms (the data transforms only
-    add, the weight transforms divide by 2 and 4), the bf16x6 / f16x3 operand splits and the sums of split-K slabs all give
-    conv64(...).float() exactly.  out_raw — prefilled with a NaN whose payload is the element index — is compared with it as
-    int32: no tolerance appears anywhere in (A).  A transposed tap order, a swapped phase or parity class, a halo staged from
-    the wrong row fail, and the message names the workgroup tile and the position inside it.
+(A) BITWISE — the rows whose Winograd tile is not 4: gather, halo, emu (both formats), wino, wino80, wino2, wino2t.
+    Integer activations in [-3, 3], scales in {1/2, 1, 2}, shifts multiples of 1/2, weights multiples of 2^-3: every product
+    is a multiple of 2^-4 and every partial sum fits float32's significand, so any summation order, the F(2x2, 3x3) and
+    F(2x2, 2x2) transforms (the data transforms only add, the weight transforms divide by 2 and 4), the bf16x6 / f16x3 operand
+    splits and the sums of split-K slabs all give conv64(...).float() exactly.  out_raw — prefilled with a NaN whose payload is
+    the element index — is compared with it as int32: no tolerance appears anywhere in (A).  A transposed tap order, a swapped
+    phase or parity class, a halo staged from the wrong row fail, and the message names the workgroup tile and the position
+    inside it.
     The activation of a source is NONE or ReLU, as exact_conv_case draws it: LeakyReLU's 0.2 is not dyadic, so that
     activation stays with the Gaussian tests (test_gpu_unet.py, test_gpu_conv_guard.py).
 
 (B) BOUNDED PER ELEMENT — the F(4x4, 3x3) kernels conv_wino4_kernel (the three wino4 rows of the table) and
-    conv_wino80f4_kernel (the smallest case of tests/test_gpu_conv_wino80f4.py).  Their weight transform divides by 81/64,
-    243/128, ... : no choice of inputs makes them exact.  On exact inputs the float64 reference is exact, so the whole error is
-    the kernel's, and the magnitude map A = conv64(|input|, |w|) is known per element:
+    conv_wino80f4_kernel (the row k0-256x16x16-16+16-78-f88, the smallest case of tests/test_gpu_conv_wino80f4.py).
+    Their weight transform divides by 81/64, 243/128, ... : no choice of inputs makes them exact.  On exact inputs the
+    float64 reference is exact, so the whole error is the kernel's, and the magnitude map A = conv64(|input|, |w|) is known
+    per element:
         |got - ref| <= c * EPS * A,   EPS = 2^-24,   and got == 0 exactly where A == 0.
     c is not chosen: it is 4 x the worst |err| / (EPS * A) of oracle.conv64.wino4_f32 on the SAME inputs, a float32 numpy
     emulation of the algorithm (U = G g G^T in float64 rounded once; input transform, accumulation two channels per step and
     output transform in float32) — what float32 arithmetic alone costs F(4x4, 3x3) on these points.  The kernels accumulate in
     MFMA steps of another width and add split-K slabs, a different draw of the same rounding process; the factor 4 covers that.
 
-(C) F(4x4, 2x2) — conv_wino42p_kernel and conv_wino42s_kernel, the first case of each kernel's own test module, on exact
-    inputs at the existing gate of 1e-4 of the output peak; the ratio |err| / (EPS * A) is recorded, no new bound.
+(C) F(4x4, 2x2) — conv_wino42p_kernel (family wino42t, the row k2-64x16x32-16+16-64-f40) and conv_wino42s_kernel (wino42s,
+    k1-64x32x64-16-256-f136), the first case of each kernel's own test module, on exact inputs at the existing gate of 1e-4 of
+    the output peak; the ratio |err| / (EPS * A) is recorded, no new bound.
+
+(B) and (C) select their rows BY ID: the 4x emulation bound and the figures below were measured on exactly these cases.  The
+table's other five F(4x4, .) rows (NOT_VALUE_SWEPT: the guard-sweep rows of wino42t, wino42s and wino80f4) get no value test
+here — a bound for them would rest on numbers nobody has measured; their values are held by the Gaussian tests of the kernels'
+own modules, and the CPU twin holds that every row is in (A), (B), (C) or that list.
 
 Worst |err| / (EPS * A) per case (profiles/conv_exact_sweep.txt has the same table with a reading of it); the emulation on the
 CPU, the kernels on an MI355X:
@@ -53,28 +61,24 @@ from test_gpu_conv_mask_sweep import nhwc_padded, prefill
 
 pytestmark = pytest.mark.gpu
 EPS = 2.0 ** -24
-WINO = _lib.CONV_WINOGRAD
-W4 = WINO | _lib.CONV_WINOGRAD4
-
-# (A) every row of the table but the F(4x4, 3x3) ones
-BITWISE_CASES = [c for c in cg.CASES if c['family'] != 'wino4']
+ALL_CASES = cg.CASES
 
 
-def _extra(kind, N, H, W, cins, c_out, flags, family, tile, algo):
-    c = cg._case(kind, N, H, W, cins, c_out, flags, family, tile, 1)
-    c['algo'] = algo
-    return c
+def _rows(family, *ids):
+    rows = [c for c in cg.CASES if c['family'] == family and c['id'] in ids]
+    assert len(rows) == len(ids), 'the plan table has lost a %s row this sweep selects: %s' % (family, ids)
+    return rows
 
 
+# (A) every row of the table but the F(4x4, .) ones
+BITWISE_CASES = [c for c in cg.CASES if c['m'] != 4]
 # (B) the wino4 rows (unsplit, one tile per view, split-K) and the smallest case of tests/test_gpu_conv_wino80f4.py
-F4_CASES = [c for c in cg.CASES if c['family'] == 'wino4'] + [
-    _extra(0, 256, 16, 16, [16, 16], 78, W4 | _lib.CONV_WINOGRAD4_OUT, 'wino80f4', (16, 16, 80), 3)]
+F4_CASES = [c for c in cg.CASES if c['family'] == 'wino4'] + _rows('wino80f4', 'k0-256x16x16-16+16-78-f88')
 # (C) the first case of tests/test_gpu_conv_wino42p.py and of tests/test_gpu_conv_wino42s.py
-F42_CASES = [_extra(2, 64, 16, 32, [16, 16], 64, WINO | _lib.CONV_WINOGRAD42, 'wino42p', (32, 16, 64), 2),
-             _extra(1, 64, 32, 64, [16], 256, WINO | _lib.CONV_WINOGRAD42S, 'wino42s', (32, 16, 64), 2)]
-ALL_CASES = BITWISE_CASES + F4_CASES + F42_CASES
-# the Winograd output tile of a family (F(m x m, .)); for wino2t per output parity class, in input pixels
-WINO_M = {'wino': 2, 'wino80': 2, 'wino2': 2, 'wino2t': 2, 'wino4': 4, 'wino80f4': 4, 'wino42p': 4, 'wino42s': 4}
+F42_CASES = _rows('wino42t', 'k2-64x16x32-16+16-64-f40') + _rows('wino42s', 'k1-64x32x64-16-256-f136')
+# the F(4x4, .) rows without a value test here (module docstring): the guard sweep's other rows of the three newest kernels
+NOT_VALUE_SWEPT = {'wino42t': ('k2-16x32x64-16+32-64-f40', 'k2-64x16x32-16-64-f40'), 'wino42s': ('k1-32x64x128-16+32-128-f136',),
+                   'wino80f4': ('k0-256x16x16-16+32-78-f88', 'k0-4x128x128-20-78-f88')}
 
 
 def exact_inputs(c):
@@ -88,13 +92,6 @@ def _reference(cid):
     c = next(x for x in ALL_CASES if x['id'] == cid)
     srcs, w = exact_inputs(c)
     return srcs, w, o64.conv64(c['kind'], srcs, w)
-
-
-def split_depth(L, c):
-    d = conv_desc(c['kind'], c['cins'], c['c_out'], c['flags'])
-    ws = L.rnr_conv_workspace_bytes(ctypes.byref(d), c['N'], c['H'], c['W'])
-    oh, ow = cg.out_hw(c['kind'], c['H'], c['W'])
-    return 1 if ws == 256 else ws // (c['N'] * oh * ow * d.c_out_pad * 4)
 
 
 def locate(c, n, y, x, col):
@@ -115,7 +112,7 @@ def locate(c, n, y, x, col):
     else:
         s += 'tile (row %d, column %d) of %d x %d pixels in view %d, position (%d, %d) inside it' % (
             gy // th, gx // tw, tw, th, n, gy % th, gx % tw)
-        m = WINO_M.get(c['family'])
+        m = c['m']
         if m:
             s += '; F(%dx%d) patch (%d, %d) of the tile, output (%d, %d) of the patch' % (
                 m, m, gy % th // m, gx % tw // m, gy % m, gx % m)
@@ -154,7 +151,7 @@ def launches(c, srcs, w):
     L = _lib.load()
     d = conv_desc(c['kind'], c['cins'], c['c_out'], c['flags'])
     assert L.rnr_conv_algorithm(ctypes.byref(d), c['N'], c['H'], c['W']) == c['algo']
-    assert split_depth(L, c) == c['split']
+    assert cg.split_depth(L, c) == c['split']
     co, cp = c['c_out'], pad16(c['c_out'])
     oh, ow = cg.out_hw(c['kind'], c['H'], c['W'])
     fill = prefill(c['N'], oh, ow, cp)

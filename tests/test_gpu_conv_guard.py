@@ -5,11 +5,12 @@ descriptors without bounds, so an index slip neither faults nor — next to fres
                     of a sentinel-filled allocation of its own at the weakest alignment the header grants, out_raw / workspace /
                     the packed weight prefilled with the sentinel NaN: guards intact, output finite and BITWISE the unguarded
                     run's, statistics / scale / shift at the bound of test_conv_fused_equals_separate_launches, sync zero.  No
-                    float64 reference here: tests/test_gpu_conv_exact_sweep.py compares the values of every one of these cases
-                    with a float64 convolution, bit for bit (the F(4x4, 3x3) rows: within a per-element bound).
+                    float64 reference here: tests/test_gpu_conv_exact_sweep.py compares the values of these cases with a
+                    float64 convolution, bit for bit (the F(4x4, .) rows it selects: within a bound; it lists the rest).  For
+                    the wino80f4 rows, whose masked launch runs the same kernel, live tiles are bitwise the unmasked launch's.
   (b) NaN tracer    one NaN in `raw`: it must surface in every output whose window contains it and may surface only where
-                    rnr_hip.h ("Non-finite inputs") allows for the algorithm that runs — a pure index property, the sharpest
-                    probe of halo staging, reflection and tile decode; everything outside is bitwise the clean run.
+                    rnr_hip.h ("Non-finite inputs") allows for the Winograd tile that runs — a pure index property, the
+                    sharpest probe of halo staging, reflection and tile decode; everything outside is bitwise the clean run.
   (c) ReLU and NaN  a NaN under RNR_ACT_RELU surfaces in all five kernel families (rnr_conv_src in rnr_hip.h).
 """
 import ctypes
@@ -70,8 +71,9 @@ def test_guard_sweep(c):
     args = (c['kind'], srcs, w, c['c_out'], c['N'], c['H'], c['W'])
     co, cp = c['c_out'], pad16(c['c_out'])
     L = _lib.load()
-    d = conv_desc(c['kind'], c['cins'], co, c['flags'])
+    d = cg.desc(c)
     assert L.rnr_conv_algorithm(ctypes.byref(d), c['N'], c['H'], c['W']) == c['algo']
+    assert L.rnr_conv_winograd_tile(ctypes.byref(d), c['N'], c['H'], c['W']) == c['m']
 
     # rnr_conv2d with statistics
     out_u, st_u = run_conv(*args, flags=c['flags'])
@@ -103,6 +105,7 @@ def test_guard_sweep(c):
     # rnr_conv2d_masked with a mixed mask, where the masked launch takes one
     tiles = L.rnr_conv_tile_count(ctypes.byref(d), c['N'], c['H'], c['W'])
     rng = np.random.default_rng(c['H'] * 131 + c['W'])
+    assert tiles or c['family'] not in ('wino80', 'wino80f4'), 'the out layer\'s Winograd plans take a tile mask'
     if tiles:
         tw, th = cg.mask_tile(c)
         mask = (rng.random(tiles) < 0.5).astype(np.uint8)
@@ -116,6 +119,8 @@ def test_guard_sweep(c):
         live = live.expand(-1, -1, th, -1, tw).reshape(c['N'], c['H'], c['W'])
         check_out('rnr_conv2d_masked', out_mg[live], co)
         assert torch.equal(bits(out_mg[live]), bits(out_mu[live])), 'rnr_conv2d_masked: guarded and unguarded differ'
+        if c['family'] == 'wino80f4':               # the masked launch runs the same kernel (the other Winograd plans: a direct one)
+            assert torch.equal(bits(out_mg[live]), bits(out_u[live])), 'rnr_conv2d_masked: live tiles differ from the unmasked launch'
         assert bool((bits(out_mg[~live]) == SENTINEL).all()), 'rnr_conv2d_masked: a masked-off tile was written'
 
     # rnr_conv2d_ray on the 80-column direct plan
@@ -171,7 +176,8 @@ def test_nan_tracer(c):
         out, _ = run_conv(c['kind'], poisoned, w, co, c['N'], c['H'], c['W'], flags=c['flags'], with_stats=False)
         tag = 'NaN at view %d pixel (%d, %d) source %d channel %d' % (n, i, j, s, ch)
         must = torch.from_numpy(nan_must(c['kind'], c['H'], c['W'], i, j))
-        may = torch.from_numpy(nan_may(c['kind'], c['algo'], c['H'], c['W'], i, j))
+        may = torch.from_numpy(nan_may(c['kind'], c['m'], c['H'], c['W'], i, j))
+        assert bool((may | ~must).all())
         nan = torch.isnan(out[..., :co])
         assert bool(nan[n][must].all()), '%s: %d of %d outputs whose window holds it are not NaN in every live column' % (
             tag, int((~nan[n][must].all(dim=-1)).sum()), int(must.sum()))
@@ -199,11 +205,12 @@ def test_relu_propagates_nan_in_every_kernel_family():
     must = torch.from_numpy(nan_must(kind, H, W, i, j))
     verdict = {}
     L = _lib.load()
-    for flags, algo in cg.RELU_NAN_FLAGS:
-        assert L.rnr_conv_algorithm(ctypes.byref(conv_desc(kind, cins, co, flags)), N, H, W) == algo
+    for flags, algo, m in cg.RELU_NAN_FLAGS:
+        d = conv_desc(kind, cins, co, flags)
+        assert L.rnr_conv_algorithm(ctypes.byref(d), N, H, W) == algo and L.rnr_conv_winograd_tile(ctypes.byref(d), N, H, W) == m
         out, _ = run_conv(kind, srcs, w, co, N, H, W, flags=flags, with_stats=False)
         nan = torch.isnan(out[n][must][:, :co])
         verdict[flags] = 'all' if bool(nan.all()) else ('none' if not bool(nan.any()) else 'some')
-        may = torch.from_numpy(nan_may(kind, algo, H, W, i, j))
+        may = torch.from_numpy(nan_may(kind, m, H, W, i, j))
         assert not bool(torch.isnan(out[n][~may]).any()) and not bool(torch.isnan(out[:n]).any())
     assert set(verdict.values()) == {'all'}, 'flags -> NaN at the window outputs: %s' % verdict

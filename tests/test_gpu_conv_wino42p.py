@@ -111,3 +111,12 @@ def test_map_off_the_tile_runs_the_old_kernel_bit_for_bit(N, H, W):
     b = run_conv_fused(2, srcs, w, c_out, N, H, W, gamma, beta, flags=W2)
     assert torch.equal(a[0].view(torch.int32), b[0].view(torch.int32))
     assert torch.allclose(a[1], b[1], rtol=1e-6, atol=1e-7) and torch.allclose(a[2], b[2], rtol=1e-5, atol=1e-6)
+
+
+def test_columns_off_the_tile_keep_the_old_plan():
+    """72 live columns: the 80 padded columns are no multiple of 64, so the flag changes nothing about the plan."""
+    N, H, W, cins, c_out = 8, 32, 64, [16], 72
+    L = _lib.load()
+    q = lambda f, fl: f(ctypes.byref(conv_desc(2, cins, c_out, fl)), N, H, W)
+    assert q(L.rnr_conv_algorithm, W42) == q(L.rnr_conv_algorithm, W2)
+    assert q(L.rnr_conv_winograd_tile, W42) == q(L.rnr_conv_winograd_tile, W2) != 4

@@ -6,18 +6,17 @@ process, so every case has exactly 256 tiles of 16 x 16 (the lowered threshold i
 tests/test_conv_wino80f4_cpu.py).
 Bounds: out_raw within 1e-4 of the output peak of the float64 convolution (the project's gate for every Winograd kernel); scale /
 shift of the same launch against the float64 statistics at the tolerances of test_gpu_unet.test_conv_winograd_f4x4_vs_torch.
-Where the kernel touches memory: the guard-band sweep and the NaN tracer of tests/test_gpu_conv_guard.py on this kernel's cases."""
+Where the kernel touches memory: the wino80f4 rows of oracle/conv_guard_cases.py, run by tests/test_gpu_conv_guard.py."""
 import ctypes
 
 import numpy as np
 import pytest
 import torch
 
-from oracle import conv_guard_cases as cg
-from oracle.conv64 import conv64, nan_may, nan_must
+from oracle.conv64 import conv64
 from rnr_amd import _lib
 from rnr_amd.testing import SENTINEL, conv_active_tiles, conv_desc, run_conv, run_conv_fused
-from test_gpu_conv_guard import SRC_NAMES, assert_intact, bits, check_out, gaussian_inputs, tracer_positions
+from test_gpu_conv_guard import bits
 
 pytestmark = pytest.mark.gpu
 W4 = _lib.CONV_WINOGRAD | _lib.CONV_WINOGRAD4             # conv_wino80_kernel (F(2x2, 3x3)) on 80 columns
@@ -144,95 +143,3 @@ def test_active_tiles_describe_16x16_blocks():
     assert buf.numel() == want.size + 64
     assert np.array_equal(buf[:want.size].numpy(), want.reshape(-1))
     assert bool((buf[want.size:] == 0xAA).all()), 'bytes behind the mask were written'
-
-
-# ---- guard band and NaN tracer (tests/test_gpu_conv_guard.py's helpers on this kernel's cases) ----
-
-def _case(*a, **k):
-    c = cg._case(*a, **k)
-    c['algo'] = 3               # rnr_conv_algorithm's code of both out-layer Winograd kernels; these cases run tile 4
-    return c
-
-
-GUARD_CASES = [
-    _case(0, 256, 16, 16, [16, 32], 78, OUT, 'wino80f4', (16, 16, 80), 1, ['one_tile_per_view', 'two_sources_unequal', 'pad_out_78_80'], tracer=True),
-    _case(0, 4, 128, 128, [20], 78, OUT, 'wino80f4', (16, 16, 80), 1, ['pad_in_20_32', 'pad_out_78_80'], tracer=True),
-]
-GUARD_IDS = [c['id'] for c in GUARD_CASES]
-
-
-@pytest.mark.parametrize('c', GUARD_CASES, ids=GUARD_IDS)
-def test_guard_sweep(c):
-    """No element outside an operand is written, none of the sentinel-filled surroundings (or of the sentinel-prefilled packed
-    weight / out_raw) is read: rnr_conv2d, rnr_conv2d_fused twice on one sync buffer, rnr_conv2d_masked."""
-    srcs, w, gamma, beta = gaussian_inputs(c)
-    args = (c['kind'], srcs, w, c['c_out'], c['N'], c['H'], c['W'])
-    co = c['c_out']
-    d = conv_desc(c['kind'], c['cins'], co, c['flags'])
-    L = _lib.load()
-    assert L.rnr_conv_algorithm(ctypes.byref(d), c['N'], c['H'], c['W']) == 3
-    assert L.rnr_conv_winograd_tile(ctypes.byref(d), c['N'], c['H'], c['W']) == 4
-    out_u, st_u = run_conv(*args, flags=c['flags'])
-    out_g, st_g, rep = run_conv(*args, flags=c['flags'], guard=True)
-    assert_intact('rnr_conv2d', rep, SRC_NAMES(c) + ['weight', 'packed', 'out_raw', 'stats', 'workspace'])
-    check_out('rnr_conv2d', out_g, co)
-    assert torch.equal(bits(out_g), bits(out_u)), 'rnr_conv2d: guarded and unguarded out_raw differ'
-    assert bool(torch.isfinite(st_g).all())
-    for k in (0, 1):
-        atol = 1e-9 * float(st_u[..., k].abs().max())
-        assert torch.allclose(st_g[:, :co, k], st_u[:, :co, k], rtol=1e-6, atol=atol), 'rnr_conv2d: stats differ'
-    assert float(st_g[:, co:].abs().max()) == 0.0, 'rnr_conv2d: statistics of the padding columns not 0'
-    out_fu, sc_u, sh_u, sy_u = run_conv_fused(*args, gamma, beta, flags=c['flags'], repeats=2)
-    out_fg, sc_g, sh_g, sy_g, rep = run_conv_fused(*args, gamma, beta, flags=c['flags'], repeats=2, guard=True)
-    assert_intact('rnr_conv2d_fused', rep, SRC_NAMES(c) + ['weight', 'packed', 'out_raw', 'workspace', 'sync', 'scale', 'shift',
-                                                            'gamma', 'beta'])
-    check_out('rnr_conv2d_fused', out_fg, co)
-    assert torch.equal(bits(out_fg), bits(out_fu)) and torch.equal(bits(out_fg), bits(out_u)), 'rnr_conv2d_fused: out_raw differs'
-    assert bool(torch.isfinite(sc_g).all()) and bool(torch.isfinite(sh_g).all()), 'scale / shift not finite'
-    assert torch.allclose(sc_g[:, :co], sc_u[:, :co], rtol=1e-6, atol=1e-7)
-    assert torch.allclose(sh_g[:, :co], sh_u[:, :co], rtol=1e-5, atol=1e-6)
-    assert int(sy_g.max()) == 0 and int(sy_u.max()) == 0, 'sync buffer not returned to zero'
-    tiles = L.rnr_conv_tile_count(ctypes.byref(d), c['N'], c['H'], c['W'])
-    assert tiles == 256
-    rng = np.random.default_rng(c['H'] * 131 + c['W'])
-    mask = (rng.random(tiles) < 0.5).astype(np.uint8)
-    mask[0], mask[-1] = 1, 0
-    mask_t = torch.from_numpy(mask)
-    out_mu, _ = run_conv(*args, flags=c['flags'], tile_mask=mask_t)
-    out_mg, _, rep = run_conv(*args, flags=c['flags'], tile_mask=mask_t, guard=True)
-    assert_intact('rnr_conv2d_masked', rep, SRC_NAMES(c) + ['weight', 'packed', 'out_raw', 'workspace', 'tile_mask'])
-    live = torch.from_numpy(mask.astype(bool)).reshape(c['N'], c['H'] // 16, 1, c['W'] // 16, 1)
-    live = live.expand(-1, -1, 16, -1, 16).reshape(c['N'], c['H'], c['W'])
-    check_out('rnr_conv2d_masked', out_mg[live], co)
-    assert torch.equal(bits(out_mg[live]), bits(out_mu[live])), 'rnr_conv2d_masked: guarded and unguarded differ'
-    assert torch.equal(bits(out_mg[live]), bits(out_u[live])), 'rnr_conv2d_masked: live tiles differ from the unmasked launch'
-    assert bool((bits(out_mg[~live]) == SENTINEL).all()), 'rnr_conv2d_masked: a masked-off tile was written'
-
-
-@pytest.mark.parametrize('c', GUARD_CASES, ids=GUARD_IDS)
-def test_nan_tracer(c):
-    """One NaN in `raw`: it surfaces in every output whose 3 x 3 window holds it and only inside the 4 x 4 tiles whose 6 x 6 patch
-    holds it; everything else is bitwise the clean run (an index property of staging, reflection and tile decode)."""
-    srcs, w, _, _ = gaussian_inputs(c, act=0)
-    co = c['c_out']
-    clean, _ = run_conv(0, srcs, w, co, c['N'], c['H'], c['W'], flags=c['flags'], with_stats=False)
-    assert bool(torch.isfinite(clean).all())
-    for n, i, j, s, ch in tracer_positions(c):
-        raw = srcs[s][0].clone()
-        raw[n, ch, i, j] = float('nan')
-        poisoned = list(srcs)
-        poisoned[s] = (raw,) + srcs[s][1:]
-        out, _ = run_conv(0, poisoned, w, co, c['N'], c['H'], c['W'], flags=c['flags'], with_stats=False)
-        tag = 'NaN at view %d pixel (%d, %d) source %d channel %d' % (n, i, j, s, ch)
-        must = torch.from_numpy(nan_must(0, c['H'], c['W'], i, j))
-        may = torch.from_numpy(nan_may(0, 4, c['H'], c['W'], i, j))
-        assert bool((may | ~must).all())
-        nan = torch.isnan(out[..., :co])
-        assert bool(nan[n][must].all()), '%s: outputs whose window holds it are not NaN in every live column' % tag
-        reach = torch.zeros(out.shape[:3], dtype=torch.bool)
-        reach[n] = may
-        stray = nan.any(dim=-1) & ~reach
-        assert not bool(stray.any()), '%s: NaN outside the footprint, first at (view, y, x) = %s' % (
-            tag, tuple(int(v) for v in stray.nonzero()[0]))
-        same = bits(out[..., :co])[~reach] == bits(clean[..., :co])[~reach]
-        assert bool(same.all()), '%s: %d outputs outside the footprint differ from the clean run' % (tag, int((~same).sum()))
