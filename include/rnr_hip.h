@@ -586,6 +586,57 @@ int rnr_conv_out_backward(const float* y, const float* scale, const float* shift
                           float* g_gamma, float* g_beta, int num_views, int h, int w, int channels, int c_pad,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Dropout2d in train mode (network.py:236-247 builds the U-Net with use_dropout = True, train_rnr.py:398-405 trains with it on) ----
+ *
+ * Dropout2d multiplies a whole channel of one view by m[n,c] in {0, 1 / (1 - p)}.  LeakyReLU and ReLU are positively homogeneous
+ * and m >= 0, so m act(a y + b) = act((m a) y + m b): a dropped layer hands its consumers (rnr_conv_src, the weight gradient,
+ * the data gradient) the tables (m a, m b) instead of (a, b), and only rnr_conv_out_backward's arithmetic changes
+ * (rnr_conv_out_backward_dropout).  Alignment: mult and the scale / shift tables are read and written in 16-byte pieces and need
+ * 16-byte alignment; extents are the [num_views, c_pad] rows stated with each entry point, nothing outside them is touched.
+ */
+#define RNR_DROPOUT_MAX_LAYERS 32
+typedef struct rnr_dropout_layer {
+    float* mult;            /* [N, c_pad] device, written: the multipliers of this layer */
+    int channels, c_pad;    /* live channels; c_pad a multiple of 16 */
+    float p;                /* drop probability, 0 <= p <= 1 */
+} rnr_dropout_layer;
+
+/*
+ * One launch draws the multipliers of every layer of a plan.  layers: HOST array of num_layers <= RNR_DROPOUT_MAX_LAYERS entries.
+ * With C_total = sum of c_pad and cbase_l = sum of c_pad over the layers before l (array order; layers with p = 0 included),
+ * element (n, l, c) has index i = n C_total + cbase_l + c (view-major: the masks of view n do not depend on num_views) and takes
+ * word i & 3 of Philox4x32-10 on counter (lo32 b, hi32 b, 0, 0x524E5244), key (lo32 seed, hi32 seed), b = (uint64)offset + (i >> 2)
+ * (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85; seed and offset are 64-bit patterns passed as
+ * int64_t).  u = (word >> 8) 2^-24, keep = u >= p in float32, mult = keep ? 1.0f / (1.0f - p) : 0; p = 1 gives 0 everywhere
+ * without a division, p = 0 exactly 1; channels >= `channels` get 0.  Rows >= num_views of mult are not written.
+ * More than RNR_DROPOUT_MAX_LAYERS layers, a p outside [0, 1] or a c_pad that is not a multiple of 16 is an error before any launch.
+ */
+int rnr_dropout_draw(const rnr_dropout_layer* layers, int num_layers, int num_views, int64_t seed, int64_t offset, void* stream);
+
+/* The consumers' tables of one dropped layer: scale_out = mult * scale, shift_out = mult * shift (scale NULL = 1, shift NULL = 0),
+ * one float32 product each, all [N, c_pad]; scale_out == scale and shift_out == shift (in place) are allowed; rows >= num_views
+ * are untouched.  c_pad: a multiple of 4. */
+int rnr_dropout_affine(const float* scale, const float* shift, const float* mult, float* scale_out, float* shift_out,
+                       int num_views, int c_pad, void* stream);
+
+/*
+ * rnr_conv_out_backward for a layer whose consumers read z = mult[n,c] act(a y + b): mult [N,c_pad] (NULL = none: then this IS
+ * rnr_conv_out_backward, bit for bit).  scale / shift are the tables the consumers applied, (mult a, mult b); the sign of
+ * v' = scale y + shift is taken from them — the function the forward evaluated — and
+ *   g_v = mult[n,c] (g_z0 + g_z1) (v' > 0 ? 1 : slope),
+ * the sum in float32 as in rnr_conv_out_backward; the factor mult (v' > 0 ? 1 : slope) is formed in float64 (exact) and applied
+ * after the conversion to float64: no float32 rounding beyond the sum's.  (rnr_conv_out_backward rounds the slope product to
+ * float32.  Here a view that drops a channel contributes zeros to a whole-batch group, S1 and D are left to the other views'
+ * terms, and that rounding is no longer small against 16 roundings of the result's own terms; a table of ones is therefore not
+ * bitwise mult = NULL.)  S1, S2, D, g_beta, g_gamma and the train-mode g_y are rnr_conv_out_backward's formulas on that
+ * g_v; RNR_BN_BWD_RUNNING: g_y = gamma r g_v with r from `saved`, in float64, rounded once (scale holds mult and cannot be used);
+ * no BatchNorm: g_y = (float)g_v.  No atomics, bit-reproducible.  Workspace and limits as rnr_conv_out_backward.
+ */
+int rnr_conv_out_backward_dropout(const float* y, const float* scale, const float* shift, const float* mult, int act,
+                                  const float* g_z0, const float* g_z1, const float* gamma, const double* saved, int mode,
+                                  float* g_y, float* g_gamma, float* g_beta, int num_views, int h, int w, int channels,
+                                  int c_pad, void* workspace, size_t workspace_bytes, void* stream);
+
 /*
  * Weight gradient of rnr_conv2d for the three kinds and one or two sources:
  *   grad_weight[co, ci, tap] = sum over views and output pixels o of  g_y[n, o, co] * value(src)[n, pad(o, tap), ci]

@@ -1,5 +1,6 @@
 // Backward of the U-Net convolution stack (include/rnr_hip.h, "U-Net backward"), exact fp32 only.
-//   * rnr_conv_out_backward            activation + BatchNorm (or bias) backward of one layer: reduce, then apply
+//   * rnr_conv_out_backward[_dropout]  activation + BatchNorm (or bias) backward of one layer: reduce, then apply; with the
+//                                      Dropout2d multipliers of a dropped layer
 //   * rnr_conv2d_weight_backward       the weight gradient as an implicit GEMM on v_mfma_f32_32x32x2_f32, split over pixels
 //   * rnr_conv2d_input_backward_ring   the border pixels of the data gradient, where the forward kernels run on the upstream
 //                                      gradient do not give the adjoint of ReflectionPad2d / zero padding
@@ -20,7 +21,10 @@ namespace {
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 // ---------------------------------------------------------------------------------------------------------------------
-// rnr_conv_out_backward: g_v = (g_z0 + g_z1) * act'(v);  reduce S1 = sum g_v, S2 = sum g_v * y per (group, channel) in
+// rnr_conv_out_backward[_dropout]: g_v = mult * (g_z0 + g_z1) * act'(v), mult the Dropout2d multiplier of (view, channel) or 1;
+// without mult the slope is taken in float32 (the bits of before), with mult the factor mult * act'(v) is formed and applied in
+// float64 (the zeros of a dropped view leave S1 and D of a whole-batch group to the other views' terms alone, where a float32
+// rounding per term is no longer small against the result);  reduce S1 = sum g_v, S2 = sum g_v * y per (group, channel) in
 // float64 (per-workgroup partials, added in workgroup order), then apply.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int OB_THREADS = 256;
@@ -28,7 +32,7 @@ constexpr int OB_MAX_PARTS = 256;     // partial sums per group
 constexpr int OB_MAX_CPAD = 1024;    // channel quads of a pixel fit one workgroup
 
 struct OutBwdParams {
-    const float* y; const float* scale; const float* shift; const float* gz0; const float* gz1;
+    const float* y; const float* scale; const float* shift; const float* mult; const float* gz0; const float* gz1;
     const float* gamma; const double* saved;
     float* gy; float* g_gamma; float* g_beta;
     double* partial;        // [groups][parts][c_pad][2]
@@ -47,7 +51,10 @@ static int ob_parts(int groups, long group_pixels) {
     return (int)std::max(1L, p);
 }
 
-__device__ __forceinline__ float4 ob_grad_v(const OutBwdParams& P, size_t off, int n, int c4, float slope, float4* y_out) {
+// -> g with g_v = g * f: without dropout g = (g_z0 + g_z1) * act'(v) in float32 and f = 1; with it g = g_z0 + g_z1 and
+// f = mult * act'(v) (exact in float64: a product of two float32)
+__device__ __forceinline__ float4 ob_grad_v(const OutBwdParams& P, size_t off, int n, int c4, float slope, float4* y_out,
+                                            double f[4]) {
     const float4 y = *reinterpret_cast<const float4*>(P.y + off);
     float4 g = *reinterpret_cast<const float4*>(P.gz0 + off);
     if (P.gz1) {
@@ -58,11 +65,17 @@ __device__ __forceinline__ float4 ob_grad_v(const OutBwdParams& P, size_t off, i
     if (P.scale) sc = *reinterpret_cast<const float4*>(P.scale + (size_t)n * P.c_pad + c4);
     if (P.shift) sh = *reinterpret_cast<const float4*>(P.shift + (size_t)n * P.c_pad + c4);
     // torch's convention at v == 0: the derivative is the negative side's slope
-    g.x *= (y.x * sc.x + sh.x > 0.f) ? 1.f : slope;
-    g.y *= (y.y * sc.y + sh.y > 0.f) ? 1.f : slope;
-    g.z *= (y.z * sc.z + sh.z > 0.f) ? 1.f : slope;
-    g.w *= (y.w * sc.w + sh.w > 0.f) ? 1.f : slope;
+    const float d[4] = {(y.x * sc.x + sh.x > 0.f) ? 1.f : slope, (y.y * sc.y + sh.y > 0.f) ? 1.f : slope,
+                        (y.z * sc.z + sh.z > 0.f) ? 1.f : slope, (y.w * sc.w + sh.w > 0.f) ? 1.f : slope};
     *y_out = y;
+    if (P.mult) {
+        const float4 m = *reinterpret_cast<const float4*>(P.mult + (size_t)n * P.c_pad + c4);
+        f[0] = (double)m.x * (double)d[0]; f[1] = (double)m.y * (double)d[1];
+        f[2] = (double)m.z * (double)d[2]; f[3] = (double)m.w * (double)d[3];
+    } else {
+        g.x *= d[0]; g.y *= d[1]; g.z *= d[2]; g.w *= d[3];
+        f[0] = f[1] = f[2] = f[3] = 1.0;
+    }
     return g;
 }
 
@@ -83,11 +96,13 @@ out_bwd_reduce_kernel(const OutBwdParams P) {
             const long gp = (long)group * P.group_pixels + p;       // pixel index over the call
             const int n = (int)(gp / P.hw);
             float4 y;
-            const float4 g = ob_grad_v(P, (size_t)gp * P.c_pad + 4 * q, n, 4 * q, slope, &y);
-            s1[0] += (double)g.x; s2[0] += (double)g.x * (double)y.x;
-            s1[1] += (double)g.y; s2[1] += (double)g.y * (double)y.y;
-            s1[2] += (double)g.z; s2[2] += (double)g.z * (double)y.z;
-            s1[3] += (double)g.w; s2[3] += (double)g.w * (double)y.w;
+            double f[4];
+            const float4 g = ob_grad_v(P, (size_t)gp * P.c_pad + 4 * q, n, 4 * q, slope, &y, f);
+            const double gv[4] = {(double)g.x * f[0], (double)g.y * f[1], (double)g.z * f[2], (double)g.w * f[3]};
+            s1[0] += gv[0]; s2[0] += gv[0] * (double)y.x;
+            s1[1] += gv[1]; s2[1] += gv[1] * (double)y.y;
+            s1[2] += gv[2]; s2[2] += gv[2] * (double)y.z;
+            s1[3] += gv[3]; s2[3] += gv[3] * (double)y.w;
         }
     }
 #pragma unroll
@@ -124,11 +139,12 @@ __device__ __forceinline__ void ob_group_sums(const OutBwdParams& P, int group, 
 
 __global__ void __launch_bounds__(OB_THREADS)
 out_bwd_apply_kernel(const OutBwdParams P) {
-    // per channel: mean, gamma * r, S1 / m, r * D / m  (train-mode BatchNorm only)
+    // per channel: mean, gamma * r, S1 / m, r * D / m  (train-mode BatchNorm; eval mode under dropout: gamma * r only)
     __shared__ double coef[OB_MAX_CPAD * 4];
     const int tid = threadIdx.x;
     const int n = blockIdx.y;
     const bool bn_train = P.gamma && P.mode != 2;
+    const bool bn_eval_dropped = P.gamma && P.mode == 2 && P.mult;      // scale holds mult: gamma * r from `saved`
     const int group = (P.gamma && P.mode == 0) ? n : 0;
     // ---- parameter gradients: the first workgroups of view 0, one lane per channel, groups in order ----
     if (n == 0) {
@@ -165,6 +181,10 @@ out_bwd_apply_kernel(const OutBwdParams P) {
             coef[c * 4 + 0] = mu; coef[c * 4 + 1] = a; coef[c * 4 + 2] = cm; coef[c * 4 + 3] = cd;
         }
         __syncthreads();
+    } else if (bn_eval_dropped) {
+        for (int c = tid; c < P.c_pad; c += OB_THREADS)
+            coef[c * 4 + 1] = c < P.channels ? (double)P.gamma[c] * P.saved[(size_t)c * 2 + 1] : 0.0;
+        __syncthreads();
     }
     const int CQ = P.c_pad >> 2;
     const long total = P.hw * CQ;                               // float4s of this view
@@ -175,15 +195,22 @@ out_bwd_apply_kernel(const OutBwdParams P) {
         const int q = (int)(i % CQ);
         const size_t off = ((size_t)n * P.hw) * P.c_pad + (size_t)i * 4;
         float4 y;
-        const float4 g = ob_grad_v(P, off, n, 4 * q, slope, &y);
+        double mm[4];
+        const float4 g = ob_grad_v(P, off, n, 4 * q, slope, &y, mm);
         float r[4] = {g.x, g.y, g.z, g.w};
         const float yy[4] = {y.x, y.y, y.z, y.w};
         if (bn_train) {
 #pragma unroll
             for (int e = 0; e < 4; e++) {
                 const double* k = &coef[(4 * q + e) * 4];
-                r[e] = (float)(k[1] * ((double)r[e] - k[2] - ((double)yy[e] - k[0]) * k[3]));
+                r[e] = (float)(k[1] * ((double)r[e] * mm[e] - k[2] - ((double)yy[e] - k[0]) * k[3]));
             }
+        } else if (bn_eval_dropped) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) r[e] = (float)(coef[(4 * q + e) * 4 + 1] * ((double)r[e] * mm[e]));
+        } else if (P.mult) {            // no BatchNorm: g_y = (float)g_v
+#pragma unroll
+            for (int e = 0; e < 4; e++) r[e] = (float)((double)r[e] * mm[e]);
         } else if (P.gamma) {        // eval-mode BatchNorm: g_y = a * g_v
             const float4 sc = *reinterpret_cast<const float4*>(P.scale + (size_t)n * P.c_pad + 4 * q);
             r[0] *= sc.x; r[1] *= sc.y; r[2] *= sc.z; r[3] *= sc.w;
@@ -531,6 +558,15 @@ extern "C" int rnr_conv_out_backward(const float* y, const float* scale, const f
                                      const float* g_z1, const float* gamma, const double* saved, int mode, float* g_y,
                                      float* g_gamma, float* g_beta, int num_views, int h, int w, int channels, int c_pad,
                                      void* workspace, size_t workspace_bytes, void* stream) {
+    return rnr_conv_out_backward_dropout(y, scale, shift, nullptr, act, g_z0, g_z1, gamma, saved, mode, g_y, g_gamma, g_beta,
+                                         num_views, h, w, channels, c_pad, workspace, workspace_bytes, stream);
+}
+
+// (the messages keep rnr_conv_out_backward's name: callers and tests match on it whichever entry point they came through)
+extern "C" int rnr_conv_out_backward_dropout(const float* y, const float* scale, const float* shift, const float* mult, int act,
+                                             const float* g_z0, const float* g_z1, const float* gamma, const double* saved,
+                                             int mode, float* g_y, float* g_gamma, float* g_beta, int num_views, int h, int w,
+                                             int channels, int c_pad, void* workspace, size_t workspace_bytes, void* stream) {
     RNR_REQUIRE(y && g_z0 && g_y && workspace, "rnr_conv_out_backward: null pointer argument");
     RNR_REQUIRE(num_views > 0 && h > 0 && w > 0 && channels > 0 && c_pad >= channels && c_pad % 16 == 0 && c_pad <= OB_MAX_CPAD,
                 "rnr_conv_out_backward: bad sizes N=%d h=%d w=%d channels=%d c_pad=%d (c_pad: a multiple of 16, at most %d)",
@@ -540,7 +576,7 @@ extern "C" int rnr_conv_out_backward(const float* y, const float* scale, const f
     RNR_REQUIRE(!gamma || (saved && scale && shift), "rnr_conv_out_backward: BatchNorm needs saved, scale and shift");
     RNR_REQUIRE(((uintptr_t)workspace & 7) == 0, "rnr_conv_out_backward: workspace must be 8-byte aligned");
     OutBwdParams P = {};
-    P.y = y; P.scale = scale; P.shift = shift; P.gz0 = g_z0; P.gz1 = g_z1; P.gamma = gamma; P.saved = saved;
+    P.y = y; P.scale = scale; P.shift = shift; P.mult = mult; P.gz0 = g_z0; P.gz1 = g_z1; P.gamma = gamma; P.saved = saved;
     P.gy = g_y; P.g_gamma = g_gamma; P.g_beta = g_beta; P.partial = reinterpret_cast<double*>(workspace);
     P.mode = mode; P.act = act; P.N = num_views; P.channels = channels; P.c_pad = c_pad;
     P.hw = (long)h * w;

@@ -152,7 +152,8 @@ class Unet(nn.Module):
         st = self._structure()
         bn_train = [m.training for m in st['bn']]
         if any(m.training for m in st['dropout']):
-            raise NotImplementedError('Dropout2d in training mode: only inference (module.eval()) is built')
+            raise NotImplementedError('Dropout2d in training mode: the inference plan has no dropout (put the Dropout2d modules in '
+                                      'eval mode); it is live only on the training path (enable_hip_backward(), grad mode)')
         if len(set(bn_train)) > 1:
             raise NotImplementedError('mixed BatchNorm train/eval modes')
         # train-mode BatchNorm2d reduces over the WHOLE batch of the call (torch semantics; the reference's scripts
@@ -197,8 +198,10 @@ class Unet(nn.Module):
     def enable_hip_backward(self, flag=True):
         """Opt in to (or out of) training on the HIP backward (rnr_amd.autograd.UNetFn): a call in grad mode whose input or any
         live parameter requires grad then records itself in the autograd graph — parameters get `.grad`, the input's graph
-        continues.  Off (the default) nothing changes: such an input is refused as before.  Exact fp32; Dropout2d modules must be
-        in eval mode (train-mode dropout has no HIP form yet); `fuse.*` and v_fea never reach the output and get no gradient."""
+        continues.  Off (the default) nothing changes: such an input is refused as before.  Exact fp32.  Dropout2d modules in
+        train mode are live, as the reference trains (train_rnr.py:398-405): their masks come from the device's default generator
+        (torch.cuda.manual_seed / get_rng_state / set_rng_state govern them; the bits are this library's, not torch's — include/
+        rnr_hip.h, rnr_dropout_draw); not under stream capture.  `fuse.*` and v_fea never reach the output and get no gradient."""
         self._hip_backward = bool(flag)
         return self
 
@@ -211,11 +214,38 @@ class Unet(nn.Module):
                 res.append((k, p))
         return res
 
+    def _step_dropouts(self):
+        """The Dropout2d module behind the activation of each convolution of the live path, in UNetPlan's step order (None where
+        there is none: the out layer, or a network built with use_dropout=False)."""
+        st = self._structure()
+        if 'step_dropout' in st:
+            return st['step_dropout']
+        convs = (nn.Conv2d, nn.ConvTranspose2d, Conv2dSame)
+
+        def of(seq):            # per convolution of a Sequential, the Dropout2d that follows it before the next one
+            res = []
+            for m in seq:
+                if isinstance(m, convs):
+                    res.append(None)
+                elif isinstance(m, nn.Dropout2d) and res and res[-1] is None:
+                    res[-1] = m
+            return res
+
+        def block(b):
+            inner = block(b.submodule) if b.submodule is not None else []
+            return of(b.down.net) + inner + of(b.up.net)
+
+        st['step_dropout'] = of(self.in_layer) + block(self.unet_block) + [None]
+        return st['step_dropout']
+
+    def _dropout_probs(self):
+        """Effective probability per plan step (a module in eval mode counts as 0), or None when no module is live."""
+        probs = tuple(float(m.p) if (m is not None and m.training) else 0.0 for m in self._step_dropouts())
+        return probs if any(probs) else None
+
     def _train_plan(self, n, h, w, device):
         st = self._structure()
-        if any(m.training for m in st['dropout']):
-            raise NotImplementedError('Dropout2d in training mode has no HIP backward yet: put the Dropout2d modules in eval mode '
-                                      '(for m in net.modules(): isinstance(m, nn.Dropout2d) and m.eval())')
+        probs = self._dropout_probs()
         bn_train = [m.training for m in st['bn']]
         if len(set(bn_train)) > 1:
             raise NotImplementedError('mixed BatchNorm train/eval modes')
@@ -224,7 +254,8 @@ class Unet(nn.Module):
             if m.eps != 1e-5 or m.momentum != 0.1:
                 raise NotImplementedError('Unet: BatchNorm2d(eps=%r, momentum=%r) — the HIP U-Net implements the reference\'s '
                                           'eps=1e-5, momentum=0.1 only' % (m.eps, m.momentum))
-        key = (h, w, str(device), mode, 'train')
+        # live Dropout2d: the effective probabilities are part of the plan (nothing live: the key, and the plan, of before)
+        key = (h, w, str(device), mode, 'train') + ((probs,) if probs else ())
         ver = self._weights_version()
         plan = self._plans.get(key)
         sd = None
@@ -233,7 +264,7 @@ class Unet(nn.Module):
             sd = {'net.' + k: v for k, v in self.state_dict().items()}
             self._plans.pop(key, None)
             plan = UNetPlan(sd, cin, cout, nf0, nd, (h, w), max(n, plan.N if plan is not None else 0), device, bn_mode=mode,
-                            update_running_stats=(mode == 'batch_all'), training=True)
+                            update_running_stats=(mode == 'batch_all'), training=True, dropout=probs)
             self._plans[key] = plan
         elif self._plan_versions.get(key) != ver:
             # an optimiser step moved the weights: refresh them in place, the plan and its buffers stay
@@ -254,7 +285,27 @@ class Unet(nn.Module):
     def _forward_train(self, x, apply_tanh):
         from rnr_amd.autograd import UNetFn
         n, _, h, w = x.shape
+        live = self._dropout_probs() is not None
+        # the masks are drawn from the default generator of the input's DEVICE: an input that is on none has no such generator,
+        # and nothing else of this path runs there either — said here, before any device call
+        if live and not x.is_cuda:
+            raise NotImplementedError('Unet: live Dropout2d draws its masks from the generator of a CUDA (HIP) device and the input '
+                                      'is on %s: move the input to the device, or put the Dropout2d modules in eval mode '
+                                      '(for m in net.modules(): isinstance(m, nn.Dropout2d) and m.eval())' % (x.device,))
+        # a captured graph would replay ONE draw of the masks: refused before any launch
+        if live and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('Unet: live Dropout2d under stream capture is not supported (a replay would repeat the masks); '
+                               'put the Dropout2d modules in eval mode to capture')
         plan = self._train_plan(n, h, w, x.device)
+        if plan.dropout_live:
+            # the masks come from the device's default generator, as torch's own dropout takes them: Philox blocks offset ..
+            # offset + blocks of its seed, and the offset moves on (in torch's granularity of 4) so that no block is used twice.
+            # No host synchronisation.
+            dev = torch.device(x.device)
+            gen = torch.cuda.default_generators[dev.index if dev.index is not None else torch.cuda.current_device()]
+            offset = gen.get_offset()
+            blocks = plan.draw_dropout(gen.initial_seed(), offset, n)
+            gen.set_offset(offset + (blocks + 3) // 4 * 4)
         sdv = self.state_dict(keep_vars=True)       # the plan names every live tensor by ONE of its state-dict keys
         keys = tuple(plan.param_keys)
         out = UNetFn.apply(x, plan, keys, bool(apply_tanh), *[sdv[k[len('net.'):]] for k in keys])

@@ -6,7 +6,8 @@
   * the U-Net (RenderingNet) in its input and in every parameter of the live path — the 22 convolutions, 17 BatchNorms and the
     biases (train_rnr.py:376) —, which also carries the gradient of the ray renderer's rays_lt on to the feature channels of the
     neural texture.  Opt-in: `Unet.enable_hip_backward()` / `RenderingNet.enable_hip_backward()`; without it RenderingNet / Unet
-    keep raising on an input that requires grad.
+    keep raising on an input that requires grad.  Dropout2d modules in train mode are live there (masks from the device's default
+    generator, rnr_dropout_draw); the plan holds them, UNetFn keeps no state of its own for them.
   * the two per-pixel terms of train_rnr.py's objective: the ray chromaticity loss in rays_lt and the cropped, alpha-weighted L1
     in the estimate (rnr_rays_chrom_loss_backward, rnr_masked_l1_loss_backward; rnr_amd.losses composes the objective).
 The backward passes are HIP kernels (rnr_ray_renderer_backward, rnr_sh_reconstruct_backward, rnr_texture_mapper_backward; for the

@@ -150,7 +150,7 @@ class Adam(torch.optim.Optimizer):
         for unet in self._bound:
             ver = unet._weights_version()
             for key, plan in unet._plans.items():
-                if len(key) == 5 and torch.device(plan.dev) == device:
+                if plan.training and torch.device(plan.dev) == device:     # (a plan with live Dropout2d has a longer key)
                     (live if unet._plan_versions.get(key) == ver else rest).append((unet, plan))
         # one slot per distinct (group, step count): the pairs (step_size, bc2s) travel in the kernel arguments
         # (the counters themselves advance only after the launch that used them was enqueued)

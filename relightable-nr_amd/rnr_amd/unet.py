@@ -5,7 +5,8 @@ Built from a reference state-dict (strict key names).  Only t
 `UnetSkipConnectionBlock.forward` recomputes `y` under `if self.flag_outer:` after the `if self.gcn:` branch
 (pytorch_prototyping.py:407-419), so `fuse.*` weights and `v_fea` never influence the output; they are accepted
 and ignored.  BatchNorm uses per-view batch statistics (the reference forces BN into train mode at inference,
-test_rnr.py:229-233, with N = 1 per call); Dropout2d is the identity in eval mode.
+test_rnr.py:229-233, with N = 1 per call); Dropout2d is the identity in eval mode, and in train mode a per-(view, channel)
+multiplier folded into the tables the consumers apply — training plans only (UNetPlan(training=True, dropout=...)).
 """
 import ctypes
 import os
@@ -106,6 +107,8 @@ class _Act:
         self.data = None      # [N,h,w,c_pad]
         self.scale = None     # [N,c_pad] or None
         self.shift = None
+        self.dscale = None    # behind a live Dropout2d: the (mult scale, mult shift) the consumers apply instead
+        self.dshift = None
 
 
 DEFAULT_CONV_ALGO = 'winograd4'
@@ -114,7 +117,7 @@ DEFAULT_CONV_ALGO = 'winograd4'
 class UNetPlan:
     def __init__(self, state_dict, in_channels, out_channels, nf0, num_down, img_hw, max_views, device,
                  prefix='net.', in_c_pad=None, bn_mode='batch', share_weights_with=None, precision='f32',
-                 update_running_stats=False, check_finite=None, conv_algo=None, training=False):
+                 update_running_stats=False, check_finite=None, conv_algo=None, training=False, dropout=None):
         """bn_mode 'batch': BatchNorm2d in train mode with PER-VIEW batch statistics — what test_rnr.py:229-233 forces,
         evaluated the way the reference evaluates it (one view per call); a batch of N poses is N independent frames.
         'batch_all': train-mode BatchNorm2d exactly as torch computes it for ONE call with an [N,C,H,W] input: statistics
@@ -145,7 +148,14 @@ class UNetPlan:
         training: the plan can run `backward` after a `forward` (include/rnr_hip.h, "U-Net backward"): exact
         fp32 only (any conv_algo, all three bn_modes), the unfused launches with rnr_bn_finalize_saved, the torch-layout weights
         and the gradient convolutions' packed weights kept next to the forward's, every gradient buffer allocated here once.
-        `repack(state_dict)` refreshes the weights in place after an optimiser step."""
+        `repack(state_dict)` refreshes the weights in place after an optimiser step.
+        dropout: train-mode Dropout2d behind the activations (network.py:236-247, train_rnr.py:398-405): one probability per step
+        in plan order, None (or 0) for the out layer, which has none; needs training=True.  None or all zeros: not live, the plan
+        is today's, launch for launch.  Live: every step with a probability (0 included: multiplier exactly 1) owns a multiplier
+        table [N, c_pad] and the pair of tables its consumers apply, (mult scale, mult shift) (include/rnr_hip.h, "Dropout2d in
+        train mode"); the multipliers come from `draw_dropout` or `set_dropout_keep` BEFORE the forward that uses them."""
+        if dropout is not None and not training:
+            raise ValueError('UNetPlan(dropout=...) needs training=True: the inference plan has no train-mode Dropout2d')
         if training and precision != 'f32':
             raise NotImplementedError("UNetPlan(training=True) is exact fp32 only: the backward kernels have no emulated form "
                                       "(precision %r)" % (precision,))
@@ -314,8 +324,10 @@ class UNetPlan:
         if has('out_layer.0.net.1.bias'):
             self.out_bias[:self.out_channels] = g('out_layer.0.net.1.bias')
         self._prefix = prefix
+        self.dropout_live = False
         if training:
             self._init_training(sd)
+            self._init_dropout(dropout)
         self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=device)
         self.flops_per_view = self._count_flops()
 
@@ -392,6 +404,90 @@ class UNetPlan:
                     rm, rv = s['_running']
                     s['bn']['saved'][0, :s['out'].c, 0] = rm.double()
                     s['bn']['saved'][0, :s['out'].c, 1] = 1.0 / torch.sqrt(rv.double() + BN_EPS)
+
+    # ---- train-mode Dropout2d (include/rnr_hip.h, "Dropout2d in train mode") ----
+    def _init_dropout(self, dropout):
+        """Per step with a probability: `mult` [N, c_pad] and the consumers' tables out.dscale / out.dshift, which `_src` hands out
+        instead of out.scale / out.shift.  Those two and s['bias'] stay what `repack`, `pack_staged` and the Adam mirrors write
+        between steps, so `_fold_dropout` forms the dropped pair on every forward."""
+        self._dropped = []
+        if dropout is None:
+            return
+        probs = [0.0 if p is None else float(p) for p in dropout]
+        if len(probs) != len(self.steps):
+            raise ValueError('UNetPlan(dropout=...): %d probabilities for %d steps' % (len(probs), len(self.steps)))
+        if probs[-1] != 0.0:
+            raise ValueError('UNetPlan(dropout=...): the out layer has no Dropout2d (its entry must be None or 0)')
+        if any(not 0.0 <= p <= 1.0 for p in probs):
+            raise ValueError('UNetPlan(dropout=...): probabilities must lie in [0, 1], got %r' % (probs,))
+        self.dropout_p = tuple(probs)
+        if not any(probs):
+            return
+        self.dropout_live = True
+        dropped = [(s, p) for s, p, d in zip(self.steps[:-1], probs, dropout) if d is not None]
+        if len(dropped) > _lib.DROPOUT_MAX_LAYERS:
+            raise NotImplementedError('UNetPlan(dropout=...): %d dropped steps, rnr_dropout_draw takes %d'
+                                      % (len(dropped), _lib.DROPOUT_MAX_LAYERS))
+        new = lambda out: torch.zeros(self.N, out.c_pad, dtype=torch.float32, device=self.dev)
+        for s, p in dropped:
+            out = s['out']
+            s['mult'], s['p'], out.dscale, out.dshift = new(out), p, new(out), new(out)
+        self._dropped = [s for s, _ in dropped]
+        self._draw_layers = (_lib.RnrDropoutLayer * len(dropped))(
+            *[_lib.RnrDropoutLayer(s['mult'].data_ptr(), s['out'].c, s['out'].c_pad, p) for s, p in dropped])
+        self.dropout_c_total = sum(s['out'].c_pad for s in self._dropped)
+        self._mult_n = 0        # rows of the multiplier tables that hold a draw
+
+    def _need_live(self, who):
+        if not self.dropout_live:
+            raise RuntimeError('UNetPlan.%s: no Dropout2d is live in this plan (UNetPlan(training=True, dropout=...))' % who)
+
+    def draw_dropout(self, seed, offset, n):
+        """Draw the multipliers of the next forward of `n` views: one rnr_dropout_draw launch over every dropped step, Philox
+        blocks offset .. offset + n C_total / 4 of `seed` (64-bit patterns).  Returns the number of blocks used."""
+        self._need_live('draw_dropout')
+        n = int(n)
+        if not 0 < n <= self.N:
+            raise RuntimeError('UNetPlan built for at most %d views, got %d' % (self.N, n))
+        i64 = lambda v: ((int(v) + (1 << 63)) % (1 << 64)) - (1 << 63)
+        with on_device(self.dev):
+            check(self.L.rnr_dropout_draw(self._draw_layers, len(self._dropped), n, i64(seed), i64(offset), _stream()))
+        self._mult_n = n
+        return n * self.dropout_c_total // 4
+
+    def set_dropout_keep(self, keeps):
+        """The caller's own masks: one bool [n, c] per dropped step, in plan order -> multipliers keep / (1 - p) (formed in
+        float32 as rnr_dropout_draw forms them), padding channels 0."""
+        self._need_live('set_dropout_keep')
+        if len(keeps) != len(self._dropped):
+            raise ValueError('set_dropout_keep: %d tables for %d dropped steps' % (len(keeps), len(self._dropped)))
+        n = int(keeps[0].shape[0])
+        for s, k in zip(self._dropped, keeps):
+            if tuple(k.shape) != (n, s['out'].c) or n > self.N:
+                raise ValueError('set_dropout_keep: a table of shape %s, expected [n <= %d, %d]' % (tuple(k.shape), self.N, s['out'].c))
+        with on_device(self.dev):
+            for s, k in zip(self._dropped, keeps):
+                p = torch.tensor(s['p'], dtype=torch.float32)
+                scale = float(1.0 / (1.0 - p)) if s['p'] < 1.0 else 0.0
+                s['mult'][:n].zero_()
+                s['mult'][:n, :s['out'].c] = k.to(device=self.dev, dtype=torch.float32) * scale
+        self._mult_n = n
+
+    def dropout_keep(self):
+        """The bool tables [n, c] of the last forward, one per dropped step in plan order, on the device."""
+        self._need_live('dropout_keep')
+        if self._fwd_n is None:
+            raise RuntimeError('UNetPlan.dropout_keep: no forward yet')
+        return [s['mult'][:self._fwd_n, :s['out'].c] > 0 for s in self._dropped]
+
+    def _fold_dropout(self, s, n, st):
+        """(mult scale, mult shift) of a dropped step, once its own scale / shift are final: after `_finalize_bn`, before the
+        first consumer."""
+        out = s['out']
+        if out.dscale is None:
+            return
+        check(self.L.rnr_dropout_affine(_ptr(out.scale), _ptr(out.shift), _ptr(s['mult']), _ptr(out.dscale), _ptr(out.dshift),
+                                        n, out.c_pad, st))
 
     def repack(self, state_dict):
         """Refresh the packed weights, BatchNorm parameters and biases IN PLACE from `state_dict` (same keys and shapes as at
@@ -531,6 +627,13 @@ class UNetPlan:
             g_gamma, g_beta = self.grads[pre + bn_key + '.weight'], self.grads[pre + bn_key + '.bias']
         else:
             g_gamma, g_beta = None, (self.grads.get(pre + bias_key) if bias_key else None)
+        if out.dscale is not None:          # a dropped step: the tables its consumers applied, and the multipliers
+            check(self.L.rnr_conv_out_backward_dropout(
+                _ptr(out.data), _ptr(out.dscale), _ptr(out.dshift), _ptr(s['mult']), out.act, _ptr(gz0), _ptr(gz1),
+                _ptr(bn['gamma']) if bn else None, _ptr(bn['saved']) if bn else None, _lib.BN_BWD_MODES[self.bn_mode],
+                _ptr(self._gy), _ptr(g_gamma), _ptr(g_beta), n, out.h, out.w, out.c, out.c_pad, _ptr(self._ob_ws),
+                self._ob_ws.numel(), st))
+            return
         check(self.L.rnr_conv_out_backward(_ptr(out.data), _ptr(out.scale), _ptr(out.shift), out.act, _ptr(gz0), _ptr(gz1),
                                            _ptr(bn['gamma']) if bn else None, _ptr(bn['saved']) if bn else None,
                                            _lib.BN_BWD_MODES[self.bn_mode], _ptr(self._gy), _ptr(g_gamma), _ptr(g_beta), n, out.h,
@@ -587,6 +690,8 @@ class UNetPlan:
         return sum(self._layer_flops(s['desc'], *s['in_hw']) for s in self.steps)
 
     def _src(self, a, n):
+        if a.dscale is not None:        # a dropped step: its consumers apply (mult scale, mult shift)
+            return RnrConvSrc(a.data.data_ptr(), a.dscale.data_ptr(), a.dshift.data_ptr(), a.c_pad, a.act)
         return RnrConvSrc(a.data.data_ptr(), a.scale.data_ptr() if a.scale is not None else None,
                           a.shift.data_ptr() if a.shift is not None else None, a.c_pad, a.act)
 
@@ -613,6 +718,9 @@ class UNetPlan:
         if self.training:
             if consumer_alpha is not None or ray is not None:
                 raise NotImplementedError('UNetPlan(training=True): the masked and the fused-ray out layer have no backward')
+            if self.dropout_live and n > self._mult_n:
+                raise RuntimeError('UNetPlan.forward: Dropout2d is live and the multipliers of %d views were never drawn '
+                                   '(draw_dropout / set_dropout_keep hold %d)' % (n, self._mult_n))
             self._fwd_n = n
         L, st = self.L, _stream()
         last = self.steps[-1]
@@ -684,6 +792,8 @@ class UNetPlan:
                                       _ptr(s['packed']), _ptr(out.data), _ptr(bn['stats']) if bn and bn['stats'] is not None else None, n, h, w,
                                       _ptr(self.workspace), self.ws_bytes, _ptr(mask) if s is last else None, st))
             self._finalize_bn(s, n, st)
+            if self.dropout_live:
+                self._fold_dropout(s, n, st)
         return self.out.data[:n]
 
     def _finalize_bn(self, s, n, st):

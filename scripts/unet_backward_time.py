@@ -13,7 +13,14 @@ train-mode BatchNorm over the call ('batch_all').
 Device events around windows of back-to-back calls (each --window s or more), a warm-up, medians over --rounds rounds with the
 range next to them.
 
+--dropout P: only the A/B of train-mode Dropout2d (profiles/unet_dropout_time.txt).  A = the training plan with the Dropout2d modules
+in eval mode (UNetPlan(training=True)), B = the same build with every module live at probability P (dropout=...: one
+rnr_dropout_draw and one rnr_dropout_affine per dropped step in front of every forward, rnr_conv_out_backward_dropout in the
+backward), in alternating windows, for the forward and for forward + backward; next to them the launch boundary of this run: a
+window of back-to-back rnr_dropout_affine launches on one [N, 64] table.
+
     python scripts/unet_backward_time.py [--views 1 16] [--size 512] [--rounds 5] [--window 0.2] [--no-torch] [--out FILE]
+                                         [--dropout P]
 """
 import argparse
 import json
@@ -28,7 +35,7 @@ for p in (ROOT, os.path.join(ROOT, 'relightable-nr_amd'), os.path.join(ROOT, 'sc
     if p not in sys.path:
         sys.path.insert(0, p)
 
-from present_time import sized_reps, window_ms  # noqa: E402
+from present_time import ab, sized_reps, window_ms  # noqa: E402
 
 DEV = 'cuda:0'
 PEAK = 157.3e12
@@ -43,6 +50,58 @@ def measure(fn, rounds, window):
     return statistics.median(t), min(t), max(t)
 
 
+def dropout_ab(args, sd, cin, cout, nf0, nd, say):
+    """A: Dropout2d in eval mode; B: live at args.dropout.  Same build, alternating windows."""
+    from rnr_amd._lib import check
+    from rnr_amd.ops import _ptr, _stream
+    from rnr_amd.unet import UNetPlan
+    S, results = args.size, {}
+    for N in args.views:
+        plan_a = UNetPlan(sd, cin, cout, nf0, nd, (S, S), N, DEV, bn_mode='batch_all', training=True)
+        plan_b = UNetPlan(sd, cin, cout, nf0, nd, (S, S), N, DEV, bn_mode='batch_all', training=True,
+                          dropout=[args.dropout] * (len(plan_a.steps) - 1) + [None])
+        x = torch.randn(N, S, S, plan_a.in_c_pad, device=DEV)
+        x[..., cin:] = 0
+        g = torch.randn(N, S, S, plan_a.out.c_pad, device=DEV)
+        g[..., cout:] = 0
+        state = {'offset': 0}
+
+        def fwd_b():
+            state['offset'] += plan_b.draw_dropout(1234, state['offset'], N)
+            plan_b.forward(x)
+
+        def step_a():
+            plan_a.forward(x)
+            plan_a.backward(g)
+
+        def step_b():
+            fwd_b()
+            plan_b.backward(g)
+        # the launch boundary of this run: back-to-back launches of the smallest kernel of the feature
+        small = torch.ones(N, 64, device=DEV)
+        out0, out1 = torch.empty_like(small), torch.empty_like(small)
+        st, L = _stream(), plan_b.L
+        t_launch = measure(lambda: check(L.rnr_dropout_affine(_ptr(small), None, _ptr(small), _ptr(out0), _ptr(out1), N, 64, st)),
+                           args.rounds, args.window)
+        extra = 1 + len(plan_b._dropped)
+        say('unet_backward_time --dropout %g: %d view(s) of %d x %d, nf0 %d, conv_algo %s; B adds %d launches per forward (1 draw, %d '
+            'folds); launch boundary of this run %.2f us (%.2f .. %.2f)'
+            % (args.dropout, N, S, S, nf0, plan_a.conv_algo, extra, extra - 1, 1e3 * t_launch[0], 1e3 * t_launch[1], 1e3 * t_launch[2]))
+        res = {'launch_us': 1e3 * t_launch[0], 'extra_launches': extra}
+        for name, fa, fb in (('training forward', lambda: plan_a.forward(x), fwd_b), ('forward + backward', step_a, step_b)):
+            r = ab(fa, fb, args.rounds, args.window)
+            diff = r['b_ms'] - r['a_ms']
+            say('  %-20s A (eval) %9.3f ms (%.3f .. %.3f)   B (live) %9.3f ms (%.3f .. %.3f)   B - A = %+.3f ms = %+.2f %%; '
+                '%d launches x boundary = %.3f ms; host per call A %.3f / B %.3f ms'
+                % (name, r['a_ms'], *r['a_spread'], r['b_ms'], *r['b_spread'], diff, 100 * diff / r['a_ms'], extra,
+                   extra * t_launch[0], r['a_host_ms'], r['b_host_ms']))
+            res[name] = {'a_ms': r['a_ms'], 'b_ms': r['b_ms'], 'a_host_ms': r['a_host_ms'], 'b_host_ms': r['b_host_ms']}
+        results[str(N)] = res
+        del plan_a, plan_b, x, g
+        torch.cuda.empty_cache()
+    say(json.dumps({'unet_dropout_time': {'size': S, 'p': args.dropout, 'device': torch.cuda.get_device_name(0), 'cases': results}}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--views', type=int, nargs='+', default=[1, 16])
@@ -52,6 +111,7 @@ def main():
     ap.add_argument('--layer-window', type=float, default=0.05)
     ap.add_argument('--no-torch', action='store_true')
     ap.add_argument('--out', default=None, help='also append the result lines to this file')
+    ap.add_argument('--dropout', type=float, default=None, help='A/B of train-mode Dropout2d at this probability, nothing else')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('unet_backward_time.py needs the GPU: a CPU run measures nothing')
@@ -69,6 +129,13 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
+    if args.dropout is not None:
+        dropout_ab(args, sd, cin, cout, nf0, nd, say)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, 'a') as f:
+                f.write('\n'.join(lines) + '\n')
+        return
     for N in args.views:
         train = UNetPlan(sd, cin, cout, nf0, nd, (S, S), N, DEV, bn_mode='batch_all', training=True)
         infer = UNetPlan(sd, cin, cout, nf0, nd, (S, S), N, DEV, bn_mode='batch_all')
