@@ -984,6 +984,23 @@ int rnr_interpolate_bilinear(const float* data, int h, int w, int c, const float
  * cv2 is not available in this image: parity with OpenCV is unpinned; the integer-ratio case is the plain box mean. */
 int rnr_resize_area(const float* src, float* dst, int src_h, int src_w, int dst_h, int dst_w, int channels, void* stream);
 
+/* A photograph for training: src [src_h,src_w,src_channels] interleaved 8-bit, src_channels 3 or 4 (the first three channels are
+ * used in their order, a fourth is ignored) -> dst [3,dst_h,dst_w] planar float32, in one launch.  What
+ * data_util.load_img(square_crop=True, downsampling_order=1) + [:, :, :3] + transpose(2,0,1) + ** img_gamma do on the host
+ * (data_util.py:21-54, dataio.py:171-174):
+ *   v   = (float)byte / 255.0f, correctly rounded (numpy's float32 quotient, bit for bit);
+ *   r   = rnr_resize_area of v over the window rows [crop_y0, crop_y0 + crop_h), columns [crop_x0, crop_x0 + crop_w) to
+ *         dst_h x dst_w: the same device function, so the bits are those of rnr_resize_area on the float window;
+ *   out = gamma == 1 ? r : (float)pow((double)r, gamma): the float32 nearest to the float64 power (numpy's float32 ** lies up to
+ *         10 ulp from it, so the reference's own bits are not reproducible).
+ * Parity: as for rnr_resize_area, parity of the resize with OpenCV is unpinned (cv2 is not available in this image).  JPEG
+ * decoders may differ by one level between two libjpeg builds; PNG and BMP decode exactly.
+ * Alignment: src 1 byte (any address), dst its element's 4 bytes.
+ * Refused before any launch: a NULL pointer, a size <= 0, src_channels other than 3 or 4, a window that is not inside the image,
+ * a gamma that is not finite or not > 0, a misaligned dst. */
+int rnr_photo_prepare(const uint8_t* src, int src_h, int src_w, int src_channels, int crop_y0, int crop_x0, int crop_h,
+                      int crop_w, double gamma, float* dst, int dst_h, int dst_w, void* stream);
+
 /* =====================================================================================================
  * 3. Stand-alone operators for the drop-in Python API (one reference function each).  The fused entry
  *    points above compute the same quantities without the intermediate HBM round trips.

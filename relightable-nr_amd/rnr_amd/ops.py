@@ -671,6 +671,24 @@ def resize_area(img, out_h, out_w):
 
 
 @_device_op
+def photo_prepare(src_u8, crop, out_hw, gamma=1.0, out=None):
+    """A photograph for training (rnr_photo_prepare): src_u8 [H,W,3 or 4] uint8 on the device, crop = (y0, x0, h, w) in source
+    pixels, out_hw = (out_h, out_w) -> float32 [3,out_h,out_w] = ((first three channels / 255), area-resized like `resize_area`)
+    ** gamma, in one launch.  `out`: a float32 [3,out_h,out_w] device tensor to write into."""
+    if not isinstance(src_u8, torch.Tensor) or src_u8.dim() != 3:
+        raise RuntimeError('src must be a [H,W,C] tensor')
+    y0, x0, h, w = (int(v) for v in crop)
+    out_h, out_w = (int(v) for v in out_hw)
+    if out is None:
+        out = torch.empty(3, max(out_h, 0), max(out_w, 0), dtype=torch.float32, device=src_u8.device)
+    elif tuple(out.shape) != (3, out_h, out_w):
+        raise RuntimeError('out must be [3,%d,%d], got %s' % (out_h, out_w, tuple(out.shape)))
+    _call('rnr_photo_prepare', src_u8, src_u8.shape[0], src_u8.shape[1], src_u8.shape[2], y0, x0, h, w, float(gamma), out,
+          out_h, out_w)
+    return out
+
+
+@_device_op
 def nchw_to_nhwc(x, c_pad):
     n, c, h, w = x.shape
     out = torch.empty(n, h, w, c_pad, dtype=torch.float32, device=x.device)
