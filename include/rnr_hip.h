@@ -1001,6 +1001,48 @@ int rnr_resize_area(const float* src, float* dst, int src_h, int src_w, int dst_
 int rnr_photo_prepare(const uint8_t* src, int src_h, int src_w, int src_channels, int crop_y0, int crop_x0, int crop_h,
                       int crop_w, double gamma, float* dst, int dst_h, int dst_w, void* stream);
 
+/* ---- OpenEXR photographs and probes (rnr_amd/exr.py reads and validates the file on the host) ---- */
+
+/* Pixel types of an OpenEXR channel, with the file format's own codes. */
+#define RNR_EXR_HALF 1
+#define RNR_EXR_FLOAT 2
+/* Bytes of a coded chunk that one pass of rnr_exr_unpack's workgroup covers: 256 lanes x 16 bytes of each half of the chunk.  A
+ * longer chunk takes ceil(bytes / RNR_EXR_PASS_BYTES) passes of the same workgroup, the running sums carried in registers. */
+#define RNR_EXR_PASS_BYTES 8192
+
+/* The scanline chunks of an OpenEXR file -> its raw scanline buffer.  payload: the chunks' bytes one behind the other (a ZIP /
+ * ZIPS chunk after inflate, any other as the file stores it); table [num_chunks, 4] int64 rows (src_offset into payload,
+ * dst_offset into raw, bytes, coded); one workgroup per row:
+ *   coded = 0   raw[dst_offset + i] = payload[src_offset + i], 0 <= i < bytes;
+ *   coded = 1   with t = payload + src_offset and n = bytes, the format's two reconstruction steps:
+ *                 predictor   t'[0] = t[0], t'[i] = (t'[i-1] + t[i] - 128) mod 256   (a prefix sum mod 256: any order, same bytes)
+ *                 interleave  raw[dst_offset + 2k] = t'[k], raw[dst_offset + 2k + 1] = t'[(n + 1) / 2 + k].
+ * CONTRACT: the table's CONTENTS are the host's responsibility.  The kernel trusts every row: [src_offset, src_offset + bytes)
+ * must lie inside payload, [dst_offset, dst_offset + bytes) inside raw, the destination ranges must not overlap, bytes >= 0,
+ * coded 0 or 1.  rnr_amd.exr checks all of this against the file before a byte is uploaded; a caller with a table of its own must
+ * do the same.  payload is not modified; bytes of raw that no row covers are not written.
+ * Alignment: payload and raw 1 byte (any address, and any offsets), table 8 bytes.
+ * Refused before any launch: a NULL pointer, num_chunks <= 0, a misaligned table. */
+int rnr_exr_unpack(const uint8_t* payload, const int64_t* table, int num_chunks, uint8_t* raw, void* stream);
+
+/* rnr_photo_prepare with a floating-point source and no / 255: src is a byte buffer of src_h rows of row_bytes bytes; the value
+ * of channel k in (R, G, B) at (y, x) lives at src + y * row_bytes + k_offset + x * k_stride and has type k_type, RNR_EXR_HALF
+ * (IEEE binary16, little endian) or RNR_EXR_FLOAT (binary32).  This covers OpenEXR's scanline-planar rows (offset: where the
+ * channel's run starts in a scanline, stride: its element size) and interleaved float32 [H,W,C] (row_bytes 4 C W, offsets 0 / 4 /
+ * 8, stride 4 C) alike.
+ *   v   = the value as float32: binary16 -> binary32 is exact for all 65 536 patterns (subnormals, infinities; a NaN stays a NaN
+ *         with its payload);
+ *   r   = rnr_resize_area of v over the window, the same device function: the bits of rnr_resize_area on the float window;
+ *   out = gamma == 1 ? r : (float)pow((double)r, gamma).
+ * Negative and non-finite values pass through the arithmetic as IEEE has it (a negative r under gamma != 1 gives NaN).
+ * Alignment: src 1 byte (with an odd width a HALF row starts at an odd multiple of 2 and a FLOAT run behind a HALF run at 2 mod 4;
+ * the kernel loads 4, 2 or 1 bytes at a time as the address allows), dst its element's 4 bytes.
+ * Refused before any launch: what rnr_photo_prepare refuses, row_bytes <= 0, a type other than the two above, a negative offset, a
+ * stride below the type's size, and a channel row that does not fit: k_offset + (src_w - 1) * k_stride + size > row_bytes. */
+int rnr_photo_prepare_hdr(const uint8_t* src, int src_h, int src_w, int64_t row_bytes, int64_t r_offset, int r_stride, int r_type,
+                          int64_t g_offset, int g_stride, int g_type, int64_t b_offset, int b_stride, int b_type, int crop_y0,
+                          int crop_x0, int crop_h, int crop_w, double gamma, float* dst, int dst_h, int dst_w, void* stream);
+
 /* =====================================================================================================
  * 3. Stand-alone operators for the drop-in Python API (one reference function each).  The fused entry
  *    points above compute the same quantities without the intermediate HBM round trips.

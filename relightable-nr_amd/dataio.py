@@ -1,8 +1,8 @@
 """Drop-in `dataio.ViewDataset` for inference (reference: dataio.py:11-247): calib.mat -> per-view camera tensors.
 
 `load_img=False` is what `test_rnr.py:112-127, 268-278` needs; `load_img=True, img_dir=...` reads the photographs of a capture
-for training (PIL decode, then one HIP crop-and-resize, `ops.photo_prepare`).  `load_precompute=True` raises: the per-view maps
-come from `rnr_amd.capture.view_maps`.  `LightProbeDataset` is cv2-free.
+for training (PIL decode, then one HIP crop-and-resize, `ops.photo_prepare`; OpenEXR through `ops.read_exr`).
+`load_precompute=True` raises: the per-view maps come from `rnr_amd.capture.view_maps`.  `LightProbeDataset` is cv2-free.
 
 Unlike the reference, `read_view` is pure: the reference writes the cropped intrinsics back into `calib['projs']`
 through a numpy view (dataio.py:189-193), so calling it twice for the same index compounds the crop.  The values
@@ -118,9 +118,14 @@ class ViewDataset():
         from PIL import Image
         from rnr_amd import capture
         fp = self.img_fp_all[idx]
-        if os.path.splitext(fp)[1].lower() in ('.exr', '.hdr', '.mat'):
+        ext = os.path.splitext(fp)[1].lower()
+        if ext in ('.hdr', '.mat'):
             raise NotImplementedError('%s: %s photographs are listed (they take part in the order) but not read here - convert '
-                                      'them to 8-bit .png' % (fp, os.path.splitext(fp)[1]))
+                                      'them to OpenEXR .exr or 8-bit .png' % (fp, ext))
+        if ext == '.exr':                   # the data window's size, from the header alone (rnr_amd.exr: no torch, no GPU)
+            from rnr_amd import exr
+            header = exr.read_header(fp)
+            return capture.crop_geometry(header.height, header.width)
         with Image.open(fp) as im:
             w, h = im.size
         return capture.crop_geometry(h, w)
@@ -140,11 +145,20 @@ class ViewDataset():
         """Photograph idx -> float32 [3,S,S] 'img_gt' (data_util.load_img(square_crop=True, downsampling_order=1)[:, :, :3]
         .transpose(2,0,1) ** img_gamma, dataio.py:171-174): PIL decodes to 8 bits, the bytes are uploaded as they are and one
         ops.photo_prepare crops, scales, resizes and applies the gamma on the GPU.  EXIF orientation is ignored, as
-        cv2.IMREAD_UNCHANGED ignores it."""
+        cv2.IMREAD_UNCHANGED ignores it.  An OpenEXR photograph goes through ops.read_exr with the same crop, size and gamma and
+        no / 255 (data_util.py:24-25 reads .exr as float)."""
         from PIL import Image
         from rnr_amd import ops
         _, _, y0, x0, side = self._photo_geometry(idx)
         fp = self.img_fp_all[idx]
+        if os.path.splitext(fp)[1].lower() == '.exr':
+            if not torch.cuda.is_available():
+                raise RuntimeError('ViewDataset.read_view: OpenEXR photographs are unpacked and prepared by HIP kernels '
+                                   '(rnr_exr_unpack, rnr_photo_prepare_hdr) and no GPU is available; there is no CPU fallback '
+                                   '(read_camera works without one)')
+            dev = torch.device(self.device) if self.device is not None else torch.device('cuda', torch.cuda.current_device())
+            img = ops.read_exr(fp, dev, (y0, x0, side, side), (self.img_size[0], self.img_size[1]), self.img_gamma)
+            return img if self.device is not None else img.cpu()
         with Image.open(fp) as im:
             if im.mode == 'P':
                 im = im.convert('RGB')
@@ -210,8 +224,9 @@ def _read_radiance_hdr(fp):
 
 class LightProbeDataset():
     """dataio.py:262-311 without cv2: items are {'lp_img': float32 tensor [3,H,W], RGB, ** img_gamma}.  Readers: Radiance
-    `.hdr` (numpy RGBE decoder), `.npy` ([H,W,3] float RGB), 8-bit `.png/.jpg/.JPEG/.bmp` via PIL (/255).  `.exr` / `.mat`
-    files are LISTED (they take part in the order) but raise when read: they need a codec this image does not ship."""
+    `.hdr` (numpy RGBE decoder), `.npy` ([H,W,3] float RGB), 8-bit `.png/.jpg/.JPEG/.bmp` via PIL (/255), OpenEXR `.exr`
+    (rnr_amd.exr on the host, two HIP kernels: needs a GPU; the item is a CPU tensor like the others).  `.mat` files are LISTED
+    (they take part in the order) but raise when read."""
     # data_util.glob_imgs' list (data_util.py:57), case-sensitive like glob, so that the sorted order — which lighting_idx
     # indexes — is the reference's; '.npy' is this build's extra (a probe the reference could not list)
     _EXT = ('.png', '.jpg', '.JPEG', '.bmp', '.exr', '.hdr', '.mat', '.npy')
@@ -232,9 +247,18 @@ class LightProbeDataset():
             img = _read_radiance_hdr(fp)
         elif ext == '.npy':
             img = np.load(fp).astype(np.float32)[:, :, :3]
-        elif ext in ('.exr', '.mat'):
-            raise NotImplementedError('%s: %s probes need a codec this image does not ship (cv2 / OpenEXR / the reference\'s own '
-                                      '.mat convention) - convert the probe to .hdr or .npy' % (fp, ext))
+        elif ext == '.exr':
+            # dataio.py:288-289 reads it as float, no / 255: ops.read_exr with the identity window and size, ** img_gamma included
+            from rnr_amd import ops
+            if not torch.cuda.is_available():
+                raise RuntimeError('LightProbeDataset: OpenEXR probes are unpacked and prepared by HIP kernels (rnr_exr_unpack, '
+                                   'rnr_photo_prepare_hdr) and no GPU is available; there is no CPU fallback')
+            dev = torch.device('cuda', torch.cuda.current_device())
+            self.lp_all[idx] = {'lp_img': ops.read_exr(fp, dev, gamma=self.img_gamma).cpu()}
+            return
+        elif ext == '.mat':
+            raise NotImplementedError('%s: .mat probes follow a convention of the reference\'s own that is not read here - convert '
+                                      'the probe to .exr, .hdr or .npy' % fp)
         else:
             from PIL import Image
             im = Image.open(fp)

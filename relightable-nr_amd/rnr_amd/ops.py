@@ -91,7 +91,7 @@ def _chk(t, name, dtype=torch.float32):
 
 # the tensor dtype a pointer parameter of the header takes; any other pointee (void, a struct) takes every dtype
 _POINTEE_DTYPES = {'float': torch.float32, 'int32_t': torch.int32, 'int': torch.int32, 'double': torch.float64,
-                   'uint8_t': torch.uint8}
+                   'uint8_t': torch.uint8, 'int64_t': torch.int64}
 
 
 def _plan(params):
@@ -686,6 +686,58 @@ def photo_prepare(src_u8, crop, out_hw, gamma=1.0, out=None):
     _call('rnr_photo_prepare', src_u8, src_u8.shape[0], src_u8.shape[1], src_u8.shape[2], y0, x0, h, w, float(gamma), out,
           out_h, out_w)
     return out
+
+
+@_device_op
+def exr_unpack(payload, table, raw_bytes=None, out=None):
+    """The chunks of an OpenEXR file -> its raw scanline buffer (rnr_exr_unpack): payload uint8 [n] on the device, table int64
+    [num_chunks,4] rows (src_offset, dst_offset, bytes, coded) on the device -> uint8 [raw_bytes] (or `out`).  The table's
+    contents are trusted (include/rnr_hip.h): pass only what rnr_amd.exr.load returned, or rows checked the same way."""
+    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.shape[1] != 4:
+        raise RuntimeError('table must be [num_chunks,4]')
+    if out is None:
+        out = torch.empty(int(raw_bytes), dtype=torch.uint8, device=payload.device)
+    _call('rnr_exr_unpack', payload, table, table.shape[0], out)
+    return out
+
+
+@_device_op
+def photo_prepare_hdr(src, src_hw, row_bytes, layout, crop, out_hw, gamma=1.0, out=None):
+    """photo_prepare for a floating-point source, no / 255 (rnr_photo_prepare_hdr): src uint8 [src_h * row_bytes] on the device,
+    layout = ((offset, stride, type) of R, of G, of B) inside a row with type _lib.EXR_HALF or _lib.EXR_FLOAT (rnr_amd.exr's
+    rgb_layout; for a float32 [H,W,C] tensor viewed as bytes: row_bytes = 4 C W and (0, 4 C, FLOAT), (4, 4 C, FLOAT), ...),
+    crop = (y0, x0, h, w), out_hw = (out_h, out_w) -> float32 [3,out_h,out_w]."""
+    if not isinstance(src, torch.Tensor) or src.dim() != 1:
+        raise RuntimeError('src must be a flat uint8 tensor')
+    src_h, src_w = (int(v) for v in src_hw)
+    if src_h > 0 and row_bytes > 0 and src.numel() < src_h * int(row_bytes):
+        raise RuntimeError('src holds %d bytes, %d rows of %d bytes need %d' % (src.numel(), src_h, row_bytes, src_h * int(row_bytes)))
+    y0, x0, h, w = (int(v) for v in crop)
+    out_h, out_w = (int(v) for v in out_hw)
+    if out is None:
+        out = torch.empty(3, max(out_h, 0), max(out_w, 0), dtype=torch.float32, device=src.device)
+    elif tuple(out.shape) != (3, out_h, out_w):
+        raise RuntimeError('out must be [3,%d,%d], got %s' % (out_h, out_w, tuple(out.shape)))
+    (ro, rs, rt), (go, gs, gt), (bo, bs, bt) = ((int(v) for v in c) for c in layout)
+    _call('rnr_photo_prepare_hdr', src, src_h, src_w, int(row_bytes), ro, rs, rt, go, gs, gt, bo, bs, bt, y0, x0, h, w, float(gamma),
+          out, out_h, out_w)
+    return out
+
+
+def read_exr(fp, device, window=None, size=None, gamma=1.0):
+    """An OpenEXR photograph or probe -> float32 [3,h,w] RGB on `device`: header and validation, inflate (rnr_amd.exr, host), ONE
+    upload of the chunk bytes, rnr_exr_unpack, rnr_photo_prepare_hdr.  window = (y0, x0, h, w) in data-window pixels (default: the
+    whole image), size = (h, w) of the result (default: the window's), gamma as photo_prepare's."""
+    from . import exr
+    header, payload, table = exr.load(fp)
+    device = torch.device(device)
+    with on_device(device):
+        dev_payload = torch.frombuffer(payload, dtype=torch.uint8).to(device)
+        dev_table = torch.tensor(table, dtype=torch.int64).to(device)
+        raw = exr_unpack(dev_payload, dev_table, header.height * header.row_bytes)
+        window = (0, 0, header.height, header.width) if window is None else window
+        size = (window[2], window[3]) if size is None else size
+        return photo_prepare_hdr(raw, (header.height, header.width), header.row_bytes, exr.rgb_layout(header), window, size, gamma)
 
 
 @_device_op

@@ -383,7 +383,7 @@ def run_unet_out_backward(g_out, out, apply_tanh, c_pad, guard=False):
 # A call is written as keyword arguments by the header's parameter names; _lib.PARAMS says which are pointers.  Every device
 # operand goes through _Operands: guarded, it sits at the weakest alignment the header's "Alignment" paragraphs grant it —
 # ALIGN_QUAD for the operands listed here (their kernels move 16 bytes through them), else its element's: ALIGN_DOUBLE for
-# float64, ALIGN_BYTE for bytes, ALIGN_WORD for the rest.
+# float64 and int64, ALIGN_BYTE for bytes, ALIGN_WORD for the rest.
 QUAD_OPERANDS = frozenset([
     ('rnr_shade_inputs', 'net_in'), ('rnr_shade_inputs', 'textures_host'),
     ('rnr_ray_render', 'unet_raw'), ('rnr_ray_render', 'net_in'),
@@ -398,7 +398,7 @@ def operand_align(fn, param, dtype=torch.float32):
     """The weakest alignment the header grants operand `param` (for a struct or a table: any of its device pointers) of `fn`."""
     if (fn, param) in QUAD_OPERANDS:
         return ALIGN_QUAD
-    return {torch.float64: ALIGN_DOUBLE, torch.uint8: ALIGN_BYTE}.get(dtype, ALIGN_WORD)
+    return {torch.float64: ALIGN_DOUBLE, torch.int64: ALIGN_DOUBLE, torch.uint8: ALIGN_BYTE}.get(dtype, ALIGN_WORD)
 
 
 class In:
