@@ -298,16 +298,19 @@ typedef struct rnr_conv_desc {
  * partial products are accumulated in fp32 by v_mfma_f32_32x32x16_bf16 (error of the order of fp32's own rounding,
  * 2.7x fewer MFMA cycles).  Must be set both when packing the weights and when convolving; layers it does not cover
  * (maps narrower than 16 pixels or of odd shape) run the fp32 MFMA kernels from the same buffer.  Range: finite operands below
- * 2^127 (the leading bf16 term of a larger value rounds to infinity); residual terms in fp32's subnormal range are
- * flushed, which only costs precision below 1e-38. */
+ * 2^127 (the leading bf16 term of a larger value rounds to infinity).  The split is exact down to |x| = 2^-110; below, residual
+ * terms under 2^-126 are bf16 subnormals, which gfx950 keeps (conversion and MFMA; a grid of 2^-133) rather than flushes: an
+ * operand x then enters as x +- 2^-134 at the worst, |out - x w| <= 2^-126 |w| whatever a device does with them — precision
+ * below 1e-38 (tests/test_gpu_conv_emu_terms.py, class R). */
 #define RNR_CONV_F32_EMU_BF16X6 2
 /* fp32 emulation on the fp16 matrix cores: every operand is split into TWO fp16 terms (22 significand bits, relative
  * representation error <= 2^-23) and the three leading partial products (hh, hl, lh) are accumulated in fp32 by
  * v_mfma_f32_32x32x16_f16: 5.3x fewer MFMA cycles than the exact-fp32 kernel, half of bf16x6.  Measured error against a
  * float64 convolution is below the exact-fp32 kernel's on every U-Net layer shape it covers (fewer accumulator roundings outweigh
  * the two missing significand bits; tests/test_gpu_unet.py).  Weights are pre-scaled per layer by a power of two at pack
- * time (2^k with |k| <= 40, undone exactly in the epilogue; a layer whose max |w| is below 2^-28 keeps fewer fp16 bits), so
- * any finite weights are fine; activations must satisfy
+ * time (2^k, k = min(12 - floor(log2 max |w|), 40), which brings max |w| into [2^12, 2^13), undone exactly in the epilogue; a
+ * layer whose max |w| is below 2^-28 keeps fewer fp16 bits, and weights more than 2^-26 below the layer's largest keep fewer
+ * bits as fp16 subnormals), so any finite weights are fine, up to FLT_MAX (k = -115); activations must satisfy
  * |act(scale * x + shift)| < 65504 — true for BatchNorm outputs and bounded network inputs; values below 2^-14 keep an
  * absolute precision of 2^-25 (fp16 subnormals are honoured by the MFMA).  Same packing / fallback rules as BF16X6;
  * the two flags are mutually exclusive. */

@@ -1473,7 +1473,7 @@ __global__ void __launch_bounds__(256) weight_amax_kernel(const float* __restric
 }
 
 // emulation image: 64-byte header, then [par][tap][chunk][NT terms][2 k-halves][wstride][8 x 16 bit]  (conv_halo_emu_kernel).
-// FMT 1 (f16x3): weights are multiplied by 2^k, k = 12 - floor(log2 max|w|), before the split; header[0] = 2^-k.
+// FMT 1 (f16x3): weights are multiplied by 2^k, k = min(12 - floor(log2 max|w|), 40), before the split; header[0] = 2^-k.
 template <int FMT>
 __global__ void __launch_bounds__(256)
 pack_weight_emu_kernel(rnr_conv_desc d, const float* __restrict__ w, char* __restrict__ image, long total) {
@@ -1486,9 +1486,11 @@ pack_weight_emu_kernel(rnr_conv_desc d, const float* __restrict__ w, char* __res
         const float amax = __builtin_bit_cast(float, reinterpret_cast<const unsigned*>(image)[2]);
         if (amax > 0.0f) {
             kexp = 12 - ilogbf(amax);
-            // +-40: the epilogue's column statistics square the SCALED accumulators before the scale is undone, and 2^80
-            // times a squared activation sum still fits fp32; weights below 2^-28 simply keep fewer fp16 bits
-            kexp = min(max(kexp, -40), 40);
+            // clamped from above only: weights below 2^-28 simply keep fewer fp16 bits.  Large weights take the k they ask for,
+            // down to -115 at FLT_MAX (2^k and 2^-k stay normal floats): a lower clamp of -40 made the leading fp16 term of
+            // max |w| >= 65520 * 2^40 infinite.  The epilogue's column statistics square the SCALED accumulators before the
+            // scale is undone, in float64, where 2^230 times a squared sum is no concern.
+            kexp = min(kexp, 40);
         }
         wscale = ldexpf(1.0f, kexp);
     }
