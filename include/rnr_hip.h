@@ -1028,6 +1028,41 @@ int rnr_photo_prepare(const uint8_t* src, int src_h, int src_w, int src_channels
  * Refused before any launch: a NULL pointer, num_chunks <= 0, a misaligned table. */
 int rnr_exr_unpack(const uint8_t* payload, const int64_t* table, int num_chunks, uint8_t* raw, void* stream);
 
+/* The bound of rnr_amd.exr (MAX_RAW_BYTES) on the raw scanline buffer of one image, which rnr_exr_pack shares: 2^31 bytes. */
+#define RNR_EXR_MAX_RAW_BYTES 2147483648
+/* 16-bit units of a chunk (bytes of EACH half of the coded chunk) that one workgroup of rnr_exr_pack produces: 256 lanes x 16.
+ * A longer chunk is ceil(bytes / 2 / RNR_EXR_PACK_SEGMENT) workgroups of one launch, never several passes of one. */
+#define RNR_EXR_PACK_SEGMENT 4096
+
+/* OpenEXR out: num_images float32 RGB images on the device -> the bytes the file format hands to deflate, in one
+ * launch.  The inverse of rnr_exr_unpack for three channels of one type.
+ * Source: value k in (r, g, b) of pixel (y, x) of image n is the float at
+ *   src + n * image_stride + y * row_stride + x * x_stride + k_offset      (all in floats, all >= 0)
+ * so [3,H,W], [H,W,3], [N,3,H,W], a crop of a larger image and channels 0..2 of an [H,W,4] buffer go in without a copy.
+ * Destination: dst uint8 [num_images, height * row_bytes], row_bytes = 3 * width * size, size = 2 (RNR_EXR_HALF) or 4
+ * (RNR_EXR_FLOAT).  With L = lines_per_chunk (1 for NONE / ZIPS, 16 for ZIP), chunk c of an image is the byte range
+ * [c * L * row_bytes, min(height, (c + 1) * L) * row_bytes); its n bytes `raw` are, per scanline in increasing y, the run of B, then
+ * of G, then of R values, little endian (the format's alphabetical channel order).
+ *   coded = 0   dst holds raw: what a NONE file stores, and a ZIP / ZIPS file for a chunk that deflate does not shrink;
+ *   coded = 1   per chunk, in integer arithmetic, the exact inverse of rnr_exr_unpack's two steps (n is even, row_bytes is):
+ *                 split[k] = raw[2k], split[n / 2 + k] = raw[2k + 1];  coded[0] = split[0],
+ *                 coded[i] = (split[i] - split[i-1] + 128) mod 256.
+ * Float -> half (RNR_EXR_HALF) is done on the bit pattern, so the wave's denormal mode cannot change it: round to nearest, ties
+ * to even; results below the half normal range are half subnormals (|x| <= 2^-25 gives +-0); magnitudes that round past 65504
+ * (from 65520 on) give +-inf; +-0 and +-inf keep their sign; a NaN becomes sign | 0x7c00 | (mantissa >> 13), with the lowest bit
+ * set when that field is 0 (OpenEXR's half(float) and numpy's software conversion: 0x7f800001 -> 0x7c01, 0xffc12000 -> 0xfe09).
+ * RNR_EXR_FLOAT passes the 32 bits through untouched.
+ * src is not modified; floats of src that no (n, y, x, k) addresses are not read; exactly num_images * height * row_bytes bytes
+ * of dst are written.
+ * Alignment: src its element's 4 bytes, dst 1 byte (any address: the kernel stores dwords where the address allows, single
+ * bytes at the ragged ends).
+ * Refused before any launch: a NULL pointer, a size <= 0, a negative stride or offset, a pixel_type other than the two above,
+ * coded other than 0 / 1, lines_per_chunk <= 0, a misaligned src, height * row_bytes above RNR_EXR_MAX_RAW_BYTES, more than
+ * 2^31 - 1 workgroups. */
+int rnr_exr_pack(const float* src, int num_images, int height, int width, int64_t image_stride, int64_t row_stride,
+                 int64_t x_stride, int64_t r_offset, int64_t g_offset, int64_t b_offset, int pixel_type, int lines_per_chunk,
+                 int coded, uint8_t* dst, void* stream);
+
 /* rnr_photo_prepare with a floating-point source and no / 255: src is a byte buffer of src_h rows of row_bytes bytes; the value
  * of channel k in (R, G, B) at (y, x) lives at src + y * row_bytes + k_offset + x * k_stride and has type k_type, RNR_EXR_HALF
  * (IEEE binary16, little endian) or RNR_EXR_FLOAT (binary32).  This covers OpenEXR's scanline-planar rows (offset: where the

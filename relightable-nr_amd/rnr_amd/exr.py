@@ -1,5 +1,5 @@
-"""A strict reader of single-part OpenEXR scanline files, as the OpenEXR file-layout document defines them: pure Python plus zlib,
-no GPU, no torch.
+"""A strict reader and a writer of single-part OpenEXR scanline files, as the OpenEXR file-layout document defines them: pure Python
+plus zlib, no GPU, no torch.
 
 What is read: magic 76 2f 31 01, version 2 (of the flag bits only 0x400, long names), the header attributes `channels`,
 `compression`, `dataWindow` and `lineOrder` (every other attribute is skipped by its size), the offset table and the chunks of
@@ -14,6 +14,14 @@ read or write outside its buffers.
 
     read_header(fp) -> Header    sizes, channel layout and chunk table: no pixel decode (what ViewDataset.read_camera needs)
     load(fp)        -> (Header, payload bytearray, table rows (src_offset, dst_offset, bytes, coded))
+
+What is written (`write`): a version-2 file with the eight required attributes, B, G and R channels of ONE type (HALF or FLOAT),
+compression NONE, ZIPS or ZIP, increasing line order, a data window from (0, 0).  The caller hands over each chunk's bytes as the
+format gives them to deflate (rnr_exr_pack makes them on the device; `pack_chunk` restates the coding on the host); this module
+deflates on the same bounded thread pool, stores a chunk that does not shrink raw, and lays out header, offset table and chunks.
+Every file it writes is one `load` reads.
+
+    write(fp, width, height, pixel_type, compression, chunks, ...) -> ['none' | 'raw' | 'deflate' per chunk]
 """
 import collections
 import struct
@@ -262,3 +270,149 @@ def unpack_chunk(t):
     out[0::2] = acc[:half]
     out[1::2] = acc[half:]
     return bytes(out)
+
+
+def pack_chunk(raw):
+    """The inverse of `unpack_chunk` on the host, as rnr_exr_pack(coded = 1) does it: raw scanline bytes -> the bytes for deflate."""
+    raw = bytes(raw)
+    split = raw[0::2] + raw[1::2]
+    return split[:1] + bytes((b - a + 128) & 0xff for a, b in zip(split, split[1:]))
+
+
+# ---------------------------------------------------------------------------------------------------
+# the writer
+# ---------------------------------------------------------------------------------------------------
+_TYPE_NAMES = {'half': HALF, 'float': FLOAT}
+_COMPRESSION_CODES = {name: code for code, (name, lines) in COMPRESSIONS.items() if lines is not None}
+
+
+def pixel_type_code(pixel_type):
+    """'half' | 'float' (any case) or HALF | FLOAT -> HALF | FLOAT; ValueError otherwise."""
+    code = _TYPE_NAMES.get(pixel_type.lower()) if isinstance(pixel_type, str) else pixel_type
+    if code not in (HALF, FLOAT) or isinstance(code, bool):
+        raise ValueError("pixel_type must be 'half' or 'float' (exr.HALF or exr.FLOAT), got %r" % (pixel_type,))
+    return code
+
+
+def compression_code(compression):
+    """'none' | 'zips' | 'zip' (any case) or the format's code 0 | 2 | 3 -> (code, name, scanlines per chunk); ValueError otherwise."""
+    code = _COMPRESSION_CODES.get(compression.upper()) if isinstance(compression, str) else compression
+    if code not in _COMPRESSION_CODES.values() or isinstance(code, bool):
+        raise ValueError("compression must be 'none', 'zips' or 'zip' (0, 2 or 3), got %r: the other methods are not written"
+                         % (compression,))
+    return (code,) + COMPRESSIONS[code]
+
+
+def chunk_sizes(width, height, pixel_type, compression):
+    """-> (row_bytes, scanlines per chunk, [raw bytes of every chunk in increasing y]) of the file `write` lays out; validates
+    the four arguments."""
+    size = TYPE_BYTES[pixel_type_code(pixel_type)]
+    _, _, lines = compression_code(compression)
+    for v, name in ((width, 'width'), (height, 'height')):
+        if isinstance(v, bool) or not isinstance(v, int) or v <= 0:
+            raise ValueError('%s must be a positive integer, got %r' % (name, v))
+    row_bytes = 3 * width * size
+    if row_bytes * height > MAX_RAW_BYTES:
+        raise ValueError('%d x %d pixels of %d bytes exceed the limit of %d bytes' % (width, height, 3 * size, MAX_RAW_BYTES))
+    return row_bytes, lines, [min(lines, height - y) * row_bytes for y in range(0, height, lines)]
+
+
+def check_level(level):
+    if isinstance(level, bool) or not isinstance(level, int) or not (-1 <= level <= 9):
+        raise ValueError('level must be an integer in -1..9 (zlib), got %r' % (level,))
+
+
+def _deflate(job):
+    data, level = job
+    return zlib.compress(data, level)
+
+
+def deflate_chunks(chunks, level=6, workers=MAX_INFLATE_WORKERS):
+    """zlib streams of `chunks` (bytes-like) in their order, on a thread pool of at most MAX_INFLATE_WORKERS (zlib releases the
+    GIL).  `write` calls it per file; a caller with several files deflates all their chunks in one call and passes the slices on."""
+    check_level(level)
+    jobs = [(c, level) for c in chunks]
+    workers = max(1, min(int(workers), MAX_INFLATE_WORKERS, len(jobs)))
+    if workers == 1:
+        return [_deflate(j) for j in jobs]
+    with ThreadPoolExecutor(workers) as pool:
+        return list(pool.map(_deflate, jobs))
+
+
+def _attribute(name, kind, value):
+    return name.encode('latin-1') + b'\0' + kind.encode('latin-1') + b'\0' + struct.pack('<i', len(value)) + value
+
+
+def write(fp, width, height, pixel_type, compression, chunks, raw_chunk=None, level=6, workers=MAX_INFLATE_WORKERS, deflated=None):
+    """Write a version-2 single-part scanline file of B, G, R channels of `pixel_type` ('half' | 'float').
+
+    chunks:    one bytes-like per chunk in increasing y (16 scanlines a chunk for 'zip', 1 for 'zips' and 'none'; sizes:
+               `chunk_sizes`).  For 'none' the raw scanlines (per scanline the run of B, of G, of R values, little endian); for
+               'zip' / 'zips' those bytes CODED for deflate (rnr_exr_pack(coded = 1), `pack_chunk`).
+    raw_chunk: callable(i) -> the raw bytes of chunk i, asked only for a chunk whose deflated size is not below its raw size:
+               the format stores such a chunk raw, and the reader tells the two apart by the size.  None: the coding is undone
+               on the host (`unpack_chunk`: slow, but such chunks are rare).
+    level:     zlib's, -1..9.  workers: the deflate pool, at most MAX_INFLATE_WORKERS.  deflated: the zlib streams of `chunks`
+               when the caller has made them already (`deflate_chunks`).
+    The header holds the eight required attributes: channels, compression, dataWindow = displayWindow = (0, 0, W-1, H-1),
+    lineOrder increasing, pixelAspectRatio 1, screenWindowCenter (0, 0), screenWindowWidth 1; then the offset table; then the
+    chunks as (y, size, data).  Everything is checked and deflated before the file is opened: a bad argument leaves no file.
+    -> per chunk 'none' (no compression), 'raw' (did not shrink) or 'deflate'."""
+    ptype = pixel_type_code(pixel_type)
+    code, _, _ = compression_code(compression)
+    row_bytes, lines, sizes = chunk_sizes(width, height, ptype, code)
+    check_level(level)
+    chunks = list(chunks)
+    if len(chunks) != len(sizes):
+        raise ValueError('%d x %d with %d scanlines per chunk has %d chunks, got %d' % (width, height, lines, len(sizes), len(chunks)))
+    views = []
+    for i, (c, n) in enumerate(zip(chunks, sizes)):
+        try:
+            v = memoryview(c).cast('B')
+        except TypeError:
+            raise ValueError('chunk %d is not bytes-like: %r' % (i, type(c)))
+        if v.nbytes != n:
+            raise ValueError('chunk %d (scanlines %d..%d) must hold %d bytes, got %d'
+                             % (i, i * lines, min(height, (i + 1) * lines) - 1, n, v.nbytes))
+        views.append(v)
+    if raw_chunk is not None and not callable(raw_chunk):
+        raise ValueError('raw_chunk must be callable(i) -> bytes or None, got %r' % (raw_chunk,))
+    if deflated is not None and (code == 0 or len(deflated) != len(views)):
+        raise ValueError("deflated: one zlib stream per chunk of a 'zip' / 'zips' file")
+    data, how = views, ['none'] * len(views)
+    if code != 0:
+        streams = deflate_chunks(views, level, workers) if deflated is None else list(deflated)
+        data, how = [], []
+        for i, (v, z) in enumerate(zip(views, streams)):
+            if len(z) < v.nbytes:
+                data.append(z)
+                how.append('deflate')
+                continue
+            raw = memoryview(raw_chunk(i) if raw_chunk is not None else unpack_chunk(v.tobytes())).cast('B')
+            if raw.nbytes != v.nbytes:
+                raise ValueError('raw_chunk(%d) returned %d bytes, the chunk has %d' % (i, raw.nbytes, v.nbytes))
+            data.append(raw)
+            how.append('raw')
+    ctype = struct.pack('<iB3xii', ptype, 0, 1, 1)
+    window = struct.pack('<4i', 0, 0, width - 1, height - 1)
+    header = MAGIC + struct.pack('<I', 2)
+    header += _attribute('channels', 'chlist', b''.join(k + b'\0' + ctype for k in (b'B', b'G', b'R')) + b'\0')
+    header += _attribute('compression', 'compression', struct.pack('<B', code))
+    header += _attribute('dataWindow', 'box2i', window)
+    header += _attribute('displayWindow', 'box2i', window)
+    header += _attribute('lineOrder', 'lineOrder', struct.pack('<B', 0))
+    header += _attribute('pixelAspectRatio', 'float', struct.pack('<f', 1.0))
+    header += _attribute('screenWindowCenter', 'v2f', struct.pack('<2f', 0.0, 0.0))
+    header += _attribute('screenWindowWidth', 'float', struct.pack('<f', 1.0))
+    header += b'\0'
+    offsets, pos = [], len(header) + 8 * len(data)
+    for d in data:
+        offsets.append(pos)
+        pos += 8 + len(d)
+    with open(fp, 'wb') as fh:
+        fh.write(header)
+        fh.write(struct.pack('<%dQ' % len(offsets), *offsets))
+        for i, d in enumerate(data):
+            fh.write(struct.pack('<ii', i * lines, len(d)))
+            fh.write(d)
+    return how

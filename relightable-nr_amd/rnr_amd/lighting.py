@@ -119,10 +119,11 @@ class StitchedProbe:
     def __init__(self, lp, mask, count, num_view):
         self.lp, self.mask, self.count, self.num_view = lp, mask, count, int(num_view)
 
-    def save(self, directory, idx=0):
-        """The reference's light_probe_stitch_<pattern> layout (stitch_lp.py:156-160) with what the libraries here write:
-        <idx>.npy (float32; the reference writes <idx>.exr, which nothing here can write — dataio.LightProbeDataset reads
-        .npy), <idx>.png (8-bit preview), mask/<idx>.png, count/<idx>.mat with `count` and `num_view`.  Copies to the host."""
+    def save(self, directory, idx=0, exr=False):
+        """The reference's light_probe_stitch_<pattern> layout (stitch_lp.py:156-160): <idx>.npy (float32), <idx>.png (8-bit
+        preview), mask/<idx>.png, count/<idx>.mat with `count` and `num_view`.  Copies to the host.  exr=True also writes
+        <idx>.exr, the file of stitch_lp.py:157 that train_rnr.py:285 reads back: FLOAT channels, ZIP, the R, G, B of `lp`
+        (ops.write_exr: packed on the GPU, so it needs one; dataio.LightProbeDataset reads .exr and .npy alike)."""
         import scipy.io
         from PIL import Image
         for d in (directory, os.path.join(directory, 'mask'), os.path.join(directory, 'count')):
@@ -131,16 +132,27 @@ class StitchedProbe:
         mask = self.mask.detach().cpu().numpy() != 0
         count = self.count.detach().cpu().numpy()
         np.save(os.path.join(directory, '%s.npy' % idx), lp)
+        if exr:
+            ops.write_exr(os.path.join(directory, '%s.exr' % idx), self.lp.detach().float(), 'float', 'zip', channels_last=True)
         Image.fromarray(np.clip(np.nan_to_num(lp) * 255.0, 0, 255).astype(np.uint8)).save(os.path.join(directory, '%s.png' % idx))
         Image.fromarray((mask * 255).astype(np.uint8)).save(os.path.join(directory, 'mask', '%s.png' % idx))
         scipy.io.savemat(os.path.join(directory, 'count', '%s.mat' % idx), {'count': count.astype(np.int64), 'num_view': self.num_view})
 
     @classmethod
-    def load(cls, directory, idx=0, device=None):
-        """What save wrote (<idx>.npy, mask/<idx>.png, count/<idx>.mat) -> StitchedProbe, on `device` (default: the host)."""
+    def load(cls, directory, idx=0, device=None, source='npy'):
+        """What save wrote (<idx>.npy, mask/<idx>.png, count/<idx>.mat) -> StitchedProbe, on `device` (default: the host).
+        source='exr' takes `lp` from <idx>.exr instead (save(exr=True), or the reference's own stitch_lp.py output) through
+        ops.read_exr: needs a GPU; the values are the file's, except that -0 reads as +0."""
         import scipy.io
         from PIL import Image
-        lp = np.load(os.path.join(directory, '%s.npy' % idx)).astype(np.float32)
+        if source == 'npy':
+            lp = np.load(os.path.join(directory, '%s.npy' % idx)).astype(np.float32)
+        elif source == 'exr':
+            dev = torch.device(device) if device is not None and torch.device(device).type == 'cuda' else \
+                torch.device('cuda', torch.cuda.current_device())
+            lp = ops.read_exr(os.path.join(directory, '%s.exr' % idx), dev).permute(1, 2, 0).contiguous().cpu().numpy()
+        else:
+            raise ValueError("StitchedProbe.load: source must be 'npy' or 'exr', got %r" % (source,))
         mask = (np.asarray(Image.open(os.path.join(directory, 'mask', '%s.png' % idx))) != 0).astype(np.uint8)
         mat = scipy.io.loadmat(os.path.join(directory, 'count', '%s.mat' % idx))
         out = [torch.from_numpy(lp), torch.from_numpy(mask.reshape(lp.shape[:2])),

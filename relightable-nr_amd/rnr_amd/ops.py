@@ -740,6 +740,109 @@ def read_exr(fp, device, window=None, size=None, gamma=1.0):
         return photo_prepare_hdr(raw, (header.height, header.width), header.row_bytes, exr.rgb_layout(header), window, size, gamma)
 
 
+def _rgb_images(images, channels_last, what):
+    """images [N,3,H,W] or [N,H,W,3] -> (H, W, channel stride, row stride, x stride) in elements.  channels_last None: the layout
+    whose channel axis is 3; ValueError when both are."""
+    if not isinstance(images, torch.Tensor) or images.dim() != 4:
+        raise ValueError('%s: expected a float32 tensor with a channel axis of 3, got %s' % (what, tuple(getattr(images, 'shape', ()))))
+    if images.dtype != torch.float32:
+        raise RuntimeError('%s: the image must be float32, got %s' % (what, images.dtype))
+    first, last = images.shape[1] == 3, images.shape[3] == 3
+    if channels_last is None:
+        if first and last:
+            raise ValueError('%s: a shape of %s reads as channels first and as channels last: pass channels_last'
+                             % (what, tuple(images.shape[1:])))
+        channels_last = last
+    if not (last if channels_last else first):
+        raise ValueError('%s: the channel axis of %s is not 3' % (what, tuple(images.shape[1:])))
+    s = images.stride()
+    if channels_last:
+        return images.shape[1], images.shape[2], s[3], s[1], s[2]
+    return images.shape[2], images.shape[3], s[1], s[2], s[3]
+
+
+@_device_op
+def exr_pack(images, pixel_type, lines_per_chunk, coded, channels_last=None, out=None):
+    """float32 RGB images on the device -> the bytes an OpenEXR file hands to deflate (coded = 1) or stores raw (coded = 0), in
+    one launch (rnr_exr_pack): images [N,3,H,W] or [N,H,W,3], any view with non-negative strides (a crop, the first three of
+    four channels: taken by its strides, never copied); pixel_type _lib.EXR_HALF | _lib.EXR_FLOAT; lines_per_chunk 1 (NONE /
+    ZIPS) or 16 (ZIP) -> uint8 [N, H * row_bytes] (or `out`), row_bytes = 3 W (2 | 4)."""
+    H, W, cs, rs, xs = _rgb_images(images, channels_last, 'exr_pack')
+    if not images.is_cuda:
+        raise RuntimeError('src must be a CUDA (HIP) tensor')
+    N = images.shape[0]
+    per = H * 3 * W * (2 if pixel_type == _lib.EXR_HALF else 4)
+    if out is None:
+        out = torch.empty(N, max(per, 0), dtype=torch.uint8, device=images.device)
+    elif out.numel() != N * per:
+        raise RuntimeError('out must hold %d x %d bytes, got %s' % (N, per, tuple(out.shape)))
+    # the address, not the tensor: _call takes tensors as contiguous, and this one is addressed by its strides
+    _call('rnr_exr_pack', images.data_ptr(), N, H, W, images.stride(0), rs, xs, 0, cs, 2 * cs, int(pixel_type), int(lines_per_chunk),
+          int(coded), out)
+    return out
+
+
+def write_exr_batch(paths, images, pixel_type='half', compression='zip', level=6, channels_last=None):
+    """N images -> N OpenEXR files (B, G, R channels of one type, linear values as they are): images [N,3,H,W] or [N,H,W,3]
+    float32 on the device (a CPU tensor is uploaded once; a non-contiguous view is taken by its strides), pixel_type 'half' |
+    'float', compression 'none' | 'zips' | 'zip', level zlib's.  ONE rnr_exr_pack launch and ONE download into pinned memory for
+    the batch, then rnr_amd.exr on the host: all chunks of all images share one deflate pool; a second launch (coded = 0) and
+    download happen only when some chunk does not shrink and is stored raw.  -> per file, per chunk 'none' | 'raw' | 'deflate'."""
+    from . import exr
+    paths = list(paths)
+    H, W, _, _, _ = _rgb_images(images, channels_last, 'write_exr')
+    if channels_last is None:
+        channels_last = images.shape[1] != 3
+    if len(paths) != images.shape[0]:
+        raise ValueError('write_exr: %d paths for %d images' % (len(paths), images.shape[0]))
+    ptype = exr.pixel_type_code(pixel_type)
+    code, _, lines = exr.compression_code(compression)
+    _, _, sizes = exr.chunk_sizes(int(W), int(H), ptype, code)
+    exr.check_level(level)
+    if not images.is_cuda:
+        images = images.to(torch.device('cuda', torch.cuda.current_device()))
+    N, per = images.shape[0], sum(sizes)
+
+    def download(coded):
+        with on_device(images.device):
+            dev = exr_pack(images, ptype, lines, coded, channels_last)
+            host = torch.empty(dev.numel(), dtype=torch.uint8, pin_memory=True)
+            host.copy_(dev.view(-1))
+        return memoryview(host.numpy())
+
+    def split(buf, n):
+        out, pos = [], n * per
+        for s in sizes:
+            out.append(buf[pos:pos + s])
+            pos += s
+        return out
+
+    packed = download(int(code != 0))
+    chunks = [split(packed, n) for n in range(N)]
+    streams = exr.deflate_chunks([c for cs in chunks for c in cs], level) if code != 0 else None
+    raw = []
+
+    def raw_chunk(n, i):
+        if not raw:
+            raw.append(download(0))
+        return split(raw[0], n)[i]
+
+    how = []
+    for n, fp in enumerate(paths):
+        how.append(exr.write(fp, int(W), int(H), ptype, code, chunks[n], raw_chunk=lambda i, n=n: raw_chunk(n, i), level=level,
+                             deflated=None if streams is None else streams[n * len(sizes):(n + 1) * len(sizes)]))
+    return how
+
+
+def write_exr(fp, image, pixel_type='half', compression='zip', level=6, channels_last=None):
+    """One image [3,H,W] or [H,W,3] -> one OpenEXR file: write_exr_batch of one (one pack launch, one download, the host writer).
+    channels_last None infers the layout from the axis of size 3 and raises when both readings fit.  -> per chunk 'none' | 'raw' |
+    'deflate'."""
+    if not isinstance(image, torch.Tensor) or image.dim() != 3:
+        raise ValueError('write_exr: image must be [3,H,W] or [H,W,3], got %s' % (tuple(getattr(image, 'shape', ())),))
+    return write_exr_batch([fp], image[None], pixel_type, compression, level, channels_last)[0]
+
+
 @_device_op
 def nchw_to_nhwc(x, c_pad):
     n, c, h, w = x.shape
