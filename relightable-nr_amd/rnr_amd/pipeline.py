@@ -73,8 +73,40 @@ class LightTransport:
         return metrics.score_frames(frames, targets, self.alpha if mask is None else mask, compute_ssim=compute_ssim)
 
 
-class _Slot:
-    """Private state of one call in flight (RNRPipeline(inflight=d)): stream, U-Net activations, G-buffer, frames."""
+class _CallState:
+    """What a call owns while it runs.  The pipeline's own state is one record; a further view-group lane (streams=k) is a record
+    that works on its own view range of lane 0's tensors (`shared`) and owns only its stream, U-Net plan and rasterizer
+    workspace; a further call in flight (inflight=d) owns everything but the packed weights inside its plan."""
+
+    def __init__(self, pipe, unet, stream, ws_views, shared=None):
+        N, S, dev = pipe.max_views, pipe.S, pipe.dev
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.stream, self.unet = stream, unet
+        self.ws = torch.empty(ops._lib.load().rnr_gbuffer_workspace_bytes(ws_views, pipe.mesh.num_faces, S), dtype=torch.uint8, device=dev)
+        self.flip = 0
+        if shared is not None:
+            # a view-group lane: lane 0's tensors (it writes its own view range of them), and no frame_prepare outputs — only a
+            # call that is not split into view groups prepares
+            self.gb, self.net_in, self.images, self.u8, self.ray_w = shared.gb, shared.net_in, shared.images, shared.u8, shared.ray_w
+            self.prep = None
+            return
+        self.gb = {m: torch.empty((N, S, S) + ops.GBUFFER_MAPS[m][1], dtype=ops.GBUFFER_MAPS[m][0], device=dev) for m in pipe._gb_maps}
+        self.net_in = torch.empty(N, S, S, unet.in_c_pad, **f32)
+        # two frame buffers: a caller that overlaps the all-gather of step k with the rendering of step k+1 alternates
+        self.images = [torch.empty(N, 3, S, S, **f32) for _ in range(2)]
+        # ... and their 8-bit companions (present=...): same alternation, same lifetime
+        self.u8 = [torch.empty(N, S, S, 3, dtype=torch.uint8, device=dev) if pipe.present else None for _ in range(2)]
+        # [max_views,S,S,c_out_pad] ray weights: with fuse_ray only
+        self.ray_w = torch.empty(N, S, S, unet.out.c_pad, **f32) if pipe.fuse_ray else None
+        # outputs of ops.frame_prepare: projected vertices, per-face tangents and (with SH lighting) the reconstructed light probe
+        self.prep = {'v_uvz': torch.empty(N, pipe.mesh.num_vertices, 3, **f32), 'tangents': torch.empty(pipe.mesh.num_faces, 3, **f32),
+                     'lp': None if pipe.sh_lighting is None else torch.empty(pipe.sh_lighting.h, pipe.sh_lighting.w, 3, **f32)}
+
+    def next_frame(self, n):
+        """(image [n,3,S,S], uint8 companion or None) of the next call: the two buffers alternate."""
+        image, u8 = self.images[self.flip][:n], self.u8[self.flip]
+        self.flip ^= 1
+        return image, None if u8 is None else u8[:n]
 
 
 class RNRPipeline:
@@ -136,15 +168,6 @@ class RNRPipeline:
         self.c_in = 3 * (self.n_spec + self.n_diff) + 6 + self.C
         self.max_views = int(max_views)
         self.n_streams = min(self.n_streams, self.max_views)
-        lane_views = (self.max_views + self.n_streams - 1) // self.n_streams
-        self.unet = UNetPlan(unet_state_dict, self.c_in, 3 * (self.n_spec + self.n_diff), nf0, num_down,
-                             (self.S, self.S), lane_views if self.n_streams > 1 else self.max_views, self.dev,
-                             precision=precision, conv_algo=conv_algo)
-        self._lane_unets = [self.unet] + [UNetPlan(unet_state_dict, self.c_in, 3 * (self.n_spec + self.n_diff), nf0, num_down,
-                                                   (self.S, self.S), lane_views, self.dev, share_weights_with=self.unet,
-                                                   precision=precision, conv_algo=conv_algo)
-                                          for _ in range(self.n_streams - 1)]
-        self._lane_streams = ops.side_streams(self.dev, self.n_streams) if self.n_streams > 1 else []
         self.sh_lighting, self.sh_coeff = None, None
         if sh_coeff is not None:
             from .lighting import SHLighting
@@ -153,65 +176,29 @@ class RNRPipeline:
             self.lp = None
         else:
             self.set_light_probe(lp)
-        N, S = self.max_views, self.S
-        self._gb = {}
-        self._gb_maps = ['face_index_map', 'alpha', 'uv_map', 'normal_map']
-        self._net_in = torch.empty(N, S, S, self.unet.in_c_pad, dtype=torch.float32, device=self.dev)
-        # two frame buffers: a caller that overlaps the all-gather of step k with the rendering of step k+1 alternates
-        self._images = [torch.empty(N, 3, S, S, dtype=torch.float32, device=self.dev) for _ in range(2)]
-        # ... and their 8-bit companions (present=...): same alternation, same lifetime
-        self._u8 = [torch.empty(N, S, S, 3, dtype=torch.uint8, device=self.dev) if self.present else None for _ in range(2)]
-        self._flip = 0
-        ws_views = N if self.n_streams == 1 else (N + self.n_streams - 1) // self.n_streams
-        self._lane_ws = [torch.empty(ops._lib.load().rnr_gbuffer_workspace_bytes(ws_views, self.mesh.num_faces, S),
-                                     dtype=torch.uint8, device=self.dev) for _ in range(self.n_streams)]
-        for m in self._gb_maps:
-            dt, tail = ops.GBUFFER_MAPS[m]
-            self._gb[m] = torch.empty((N, S, S) + tail, dtype=dt, device=self.dev)
-        self.last = {}
-        self._v_uvz_override = None
-        # calls in flight (submit): slot 0 is the pipeline's own state; the others share the packed weights and own the rest
         self.inflight = max(1, int(inflight))
         if self.inflight > 1 and self.n_streams > 1:
             raise ValueError('streams > 1 (view groups of one batch) and inflight > 1 (several calls in flight) are exclusive')
+        self._gb_maps = ['face_index_map', 'alpha', 'uv_map', 'normal_map']
+        N, S = self.max_views, self.S
+        group = (N + self.n_streams - 1) // self.n_streams          # views per lane (N itself on a single stream)
+        plan = lambda n, **k: UNetPlan(unet_state_dict, self.c_in, 3 * (self.n_spec + self.n_diff), nf0, num_down, (S, S), n,
+                                       self.dev, precision=precision, conv_algo=conv_algo, **k)
+        # the pipeline's own call state is lane 0 and slot 0; its plan is the one whose packed weights the others borrow
+        k = max(self.n_streams, self.inflight)
+        side = ops.side_streams(self.dev, k) if k > 1 else [None]
+        self.unet = plan(group)
+        self._lanes = [_CallState(self, self.unet, side[0], group)]
+        self._own = self._lanes[0]
+        # view groups of one batch (streams=k): each further lane works on its range of the own record's tensors
+        self._lanes += [_CallState(self, plan(group, share_weights_with=self.unet), side[i], group, shared=self._own)
+                        for i in range(1, self.n_streams)]
+        # calls in flight (submit, inflight=d): the further slots own everything but the packed weights
         self._slots, self._next_slot = [], 0
-        slot_streams = ops.side_streams(self.dev, self.inflight) if self.inflight > 1 else []
-        for i in range(self.inflight if self.inflight > 1 else 0):
-            sl = _Slot()
-            sl.stream = slot_streams[i]
-            sl.unet = self.unet if i == 0 else UNetPlan(unet_state_dict, self.c_in, 3 * (self.n_spec + self.n_diff), nf0,
-                                                        num_down, (S, S), N, self.dev, share_weights_with=self.unet,
-                                                        precision=precision, conv_algo=conv_algo)
-            sl.ws = self._lane_ws[0] if i == 0 else torch.empty_like(self._lane_ws[0])
-            sl.gb = self._gb if i == 0 else {m: torch.empty_like(t) for m, t in self._gb.items()}
-            sl.net_in = self._net_in if i == 0 else torch.empty_like(self._net_in)
-            sl.images = [torch.empty(N, 3, S, S, dtype=torch.float32, device=self.dev) for _ in range(2)]
-            sl.u8 = [torch.empty(N, S, S, 3, dtype=torch.uint8, device=self.dev) if self.present else None for _ in range(2)]
-            sl.flip = 0
-            self._slots.append(sl)
-
-    def _prep(self, slot):
-        """Outputs of ops.frame_prepare private to the pipeline's own call state or to a slot in flight: projected vertices
-        [max_views, nv, 3], per-face tangents [nf, 3] and (with SH lighting) the reconstructed light probe [h, w, 3]."""
-        owner = self if slot is None else slot
-        b = getattr(owner, '_prep_buf', None)
-        if b is None:
-            b = {'v_uvz': torch.empty(self.max_views, self.mesh.num_vertices, 3, dtype=torch.float32, device=self.dev),
-                 'tangents': torch.empty(self.mesh.num_faces, 3, dtype=torch.float32, device=self.dev),
-                 'lp': None if self.sh_lighting is None else
-                 torch.empty(self.sh_lighting.h, self.sh_lighting.w, 3, dtype=torch.float32, device=self.dev)}
-            owner._prep_buf = b
-        return b
-
-    def _ray_w(self, slot, lane):
-        """[max_views,S,S,c_out_pad] ray-weight buffer of the pipeline (shared by the view-group lanes, which use disjoint
-        view ranges) or of a slot."""
-        owner = self if slot is None else slot
-        buf = getattr(owner, '_ray_w_buf', None)
-        if buf is None:
-            buf = torch.empty(self.max_views, self.S, self.S, self.unet.out.c_pad, dtype=torch.float32, device=self.dev)
-            owner._ray_w_buf = buf
-        return buf
+        if self.inflight > 1:
+            self._slots = [self._own] + [_CallState(self, plan(N, share_weights_with=self.unet), side[i], N)
+                                         for i in range(1, self.inflight)]
+        self.last = {}
 
     def set_light_probe(self, lp):
         lp = torch.as_tensor(lp, dtype=torch.float32)
@@ -226,11 +213,7 @@ class RNRPipeline:
         here (parity tests feed the reference's own projection: the integer maps then do not depend on how this device
         rounds a 3x3 matmul); single-stream calls only."""
         with ops.on_device(self.dev):
-            self._v_uvz_override = v_uvz
-            try:
-                return self._render(proj, pose, proj_inv, R_inv, keep_intermediates, lighting_idx, stage_events)
-            finally:
-                self._v_uvz_override = None
+            return self._render(proj, pose, proj_inv, R_inv, keep_intermediates, lighting_idx, stage_events, v_uvz)
 
     def light_transport(self, proj, pose, proj_inv, R_inv):
         """Rasterizer, shading and the U-Net ONCE for the poses [N,...] (any N: in groups the pipeline's buffers hold), then ops.ray_transport:
@@ -247,7 +230,7 @@ class RNRPipeline:
             out = (torch.empty(N, S, S, 2, R, **f32), torch.empty(N, R, 3, S, S, **f32), torch.empty(N, 3, S, S, **f32),
                    torch.empty(N, 3, S, S, **f32))
             alpha = torch.empty(N, S, S, **f32)
-            group, kept = self._lane_unets[0].N, self.last      # a single-stream call takes one lane's views
+            group, kept = self.unet.N, self.last      # a single-stream call takes one lane's views
             for lo in range(0, N, group):
                 hi = min(N, lo + group)
                 self.render(proj[lo:hi], pose[lo:hi], proj_inv[lo:hi], R_inv[lo:hi], keep_intermediates=True)
@@ -278,21 +261,19 @@ class RNRPipeline:
                 # per-call work of the reference inside the slot's stream too (tangents, SH light probe, projection): one
                 # launch (ops.frame_prepare inside _render_group), outputs private to the slot
                 lp = self.lp if self.sh_lighting is None else ('sh', lighting_idx)
-                image = sl.images[sl.flip][:N]
-                u8 = sl.u8[sl.flip][:N] if self.present else None
-                sl.flip ^= 1
+                image, u8 = sl.next_frame(N)
                 args = [t.contiguous() for t in (proj, pose, proj_inv, R_inv)]
                 for t in args:
                     # the caller's tensors are read by kernels of THIS stream: tell the caching allocator, or a caller that
                     # drops its pose tensors right after submit() gets their memory recycled under the running kernels
                     t.record_stream(sl.stream)
-                self._render_group(0, 0, N, *args, lp, image, lambda name: None, slot=sl, fused=True, u8=u8)
+                self._render_group(sl, 0, N, *args, lp, image, lambda name: None, fused=True, u8=u8)
                 ev = torch.cuda.Event()
                 ev.record(sl.stream)
             self.presented = u8
             return FrameHandle(image, ev, u8)
 
-    def _render(self, proj, pose, proj_inv, R_inv, keep_intermediates, lighting_idx, stage_events):
+    def _render(self, proj, pose, proj_inv, R_inv, keep_intermediates, lighting_idx, stage_events, v_uvz=None):
 
         def mark(name):
             if stage_events is not None:
@@ -304,12 +285,10 @@ class RNRPipeline:
         if N > self.max_views:
             raise RuntimeError('pipeline built for max_views=%d, got %d poses' % (self.max_views, N))
         proj, pose, proj_inv, R_inv = proj.contiguous(), pose.contiguous(), proj_inv.contiguous(), R_inv.contiguous()
-        image = self._images[self._flip][:N]
-        u8 = self._u8[self._flip][:N] if self.present else None
+        image, u8 = self._own.next_frame(N)
         self.presented = u8
-        self._flip ^= 1
-        lanes = 1 if (stage_events is not None or keep_intermediates or self._v_uvz_override is not None) else min(self.n_streams, N)
-        fused = lanes == 1 and self._v_uvz_override is None
+        lanes = 1 if (stage_events is not None or keep_intermediates or v_uvz is not None) else min(self.n_streams, N)
+        fused = lanes == 1 and v_uvz is None
         if fused:
             # per-face tangents (recomputed per call, as get_TBN_map does, render.py:135-150), the light probe and the vertex
             # projection share one launch with the rasterizer's workspace clearing: ops.frame_prepare in _render_group
@@ -319,10 +298,11 @@ class RNRPipeline:
             self.mesh.tangents()
             lp = self.lp if self.sh_lighting is None else self.sh_lighting.light_probe(self.sh_coeff[lighting_idx])
         if lanes == 1:
-            if N > self._lane_unets[0].N:
+            if N > self.unet.N:
                 raise RuntimeError('pipeline built with streams=%d: a single-stream call takes at most %d poses'
-                                   % (self.n_streams, self._lane_unets[0].N))
-            inter = self._render_group(0, 0, N, proj, pose, proj_inv, R_inv, lp, image, mark, fused=fused, u8=u8)
+                                   % (self.n_streams, self.unet.N))
+            inter = self._render_group(self._own, 0, N, proj, pose, proj_inv, R_inv, lp, image, mark, fused=fused, u8=u8,
+                                       v_uvz=v_uvz)
             if keep_intermediates:
                 self.last = inter
             return image
@@ -333,27 +313,23 @@ class RNRPipeline:
             lo, hi = i * per, min(N, (i + 1) * per)
             if lo >= hi:
                 break
-            st = self._lane_streams[i]
-            st.wait_stream(cur)
-            with torch.cuda.stream(st):
-                self._render_group(i, lo, hi, proj, pose, proj_inv, R_inv, lp, image, lambda name: None, u8=u8)
-        for st in self._lane_streams[:lanes]:
-            cur.wait_stream(st)
+            lane = self._lanes[i]
+            lane.stream.wait_stream(cur)
+            with torch.cuda.stream(lane.stream):
+                self._render_group(lane, lo, hi, proj, pose, proj_inv, R_inv, lp, image, lambda name: None, u8=u8)
+        for lane in self._lanes[:lanes]:
+            cur.wait_stream(lane.stream)
         return image
 
-    def _render_group(self, lane, lo, hi, proj, pose, proj_inv, R_inv, lp, image, mark, slot=None, fused=False, u8=None):
-        """Views [lo, hi) of the batch on the current stream, with lane-private scratch and U-Net activations (or, for a
-        submitted call, everything private to its slot).  u8: the batch's [N,S,S,3] uint8 buffer (present=...) or None."""
+    def _render_group(self, call, lo, hi, proj, pose, proj_inv, R_inv, lp, image, mark, fused=False, u8=None, v_uvz=None):
+        """Views [lo, hi) of the batch on the current stream, with the stream-private scratch and U-Net activations of `call` (a
+        _CallState: the pipeline's own, a view-group lane's or a slot's in flight).  u8: the batch's [N,S,S,3] uint8 buffer
+        (present=...) or None.  v_uvz: projected vertices to rasterize instead of projecting here (`render`)."""
         n = hi - lo
-        unet = self._lane_unets[lane] if slot is None else slot.unet
-        gbufs = self._gb if slot is None else slot.gb
-        net_in = self._net_in if slot is None else slot.net_in
-        ov = getattr(self, '_v_uvz_override', None) if slot is None else None
-        gb = {m: gbufs[m][lo:hi] for m in self._gb_maps}
-        ws = self._lane_ws[lane] if slot is None else slot.ws
-        fused_prepare = fused and ov is None
-        if fused_prepare:
-            pb = self._prep(slot)
+        unet, ws = call.unet, call.ws
+        gb = {m: call.gb[m][lo:hi] for m in self._gb_maps}
+        if fused:
+            pb = call.prep
             sh_lp = isinstance(lp, tuple)
             ops.frame_prepare(self.mesh, proj[lo:hi], pose[lo:hi], self.S, v_uvz=pb['v_uvz'][:n], tangents=pb['tangents'],
                               lp_basis=self.sh_lighting.basis_recon if sh_lp else None,
@@ -365,20 +341,20 @@ class RNRPipeline:
             ops.rasterize_gbuffer(self.mesh, v_uvz, None, self.S, self.near, self.far, maps=self._gb_maps, out=gb, workspace=ws,
                                   prepared=True)
         else:
-            if ov is None:
+            if v_uvz is None:
                 v_uvz = ops.project_vertices(self.mesh.v, proj[lo:hi], pose[lo:hi, :3, :3].contiguous(),
                                              pose[lo:hi, :3, 3].contiguous(), self.S)
             else:
-                v_uvz = ov[lo:hi].contiguous()
+                v_uvz = v_uvz[lo:hi].contiguous()
             tangents = None             # mesh.tangents(): computed by the caller for this call
             ops.rasterize_gbuffer(self.mesh, v_uvz, None, self.S, self.near, self.far, maps=self._gb_maps, out=gb, workspace=ws)
         mark('raster')
         sh = ops.shade_inputs(gb, self.mesh, proj_inv[lo:hi], R_inv[lo:hi], self.textures, self.pivots_spec,
-                              self.pivots_diff, self.sh_start_ch, c_pad=unet.in_c_pad, net_in=net_in[lo:hi], tangents=tangents)
+                              self.pivots_diff, self.sh_start_ch, c_pad=unet.in_c_pad, net_in=call.net_in[lo:hi], tangents=tangents)
         mark('shade_inputs')
         if self.fuse_ray:
             ray_w = ops.ray_weights(sh['net_in'], gb['alpha'], lp, self.n_spec, self.n_diff, unet.out.c_pad, albedo_diff_ch=0,
-                                    albedo_spec_ch=3, out=self._ray_w(slot, lane)[lo:hi] if slot is None else self._ray_w(slot, lane)[:n])
+                                    albedo_spec_ch=3, out=call.ray_w[lo:hi])
             mark('ray_weights')
             unet.forward(sh['net_in'], n, gb['alpha'] if self.skip_background_tiles else None, ray=(ray_w, image[lo:hi]))
             mark('unet')

@@ -37,12 +37,6 @@ def _fetch(sd, key, device):
     return sd[key].detach().to(device=device, dtype=torch.float32).contiguous()
 
 
-def _running_affine(gamma, beta, running_mean, running_var):
-    """Eval-mode BatchNorm as the (scale, shift) a consumer applies."""
-    sc = gamma / torch.sqrt(running_var + BN_EPS)
-    return sc, beta - running_mean * sc
-
-
 def _backward_weight(kind, w, off, c):
     """The weight of the gradient convolution for the source at input channels [off, off + c) of forward weight `w` (include/
     rnr_hip.h, rnr_conv_backward_desc): flipped and transposed for the 3x3 kind, the same tensor read the other way for the two 4x4
@@ -143,8 +137,8 @@ class UNetPlan:
         F(2x2, 2x2), <= 9.3e-6 of the output peak vs float64 on L3 - L9, all 720 frames <= 2.03e-6 from the direct path; profiles/r09_wino42s_ab.txt);
         'direct': every convolution as a direct implicit GEMM.
         None: $RNR_CONV_ALGO, else DEFAULT_CONV_ALGO.
-        share_weights_with: another UNetPlan of the same network whose packed weights / BN parameters are reused
-        (activations, statistics and scratch stay private) — one plan per HIP stream of RNRPipeline.
+        share_weights_with: another UNetPlan of the same network whose packed weights are borrowed: nothing is packed
+        (BatchNorm parameters, biases, activations, statistics and scratch stay private) — one plan per HIP stream of RNRPipeline.
         training: the plan can run `backward` after a `forward` (include/rnr_hip.h, "U-Net backward"): exact
         fp32 only (any conv_algo, all three bn_modes), the unfused launches with rnr_bn_finalize_saved, the torch-layout weights
         and the gradient convolutions' packed weights kept next to the forward's, every gradient buffer allocated here once.
@@ -243,10 +237,7 @@ class UNetPlan:
                 if packed.numel() != self.L.rnr_packed_weight_floats(ctypes.byref(desc)):
                     raise ValueError('share_weights_with: layer %d of the donor plan was packed for another descriptor' % len(self.steps))
             else:
-                w = g(wkey)
                 packed = torch.empty(self.L.rnr_packed_weight_floats(ctypes.byref(desc)), dtype=torch.float32, device=device)
-                with on_device(device):
-                    check(self.L.rnr_pack_conv_weight(ctypes.byref(desc), _ptr(w), _ptr(packed), _stream()))
             oh, ow = _out_hw(kind, s0.h, s0.w)
             out = _Act(c_out, desc.c_out_pad, oh, ow, act)
             out.data = torch.empty(self.N, oh, ow, desc.c_out_pad, dtype=torch.float32, device=device)
@@ -256,11 +247,13 @@ class UNetPlan:
             if self.fused or self.fused_single:       # arrival counters + statistics shards: zero now, left at zero by every call
                 step['sync'] = torch.zeros(self.L.rnr_conv_sync_bytes(ctypes.byref(desc), self.N, s0.h, s0.w),
                                            dtype=torch.uint8, device=device)
+            # parameter-derived buffers are allocated here and filled by `_load` (padding channels stay 0)
+            rows = lambda: torch.zeros(self.N, desc.c_out_pad, dtype=torch.float32, device=device)
             if bn_key is not None and has(bn_key + '.weight') and bn_mode == 'running':
-                sc, sh = _running_affine(*(g(bn_key + k) for k in ('.weight', '.bias', '.running_mean', '.running_var')))
-                pad = lambda t: torch.cat([t, torch.zeros(desc.c_out_pad - c_out, device=device)])[None].repeat(self.N, 1)
-                out.scale, out.shift = pad(sc).contiguous(), pad(sh).contiguous()
+                out.scale, out.shift = rows(), rows()
             elif bn_key is not None and has(bn_key + '.weight'):
+                # the one exception: BatchNorm's gamma and beta are fetched here, because where `_fetch` returns the module's own
+                # tensor the plan reads the parameter's memory — there is nothing to allocate, and nothing to copy per step
                 gamma, beta = g(bn_key + '.weight'), g(bn_key + '.bias')
                 out.scale = torch.empty(self.N, desc.c_out_pad, dtype=torch.float32, device=device)
                 out.shift = torch.empty(self.N, desc.c_out_pad, dtype=torch.float32, device=device)
@@ -283,10 +276,8 @@ class UNetPlan:
                                             rm.data_ptr() if rm is not None else None, rv.data_ptr() if rv is not None else None,
                                             BN_MOMENTUM)
             elif bias_key is not None and has(bias_key):
-                b = torch.zeros(desc.c_out_pad, dtype=torch.float32, device=device)
-                b[:c_out] = g(bias_key)
-                out.shift = b[None].repeat(self.N, 1).contiguous()
-                step['bias'] = b
+                step['bias'] = torch.zeros(desc.c_out_pad, dtype=torch.float32, device=device)
+                out.shift = rows()
             # split-K depends on the number of views actually passed at call time: size the scratch for every n <= N
             self.ws_bytes = max(self.ws_bytes, _max_over_views(
                 self.N, lambda n: self.L.rnr_conv_workspace_bytes(ctypes.byref(desc), n, s0.h, s0.w)))
@@ -321,8 +312,6 @@ class UNetPlan:
         out = conv_step(CONV3x3_REFLECT, cat, 'out_layer.0.net.1.weight', None, None, ACT_NONE, self.out_channels)
         self.out = out
         self.out_bias = torch.zeros(out.c_pad, dtype=torch.float32, device=device)
-        if has('out_layer.0.net.1.bias'):
-            self.out_bias[:self.out_channels] = g('out_layer.0.net.1.bias')
         self._prefix = prefix
         self.dropout_live = False
         if training:
@@ -330,15 +319,35 @@ class UNetPlan:
             self._init_dropout(dropout)
         self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=device)
         self.flops_per_view = self._count_flops()
+        # every buffer exists: the argument arrays of the one batched pack (a plan on a donor's packed weights packs nothing),
+        # then the values
+        self._pack_args = None if share_weights_with is not None else self._pack_table()
+        self._load(sd, built=True)
+
+    def _pack_table(self):
+        """(descriptors, staged weights, packed buffers, count) of rnr_pack_conv_weights: per step the forward weight, then in a
+        training plan the gradient convolution of each source.  An inference plan has no staging (None): `_load` points the call at
+        the tensors it fetched."""
+        jobs = []
+        for s in self.steps:
+            jobs.append((s['desc'], s.get('w'), s['packed']))
+            jobs += [(b['desc'], b['w'], b['packed']) for b in s.get('bwd', ())]
+        n = len(jobs)
+        ptrs = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
+        return ((RnrConvDesc * n)(*[j[0] for j in jobs]), ptrs([j[1] for j in jobs]) if self.training else None,
+                ptrs([j[2] for j in jobs]), n)
 
     # ---- training (include/rnr_hip.h, "U-Net backward") ----
     def _init_training(self, sd):
-        """Everything `backward` needs, allocated once: per layer the torch-layout weight, the gradient convolutions' descriptors
-        and packed weights (one per source), the saved BatchNorm statistics, one gradient buffer per (layer, source) — an
-        activation with two consumers (down conv and skip concat) owns two, which rnr_conv_out_backward adds — and the parameter
-        gradients; shared by all layers: one g_y buffer and the two workspaces."""
+        """Everything `backward` needs, allocated once (`_load` fills what derives from the parameters): per layer the staging of
+        the torch-layout weight s['w'] and, per source, of the gradient convolution's weight b['w'] (`_backward_weight` made
+        contiguous: a second copy of the weights, each its own allocation, which the packs and the Adam mirrors address), the
+        gradient convolutions' descriptors and packed weights, the saved BatchNorm statistics, one gradient buffer per (layer,
+        source) — an activation with two consumers (down conv and skip concat) owns two, which rnr_conv_out_backward adds — and the
+        parameter gradients; shared by all layers: one g_y buffer and the two workspaces."""
         L, dev, N = self.L, self.dev, self.N
         pre = self._prefix
+        f32 = dict(dtype=torch.float32, device=dev)
         for a in [self.input] + [s['out'] for s in self.steps]:
             a.grads = []
         self.grads = {}
@@ -346,28 +355,28 @@ class UNetPlan:
         for s in self.steps:
             d, (h, w), out = s['desc'], s['in_hw'], s['out']
             wkey, bn_key, bias_key = s['keys']
-            s['w'] = _fetch(sd, pre + wkey, dev).clone()
+            s['w'] = torch.empty(tuple(sd[pre + wkey].shape), **f32)
             self.grads[pre + wkey] = torch.zeros_like(s['w'])
             if s['bn'] is not None or (bn_key is not None and self.bn_mode == 'running'):
                 if s['bn'] is None:         # 'running': forward folds the statistics; the backward wants gamma and (mean, r)
-                    s['bn'] = {'gamma': _fetch(sd, pre + bn_key + '.weight', dev).clone(), 'beta': None, 'stats': None,
+                    s['bn'] = {'gamma': torch.empty(out.c, **f32), 'beta': None, 'stats': None,
                                'running_mean': None, 'running_var': None}
-                if self.bn_mode == 'running':
-                    s['_running'] = tuple(_fetch(sd, pre + bn_key + k, dev) for k in ('.running_mean', '.running_var'))
                 groups = N if self.bn_mode == 'batch' else 1
                 s['bn']['saved'] = torch.zeros(groups, d.c_out_pad, 2, dtype=torch.float64, device=dev)
                 self.grads[pre + bn_key + '.weight'] = torch.zeros(out.c, dtype=torch.float32, device=dev)
                 self.grads[pre + bn_key + '.bias'] = torch.zeros(out.c, dtype=torch.float32, device=dev)
             elif bias_key is not None:
                 self.grads[pre + bias_key] = torch.zeros(out.c, dtype=torch.float32, device=dev)
-            s['bwd'] = []
+            s['bwd'], off = [], 0
             for i, a in enumerate(s['srcs']):
                 bd = RnrConvDesc()
                 check(L.rnr_conv_backward_desc(ctypes.byref(d), i, ctypes.byref(bd)))
-                packed = torch.empty(L.rnr_packed_weight_floats(ctypes.byref(bd)), dtype=torch.float32, device=dev)
-                g = torch.zeros(N, a.h, a.w, a.c_pad, dtype=torch.float32, device=dev)
+                packed = torch.empty(L.rnr_packed_weight_floats(ctypes.byref(bd)), **f32)
+                g = torch.zeros(N, a.h, a.w, a.c_pad, **f32)
                 a.grads.append(g)
-                s['bwd'].append({'desc': bd, 'packed': packed, 'grad': g})
+                s['bwd'].append({'desc': bd, 'packed': packed, 'grad': g, 'off': off,
+                                 'w': torch.empty(tuple(_backward_weight(d.kind, s['w'], off, a.c).shape), **f32)})
+                off += a.c
                 self.ws_bytes = max(self.ws_bytes, _max_over_views(
                     N, lambda n: L.rnr_conv_workspace_bytes(ctypes.byref(bd), n, out.h, out.w)))
             gy_floats = max(gy_floats, N * out.h * out.w * out.c_pad)
@@ -382,28 +391,6 @@ class UNetPlan:
         self._ob_ws = torch.empty(ob_bytes, dtype=torch.uint8, device=dev)
         self._fwd_n = None
         self.param_keys = sorted(self.grads)
-        self._pack_backward()
-
-    def _pack_backward(self):
-        """Gradient-convolution weights from the torch-layout ones (include/rnr_hip.h, rnr_conv_backward_desc): flipped and
-        transposed for the 3x3 kind, the same tensor read the other way for the two 4x4 kinds; sliced per source."""
-        with on_device(self.dev):
-            for s in self.steps:
-                d, w, off = s['desc'], s['w'], 0
-                for b, a in zip(s['bwd'], s['srcs']):
-                    wb = _backward_weight(d.kind, w, off, a.c)
-                    if 'w' in b:        # the persistent staging of `_ensure_staging`: kept current, and packed from
-                        b['w'].copy_(wb)
-                        wb = b['w']
-                    else:
-                        wb = wb.contiguous()
-                    check(self.L.rnr_pack_conv_weight(ctypes.byref(b['desc']), _ptr(wb), _ptr(b['packed']), _stream()))
-                    off += a.c
-                if s['bn'] is not None and self.bn_mode == 'running':
-                    # eval mode: (running mean, 1 / sqrt(running var + eps)) in rnr_bn_finalize_saved's form
-                    rm, rv = s['_running']
-                    s['bn']['saved'][0, :s['out'].c, 0] = rm.double()
-                    s['bn']['saved'][0, :s['out'].c, 1] = 1.0 / torch.sqrt(rv.double() + BN_EPS)
 
     # ---- train-mode Dropout2d (include/rnr_hip.h, "Dropout2d in train mode") ----
     def _init_dropout(self, dropout):
@@ -489,69 +476,86 @@ class UNetPlan:
         check(self.L.rnr_dropout_affine(_ptr(out.scale), _ptr(out.shift), _ptr(s['mult']), _ptr(out.dscale), _ptr(out.dshift),
                                         n, out.c_pad, st))
 
+    # ---- from parameters to the plan's device state: one route ----
     def repack(self, state_dict):
-        """Refresh the packed weights, BatchNorm parameters and biases IN PLACE from `state_dict` (same keys and shapes as at
-        construction): what a training step does after the optimiser moved the parameters.  No buffer is reallocated."""
+        """Bring every parameter-derived buffer up to date IN PLACE from `state_dict` (same keys and shapes as at construction):
+        what a training step does after an optimiser moved the parameters, and what construction itself runs once the buffers
+        exist.  No buffer is reallocated."""
+        self._load(state_dict)
+
+    def _load(self, state_dict, built=False):
+        """The values of `state_dict` into the weight staging of a training plan (s['w'], and b['w'] per source), BatchNorm's gamma
+        and beta, the padded biases with the shift rows made of them, out_bias and, in 'running' mode, the running statistics the
+        folds read; then `pack_staged`.  An inference plan has no staging: its packs read the fetched weights, which live until
+        the call returns.  built: the call of __init__, whose gamma and beta hold their values already — where they ARE the
+        module's tensors, copying them onto themselves would advance the version counters Unet._plan judges a plan by."""
         pre, dev = self._prefix, self.dev
         g = lambda k: _fetch(state_dict, pre + k, dev)
+        fetched = []
         with on_device(dev):
             for s in self.steps:
                 wkey, bn_key, bias_key = s['keys']
                 out = s['out']
                 if self.training:
                     s['w'].copy_(g(wkey))
-                    w = s['w']
-                else:
-                    w = g(wkey)
-                check(self.L.rnr_pack_conv_weight(ctypes.byref(s['desc']), _ptr(w), _ptr(s['packed']), _stream()))
+                    for b, a in zip(s['bwd'], s['srcs']):
+                        b['w'].copy_(_backward_weight(s['desc'].kind, s['w'], b['off'], a.c))
+                elif self._pack_args is not None:
+                    fetched.append(g(wkey))
                 if bn_key is not None and self.bn_mode == 'running':
-                    gamma, beta = g(bn_key + '.weight'), g(bn_key + '.bias')
-                    rm, rv = g(bn_key + '.running_mean'), g(bn_key + '.running_var')
-                    out.scale[:, :out.c], out.shift[:, :out.c] = _running_affine(gamma, beta, rm, rv)
+                    s['_running'] = (g(bn_key + '.running_mean'), g(bn_key + '.running_var'))
                     if self.training:
-                        s['bn']['gamma'].copy_(gamma)
-                        s['_running'] = (rm, rv)
+                        s['bn']['gamma'].copy_(g(bn_key + '.weight'))
                 elif bn_key is not None:
-                    s['bn']['gamma'].copy_(g(bn_key + '.weight'))
-                    s['bn']['beta'].copy_(g(bn_key + '.bias'))
+                    if not built:
+                        s['bn']['gamma'].copy_(g(bn_key + '.weight'))
+                        s['bn']['beta'].copy_(g(bn_key + '.bias'))
                 elif bias_key is not None:
                     s['bias'][:out.c] = g(bias_key)
                     out.shift.copy_(s['bias'][None].expand_as(out.shift))
             if (pre + 'out_layer.0.net.1.bias') in state_dict:
                 self.out_bias[:self.out_channels] = g('out_layer.0.net.1.bias')
-        if self.training:
-            self._pack_backward()
+        self.pack_staged(state_dict, fetched)
 
-    # ---- what rnr_amd.optim.Adam.bind keeps current instead of `repack` (include/rnr_hip.h, "Adam step") ----
-    def _ensure_staging(self):
-        """The gradient convolutions' weights as persistent buffers next to s['w'] (`_pack_backward` forms them as temporaries),
-        filled from s['w'] here and by every later `_pack_backward` (so a `repack` leaves them current too); the argument arrays of
-        the batched pack."""
-        if not self.training:
+    def _fold_running(self, s, gamma, beta):
+        """Eval-mode BatchNorm of step `s` from the running statistics of the last load: the (scale, shift) its consumers apply and,
+        for the backward of a training plan, (mean, 1 / sqrt(var + eps)) in rnr_bn_finalize_saved's form."""
+        out, (rm, rv) = s['out'], s['_running']
+        sc = gamma / torch.sqrt(rv + BN_EPS)
+        out.scale[:, :out.c], out.shift[:, :out.c] = sc, beta - rm * sc
+        if self.training:
+            s['bn']['saved'][0, :out.c, 0] = rm.double()
+            s['bn']['saved'][0, :out.c, 1] = 1.0 / torch.sqrt(rv.double() + BN_EPS)
+
+    def pack_staged(self, state_dict=None, weights=None):
+        """The tail of `_load`, and all a bound rnr_amd.optim.Adam step needs after its mirrors wrote the staging: every forward and
+        gradient-convolution weight packed by ONE rnr_pack_conv_weights call, and in 'running' mode BatchNorm refolded from
+        `state_dict` (the keys `repack` takes; required there) and the running statistics of the last load.
+        weights: `_load`'s fetched forward weights, which an inference plan packs from instead of a staging."""
+        if weights is None and not self.training:
             raise RuntimeError('UNetPlan.staging_table / pack_staged need a plan built with training=True')
-        if getattr(self, '_pack_args', None) is not None:
-            return
-        jobs = []
         with on_device(self.dev):
-            for s in self.steps:
-                jobs.append((s['desc'], s['w'], s['packed']))
-                off = 0
-                for b, a in zip(s['bwd'], s['srcs']):
-                    b['w'] = _backward_weight(s['desc'].kind, s['w'], off, a.c).contiguous()
-                    if b['w'].data_ptr() == s['w'].data_ptr():      # one source: contiguous() returned the forward staging itself
-                        b['w'] = b['w'].clone()
-                    jobs.append((b['desc'], b['w'], b['packed']))
-                    off += a.c
-        n = len(jobs)
-        self._pack_args = ((RnrConvDesc * n)(*[j[0] for j in jobs]), (ctypes.c_void_p * n)(*[j[1].data_ptr() for j in jobs]),
-                           (ctypes.c_void_p * n)(*[j[2].data_ptr() for j in jobs]), n)
+            if self._pack_args is not None:
+                descs, staged, packed, n = self._pack_args
+                if staged is None:
+                    staged = (ctypes.c_void_p * n)(*[w.data_ptr() for w in weights])
+                check(self.L.rnr_pack_conv_weights(descs, staged, packed, n, _stream()))
+            if self.bn_mode == 'running':
+                if state_dict is None:
+                    raise ValueError("UNetPlan.pack_staged: bn_mode 'running' needs the state dict to fold BatchNorm from")
+                g = lambda k: _fetch(state_dict, self._prefix + k, self.dev)
+                for s in self.steps:
+                    bn_key = s['keys'][1]
+                    if bn_key is not None:
+                        self._fold_running(s, g(bn_key + '.weight'), g(bn_key + '.bias'))
 
     def staging_table(self):
         """{state-dict key: [mirror descriptors]} of a training plan: where the new value of every live parameter has to be
         stored for `pack_staged` (and the forward's BatchNorm / bias reads) to see it — `identity_mirror` / `backward_mirrors`
         dictionaries with 'dst', the destination tensor, added.  In 'running' mode BatchNorm's bias has no staged copy (the
         forward reads the folded scale / shift, which `pack_staged` recomputes)."""
-        self._ensure_staging()
+        if not self.training:
+            raise RuntimeError('UNetPlan.staging_table / pack_staged need a plan built with training=True')
         pre, table = self._prefix, {}
         vec = lambda dst, n, **k: dict(identity_mirror((n,), **k), dst=dst)
         for s in self.steps:
@@ -568,24 +572,6 @@ class UNetPlan:
         if (pre + 'out_layer.0.net.1.bias') in self.grads:
             table[pre + 'out_layer.0.net.1.bias'] = [vec(self.out_bias, self.out_channels)]
         return table
-
-    def pack_staged(self, state_dict=None):
-        """Pack every forward and gradient-convolution weight from the staging buffers: one rnr_pack_conv_weights call, the bytes
-        `repack` produces once the staging holds the state-dict's values.  'running' mode folds BatchNorm into the consumers'
-        scale / shift from two parameters each: `state_dict` (the keys `repack` takes) is needed there and refolded as `repack` does."""
-        self._ensure_staging()
-        descs, weights, packed, n = self._pack_args
-        with on_device(self.dev):
-            check(self.L.rnr_pack_conv_weights(descs, weights, packed, n, _stream()))
-            if self.bn_mode == 'running':
-                if state_dict is None:
-                    raise ValueError("UNetPlan.pack_staged: bn_mode 'running' needs the state dict to fold BatchNorm from")
-                g = lambda k: _fetch(state_dict, self._prefix + k, self.dev)
-                for s in self.steps:
-                    bn_key, out = s['keys'][1], s['out']
-                    if bn_key is not None:
-                        out.scale[:, :out.c], out.shift[:, :out.c] = _running_affine(
-                            g(bn_key + '.weight'), g(bn_key + '.bias'), *s['_running'])
 
     def backward(self, grad_raw, want_input_grad=True):
         """The adjoint of the last `forward` (same number of views; its activations are still in the plan): grad_raw

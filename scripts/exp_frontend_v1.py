@@ -38,7 +38,7 @@ if os.environ.get('STATS', '1') == '1':
     for vid in [int(x) for x in os.environ.get('VIEWS', '0,111,300,552').split(',')]:
         pipe.render(*pose(vid))
         torch.cuda.synchronize()
-        ws = pipe._lane_ws[0]
+        ws = pipe._own.ws
         counts = ws[off_counts:off_counts + 4 * (ntiles + 1)].view(torch.int32).cpu().numpy()
         boxes = ws[:nf * 8].view(torch.int16).reshape(nf, 4).cpu().numpy().astype(np.int64)
         tc, wide = counts[:ntiles], counts[ntiles]
@@ -74,9 +74,9 @@ if os.environ.get('STATS', '1') == '1':
                  int((a > 256).sum()), int(((a > 64) & (a <= 256)).sum()), int(a[a <= 256].sum())), flush=True)
 
 # the front end alone, looped (what the rocprofv3 kernel statistics of this run then show)
-pb = pipe._prep(None)
-gb = {m: pipe._gb[m][:1] for m in pipe._gb_maps}
-ws = pipe._lane_ws[0]
+pb = pipe._own.prep
+gb = {m: pipe._own.gb[m][:1] for m in pipe._gb_maps}
+ws = pipe._own.ws
 
 
 def front(i, shade=True):
@@ -86,7 +86,7 @@ def front(i, shade=True):
     ops.rasterize_gbuffer(pipe.mesh, pb['v_uvz'][:1], None, S, pipe.near, pipe.far, maps=pipe._gb_maps, out=gb, workspace=ws, prepared=True)
     if shade:
         ops.shade_inputs(gb, pipe.mesh, proj_inv, R_inv, pipe.textures, pipe.pivots_spec, pipe.pivots_diff, pipe.sh_start_ch,
-                         c_pad=pipe.unet.in_c_pad, net_in=pipe._net_in[:1], tangents=pb['tangents'])
+                         c_pad=pipe.unet.in_c_pad, net_in=pipe._own.net_in[:1], tangents=pb['tangents'])
 
 
 with ops.on_device(dev):

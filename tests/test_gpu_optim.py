@@ -157,6 +157,7 @@ def _plan_buffers(plan):
         res['%d.w' % i] = s['w']
         for j, b in enumerate(s['bwd']):
             res['%d.bwd%d.packed' % (i, j)] = b['packed']
+            res['%d.bwd%d.w' % (i, j)] = b['w']
         if s['bn'] is not None:
             res['%d.gamma' % i] = s['bn']['gamma']
             if s['bn']['beta'] is not None:
@@ -206,6 +207,117 @@ def test_bound_step_leaves_the_plan_as_a_fresh_one(num_down, bn_train):
     net(x, None)
     assert _train_plans(net) == [plan] and not calls, 'the next forward rebuilt or repacked the plan'
     del plan.repack
+
+
+def _perturb(net, seed, running):
+    """Seeded noise, in place, on every live parameter — and on the running statistics, which an eval-mode plan folds (the
+    variance stays positive)."""
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for _, p in net.net._live_params():
+            p.add_(torch.randn(p.shape, generator=g).to(DEV) * 0.1)
+        if running:
+            for m in net.net._live_batchnorms():
+                m.running_mean.add_(torch.randn(m.running_mean.shape, generator=g).to(DEV) * 0.1)
+                m.running_var.add_(torch.rand(m.running_var.shape, generator=g).to(DEV) * 0.1)
+
+
+def _fresh_training_plan(net, plan, hw, n):
+    from rnr_amd.unet import UNetPlan
+    cin, cout, nf0, nd = net.net.cfg
+    sd = {'net.' + k: v for k, v in net.net.state_dict().items()}
+    return UNetPlan(sd, cin, cout, nf0, nd, hw, n, DEV, bn_mode=plan.bn_mode, update_running_stats=plan.bn_mode == 'batch_all',
+                    training=True)
+
+
+def _assert_as_fresh(plan, fresh, before):
+    """Every buffer of `plan` bit-equal to the fresh plan's, none reallocated; returns how many differ from `before`."""
+    got, want = _plan_buffers(plan), _plan_buffers(fresh)
+    assert set(got) == set(want) == set(before)
+    moved = 0
+    for k in sorted(want):
+        assert got[k].data_ptr() == before[k][0], 'buffer %s was reallocated' % k
+        assert torch.equal(got[k], want[k]), k
+        moved += not torch.equal(got[k], before[k][1])
+    return moved
+
+
+@pytest.mark.parametrize('bn_train', [True, False], ids=['bn_train', 'bn_eval'])
+@pytest.mark.parametrize('num_down', [2, 5])
+def test_repack_leaves_a_training_plan_as_a_fresh_one(num_down, bn_train):
+    """The route every unbound training step takes (Unet._train_plan): after `repack` on moved parameters the plan holds what
+    construction from those parameters leaves — two-source layers (num_down = 5 adds more of them) and the single-source
+    stride-2 layers whose gradient weight is the forward tensor itself included."""
+    N, H, W = 2, 32, 32
+    net = _ready(_make_net(num_down, 60 + num_down), bn_train)
+    g = torch.Generator().manual_seed(6)
+    x, lw = torch.randn(N, 16, H, W, generator=g).to(DEV), torch.randn(N, 6, H, W, generator=g).to(DEV)
+    (net(x, None) * lw).sum().backward()
+    plan, = _train_plans(net)
+    assert plan.bn_mode == ('batch_all' if bn_train else 'running')
+    before = {k: (t.data_ptr(), t.clone()) for k, t in _plan_buffers(plan).items()}
+    _perturb(net, 17, running=not bn_train)
+    plan.repack({'net.' + k: v for k, v in net.net.state_dict().items()})
+    torch.cuda.synchronize()
+    moved = _assert_as_fresh(plan, _fresh_training_plan(net, plan, (H, W), N), before)
+    assert moved >= 3 * len(plan.steps), 'the repack changed only %d of %d buffers' % (moved, len(before))
+
+
+@pytest.mark.parametrize('bn_mode', ['batch', 'running'])
+def test_repack_of_an_inference_plan_equals_a_plan_built_from_the_new_weights(bn_mode):
+    from rnr_amd.unet import UNetPlan
+    H, W = 32, 32
+    sd1, sd2 = ({'net.' + k: v for k, v in _make_net(2, seed).net.state_dict().items()} for seed in (21, 22))
+    plan = UNetPlan(sd1, 16, 6, 4, 2, (H, W), 1, DEV, bn_mode=bn_mode)
+    want = UNetPlan(sd2, 16, 6, 4, 2, (H, W), 1, DEV, bn_mode=bn_mode)
+
+    def buffers(p):
+        res = {'out_bias': p.out_bias}
+        for i, s in enumerate(p.steps):
+            res['%d.packed' % i] = s['packed']
+            if 'bias' in s:
+                res['%d.bias' % i], res['%d.shift' % i] = s['bias'], s['out'].shift
+            if s['bn'] is not None:         # 'batch': the parameters the finalise reads
+                res['%d.gamma' % i], res['%d.beta' % i] = s['bn']['gamma'], s['bn']['beta']
+            elif s['keys'][1] is not None:  # 'running': the folded pair
+                res['%d.scale' % i], res['%d.shift' % i] = s['out'].scale, s['out'].shift
+        return res
+
+    before = {k: (t.data_ptr(), t.clone()) for k, t in buffers(plan).items()}
+    plan.repack(sd2)
+    torch.cuda.synchronize()
+    got, ref = buffers(plan), buffers(want)
+    assert set(got) == set(ref) and len(got) >= 2 * len(plan.steps)
+    for k in sorted(ref):
+        assert got[k].data_ptr() == before[k][0], 'buffer %s was reallocated' % k
+        assert torch.equal(got[k], ref[k]), k
+        assert not torch.equal(got[k], before[k][1]), '%s did not change' % k
+    x = torch.randn(1, H, W, plan.in_c_pad, generator=torch.Generator().manual_seed(3)).to(DEV)
+    assert torch.equal(plan.forward(x), want.forward(x))
+
+
+def test_bound_step_then_unbound_change_on_one_plan():
+    """One bound step (mirrors and the batched pack), then parameters move behind the optimiser's back: the next forward
+    repacks the same plan, staging included, to what a fresh plan holds."""
+    from rnr_amd.optim import Adam
+    N, H, W = 2, 32, 32
+    net = _ready(_make_net(2, 93), True)
+    g = torch.Generator().manual_seed(8)
+    x, lw = torch.randn(N, 16, H, W, generator=g).to(DEV), torch.randn(N, 6, H, W, generator=g).to(DEV)
+    (net(x, None) * lw).sum().backward()
+    plan, = _train_plans(net)
+    before = {k: (t.data_ptr(), t.clone()) for k, t in _plan_buffers(plan).items()}
+    Adam([p for p in net.parameters() if p.grad is not None], lr=1e-2).bind(net).step()
+    _perturb(net, 4, running=False)
+    calls = []
+    repack = plan.repack
+    plan.repack = lambda *a, **k: (calls.append(1), repack(*a, **k))[1]
+    net(x, None)
+    del plan.repack
+    torch.cuda.synchronize()
+    assert calls == [1] and _train_plans(net) == [plan]
+    moved = _assert_as_fresh(plan, _fresh_training_plan(net, plan, (H, W), N), before)
+    assert moved >= 3 * len(plan.steps)
 
 
 def test_mirrors_through_the_c_abi():

@@ -326,12 +326,13 @@ def test_pipeline_present_off_is_todays_pipeline(small):
     and no 8-bit buffer exists."""
     off = small['mk'](present=None)
     assert torch.equal(off.render(*small['args'](0, 4)), small['frames'])
-    assert off.presented is None and off._u8 == [None, None]
+    assert off.presented is None and off._own.u8 == [None, None]
     h = off.submit(*small['args'](1, 3))
     assert torch.equal(h.synchronize(), small['base'].render(*small['args'](1, 3))) and h.u8 is None and off.presented is None
     fly = small['mk'](present=None, inflight=2)
     h = fly.submit(*small['args'](0, 2))
     assert torch.equal(h.synchronize(), small['base'].render(*small['args'](0, 2))) and h.u8 is None
+    assert all(s.u8 == [None, None] for s in fly._slots)
 
 
 @pytest.mark.parametrize('kw', [dict(), dict(fuse_ray=True), dict(streams=2, max_views=3), dict(present_rgb=True), dict(present='frame')],

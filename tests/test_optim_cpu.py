@@ -1,5 +1,5 @@
 """CPU: what rnr_amd.optim rests on without a GPU — the numpy restatement of the kernel's formula (tests/optim_ref.py) against
-torch.optim.Adam, the mirror descriptors against the torch expressions of UNetPlan._pack_backward, the new symbols, the
+torch.optim.Adam, the mirror descriptors against the torch expressions of rnr_amd.unet._backward_weight, the new symbols, the
 refusals and the state-dict interchange with torch.optim.Adam."""
 import ctypes
 import os
@@ -67,7 +67,7 @@ def test_float32_restatement_is_as_close_to_float64_as_torch_float32(steps, weig
 # mirror descriptors
 # ------------------------------------------------------------------------------------------------
 def _torch_backward_weights(kind, w, cs):
-    """The expressions of UNetPlan._pack_backward, per source."""
+    """The expressions of rnr_amd.unet._backward_weight as UNetPlan._load stages them, per source."""
     res, off = [], 0
     for c in cs:
         if kind == 0:
