@@ -316,6 +316,23 @@ typedef struct rnr_conv_desc {
  * the two flags are mutually exclusive. */
 #define RNR_CONV_F32_EMU_F16X3 4
 #define RNR_CONV_F32_EMU_ANY (RNR_CONV_F32_EMU_BF16X6 | RNR_CONV_F32_EMU_F16X3)
+/* Half-precision operands on the fp16 matrix cores.  NOT an emulation of fp32: every activation act(scale * x + shift) and every
+ * prescaled weight is rounded ONCE to fp16 (round-to-nearest-even, fp16 subnormals kept) and the products, each exact in fp32,
+ * are accumulated in fp32 by v_mfma_f32_32x32x16_f16 — one MFMA where F16X3 issues three, 16 x fewer MFMA cycles than the
+ * exact-fp32 kernel.  Relative error 2^-11 per operand, i.e. |out - conv(x, w)| <= ((1 + 2^-11)^2 - 1) sum |x w| plus the fp32
+ * accumulation's rounding (tests/test_gpu_conv_f16.py, class D); a U-Net's tanh output keeps >= 50 dB PSNR against the fp32 one
+ * (tests/test_gpu_unet_f16.py).  Weights take F16X3's per-layer power-of-two prescale — the same 2^k, k = min(12 - floor(log2
+ * max |w|), 40), undone exactly in the epilogue — so any finite weights are fine, up to FLT_MAX; a layer whose max |w| is below
+ * 2^-28, and weights more than 2^-26 below the layer's largest, are fp16 subnormals on the 2^-24 grid of the prescaled value and
+ * keep fewer bits.  Range of the activations: magnitudes below 65520 round to a finite fp16 (at most 65504); anything larger
+ * becomes infinite and surfaces in out_raw per "Non-finite inputs" of the direct kernels (the outputs whose window contains it);
+ * values below 2^-14 lie on the 2^-24 grid (fp16 subnormals, honoured by conversion and MFMA), |x| <= 2^-25 enters as 0.  The
+ * weight image is ONE fp16 plane behind the fp32 image (rnr_packed_weight_floats = f32 + 16 + ceil(f32 / 2)).  Same packing /
+ * fallback rules as F16X3: set when packing AND convolving, tile and split-K plans are F16X3's on every shape, shapes the 16-bit
+ * kernels do not cover run the fp32 MFMA kernels from the same buffer (exactly), rnr_conv_algorithm reports 0, refused wherever
+ * the emulation flags are.  Mutually exclusive with both emulation flags and with RNR_CONV_WINOGRAD*; a flag of its own, outside
+ * RNR_CONV_F32_EMU_ANY. */
+#define RNR_CONV_F16 256
 /* Winograd minimal filtering (Lavin & Gray 2016): F(2x2, 3x3) for the 3x3 convolutions — 16 multiplications per 2 x 2
  * output tile instead of 36 — and F(2x2, 2x2) for the two 4x4 stride-2 convolutions, which are sums of 2x2-tap correlations
  * (per input parity phase resp. per output parity class) — 9 instead of 16.  fp32 operands and fp32 accumulation on

@@ -17,7 +17,7 @@
 //                 one fp64 atomic per channel per workgroup) for the next BatchNorm's batch statistics.
 //
 // Kernels: conv_halo_kernel (LDS-halo tiles, exact fp32: every map whose width is a multiple of 32, or 16), conv_mfma_kernel (tap-by-tap gather:
-// the small maps), conv_halo_emu_kernel (opt-in: fp32 emulated on the 16-bit matrix cores, RNR_CONV_F32_EMU_BF16X6 / _F16X3), and — the
+// the small maps), conv_halo_emu_kernel (opt-in: fp32 emulated on the 16-bit matrix cores, RNR_CONV_F32_EMU_BF16X6 / _F16X3, or plain fp16 operands, RNR_CONV_F16), and — the
 // product path since r03, RNR_CONV_WINOGRAD — the fp32 Winograd kernels of conv_wino.inc (F(2x2, 3x3): conv_wino_kernel),
 // conv_wino80.inc (the 80-column out layer), conv_wino2.inc / conv_wino2p.inc (F(2x2, 2x2): conv_wino2_kernel<1> for the
 // stride-2 convolution, conv_wino2p_kernel<2> for the transposed one), conv_wino4.inc (F(4x4, 3x3), RNR_CONV_WINOGRAD4) and
@@ -963,7 +963,8 @@ conv_halo_kernel(const ConvParams P) {
 //
 // Every conv operand is split into a few 16-bit terms whose sum is (nearly) the fp32 value, the partial products of
 // significant weight are accumulated in fp32 by v_mfma_f32_32x32x16_{bf16,f16}; every partial product of two 16-bit
-// terms is exact in fp32.  Two formats:
+// terms is exact in fp32.  Two emulation formats, and the same kernel with ONE term per operand (FMT 2 "f16", RNR_CONV_F16, at
+// EmuFmt<2> below: plain half-precision operands, not an emulation):
 //   FMT 0 "bf16x6": x = h + m + l EXACTLY, three bf16 terms (8 + 8 + 8 significand bits, each the round-to-nearest bf16
 //          of the running remainder); six products of weight >= 2^-16: hh, hm, mh, hl, lh, mm (dropped: <= 2^-24 |ab|).
 //          6 x 32 = 192 MFMA cycles per 16-channel chunk instead of 8 x 64 = 512.
@@ -1011,6 +1012,7 @@ __device__ __forceinline__ void split_f16x2(float x0, float x1, unsigned& h, uns
 template <int FMT> struct EmuFmt;
 template <> struct EmuFmt<0> {
     static constexpr int NT = 3;
+    static constexpr bool PRESCALED = false;     // weights packed as they are
     typedef bf16x8 vec8;
     static __device__ __forceinline__ floatx16 mfma(vec8 a, vec8 b, floatx16 c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
@@ -1019,11 +1021,25 @@ template <> struct EmuFmt<0> {
 };
 template <> struct EmuFmt<1> {
     static constexpr int NT = 2;
+    static constexpr bool PRESCALED = true;      // weights times 2^k at pack time, accumulators times 2^-k in the epilogue
     typedef halfx8 vec8;
     static __device__ __forceinline__ floatx16 mfma(vec8 a, vec8 b, floatx16 c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
     }
     static __device__ __forceinline__ void split(float x0, float x1, unsigned (&t)[2]) { split_f16x2(x0, x1, t[0], t[1]); }
+};
+// FMT 2 "f16" (RNR_CONV_F16): NOT an emulation of fp32 — each operand is ONE fp16 term, its round-to-nearest-even fp16 value
+// (subnormals kept), one product per operand pair: 32 MFMA cycles per chunk, a relative error of 2^-11 per operand.  Weights
+// carry FMT 1's power-of-two prescale (PRESCALED: one definition, pack_weight_emu_kernel), activations enter as they are.
+template <> struct EmuFmt<2> {
+    static constexpr int NT = 1;
+    static constexpr bool PRESCALED = true;
+    typedef halfx8 vec8;
+    static __device__ __forceinline__ floatx16 mfma(vec8 a, vec8 b, floatx16 c) { return EmuFmt<1>::mfma(a, b, c); }
+    static __device__ __forceinline__ void split(float x0, float x1, unsigned (&t)[1]) {
+        const floatx2 v = {x0, x1};
+        t[0] = __builtin_bit_cast(unsigned, __builtin_convertvector(v, halfx2));
+    }
 };
 constexpr int EMU_HEADER_BYTES = 64;     // packed emulation image: [0] float 2^-k (accumulator rescale), [1] float k, [2] uint bits of max|w|
 
@@ -1222,10 +1238,10 @@ conv_halo_emu_kernel(const ConvParams P) {
     }
 
     // ---- epilogue (as conv_halo_kernel: same accumulator layout) ----
-    // f16x3: undo the power-of-two weight scale — at the store, and on the column sums of the statistics (a power of
+    // f16x3, f16: undo the power-of-two weight scale — at the store, and on the column sums of the statistics (a power of
     // two commutes with every fp32 rounding involved, so this equals scaling the accumulators first; scaling all 128 of
     // them in place made the compiler keep both copies and spill)
-    const float winv = FMT == 1 ? *reinterpret_cast<const float*>(P.weight_emu) : 1.0f;
+    const float winv = F::PRESCALED ? *reinterpret_cast<const float*>(P.weight_emu) : 1.0f;
     typedef StatScratch<WAVES_M, BN> Stats;
     static_assert(Stats::BYTES <= 2 * ACHB, "statistics scratch and flag fit the halo buffers");
     double* red = Stats::red(As);
@@ -1238,7 +1254,7 @@ conv_halo_emu_kernel(const ConvParams P) {
     BnArrival arr = {nullptr, 0u};
     const bool bn = with_stats && P.arrive;      // producer-side BatchNorm
     if (bn) arr = bn_arrive(P, n, tid);
-    store_acc_tiles<KIND, WM, WN, TW, FMT == 1>(P, out, acc, n, y0, x0, py, px, wave_m, n0, wn0, l31, h, winv);
+    store_acc_tiles<KIND, WM, WN, TW, F::PRESCALED>(P, out, acc, n, y0, x0, py, px, wave_m, n0, wn0, l31, h, winv);
     if (bn) bn_complete(P, arr, n, tid, Stats::flag(As));
 }
 
@@ -1473,7 +1489,8 @@ __global__ void __launch_bounds__(256) weight_amax_kernel(const float* __restric
 }
 
 // emulation image: 64-byte header, then [par][tap][chunk][NT terms][2 k-halves][wstride][8 x 16 bit]  (conv_halo_emu_kernel).
-// FMT 1 (f16x3): weights are multiplied by 2^k, k = min(12 - floor(log2 max|w|), 40), before the split; header[0] = 2^-k.
+// FMT 1 (f16x3) and FMT 2 (f16): weights are multiplied by 2^k, k = min(12 - floor(log2 max|w|), 40), before the split (FMT 2:
+// before the one rounding to fp16); header[0] = 2^-k.
 template <int FMT>
 __global__ void __launch_bounds__(256)
 pack_weight_emu_kernel(rnr_conv_desc d, const float* __restrict__ w, char* __restrict__ image, long total) {
@@ -1482,7 +1499,7 @@ pack_weight_emu_kernel(rnr_conv_desc d, const float* __restrict__ w, char* __res
     unsigned short* packed = reinterpret_cast<unsigned short*>(image + EMU_HEADER_BYTES);
     float wscale = 1.0f;
     int kexp = 0;
-    if (FMT == 1) {
+    if (EmuFmt<FMT>::PRESCALED) {
         const float amax = __builtin_bit_cast(float, reinterpret_cast<const unsigned*>(image)[2]);
         if (amax > 0.0f) {
             kexp = 12 - ilogbf(amax);
@@ -1553,7 +1570,7 @@ typedef void (*ConvLaunch)(const dim3, const ConvParams&, hipStream_t);
 struct ConvTile {
     ConvFamily family;
     int tw, th, bn;             // pixel tile and columns (80: 64 + a 16-column remainder tile); GATHER: tw consecutive GEMM rows
-    ConvLaunch launch[2][3];    // [HALO_EMU: 0 bf16x6, 1 f16x3; the others: 0][kind], null where there is no such instantiation
+    ConvLaunch launch[3][3];    // [HALO_EMU: 0 bf16x6, 1 f16x3, 2 f16; the others: 0][kind], null where there is no such instantiation
 };
 
 template <int KIND, int WAVES_M, int WAVES_N, int WM, int WN>
@@ -1577,6 +1594,7 @@ static void emu_launchers(ConvTile& t) {
     if constexpr ((KINDS >> KIND) & 1) {
         t.launch[0][KIND] = launch_halo_emu_cfg<0, KIND, WAVES_M, WAVES_N, WM, WN, TW>;
         t.launch[1][KIND] = launch_halo_emu_cfg<1, KIND, WAVES_M, WAVES_N, WM, WN, TW>;
+        t.launch[2][KIND] = launch_halo_emu_cfg<2, KIND, WAVES_M, WAVES_N, WM, WN, TW>;
     }
 }
 template <int KINDS, int WAVES_M, int WAVES_N, int WM, int WN, int TW = 32>
@@ -1616,9 +1634,12 @@ static const ConvTile CONV_TILES[] = {
     {WINO42S, W42_PW, W42_PH, W42_BN, {{nullptr, launch_wino42s, nullptr}, {}}},    // F(4x4, 2x2) stride 2: 32 x 16 output pixels
 };
 
+// EmuFmt's FMT of a descriptor that carries one of CONV_16BIT_FLAGS
+static int emu_format(int flags) { return flags & RNR_CONV_F16 ? 2 : (flags & RNR_CONV_F32_EMU_F16X3 ? 1 : 0); }
+
 static ConvLaunch tile_launcher(const ConvTile& t, const rnr_conv_desc* d) {
     if (d->kind < 0 || d->kind > 2) return nullptr;
-    return t.launch[t.family == HALO_EMU && (d->flags & RNR_CONV_F32_EMU_F16X3) ? 1 : 0][d->kind];
+    return t.launch[t.family == HALO_EMU ? emu_format(d->flags) : 0][d->kind];
 }
 
 // the row of that family and tile which has a kernel for this descriptor's kind (null: none)
@@ -1765,7 +1786,7 @@ static ConvChoice direct_choice(const ConvTile* t, const rnr_conv_desc* d, const
 // The halo kernels (conv_halo_kernel, with an emulation flag conv_halo_emu_kernel): 2-D pixel tiles, 32 or 16 pixels wide, all of
 // them inside the map.
 static ConvChoice try_halo(const rnr_conv_desc* d, const ConvPlan& g) {
-    const bool emu = (d->flags & RNR_CONV_F32_EMU_ANY) != 0, s2 = d->kind == RNR_CONV4x4S2_REFLECT;
+    const bool emu = (d->flags & CONV_16BIT_FLAGS) != 0, s2 = d->kind == RNR_CONV4x4S2_REFLECT;
     const int c = d->c_out_pad;
     auto tile = [&](int tw, int th, int bn) {
         const ConvTile* t = find_tile(emu ? HALO_EMU : HALO, d, tw, th, bn);
@@ -1792,7 +1813,7 @@ static ConvChoice try_halo(const rnr_conv_desc* d, const ConvPlan& g) {
         // (the 80-column out layer was tried on 128 x 80 tiles at one view per call: 364 vs 351 us, not kept)
         if (t && !emu && c <= 64 && count(t) <= tuning().cfg0_small_max) t = tile(32, 4, 64);
     } else if (emu) {
-        // bf16x6 / f16x3 emulation: 256 x 128 tiles (32 x 8 pixels, two waves per SIMD) halve the weight traffic and barriers per
+        // bf16x6 / f16x3 emulation and f16: 256 x 128 tiles (32 x 8 pixels, two waves per SIMD) halve the weight traffic and barriers per
         // MFMA; else 128 rows, and the 4x4-s2 convolution, which runs per input parity phase, also has 64-row tiles
         for (int th = 8; th >= 2 && !t; th /= 2) t = tile(32, th, 128);
     } else {
@@ -1917,9 +1938,10 @@ static size_t packed_f32_floats(const rnr_conv_desc* d) {
 extern "C" size_t rnr_packed_weight_floats(const rnr_conv_desc* d) {
     if (!d) return 0;
     const size_t f32 = packed_f32_floats(d);
-    // emulation image behind the fp32 image: 64-byte header + 3 bf16 terms (6 bytes) or 2 fp16 terms (4 bytes) per weight
+    // 16-bit image behind the fp32 image: 64-byte header + 3 bf16 terms (6 bytes), 2 fp16 terms (4 bytes) or 1 fp16 term per weight
     if (d->flags & RNR_CONV_F32_EMU_BF16X6) return f32 + EMU_HEADER_BYTES / 4 + (f32 * 6 + 3) / 4;
     if (d->flags & RNR_CONV_F32_EMU_F16X3) return f32 + EMU_HEADER_BYTES / 4 + f32;
+    if (d->flags & RNR_CONV_F16) return f32 + EMU_HEADER_BYTES / 4 + (f32 + 1) / 2;
     // Winograd image behind the fp32 image: 16 planes instead of 9 taps (and, with RNR_CONV_WINOGRAD4, the 36-plane image behind it)
     // (with RNR_CONV_WINOGRAD42, the transposed convolution's 25-plane image in the same place; with RNR_CONV_WINOGRAD4_OUT, the
     // 80-column out layer's 36-plane image; with RNR_CONV_WINOGRAD42S, the stride-2 convolution's 25-plane image; at most one of
@@ -1935,17 +1957,18 @@ extern "C" int rnr_pack_conv_weight(const rnr_conv_desc* d, const float* weight,
     hipLaunchKernelGGL(pack_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream),
                        *d, weight, packed, total);
     if (int e = check_launch("pack_weight_kernel")) return e;
-    if (d->flags & RNR_CONV_F32_EMU_ANY) {
+    if (d->flags & CONV_16BIT_FLAGS) {
         char* image = reinterpret_cast<char*>(packed + total);
         static_assert(EMU_HEADER_BYTES % sizeof(double) == 0, "header cleared as doubles");
         hipLaunchKernelGGL(zero_f64_kernel, dim3(1), dim3(256), 0, as_stream(stream), reinterpret_cast<double*>(image),
                            (long)(EMU_HEADER_BYTES / sizeof(double)));
         const dim3 grid((unsigned)((total + 255) / 256));
-        if (d->flags & RNR_CONV_F32_EMU_F16X3) {
+        if (d->flags & (RNR_CONV_F32_EMU_F16X3 | RNR_CONV_F16)) {       // the prescaled formats
             const long nw = (long)(d->c_in0 + d->c_in1) * d->c_out * (d->kind == RNR_CONV3x3_REFLECT ? 9 : 16);
             hipLaunchKernelGGL(weight_amax_kernel, dim3((unsigned)std::min<long>((nw + 255) / 256, 1024)), dim3(256), 0,
                                as_stream(stream), weight, nw, reinterpret_cast<unsigned*>(image) + 2);
-            hipLaunchKernelGGL(pack_weight_emu_kernel<1>, grid, dim3(256), 0, as_stream(stream), *d, weight, image, total);
+            hipLaunchKernelGGL(d->flags & RNR_CONV_F16 ? pack_weight_emu_kernel<2> : pack_weight_emu_kernel<1>, grid, dim3(256), 0,
+                               as_stream(stream), *d, weight, image, total);
         } else {
             hipLaunchKernelGGL(pack_weight_emu_kernel<0>, grid, dim3(256), 0, as_stream(stream), *d, weight, image, total);
         }

@@ -56,6 +56,9 @@ __host__ __device__ __forceinline__ int live_channel(int c, int c_in0, int c_in0
     return ci;
 }
 
+// the flags whose convolutions run conv_halo_emu_kernel on the 16-bit matrix cores: the two fp32 emulations and plain fp16
+constexpr int CONV_16BIT_FLAGS = RNR_CONV_F32_EMU_ANY | RNR_CONV_F16;
+
 // the refusals every entry point that takes a descriptor shares
 inline int check_desc(const rnr_conv_desc* d, const char* who) {
     RNR_REQUIRE(d, "%s: null descriptor", who);
@@ -66,7 +69,7 @@ inline int check_desc(const rnr_conv_desc* d, const char* who) {
                 "%s: c_in1 %d / pad %d", who, d->c_in1, d->c_in1_pad);
     RNR_REQUIRE(d->c_out > 0 && d->c_out_pad >= d->c_out && d->c_out_pad % BK == 0,
                 "%s: c_out %d / pad %d", who, d->c_out, d->c_out_pad);
-    RNR_REQUIRE((d->flags & ~(RNR_CONV_STATS_PREZEROED | RNR_CONV_F32_EMU_ANY | RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD4 |
+    RNR_REQUIRE((d->flags & ~(RNR_CONV_STATS_PREZEROED | CONV_16BIT_FLAGS | RNR_CONV_WINOGRAD | RNR_CONV_WINOGRAD4 |
                               RNR_CONV_WINOGRAD42 | RNR_CONV_WINOGRAD4_OUT | RNR_CONV_WINOGRAD42S)) == 0,
                 "%s: unknown flags 0x%x", who, d->flags);
     RNR_REQUIRE(!(d->flags & RNR_CONV_WINOGRAD4) || (d->flags & RNR_CONV_WINOGRAD),
@@ -78,8 +81,11 @@ inline int check_desc(const rnr_conv_desc* d, const char* who) {
     RNR_REQUIRE(!(d->flags & RNR_CONV_WINOGRAD4_OUT) || (d->flags & RNR_CONV_WINOGRAD),
                 "%s: RNR_CONV_WINOGRAD4_OUT goes with RNR_CONV_WINOGRAD (its fallback for the shapes it does not cover)", who);
     RNR_REQUIRE((d->flags & RNR_CONV_F32_EMU_ANY) != RNR_CONV_F32_EMU_ANY, "%s: choose ONE emulation format", who);
-    RNR_REQUIRE(!(d->flags & RNR_CONV_WINOGRAD) || !(d->flags & RNR_CONV_F32_EMU_ANY),
-                "%s: RNR_CONV_WINOGRAD is an exact-fp32 algorithm, not combined with the emulation formats", who);
+    RNR_REQUIRE(!(d->flags & RNR_CONV_F16) || !(d->flags & RNR_CONV_F32_EMU_ANY),
+                "%s: RNR_CONV_F16 is a precision of its own, not combined with the emulation formats (flags 0x%x)", who,
+                d->flags & CONV_16BIT_FLAGS);
+    RNR_REQUIRE(!(d->flags & RNR_CONV_WINOGRAD) || !(d->flags & CONV_16BIT_FLAGS),
+                "%s: RNR_CONV_WINOGRAD is an exact-fp32 algorithm, not combined with the emulation formats or RNR_CONV_F16", who);
     return 0;
 }
 inline int check_size(const rnr_conv_desc* d, int num_views, int in_h, int in_w, const char* who) {

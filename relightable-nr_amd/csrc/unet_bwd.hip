@@ -534,8 +534,8 @@ unet_out_backward_kernel(const float* __restrict__ g_out, const float* __restric
 
 static int check_bwd_desc(const rnr_conv_desc* d, const char* who) {
     if (int e = check_desc(d, who)) return e;
-    RNR_REQUIRE(!(d->flags & RNR_CONV_F32_EMU_ANY), "%s: the backward is exact fp32 only (emulation flags 0x%x)", who,
-                d->flags & RNR_CONV_F32_EMU_ANY);
+    RNR_REQUIRE(!(d->flags & CONV_16BIT_FLAGS), "%s: the backward is exact fp32 only (emulation flags 0x%x)", who,
+                d->flags & CONV_16BIT_FLAGS);
     return 0;
 }
 static int check_bwd_size(const rnr_conv_desc* d, int num_views, int in_h, int in_w, const char* who) {

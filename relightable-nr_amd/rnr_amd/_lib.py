@@ -187,6 +187,8 @@ def _enum_keys(first):          # the enum that starts with RNR_<first>, as lowe
 
 
 EMU_FLAGS = {'f32': 0, 'bf16x6': CONSTANTS['CONV_F32_EMU_BF16X6'], 'f16x3': CONSTANTS['CONV_F32_EMU_F16X3']}
+# every UNetPlan / RNRPipeline precision -> its descriptor flag: the emulations of fp32 and plain half precision (RNR_CONV_F16)
+PRECISION_FLAGS = dict(EMU_FLAGS, f16=CONSTANTS['CONV_F16'])
 BN_BWD_MODES = {k: CONSTANTS['BN_BWD_' + k.upper()] for k in _enum_keys('BN_BWD_BATCH')}
 PRESENT_MODES = {k: CONSTANTS['PRESENT_' + k.upper()] for k in _enum_keys('PRESENT_FRAME')}
 # RNR_METRIC_* outputs, in the order of rnr_image_metrics' out columns

@@ -23,7 +23,7 @@ Calling modes:
 import numpy as np
 import torch
 
-from . import autograd, metrics, ops
+from . import _lib, autograd, metrics, ops
 from .unet import UNetPlan
 
 
@@ -123,6 +123,9 @@ class RNRPipeline:
         lp: environment map [1,Hl,Wl,3] or [Hl,Wl,3] (LightingSH.reconstruct_lp output); may be None when
             sh_coeff [L,(lmax+1)^2,3] is given: then the probe is reconstructed from the coefficients on every call
             (like `lighting_model(lighting_idx, is_lp=True)` inside RayRenderer.forward, network.py:494-495)
+        precision: UNetPlan's — 'f32' (default), the fp32 emulations 'bf16x6' / 'f16x3', or 'f16' (half-precision operands, fp32
+            accumulation: frames within >= 50 dB PSNR of the 'f32' ones, include/rnr_hip.h RNR_CONV_F16); other than 'f32' forces
+            conv_algo 'direct' and excludes fuse_ray.
         present: None (no 8-bit output: no launch, no buffer), 'frame' (the frame as cv2.imwrite gets it, test_rnr.py:377) or
             'composite' (that over the background of test_rnr.py:386-393 wherever alpha is 0): ops.present_u8 behind the ray
             stage of every view group / call in flight.  The bytes of the last call: `self.presented` [N,S,S,3] uint8, B,G,R
@@ -130,6 +133,8 @@ class RNRPipeline:
         background_probe: [Hl,Wl,3] probe shown by 'composite' instead of the one the frame was lit with — LightingLP's
             full-resolution probe (img_bg_lp) for a sharp background under smooth SH lighting (default: img_bg_sh).
         """
+        if precision not in _lib.PRECISION_FLAGS:           # before anything is uploaded
+            raise ValueError("precision must be one of %s" % sorted(_lib.PRECISION_FLAGS))
         self.dev = torch.device(device)
         # fuse_ray: the ray renderer split in two — ops.ray_weights (everything that does not depend on the U-Net) and the out
         # layer's epilogue (rnr_conv2d_ray: bias + tanh + the sum over the 26 rays, straight from the accumulators) — instead

@@ -122,7 +122,10 @@ class UNetPlan:
         precision 'f32': exact fp32 MFMA (v_mfma_f32_32x32x2_f32).  'bf16x6' / 'f16x3': fp32 emulated on the 16-bit matrix
         cores — operands split into three bf16 terms (exactly; six partial products) or two fp16 terms (22 significand
         bits; three partial products), accumulated in fp32; error of the order of fp32's own rounding, 2.7x / 5.3x fewer
-        MFMA cycles (include/rnr_hip.h, RNR_CONV_F32_EMU_BF16X6 / RNR_CONV_F32_EMU_F16X3).
+        MFMA cycles (include/rnr_hip.h, RNR_CONV_F32_EMU_BF16X6 / RNR_CONV_F32_EMU_F16X3).  'f16': half-precision operands, NOT
+        an emulation — every activation and prescaled weight rounded once to fp16, fp32 accumulation, one MFMA where f16x3 issues
+        three; relative error 2^-11 per operand, the tanh output keeps >= 50 dB PSNR against 'f32' (RNR_CONV_F16; activations
+        must stay below 65520 in magnitude).  The three 16-bit precisions follow the same rules: conv_algo 'direct', inference only.
         conv_algo 'winograd': the 3x3 convolutions run as Winograd F(2x2, 3x3) and the 4x4 stride-2 ones (both directions) as
         F(2x2, 2x2) — fp32 operands and accumulation on the same matrix-core instruction, 2.25x / 1.78x fewer multiplications
         (include/rnr_hip.h, RNR_CONV_WINOGRAD; 'f32' only) — where the layer shape allows; 'winograd4' (the DEFAULT since r04): additionally
@@ -155,8 +158,8 @@ class UNetPlan:
                                       "(precision %r)" % (precision,))
         if training and share_weights_with is not None:
             raise NotImplementedError('UNetPlan(training=True) owns its weights (share_weights_with)')
-        if precision not in _lib.EMU_FLAGS:
-            raise ValueError("precision must be one of %s" % sorted(_lib.EMU_FLAGS))
+        if precision not in _lib.PRECISION_FLAGS:
+            raise ValueError("precision must be one of %s" % sorted(_lib.PRECISION_FLAGS))
         if bn_mode not in ('batch', 'batch_all', 'running'):
             raise ValueError("bn_mode must be 'batch', 'batch_all' or 'running'")
         if share_weights_with is not None:
@@ -174,18 +177,20 @@ class UNetPlan:
         if conv_algo not in ('direct', 'winograd', 'winograd4'):
             raise ValueError("conv_algo must be 'direct', 'winograd' or 'winograd4'")
         if precision != 'f32':
-            conv_algo = 'direct'        # the emulation kernels have no Winograd form
+            conv_algo = 'direct'        # the 16-bit kernels (emulations and f16) have no Winograd form
         self.conv_algo = conv_algo
         self.bn_mode = bn_mode
         self.precision = precision
-        # f16x3 splits activations into fp16 terms: |act(scale * x + shift)| must stay below 65504, which BatchNorm outputs do
+        # f16x3 splits activations into fp16 terms, f16 rounds them to one: |act(scale * x + shift)| must stay below 65504, which BatchNorm outputs do
         # but the four un-normalised convolutions of the innermost block need not for exotic weights.  check_finite=True makes
         # every forward verify (one host synchronisation) that its result holds no inf / NaN — a debugging aid, off by default.
         # Winograd spreads an inf / NaN activation over the whole 2 x 2 tiles whose patch contains it (a direct convolution
         # confines it to the windows that contain it; include/rnr_hip.h, RNR_CONV_WINOGRAD).  check_finite=None (the default)
         # therefore checks the FIRST forward of a Winograd plan — input and output, one host synchronisation, once — and warns;
-        # True checks every forward and raises; False never checks.
-        self.check_finite = 'first' if (check_finite is None and conv_algo != 'direct') else bool(check_finite)
+        # True checks every forward and raises; False never checks.  An explicit 'first' on a direct plan (the 16-bit precisions)
+        # checks the first forward in the same way and RAISES, naming the precision's range: there a non-finite value is an error of
+        # the operands' range, not a property of the algorithm.
+        self.check_finite = 'first' if (check_finite == 'first' or (check_finite is None and conv_algo != 'direct')) else bool(check_finite)
         self.L = _lib.load()
         self.dev = device
         self.N = int(max_views)
@@ -215,7 +220,7 @@ class UNetPlan:
             s0 = srcs[0]
             s1 = srcs[1] if len(srcs) > 1 else None
             desc = RnrConvDesc(kind, s0.c, s0.c_pad, s1.c if s1 else 0, s1.c_pad if s1 else 0, c_out, _pad16(c_out))
-            desc.flags |= _lib.EMU_FLAGS[precision]
+            desc.flags |= _lib.PRECISION_FLAGS[precision]
             if conv_algo != 'direct':
                 desc.flags |= _lib.CONV_WINOGRAD
             if conv_algo == 'winograd4' and kind == CONV3x3_REFLECT and desc.c_out_pad % 64 == 0:
@@ -741,7 +746,10 @@ class UNetPlan:
         res = self.out.data[:n] if ray is None else ray[1]
         if self.check_finite == 'first' and not torch.cuda.is_current_stream_capturing():
             self.check_finite = False
-            if not (bool(torch.isfinite(net_in[:n]).all()) and (mask is not None or bool(torch.isfinite(res).all()))):
+            finite = bool(torch.isfinite(net_in[:n]).all()) and (mask is not None or bool(torch.isfinite(res).all()))
+            if not finite and self.conv_algo == 'direct':
+                raise FloatingPointError(self._range_message('input or output of the first call'))
+            if not finite:
                 import warnings
                 warnings.warn("UNetPlan(conv_algo=%r): non-finite values in the network input or output of the first call; the "
                               "Winograd kernels spread an inf / NaN activation over every output tile whose input patch contains it "
@@ -750,9 +758,16 @@ class UNetPlan:
                               "(include/rnr_hip.h, RNR_CONV_WINOGRAD / RNR_CONV_WINOGRAD4) — use conv_algo='direct' to localise it"
                               % self.conv_algo, RuntimeWarning, stacklevel=2)
         elif self.check_finite is True and mask is None and not bool(torch.isfinite(res).all()):
-            raise FloatingPointError('UNetPlan(precision=%r): non-finite values in the network output (f16x3 needs activations '
-                                     'below 65504: include/rnr_hip.h, RNR_CONV_F32_EMU_F16X3)' % self.precision)
+            raise FloatingPointError(self._range_message('output'))
         return res
+
+    def _range_message(self, where):
+        """check_finite's error text: what the plan's precision asks of its activations"""
+        ranges = {'f16': 'f16 rounds every activation to fp16: magnitudes of 65520 and above become infinite; include/rnr_hip.h, RNR_CONV_F16',
+                  'f16x3': 'f16x3 needs activations below 65504: include/rnr_hip.h, RNR_CONV_F32_EMU_F16X3',
+                  'bf16x6': 'bf16x6 needs finite operands below 2^127: include/rnr_hip.h, RNR_CONV_F32_EMU_BF16X6'}
+        return 'UNetPlan(precision=%r): non-finite values in the network %s (%s)' % (
+            self.precision, where, ranges.get(self.precision, 'the direct kernels confine an inf / NaN activation to the windows that contain it'))
 
     def _run_steps(self, n, mask, L, st, ray=None):
         last = self.steps[-1]
