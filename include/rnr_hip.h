@@ -407,6 +407,24 @@ size_t rnr_packed_weight_floats(const rnr_conv_desc* d);
  * ConvTranspose2d weight [c_in0 + c_in1, c_out, 4, 4] (pytorch_prototyping.py:154-159). */
 int rnr_pack_conv_weight(const rnr_conv_desc* d, const float* weight, float* packed, void* stream);
 
+/* Size limits of the forward convolutions (rnr_conv2d, rnr_conv2d_masked, rnr_conv2d_fused, rnr_conv2d_ray,
+ * rnr_conv_active_tiles).  A call beyond one of them fails with "too large" and the limit BEFORE anything is launched; the
+ * host queries below answer such sizes with their error value (rnr_conv_algorithm / rnr_conv_winograd_tile: -1;
+ * rnr_conv_tile_count, rnr_conv_workspace_bytes, rnr_conv_sync_bytes: 0).  With OH x OW the output map:
+ *   H * W < 2^31                          pixels of one view (the 32-bit pixel index)
+ *   N * H * W < 2^31, N * OH * OW < 2^31  GEMM rows and output pixels of the call (int)
+ *   workgroups of the launch < 2^31       (pixel tiles x column tiles x parity classes x K slices; binds only beyond 65536 columns)
+ *   64 * OW * c_out_pad * 4 < 2^31        bytes of 64 output rows: the 32-bit store offsets behind a tile's first pixel
+ *   N * c_out_pad < 2^24                  statistics entries (32-bit byte offsets into the eight statistics shards)
+ *   rnr_packed_weight_floats(d) * 4 < 2^31  the packed weight (read with 32-bit byte offsets; rnr_pack_conv_weight refuses it too)
+ * Buffers themselves may be of any size: views, output tiles and split-K slabs are addressed from 64-bit bases (tested with
+ * input and output buffers beyond 4 GiB).  INSIDE one source view the halo and Winograd kernels use a 32-bit byte offset:
+ * a source view of 2^31 bytes or more (H * W * c_in_pad * 4 of the larger source) runs the gather kernel (direct, algorithm
+ * 0, no tile mask: rnr_conv_tile_count is 0) whatever Winograd flags the descriptor carries — exact fp32 — and, since that
+ * kernel has no 16-bit form, a call with RNR_CONV_F32_EMU_* or RNR_CONV_F16 on such a view is refused ("no 16-bit-format kernel
+ * for a source view of ... bytes").  A view of exactly 2^31 bytes (2048 x 2048 x 128) is already outside: the hardware would
+ * lose its last dword. */
+
 /* Which algorithm rnr_conv2d* runs for (desc, N, input H, input W): 0 = direct implicit GEMM, 1 = Winograd F(2x2, 3x3),
  * 3 = the same for the 80-column out layer (16 x 16 x 4 MFMA tiles; with RNR_CONV_WINOGRAD4_OUT it may run F(4x4, 3x3) under the
  * same code: rnr_conv_winograd_tile), 2 = Winograd F(2x2, 2x2) (16 multiplications per 2 x 2

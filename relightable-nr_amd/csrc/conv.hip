@@ -1843,7 +1843,9 @@ static ConvChoice try_gather(const rnr_conv_desc* d, const ConvPlan& g) {
 // The candidates in priority order; the first that qualifies runs.  The columns are THE rule for masked and ray-epilogue
 // launches: the out layer's own Winograd kernels take a tile mask, the other Winograd kernels do not, and the ray-renderer
 // epilogue lives in the direct 80-column kernel — those calls run the direct kernels, on the direct kernels' tiles.  The halo and
-// Winograd kernels address a view with 32-bit element offsets: views of 2^30 elements and more are left to the gather kernel.
+// Winograd kernels address a source view with a 32-bit BYTE offset into a buffer resource of 0x7fffffff bytes (buffer_rsrc,
+// halo_load): a source view of VIEW_BYTES_MAX bytes or more (big_view) is left to the gather kernel, which addresses with size_t.
+// The gather kernel has no 16-bit form: such a view with one of CONV_16BIT_FLAGS has no kernel (big_view_refused).
 static const struct {
     ConvChoice (*qualify)(const rnr_conv_desc*, const ConvPlan&);
     bool masked, ray, big_view;
@@ -1859,6 +1861,26 @@ static const struct {
     {try_gather, true, true, true},
 };
 
+// The halo and Winograd kernels read source views of fewer bytes than this: every dword of a load must END inside the 0x7fffffff
+// bytes of the resource's range.  Measured (profiles/conv_large.txt): the range check is per dword and on its end — of a view
+// of exactly 2^31 bytes the last dword alone (it ends at byte 2^31) reads as zero, beyond 2^31 bytes every dword does.
+constexpr long VIEW_BYTES_MAX = 1L << 31;
+// bytes of the larger source view of a call
+static long source_view_bytes(const rnr_conv_desc* d, int H, int W) {
+    return (long)H * W * (d->c_in0_pad > d->c_in1_pad ? d->c_in0_pad : d->c_in1_pad) * (long)sizeof(float);
+}
+static bool big_view_refused(const rnr_conv_desc* d, int H, int W) {
+    return (d->flags & CONV_16BIT_FLAGS) && source_view_bytes(d, H, W) >= VIEW_BYTES_MAX;
+}
+// The kernels read the packed weight — the fp32 image and the 16-bit or Winograd image behind it — through buffer resources
+// with 32-bit byte offsets (wrsrc), like a source view: all of it must lie below 2^31 bytes.
+static bool weight_fits(const rnr_conv_desc* d) { return rnr_packed_weight_floats(d) * sizeof(float) < (size_t)VIEW_BYTES_MAX; }
+// what a host query checks before it plans: a descriptor it can read, sizes inside the limits, a kernel for the view
+static bool plannable(const rnr_conv_desc* d, int N, int H, int W) {
+    return d && N > 0 && H > 0 && W > 0 && d->kind >= 0 && d->kind <= 2 && !conv_size_limit(d, N, H, W) && weight_fits(d) &&
+           !big_view_refused(d, H, W);
+}
+
 // the plan of ONE call: geometry, kernel, grid and split depth of the launch `mode` describes
 static ConvPlan plan_conv(const rnr_conv_desc* d, int N, int H, int W, ConvMode mode) {
     ConvPlan p = {};
@@ -1870,7 +1892,7 @@ static ConvPlan plan_conv(const rnr_conv_desc* d, int N, int H, int W, ConvMode 
     p.M = N * p.Ho * p.Wo;
     p.chunks_per_tap = (d->c_in0_pad + d->c_in1_pad) / BK;
     p.kt_total = p.taps * p.chunks_per_tap;
-    const bool big_view = (long)H * W * (d->c_in0_pad > d->c_in1_pad ? d->c_in0_pad : d->c_in1_pad) >= (1L << 30);
+    const bool big_view = source_view_bytes(d, H, W) >= VIEW_BYTES_MAX;
     ConvChoice c = NO_CHOICE;
     for (const auto& cand : CONV_CANDIDATES) {
         if ((mode == CONV_MASKED && !cand.masked) || (mode == CONV_RAY && !cand.ray) || (big_view && !cand.big_view)) continue;
@@ -1953,6 +1975,9 @@ extern "C" size_t rnr_packed_weight_floats(const rnr_conv_desc* d) {
 extern "C" int rnr_pack_conv_weight(const rnr_conv_desc* d, const float* weight, float* packed, void* stream) {
     if (int e = check_desc(d, "rnr_pack_conv_weight")) return e;
     RNR_REQUIRE(weight && packed, "rnr_pack_conv_weight: null pointer argument");
+    RNR_REQUIRE(rnr_packed_weight_floats(d) * sizeof(float) < (1ul << 31),
+                "rnr_pack_conv_weight: too large (packed weight of %zu bytes does not fit a 32-bit byte offset)",
+                rnr_packed_weight_floats(d) * sizeof(float));
     const long total = (long)packed_f32_floats(d);
     hipLaunchKernelGGL(pack_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream),
                        *d, weight, packed, total);
@@ -2013,8 +2038,9 @@ extern "C" int rnr_pack_conv_weight(const rnr_conv_desc* d, const float* weight,
 }
 
 extern "C" size_t rnr_conv_workspace_bytes(const rnr_conv_desc* d, int num_views, int in_h, int in_w) {
-    if (!d || num_views <= 0) return 0;
+    if (!plannable(d, num_views, in_h, in_w)) return 0;
     const ConvPlan pl = plan_conv(d, num_views, in_h, in_w, CONV_PLAIN);
+    if (pl.wgs() * pl.splitk > CONV_INT_MAX) return 0;
     if (pl.splitk <= 1) return 256;
     return (size_t)pl.splitk * num_views * pl.OH * pl.OW * d->c_out_pad * sizeof(float) + 256;
 }
@@ -2030,33 +2056,38 @@ static SyncLayout sync_layout(const rnr_conv_desc* d, int num_views) {
 }
 
 // (the size does not depend on the plan, hence not on the map size, and grows with the number of views)
-extern "C" size_t rnr_conv_sync_bytes(const rnr_conv_desc* d, int max_views, int /*in_h*/, int /*in_w*/) {
-    if (!d || max_views <= 0) return 0;
+// (in_h, in_w = 0, 0: no map size to hold against the limits)
+extern "C" size_t rnr_conv_sync_bytes(const rnr_conv_desc* d, int max_views, int in_h, int in_w) {
+    if (!d || max_views <= 0 || (long)max_views * d->c_out_pad >= (1L << 24)) return 0;
+    if (in_h > 0 && in_w > 0 && !plannable(d, max_views, in_h, in_w)) return 0;
     return sync_layout(d, max_views).total;
 }
 
 extern "C" int rnr_conv_algorithm(const rnr_conv_desc* d, int num_views, int in_h, int in_w) {
-    if (!d || num_views <= 0 || d->kind < 0 || d->kind > 2) return -1;
-    return CONV_ALGORITHM[plan_conv(d, num_views, in_h, in_w, CONV_PLAIN).tile->family];
+    if (!plannable(d, num_views, in_h, in_w)) return -1;
+    const ConvPlan pl = plan_conv(d, num_views, in_h, in_w, CONV_PLAIN);
+    return pl.tile && pl.wgs() * pl.splitk <= CONV_INT_MAX ? CONV_ALGORITHM[pl.tile->family] : -1;
 }
 
 extern "C" int rnr_conv_winograd_tile(const rnr_conv_desc* d, int num_views, int in_h, int in_w) {
-    if (!d || num_views <= 0 || d->kind < 0 || d->kind > 2) return -1;
-    return CONV_WINOGRAD_TILE[plan_conv(d, num_views, in_h, in_w, CONV_PLAIN).tile->family];
+    if (!plannable(d, num_views, in_h, in_w)) return -1;
+    const ConvPlan pl = plan_conv(d, num_views, in_h, in_w, CONV_PLAIN);
+    return pl.tile && pl.wgs() * pl.splitk <= CONV_INT_MAX ? CONV_WINOGRAD_TILE[pl.tile->family] : -1;
 }
 
 // (the tiles of a MASKED launch of this descriptor; the mask of a ray-epilogue launch is laid out like that of a masked
 // launch of the descriptor without its Winograd flags)
 extern "C" size_t rnr_conv_tile_count(const rnr_conv_desc* d, int num_views, int in_h, int in_w) {
-    if (!d || num_views <= 0) return 0;
+    if (!plannable(d, num_views, in_h, in_w)) return 0;
     const ConvPlan pl = plan_conv(d, num_views, in_h, in_w, CONV_MASKED);
-    return pl.maskable ? (size_t)pl.mtiles : 0;
+    return pl.maskable && pl.wgs() * pl.splitk <= CONV_INT_MAX ? (size_t)pl.mtiles : 0;
 }
 
 extern "C" int rnr_conv_active_tiles(const rnr_conv_desc* d, const float* alpha, uint8_t* tile_mask, int num_views,
                                      int in_h, int in_w, void* stream) {
     if (int e = check_desc(d, "rnr_conv_active_tiles")) return e;
     RNR_REQUIRE(alpha && tile_mask, "rnr_conv_active_tiles: null pointer argument");
+    if (int e = check_size(d, num_views, in_h, in_w, "rnr_conv_active_tiles")) return e;
     const ConvPlan pl = plan_conv(d, num_views, in_h, in_w, CONV_MASKED);
     RNR_REQUIRE(pl.maskable && pl.mtiles > 0,
                 "rnr_conv_active_tiles: this convolution does not run on maskable pixel tiles (3x3 halo plan without split-K)");
@@ -2076,6 +2107,8 @@ static int check_call(const rnr_conv_desc* d, const rnr_conv_src* src0, const rn
     RNR_REQUIRE(d->c_in1_pad == 0 || (src1 && src1->data && src1->channels == d->c_in1_pad),
                 "rnr_conv2d: second source missing or channel mismatch");
     if (int e = check_size(d, num_views, in_h, in_w, "rnr_conv2d")) return e;
+    RNR_REQUIRE(weight_fits(d), "rnr_conv2d: too large (packed weight of %zu bytes does not fit a 32-bit byte offset)",
+                rnr_packed_weight_floats(d) * sizeof(float));
     if (bn && bn->gamma) {
         RNR_REQUIRE(bn->beta && bn->scale && bn->shift, "rnr_conv2d_fused: null BatchNorm pointer");
         RNR_REQUIRE(!(bn->running_mean || bn->running_var) || num_views == 1,
@@ -2153,8 +2186,14 @@ static int conv2d_run(const rnr_conv_desc* d, const rnr_conv_src* src0, const rn
     const bool with_bn = sync && bn && bn->gamma;            // sync: rnr_conv2d_fused
     hipStream_t st = as_stream(stream);
 
+    RNR_REQUIRE(!big_view_refused(d, in_h, in_w),
+                "rnr_conv2d: no 16-bit-format kernel for a source view of %ld bytes (H=%d W=%d, %d channels): the halo kernels "
+                "address a view with a 32-bit byte offset, limit %ld bytes (flags 0x%x)",
+                source_view_bytes(d, in_h, in_w), in_h, in_w, d->c_in0_pad > d->c_in1_pad ? d->c_in0_pad : d->c_in1_pad,
+                VIEW_BYTES_MAX - 1, d->flags & CONV_16BIT_FLAGS);
     const ConvPlan pl = plan_conv(d, num_views, in_h, in_w, ray ? CONV_RAY : (tile_mask ? CONV_MASKED : CONV_PLAIN));
     RNR_REQUIRE(pl.tile, "rnr_conv2d: no kernel for this convolution");
+    RNR_REQUIRE(pl.wgs() * pl.splitk <= CONV_INT_MAX, "rnr_conv2d: too large (%ld workgroups do not fit an int)", pl.wgs() * pl.splitk);
     if (ray)
         RNR_REQUIRE(d->kind == RNR_CONV3x3_REFLECT && pl.tile->family == HALO && pl.tile->bn == 80 && d->c_out % 3 == 0,
                     "rnr_conv2d_ray: only the exact-fp32 3x3 out layer on the 80-column plan (65 <= c_out <= 80, c_out = 3 x rays, map "

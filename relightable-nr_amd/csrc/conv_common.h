@@ -88,11 +88,36 @@ inline int check_desc(const rnr_conv_desc* d, const char* who) {
                 "%s: RNR_CONV_WINOGRAD is an exact-fp32 algorithm, not combined with the emulation formats or RNR_CONV_F16", who);
     return 0;
 }
+// The upper size limits of a convolution call (include/rnr_hip.h, "Size limits"): what the kernels and the planner hold in an
+// int or in a 32-bit buffer offset.  Null when the sizes fit, else the limit they break — for check_size's message and for the
+// host queries, which return their error value instead of planning with a wrapped int.
+//   pixels per view            H * W < 2^31                    the pixel index inside a view (halo_pixel, the gather kernel's rows)
+//   GEMM rows, output pixels   N * H * W, N * OH * OW < 2^31   ConvPlan::M, mtiles, the tile decode, the split-K reduce's rows per view
+//   one band of output rows    64 * OW * c_out_pad * 4 < 2^31  ColumnStore's offsets behind a tile's first pixel (a tile spans at most
+//                                                              33 output rows), which must stay below the offset the stores drop
+//   statistics                 N * c_out_pad < 2^24            bn_finalize_views' byte offsets into the eight statistics shards
+// (conv.hip adds what needs the plan or the packed layout: the workgroup count, the packed weight below 2^31 bytes, a source view
+// of 2^31 bytes or more)
+constexpr long CONV_INT_MAX = 0x7fffffffL;
+inline const char* conv_size_limit(const rnr_conv_desc* d, int num_views, int in_h, int in_w) {
+    // (the output size in long: conv_out_size doubles the transposed kind's map in an int)
+    const long N = num_views, hw = (long)in_h * in_w, up = d->kind == RNR_CONVT4x4S2 ? 2 : 1;
+    const long oh = d->kind == RNR_CONV4x4S2_REFLECT ? in_h / 2 : up * in_h, ow = d->kind == RNR_CONV4x4S2_REFLECT ? in_w / 2 : up * in_w;
+    if (hw > CONV_INT_MAX) return "H * W pixels per view do not fit the 32-bit pixel index";
+    const long ohw = oh * ow;                       // <= 4 H W: no long overflows below
+    if (N * hw > CONV_INT_MAX || N * ohw > CONV_INT_MAX) return "N * H * W or N * OH * OW does not fit an int";
+    if (ow * d->c_out_pad > CONV_INT_MAX / 256)     // 64 rows x 4 bytes
+        return "64 output rows of OW * c_out_pad floats do not fit a 32-bit byte offset";
+    if (N * d->c_out_pad >= (1L << 24)) return "N * c_out_pad statistics do not fit a 32-bit byte offset";
+    return nullptr;
+}
 inline int check_size(const rnr_conv_desc* d, int num_views, int in_h, int in_w, const char* who) {
     const int min_hw = d->kind == RNR_CONVT4x4S2 ? 1 : 2;   // ReflectionPad2d(1) needs >= 2 pixels
     RNR_REQUIRE(num_views > 0 && in_h >= min_hw && in_w >= min_hw, "%s: bad sizes N=%d H=%d W=%d", who, num_views, in_h, in_w);
     RNR_REQUIRE(d->kind != RNR_CONV4x4S2_REFLECT || (in_h % 2 == 0 && in_w % 2 == 0), "%s: stride-2 conv needs even input size",
                 who);
+    const char* limit = conv_size_limit(d, num_views, in_h, in_w);
+    RNR_REQUIRE(!limit, "%s: too large (N=%d H=%d W=%d, c_out_pad %d): %s", who, num_views, in_h, in_w, d->c_out_pad, limit);
     return 0;
 }
 

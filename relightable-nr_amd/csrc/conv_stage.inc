@@ -4,8 +4,11 @@
 // columns go (ColumnStore) and what do they sum to (acc_column_stats).  Included by conv.hip in front of its first kernel.
 // Everything is a __forceinline__ function over small structs of scalars; a member a kernel does not use costs it nothing.
 
-// the raw buffer resource of the convolution kernels: base pointer, no stride, no bounds worth the name (offsets stay below 2^31;
-// an offset of 0x7fffffff is out of range and the hardware drops the access), dword data format
+// the raw buffer resource of the convolution kernels: base pointer, no stride, 0x7fffffff BYTES of range, dword data format.  The
+// hardware drops a dword that does not END inside the range instead of faulting (a load returns zero for it): the stores of
+// padding columns rely on it (an offset of 0x7fffffff), and so every byte a kernel means to reach must lie below 0x7fffffff —
+// plan_conv keeps a source view the halo and Winograd kernels read below VIEW_BYTES_MAX = 2^31 bytes, conv_size_limit a band of
+// output rows
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_rsrc(const void* p) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x27000);
 }
@@ -85,8 +88,9 @@ __device__ __forceinline__ ConvParams touch_params() {
 }
 // Next-tile touch (conv_wino4.inc, "Next-tile prefetch"): TOUCH dwords of pixel `pixel` (index inside view n) of source 0, 128
 // bytes apart from the first chunk's channel offset, clamped to the pixel's last dword.  The resource covers exactly the view
-// (plan_conv keeps H * W * C below 2^30), so the hardware drops an offset outside it instead of faulting; the values are never
-// used and the caller pins pf[] to the kernel's end.
+// (plan_conv keeps a view's H * W * C * 4 bytes below 2^31, so the byte count fits the resource's range and the byte offsets an
+// int), so the hardware drops an offset outside it instead of faulting; the values are never used and the caller pins pf[] to
+// the kernel's end.
 template <int TOUCH>
 __device__ __forceinline__ void touch_pixel(const ConvParams& P, int n, unsigned pixel, unsigned (&pf)[TOUCH]) {
     const unsigned C = (unsigned)P.src_c[0];
@@ -101,8 +105,9 @@ __device__ __forceinline__ void touch_pixel(const ConvParams& P, int n, unsigned
 // ---- which source and channel chunk feeds this K step ----
 // K step = chunk * NPH + input parity phase (NPH = 4 for the 4x4 stride-2 convolution, else 1).  The chunk selects the source
 // across the skip concat; view base + channel offset are wave-uniform (resource + scalar offset), the per-lane part of a halo
-// fetch is a 32-bit byte offset (plan_conv keeps H*W*C below 2^30): one buffer load and one VALU mad.  (Flat 64-bit addresses make
-// the unrolled tap loops keep a strength-reduced pointer pair per tap alive across the chunk loop — registers the kernels lack.)
+// fetch is a 32-bit byte offset (plan_conv keeps a view's H*W*C*4 bytes below 2^31, inside the resource's range): one buffer load
+// and one VALU mad.  (Flat 64-bit addresses make the unrolled tap loops keep a strength-reduced pointer pair per tap alive
+// across the chunk loop — registers the kernels lack.)
 // sc / sh: the producer's BatchNorm scale / shift of view n for channel quad q of the chunk.
 struct HaloSrc { __amdgpu_buffer_rsrc_t rsrc; unsigned C; unsigned soff; int act; int phy, phx; float4 sc, sh; };
 // (affine = false: the caller has scale / shift elsewhere and sc / sh stay 1 / 0 unread)

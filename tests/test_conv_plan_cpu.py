@@ -175,7 +175,8 @@ def plan_sweep():
                 for c_out in (48, 78, 96, 128):
                     for cins in ((64,), (1024, 512)):
                         awkward.append((kind, up * ho, up * wo, cins, c_out))
-    # a view of 2^30 elements and more: the halo and Winograd kernels address a view with 32-bit offsets
+    # source views of 2^31 bytes and more (the (48,) row: 3 GiB, the last row: exactly 2 GiB — both below 2^30 elements): the halo and Winograd kernels address a
+    # view with a 32-bit byte offset, so the gather kernel runs them and the 16-bit formats have no kernel (-1 / 0 / 0)
     for kind, h, w, cins, c_out in ((0, 4096, 4096, (64,), 64), (0, 4096, 4096, (64, 64), 78), (0, 4096, 4112, (64,), 128),
                                     (1, 4096, 4096, (64,), 64), (1, 4096, 4096, (64,), 128), (2, 4096, 4096, (32, 64), 64),
                                     (0, 4096, 4096, (48,), 64), (1, 512, 1024, (1024, 1024), 64)):
@@ -195,15 +196,17 @@ def test_plan_sweep_matches_the_recorded_table():
     """Algorithm, workspace size (hence the split depth), maskable tile count and packed-weight size of every call of the sweep
     equal the table recorded from the library BEFORE the planner was rewritten as a list of candidates (tests/golden/
     conv_plan_sweep.csv; `python tests/test_conv_plan_cpu.py` records it again from the library in the tree, or from the one
-    RNR_HIP_LIB names).  The sweep holds shapes where several candidates qualify (F(4x4, 3x3) over F(2x2, 3x3), the small direct
-    tiles over the 128 x 128 ones), so precedence is part of what is compared."""
+    RNR_HIP_LIB names).  38 rows were recorded again when the big-view bound became 2^31 bytes (it was 2^30 elements): the
+    eight shapes with a source view of 2 GiB and more, where the 2 and 3 GiB views moved to the gather kernel and the emulation
+    flags are refused (tests/test_conv_large_cpu.py holds the bound itself).  The sweep holds shapes where several candidates qualify
+    (F(4x4, 3x3) over F(2x2, 3x3), the small direct tiles over the 128 x 128 ones), so precedence is part of what is compared."""
     L = _lib.load()
     with open(SWEEP_FIXTURE) as f:
         lines = [ln.strip() for ln in f if ln.strip() and not ln.startswith('#')]
     recorded = [tuple(int(v) for v in ln.split(',')) for ln in lines]
     calls = plan_sweep()
     assert len(calls) > 3000 and [r[:8] for r in recorded] == calls
-    assert {r[8] for r in recorded} == {0, 1, 2, 3, 4} and any(r[10] > 0 for r in recorded)
+    assert {r[8] for r in recorded} == {-1, 0, 1, 2, 3, 4} and any(r[10] > 0 for r in recorded)       # -1: a 16-bit format on a big view
     wrong = [(r[:8], r[8:], plan_row(L, r[:8])) for r in recorded if plan_row(L, r[:8]) != r[8:]]
     assert not wrong, '%d of %d calls differ, first: %s' % (len(wrong), len(recorded), wrong[:5])
 
